@@ -8,8 +8,15 @@ contiguous share of its chunk-proofs, witness generation -> serialized proof, SR
 region criterion times in the reference: benches/benchmark_encrypt.rs:45-47).  value = blocks of the whole message(s) / timed region.
 The slices are issued through a 2-deep software pipeline (slice i+1 is submitted while slice i drains, as a streaming caller of the library would do), so
 the chip does not idle between steps; the timed region is still exactly the --steps slices between two barriers.
-Warm-up steps prove a separate short message.  Every timed proof is verified afterwards on the host (accept rate must be 100 %) together
+Warm-up steps have the shape of the timed steps (the same slices through the same pipeline, over a separate message of the same length; the first covers
+every prover context), so a warm-up step costs about what a timed step does.  Every timed proof is verified afterwards on the host (accept rate must be 100 %) together
 with the reference's negative case (a wrong ciphertext must be rejected).
+The timed proofs draw their prover randomness from one fixed 32-byte job seed (proof i: the job-global chunk index i, zkaes_encrypt_chunked_seeded_at), so that
+the same arguments give the same proof bytes on every run and every build: `--dump-outputs DIR` writes the proofs of the last timed step there.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, verification, the result line.  `--full` adds everything
+measured beside it: the per-box integer-rate calibration, clock / power telemetry of the timed region, the one-context probe and the library's op
+lists, the roofline and SRS reports, the `alt` and `latency_ms` legs, the `big` leg (child process) and the CPU-oracle baseline.
 
 modes (all one process per GPU, torch.distributed over RCCL):
   headline (default at 1 GPU)   every rank proves its own --blocks message (default 4096)    -> "scaling": "weak", no data-path collective
@@ -20,6 +27,7 @@ modes (all one process per GPU, torch.distributed over RCCL):
   batch                         --proofs independent single-block proofs on one SRS (configs[4]), sharded the same way -> "scaling": "strong"
 
     python bench.py --gpus 1 --steps 4 --warmup 1
+    python bench.py --gpus 1 --steps 4 --warmup 1 --full --dump-outputs bench_outputs/
     python bench.py --gpus 8                      # starts 8 ranks itself (re-executes under torch.distributed.run, rank r on GPU r)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...   # what the driver does
 """
@@ -110,6 +118,26 @@ class _stdout_to_stderr:
         return False
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, proofs, indices):
+    """--dump-outputs: the proofs of one timed step as DIR/proofs.npy (float32 [n, longest proof]: byte values 0..255, -1 past the end of a shorter proof) and
+    DIR/proof_index.npy (float64: the job-global chunk index of each row).  Beyond 64 MB in all, a fixed seeded sample of the rows is written."""
+    import numpy as np
+    assert len(proofs) == len(indices), (len(proofs), len(indices))
+    width = max((len(p) for p in proofs), default=0)
+    rows = np.arange(len(proofs))
+    max_rows = DUMP_LIMIT_BYTES // (4 * max(width, 1) + 8)
+    if len(rows) > max_rows:
+        rows = np.sort(np.random.RandomState(0x5EED).choice(len(rows), max_rows, replace=False))
+    arr = np.full((len(rows), width), -1.0, dtype=np.float32)
+    for j, i in enumerate(rows):
+        arr[j, :len(proofs[i])] = np.frombuffer(proofs[i], dtype=np.uint8)
+    np.save(os.path.join(dirname, "proofs.npy"), arr)
+    np.save(os.path.join(dirname, "proof_index.npy"), np.asarray(indices, dtype=np.float64)[rows])
+
+
 def even_slices(lo, hi, parts):
     """`parts` contiguous shares of [lo, hi), sizes differing by at most one"""
     return [tuple(lo + x for x in sharding.split_chunks(hi - lo, i, parts)) for i in range(parts)]
@@ -141,6 +169,9 @@ def build_parser():
     ap.add_argument("--big-only", action="store_true", help=argparse.SUPPRESS)       # the child process of the big leg
     ap.add_argument("--calibrate-s", type=float, default=0.5, help="seconds of the per-box integer-rate calibration before and after the timed region (0 = off)")
     ap.add_argument("--cpu-small-samples", type=int, default=0, help="CPU-oracle samples of a one-block chunk-proof (~17 s each + 20 s of setup; off by default: the run stays under 400 s)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (calibration, telemetry, one-context probe, roofline, SRS report, alt / latency / big "
+                                                        "legs, CPU baseline); the options above that tune those legs take effect only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the proofs of the last timed step to DIR/*.npy (float32 byte values; rank 0)")
     return ap
 
 
@@ -249,6 +280,11 @@ def run(args, api, dist_env=None):
         key = synthetic(16, 0x5EED)
         msg = synthetic(16 * total_blocks, 0x5EED + 1)
         keys16 = synthetic(16 * total_blocks, 0x5EED + 2) if mode == "batch" else None   # batch: one key per proof
+    # prover randomness of the timed proofs: one seed per job (headline: every rank its own job), proof i of the job at index i -- reproducible, and no two proofs of
+    # a job share blinding factors
+    job_seed = synthetic(32, 0x5EED + 3 + (rank if mode == "headline" else 0))
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)          # (a bad path fails here, before any GPU work)
     contexts = max(1, args.contexts)
     t_setup = time.perf_counter()
     chunk_bytes = 16 * chunk
@@ -277,15 +313,16 @@ def run(args, api, dist_env=None):
         if have_cuda:
             torch.cuda.synchronize()
 
-    def prove_range(a, b, source=None, source_keys=None):
-        """chunk-proofs [a, b) of this job -> list of proof bytes (the remainder chunk, if inside the range, is proven alongside on its own key)"""
+    def prove_range(a, b, source=None, source_keys=None, seed=job_seed):
+        """chunk-proofs [a, b) of this job -> list of proof bytes (the remainder chunk, if inside the range, is proven alongside on its own key).
+        source / source_keys: another message (and batch keys) of the job's length instead, without the remainder chunk; seed None = a fresh OS seed per call"""
         m = source if source is not None else msg
         out_full, out_rem = [], []
         fa, fb = a, min(b, n_full)
 
         def run_rem():
             api.set_device(device_ordinal)                    # HIP's current device is per thread (libzkaes re-selects the key's device itself, too)
-            out_rem.extend(pk_rem.encrypt_chunked(m[16 * chunk * n_full:16 * total_blocks], key))
+            out_rem.extend(pk_rem.encrypt_chunked(m[16 * chunk * n_full:16 * total_blocks], key, zk_seed=seed, first_proof_index=n_full))
         t = None
         if rem and b == n_chunks and b > a and source is None:
             t = threading.Thread(target=run_rem)
@@ -293,9 +330,9 @@ def run(args, api, dist_env=None):
         if fb > fa:
             if mode == "batch":
                 ks = source_keys if source_keys is not None else keys16
-                out_full = pk.encrypt_batch([m[16 * i:16 * i + 16] for i in range(fa, fb)], [ks[16 * i:16 * i + 16] for i in range(fa, fb)])
+                out_full = pk.encrypt_batch([m[16 * i:16 * i + 16] for i in range(fa, fb)], [ks[16 * i:16 * i + 16] for i in range(fa, fb)], zk_seed=seed, first_proof_index=fa)
             else:
-                out_full = pk.encrypt_chunked(m[chunk_bytes * fa:chunk_bytes * fb], key)
+                out_full = pk.encrypt_chunked(m[chunk_bytes * fa:chunk_bytes * fb], key, zk_seed=seed, first_proof_index=fa)
         if t:
             t.join()
         return out_full + out_rem
@@ -303,29 +340,35 @@ def run(args, api, dist_env=None):
     # ---- per-box calibration of the integer roof (the same kernel read 5.02 ... 5.54 ms per launch on five boxes): the isolated Fq product stream and the hot
     # loop over an L2-resident table, ~0.5 s, before anything is timed; repeated right after the timed region (a warm chip clocks lower)
     calibration = None
-    if rank == 0 and args.calibrate_s > 0 and hasattr(api, "int_rate_bench"):
+    if args.full and rank == 0 and args.calibrate_s > 0 and hasattr(api, "int_rate_bench"):
         try:
             calibration = {"before": api.int_rate_bench(args.calibrate_s)}
         except Exception as e:                                      # noqa: BLE001 -- the bench line says so instead of dying on a diagnostic
             calibration = {"error": str(e)[:200]}
 
-    # ---- warm-up on a separate short message: `contexts` chunk-proofs per step (allocates every context's workspace outside the timed region)
+    # ---- warm-up steps shaped like the timed ones: warm-up step j proves the chunk range of timed step j (mod --steps) of a separate message of the job's length,
+    # through the same pipeline; the first covers at least `contexts` chunk-proofs (allocates every context's workspace outside the timed region)
+    slices = even_slices(lo, hi, args.steps)
     warm_n = min(contexts, max(1, n_full))
-    warm_msg = synthetic(chunk_bytes * warm_n, 0x5EED + 7777 + rank)
-    warm_keys = synthetic(16 * warm_n, 0x5EED + 7778)
-    for _ in range(args.warmup):
-        if mode == "batch":
-            pk.encrypt_batch([warm_msg[16 * i:16 * i + 16] for i in range(warm_n)], [warm_keys[16 * i:16 * i + 16] for i in range(warm_n)])
-        else:
-            pk.encrypt_chunked(warm_msg, key)
+    warm_msg = synthetic(16 * total_blocks, 0x5EED + 7777 + rank)
+    warm_keys = synthetic(16 * total_blocks, 0x5EED + 7778) if mode == "batch" else None
+    warm_slices = [slices[j % len(slices)] for j in range(args.warmup)]
+    if warm_slices and min(warm_slices[0][1], n_full) - warm_slices[0][0] < warm_n:
+        warm_slices[0] = (0, warm_n)
+
+    def warm_slice(ab):
+        api.set_device(device_ordinal)
+        prove_range(*ab, source=warm_msg, source_keys=warm_keys, seed=None)
+    with ThreadPoolExecutor(max_workers=max(1, args.pipeline)) as ex:
+        list(ex.map(warm_slice, warm_slices))
     if need_rem and args.warmup > 0:
         pk_rem.encrypt_chunked(synthetic(16 * rem, 0x5EED + 7779), key)
 
-    slices = even_slices(lo, hi, args.steps)
     api.msm_stats(reset=True)
     phase = dict(witness_ms=0.0, round1_ms=0.0, round2_ms=0.0, round3_ms=0.0, open_ms=0.0, total_ms=0.0)
     proofs = []
-    telemetry = gpu_telemetry.Sampler(device_ordinal, 0.5) if rank == 0 else None
+    last_step = []                                                           # the proofs of the last timed step (--dump-outputs)
+    telemetry = gpu_telemetry.Sampler(device_ordinal, 0.5) if (args.full and rank == 0) else None
     barrier()
     if telemetry:
         telemetry.__enter__()
@@ -338,6 +381,7 @@ def run(args, api, dist_env=None):
     with ThreadPoolExecutor(max_workers=max(1, args.pipeline)) as ex:        # slice i+1 starts while slice i drains: both queue on the same prover contexts
         for r, t in ex.map(timed_slice, slices):
             proofs.extend(r)
+            last_step = r
             if t:
                 for k, v in t.items():
                     phase[k] += v
@@ -355,7 +399,7 @@ def run(args, api, dist_env=None):
         except Exception as e:                                      # noqa: BLE001
             calibration["after_error"] = str(e)[:200]
     mem_after_timed = None
-    if rank == 0 and hasattr(api, "mem_info"):
+    if args.full and rank == 0 and hasattr(api, "mem_info"):
         try:
             f_, t_ = api.mem_info()
             mem_after_timed = t_ - f_                           # device bytes in use right after the timed region: the SRS + this rank's keys and prover contexts
@@ -364,7 +408,7 @@ def run(args, api, dist_env=None):
 
     # ---- un-overlapped kernel durations: a few chunk-proofs one at a time (outside the timed region; cross-check for the rocprof one-context profile)
     serial = oplists = None
-    if args.serial_probe > 0 and rank == 0 and pk is not None and mode != "batch":
+    if args.full and args.serial_probe > 0 and rank == 0 and pk is not None and mode != "batch":
         pk.set_contexts(1)
         api.msm_stats(reset=True)
         ts = time.perf_counter()
@@ -390,7 +434,7 @@ def run(args, api, dist_env=None):
     #   latency_ms ONE encrypt() per message size, keys resident: the reference's own criterion shape (benches/benchmark_encrypt.rs:45-47)
     alt = latency = None
     extra_keys = []                                             # every further proving key of the two legs below (released before the big leg)
-    if world == 1 and mode == "headline" and rank == 0 and (args.alt_proofs > 0 or args.latency_samples > 0):
+    if args.full and world == 1 and mode == "headline" and rank == 0 and (args.alt_proofs > 0 or args.latency_samples > 0):
         small_keys = {}
 
         def key_for(nbytes):
@@ -479,95 +523,8 @@ def run(args, api, dist_env=None):
 
     out = None
     if rank == 0:
-        srs_report = None
-        if hasattr(pk or pk_rem, "srs_info"):
-            si = (pk or pk_rem).srs_info()
-            srs_report = {"universal_srs_bytes": si["bytes"], "copies": si["copies"], "points_per_copy": si["points_per_copy"], "keys_sharing_now": si["keys_sharing"],
-                          "first_key_srs_build_s": round(si["srs_build_s"], 2), "lagrange_bytes": si["lagrange_bytes"],
-                          "note": "ONE universal SRS (powers_of_g[0..=max_degree] + 12 window-table copies) per process and device, shared by every key (src/lib.rs:139-141); "
-                                  "key_setup_s = wall seconds of synthesize_keys per key, in creation order -- the second key only indexes its circuit"}
-            srs_report["device_bytes_in_use_after_timed_region"] = mem_after_timed
         job_blocks = total_blocks * (world if mode == "headline" else 1)
         value = job_blocks / elapsed
-        # roofline of the dominant kernel (MSM bucket accumulation, kernels_msm.hip k_accumulate): algorithmic bytes per launch =
-        # 128 B per point (96 B affine base + 32 B scalar) x points in the launch, divided by the kernel's CHIP time per launch.
-        # HIP events on the kernel's own stream bracket every launch of the timed region, but 16 prover contexts overlap their launches (launch_overlap =
-        # sum of in-situ durations / wall ~ 1.9), so an in-situ duration is stretched by whatever shares the chip with it and summing them counts the chip
-        # twice (round 2's line did that).  Chip time = the un-overlapped duration: the one-context probe right after the timed region (same key, same
-        # kernel, same launch shapes; this is what the one-context rocprof summary under profiles/ must agree with).  Self-check: launches per step x chip
-        # time per launch must fit into a step.
-        acc_ms, pts, launches = stats["accumulate_ms"], stats["points"], stats["launches"]
-        in_situ_ms = acc_ms / max(launches, 1)
-        overlap = acc_ms / (1e3 * elapsed) if elapsed > 0 else 0.0
-        if serial:
-            chip_ms, bytes_per_launch, chip_src = serial["avg_launch_ms"], serial["algorithmic_bytes_per_launch"], "one_context_probe (un-overlapped HIP-event duration, %d launches)" % serial["launches"]
-            pairs_per_launch = serial["pairs_per_launch"]
-        else:
-            chip_ms, bytes_per_launch = in_situ_ms / max(1.0, overlap), 128.0 * pts / max(launches, 1)
-            chip_src = "in-situ duration / launch_overlap (no one-context probe in this mode)"
-            pairs_per_launch = stats["pairs"] / max(launches, 1)
-        achieved = (bytes_per_launch / 1e9) / (chip_ms / 1e3) if chip_ms > 0 else 0.0
-        kernel_ms_per_step = launches / max(args.steps, 1) * chip_ms
-        traffic = traffic_src = None
-        for name in ("r06_pmc_k_accumulate_tables.json", "r05_pmc_k_accumulate_tables.json", "r04_pmc_k_accumulate_tables.json", "r03_pmc_k_accumulate_tables.json", "r02_pmc_k_accumulate_tables.json"):
-            try:
-                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-                traffic = round(pmc["hbm_bytes_per_point_window"] * pairs_per_launch)
-                traffic_src = ("separate PMC run of the isolated kernel (profiles/%s, measured at commit %s: rocprofv3 --pmc bytes per (point, window) gather), scaled by this run's pairs per launch -- "
-                               "not counters of this run" % (name, pmc.get("measured_at_commit", "unrecorded (rounds 2-5 did not stamp their PMC files)")))
-                break
-            except Exception:
-                pass
-        try:
-            copy_gbs = round(api.stream_copy_bench(1 << 30, 20), 1)
-        except Exception:
-            copy_gbs = None
-        # ---- whole-proof algorithmic bytes: bytes = W + S + T + M from the library's ACTUAL op lists of one chunk-proof (zkaes_pk_op_lists), not a literal:
-        #   W = 16 c + 16 + 32 V (message + key in, z written once);  S = 36 (nnzA + nnzB) + 36 (nnzA + nnzB + nnzC) + 32 V + 64 N (the two SpMVs + round 2's t pass);
-        #   T = sum over transforms of 64 n_i (one read + one write);  M = sum over MSMs of 128 m_j (96 B affine base + 32 B scalar, each read once)
-        proof_roof = None
-        if oplists:
-            V, N, (na, nb_, nc) = oplists["variables"], oplists["constraints"], oplists["nnz"]
-            ntt_sizes = {}
-            for n_i, cnt in oplists["ntt"]:
-                ntt_sizes[n_i] = ntt_sizes.get(n_i, 0) + cnt
-            msm_by_kind = {}
-            for m_j, kind in oplists["msm"]:
-                msm_by_kind.setdefault(kind, []).append(m_j)
-            Wb = 16 * oplists["blocks"] + 16 + 32 * V
-            Sb = 36 * (na + nb_) + 36 * (na + nb_ + nc) + 32 * V + 64 * N
-            Tb = sum(64 * n_i * cnt for n_i, cnt in ntt_sizes.items())
-            Mb = sum(128 * m_j for ms_ in msm_by_kind.values() for m_j in ms_)
-            total_b = Wb + Sb + Tb + Mb
-            proofs_per_s = (n_chunks * (world if mode == "headline" else 1)) / elapsed
-            # (the remainder chunk-proof, if any, is counted at the full chunk's bytes: same |H|, |K|, same launches)
-            proof_roof = {"W": Wb, "S": Sb, "T": Tb, "M": Mb, "bytes": total_b, "unit": "B per %d-block chunk-proof" % oplists["blocks"],
-                          "ntt_list": {"transforms_by_size": {str(k_): v_ for k_, v_ in sorted(ntt_sizes.items())}, "launches": len(oplists["ntt"]),
-                                       "transforms": sum(ntt_sizes.values())},
-                          "msm_list": {kind: {"count": len(v_), "points": sum(v_), "sizes": sorted(v_, reverse=True)} for kind, v_ in sorted(msm_by_kind.items())},
-                          "k_accumulate_launches_per_proof": len(msm_by_kind.get("buckets", [])) + len(msm_by_kind.get("second_bases", [])),
-                          "path": oplists["path"], "h": oplists["h"], "k": oplists["k"],
-                          "proofs_per_s": round(proofs_per_s / max(world, 1), 3), "achieved_GBs": round(total_b * proofs_per_s / max(world, 1) / 1e9, 2),
-                          "frac": round(total_b * proofs_per_s / max(world, 1) / 1e9 / HBM_PEAK_GBS, 6),
-                          "source": "zkaes_pk_op_lists: one chunk-proof proven with the library's op recorder open (every ntt / msm launch appends its size); per GPU",
-                          "not_counted": "the <= 3-term hiding MSMs and blinding products (host comb tables), Fiat-Shamir, the streaming polynomial kernels between the transforms"}
-        mads = MADS_PER_ADD * stats["pairs"] / 1e12
-        mads_per_launch = MADS_PER_ADD * pairs_per_launch / 1e12
-        # the integer roof, calibrated on THIS box (zkaes_int_rate_bench right after the timed region, chip warm; `before` = cold, ahead of the warm-up)
-        PEAK_REF = 28.1          # T v_mad_u64_u32/s: round 3's measurement on one box (tools/ubench/rates.hip), what rounds 3-5 divided by
-        cal = (calibration or {}).get("after") or (calibration or {}).get("before")
-        peak_box = round(cal["mad_per_s"] / 1e12, 2) if cal else None
-        peak = peak_box or PEAK_REF
-        mad_rate = mads_per_launch / (chip_ms / 1e3) if chip_ms > 0 else 0.0
-        add_rate = pairs_per_launch / (chip_ms / 1e3) if chip_ms > 0 else 0.0
-        hot_loop = None
-        if cal:
-            hot_loop = {"additions_per_s": round(add_rate / 1e9, 3), "additions_per_s_gathers_from_L2_this_box": round(cal["hot_loop_l2_additions_per_s"] / 1e9, 3), "unit": "G bucket additions/s",
-                        "frac": round(add_rate / cal["hot_loop_l2_additions_per_s"], 4), "shader_cycles_per_addition_per_simd": round(cal["hot_loop_cycles_per_addition_per_wave"] / 3.0),
-                        "sclk_mhz_of_the_l2_resident_loop": round(cal["hot_loop_l2_sclk_mhz"]),
-                        "note": "k_accumulate's own loop (te_madd_hot, same launch shape) over a table that stays in L2, timed on this box after the timed region: what the kernel would do if its gathers were free. "
-                                "The loop costs the same ~13,380 shader cycles per addition per SIMD either way (3,349 VALU instructions x 4 cycles = 13,396: the SIMD issues back to back at three waves, "
-                                "profiles/r06_accumulate_4waves.md); the gap to frac 1.0 is shader clock the chip gives back while ~1.9 TB/s of random 192-byte gathers are live, plus uneven bucket sizes"}
         workload = {
             "headline": "%d-block (%d B) ECB message per GPU as %d chunk-proofs of %d block(s)%s, sliced over the %d timed steps" % (total_blocks, 16 * total_blocks, n_full, chunk, (" + 1 of %d" % rem) if rem else "", args.steps),
             "strong": "ONE %d-block (%d B) ECB message%s as %d chunk-proofs of %d block(s)%s, chunk ranges sharded over %d rank(s), proofs all-gathered, rank 0 verifies all" % (
@@ -586,34 +543,125 @@ def run(args, api, dist_env=None):
                        "parallelism": "independent chunk-proofs per rank, no data-path collective" if mode == "headline" else "chunk range per rank + one all-gather of proof bytes",
                        "circuit_model": CIRCUIT_MODEL_NOTE},
             "proofs_verified": "%d/%d" % (acc_sum, tot_sum), "wrong_ciphertext_rejected": bool(neg_sum == world),
-            "alt": alt, "latency_ms": latency,
-            "setup_s": round(setup_s, 2), "key_setup_s": key_setup_s, "srs": srs_report, "cpu_affinity": affinity, "cpu_affinity_by_rank": affinity_by_rank,
+            "setup_s": round(setup_s, 2), "key_setup_s": key_setup_s, "cpu_affinity": affinity, "cpu_affinity_by_rank": affinity_by_rank,
             "phase_ms_last_proof_avg": {k: round(v / args.steps, 2) for k, v in phase.items()},
-            "telemetry": dict(telemetry.summary(), window="the timed region, sampled from a side thread (tools/gpu_telemetry.py)") if telemetry else None,
-            "roofline": {"bound": "hbm", "kernel": "k_accumulate (Pippenger bucket accumulation)", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
-                         "peak_measured_stream_copy": copy_gbs,
-                         "avg_launch_ms": round(chip_ms, 4), "avg_launch_ms_source": chip_src, "algorithmic_bytes_per_launch": round(bytes_per_launch),
-                         "launches": launches, "kernel_ms_per_step": round(kernel_ms_per_step, 1), "kernel_share_of_step": round(kernel_ms_per_step / (1e3 * elapsed / args.steps), 3) if elapsed > 0 else None,
-                         "avg_launch_ms_in_situ": round(in_situ_ms, 4), "launch_overlap": round(overlap, 3),
-                         "one_context_probe": serial, "proof": proof_roof,
-                         "int_multiplier": {"unit": "T v_mad_u64_u32/s", "achieved": round(mad_rate, 2), "peak": peak, "peak_this_box": peak_box, "peak_reference_round3_box": PEAK_REF,
-                                            "frac": round(mad_rate / peak, 4), "frac_vs_round3_reference_peak": round(mad_rate / PEAK_REF, 4), "frac_of_wall": round(mads / elapsed / peak, 4),
-                                            "calibration": calibration, "hot_loop": hot_loop,
-                                            "note": "the kernel's real roof: 2649 v_mad_u64_u32 per bucket addition (7 Fq products x 378 on the curve's twisted Edwards model; round 2's XYZZ mixed add needed 3416), one addition per "
-                                                    "(point, window) pair; peak = rate of the same Fq product stream in isolation MEASURED ON THIS BOX in this run (zkaes_int_rate_bench, four waves per SIMD; rounds 3-5 divided by one "
-                                                    "box's 28.1). frac uses the same chip time per launch as roofline.frac; frac_of_wall = all multiplies of the timed region / whole timed region."},
-                         "note": "integer-ALU bound (7 Fq limb products with their Montgomery reductions = 2649 v_mad_u64_u32 per bucket addition); HBM fraction of O(1%) is the expected regime (BASELINE.md §3); traffic is ~23x the "
-                                 "algorithmic bytes by construction: every one of the 13 windows gathers its own 192-byte (64-byte aligned) precomputed copy of the base + a 4-byte index (2,548 B per point against 128 B), "
-                                 "~1.7 TB/s, not the limiter"},
         }
-        if kernel_ms_per_step > 1e3 * elapsed / args.steps * 1.02:
-            out["roofline"]["inconsistent"] = "kernel chip time per step exceeds the step itself"
         if acc_sum != tot_sum or neg_sum != world or tot_sum != out["config"]["proofs_total"]:
             out["error"] = "verification failure"
-        if (alt and alt["proofs_verified"] != "%d/%d" % (alt["proofs"], alt["proofs"])) or (latency and not latency["verified"]):
-            out["error"] = "verification failure (alt / latency leg)"
-        if world == 1 and mode == "headline" and args.big_chunk > 0 and not use_dist and have_cuda:
+        if args.full:
+            srs_report = None
+            if hasattr(pk or pk_rem, "srs_info"):
+                si = (pk or pk_rem).srs_info()
+                srs_report = {"universal_srs_bytes": si["bytes"], "copies": si["copies"], "points_per_copy": si["points_per_copy"], "keys_sharing_now": si["keys_sharing"],
+                              "first_key_srs_build_s": round(si["srs_build_s"], 2), "lagrange_bytes": si["lagrange_bytes"],
+                              "note": "ONE universal SRS (powers_of_g[0..=max_degree] + 12 window-table copies) per process and device, shared by every key (src/lib.rs:139-141); "
+                                      "key_setup_s = wall seconds of synthesize_keys per key, in creation order -- the second key only indexes its circuit"}
+                srs_report["device_bytes_in_use_after_timed_region"] = mem_after_timed
+            # roofline of the dominant kernel (MSM bucket accumulation, kernels_msm.hip k_accumulate): algorithmic bytes per launch =
+            # 128 B per point (96 B affine base + 32 B scalar) x points in the launch, divided by the kernel's CHIP time per launch.
+            # HIP events on the kernel's own stream bracket every launch of the timed region, but 16 prover contexts overlap their launches (launch_overlap =
+            # sum of in-situ durations / wall ~ 1.9), so an in-situ duration is stretched by whatever shares the chip with it and summing them counts the chip
+            # twice (round 2's line did that).  Chip time = the un-overlapped duration: the one-context probe right after the timed region (same key, same
+            # kernel, same launch shapes; this is what the one-context rocprof summary under profiles/ must agree with).  Self-check: launches per step x chip
+            # time per launch must fit into a step.
+            acc_ms, pts, launches = stats["accumulate_ms"], stats["points"], stats["launches"]
+            in_situ_ms = acc_ms / max(launches, 1)
+            overlap = acc_ms / (1e3 * elapsed) if elapsed > 0 else 0.0
+            if serial:
+                chip_ms, bytes_per_launch, chip_src = serial["avg_launch_ms"], serial["algorithmic_bytes_per_launch"], "one_context_probe (un-overlapped HIP-event duration, %d launches)" % serial["launches"]
+                pairs_per_launch = serial["pairs_per_launch"]
+            else:
+                chip_ms, bytes_per_launch = in_situ_ms / max(1.0, overlap), 128.0 * pts / max(launches, 1)
+                chip_src = "in-situ duration / launch_overlap (no one-context probe in this mode)"
+                pairs_per_launch = stats["pairs"] / max(launches, 1)
+            achieved = (bytes_per_launch / 1e9) / (chip_ms / 1e3) if chip_ms > 0 else 0.0
+            kernel_ms_per_step = launches / max(args.steps, 1) * chip_ms
+            traffic = traffic_src = None
+            for name in ("r06_pmc_k_accumulate_tables.json", "r05_pmc_k_accumulate_tables.json", "r04_pmc_k_accumulate_tables.json", "r03_pmc_k_accumulate_tables.json", "r02_pmc_k_accumulate_tables.json"):
+                try:
+                    pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+                    traffic = round(pmc["hbm_bytes_per_point_window"] * pairs_per_launch)
+                    traffic_src = ("separate PMC run of the isolated kernel (profiles/%s, measured at commit %s: rocprofv3 --pmc bytes per (point, window) gather), scaled by this run's pairs per launch -- "
+                                   "not counters of this run" % (name, pmc.get("measured_at_commit", "unrecorded (rounds 2-5 did not stamp their PMC files)")))
+                    break
+                except Exception:
+                    pass
+            try:
+                copy_gbs = round(api.stream_copy_bench(1 << 30, 20), 1)
+            except Exception:
+                copy_gbs = None
+            # ---- whole-proof algorithmic bytes: bytes = W + S + T + M from the library's ACTUAL op lists of one chunk-proof (zkaes_pk_op_lists), not a literal:
+            #   W = 16 c + 16 + 32 V (message + key in, z written once);  S = 36 (nnzA + nnzB) + 36 (nnzA + nnzB + nnzC) + 32 V + 64 N (the two SpMVs + round 2's t pass);
+            #   T = sum over transforms of 64 n_i (one read + one write);  M = sum over MSMs of 128 m_j (96 B affine base + 32 B scalar, each read once)
+            proof_roof = None
+            if oplists:
+                V, N, (na, nb_, nc) = oplists["variables"], oplists["constraints"], oplists["nnz"]
+                ntt_sizes = {}
+                for n_i, cnt in oplists["ntt"]:
+                    ntt_sizes[n_i] = ntt_sizes.get(n_i, 0) + cnt
+                msm_by_kind = {}
+                for m_j, kind in oplists["msm"]:
+                    msm_by_kind.setdefault(kind, []).append(m_j)
+                Wb = 16 * oplists["blocks"] + 16 + 32 * V
+                Sb = 36 * (na + nb_) + 36 * (na + nb_ + nc) + 32 * V + 64 * N
+                Tb = sum(64 * n_i * cnt for n_i, cnt in ntt_sizes.items())
+                Mb = sum(128 * m_j for ms_ in msm_by_kind.values() for m_j in ms_)
+                total_b = Wb + Sb + Tb + Mb
+                proofs_per_s = (n_chunks * (world if mode == "headline" else 1)) / elapsed
+                # (the remainder chunk-proof, if any, is counted at the full chunk's bytes: same |H|, |K|, same launches)
+                proof_roof = {"W": Wb, "S": Sb, "T": Tb, "M": Mb, "bytes": total_b, "unit": "B per %d-block chunk-proof" % oplists["blocks"],
+                              "ntt_list": {"transforms_by_size": {str(k_): v_ for k_, v_ in sorted(ntt_sizes.items())}, "launches": len(oplists["ntt"]),
+                                           "transforms": sum(ntt_sizes.values())},
+                              "msm_list": {kind: {"count": len(v_), "points": sum(v_), "sizes": sorted(v_, reverse=True)} for kind, v_ in sorted(msm_by_kind.items())},
+                              "k_accumulate_launches_per_proof": len(msm_by_kind.get("buckets", [])) + len(msm_by_kind.get("second_bases", [])),
+                              "path": oplists["path"], "h": oplists["h"], "k": oplists["k"],
+                              "proofs_per_s": round(proofs_per_s / max(world, 1), 3), "achieved_GBs": round(total_b * proofs_per_s / max(world, 1) / 1e9, 2),
+                              "frac": round(total_b * proofs_per_s / max(world, 1) / 1e9 / HBM_PEAK_GBS, 6),
+                              "source": "zkaes_pk_op_lists: one chunk-proof proven with the library's op recorder open (every ntt / msm launch appends its size); per GPU",
+                              "not_counted": "the <= 3-term hiding MSMs and blinding products (host comb tables), Fiat-Shamir, the streaming polynomial kernels between the transforms"}
+            mads = MADS_PER_ADD * stats["pairs"] / 1e12
+            mads_per_launch = MADS_PER_ADD * pairs_per_launch / 1e12
+            # the integer roof, calibrated on THIS box (zkaes_int_rate_bench right after the timed region, chip warm; `before` = cold, ahead of the warm-up)
+            PEAK_REF = 28.1          # T v_mad_u64_u32/s: round 3's measurement on one box (tools/ubench/rates.hip), what rounds 3-5 divided by
+            cal = (calibration or {}).get("after") or (calibration or {}).get("before")
+            peak_box = round(cal["mad_per_s"] / 1e12, 2) if cal else None
+            peak = peak_box or PEAK_REF
+            mad_rate = mads_per_launch / (chip_ms / 1e3) if chip_ms > 0 else 0.0
+            add_rate = pairs_per_launch / (chip_ms / 1e3) if chip_ms > 0 else 0.0
+            hot_loop = None
+            if cal:
+                hot_loop = {"additions_per_s": round(add_rate / 1e9, 3), "additions_per_s_gathers_from_L2_this_box": round(cal["hot_loop_l2_additions_per_s"] / 1e9, 3), "unit": "G bucket additions/s",
+                            "frac": round(add_rate / cal["hot_loop_l2_additions_per_s"], 4), "shader_cycles_per_addition_per_simd": round(cal["hot_loop_cycles_per_addition_per_wave"] / 3.0),
+                            "sclk_mhz_of_the_l2_resident_loop": round(cal["hot_loop_l2_sclk_mhz"]),
+                            "note": "k_accumulate's own loop (te_madd_hot, same launch shape) over a table that stays in L2, timed on this box after the timed region: what the kernel would do if its gathers were free. "
+                                    "The loop costs the same ~13,380 shader cycles per addition per SIMD either way (3,349 VALU instructions x 4 cycles = 13,396: the SIMD issues back to back at three waves, "
+                                    "profiles/r06_accumulate_4waves.md); the gap to frac 1.0 is shader clock the chip gives back while ~1.9 TB/s of random 192-byte gathers are live, plus uneven bucket sizes"}
+            out.update({
+                "alt": alt, "latency_ms": latency,
+                "srs": srs_report,
+                "telemetry": dict(telemetry.summary(), window="the timed region, sampled from a side thread (tools/gpu_telemetry.py)") if telemetry else None,
+                "roofline": {"bound": "hbm", "kernel": "k_accumulate (Pippenger bucket accumulation)", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
+                             "peak_measured_stream_copy": copy_gbs,
+                             "avg_launch_ms": round(chip_ms, 4), "avg_launch_ms_source": chip_src, "algorithmic_bytes_per_launch": round(bytes_per_launch),
+                             "launches": launches, "kernel_ms_per_step": round(kernel_ms_per_step, 1), "kernel_share_of_step": round(kernel_ms_per_step / (1e3 * elapsed / args.steps), 3) if elapsed > 0 else None,
+                             "avg_launch_ms_in_situ": round(in_situ_ms, 4), "launch_overlap": round(overlap, 3),
+                             "one_context_probe": serial, "proof": proof_roof,
+                             "int_multiplier": {"unit": "T v_mad_u64_u32/s", "achieved": round(mad_rate, 2), "peak": peak, "peak_this_box": peak_box, "peak_reference_round3_box": PEAK_REF,
+                                                "frac": round(mad_rate / peak, 4), "frac_vs_round3_reference_peak": round(mad_rate / PEAK_REF, 4), "frac_of_wall": round(mads / elapsed / peak, 4),
+                                                "calibration": calibration, "hot_loop": hot_loop,
+                                                "note": "the kernel's real roof: 2649 v_mad_u64_u32 per bucket addition (7 Fq products x 378 on the curve's twisted Edwards model; round 2's XYZZ mixed add needed 3416), one addition per "
+                                                        "(point, window) pair; peak = rate of the same Fq product stream in isolation MEASURED ON THIS BOX in this run (zkaes_int_rate_bench, four waves per SIMD; rounds 3-5 divided by one "
+                                                        "box's 28.1). frac uses the same chip time per launch as roofline.frac; frac_of_wall = all multiplies of the timed region / whole timed region."},
+                             "note": "integer-ALU bound (7 Fq limb products with their Montgomery reductions = 2649 v_mad_u64_u32 per bucket addition); HBM fraction of O(1%) is the expected regime (BASELINE.md §3); traffic is ~23x the "
+                                     "algorithmic bytes by construction: every one of the 13 windows gathers its own 192-byte (64-byte aligned) precomputed copy of the base + a 4-byte index (2,548 B per point against 128 B), "
+                                     "~1.7 TB/s, not the limiter"},
+            })
+            if kernel_ms_per_step > 1e3 * elapsed / args.steps * 1.02:
+                out["roofline"]["inconsistent"] = "kernel chip time per step exceeds the step itself"
+            if (alt and alt["proofs_verified"] != "%d/%d" % (alt["proofs"], alt["proofs"])) or (latency and not latency["verified"]):
+                out["error"] = "verification failure (alt / latency leg)"
+        if args.full and world == 1 and mode == "headline" and args.big_chunk > 0 and not use_dist and have_cuda:
             # the big leg needs the device to itself (126 GB of tables for its own SRS): this process lets go of its keys first, the leg runs in a child process
             # (a failure there cannot take this line down) and comes back as one JSON object
             import subprocess
@@ -627,10 +675,12 @@ def run(args, api, dist_env=None):
                 out["big"] = json.loads(lines[-1]) if lines else {"error": "no output (rc %d): %s" % (r.returncode, (r.stderr or "")[-300:])}
             except Exception as e:                                  # noqa: BLE001
                 out["big"] = {"error": str(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(samples_small=args.cpu_small_samples, samples_chunk=args.cpu_chunk_samples, chunk_blocks=chunk if chunk > 1 else 6, budget_s=100.0 * max(1, args.cpu_chunk_samples))
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu_baseline"] = round(value / cb["value"], 2)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_step, list(range(*slices[-1])))      # (a step's proofs come back in chunk order, the remainder chunk last)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

@@ -71,7 +71,7 @@ def test_two_rank_report_reduction():
 # all-gathered, rank 0 verifies every one (BASELINE configs[3] / [4]); weak scaling = every rank its own message (configs[2])
 class _StubKey:
     def __init__(self, nbytes, log):
-        self.nbytes, self.log = nbytes, log
+        self.nbytes, self.log, self.seeds = nbytes, log, []
 
     def info(self):
         return {"raw_instance": 8 * self.nbytes + 1, "h": 1 << 20, "k": 1 << 22}
@@ -99,16 +99,18 @@ class _StubKey:
         import hashlib
         return (hashlib.sha256(bytes(ct)).digest() * 27)[:855]          # a "proof" is a digest of the ciphertext it attests
 
-    def encrypt_chunked(self, message, key):
+    def encrypt_chunked(self, message, key, zk_seed=None, first_proof_index=0):
         from oracle import zko
         n = self.nbytes
         assert len(message) % n == 0
         self.log.append(("chunked", n, len(message) // n))
+        self.seeds.append((zk_seed, first_proof_index))
         return [self.make(zko.aes_encrypt(message[i:i + n], key)) for i in range(0, len(message), n)]
 
-    def encrypt_batch(self, messages, keys):
+    def encrypt_batch(self, messages, keys, zk_seed=None, first_proof_index=0):
         from oracle import zko
         self.log.append(("batch", self.nbytes, len(messages)))
+        self.seeds.append((zk_seed, first_proof_index))
         return [self.make(zko.aes_encrypt(m, k)) for m, k in zip(messages, keys)]
 
 
@@ -116,7 +118,7 @@ class _StubApi:
     """stands in for aes_zero_knowledge_proof_circuit_amd.api (no GPU here): same calls bench.run makes, proofs are ciphertext digests"""
 
     def __init__(self):
-        self.log = []
+        self.log, self.keys = [], []
 
     def device_count(self):
         return 1
@@ -126,6 +128,7 @@ class _StubApi:
 
     def synthesize_keys(self, nbytes):
         k = _StubKey(nbytes, self.log)
+        self.keys.append(k)
         return k, k
 
     def msm_stats(self, reset=False):
@@ -168,7 +171,7 @@ def _run_bench(argv, world=2):
 
 
 def test_bench_strong_mode_two_ranks_gathers_and_verifies_every_proof():
-    out = _run_bench(["--gpus", "2", "--mode", "strong", "--blocks", "64", "--chunk", "6", "--steps", "2", "--warmup", "1", "--contexts", "3", "--no-cpu-baseline"])
+    out = _run_bench(["--gpus", "2", "--mode", "strong", "--blocks", "64", "--chunk", "6", "--steps", "2", "--warmup", "1", "--contexts", "3", "--no-cpu-baseline", "--full"])
     res, log0, printed = out[0]
     assert out[1][0] is None and out[1][2] == ""               # only rank 0 reports
     assert json.loads(printed)["value"] == res["value"]         # ONE JSON line
@@ -252,7 +255,7 @@ def test_bench_one_rank_reports_the_measured_alt_and_latency_legs():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         os.environ.pop(k, None)
     api = _StubApi()
-    argv = ["--blocks", "40", "--steps", "2", "--warmup", "1", "--contexts", "3", "--no-cpu-baseline", "--serial-probe", "0", "--alt-proofs", "5", "--latency-samples", "2"]
+    argv = ["--blocks", "40", "--steps", "2", "--warmup", "1", "--contexts", "3", "--no-cpu-baseline", "--serial-probe", "0", "--alt-proofs", "5", "--latency-samples", "2", "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         res = bench.run(bench.build_parser().parse_args(argv), api)
@@ -265,6 +268,57 @@ def test_bench_one_rank_reports_the_measured_alt_and_latency_legs():
     assert ("chunked", 64, 5) in api.log                                                                          # the timed alt call: five 4-block chunk-proofs
     src = open(bench.__file__).read()
     assert "blocks/s on this code" not in src                   # no measurement is quoted as a literal
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """without --full a one-rank run does the headline only: no calibration, probe, legs, roofline or CPU baseline.  The timed proofs draw from ONE job seed at
+    job-global chunk indices, and --dump-outputs writes the last timed step's proofs; a second run with the same arguments writes the same arrays"""
+    import contextlib
+    import io
+    import numpy as np
+    import bench
+    from oracle import zko
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        os.environ.pop(k, None)
+    dumps = []
+    for run_i in range(2):
+        api = _StubApi()
+        d = tmp_path / ("run%d" % run_i)
+        argv = ["--blocks", "40", "--steps", "3", "--warmup", "2", "--contexts", "3", "--dump-outputs", str(d)]
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            res = bench.run(bench.build_parser().parse_args(argv), api)
+        assert json.loads(buf.getvalue()) == res and "error" not in res and res["proofs_verified"] == "7/7"        # 6 chunks of 6 blocks + 1 of 4
+        assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["metric"] and res["unit"] == "blocks/s" and res["higher_is_better"] is True and res["dtype"]
+        assert not {"alt", "latency_ms", "roofline", "srs", "telemetry", "big", "cpu_baseline"} & set(res)
+        assert [e for e in api.log if e[0] in ("lone", "contexts")] == [("contexts", "key96", 3), ("contexts", "key64", 3)]      # no one-context probe, no latency leg
+        k96, k64 = api.keys
+        timed = [s_ for s_ in k96.seeds + k64.seeds if s_[0] is not None]
+        assert [i for _, i in timed] == [0, 3, 5, 6] and len({s_ for s_, _ in timed}) == 1 and len(timed[0][0]) == 32     # slices [0, 3) [3, 5) [5, 7)
+        # warm-up steps have the timed steps' shape (slices [0, 3) and [3, 5) of a separate message; the remainder key gets its own single proof), fresh OS seeds
+        assert sorted(i for s_, i in k96.seeds if s_ is None) == [0, 3] and [i for s_, i in k64.seeds if s_ is None] == [0]
+        assert sorted([e for e in api.log if e[0] == "chunked"][:3]) == [("chunked", 64, 1), ("chunked", 96, 2), ("chunked", 96, 3)]     # (two in flight)
+        proofs, index = np.load(d / "proofs.npy"), np.load(d / "proof_index.npy")
+        assert proofs.dtype == np.float32 and index.dtype == np.float64 and proofs.shape == (2, 855) and index.tolist() == [5.0, 6.0]
+        msg, key = bench.synthetic(16 * 40, 0x5EED + 1), bench.synthetic(16, 0x5EED)
+        want = [_StubKey.make(zko.aes_encrypt(msg[96 * 5:96 * 6], key)), _StubKey.make(zko.aes_encrypt(msg[96 * 6:], key))]
+        assert [bytes(r.astype(np.uint8)) for r in proofs] == want
+        dumps.append((proofs, index))
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))
+
+
+def test_bench_dump_pads_short_proofs_and_samples_beyond_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    proofs = [bytes([i]) * (10 - i % 2) for i in range(8)]
+    bench.dump_outputs(str(tmp_path), proofs, list(range(100, 108)))
+    got = np.load(tmp_path / "proofs.npy")
+    assert got.shape == (8, 10) and got[1, 9] == -1 and got[2, 9] == 2 and np.load(tmp_path / "proof_index.npy").tolist() == list(range(100, 108))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * (4 * 10 + 8))
+    bench.dump_outputs(str(tmp_path), proofs, list(range(100, 108)))
+    got, idx = np.load(tmp_path / "proofs.npy"), np.load(tmp_path / "proof_index.npy")
+    assert got.shape == (3, 10) and idx.tolist() == sorted(idx.tolist()) and all(got[j, 0] == idx[j] - 100 for j in range(3))
+    assert got.nbytes + idx.nbytes <= bench.DUMP_LIMIT_BYTES
 
 
 def test_bench_gpus_flag_launches_the_ranks_itself(monkeypatch):
@@ -528,7 +582,7 @@ def test_bench_two_ranks_real_prover_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--blocks", "100", "--steps", "2", "--warmup", "1", "--contexts", "4", "--no-cpu-baseline", "--alt-proofs", "0",
-           "--latency-samples", "0"]
+           "--latency-samples", "0", "--full"]
     t0 = time.perf_counter()
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     took = time.perf_counter() - t0
