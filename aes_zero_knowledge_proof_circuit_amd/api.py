@@ -334,6 +334,114 @@ def ntt_batch(field_id, vectors, cosets=None, lg_big=0, inverse=False):
     return [buf.raw[32 * n * i:32 * n * (i + 1)] for i in range(count)]
 
 
+# ---- kernel-level entry points for tests (include/zkaes.h): one call = one launch wrapper of the prover's polynomial layer; 32-byte Montgomery limbs in and out
+def _ptr_array(bufs):
+    """(array of const uint8_t *, array of size_t lengths in elements) for a list of byte strings; the list itself keeps the buffers alive"""
+    n = len(bufs)
+    return (C.c_char_p * n)(*[bytes(b) if len(b) else None for b in bufs]), (C.c_size_t * n)(*[len(b) // 32 for b in bufs])
+
+
+def poly_divide_by_vanishing(p, m, with_scratch=False, want_rem=True):
+    """(quotient, remainder or None) of p / (X^m - 1)"""
+    n = len(p) // 32
+    q = C.create_string_buffer(32 * max(n - m, 0) or 1)
+    rem = C.create_string_buffer(32 * m or 1) if want_rem else None
+    _check(lib().zkaes_poly_divide_by_vanishing(bytes(p), C.c_size_t(n), C.c_size_t(m), 1 if with_scratch else 0, q, rem))
+    return q.raw[:32 * (n - m)], (rem.raw[:32 * m] if want_rem else None)
+
+
+def poly_divide_by_linear(p, z):
+    n = len(p) // 32
+    q = C.create_string_buffer(32 * max(n - 1, 0) or 1)
+    _check(lib().zkaes_poly_divide_by_linear(bytes(p), C.c_size_t(n), bytes(z), q))
+    return q.raw[:32 * max(n - 1, 0)]
+
+
+def poly_eval_multi(polys, xs):
+    """[p(x) for p, x in zip(polys, xs)] as 32-byte strings; 1..8 polynomials"""
+    count = len(polys)
+    ptrs, lens = _ptr_array(polys)
+    out = C.create_string_buffer(32 * max(count, 1))
+    _check(lib().zkaes_poly_eval_multi(ptrs, lens, b"".join(bytes(x) for x in xs), count, out))
+    return [out.raw[32 * i:32 * i + 32] for i in range(count)]
+
+
+def batch_inverse(v, post=None, throughput_variant=False):
+    n = len(v) // 32
+    buf = C.create_string_buffer(bytes(v), max(len(v), 1))
+    _check(lib().zkaes_batch_inverse(buf, C.c_size_t(n), None if post is None else bytes(post), 1 if throughput_variant else 0))
+    return buf.raw[:32 * n]
+
+
+def poly_lincomb(polys, scalars, n):
+    count = len(polys)
+    ptrs, lens = _ptr_array(polys)
+    out = C.create_string_buffer(32 * n or 1)
+    _check(lib().zkaes_poly_lincomb(ptrs, lens, b"".join(bytes(x) for x in scalars), count, C.c_size_t(n), out))
+    return out.raw[:32 * n]
+
+
+def vanishing_quotient_evals(lg_n, gs, a, indices=None):
+    """one byte string per coset g in gs: the whole table (2^lg_n elements), or the values at `indices`"""
+    ncosets, per = len(gs), (1 << lg_n) if indices is None else len(indices)
+    out = C.create_string_buffer(32 * per * ncosets or 1)
+    idx = None if indices is None else (C.c_uint32 * max(per, 1))(*indices)
+    _check(lib().zkaes_vanishing_quotient_evals(int(lg_n), b"".join(bytes(g) for g in gs), ncosets, bytes(a), idx, C.c_size_t(0 if indices is None else per), out))
+    return [out.raw[32 * per * c:32 * per * (c + 1)] for c in range(ncosets)]
+
+
+def q1_coset_pointwise(r, za, zb, t, z, ca, cb, cz, eta_a, eta_b, eta_c):
+    n = len(r) // 32
+    out = C.create_string_buffer(32 * n or 1)
+    consts = b"".join(bytes(x) for x in (ca, cb, cz, eta_a, eta_b, eta_c))
+    _check(lib().zkaes_q1_coset_pointwise(bytes(r), bytes(za), bytes(zb), bytes(t), bytes(z), consts, C.c_size_t(n), out))
+    return out.raw[:32 * n]
+
+
+def h2_coset(row, col, va, vb, vc, rc, f, alpha, beta, alpha_beta, ea, eb, ec, vinv):
+    k = len(row) // 32
+    out = C.create_string_buffer(32 * k or 1)
+    arrays = (C.c_char_p * 7)(*[bytes(x) for x in (row, col, va, vb, vc, rc, f)])
+    consts = b"".join(bytes(x) for x in (alpha, beta, alpha_beta, ea, eb, ec, vinv))
+    _check(lib().zkaes_h2_coset(arrays, consts, C.c_size_t(k), out))
+    return out.raw[:32 * k]
+
+
+def q1_combine(q0, q1, q3, mask, inv2, inv2zeta):
+    """(h1: 2n elements, g1: n - 1 elements)"""
+    n = len(q0) // 32
+    h1, g1 = C.create_string_buffer(64 * n or 1), C.create_string_buffer(32 * max(n - 1, 0) or 1)
+    _check(lib().zkaes_q1_combine(bytes(q0), bytes(q1), bytes(q3), bytes(mask), bytes(inv2), bytes(inv2zeta), C.c_size_t(n), h1, g1))
+    return h1.raw[:64 * n], g1.raw[:32 * max(n - 1, 0)]
+
+
+def coset_scale(data, g, n):
+    out = C.create_string_buffer(32 * n or 1)
+    _check(lib().zkaes_coset_scale(bytes(data), C.c_size_t(len(data) // 32), bytes(g), C.c_size_t(n), out))
+    return out.raw[:32 * n]
+
+
+def z_poly_from_w(w, x_poly, n):
+    """w (X^m - 1) + x_poly with m = len(x_poly): n + 1 coefficients"""
+    out = C.create_string_buffer(32 * (n + 1))
+    _check(lib().zkaes_z_poly_from_w(bytes(w), C.c_size_t(len(w) // 32), bytes(x_poly), C.c_uint32(len(x_poly) // 32), C.c_size_t(n), out))
+    return out.raw
+
+
+def ntt_padded(field_id, data_mont_bytes, n, inverse=False, coset_c=0, lg_big=0):
+    """the transform of a short input that the first pass's gather pads with zeros to n elements"""
+    out = C.create_string_buffer(32 * n)
+    _check(lib().zkaes_ntt_padded(int(field_id), bytes(data_mont_bytes), C.c_size_t(len(data_mont_bytes) // 32), C.c_size_t(n), 1 if inverse else 0, int(coset_c), int(lg_big), out))
+    return out.raw
+
+
+def ntt_scaled(g, data_mont_bytes, n, inverse=False):
+    """BLS12-377: forward = the values on g D of the (zero-padded) coefficients, inverse = the coefficients from such values"""
+    out = C.create_string_buffer(32 * n)
+    _check(lib().zkaes_ntt_scaled(bytes(g), bytes(data_mont_bytes), C.c_size_t(len(data_mont_bytes) // 32), C.c_size_t(n), 1 if inverse else 0, out))
+    return out.raw
+
+
 def msm(curve_id, bases_bytes, scalars_bytes):
     n = len(scalars_bytes) // 32
     out = C.create_string_buffer(96)

@@ -210,6 +210,40 @@ template <class Curve> void run_g1_sum(const uint8_t *points_xy, const int *inf,
     *out_inf = r.is_inf() ? 1 : 0;
     memcpy(out_xy, r.x.l, 48); memcpy(out_xy + 48, r.y.l, 48);
 }
+
+// ---- the prover's polynomial kernels (kernels_poly.hip) and the NTT entry points the prover uses but zkaes_ntt does not reach, one launch wrapper per call: host byte
+// buffers of 32-byte Montgomery limbs in and out, so that a test can compare every multi-launch algorithm with a big-integer model at the block, chunk and level
+// boundaries of its constants (tests/test_gpu_poly.py).  Elements must be canonical (< r); they are not checked one by one.
+using PF = zk::gpu::F;
+PF load_f(const uint8_t *b, const char *who) {
+    if (!b) throw std::invalid_argument(std::string(who) + ": null field element");
+    PF x; memcpy(x.l, b, 32); return x;
+}
+void need(bool ok, const char *who, const char *what) { if (!ok) throw std::invalid_argument(std::string(who) + ": " + what); }
+constexpr size_t POLY_MAX = (size_t)1 << 28;        // elements per array a kernel-level call accepts (8 GB)
+// device copy of `count` host elements (at least one element is allocated, so that the pointer is valid for an empty array)
+DevPtr<PF> upload(const uint8_t *host, size_t count, zk::gpu::stream_t s) {
+    DevPtr<PF> d(count ? count : 1);
+    zk::gpu::h2d(d, host, count * sizeof(PF), s);
+    return d;
+}
+struct TableGuard {                                  // coset_power_table hands its table over as a raw pointer
+    void *p = nullptr;
+    ~TableGuard() { zk::gpu::dfree(p); }
+};
+template <class Fr> void run_ntt_padded(const uint8_t *in, size_t in_len, size_t n, int inverse, int coset_c, int lg_big, uint8_t *out) {
+    const int lg = exact_log2(n, "zkaes_ntt_padded");
+    need(in_len <= n, "zkaes_ntt_padded", "in_len must not exceed n");
+    need(out && (in || !in_len), "zkaes_ntt_padded", "null argument");
+    need(coset_c >= 0, "zkaes_ntt_padded", "coset index must not be negative");
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<Fr> a(in_len ? in_len : 1), b(n);
+    zk::gpu::h2d(a, in, in_len * sizeof(Fr), s);
+    if (coset_c) zk::gpu::ntt_coset<Fr>(b, a, in_len, lg, inverse != 0, coset_c, lg_big, s);
+    else zk::gpu::ntt<Fr>(b, a, in_len, lg, inverse != 0, s);
+    zk::gpu::d2h(out, b, n * sizeof(Fr), s);
+}
 }  // namespace
 
 extern "C" {
@@ -261,6 +295,198 @@ int zkaes_ntt_batch(int field_id, uint8_t *data, size_t n, int count, int invers
     return guardk([&] {
         if (field_id == 381) run_ntt_batch<zk::Fr381>(data, n, count, inverse, coset_c, lg_big); else if (field_id == 377) run_ntt_batch<zk::Fr377>(data, n, count, inverse, coset_c, lg_big);
         else throw std::invalid_argument("field_id must be 377 or 381");
+    });
+}
+// ---- kernel-level entry points for tests (include/zkaes.h): BLS12-377 Fr unless a field_id says otherwise
+int zkaes_poly_divide_by_vanishing(const uint8_t *p, size_t len, size_t m, int with_scratch, uint8_t *q, uint8_t *rem_or_null) {
+    return guardk([&] {
+        const char *who = "zkaes_poly_divide_by_vanishing";
+        if (m == 0 || len <= m) throw std::invalid_argument("divide_by_vanishing: dividend shorter than divisor");
+        need(p && q, who, "null argument"); need(len <= POLY_MAX, who, "polynomial too long");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dp = upload(p, len, s), dq(len - m), drem(m), scratch;
+        size_t scratch_len = 0;
+        if (with_scratch) { scratch_len = zk::gpu::divide_by_vanishing_scratch(len, m); scratch.alloc(scratch_len ? scratch_len : 1); }
+        zk::gpu::divide_by_vanishing(dq, rem_or_null ? drem.get() : nullptr, dp, len, m, s, with_scratch ? scratch.get() : nullptr, scratch_len);
+        zk::gpu::d2h(q, dq, (len - m) * sizeof(PF), s);
+        if (rem_or_null) zk::gpu::d2h(rem_or_null, drem, m * sizeof(PF), s);
+    });
+}
+int zkaes_poly_divide_by_linear(const uint8_t *p, size_t len, const uint8_t z[32], uint8_t *q) {
+    return guardk([&] {
+        const char *who = "zkaes_poly_divide_by_linear";
+        const PF zf = load_f(z, who);
+        need(len <= POLY_MAX, who, "polynomial too long"); need(len < 2 || (p && q), who, "null argument");
+        if (len < 2) return;                                   // a constant has the empty quotient
+        zk::gpu::require_device();
+        StreamGuard s;
+        const size_t scratch_len = zk::gpu::divide_by_linear_scratch(len);
+        DevPtr<PF> dp = upload(p, len, s), dq(len - 1), scratch(scratch_len);
+        zk::gpu::divide_by_linear(dq, dp, len, zf, scratch, scratch_len, s);
+        zk::gpu::d2h(q, dq, (len - 1) * sizeof(PF), s);
+    });
+}
+int zkaes_poly_eval_multi(const uint8_t *const *polys, const size_t *lens, const uint8_t *x, int count, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_poly_eval_multi";
+        need(count >= 1 && count <= 8, who, "1..8 polynomials"); need(polys && lens && x && out, who, "null argument");
+        size_t scratch_len = 8;
+        for (int i = 0; i < count; i++) { need(lens[i] <= POLY_MAX, who, "polynomial too long"); need(!lens[i] || polys[i], who, "null polynomial"); scratch_len += zk::gpu::poly_eval_scratch(lens[i]); }
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dp[8];
+        const PF *ptr[8];
+        PF xs[8], res[8];
+        for (int i = 0; i < count; i++) { dp[i] = upload(polys[i], lens[i], s); ptr[i] = dp[i]; xs[i] = load_f(x + 32 * i, who); }
+        DevPtr<PF> scratch(scratch_len);
+        zk::gpu::poly_eval_multi(ptr, lens, xs, count, res, scratch, scratch_len, s);
+        memcpy(out, res, (size_t)count * sizeof(PF));
+    });
+}
+int zkaes_batch_inverse(uint8_t *v, size_t n, const uint8_t *post_or_null, int throughput_variant) {
+    return guardk([&] {
+        const char *who = "zkaes_batch_inverse";
+        need(v || !n, who, "null argument"); need(n <= POLY_MAX, who, "vector too long");
+        PF post; if (post_or_null) post = load_f(post_or_null, who);
+        if (!n) return;
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dv = upload(v, n, s);
+        {
+            zk::gpu::ThroughputWaits as_between_overlapping_proofs(throughput_variant != 0);    // batch_inverse's own dispatch rule then takes the 16-element Fermat variant
+            zk::gpu::batch_inverse(dv, n, post_or_null ? &post : nullptr, s);
+            zk::gpu::sync(s);
+        }
+        zk::gpu::d2h(v, dv, n * sizeof(PF), s);
+    });
+}
+int zkaes_poly_lincomb(const uint8_t *const *polys, const size_t *lens, const uint8_t *scalars, int count, size_t n, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_poly_lincomb";
+        need(count >= 1 && count <= 8, who, "1..8 terms"); need(polys && lens && scalars && (out || !n), who, "null argument"); need(n <= POLY_MAX, who, "polynomial too long");
+        for (int i = 0; i < count; i++) { need(lens[i] <= n, who, "a term longer than the result"); need(!lens[i] || polys[i], who, "null polynomial"); }
+        if (!n) return;
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dp[8], dout(n);
+        const PF *ptr[8];
+        PF sc[8];
+        for (int i = 0; i < count; i++) { dp[i] = upload(polys[i], lens[i], s); ptr[i] = dp[i]; sc[i] = load_f(scalars + 32 * i, who); }
+        zk::gpu::poly_lincomb_n(dout, n, ptr, lens, sc, count, s);
+        zk::gpu::d2h(out, dout, n * sizeof(PF), s);
+    });
+}
+int zkaes_vanishing_quotient_evals(int lg_n, const uint8_t *g, int ncosets, const uint8_t a[32], const uint32_t *idx_or_null, size_t nidx, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_vanishing_quotient_evals";
+        need(lg_n >= 0 && lg_n <= 24, who, "lg_n must be in [0, 24]"); need(ncosets >= 1 && ncosets <= 3, who, "1..3 cosets"); need(g && out, who, "null argument");
+        const size_t n = (size_t)1 << lg_n;
+        for (size_t i = 0; idx_or_null && i < nidx; i++) need(idx_or_null[i] < n, who, "index out of range");
+        const PF af = load_f(a, who);
+        PF gs[3];
+        for (int c = 0; c < ncosets; c++) gs[c] = load_f(g + 32 * c, who);
+        zk::gpu::require_device();
+        StreamGuard s;
+        const PF *elems = zk::gpu::domain_elements<zk::Fr377>(lg_n);
+        const size_t scratch_len = zk::gpu::vanishing_quotient_scratch(lg_n, ncosets);
+        DevPtr<PF> tabs[3], scratch(scratch_len);
+        PF *outs[3] = {nullptr, nullptr, nullptr};
+        for (int c = 0; c < ncosets; c++) { tabs[c].alloc(n); outs[c] = tabs[c]; }
+        zk::gpu::vanishing_quotient_evals(outs, gs, ncosets, af, elems, (uint32_t)n, lg_n, scratch, scratch_len, s);
+        if (!idx_or_null) { for (int c = 0; c < ncosets; c++) zk::gpu::d2h(out + (size_t)c * n * sizeof(PF), tabs[c], n * sizeof(PF), s); return; }
+        std::vector<PF> host(n);
+        for (int c = 0; c < ncosets; c++) {
+            zk::gpu::d2h(host.data(), tabs[c], n * sizeof(PF), s);
+            for (size_t i = 0; i < nidx; i++) memcpy(out + ((size_t)c * nidx + i) * sizeof(PF), &host[idx_or_null[i]], sizeof(PF));
+        }
+    });
+}
+int zkaes_q1_coset_pointwise(const uint8_t *r, const uint8_t *za, const uint8_t *zb, const uint8_t *t, const uint8_t *z, const uint8_t consts[192], size_t n, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_q1_coset_pointwise";
+        need(r && za && zb && t && z && consts && out, who, "null argument"); need(n >= 1 && n <= POLY_MAX, who, "n out of range");
+        PF c[6];
+        for (int i = 0; i < 6; i++) c[i] = load_f(consts + 32 * i, who);
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dr = upload(r, n, s), dza = upload(za, n, s), dzb = upload(zb, n, s), dt = upload(t, n, s), dz = upload(z, n, s), dout(n);
+        zk::gpu::q1_coset_pointwise(dout, dr, dza, dzb, dt, dz, c[0], c[1], c[2], c[3], c[4], c[5], n, s);
+        zk::gpu::d2h(out, dout, n * sizeof(PF), s);
+    });
+}
+int zkaes_h2_coset(const uint8_t *const arrays[7], const uint8_t consts[224], size_t k, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_h2_coset";
+        need(arrays && consts && out, who, "null argument"); need(k >= 1 && k <= POLY_MAX, who, "k out of range");
+        for (int i = 0; i < 7; i++) need(arrays[i], who, "null array");
+        PF c[7];
+        for (int i = 0; i < 7; i++) c[i] = load_f(consts + 32 * i, who);
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> d[7], dout(k);
+        for (int i = 0; i < 7; i++) d[i] = upload(arrays[i], k, s);
+        zk::gpu::h2_coset(dout, d[0], d[1], d[2], d[3], d[4], d[5], d[6], c[0], c[1], c[2], c[3], c[4], c[5], c[6], k, s);
+        zk::gpu::d2h(out, dout, k * sizeof(PF), s);
+    });
+}
+int zkaes_q1_combine(const uint8_t *q0, const uint8_t *q1, const uint8_t *q3, const uint8_t *mask, const uint8_t inv2[32], const uint8_t inv2zeta[32], size_t n, uint8_t *h1, uint8_t *g1) {
+    return guardk([&] {
+        const char *who = "zkaes_q1_combine";
+        need(q0 && q1 && q3 && mask && h1 && (g1 || n < 2), who, "null argument"); need(n >= 1 && n <= POLY_MAX / 4, who, "n out of range");
+        const PF i2 = load_f(inv2, who), i2z = load_f(inv2zeta, who);
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> d0 = upload(q0, n, s), d1 = upload(q1, n, s), d3 = upload(q3, n, s), dm = upload(mask, 3 * n, s), dh(2 * n), dg(n);
+        zk::gpu::q1_combine(dh, dg, d0, d1, d3, dm, i2, i2z, n, s);
+        zk::gpu::d2h(h1, dh, 2 * n * sizeof(PF), s);
+        zk::gpu::d2h(g1, dg, (n - 1) * sizeof(PF), s);
+    });
+}
+int zkaes_coset_scale(const uint8_t *in, size_t in_len, const uint8_t g[32], size_t n, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_coset_scale";
+        need((in || !in_len) && (out || !n), who, "null argument"); need(n <= POLY_MAX && in_len <= POLY_MAX, who, "polynomial too long");
+        const PF gf = load_f(g, who);
+        if (!n) return;
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> din = upload(in, in_len, s), dout(n);
+        zk::gpu::coset_scale(dout, din, gf, in_len, n, s);
+        zk::gpu::d2h(out, dout, n * sizeof(PF), s);
+    });
+}
+int zkaes_z_poly_from_w(const uint8_t *w, size_t wlen, const uint8_t *x_poly, uint32_t m, size_t n, uint8_t *zp) {
+    return guardk([&] {
+        const char *who = "zkaes_z_poly_from_w";
+        need((w || !wlen) && (x_poly || !m) && zp, who, "null argument"); need(n < POLY_MAX && wlen <= POLY_MAX, who, "polynomial too long");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dw = upload(w, wlen, s), dx = upload(x_poly, m, s), dz(n + 1);
+        zk::gpu::z_poly_from_w(dz, dw, wlen, dx, m, n, s);
+        zk::gpu::d2h(zp, dz, (n + 1) * sizeof(PF), s);
+    });
+}
+int zkaes_ntt_padded(int field_id, const uint8_t *in, size_t in_len, size_t n, int inverse, int coset_c, int lg_big, uint8_t *out) {
+    return guardk([&] {
+        if (field_id == 381) run_ntt_padded<zk::Fr381>(in, in_len, n, inverse, coset_c, lg_big, out); else if (field_id == 377) run_ntt_padded<zk::Fr377>(in, in_len, n, inverse, coset_c, lg_big, out);
+        else throw std::invalid_argument("field_id must be 377 or 381");
+    });
+}
+int zkaes_ntt_scaled(const uint8_t g[32], const uint8_t *in, size_t in_len, size_t n, int inverse, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_ntt_scaled";
+        const int lg = exact_log2(n, who);
+        need(lg >= 1 && lg <= 28, who, "n must be in [2, 2^28]"); need(in_len <= n, who, "in_len must not exceed n"); need(out && (in || !in_len), who, "null argument");
+        const PF gf = load_f(g, who);
+        need(!gf.is_zero(), who, "the coset generator must not be zero");
+        zk::gpu::require_device();
+        StreamGuard s;
+        TableGuard table;
+        table.p = zk::gpu::coset_power_table<PF>(inverse ? gf.inverse() : gf, n, s);      // g^i evaluates on g D, g^-i interpolates from there
+        DevPtr<PF> a = upload(in, in_len, s), b(n);
+        zk::gpu::ntt_scaled<PF>(b, a, in_len, lg, inverse != 0, table.p, s);
+        zk::gpu::d2h(out, b, n * sizeof(PF), s);
     });
 }
 int zkaes_msm(int curve_id, const uint8_t *bases, const uint8_t *scalars, size_t n, uint8_t *out_xy, int *out_inf) {

@@ -201,13 +201,15 @@ void poly_add_at(F *p, size_t idx, const F &val, stream_t s);                 //
 void poly_scale(F *p, const F &sc, size_t n, stream_t s);                     // p[i] *= sc
 // out[i] = sum_j scalars[j] * polys[j][i] for i < n, each polynomial contributing only below its own length (1..8 terms)
 void poly_lincomb_n(F *out, size_t n, const F *const *polys, const size_t *lens, const F *scalars, int count, stream_t s);
-// q = p / (X^m - 1) (len - m coefficients), rem = remainder (m coefficients); requires len > m
+// q = p / (X^m - 1) (len - m coefficients), rem = remainder (m coefficients, may be null); requires len > m >= 1.  With scratch >= divide_by_vanishing_scratch(len, m)
+// elements, chains of 64 and more steps take the segmented kernels
+size_t divide_by_vanishing_scratch(size_t len, size_t m);
 void divide_by_vanishing(F *q, F *rem, const F *p, size_t len, size_t m, stream_t s, F *scratch = nullptr, size_t scratch_len = 0);
 // q = p / (X - z) (len - 1 coefficients, remainder dropped); scratch >= divide_by_linear_scratch(len) elements (block values and carries of the blocked recurrence)
 void divide_by_linear(F *q, const F *p, size_t len, const F &z, F *scratch, size_t scratch_elems, stream_t s);
 size_t divide_by_linear_scratch(size_t len);   // field elements of scratch a division of `len` coefficients needs
-// p(x) returned to the host (synchronizes); scratch >= ceil(len/64) + 1 elements
-F poly_eval(const F *p, size_t len, const F &x, F *scratch, stream_t s);       // scratch: 8 + poly_eval_scratch(len) elements
+// p(x) returned to the host (synchronizes); scratch >= 8 + poly_eval_scratch(len) elements
+F poly_eval(const F *p, size_t len, const F &x, F *scratch, stream_t s);
 size_t poly_eval_scratch(size_t len);
 // out[i] = p[i](x[i]), 1..8 polynomials: all launches, then one wait and one copy.  scratch: 8 + sum poly_eval_scratch(len[i]) elements
 void poly_eval_multi(const F *const *p, const size_t *len, const F *x, int count, F *out, F *scratch, size_t scratch_elems, stream_t s);

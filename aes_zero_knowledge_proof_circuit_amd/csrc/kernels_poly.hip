@@ -84,8 +84,13 @@ __global__ void k_divvan_apply(F *__restrict__ q, F *__restrict__ rem, const F *
     if (seg == 0 && rem) rem[j] = (j < len ? p[j] : F::zero()) + carry;
 }
 // `scratch` (optional, `scratch_len` elements, must not overlap q / rem / p): the segment sums of the small-divisor path
+size_t divide_by_vanishing_scratch(size_t len, size_t m) {          // field elements of `scratch` the segmented path needs (0: the chains are too short for it)
+    if (m == 0 || len <= m) return 0;
+    const size_t chain = (len - m + m - 1) / m;
+    return chain >= 64 ? (chain + 15) / 16 * m : 0;
+}
 void divide_by_vanishing(F *q, F *rem, const F *p, size_t len, size_t m, stream_t s, F *scratch, size_t scratch_len) {
-    if (len <= m) throw GpuError("divide_by_vanishing: dividend shorter than divisor");
+    if (m == 0 || len <= m) throw GpuError("divide_by_vanishing: dividend shorter than divisor");
     const size_t chain = (len - m + m - 1) / m;            // steps of the longest residue class
     const size_t C = 16, S = (chain + C - 1) / C;          // 16 dependent steps per lane; the carry of a segment is a sum of up to S segment sums (independent loads)
     if (chain >= 64 && scratch && S * m <= scratch_len) {

@@ -172,6 +172,43 @@ int zkaes_ntt_coset(int field_id, uint8_t *data, size_t n, int inverse, int cose
 /* `count` (1..12) transforms of one shape in shared launches, as the prover's rounds 1 and 2 issue them: data = count x n x 32 B, transformed in place; coset_c[i] = 0 for a
  * plain transform, > 0 for the coset W^coset_c[i] D (coset_c may be NULL: all plain; lg_big as in zkaes_ntt_coset, ignored when no job is a coset transform). */
 int zkaes_ntt_batch(int field_id, uint8_t *data, size_t n, int count, int inverse, const int *coset_c, int lg_big);
+/* ---- kernel-level entry points for tests ------------------------------------------------------------------------- */
+/* One call = one launch wrapper of the prover's polynomial layer (csrc/kernels_poly.hip) or of a transform entry point the prover uses and zkaes_ntt does not reach, so that
+ * tests can compare every multi-launch algorithm with a big-integer model at the boundaries of its block, chunk and level constants.  Host buffers of 32-byte little-endian
+ * Montgomery limbs in and out, BLS12-377 Fr unless a field_id says otherwise; every element must be canonical (< r).  Diagnostic use: each call allocates, copies and waits. */
+/* q (len - m elements) = p / (X^m - 1), rem_or_null (m elements) = the remainder; needs len > m >= 1.  with_scratch != 0 hands the library the scratch its segmented
+ * kernels want, which it then uses for chains of 64 and more steps; 0: one lane per residue class at every length */
+int zkaes_poly_divide_by_vanishing(const uint8_t *p, size_t len, size_t m, int with_scratch, uint8_t *q, uint8_t *rem_or_null);
+/* q (len - 1 elements) = p / (X - z), remainder dropped; len < 2 writes nothing */
+int zkaes_poly_divide_by_linear(const uint8_t *p, size_t len, const uint8_t z[32], uint8_t *q);
+/* out[i] = polys[i](x[i]) for count = 1..8 polynomials of lens[i] coefficients (0 allowed: the value is 0, polys[i] may be NULL); x, out: count elements */
+int zkaes_poly_eval_multi(const uint8_t *const *polys, const size_t *lens, const uint8_t *x, int count, uint8_t *out);
+/* v[i] <- post / v[i] in place (post_or_null == NULL: 1 / v[i]); zeros stay zero.  throughput_variant != 0: run as between overlapping proofs of a multi-proof call, where
+ * the library picks its 16-elements-per-lane Fermat kernel; 0: as a lone call (4 per lane, Euclidean inverse, up to 2^21 elements; the other kernel above) */
+int zkaes_batch_inverse(uint8_t *v, size_t n, const uint8_t *post_or_null, int throughput_variant);
+/* out[i] = sum_j scalars[j] polys[j][i] for i < n, term j contributing below lens[j] <= n only; count = 1..8 */
+int zkaes_poly_lincomb(const uint8_t *const *polys, const size_t *lens, const uint8_t *scalars, int count, size_t n, uint8_t *out);
+/* r(a, y) = (a^n - y^n) / (a - y) at y = g[c] h_i, h_i the elements of the size-2^lg_n domain (the library's own table), for c < ncosets <= 3 cosets.
+ * idx_or_null == NULL: out = ncosets x n elements, coset-major; otherwise out = ncosets x nidx elements, the values at the given indices */
+int zkaes_vanishing_quotient_evals(int lg_n, const uint8_t *g, int ncosets, const uint8_t a[32], const uint32_t *idx_or_null, size_t nidx, uint8_t *out);
+/* round 2 on a coset: out[i] = r[i] (eta_a A + eta_b B + eta_c A B) - t[i] Z, A = za[i] + ca, B = zb[i] + cb, Z = z[i] + cz; consts = ca, cb, cz, eta_a, eta_b, eta_c */
+int zkaes_q1_coset_pointwise(const uint8_t *r, const uint8_t *za, const uint8_t *zb, const uint8_t *t, const uint8_t *z, const uint8_t consts[192], size_t n, uint8_t *out);
+/* round 3 on a coset: out[i] = ((ea va + eb vb + ec vc) - (alpha_beta - alpha row - beta col + rc) f)[i] vinv; arrays = row, col, va, vb, vc, rc, f (k elements each);
+ * consts = alpha, beta, alpha_beta, ea, eb, ec, vinv */
+int zkaes_h2_coset(const uint8_t *const arrays[7], const uint8_t consts[224], size_t k, uint8_t *out);
+/* h1 (2n) and g1 (n - 1) from the interpolants q0 (on H), q1, q3 (on W H, W^3 H) of q_1 - mask and the mask (3n coefficients); inv2 = 1/2, inv2zeta = 1/(2 zeta), zeta = W^n */
+int zkaes_q1_combine(const uint8_t *q0, const uint8_t *q1, const uint8_t *q3, const uint8_t *mask, const uint8_t inv2[32], const uint8_t inv2zeta[32], size_t n, uint8_t *h1, uint8_t *g1);
+/* out[j] = in[j] g^j for j < n, in zero-padded beyond in_len */
+int zkaes_coset_scale(const uint8_t *in, size_t in_len, const uint8_t g[32], size_t n, uint8_t *out);
+/* zp (n + 1 elements) = w (X^m - 1) + x_poly: zp[i] = w[i - m] - w[i] + x_poly[i], each term where its index exists (w: wlen, x_poly: m elements) */
+int zkaes_z_poly_from_w(const uint8_t *w, size_t wlen, const uint8_t *x_poly, uint32_t m, size_t n, uint8_t *zp);
+/* zkaes_ntt / zkaes_ntt_coset (coset_c > 0) of an input of in_len <= n elements that the first pass's gather pads with zeros; out: n elements */
+int zkaes_ntt_padded(int field_id, const uint8_t *in, size_t in_len, size_t n, int inverse, int coset_c, int lg_big, uint8_t *out);
+/* the transform on the coset g D of a generator that need not be a root of unity: forward out[i] = p(g w^i) from the in_len coefficients (table of g^i riding on the first
+ * pass), inverse the coefficients from such values (table of g^-i at the last store); n = 2 .. 2^28 */
+int zkaes_ntt_scaled(const uint8_t g[32], const uint8_t *in, size_t in_len, size_t n, int inverse, uint8_t *out);
+
+/* ---- MSM ---- */
 /* curve_id 377 / 381.  bases: n x 96 B affine (x||y Montgomery), scalars: n x 32 B Montgomery Fr; out_xy 96 B, *out_inf = 1 if infinity */
 int zkaes_msm(int curve_id, const uint8_t *bases, const uint8_t *scalars, size_t n, uint8_t *out_xy, int *out_inf);
 /* host-side sum of n affine points (n x 96 B, inf[i] != 0 marks the point at infinity; inf may be NULL): the local EC add that follows the

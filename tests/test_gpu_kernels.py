@@ -22,7 +22,7 @@ def rand_fr_mont(n, p, seed):
 
 
 @pytest.mark.parametrize("cid", [377, 381])
-@pytest.mark.parametrize("lg", [0, 1, 2, 5, 9, 10, 11, 13, 16, 18])
+@pytest.mark.parametrize("lg", list(range(0, 19)))
 def test_ntt_matches_oracle(zko, api, cid, lg):
     n = 1 << lg
     data = rand_fr_mont(n, zko.FR[cid], 1000 + lg)
@@ -95,6 +95,100 @@ def test_ntt_full_size_roundtrip_and_linearity(zko, api):
         gv = zko.fr_unpack(g.raw)[0]
         for i in (0, 1, 2, 12345, n - 1):
             assert zko.fr_unpack(fd[32 * i:32 * i + 32])[0] == pow(gv, i, p)
+
+
+def _ntt_in_place(api, cid, arr, n, inverse):
+    """zkaes_ntt on a numpy buffer in place: no copies of a 512 MB vector on the Python side"""
+    rc = api.lib().zkaes_ntt(cid, arr.ctypes.data_as(C.c_void_p), C.c_size_t(n), 1 if inverse else 0)
+    assert rc == 0, api.lib().zkaes_last_error().decode()
+
+
+def _word(v):
+    return np.frombuffer(v.to_bytes(32, "little"), dtype="<u8")
+
+
+@pytest.mark.parametrize("cid", [377, 381])
+@pytest.mark.parametrize("inverse", [False, True], ids=["forward", "inverse"])
+@pytest.mark.parametrize("lg", [10, 18, 19, 20, 22, 24])
+def test_ntt_of_inputs_with_closed_form_outputs(zko, api, cid, inverse, lg):
+    """One-, two- and three-pass plans up to |K| of a 28-block proof against values that need no reference run.  The all-zero and the single-coefficient input walk the worst
+    case of the butterfly schedule (kernels_ntt.hip: t = 0 in every butterfly, so x - t + 2 p grows by the full 2 p per stage, and the store must land on exactly 0, not p):
+      all zero -> all zero;   delta_j -> w^(i j) (inverse: w^(-i j) / n), every i up to lg 18, sampled i above;
+      constant c -> (n c, 0, ..., 0) (inverse: (c, 0, ..., 0)), also c = r - 1;   alternating 0, r - 1 -> -(n / 2) at 0, +(n / 2) at n / 2 (inverse: -+ 1/2), zero elsewhere.
+    Inputs are built by repeating one 32-byte pattern; values are Montgomery representatives, and the transform is linear, so a representative goes in and comes out."""
+    n, r = 1 << lg, zko.FR[cid]
+    mont = (1 << 256) % r
+    gb = C.create_string_buffer(32)
+    zko.lib().zko_api_domain_gen(cid, C.c_size_t(n), gb)
+    w = zko.fr_unpack(gb.raw, cid)[0]
+    if inverse:
+        w = pow(w, -1, r)
+    scale = pow(n, -1, r) if inverse else 1
+    buf = np.zeros((n, 4), dtype="<u8")
+    rng = np.random.RandomState(lg)
+
+    def word_at(i):
+        return int.from_bytes(buf[i].tobytes(), "little")
+
+    # all zero
+    _ntt_in_place(api, cid, buf, n, inverse)
+    assert not buf.any(), "NTT(0) != 0 at element %d" % int(np.argmax(buf.any(axis=1)))
+    # single coefficients
+    for j in (0, 1, n // 2, n - 1):
+        buf[:] = 0
+        buf[j] = _word(mont)                                                    # the value 1
+        _ntt_in_place(api, cid, buf, n, inverse)
+        idx = range(n) if lg <= 18 else sorted(set([0, 1, 2, n // 2, n - 1] + [int(x) for x in rng.randint(0, n, size=200)]))
+        wj = pow(w, j, r)
+        if lg <= 18:
+            want, pw = bytearray(), scale * mont % r
+            for _ in range(n):
+                want += pw.to_bytes(32, "little")
+                pw = pw * wj % r
+            assert buf.tobytes() == bytes(want), "delta_%d" % j
+        else:
+            for i in idx:
+                assert word_at(i) == pow(wj, i, r) * scale * mont % r, "delta_%d, output %d" % (j, i)
+    # constants
+    for c in (_word(mont * 5 % r), _word(r - 1)):
+        buf[:] = c
+        _ntt_in_place(api, cid, buf, n, inverse)
+        c_int = int.from_bytes(c.tobytes(), "little")
+        assert word_at(0) == c_int * n * scale % r
+        assert not buf[1:].any(), "constant input: non-zero output at element %d" % (1 + int(np.argmax(buf[1:].any(axis=1))))
+    # alternating 0, r - 1: the representative r - 1 at the odd positions
+    buf[:] = 0
+    buf[1::2] = _word(r - 1)
+    _ntt_in_place(api, cid, buf, n, inverse)
+    half = (r - 1) * (n // 2) * scale % r
+    assert word_at(0) == half and word_at(n // 2) == (r - half) % r
+    buf[0] = 0
+    buf[n // 2] = 0
+    assert not buf.any(), "alternating input: non-zero output at element %d" % int(np.argmax(buf.any(axis=1)))
+
+
+@pytest.mark.parametrize("cid", [377, 381])
+@pytest.mark.parametrize("inverse", [False, True], ids=["forward", "inverse"])
+@pytest.mark.parametrize("lg", [19, 20])
+def test_three_pass_ntt_of_a_random_vector_at_sampled_outputs(zko, api, cid, inverse, lg):
+    """no three-pass plan was compared with an independent value before: out[i] = sum_j a_j w^(i j) (inverse: w^(-i j) / n) at two sampled i, by Horner in Python over the
+    raw representatives (the transform is linear: no conversion)"""
+    n, r = 1 << lg, zko.FR[cid]
+    data = fast_fr_mont(n, 1900 + lg + cid)
+    got = api.ntt(cid, data, inverse=inverse)
+    gb = C.create_string_buffer(32)
+    zko.lib().zko_api_domain_gen(cid, C.c_size_t(n), gb)
+    w = zko.fr_unpack(gb.raw, cid)[0]
+    if inverse:
+        w = pow(w, -1, r)
+    scale = pow(n, -1, r) if inverse else 1
+    a = [int.from_bytes(data[k:k + 32], "little") for k in range(0, 32 * n, 32)]
+    rng = np.random.RandomState(lg + cid)
+    for i in (int(rng.randint(0, n)) | 1, int(rng.randint(0, n))):
+        x, acc = pow(w, i, r), 0
+        for c in reversed(a):
+            acc = (acc * x + c) % r
+        assert int.from_bytes(got[32 * i:32 * i + 32], "little") == acc * scale % r, "output %d" % i
 
 
 def oracle_points(zko, cid, n, seed):
