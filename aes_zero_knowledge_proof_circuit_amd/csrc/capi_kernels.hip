@@ -227,10 +227,6 @@ DevPtr<PF> upload(const uint8_t *host, size_t count, zk::gpu::stream_t s) {
     zk::gpu::h2d(d, host, count * sizeof(PF), s);
     return d;
 }
-struct TableGuard {                                  // coset_power_table hands its table over as a raw pointer
-    void *p = nullptr;
-    ~TableGuard() { zk::gpu::dfree(p); }
-};
 template <class Fr> void run_ntt_padded(const uint8_t *in, size_t in_len, size_t n, int inverse, int coset_c, int lg_big, uint8_t *out) {
     const int lg = exact_log2(n, "zkaes_ntt_padded");
     need(in_len <= n, "zkaes_ntt_padded", "in_len must not exceed n");
@@ -482,10 +478,9 @@ int zkaes_ntt_scaled(const uint8_t g[32], const uint8_t *in, size_t in_len, size
         need(!gf.is_zero(), who, "the coset generator must not be zero");
         zk::gpu::require_device();
         StreamGuard s;
-        TableGuard table;
-        table.p = zk::gpu::coset_power_table<PF>(inverse ? gf.inverse() : gf, n, s);      // g^i evaluates on g D, g^-i interpolates from there
+        DevPtr<void> table = zk::gpu::coset_power_table<PF>(inverse ? gf.inverse() : gf, n, s);      // g^i evaluates on g D, g^-i interpolates from there
         DevPtr<PF> a = upload(in, in_len, s), b(n);
-        zk::gpu::ntt_scaled<PF>(b, a, in_len, lg, inverse != 0, table.p, s);
+        zk::gpu::ntt_scaled<PF>(b, a, in_len, lg, inverse != 0, table, s);
         zk::gpu::d2h(out, b, n * sizeof(PF), s);
     });
 }
@@ -548,7 +543,7 @@ int zkaes_stream_copy_bench(size_t bytes, int reps, double *gb_per_s) {
         const size_t n16 = bytes / 16;
         DevPtr<uint4> a(n16), b(n16);
         zk::gpu::dzero(a, n16 * 16, s);
-        hipStream_t hs = (hipStream_t)s.s;
+        hipStream_t hs = (hipStream_t)s.h;
         k_stream_copy<<<(unsigned)((n16 + 1023) / 1024), 256, 0, hs>>>(b, a, n16);
         EventGuard e0, e1;
         zk::gpu::event_record(e0, s);
@@ -564,7 +559,7 @@ int zkaes_int_rate_bench(double seconds, double out[8]) {
         zk::gpu::require_device();
         using P = zk::Fq377P; using G = zk::FpMsm<P>;
         StreamGuard s;
-        hipStream_t hs = (hipStream_t)s.s;
+        hipStream_t hs = (hipStream_t)s.h;
         const int GRID_A = 4096, ITERS_A = 300, GRID_B = 8192, ITERS_B = 83;      // A: 4 waves per SIMD, 600 products per lane; B: k_accumulate's launch shape for 2^19 buckets of ~83 points
         const uint32_t NREC = 4096;                                                // 768 KB of records: L2-resident
         DevPtr<CalStamp> st(GRID_B);

@@ -45,33 +45,61 @@ void stream_wait_event(stream_t s, void *ev);   // work queued on s after this c
 float event_elapsed_ms(void *start, void *stop);
 void event_destroy(void *ev);
 
-// RAII owners of the raw handles above: an exception between an allocation and its release must not leak device memory, a stream or an MSM workspace
-// (every kernel-level C entry point and the setup helpers hold their temporaries through these)
+// pinned host memory a kernel can write (mapped into the device's address space)
+void *pinned_alloc(size_t bytes);
+void *pinned_device_address(void *host);
+void pinned_free(void *host);
+
+// RAII owners of the raw handles above: an exception between an allocation and its release must not leak device memory, a stream or an MSM workspace.
+// EVERY device buffer, stream, event and workspace the library holds is a member or a local of one of these types; what lives for the life of the process
+// (the NTT's table caches, the S-box table) is the only raw dmalloc.
+template <class T> struct DevElem { static constexpr size_t bytes = sizeof(T); };
+template <> struct DevElem<void> { static constexpr size_t bytes = 1; };      // untyped storage is counted in bytes
 template <class T> struct DevPtr {
     T *p = nullptr;
+    size_t n = 0;                             // elements held; the buffer is EMPTY when p is null (a buffer of 0 elements still holds memory)
     DevPtr() = default;
-    explicit DevPtr(size_t count) : p((T *)dmalloc(count * sizeof(T))) {}
+    explicit DevPtr(size_t count) { alloc(count); }
     DevPtr(const DevPtr &) = delete; DevPtr &operator=(const DevPtr &) = delete;
-    DevPtr(DevPtr &&o) noexcept : p(o.p) { o.p = nullptr; }
-    DevPtr &operator=(DevPtr &&o) noexcept { if (this != &o) { dfree(p); p = o.p; o.p = nullptr; } return *this; }
+    DevPtr(DevPtr &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevPtr &operator=(DevPtr &&o) noexcept { if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
     ~DevPtr() { dfree(p); }
-    void alloc(size_t count) { dfree(p); p = nullptr; p = (T *)dmalloc(count * sizeof(T)); }
+    void reset() { dfree(p); p = nullptr; n = 0; }
+    // release first, then allocate (the peak is the larger of the two sizes, not their sum); a dmalloc that throws leaves the buffer empty
+    void alloc(size_t count) { reset(); p = (T *)dmalloc(count * DevElem<T>::bytes); n = count; }
+    void grow(size_t count) { if (!p || count > n) alloc(count); }      // no-op when `count` elements are already there
     T *get() const { return p; }
     operator T *() const { return p; }
 };
-struct StreamGuard {
-    stream_t s = nullptr;
-    StreamGuard() : s(stream_create()) {}
-    StreamGuard(const StreamGuard &) = delete; StreamGuard &operator=(const StreamGuard &) = delete;
-    ~StreamGuard() { stream_destroy(s); }
-    operator stream_t() const { return s; }
+// Buffers that are sized together (the four key / value arrays of the sort, the levels of a reduction): grown as ONE unit.  Nothing happens when every member already holds
+// its count; otherwise ALL members are released before any is allocated, and whichever allocation throws, all of them are left empty -- so the test above cannot pass on a
+// half-allocated group and the next call allocates everything afresh.
+template <class... T> void grow_together(const size_t (&counts)[sizeof...(T)], DevPtr<T> &...bufs) {
+    size_t i = 0;
+    if (((bufs.p && counts[i++] <= bufs.n) && ...)) return;
+    (bufs.reset(), ...);
+    i = 0;
+    try { (bufs.alloc(counts[i++]), ...); } catch (...) { (bufs.reset(), ...); throw; }
+}
+// a stream, an event, an MSM workspace or pinned host memory: created by the default constructor, or adopted from a create call (a null handle = empty, to be filled by move later)
+template <class H, H (*Create)(), void (*Destroy)(H)> struct Handle {
+    H h = nullptr;
+    Handle() : h(Create()) {}
+    explicit Handle(H adopt) : h(adopt) {}
+    Handle(const Handle &) = delete; Handle &operator=(const Handle &) = delete;
+    Handle(Handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle &operator=(Handle &&o) noexcept { if (this != &o) { Destroy(h); h = o.h; o.h = nullptr; } return *this; }
+    ~Handle() { Destroy(h); }
+    operator H() const { return h; }
 };
-struct EventGuard {
-    void *e = nullptr;
-    EventGuard() : e(event_create()) {}
-    EventGuard(const EventGuard &) = delete; EventGuard &operator=(const EventGuard &) = delete;
-    ~EventGuard() { event_destroy(e); }
-    operator void *() const { return e; }
+using StreamGuard = Handle<stream_t, stream_create, stream_destroy>;
+using EventGuard = Handle<void *, event_create, event_destroy>;
+struct PinnedPtr {
+    void *host = nullptr, *dev = nullptr;     // the same bytes as the host and as the device address them
+    PinnedPtr() = default;
+    PinnedPtr(const PinnedPtr &) = delete; PinnedPtr &operator=(const PinnedPtr &) = delete;
+    ~PinnedPtr() { pinned_free(host); }
+    void alloc(size_t bytes) { pinned_free(host); host = dev = nullptr; host = pinned_alloc(bytes); dev = pinned_device_address(host); }
 };
 
 // ---- op lists (debug; zkaes_pk_op_lists): while a recording is open, every transform and every MSM the library launches is appended -- the ACTUAL lists the whole-proof
@@ -96,8 +124,8 @@ template <class Fr> void ntt_coset(Fr *dst, const Fr *src, size_t in_len, int lg
 template <class Fr> struct NttJob { Fr *dst; const Fr *src; int coset_c; };
 template <class Fr> void ntt_batch(const NttJob<Fr> *jobs, int count, size_t in_len, int lg, bool inverse, int lg_big, stream_t s);
 // A coset whose generator g is not a root of unity (round 3 uses the field's multiplicative generator): coset_power_table builds g^i (i < n) once per key in the kernel's
-// reduced-radix form (free with dfree); ntt_scaled(.., table of g^i) evaluates on g D, ntt_scaled(.., inverse = true, table of g^-i) interpolates from there.
-template <class Fr> void *coset_power_table(const Fr &g, size_t n, stream_t s);
+// reduced-radix form; ntt_scaled(.., table of g^i) evaluates on g D, ntt_scaled(.., inverse = true, table of g^-i) interpolates from there.
+template <class Fr> DevPtr<void> coset_power_table(const Fr &g, size_t n, stream_t s);
 template <class Fr> void ntt_scaled(Fr *dst, const Fr *src, size_t in_len, int lg, bool inverse, const void *table, stream_t s);
 template <class Fr> const Fr *domain_elements(int lg);   // device table g^i, i < 2^lg  (built lazily)
 
@@ -106,13 +134,7 @@ template <class Fr> const Fr *domain_elements(int lg);   // device table g^i, i 
 struct MsmWorkspace;
 MsmWorkspace *msm_workspace_create();
 void msm_workspace_destroy(MsmWorkspace *ws);
-struct WorkspaceGuard {
-    MsmWorkspace *ws = nullptr;
-    WorkspaceGuard() : ws(msm_workspace_create()) {}
-    WorkspaceGuard(const WorkspaceGuard &) = delete; WorkspaceGuard &operator=(const WorkspaceGuard &) = delete;
-    ~WorkspaceGuard() { msm_workspace_destroy(ws); }
-    operator MsmWorkspace *() const { return ws; }
-};
+using WorkspaceGuard = Handle<MsmWorkspace *, msm_workspace_create, msm_workspace_destroy>;
 // Bases are consumed in the reduced-radix form (Affine28, ff28.cuh): convert once with convert_bases (the SRS at key synthesis).
 template <class Curve> void convert_bases(Affine28<typename Curve::FqP> *dst, const Affine<typename Curve::Fq> *src, size_t n, stream_t s);
 template <class Curve>

@@ -764,75 +764,50 @@ static_assert(sizeof(Acc28<Fq381P>) == ACC_BYTES, "bucket size differs between t
 static_assert(sizeof(AccTE<Fq377P>) == ACC_BYTES, "the Edwards accumulator must fit the XYZZ bucket slots");
 constexpr int MAX_WSUMS = 64;                                // window sums per MSM (per-window mode: <= 37 windows)
 struct MsmWorkspace {
-    size_t cap_pairs = 0, cap_buckets = 0, cap_tmp = 0, cap_result = 0;
-    uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr, *start = nullptr, *end = nullptr;
-    uint32_t *sorted_keys = nullptr, *sorted_vals = nullptr;      // whichever half of the double buffers the radix sort finished in
-    uint32_t *order = nullptr, *ovf_slot = nullptr;               // per bucket: visiting order, slot in the overflow list (NO_SLOT for all but oversized buckets)
-    uint32_t *ovf_bucket = nullptr, *ovf_nseg = nullptr, *ovf_off = nullptr; void *ovf_partial = nullptr; size_t cap_ovf = 0;    // overflow list + the segments' partial sums
-    uint32_t *part_hist = nullptr, *part_offs = nullptr; size_t cap_part = 0;      // two-level partition: (coarse bin, workgroup) counts and their scan
-    uint32_t *canon = nullptr; size_t cap_canon = 0;                               // two-level partition: the scalars as canonical integers (8 words each), between its two passes
-    uint32_t *ord_hist = nullptr, *ord_offs = nullptr;            // ORD_BINS x ORD_MAX_BLOCKS counts and their scan
-    uint32_t *ctrl = nullptr;                                     // 8 control words (see k_order_hist); armed at zero between MSMs
+    // (buffers on one line are sized together and grown as one group: gpu.hpp grow_together)
+    DevPtr<uint32_t> keys_a, keys_b, vals_a, vals_b;              // the (key, value) pairs of the sort, double-buffered
+    uint32_t *sorted_keys = nullptr, *sorted_vals = nullptr;      // (views) whichever half of the double buffers the radix sort finished in
+    DevPtr<uint32_t> start, end, order, ovf_slot;                 // per bucket: its range of pairs, visiting order, slot in the overflow list (NO_SLOT for all but oversized buckets)
+    DevPtr<uint32_t> ovf_bucket, ovf_nseg, ovf_off; DevPtr<void> ovf_partial;      // overflow list (ovf_bucket.n slots) + the segments' partial sums
+    DevPtr<uint32_t> part_hist, part_offs;                        // two-level partition: (coarse bin, workgroup) counts and their scan
+    DevPtr<uint32_t> canon;                                       // two-level partition: the scalars as canonical integers (8 words each), between its two passes
+    DevPtr<void> buckets, seg_s, seg_w, partial;                  // the accumulators and the reduction's levels
+    DevPtr<void> tmp;                                             // rocprim's scratch (sort, scan)
     bool ctrl_dirty = false;                                      // an exception left the order pass half done: re-arm ctrl before the next one
     size_t plan_n = 0, plan_pairs = 0; int plan_c = 0, plan_nwin = 0;     // state between msm_prepare and msm_finish
     bool plan_table = false; uint32_t plan_cap = BUCKET_CAP;
-    uint32_t *deferred = nullptr, *deferred_count = nullptr;
-    void *buckets = nullptr, *seg_s = nullptr, *seg_w = nullptr, *partial = nullptr, *tmp = nullptr;
-    void *h_res = nullptr, *d_res = nullptr;                      // pinned host memory the last reduction kernel writes the window sums (+ flags) into, and its device address
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // [2 rep], [2 rep + 1]: around the k_accumulate launch of base array `rep`
+    // fixed-size part, made by the first MSM (ensure_scratch); h_res is created last and stands for all of it
+    EventGuard ev[4] = {EventGuard(nullptr), EventGuard(nullptr), EventGuard(nullptr), EventGuard(nullptr)};      // [2 rep], [2 rep + 1]: around the k_accumulate launch of base array `rep`
+    DevPtr<uint32_t> deferred, deferred_count;
+    DevPtr<uint32_t> ord_hist, ord_offs;                          // ORD_BINS x ORD_MAX_BLOCKS counts and their scan
+    DevPtr<uint32_t> ctrl;                                        // 8 control words (see k_order_hist); armed at zero between MSMs
+    PinnedPtr h_res;                                              // pinned host memory the last reduction kernel writes the window sums (+ flags) into
 };
 constexpr size_t RES_BYTES = 192 * MAX_WSUMS * 6 + 64;        // six terms per set when the Edwards reduction ends on the host (k_reduce_terms RF_OUT)
 // the accumulators and the reduction's levels, sized by the number of buckets ACCUMULATED (twice the prepared ones when one prepared state serves two base arrays at once)
 static void ensure_result(MsmWorkspace &S, size_t buckets) {
-    if (buckets <= S.cap_result) return;
-    dfree(S.buckets); dfree(S.partial); dfree(S.seg_s); dfree(S.seg_w);
-    S.cap_result = buckets;
-    S.buckets = dmalloc(buckets * ACC_BYTES);
-    S.seg_s = dmalloc((buckets / RED_L1 + 64) * ACC_BYTES); S.seg_w = dmalloc((buckets / RED_L1 + 64) * ACC_BYTES);
-    S.partial = dmalloc((2 * (buckets / (RED_L1 * RED_L2)) + 2 * 64 * 64) * ACC_BYTES);
+    grow_together({buckets * ACC_BYTES, (buckets / RED_L1 + 64) * ACC_BYTES, (buckets / RED_L1 + 64) * ACC_BYTES, (2 * (buckets / (RED_L1 * RED_L2)) + 2 * 64 * 64) * ACC_BYTES},
+                  S.buckets, S.seg_s, S.seg_w, S.partial);
 }
 static void ensure_scratch(MsmWorkspace &S, size_t pairs, size_t buckets, size_t cap) {
     if (cap == 0) cap = BUCKET_CAP;
-    if (!S.ev[0]) {
-        for (auto &e : S.ev) HIP_CHECK(hipEventCreate(&e));
-        S.deferred = (uint32_t *)dmalloc(2 * DEFERRED_CAP * 4); S.deferred_count = (uint32_t *)dmalloc(8);
+    if (!S.h_res.dev) {
+        for (auto &e : S.ev) e = EventGuard();
+        S.deferred.alloc(2 * DEFERRED_CAP); S.deferred_count.alloc(2);
         HIP_CHECK(hipMemset(S.deferred_count, 0, 8));                 // [1] is the tail kernel's ticket: armed at zero, re-armed by the workgroup that takes the last one
-        S.ord_hist = (uint32_t *)dmalloc((size_t)ORD_BINS * ORD_MAX_BLOCKS * 4); S.ord_offs = (uint32_t *)dmalloc((size_t)ORD_BINS * ORD_MAX_BLOCKS * 4);
-        S.ctrl = (uint32_t *)dmalloc(32);
+        S.ord_hist.alloc((size_t)ORD_BINS * ORD_MAX_BLOCKS); S.ord_offs.alloc((size_t)ORD_BINS * ORD_MAX_BLOCKS);
+        S.ctrl.alloc(8);
         HIP_CHECK(hipMemset(S.ctrl, 0, 32));
-        HIP_CHECK(hipHostMalloc(&S.h_res, RES_BYTES, hipHostMallocMapped));
-        HIP_CHECK(hipHostGetDevicePointer(&S.d_res, S.h_res, 0));
+        S.h_res.alloc(RES_BYTES);
     }
-    if (pairs / cap + 64 > S.cap_ovf) {
-        dfree(S.ovf_partial); dfree(S.ovf_bucket); dfree(S.ovf_nseg); dfree(S.ovf_off);
-        S.cap_ovf = pairs / cap + 64;
-        S.ovf_partial = dmalloc(2 * S.cap_ovf * ACC_BYTES);          // (x 2: run_buckets with a second base array)
-        S.ovf_bucket = (uint32_t *)dmalloc(S.cap_ovf * 4); S.ovf_nseg = (uint32_t *)dmalloc(S.cap_ovf * 4); S.ovf_off = (uint32_t *)dmalloc((S.cap_ovf + 1) * 4);
-    }
-    if (pairs > S.cap_pairs) {
-        dfree(S.keys_a); dfree(S.keys_b); dfree(S.vals_a); dfree(S.vals_b);
-        S.cap_pairs = pairs;
-        S.keys_a = (uint32_t *)dmalloc(pairs * 4); S.keys_b = (uint32_t *)dmalloc(pairs * 4);
-        S.vals_a = (uint32_t *)dmalloc(pairs * 4); S.vals_b = (uint32_t *)dmalloc(pairs * 4);
-    }
-    if (buckets > S.cap_buckets) {
-        dfree(S.start); dfree(S.end); dfree(S.order); dfree(S.ovf_slot);
-        S.cap_buckets = buckets;
-        S.start = (uint32_t *)dmalloc(buckets * 4); S.end = (uint32_t *)dmalloc(buckets * 4);
-        S.order = (uint32_t *)dmalloc(buckets * 4); S.ovf_slot = (uint32_t *)dmalloc(buckets * 4);
-    }
+    const size_t ovf = pairs / cap + 64;
+    grow_together({2 * ovf * ACC_BYTES /* x 2: run_buckets with a second base array */, ovf, ovf, ovf + 1}, S.ovf_partial, S.ovf_bucket, S.ovf_nseg, S.ovf_off);
+    grow_together({pairs, pairs, pairs, pairs}, S.keys_a, S.keys_b, S.vals_a, S.vals_b);
+    grow_together({buckets, buckets, buckets, buckets}, S.start, S.end, S.order, S.ovf_slot);
     ensure_result(S, buckets);
 }
 MsmWorkspace *msm_workspace_create() { return new MsmWorkspace(); }
-void msm_workspace_destroy(MsmWorkspace *w) {
-    if (!w) return;
-    for (void *p : {(void *)w->keys_a, (void *)w->keys_b, (void *)w->vals_a, (void *)w->vals_b, (void *)w->start, (void *)w->end, (void *)w->order, (void *)w->ovf_slot,
-                    (void *)w->ovf_bucket, (void *)w->ovf_nseg, (void *)w->ovf_off, w->ovf_partial, (void *)w->part_hist, (void *)w->part_offs, (void *)w->canon, (void *)w->ord_hist, (void *)w->ord_offs,
-                    (void *)w->ctrl, (void *)w->deferred, (void *)w->deferred_count, w->buckets, w->seg_s, w->seg_w, w->partial, w->tmp}) dfree(p);
-    if (w->h_res) (void)hipHostFree(w->h_res);
-    for (auto e : w->ev) if (e) (void)hipEventDestroy(e);
-    delete w;
-}
+void msm_workspace_destroy(MsmWorkspace *w) { delete w; }
 
 // size-balanced visiting order of the buckets + the overflow list: three small launches, no memset, no generic sort (k_order_* above).  The same path serves lone calls
 // and multi-proof calls: positions are deterministic (buckets of one size keep the order of their index ranges), which the generic stable sort used to provide at ~16 launches.
@@ -843,9 +818,9 @@ static void order_buckets(MsmWorkspace &S, size_t nb, uint32_t cap, hipStream_t 
     if (nblk > (unsigned)ORD_MAX_BLOCKS) nblk = ORD_MAX_BLOCKS;
     if (nblk < 1) nblk = 1;
     const uint32_t per_block = (uint32_t)((nb + nblk - 1) / nblk);
-    hipLaunchKernelGGL(k_order_hist, dim3(nblk), dim3(ORD_THREADS), 0, s, S.start, S.end, (uint32_t)nb, per_block, cap, S.ovf_slot, S.ovf_bucket, S.ovf_nseg, (uint32_t)S.cap_ovf - 1, S.ctrl, S.ord_hist);
+    hipLaunchKernelGGL(k_order_hist, dim3(nblk), dim3(ORD_THREADS), 0, s, S.start, S.end, (uint32_t)nb, per_block, cap, S.ovf_slot, S.ovf_bucket, S.ovf_nseg, (uint32_t)S.ovf_bucket.n - 1, S.ctrl, S.ord_hist);
     HIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORD_BINS), 0, s, S.ord_hist, S.ord_offs, nblk, S.ctrl, S.ovf_nseg, S.ovf_off, (uint32_t)S.cap_ovf - 1);
+    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORD_BINS), 0, s, S.ord_hist, S.ord_offs, nblk, S.ctrl, S.ovf_nseg, S.ovf_off, (uint32_t)S.ovf_bucket.n - 1);
     HIP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_order_scatter, dim3(nblk), dim3(ORD_THREADS), 0, s, S.start, S.end, (uint32_t)nb, per_block, S.ord_offs, S.order);
     HIP_LAUNCH_CHECK();
@@ -864,10 +839,10 @@ static void prepare_buckets(MsmWorkspace &S, size_t pairs, int c, int nsets, int
     // ping-pong sort: the result stays in whichever buffer the last radix pass wrote (no copy back)
     rocprim::double_buffer<uint32_t> dk(S.keys_a, S.keys_b), dv(S.vals_a, S.vals_b);
     HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, pairs, (unsigned)begin_bit, (unsigned)key_bits, s));
-    if (tmp_bytes > S.cap_tmp) { dfree(S.tmp); S.tmp = dmalloc(tmp_bytes); S.cap_tmp = tmp_bytes; }
-    HIP_CHECK(rocprim::radix_sort_pairs(S.tmp, tmp_bytes, dk, dv, pairs, (unsigned)begin_bit, (unsigned)key_bits, s));
+    S.tmp.grow(tmp_bytes);
+    HIP_CHECK(rocprim::radix_sort_pairs(S.tmp.p, tmp_bytes, dk, dv, pairs, (unsigned)begin_bit, (unsigned)key_bits, s));
 #ifdef ZKAES_MEASURE
-    if (knockin() & 1) HIP_CHECK(rocprim::radix_sort_pairs(S.tmp, tmp_bytes, dk, dv, pairs, (unsigned)begin_bit, (unsigned)key_bits, s));
+    if (knockin() & 1) HIP_CHECK(rocprim::radix_sort_pairs(S.tmp.p, tmp_bytes, dk, dv, pairs, (unsigned)begin_bit, (unsigned)key_bits, s));
 #endif
     S.sorted_keys = dk.current(); S.sorted_vals = dv.current();
     hipLaunchKernelGGL(k_bounds, dim3((unsigned)(((pairs + 3) / 4 + 255) / 256)), dim3(256), 0, s, S.sorted_keys, pairs, c, (uint32_t)nsets, S.start, S.end);
@@ -893,7 +868,7 @@ static std::vector<XYZZ<Fp<typename Law::Params>>> run_buckets(MsmWorkspace &S, 
 #ifdef ZKAES_MEASURE
     if (knockin() & 8) {        // (measurement builds only) one extra, untimed launch
         hipLaunchKernelGGL((k_accumulate<Law>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, s, bases, S.sorted_vals, S.start, S.end, S.order, (uint32_t)nb, cap,
-                           (A *)S.buckets, S.deferred, DEFERRED_CAP, S.deferred_count);
+                           (A *)S.buckets.p, S.deferred, DEFERRED_CAP, S.deferred_count);
         if constexpr (!Law::edwards) HIP_CHECK(hipMemsetAsync(S.deferred_count, 0, 8, s));
     }
 #endif
@@ -902,22 +877,22 @@ static std::vector<XYZZ<Fp<typename Law::Params>>> run_buckets(MsmWorkspace &S, 
     // measured in round 5 and dropped: the 64-byte lone call went from 74 to 105 ms, profiles/r05_lone_latency.md.)
     for (int rep = 0; rep < nrep; rep++) {
         const typename Law::Base *src = rep ? bases2 : bases;
-        HIP_CHECK(hipEventRecord(S.ev[2 * rep], s));          // every k_accumulate launch is bracketed and booked by itself (msm_stats: launches, points, pairs, ms)
+        HIP_CHECK(hipEventRecord((hipEvent_t)S.ev[2 * rep].h, s));          // every k_accumulate launch is bracketed and booked by itself (msm_stats: launches, points, pairs, ms)
         hipLaunchKernelGGL((k_accumulate<Law>), dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, s, src, S.sorted_vals, S.start, S.end, S.order, (uint32_t)nb, cap,
-                           (A *)S.buckets + rep * nb, S.deferred, DEFERRED_CAP, S.deferred_count);
+                           (A *)S.buckets.p + rep * nb, S.deferred, DEFERRED_CAP, S.deferred_count);
         HIP_LAUNCH_CHECK();
-        HIP_CHECK(hipEventRecord(S.ev[2 * rep + 1], s));
+        HIP_CHECK(hipEventRecord((hipEvent_t)S.ev[2 * rep + 1].h, s));
         // oversized buckets + deferred degenerate additions (none for uniformly distributed digits: every lane exits at once)
         hipLaunchKernelGGL((k_accumulate_tail<Law>), dim3((max_seg + 63) / 64), dim3(64), 0, s, src, S.sorted_vals, S.start, S.end, S.ctrl, S.ovf_bucket, S.ovf_off, max_seg, cap,
-                           (A *)S.ovf_partial + rep * S.cap_ovf, (A *)S.buckets + rep * nb, S.deferred, DEFERRED_CAP, S.deferred_count);
+                           (A *)S.ovf_partial.p + rep * S.ovf_bucket.n, (A *)S.buckets.p + rep * nb, S.deferred, DEFERRED_CAP, S.deferred_count);
         HIP_LAUNCH_CHECK();
     }
     if constexpr (!Law::edwards) for (int rep = 0; rep < nrep; rep++) {
         // overflow partials -> their buckets (overflow list entries <= buckets with more than `cap` pairs <= pairs / cap); the Edwards law's tail kernel does it itself
-        hipLaunchKernelGGL((k_fold_overflow<A>), dim3((max_seg + 63) / 64), dim3(64), 0, s, (A *)S.buckets + rep * nb, S.ctrl, S.ovf_bucket, S.ovf_off, max_seg, (const A *)S.ovf_partial + rep * S.cap_ovf);
+        hipLaunchKernelGGL((k_fold_overflow<A>), dim3((max_seg + 63) / 64), dim3(64), 0, s, (A *)S.buckets.p + rep * nb, S.ctrl, S.ovf_bucket, S.ovf_off, max_seg, (const A *)S.ovf_partial.p + rep * S.ovf_bucket.n);
         HIP_LAUNCH_CHECK();
     }
-    XYZZ<Fq> *res = (XYZZ<Fq> *)S.d_res;
+    XYZZ<Fq> *res = (XYZZ<Fq> *)S.h_res.dev;
     uint32_t segs = (1u << c) / RED_L1, groups = (segs + RED_L2 - 1) / RED_L2;
     [[maybe_unused]] int te_lgR = 0, te_lgC = 0;
     [[maybe_unused]] bool te_host_tail = false;
@@ -926,17 +901,17 @@ static std::vector<XYZZ<Fp<typename Law::Params>>> run_buckets(MsmWorkspace &S, 
 #endif
     {
     if constexpr (Law::edwards)
-        hipLaunchKernelGGL((k_reduce_l1_pair<A>), dim3((unsigned)((2 * segs * nsets + 63) / 64)), dim3(64), 0, s, (const A *)S.buckets, c, nsets, (A *)S.seg_s, (A *)S.seg_w);
+        hipLaunchKernelGGL((k_reduce_l1_pair<A>), dim3((unsigned)((2 * segs * nsets + 63) / 64)), dim3(64), 0, s, (const A *)S.buckets.p, c, nsets, (A *)S.seg_s.p, (A *)S.seg_w.p);
     else
-        hipLaunchKernelGGL((k_reduce_l1<A>), dim3((unsigned)((segs * nsets + 63) / 64)), dim3(64), 0, s, (const A *)S.buckets, c, nsets, (A *)S.seg_s, (A *)S.seg_w);
+        hipLaunchKernelGGL((k_reduce_l1<A>), dim3((unsigned)((segs * nsets + 63) / 64)), dim3(64), 0, s, (const A *)S.buckets.p, c, nsets, (A *)S.seg_s.p, (A *)S.seg_w.p);
     HIP_LAUNCH_CHECK();
     if constexpr (Law::edwards) {
         // Edwards law: plain row / column sums of the segment sums, then six small quad-cooperative workgroups per set (k_reduce_rc / k_reduce_terms above)
         const int lgG = c - 3 > 0 ? c - 3 : 0, lgC = (lgG + 1) / 2, lgR = lgG - lgC;
         if (lgC > 8) throw GpuError("msm: more than 2^19 buckets per set");
         const unsigned jobs = 2u * (1u << lgR) + (1u << lgC);
-        A *rc = (A *)S.partial, *part = rc + (size_t)nsets * jobs;
-        hipLaunchKernelGGL((k_reduce_rc<P>), dim3((unsigned)nsets * jobs), dim3(RQ_THREADS), 0, s, (const A *)S.seg_s, (const A *)S.seg_w, lgR, lgC, rc);
+        A *rc = (A *)S.partial.p, *part = rc + (size_t)nsets * jobs;
+        hipLaunchKernelGGL((k_reduce_rc<P>), dim3((unsigned)nsets * jobs), dim3(RQ_THREADS), 0, s, (const A *)S.seg_s.p, (const A *)S.seg_w.p, lgR, lgC, rc);
         HIP_LAUNCH_CHECK();
         te_host_tail = !dev_wsum_out && nsets <= 4;
         hipLaunchKernelGGL((k_reduce_terms<P>), dim3((unsigned)(RF_OUT * nsets)), dim3(RT_THREADS), 0, s, (const A *)rc, lgR, lgC, part, res, te_host_tail);
@@ -947,17 +922,17 @@ static std::vector<XYZZ<Fp<typename Law::Params>>> run_buckets(MsmWorkspace &S, 
         }
         te_lgR = lgR; te_lgC = lgC;
     } else {
-    hipLaunchKernelGGL((k_reduce_l2<A>), dim3(2u * (unsigned)((groups * nsets + 63) / 64)), dim3(64), 0, s, (const A *)S.seg_s, (const A *)S.seg_w, c, nsets, (A *)S.partial);
+    hipLaunchKernelGGL((k_reduce_l2<A>), dim3(2u * (unsigned)((groups * nsets + 63) / 64)), dim3(64), 0, s, (const A *)S.seg_s.p, (const A *)S.seg_w.p, c, nsets, (A *)S.partial.p);
     HIP_LAUNCH_CHECK();
     const uint32_t parts = 2 * groups;                 // two partials per group (k_reduce_l2's two roles)
     if (nsets == 1 && parts > 2048) {
         // one big bucket set: 256-partial blocks first, so the final LDS tree does not walk tens of thousands of partials serially
         uint32_t mid = (parts + 255) / 256;
-        hipLaunchKernelGGL((k_sum_tree<A>), dim3(mid), dim3(256), 0, s, (const A *)S.partial, parts, 256u, (A *)S.seg_s, 0u, 0u);
+        hipLaunchKernelGGL((k_sum_tree<A>), dim3(mid), dim3(256), 0, s, (const A *)S.partial.p, parts, 256u, (A *)S.seg_s.p, 0u, 0u);
         HIP_LAUNCH_CHECK();
-        hipLaunchKernelGGL((k_reduce_window<A>), dim3(1), dim3(256), 0, s, (const A *)S.seg_s, mid, res, dev_wsum_out);
+        hipLaunchKernelGGL((k_reduce_window<A>), dim3(1), dim3(256), 0, s, (const A *)S.seg_s.p, mid, res, dev_wsum_out);
     } else {
-        hipLaunchKernelGGL((k_reduce_window<A>), dim3((unsigned)nsets), dim3(256), 0, s, (const A *)S.partial, parts, res, dev_wsum_out);
+        hipLaunchKernelGGL((k_reduce_window<A>), dim3((unsigned)nsets), dim3(256), 0, s, (const A *)S.partial.p, parts, res, dev_wsum_out);
     }
     HIP_LAUNCH_CHECK();
     }
@@ -967,15 +942,15 @@ static std::vector<XYZZ<Fp<typename Law::Params>>> run_buckets(MsmWorkspace &S, 
     sync((stream_t)s);        // (sleeps in throughput mode) the window sums are in pinned host memory once the stream has drained: no copy launch
     if (Law::edwards && te_host_tail) {       // host tail of the Edwards reduction: six unweighted terms per set
         std::vector<XYZZ<Fq>> terms((size_t)nsets * RF_OUT);
-        memcpy(terms.data(), S.h_res, sizeof(XYZZ<Fq>) * terms.size());
+        memcpy(terms.data(), S.h_res.host, sizeof(XYZZ<Fq>) * terms.size());
         for (int i = 0; i < nsets; i++) ws[i] = reduce_host_tail<Fq>(terms.data() + (size_t)i * RF_OUT, te_lgR, te_lgC);
-    } else memcpy(ws.data(), S.h_res, sizeof(XYZZ<Fq>) * nsets);
+    } else memcpy(ws.data(), S.h_res.host, sizeof(XYZZ<Fq>) * nsets);
     if constexpr (!Law::edwards) {
         HIP_CHECK(hipMemcpyAsync(&n_deferred, S.deferred_count, 4, hipMemcpyDeviceToHost, s));
         sync((stream_t)s);
         if (n_deferred > DEFERRED_CAP) throw GpuError("msm: more than 2^20 degenerate additions (repeated base points); refusing to return a wrong sum");
     }
-    for (int rep = 0; rep < nrep; rep++) HIP_CHECK(hipEventElapsedTime(acc_ms + rep, S.ev[2 * rep], S.ev[2 * rep + 1]));
+    for (int rep = 0; rep < nrep; rep++) HIP_CHECK(hipEventElapsedTime(acc_ms + rep, (hipEvent_t)S.ev[2 * rep].h, (hipEvent_t)S.ev[2 * rep + 1].h));
     (void)n_points;
     return ws;
 }
@@ -1476,8 +1451,8 @@ static void partition_buckets(MsmWorkspace &S, const Fr *scal1, size_t n1, size_
     const int B = L.c_hi - 1;                                         // bucket bits
     const uint32_t nbin = 1u << (B - PART_FINE_BITS), G = PART_GRID;
     const size_t n = n1 + n2, nb = (size_t)1 << B, nh = (size_t)nbin * G + 1;
-    if (n > S.cap_canon) { dfree(S.canon); S.canon = (uint32_t *)dmalloc(n * Fr::N * 4); S.cap_canon = n; }
-    if (nh > S.cap_part) { dfree(S.part_hist); dfree(S.part_offs); S.part_hist = (uint32_t *)dmalloc(nh * 4); S.part_offs = (uint32_t *)dmalloc(nh * 4); S.cap_part = nh; }
+    S.canon.grow(n * Fr::N);
+    grow_together({nh, nh}, S.part_hist, S.part_offs);
 #ifdef ZKAES_MEASURE
     for (int rep = (knockin() & 1) ? 0 : 1; rep < 2; rep++)
 #endif
@@ -1485,13 +1460,13 @@ static void partition_buckets(MsmWorkspace &S, const Fr *scal1, size_t n1, size_
     hipLaunchKernelGGL((k_part_hist<Fr>), dim3(G), dim3(PART_THREADS), 0, s, scal1, (uint32_t)n1, scal2, (uint32_t)n2, L, nbin, S.canon, S.part_hist);
     HIP_LAUNCH_CHECK();
     size_t tb = 0;
-    HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, S.part_hist, S.part_offs, 0u, nh, rocprim::plus<uint32_t>(), s));
-    if (tb > S.cap_tmp) { dfree(S.tmp); S.tmp = dmalloc(tb); S.cap_tmp = tb; }
-    HIP_CHECK(rocprim::exclusive_scan(S.tmp, tb, S.part_hist, S.part_offs, 0u, nh, rocprim::plus<uint32_t>(), s));
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, S.part_hist.p, S.part_offs.p, 0u, nh, rocprim::plus<uint32_t>(), s));
+    S.tmp.grow(tb);
+    HIP_CHECK(rocprim::exclusive_scan(S.tmp.p, tb, S.part_hist.p, S.part_offs.p, 0u, nh, rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL((k_part_scatter<Fr::N>), dim3(G), dim3(PART_THREADS), 0, s, (const uint32_t *)S.canon, (uint32_t)n, (uint32_t)n1, L, (uint32_t)off1, (uint32_t)off2, (uint32_t)stride, nbin,
-                       (const uint32_t *)S.part_offs, S.vals_a, (uint16_t *)S.keys_a);
+                       (const uint32_t *)S.part_offs, S.vals_a, (uint16_t *)S.keys_a.p);
     HIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_part_fine, dim3(nbin), dim3(PART_FINE_THREADS), 0, s, (const uint32_t *)S.part_offs, G, (const uint32_t *)S.vals_a, (const uint16_t *)S.keys_a, S.vals_b, S.start, S.end);
+    hipLaunchKernelGGL(k_part_fine, dim3(nbin), dim3(PART_FINE_THREADS), 0, s, (const uint32_t *)S.part_offs, G, (const uint32_t *)S.vals_a, (const uint16_t *)S.keys_a.p, S.vals_b, S.start, S.end);
     HIP_LAUNCH_CHECK();
     }
     S.sorted_vals = S.vals_b; S.sorted_keys = nullptr;
@@ -1729,7 +1704,7 @@ static bool class_sum_impl(MsmWorkspace *ws_, const typename Law::Base *bases, c
     // scratch carved from the bucket array (sized for >= 2 * chunks + 2 * mid + 2 points by any prior msm of this context, else grown here)
     size_t need_buckets = 2 * (size_t)chunks + 2 * mid + 8;
     ensure_scratch(S, 1, need_buckets, 0);
-    A *p1 = (A *)S.buckets, *p2 = p1 + chunks, *m1 = p2 + chunks, *m2 = m1 + mid, *fin = m2 + mid;
+    A *p1 = (A *)S.buckets.p, *p2 = p1 + chunks, *m1 = p2 + chunks, *m2 = m1 + mid, *fin = m2 + mid;
     hipLaunchKernelGGL((k_class_partials<Law>), dim3((chunks + 63) / 64), dim3(64), 0, s, bases, vals, (uint32_t)n, p1, p2, S.ctrl + 3);
     HIP_LAUNCH_CHECK();
     (void)p2; (void)m2;          // (class 2's arrays follow class 1's at the strides below)
@@ -1740,12 +1715,12 @@ static bool class_sum_impl(MsmWorkspace *ws_, const typename Law::Base *bases, c
         hipLaunchKernelGGL((k_sum_tree<A>), dim3(mid, 2), dim3(256), 0, s, (const A *)p1, chunks, 256u, m1, chunks, mid); HIP_LAUNCH_CHECK();
         hipLaunchKernelGGL((k_sum_tree<A>), dim3(1, 2), dim3(256), 0, s, (const A *)m1, mid, mid, fin, mid, 1u); HIP_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((k_class_result<A>), dim3(1), dim3(64), 0, s, (const A *)fin, S.ctrl + 3, (XYZZ<Fq> *)S.d_res); HIP_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_class_result<A>), dim3(1), dim3(64), 0, s, (const A *)fin, S.ctrl + 3, (XYZZ<Fq> *)S.h_res.dev); HIP_LAUNCH_CHECK();
     XYZZ<Fq> r[2];
     uint32_t flags = 0;
     sync((stream_t)s);        // (sleeps in throughput mode) results are in pinned host memory once the stream has drained
-    memcpy(r, S.h_res, sizeof r);
-    memcpy(&flags, (const char *)S.h_res + sizeof r, 4);
+    memcpy(r, S.h_res.host, sizeof r);
+    memcpy(&flags, (const char *)S.h_res.host + sizeof r, 4);
     if (flags) return false;          // a value outside [-2, 2] or a degenerate addition: the caller falls back to the generic MSM
     oplog_msm(n, OP_MSM_CLASS_SUM);
     XYZZ<Fq> t = r[1].dbl();

@@ -161,7 +161,7 @@ struct Tables {
         const int lg = cache_key(lg_);
         auto it = m.find(lg);
         if (it != m.end()) return it->second;
-        Fr *d = (Fr *)dmalloc((size_t)(count ? count : 1) * sizeof(Fr));
+        Fr *d = (Fr *)dmalloc((size_t)(count ? count : 1) * sizeof(Fr));      // lives for the life of the process (cached per size)
         if (count) {
             hipLaunchKernelGGL((k_fill_powers<Fr>), dim3((count + 255) / 256), dim3(256), 0, 0, w, count, d);
             HIP_LAUNCH_CHECK();
@@ -181,7 +181,7 @@ const Fp29<typename Fr::Params> *twiddles29(std::map<int, Fp29<typename Fr::Para
     const int lg = Tables<Fr>::cache_key(lg_);
     auto it = m.find(lg);
     if (it != m.end()) return it->second;
-    G *d = (G *)dmalloc((size_t)(count ? count : 1) * sizeof(G));
+    G *d = (G *)dmalloc((size_t)(count ? count : 1) * sizeof(G));      // lives for the life of the process (cached per size)
     if (count) {
         hipLaunchKernelGGL((k_twiddles29<Fr>), dim3((count + 255) / 256), dim3(256), 0, 0, std_table, count, d);
         HIP_LAUNCH_CHECK();
@@ -288,26 +288,24 @@ void ntt_coset(Fr *dst, const Fr *src, size_t in_len, int lg, bool inverse, int 
 
 // g^i R' for i < n as reduced-radix limbs: the scaling table of a coset whose generator is NOT a root of unity (the field's multiplicative generator in round 3)
 template <class Fr>
-void *coset_power_table(const Fr &g, size_t n, stream_t s_) {
+DevPtr<void> coset_power_table(const Fr &g, size_t n, stream_t s_) {
     using G = Fp29<typename Fr::Params>;
     hipStream_t s = (hipStream_t)s_;
     DevPtr<Fr> tmp(n);
-    DevPtr<G> out(n);
+    DevPtr<void> out(n * sizeof(G));
     hipLaunchKernelGGL((k_fill_powers<Fr>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, (uint32_t)n, tmp.get());
     HIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_twiddles29<Fr>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const Fr *)tmp.get(), (uint32_t)n, out.get());
+    hipLaunchKernelGGL((k_twiddles29<Fr>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const Fr *)tmp.get(), (uint32_t)n, (G *)out.p);
     HIP_LAUNCH_CHECK();
     sync(s_);
-    G *r = out.p;
-    out.p = nullptr;              // ownership passes to the caller (free with dfree)
-    return r;
+    return out;
 }
 template <class Fr>
 void ntt_scaled(Fr *dst, const Fr *src, size_t in_len, int lg, bool inverse, const void *table, stream_t s) {
     if (!table) throw GpuError("ntt_scaled: null table");
     ntt_impl<Fr>(dst, src, in_len, lg, inverse, 0, 0, s, table);
 }
-template void *coset_power_table<Fr377>(const Fr377 &, size_t, stream_t);
+template DevPtr<void> coset_power_table<Fr377>(const Fr377 &, size_t, stream_t);
 template void ntt_scaled<Fr377>(Fr377 *, const Fr377 *, size_t, int, bool, const void *, stream_t);
 template void ntt<Fr377>(Fr377 *, const Fr377 *, size_t, int, bool, stream_t);
 template void ntt_batch<Fr377>(const NttJob<Fr377> *, int, size_t, int, bool, int, stream_t);

@@ -32,7 +32,7 @@ void upload_sbox(const uint8_t table[256]) {
     HIP_CHECK(hipGetDevice(&d));
     if (d < 0 || d >= 64) throw GpuError("device ordinal out of range");
     std::lock_guard<std::mutex> g(g_sbox_mu);
-    if (!g_sbox_dev[d]) g_sbox_dev[d] = (uint8_t *)dmalloc(256);
+    if (!g_sbox_dev[d]) g_sbox_dev[d] = (uint8_t *)dmalloc(256);      // lives for the life of the process (one table per device)
     HIP_CHECK(hipMemcpy(g_sbox_dev[d], table, 256, hipMemcpyHostToDevice));
 }
 

@@ -45,11 +45,7 @@ struct DeviceScope {
     explicit DeviceScope(int device) noexcept { try { prev = gpu::current_device(); if (prev != device) gpu::set_device(device); else prev = -1; } catch (...) { prev = -1; } }
     ~DeviceScope() { if (prev >= 0) { try { gpu::set_device(prev); } catch (...) {} } }
 };
-struct DevBuf {
-    F *p = nullptr; size_t n = 0;
-    void alloc(size_t count) { n = count; p = (F *)gpu::dmalloc(count * sizeof(F)); }
-    void release() { gpu::dfree(p); p = nullptr; }
-};
+using gpu::DevPtr;
 struct KzgRand { bool hiding = false; Fr b[3]; };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -70,22 +66,22 @@ struct UniversalSrs {
     pairing::G2Affine h, beta_h;
     G1A gamma_powers[3];
     FixedBaseHost gamma_tab[3];              // host comb tables of the points multiplied by per-proof blinding scalars
-    SrsPoint *d_points = nullptr;
+    DevPtr<SrsPoint> d_points;
     double build_s = 0;
     bool tables() const { return n_tab > 1; }
     uint64_t bytes() const { return (uint64_t)n_tab * stride * sizeof(SrsPoint); }
-    ~UniversalSrs() { DeviceScope on(device); gpu::dfree(d_points); }
+    ~UniversalSrs() { DeviceScope on(device); d_points.reset(); }      // (released HERE, on its own device: members go after this body, when the caller's device is back)
 };
 // Lagrange-basis points over H (per |H| and |X|, shared the same way): L_k(beta) G for z_A, z_B; L_k(beta)/v_X(beta) G (zero on X) for w; P_j for the public-input part
 // of w; v_H(beta) G and (v_H/v_X)(beta) G for the blinding terms
 struct LagrangeSrs {
     int device = 0;
     size_t n = 0, m = 0;
-    SrsPoint *d_lag_h = nullptr, *d_lag_w = nullptr;
+    DevPtr<SrsPoint> d_lag_h, d_lag_w;
     std::vector<G1A> lag_pj;
     G1A lag_vh, lag_vw;
     FixedBaseHost lag_vh_tab, lag_vw_tab;
-    ~LagrangeSrs() { DeviceScope on(device); gpu::dfree(d_lag_h); gpu::dfree(d_lag_w); }
+    ~LagrangeSrs() { DeviceScope on(device); d_lag_h.reset(); d_lag_w.reset(); }      // (as ~UniversalSrs)
 };
 namespace {
 std::mutex g_srs_mu;                          // serializes SRS construction: two keys synthesized concurrently must not both build 31 GB of tables
@@ -139,15 +135,15 @@ static std::shared_ptr<UniversalSrs> acquire_srs(size_t max_degree, bool want_ta
     {
         // copy j is made from copy j - 1 in a two-slot staging buffer (standard form) and converted into its place: the setup peak is the final array
         // + two staging copies, not twice the final array
-        struct Stage { G1A *p[2] = {nullptr, nullptr}; ~Stage() { gpu::dfree(p[0]); gpu::dfree(p[1]); } } stage;
-        stage.p[0] = (G1A *)gpu::dmalloc(S->stride * sizeof(G1A));
-        if (n_tab > 1) stage.p[1] = (G1A *)gpu::dmalloc(S->stride * sizeof(G1A));
-        gpu::fixed_base_powers<Bls377>(stage.p[0], S->g, S->beta, 0, S->stride, stream);
-        S->d_points = (SrsPoint *)gpu::dmalloc(n_tab * S->stride * sizeof(SrsPoint));
-        srs_convert(S->d_points, stage.p[0], S->stride, stream);
+        DevPtr<G1A> stage[2];
+        stage[0].alloc(S->stride);
+        if (n_tab > 1) stage[1].alloc(S->stride);
+        gpu::fixed_base_powers<Bls377>(stage[0], S->g, S->beta, 0, S->stride, stream);
+        S->d_points.alloc(n_tab * S->stride);
+        srs_convert(S->d_points, stage[0], S->stride, stream);
         for (size_t j = 1; j < n_tab; j++) {
-            gpu::table_next<Bls377>(stage.p[j & 1], stage.p[(j - 1) & 1], S->stride, S->table_c, (int)j, stream);
-            srs_convert(S->d_points + j * S->stride, stage.p[j & 1], S->stride, stream);
+            gpu::table_next<Bls377>(stage[j & 1], stage[(j - 1) & 1], S->stride, S->table_c, (int)j, stream);
+            srs_convert(S->d_points + j * S->stride, stage[j & 1], S->stride, stream);
         }
         gpu::sync(stream);
     }
@@ -167,13 +163,12 @@ static std::shared_ptr<LagrangeSrs> acquire_lagrange(const UniversalSrs &U, size
     Lg->device = device; Lg->n = n; Lg->m = m;
     // With the (public, test_rng-derived) trapdoor the Lagrange-basis points are direct fixed-base products; a trapdoor-free universal SRS
     // yields the same points through an inverse FFT over the group elements powers_of_g[0..|H|) (one time per |H|).
-    struct Tmp { void *p[4] = {nullptr, nullptr, nullptr, nullptr}; ~Tmp() { for (auto q : p) gpu::dfree(q); } } tmp;
-    F *d_lag = (F *)(tmp.p[0] = gpu::dmalloc(n * sizeof(F))), *d_lagw = (F *)(tmp.p[1] = gpu::dmalloc(n * sizeof(F)));
+    DevPtr<F> d_lag(n), d_lagw(n);
     gpu::lagrange_scalars(d_lag, d_lagw, gpu::domain_elements<F>(lg_n), U.beta, (uint32_t)n, (uint32_t)m, stream);
-    G1A *pts = (G1A *)(tmp.p[2] = gpu::dmalloc(n * sizeof(G1A)));
-    auto to28 = [&](const F *sc, SrsPoint *&dst) {
+    DevPtr<G1A> pts(n);
+    auto to28 = [&](const F *sc, DevPtr<SrsPoint> &dst) {
         gpu::fixed_base_scalars<Bls377>(pts, U.g, sc, n, stream);
-        dst = (SrsPoint *)gpu::dmalloc(n * sizeof(SrsPoint));
+        dst.alloc(n);
         srs_convert(dst, pts, n, stream);
         gpu::sync(stream);
     };
@@ -187,7 +182,7 @@ static std::shared_ptr<LagrangeSrs> acquire_lagrange(const UniversalSrs &U, size
     for (size_t j = 0; j < m; j++) { den[j] = U.beta - e; pj[j] = e; e = e * gx; }
     { std::vector<Fr> pre(m); Fr acc = Fr::one(); for (size_t j = 0; j < m; j++) { pre[j] = acc; acc = acc * den[j]; } Fr inv = acc.inverse(); for (size_t j = m; j-- > 0;) { Fr d = den[j]; den[j] = inv * pre[j]; inv = inv * d; } }
     for (size_t j = 0; j < m; j++) pj[j] = pj[j] * den[j] * (cm - cn) * vx_inv;
-    F *d_pj = (F *)(tmp.p[3] = gpu::dmalloc(m * sizeof(F)));
+    DevPtr<F> d_pj(m);
     gpu::h2d(d_pj, pj.data(), m * sizeof(F), stream);
     gpu::fixed_base_scalars<Bls377>(pts, U.g, d_pj, m, stream);
     Lg->lag_pj.resize(m);
@@ -236,51 +231,42 @@ struct LaneWorker {
     }
     void submit(std::function<void()> f) { { std::lock_guard<std::mutex> g(mu); q.push_back(std::move(f)); } cv.notify_one(); }
 };
+// Members are destroyed in reverse order of declaration, and that order is all the teardown there is: the lanes come last, behind every buffer their jobs can touch
+// (inside a lane the worker thread is joined before the lane's stream and workspace go); the main stream and workspace come first and so go last.
 struct ProverContext {
     std::mutex in_use;                                // one proof at a time per context: concurrent callers of one key queue up here
-    gpu::stream_t stream = nullptr;
-    gpu::MsmWorkspace *msm_ws = nullptr;
-    uint8_t *d_trace = nullptr, *d_z = nullptr, *d_msg = nullptr, *d_key = nullptr;
-    void *d_rng = nullptr; size_t rng_bytes = 0;      // scratch of the device-side ChaCha12 / Fr::rand stream
-    int8_t *d_cls[3] = {nullptr, nullptr, nullptr};   // small-integer evaluation classes of w, z_A, z_B on H (Lagrange-basis commitments)
-    DevBuf za_ev, zb_ev, x_poly, x_tmp, x_evals, tmp_n, ra_ev, ra_poly, zpoly, t_partial;
-    DevBuf poly[9];                    // w z_a z_b mask t g_1 h_1 g_2 h_2
+    gpu::StreamGuard stream;
+    gpu::WorkspaceGuard msm_ws;
+    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key;
+    DevPtr<void> d_rng;                               // scratch of the device-side ChaCha12 / Fr::rand stream
+    DevPtr<int8_t> d_cls[3];                          // small-integer evaluation classes of w, z_A, z_B on H (Lagrange-basis commitments)
+    DevPtr<F> za_ev, zb_ev, x_poly, x_tmp, x_evals, tmp_n, ra_ev, ra_poly, zpoly, t_partial;
+    DevPtr<F> poly[9];                 // w z_a z_b mask t g_1 h_1 g_2 h_2
     size_t poly_len[9] = {0};
-    DevBuf e[5], f_poly, acc, wit, wit2, scratch;
+    DevPtr<F> e[5], f_poly, acc, wit, wit2, scratch;
     ProverTimings timings;
+    DevPtr<F> acc_b, wit_b, wit2_b, scratch_b;          // second set of opening buffers (the two openings run side by side on the latency path)
+    DevPtr<F> scratch_c; gpu::EventGuard ev_aux{nullptr};      // ... and the calling thread divides g_2 by (X - gamma) on the main stream beside them: its own division scratch + the event the gamma opening waits for
+    bool throughput = false;           // set per proof: several proofs in flight (chunked / batch calls) -> window tables; a lone encrypt() call -> per-window buckets
     // MSM lanes: lane 0 = (stream, msm_ws) above; lanes 1..4 (own stream + MSM scratch, created on first use) let a LONE encrypt() call run the independent
     // commitments of a round side by side, each started as soon as ITS polynomial exists (latency path only: with several proofs in flight the chip is already full)
     static constexpr int N_LANES = 5;
-    struct Lane { gpu::stream_t stream = nullptr; gpu::MsmWorkspace *ws = nullptr; void *ready = nullptr; /* event: the lane's input exists on the main stream */ std::unique_ptr<LaneWorker> worker; };
+    struct Lane {
+        gpu::stream_t stream = nullptr; gpu::MsmWorkspace *ws = nullptr;      // what the lane's jobs use: lane 0 views the main stream and workspace, lanes 1.. their own
+        gpu::StreamGuard own_stream{nullptr}; gpu::WorkspaceGuard own_ws{nullptr};
+        gpu::EventGuard ready{nullptr};               // the lane's input exists on the main stream
+        std::unique_ptr<LaneWorker> worker;           // (last: joined first)
+    };
     // (lane 3 is the background lane: the early mask commitment of round 1 runs there, under the witness generation on the main stream)
     Lane lane[N_LANES];
-    DevBuf acc_b, wit_b, wit2_b, scratch_b;             // second set of opening buffers (the two openings run side by side on the latency path)
-    DevBuf scratch_c; void *ev_aux = nullptr;           // ... and the calling thread divides g_2 by (X - gamma) on the main stream beside them: its own division scratch + the event the gamma opening waits for
-    bool throughput = false;           // set per proof: several proofs in flight (chunked / batch calls) -> window tables; a lone encrypt() call -> per-window buckets
-    ProverContext() { stream = gpu::stream_create(); msm_ws = gpu::msm_workspace_create(); lane[0].stream = stream; lane[0].ws = msm_ws; }
+    ProverContext() { lane[0].stream = stream; lane[0].ws = msm_ws; }
     void ensure_lanes() {
-        for (int i = 1; i < N_LANES; i++) if (!lane[i].worker) {        // guarded by the LAST member created; leftovers of an attempt that threw half way are released first (advisor r05)
+        for (int i = 1; i < N_LANES; i++) if (!lane[i].worker) {        // the worker is made last: a lane whose creation threw half way is made again, and the owners drop what that attempt left
             Lane &L = lane[i];
-            gpu::msm_workspace_destroy(L.ws); L.ws = nullptr;
-            gpu::event_destroy(L.ready); L.ready = nullptr;
-            gpu::stream_destroy(L.stream); L.stream = nullptr;
-            L.stream = i == 3 ? gpu::stream_create_background() : gpu::stream_create(); L.ws = gpu::msm_workspace_create(); L.ready = gpu::event_create();
+            L.own_stream = gpu::StreamGuard(i == 3 ? gpu::stream_create_background() : gpu::stream_create()); L.own_ws = gpu::WorkspaceGuard(); L.ready = gpu::EventGuard();
+            L.stream = L.own_stream; L.ws = L.own_ws;
             L.worker.reset(new LaneWorker());
         }
-    }
-    ~ProverContext() {
-        gpu::dfree(d_trace); gpu::dfree(d_z); gpu::dfree(d_msg); gpu::dfree(d_key);
-        for (auto p : d_cls) gpu::dfree(p);
-        gpu::dfree(d_rng);
-        for (DevBuf *b : {&za_ev, &zb_ev, &x_poly, &x_tmp, &x_evals, &tmp_n, &ra_ev, &ra_poly, &zpoly, &t_partial, &f_poly, &acc, &wit, &wit2, &scratch}) b->release();
-        for (auto &b : poly) b.release();
-        for (auto &b : e) b.release();
-        for (DevBuf *b : {&acc_b, &wit_b, &wit2_b, &scratch_b, &scratch_c}) b->release();
-        gpu::event_destroy(ev_aux);
-        for (int i = 1; i < N_LANES; i++) lane[i].worker.reset();        // (joins the lane threads before their streams go)
-        for (int i = 1; i < N_LANES; i++) if (lane[i].stream) { gpu::msm_workspace_destroy(lane[i].ws); gpu::stream_destroy(lane[i].stream); gpu::event_destroy(lane[i].ready); }
-        gpu::msm_workspace_destroy(msm_ws);
-        gpu::stream_destroy(stream);
     }
 };
 
@@ -288,8 +274,6 @@ class ProvingKeyImpl {
   public:
     VerifyingKey vk;
     Circuit circuit;
-    std::vector<std::unique_ptr<ProverContext>> ctxs;
-    std::mutex ctx_mu;
     size_t message_len = 0;
     size_t n = 0, k = 0, m = 0;       // |H|, |K|, |X|
     int lg_n = 0, lg_k = 0, lg_m = 0;
@@ -313,30 +297,22 @@ class ProvingKeyImpl {
     std::atomic<size_t> n_contexts{0};          // proofs in flight per multi-proof call on this key (zkaes_pk_set_contexts); 0 = the process default
     double setup_srs_s = 0, setup_total_s = 0;  // how long key synthesis spent building (not sharing) the SRS, and in total
     // device: circuit
-    uint32_t *d_desc = nullptr, *d_sbox_in = nullptr, *d_sbox_tmpl = nullptr;
-    uint32_t *d_a_rowptr = nullptr, *d_a_col = nullptr, *d_b_rowptr = nullptr, *d_b_col = nullptr;
-    int64_t *d_a_coeff = nullptr, *d_b_coeff = nullptr;
-    uint32_t *d_t_colptr = nullptr, *d_t_seg_start = nullptr, *d_t_seg_end = nullptr, *d_t_row = nullptr; uint8_t *d_t_mat = nullptr; int64_t *d_t_coeff = nullptr;
+    DevPtr<uint32_t> d_desc, d_sbox_in, d_sbox_tmpl;
+    DevPtr<uint32_t> d_a_rowptr, d_a_col, d_b_rowptr, d_b_col;
+    DevPtr<int64_t> d_a_coeff, d_b_coeff;
+    DevPtr<uint32_t> d_t_colptr, d_t_seg_start, d_t_seg_end, d_t_row; DevPtr<uint8_t> d_t_mat; DevPtr<int64_t> d_t_coeff;
     uint32_t t_nseg = 0, t_nheavy = 0;
-    uint32_t *d_t_heavy = nullptr;
-    uint32_t *d_ix_ci = nullptr, *d_ix_ri = nullptr;     // per entry of K: the indices into H of its "row" / "col" domain elements (zero past the joint matrix's non-zeros): round 3 gathers through them
+    DevPtr<uint32_t> d_t_heavy;
+    DevPtr<uint32_t> d_ix_ci, d_ix_ri;     // per entry of K: the indices into H of its "row" / "col" domain elements (zero past the joint matrix's non-zeros): round 3 gathers through them
     // device: index polynomials (evaluations on K and coefficients); order row col a_val b_val c_val row_col
-    DevBuf ix_ev[6], ix_co[6], ix_cs[6];       // index polynomials: values on K, coefficients, values on the coset g K (round 3)
+    DevPtr<F> ix_ev[6], ix_co[6], ix_cs[6];       // index polynomials: values on K, coefficients, values on the coset g K (round 3)
     Fr coset_g, coset_g_inv, coset_vk_inv;     // g = the field's multiplicative generator, 1 / (g^|K| - 1)
-    void *coset_tab = nullptr, *coset_tab_inv = nullptr;   // g^i and g^-i, i < |K|, in the NTT's reduced-radix form: round 3's coset scalings ride on its two transforms
+    DevPtr<void> coset_tab, coset_tab_inv;   // g^i and g^-i, i < |K|, in the NTT's reduced-radix form: round 3's coset scalings ride on its two transforms
     ProverTimings last_timings;
 
-    ~ProvingKeyImpl() {
-        gpu::dfree(coset_tab); gpu::dfree(coset_tab_inv);
-        gpu::dfree(d_desc); gpu::dfree(d_sbox_in); gpu::dfree(d_sbox_tmpl);
-        gpu::dfree(d_a_rowptr); gpu::dfree(d_a_col); gpu::dfree(d_b_rowptr); gpu::dfree(d_b_col); gpu::dfree(d_a_coeff); gpu::dfree(d_b_coeff);
-        gpu::dfree(d_ix_ci); gpu::dfree(d_ix_ri);
-        gpu::dfree(d_t_heavy); gpu::dfree(d_t_colptr); gpu::dfree(d_t_seg_start); gpu::dfree(d_t_seg_end); gpu::dfree(d_t_row); gpu::dfree(d_t_mat); gpu::dfree(d_t_coeff);
-        for (auto &b : ix_ev) b.release();
-        for (auto &b : ix_co) b.release();
-        for (auto &b : ix_cs) b.release();
-        ctxs.clear();
-    }
+    std::mutex ctx_mu;
+    std::vector<std::unique_ptr<ProverContext>> ctxs;      // (the last member: the contexts and their lane threads go first)
+
     // context i, created on first use (workspace allocation happens outside any timed region when callers warm up)
     ProverContext &context(size_t i) {
         gpu::set_device(device);
@@ -351,10 +327,10 @@ class ProvingKeyImpl {
     void alloc_workspace(ProverContext &cx) {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
-        cx.d_trace = (uint8_t *)gpu::dmalloc(c.trace_bytes + 64); cx.d_z = (uint8_t *)gpu::dmalloc(c.num_variables() + 64);
-        cx.d_msg = (uint8_t *)gpu::dmalloc(std::max<size_t>(message_len, 16)); cx.d_key = (uint8_t *)gpu::dmalloc(16);
-        for (auto &p : cx.d_cls) p = (int8_t *)gpu::dmalloc(n + 64);
-        { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.rng_bytes = (ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20); cx.d_rng = gpu::dmalloc(cx.rng_bytes); }
+        cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(16);
+        for (auto &p : cx.d_cls) p.alloc(n + 64);
+        { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
         cx.zpoly.alloc(n + 1); cx.t_partial.alloc(t_nseg + 1);
         size_t caps[9] = {n + 1, n + 1, n + 1, 3 * n, n, n, 3 * n, k, k + 1};
@@ -367,8 +343,8 @@ class ProvingKeyImpl {
         cx.acc.alloc(std::max(3 * n, k) + 1); cx.wit.alloc(std::max(3 * n, k) + 1); cx.wit2.alloc(std::max(n, k) + 1); cx.scratch.alloc(std::max(8 + 3 * gpu::poly_eval_scratch(n + 1) + gpu::poly_eval_scratch(k), gpu::divide_by_linear_scratch(std::max(3 * n, k) + 1)));
     }
 
-    template <class T> static T *upload(const std::vector<T> &v, gpu::stream_t s) {
-        T *d = (T *)gpu::dmalloc(v.size() * sizeof(T));
+    template <class T> static DevPtr<T> upload(const std::vector<T> &v, gpu::stream_t s) {
+        DevPtr<T> d(v.size());
         gpu::h2d(d, v.data(), v.size() * sizeof(T), s);
         return d;
     }
@@ -636,29 +612,28 @@ void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lit
     for (int i = 0; i < 6; i++) { ix_ev[i].alloc(k); ix_co[i].alloc(k); }
     {
         j_ci.resize(k, 0u); j_ri.resize(k, 0u);           // (entries past the non-zeros: elems[0], as index_evals pads row / col)
-        uint32_t *d_ci = upload(j_ci, stream), *d_ri = upload(j_ri, stream);
-        int64_t *d_ja = upload(j_a.empty() ? std::vector<int64_t>{0} : j_a, stream), *d_jb = upload(j_b.empty() ? std::vector<int64_t>{0} : j_b, stream), *d_jc = upload(j_c.empty() ? std::vector<int64_t>{0} : j_c, stream);
+        d_ix_ci = upload(j_ci, stream); d_ix_ri = upload(j_ri, stream);
+        DevPtr<int64_t> d_ja = upload(j_a.empty() ? std::vector<int64_t>{0} : j_a, stream), d_jb = upload(j_b.empty() ? std::vector<int64_t>{0} : j_b, stream), d_jc = upload(j_c.empty() ? std::vector<int64_t>{0} : j_c, stream);
         const F *elems = gpu::domain_elements<F>(lg_n);
         // order: 0 row, 1 col, 2 a_val, 3 b_val, 4 c_val, 5 row_col ; ix_co[0] doubles as the batch-inverse scratch
-        gpu::index_evals(ix_ev[0].p, ix_ev[1].p, ix_ev[5].p, ix_ev[2].p, ix_ev[3].p, ix_ev[4].p, ix_co[0].p, d_ci, d_ri, d_ja, d_jb, d_jc, nnz, k, elems, (uint32_t)n, stream);
+        gpu::index_evals(ix_ev[0].p, ix_ev[1].p, ix_ev[5].p, ix_ev[2].p, ix_ev[3].p, ix_ev[4].p, ix_co[0].p, d_ix_ci, d_ix_ri, d_ja, d_jb, d_jc, nnz, k, elems, (uint32_t)n, stream);
         for (int i = 0; i < 6; i++) gpu::ntt<F>(ix_co[i].p, ix_ev[i].p, k, lg_k, true, stream);
         gpu::sync(stream);
-        d_ix_ci = d_ci; d_ix_ri = d_ri;
-        gpu::dfree(d_ja); gpu::dfree(d_jb); gpu::dfree(d_jc);
     }
     for (int i = 0; i < 6; i++) vk.index_comms[i] = msm_powers(*cx0, cx0->lane[0], false, 0, ix_co[i].p, k).to_affine();
     {   // values of the index polynomials on the coset g K, once per key: round 3 then needs no transform for a(X) and b(X)
         for (int i = 0; i < 8; i++) coset_g.l[i] = FR377_GEN_MONT[i];
         coset_g_inv = coset_g.inverse();
         coset_vk_inv = (coset_g.pow_u64(k) - Fr::one()).inverse();
-        F *tmp = (F *)gpu::dmalloc(k * sizeof(F));
-        for (int i = 0; i < 6; i++) {
-            ix_cs[i].alloc(k);
-            gpu::coset_scale(tmp, ix_co[i].p, coset_g, k, k, stream);
-            gpu::ntt<F>(ix_cs[i].p, tmp, k, lg_k, false, stream);
+        {
+            DevPtr<F> tmp(k);
+            for (int i = 0; i < 6; i++) {
+                ix_cs[i].alloc(k);
+                gpu::coset_scale(tmp, ix_co[i].p, coset_g, k, k, stream);
+                gpu::ntt<F>(ix_cs[i].p, tmp, k, lg_k, false, stream);
+            }
+            gpu::sync(stream);
         }
-        gpu::sync(stream);
-        gpu::dfree(tmp);
         coset_tab = gpu::coset_power_table<F>(coset_g, k, stream);
         coset_tab_inv = gpu::coset_power_table<F>(coset_g_inv, k, stream);
     }
@@ -684,7 +659,7 @@ void ProvingKeyImpl::prove_round1(ProofRun &R) {
     for (auto &r : R.rhos) r = R.zk.rand_field<Fr>();
     {   // mask polynomial: degree 3|H| + 2 zk_bound - 3, sum over H forced to zero.  The 3|H| coefficients are the next 3|H| Fr::rand draws
         // of the prover RNG: generated on the device from the same ChaCha12 key stream, then the host RNG skips past them.
-        uint64_t next = gpu::chacha_field_stream(cx.poly[3].p, 3 * n, R.zk.key_words(), R.zk.rounds(), R.zk.word_pos(), cx.d_rng, cx.rng_bytes, s);
+        uint64_t next = gpu::chacha_field_stream(cx.poly[3].p, 3 * n, R.zk.key_words(), R.zk.rounds(), R.zk.word_pos(), cx.d_rng, cx.d_rng.n, s);
         R.zk.set_word_pos(next);
         gpu::mask_fixup(cx.poly[3].p, n, s);
         cx.poly_len[3] = 3 * n;
@@ -884,10 +859,9 @@ void ProvingKeyImpl::prove_open(ProofRun &R) {
     auto host_divide_by_linear = [](Fr q[2], const Fr p[3], const Fr &z) { q[1] = p[2]; q[0] = p[1] + z * p[2]; };
     auto host_eval3 = [](const Fr p[3], const Fr &z) { return p[0] + z * (p[1] + z * p[2]); };
     // the two openings are independent: on the latency path they run side by side, the second one on its own buffers
-    if (R.jobs.async && !cx.ev_aux) {          // guarded by the LAST resource created: an allocation that throws leaves ev_aux null, and the next lone call starts over (advisor r05)
-        for (DevBuf *b : {&cx.acc_b, &cx.wit_b, &cx.wit2_b, &cx.scratch_b, &cx.scratch_c}) b->release();
+    if (R.jobs.async && !cx.ev_aux) {          // the event is made last: an allocation that throws leaves it empty, and the next lone call starts over
         cx.acc_b.alloc(cx.acc.n); cx.wit_b.alloc(cx.wit.n); cx.wit2_b.alloc(cx.wit2.n); cx.scratch_b.alloc(cx.scratch.n);
-        cx.scratch_c.alloc(gpu::divide_by_linear_scratch(std::max(n, k) + 1)); cx.ev_aux = gpu::event_create();
+        cx.scratch_c.alloc(gpu::divide_by_linear_scratch(std::max(n, k) + 1)); cx.ev_aux = gpu::EventGuard();
     }
     const bool two_sets = cx.ev_aux != nullptr && R.jobs.async;
     if (R.jobs.async) gpu::sync(s);                 // (the opening jobs read what the main stream made: everything is in place from here)
@@ -926,7 +900,7 @@ void ProvingKeyImpl::prove_open(ProofRun &R) {
     }, false);
     R.jobs.start(2, [&](Lane &ln) {   // open at gamma: g_2 (ch^0; shifted ch^1), inner_sumcheck (ch^2)
         gpu::stream_t ls_ = ln.stream;
-        DevBuf &acc_ = two_sets ? cx.acc_b : cx.acc, &wit_ = two_sets ? cx.wit_b : cx.wit, &wit2_ = two_sets ? cx.wit2_b : cx.wit2, &scr_ = two_sets ? cx.scratch_b : cx.scratch;
+        DevPtr<F> &acc_ = two_sets ? cx.acc_b : cx.acc, &wit_ = two_sets ? cx.wit_b : cx.wit, &wit2_ = two_sets ? cx.wit2_b : cx.wit2, &scr_ = two_sets ? cx.scratch_b : cx.scratch;
         size_t plen = k;
         {
             const F *ps[8] = {cx.poly[7].p, ix_co[2].p, ix_co[3].p, ix_co[4].p, ix_co[0].p, ix_co[1].p, ix_co[5].p, cx.poly[8].p};
@@ -1147,9 +1121,7 @@ Fr fr_from_small(int64_t c) { return c >= 0 ? Fr::from_u64((uint64_t)c) : Fr::fr
 uint64_t ProvingKey::serialize_ark_to_file(const std::string &path, bool uncompressed) const {
     ProvingKeyImpl &K = *impl;
     gpu::set_device(K.device);
-    struct StreamGuard { gpu::stream_t s = nullptr; ~StreamGuard() { gpu::stream_destroy(s); } } sg;
-    sg.s = gpu::stream_create();
-    gpu::stream_t s = sg.s;
+    gpu::StreamGuard s;
     FileSink o(path);                                   // (throws if the file cannot be opened: nothing of ours to remove then)
     struct Unlink { const std::string &p; bool armed = true; ~Unlink() { if (armed) ::remove(p.c_str()); } } partial{path};      // armed only once this call has created / truncated the file
     { auto v = serialize_vk_ark(K.vk, uncompressed); o.buf.put(v.data(), v.size()); }
@@ -1184,15 +1156,14 @@ uint64_t ProvingKey::serialize_ark_to_file(const std::string &path, bool uncompr
     }
     // committer key: the powers in the standard affine form, re-made on the device chunk by chunk
     const size_t CH = (size_t)1 << 20;
-    struct Chunk { G1A *d = nullptr; ~Chunk() { gpu::dfree(d); } } chunk;
-    chunk.d = (G1A *)gpu::dmalloc(CH * sizeof(G1A));
+    DevPtr<G1A> chunk(CH);
     std::vector<G1A> h(CH);
     auto write_powers = [&](size_t from, size_t count) {
         o.buf.u64(count);
         for (size_t off = 0; off < count; off += CH) {
             const size_t m_ = std::min(CH, count - off);
-            gpu::fixed_base_powers<Bls377>(chunk.d, K.vk.g, K.srs->beta, from + off, m_, s);
-            gpu::d2h(h.data(), chunk.d, m_ * sizeof(G1A), s);
+            gpu::fixed_base_powers<Bls377>(chunk, K.vk.g, K.srs->beta, from + off, m_, s);
+            gpu::d2h(h.data(), chunk, m_ * sizeof(G1A), s);
             for (size_t i = 0; i < m_; i++) { o.buf.g1(h[i], uncompressed); o.maybe_flush(); }
         }
     };

@@ -120,6 +120,9 @@ void event_record(void *ev, stream_t s) { HIP_CHECK(hipEventRecord((hipEvent_t)e
 void stream_wait_event(stream_t s, void *ev) { HIP_CHECK(hipStreamWaitEvent((hipStream_t)s, (hipEvent_t)ev, 0)); }
 float event_elapsed_ms(void *a, void *b) { float ms = 0; HIP_CHECK(hipEventSynchronize((hipEvent_t)b)); HIP_CHECK(hipEventElapsedTime(&ms, (hipEvent_t)a, (hipEvent_t)b)); return ms; }
 void event_destroy(void *ev) { if (ev) (void)hipEventDestroy((hipEvent_t)ev); }
+void *pinned_alloc(size_t bytes) { void *h = nullptr; HIP_CHECK(hipHostMalloc(&h, bytes, hipHostMallocMapped)); return h; }
+void *pinned_device_address(void *host) { void *d = nullptr; HIP_CHECK(hipHostGetDevicePointer(&d, host, 0)); return d; }
+void pinned_free(void *host) { if (host) (void)hipHostFree(host); }
 
 }  // namespace gpu
 }  // namespace zk

@@ -658,6 +658,45 @@ def test_srs_hold_keeps_the_tables_resident_between_keys(api):
         gc.collect()
 
 
+def test_a_key_gives_back_what_it_took(api, vectors):
+    """Every device buffer, stream, event and MSM workspace of a key has one owner (csrc/gpu.hpp), so freeing the key returns all of it: the index, three prover
+    contexts, the lanes and the second opening set a lone call creates, the workspaces the MSMs grew.  The shared SRS is held across the cycles so that it stays out of
+    the picture; the first cycle warms the runtime's own pools, and the bound is the one test_error_paths_release_device_memory allows for them.  A key synthesis that
+    fails half way (IndexTooLarge, after the circuit is compiled) must not keep anything either."""
+    import gc
+    msg, key = bytes(vectors["plaintext"]), bytes(vectors["key"])
+
+    def cycle():
+        pk, vk = api.synthesize_keys(16)
+        lone = api.encrypt(msg, key, pk)                  # a lone call: the lanes and the second opening set
+        pk.set_contexts(3)
+        proofs = pk.encrypt_chunked(msg * 4, key)
+        ct = vectors["ciphertext"]
+        assert len(proofs) == 4 and api.verify_encryption(vk, lone, bytes(ct)) and api.verify_encryption(vk, proofs[3], bytes(ct))
+        held = api.mem_info()[0]
+        pk.free()
+        return held
+
+    gc.collect()
+    api.srs_hold(True)
+    try:
+        cycle()
+        free0, _ = api.mem_info()
+        held = cycle()
+        free1, _ = api.mem_info()
+        print("free before the cycle %d, with the key alive %d, after its free() %d bytes" % (free0, held, free1))
+        assert abs(free0 - free1) < 16 << 20, "a freed key kept %d bytes of device memory" % (free0 - free1)
+        for _ in range(3):
+            with pytest.raises(api.ZkAesError, match="IndexTooLarge"):
+                api.synthesize_keys(112)
+        free2, _ = api.mem_info()
+        print("after three failed key syntheses %d bytes" % free2)
+        assert abs(free0 - free2) < 16 << 20, "failed key syntheses kept %d bytes of device memory" % (free0 - free2)
+    finally:
+        api.srs_hold(False)
+        gc.collect()
+
+
 def test_twenty_eight_block_chunk_over_a_larger_universal_srs(zko, api):
     """bench.py's `big` leg in small: a 28-block (448-byte) chunk-proof needs a universal SRS four times the reference's literal (zkaes_synthesize_keys_ex with
     (2^22, 513, 2^24)); 28 blocks fill |H| = 2^22 to 99.9 % and |K| = 2^24 to 98.3 %.  Here without the window tables (126 GB for that SRS: the bench leg builds them in a
