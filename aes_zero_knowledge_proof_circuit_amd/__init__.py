@@ -5,4 +5,5 @@ Everything heavy lives in libzkaes.so (HIP kernels + C++ host, C ABI in include/
 ctypes binding a Python harness uses.  There is no CPU fallback: proving raises ZkAesError without a GPU.
 """
 from .api import (ZkAesError, ProvingKey, VerifyingKey, synthesize_keys, encrypt, verify_encryption, lib, lib_path,  # noqa: F401
-                  CIRCUIT_AES, CIRCUIT_OPS_XOR, CIRCUIT_OPS_ADD)
+                  CIRCUIT_AES, CIRCUIT_OPS_XOR, CIRCUIT_OPS_ADD, CIRCUIT_AES_CBC,
+                  cbc_ciphertext, encrypt_cbc, verify_encryption_cbc, verify_cbc_chunked)

@@ -6,6 +6,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CIRCUIT_AES, CIRCUIT_OPS_XOR, CIRCUIT_OPS_ADD = 0, 1, 2
+CIRCUIT_AES_CBC = 3                # AES-128-CBC: public input = iv, ciphertext (include/zkaes.h, DESIGN.md "CBC")
 KEY_NO_TABLES = 1                  # zkaes_synthesize_keys_ex2 flag: no fixed-base window tables (saves 10-42 GB per key)
 PARITY = "parity"                  # zk_seed=PARITY: the reference's fixed ark_std::test_rng() stream for every proof (byte-parity tests only)
 
@@ -188,6 +189,41 @@ class ProvingKey:
         _check(lib().zkaes_aes_witness(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), buf, n, C.byref(n)))
         return buf.raw
 
+    def witness_cbc(self, message, secret_key, iv):
+        """z (padded instance + witness, one byte per variable) of a CBC key: One, the 128 IV bits, the ciphertext bits, padding, then the witness"""
+        if len(secret_key) != 16 or len(iv) != 16:
+            raise ZkAesError("secret_key and iv must be 16 bytes")
+        n = C.c_size_t()
+        _check(lib().zkaes_aes_witness_cbc(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().zkaes_aes_witness_cbc(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), buf, n, C.byref(n)))
+        return buf.raw
+
+    def encrypt_cbc_chunked(self, message, secret_key, iv, zk_seed=None, first_proof_index=0):
+        """(ciphertext, chunk-proofs) of a long CBC message.  iv = the chaining value entering this call's first chunk (a job split over several calls takes each call's
+        from cbc_ciphertext); zk_seed and first_proof_index as encrypt_chunked"""
+        if len(secret_key) != 16 or len(iv) != 16:
+            raise ZkAesError("secret_key and iv must be 16 bytes")
+        seed = self._seed_arg(zk_seed)
+        chunk = (self.info()["raw_instance"] - 129) // 8        # One + 128 IV bits, then 8 public-input bits per ciphertext byte
+        if chunk <= 0:
+            raise ZkAesError("proving key was not synthesized for the AES-CBC circuit")
+        n_chunks = len(message) // chunk
+        lens = (C.c_size_t * max(n_chunks, 1))()
+        ct = C.create_string_buffer(max(len(message), 1))
+        out, n = C.c_void_p(), C.c_size_t()
+        if zk_seed is None:
+            _check(lib().zkaes_encrypt_cbc_chunked(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), self._p, ct, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
+        else:
+            _check(lib().zkaes_encrypt_cbc_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), self._p, seed, C.c_uint64(first_proof_index), ct,
+                                                             C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
+        blob = _take(out, n)
+        proofs, off = [], 0
+        for i in range(n_chunks):
+            proofs.append(blob[off:off + lens[i]])
+            off += lens[i]
+        return ct.raw[:len(message)], proofs
+
     def prove_ops(self, x, y, zk_seed=None):
         out, n = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_prove_ops(self._p, C.c_uint32(x), C.c_uint32(y), zk_seed, C.byref(out), C.byref(n)))
@@ -283,6 +319,46 @@ def verify_encryption(verifying_key, proof, ciphertext):
     acc = C.c_int()
     _check(lib().zkaes_verify_encryption(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(ciphertext), C.c_size_t(len(ciphertext)), C.byref(acc)))
     return bool(acc.value)
+
+
+def cbc_ciphertext(message, secret_key, iv):
+    """AES-128-CBC of whole blocks on the host (zkaes_cbc_ciphertext; no GPU)"""
+    if len(secret_key) != 16 or len(iv) != 16:
+        raise ZkAesError("secret_key and iv must be 16 bytes")
+    ct = C.create_string_buffer(max(len(message), 1))
+    _check(lib().zkaes_cbc_ciphertext(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), ct))
+    return ct.raw[:len(message)]
+
+
+def encrypt_cbc(message, secret_key, iv, proving_key, zk_seed=None):
+    """one proof over a CBC key -> (ciphertext, serialized MarlinProof bytes); zk_seed as encrypt"""
+    if len(secret_key) != 16 or len(iv) != 16:
+        raise ZkAesError("secret_key and iv must be 16 bytes")
+    ct = C.create_string_buffer(max(len(message), 1))
+    out, n = C.c_void_p(), C.c_size_t()
+    _check(lib().zkaes_encrypt_cbc_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), proving_key._p, zk_seed, ct, C.byref(out), C.byref(n)))
+    return ct.raw[:len(message)], _take(out, n)
+
+
+def verify_encryption_cbc(verifying_key, proof, iv, ciphertext):
+    """is `proof` a proof that `ciphertext` is the AES-128-CBC encryption under `iv` of a hidden message with a hidden key? -> bool"""
+    if len(iv) != 16:
+        raise ZkAesError("iv must be 16 bytes")
+    acc = C.c_int()
+    _check(lib().zkaes_verify_encryption_cbc(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(iv), bytes(ciphertext), C.c_size_t(len(ciphertext)), C.byref(acc)))
+    return bool(acc.value)
+
+
+def verify_cbc_chunked(verifying_key, proofs, iv, ciphertext):
+    """chunk-proofs of a long CBC message against (iv, ciphertext): chunk j is checked under the 16 ciphertext bytes ahead of it (iv for j = 0) -> list of bools"""
+    if len(iv) != 16:
+        raise ZkAesError("iv must be 16 bytes")
+    n = len(proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each = (C.c_int * max(n, 1))()
+    ok = C.c_size_t()
+    _check(lib().zkaes_verify_cbc_chunked(verifying_key._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), bytes(iv), bytes(ciphertext), C.c_size_t(len(ciphertext)), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
 
 
 def proof_roundtrip(proof):

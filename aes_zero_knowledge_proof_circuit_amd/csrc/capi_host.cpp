@@ -5,7 +5,13 @@
 
 namespace {
 thread_local std::string g_err;
-zk::Circuit compile(int kind, size_t len) { return kind == ZKAES_CIRCUIT_AES ? zk::compile_aes_circuit(len) : zk::compile_ops_circuit(kind); }
+zk::Circuit compile(int kind, size_t len) { return zk::compile_circuit(kind, len); }
+// the CBC instance without the leading One: 128 IV bits, then the ciphertext bits, each byte LSB first
+std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
+    std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 16), c = zk::ciphertext_to_public_input(ct, ct_len);
+    pub.insert(pub.end(), c.begin(), c.end());
+    return pub;
+}
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
 // image of the struct: reading it back from untrusted bytes put arbitrary limbs into field elements and an arbitrary byte into a bool, and skipped the curve / subgroup
 // checks the ark path makes -- found while writing the fuzz target (tests/fuzz_host.cpp).  v2 goes through deserialize_vk_ark and inherits every check.
@@ -34,6 +40,45 @@ int zkaes_verify_encryption(const zkaes_vk *vk, const uint8_t *proof, size_t pro
         if (!vk || !proof || !accepted) throw std::invalid_argument("null argument");
         zk::Proof p = zk::deserialize_proof(proof, proof_len);
         *accepted = zk::verify(vk->vk, zk::ciphertext_to_public_input(ct, ct_len), p) ? 1 : 0;
+    });
+}
+int zkaes_cbc_ciphertext(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *ct) {
+    return guard([&] {
+        if (!msg || !key || !iv || !ct) throw std::invalid_argument("null argument");
+        if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
+        zk::aes128_cbc_encrypt_host(msg, len, key, iv, ct);
+    });
+}
+int zkaes_verify_encryption_cbc(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[16], const uint8_t *ct, size_t ct_len, int *accepted) {
+    return guard([&] {
+        if (!vk || !proof || !iv || !ct || !accepted) throw std::invalid_argument("null argument");
+        *accepted = 0;
+        if (ct_len == 0 || ct_len % 16) throw std::invalid_argument("CBC: the ciphertext must be a non-zero multiple of 16 bytes");
+        zk::Proof p = zk::deserialize_proof(proof, proof_len);
+        *accepted = zk::verify(vk->vk, cbc_public_input(iv, ct, ct_len), p) ? 1 : 0;
+    });
+}
+// Chunk j is checked against (IV_j, its slice of the ciphertext), IV_0 = iv and IV_j = the 16 ciphertext bytes ahead of the slice: all of it public, so the
+// chunks are independent statements.  A chunk whose proof bytes do not parse is a rejected chunk, not an error of the call.
+int zkaes_verify_cbc_chunked(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t iv[16], const uint8_t *ct, size_t ct_len,
+                             int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (!vk || !proofs || !proof_lens || !iv || !ct) throw std::invalid_argument("null argument");
+        if (n_accepted) *n_accepted = 0;
+        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks || (ct_len / n_chunks) % 16) throw std::invalid_argument("CBC: the ciphertext must be n_chunks x a non-zero multiple of 16 bytes");
+        const size_t chunk = ct_len / n_chunks;
+        size_t off = 0, ok = 0;
+        for (size_t j = 0; j < n_chunks; j++) {
+            int acc = 0;
+            try {
+                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
+                acc = zk::verify(vk->vk, cbc_public_input(j ? ct + chunk * j - 16 : iv, ct + chunk * j, chunk), p) ? 1 : 0;
+            } catch (const std::runtime_error &) { acc = 0; }
+            if (accepted_each) accepted_each[j] = acc;
+            ok += (size_t)acc;
+            off += proof_lens[j];
+        }
+        if (n_accepted) *n_accepted = ok;
     });
 }
 int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out, size_t *out_len) {

@@ -244,43 +244,51 @@ uint8_t aes_sbox_value(uint8_t x) {   // algebraic S-box (FIPS-197 5.1.1; equals
     return r ^ 0x63;
 }
 
-Circuit compile_aes_circuit(size_t len) {
-    if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
-    size_t nb = len / 16;
-    Builder b;
-    std::vector<Byte> table(256);
-    for (int i = 0; i < 256; i++) table[i] = Builder::const_byte(aes_sbox_value((uint8_t)i));
-    auto blk = [](size_t bi) { return (uint32_t)(TR_BLOCK0 + bi * TR_BLOCK_STRIDE); };
-    // message then key witnesses (src/lib.rs:70-76, 82-88)
-    std::vector<Byte> msg(len);
-    for (size_t i = 0; i < len; i++) msg[i] = b.alloc_byte(false, blk(i / 16) + TR_BL_MSG + (uint32_t)(i % 16));
+namespace {
+
+// The gates both AES modes share, in the reference's order: the key schedule once, then per block the ten rounds behind a round-0 input.  ECB feeds the message block,
+// CBC the chained block X_b; everything a block allocates from its round 0 on is the same gate sequence in both.
+struct AesGates {
+    Builder &b;
+    std::vector<Byte> table;
     std::array<Byte, 16> key;
-    for (int i = 0; i < 16; i++) key[i] = b.alloc_byte(false, TR_KEY + i);
+    std::array<std::array<Byte, 4>, 44> w;
+    explicit AesGates(Builder &b_) : b(b_), table(256) {
+        for (int i = 0; i < 256; i++) table[i] = Builder::const_byte(aes_sbox_value((uint8_t)i));
+    }
+    static uint32_t blk(size_t bi) { return (uint32_t)(TR_BLOCK0 + bi * TR_BLOCK_STRIDE); }
+    // message then key witnesses (src/lib.rs:70-76, 82-88)
+    std::vector<Byte> alloc_message_and_key(size_t len) {
+        std::vector<Byte> msg(len);
+        for (size_t i = 0; i < len; i++) msg[i] = b.alloc_byte(false, blk(i / 16) + TR_BL_MSG + (uint32_t)(i % 16));
+        for (int i = 0; i < 16; i++) key[i] = b.alloc_byte(false, TR_KEY + i);
+        return msg;
+    }
     // derive_keys (src/aes_circuit.rs:20-129): words are big-endian byte quadruples; UInt32::xor runs LSB-first over the
     // u32, i.e. byte 3 first (to_u32, :201-212)
-    std::array<std::array<Byte, 4>, 44> w;
-    for (int i = 0; i < 4; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
-    static const uint8_t rc[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
-    for (int i = 4; i < 44; i++) {
-        if (i % 4 == 0) {
-            int q = i / 4 - 1;
-            std::array<Byte, 4> sub;
-            for (int k = 0; k < 4; k++) {
-                int src = (k + 1) % 4;                                            // rotate_word: rotate_left(1)
-                sub[k] = b.sbox(w[i - 1][src], table, (uint32_t)(TR_KS_W + 4 * (i - 1) + src));
+    void key_schedule() {
+        for (int i = 0; i < 4; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
+        static const uint8_t rc[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
+        for (int i = 4; i < 44; i++) {
+            if (i % 4 == 0) {
+                int q = i / 4 - 1;
+                std::array<Byte, 4> sub;
+                for (int k = 0; k < 4; k++) {
+                    int src = (k + 1) % 4;                                            // rotate_word: rotate_left(1)
+                    sub[k] = b.sbox(w[i - 1][src], table, (uint32_t)(TR_KS_W + 4 * (i - 1) + src));
+                }
+                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - 4][k], sub[k], (uint32_t)(TR_KS_PRE + 4 * q + k));
+                w[i][0] = b.xor_byte(w[i][0], Builder::const_byte(rc[q]), 0);         // Rcon: constant operand, free
+            } else {
+                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - 4][k], w[i - 1][k], (uint32_t)(TR_KS_W + 4 * i + k));
             }
-            for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - 4][k], sub[k], (uint32_t)(TR_KS_PRE + 4 * q + k));
-            w[i][0] = b.xor_byte(w[i][0], Builder::const_byte(rc[q]), 0);         // Rcon: constant operand, free
-        } else {
-            for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - 4][k], w[i - 1][k], (uint32_t)(TR_KS_W + 4 * i + k));
         }
     }
-    // per block rounds (src/lib.rs:194-278)
-    std::vector<Byte> ct(len);
-    for (size_t bi = 0; bi < nb; bi++) {
+    // one block's rounds (src/lib.rs:194-278) from its round-0 input `in`; returns S_10
+    std::array<Byte, 16> block_rounds(const Byte *in, size_t bi) {
         uint32_t base = blk(bi);
         std::array<Byte, 16> s, t, u;
-        for (int i = 0; i < 16; i++) s[i] = b.xor_byte(msg[16 * bi + i], key[i], base + TR_BL_S + i);          // :196 raw key
+        for (int i = 0; i < 16; i++) s[i] = b.xor_byte(in[i], key[i], base + TR_BL_S + i);          // :196 raw key
         for (int r = 1; r <= 10; r++) {
             for (int i = 0; i < 16; i++) {                                                                      // substitute_bytes
                 t[i] = b.sbox(s[i], table, base + TR_BL_S + 16 * (r - 1) + i);
@@ -315,14 +323,92 @@ Circuit compile_aes_circuit(size_t len) {
                 s[i] = b.xor_byte(t[i], rk, base + TR_BL_S + 16 * r + i);
             }
         }
-        for (int i = 0; i < 16; i++) ct[16 * bi + i] = s[i];
+        return s;
     }
     // public inputs + equality (src/lib.rs:282-286)
-    for (size_t i = 0; i < len; i++) {
-        Byte pi = b.alloc_byte(true, blk(i / 16) + TR_BL_S + 160 + (uint32_t)(i % 16));
-        for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
+    void ciphertext_inputs(const std::vector<Byte> &ct) {
+        for (size_t i = 0; i < ct.size(); i++) {
+            Byte pi = b.alloc_byte(true, blk(i / 16) + TR_BL_S + 160 + (uint32_t)(i % 16));
+            for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
+        }
     }
+};
+
+}  // namespace
+
+Circuit compile_aes_circuit(size_t len) {
+    if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
+    size_t nb = len / 16;
+    Builder b;
+    AesGates g(b);
+    std::vector<Byte> msg = g.alloc_message_and_key(len);
+    g.key_schedule();
+    std::vector<Byte> ct(len);
+    for (size_t bi = 0; bi < nb; bi++) {
+        std::array<Byte, 16> s = g.block_rounds(&msg[16 * bi], bi);
+        for (int i = 0; i < 16; i++) ct[16 * bi + i] = s[i];
+    }
+    g.ciphertext_inputs(ct);
     return finish(b, CIRCUIT_AES, nb, TR_BLOCK0 + nb * TR_BLOCK_STRIDE);
+}
+
+// Gate order: message and key witnesses, the 16 IV bytes as inputs, the key schedule, per block the 128 xor gates of X_b = M_b ^ prev (prev = the IV bytes, then the
+// previous block's S_10) and the block's rounds from X_b, the ciphertext inputs.  The instance is One, 128 IV bits, 128 nb ciphertext bits.
+Circuit compile_aes_cbc_circuit(size_t len) {
+    if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
+    size_t nb = len / 16;
+    const uint32_t cbc = (uint32_t)TR_CBC(nb);
+    Builder b;
+    AesGates g(b);
+    std::vector<Byte> msg = g.alloc_message_and_key(len);
+    std::array<Byte, 16> prev;
+    for (int i = 0; i < 16; i++) prev[i] = b.alloc_byte(true, cbc + TR_CBC_IV + (uint32_t)i);
+    g.key_schedule();
+    std::vector<Byte> ct(len);
+    for (size_t bi = 0; bi < nb; bi++) {
+        std::array<Byte, 16> x;
+        for (int i = 0; i < 16; i++) x[i] = b.xor_byte(msg[16 * bi + i], prev[i], cbc + TR_CBC_X + (uint32_t)(16 * bi + i));
+        prev = g.block_rounds(x.data(), bi);
+        for (int i = 0; i < 16; i++) ct[16 * bi + i] = prev[i];
+    }
+    g.ciphertext_inputs(ct);
+    return finish(b, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb);
+}
+
+Circuit compile_circuit(int kind, size_t message_len) {
+    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len);
+    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len);
+    return compile_ops_circuit(kind);
+}
+
+void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out) {
+    if (len % 16) throw std::invalid_argument("CBC: the message must be a multiple of 16 bytes");
+    uint8_t sb[256];
+    for (int i = 0; i < 256; i++) sb[i] = aes_sbox_value((uint8_t)i);
+    auto xt = [](uint8_t c) { return (uint8_t)((c << 1) ^ ((c >> 7) * 0x1B)); };
+    uint8_t rk[11][16];                                                       // FIPS-197 5.2, round keys as 16 bytes in word order
+    for (int i = 0; i < 16; i++) rk[0][i] = key[i];
+    uint8_t rc = 1;
+    for (int r = 1; r <= 10; r++) {
+        const uint8_t *p = rk[r - 1];
+        uint8_t t[4] = {(uint8_t)(sb[p[13]] ^ rc), sb[p[14]], sb[p[15]], sb[p[12]]};
+        for (int i = 0; i < 16; i++) rk[r][i] = (uint8_t)(p[i] ^ (i < 4 ? t[i] : rk[r][i - 4]));
+        rc = xt(rc);
+    }
+    uint8_t prev[16], s[16], u[16];
+    for (int i = 0; i < 16; i++) prev[i] = iv[i];
+    for (size_t off = 0; off < len; off += 16) {
+        for (int i = 0; i < 16; i++) s[i] = (uint8_t)(msg[off + i] ^ prev[i] ^ rk[0][i]);
+        for (int r = 1; r <= 10; r++) {
+            for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = sb[s[4 * ((c + rr) & 3) + rr]];     // SubBytes + ShiftRows
+            for (int c = 0; c < 4; c++) {
+                const uint8_t *a = u + 4 * c;
+                for (int k = 0; k < 4; k++)
+                    s[4 * c + k] = (uint8_t)((r <= 9 ? xt(a[k]) ^ xt(a[(k + 1) & 3]) ^ a[(k + 1) & 3] ^ a[(k + 2) & 3] ^ a[(k + 3) & 3] : a[k]) ^ rk[r][4 * c + k]);
+            }
+        }
+        for (int i = 0; i < 16; i++) out[off + i] = prev[i] = s[i];
+    }
 }
 
 // src/ops.rs:8-29.  Trace: x (4 B LE) | y (4 B LE) | result (8 B LE)

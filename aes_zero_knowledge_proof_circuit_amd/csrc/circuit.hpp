@@ -22,7 +22,7 @@ struct CsrMatrix {
     size_t nnz() const { return col.size(); }
 };
 
-enum CircuitKind { CIRCUIT_AES = 0, CIRCUIT_OPS_XOR = 1, CIRCUIT_OPS_ADD = 2 };
+enum CircuitKind { CIRCUIT_AES = 0, CIRCUIT_OPS_XOR = 1, CIRCUIT_OPS_ADD = 2, CIRCUIT_AES_CBC = 3 };
 
 struct Circuit {
     int kind = CIRCUIT_AES;
@@ -42,6 +42,13 @@ struct Circuit {
 // message_len must be a multiple of 16 (else throws std::invalid_argument with the reference's message)
 Circuit compile_aes_circuit(size_t message_len);
 Circuit compile_ops_circuit(int kind);
+// AES-128-CBC over the same gadgets (no upstream counterpart; DESIGN.md "CBC"): public = 16 IV bytes then the ciphertext, private = message and key;
+// per block X_b = M_b ^ C_{b-1} (C_{-1} = IV) ahead of the block's round 0.  message_len must be a non-zero multiple of 16 (else std::invalid_argument)
+Circuit compile_aes_cbc_circuit(size_t message_len);
+// kind = CIRCUIT_AES, CIRCUIT_AES_CBC, or an ops kind (message_len ignored)
+Circuit compile_circuit(int kind, size_t message_len);
 uint8_t aes_sbox_value(uint8_t x);   // the lookup table of src/aes_circuit.rs:433-694
+// plain byte-wise AES-128-CBC over aes_sbox_value, host only: out = len bytes, len a multiple of 16
+void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out);
 
 }  // namespace zk

@@ -2,8 +2,8 @@
 //
 // Replaces the value side of the gadget synthesis in /root/reference/src/lib.rs:176-293 and src/aes_circuit.rs:20-427
 // (every UInt8/Boolean op there both allocates a variable and computes its value on the CPU): here
-//   k_aes_trace       one lane per ECB block: plain AES-128 with every intermediate byte the circuit names written to the
-//                     per-proof trace buffer (layout: trace_layout.h),
+//   k_aes_trace       one lane per block: plain AES-128 with every intermediate byte the circuit names written to the
+//                     per-proof trace buffer (layout: trace_layout.h); the mode (ECB / CBC) is a template parameter,
 //   k_witness_expand  one lane per column of z: decode the variable's descriptor (compiled once by circuit.cpp) and gather
 //                     its bit -- S-box mux-tree variables are a table lookup S[(node << (level+1)) | (x & mask)],
 //   k_spmv_bits       z_A = A z, z_B = B z over 0/1 assignments with small integer coefficients (ark-marlin prover_init),
@@ -38,9 +38,40 @@ void upload_sbox(const uint8_t table[256]) {
 
 __device__ __forceinline__ uint8_t xtime(uint8_t c) { return (uint8_t)((c << 1) ^ (((c >> 7) & 1) * 0x1B)); }
 
-// grid: nproofs * (nblocks + 1) lanes; lane (p, 0) writes the key schedule part, lane (p, 1 + b) block b
-__global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, uint32_t nproofs,
-                            uint32_t nblocks, const uint8_t *__restrict__ sbox) {
+// One block's ten rounds from s = its state after round 0.  STORE: write every intermediate the circuit names into the block's trace slot `bl`; without it the
+// lane only wants the ciphertext block left in s (a CBC lane walking to its chaining value).
+template <bool STORE>
+__device__ __forceinline__ void aes_block_rounds(uint8_t s[16], const uint8_t (*w)[4], const uint8_t *__restrict__ sbox, uint8_t *__restrict__ bl) {
+    uint8_t u[16], v[16];
+    for (int r = 1; r <= 10; r++) {
+        for (int i = 0; i < 16; i++) { v[i] = sbox[s[i]]; if (STORE) bl[TR_BL_SB + 16 * (r - 1) + i] = v[i]; }
+        for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = v[4 * ((c + rr) & 3) + rr];     // ShiftRows
+        if (r <= 9) {
+            for (int c = 0; c < 4; c++) {
+                uint8_t a[4], xb[4];
+                for (int k = 0; k < 4; k++) { a[k] = u[4 * c + k]; xb[k] = xtime(a[k]); if (STORE) bl[TR_BL_XT + 16 * (r - 1) + 4 * c + k] = xb[k]; }
+                // left-assoc xor chains of src/aes_circuit.rs:391-426
+                const uint8_t term[4][5] = {{xb[0], a[3], a[2], xb[1], a[1]}, {xb[1], a[0], a[3], xb[2], a[2]}, {xb[2], a[1], a[0], xb[3], a[3]}, {xb[3], a[2], a[1], xb[0], a[0]}};
+                for (int o = 0; o < 4; o++) {
+                    uint8_t acc = term[o][0];
+                    for (int q = 1; q < 5; q++) { acc ^= term[o][q]; if (STORE) bl[TR_BL_MP + 64 * (r - 1) + 4 * (4 * c + o) + (q - 1)] = acc; }
+                    v[4 * c + o] = acc;
+                }
+            }
+        } else {
+            for (int i = 0; i < 16; i++) v[i] = u[i];
+        }
+        for (int i = 0; i < 16; i++) { s[i] = v[i] ^ w[4 * r + i / 4][i % 4]; if (STORE) bl[TR_BL_S + 16 * r + i] = s[i]; }
+    }
+}
+
+// grid: nproofs * (nblocks + 1) lanes; lane (p, 0) writes the key schedule part, lane (p, 1 + b) block b.
+// CBC: lane (p, 0) also stores the proof's IV in the trace tail; lane (p, 1 + b) starts from prev = ivs[p], runs plain AES without stores over blocks 0 .. b - 1 to reach
+// its own chaining value (at most nblocks - 1 extra blocks per lane), stores X_b = M_b ^ prev in the tail and goes on from s = X_b ^ key with all the usual stores.  The
+// kernel is handed the chunk's IV only, never a chain made on the host.  ivs is not read in the ECB instantiation.
+template <bool CBC>
+__global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ ivs,
+                            uint32_t nproofs, uint32_t nblocks, const uint8_t *__restrict__ sbox) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nproofs * (nblocks + 1)) return;
     uint32_t p = t / (nblocks + 1), which = t % (nblocks + 1);
@@ -62,43 +93,50 @@ __global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const ui
             for (int k = 0; k < 4; k++) w[i][k] = w[i - 4][k] ^ w[i - 1][k];
         }
     }
+    uint8_t *tail = tr + TR_CBC((size_t)nblocks);          // (CBC only)
     if (which == 0) {
         for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
         for (int i = 0; i < 44; i++) for (int k = 0; k < 4; k++) tr[TR_KS_W + 4 * i + k] = w[i][k];
+        if (CBC) for (int i = 0; i < 16; i++) tail[TR_CBC_IV + i] = ivs[16 * (size_t)p + i];
         return;
     }
     uint32_t b = which - 1;
     uint8_t *bl = tr + TR_BLOCK0 + (size_t)b * TR_BLOCK_STRIDE;
     const uint8_t *msg = msgs + ((size_t)p * nblocks + b) * 16;
-    uint8_t s[16], u[16], v[16];
-    for (int i = 0; i < 16; i++) { bl[TR_BL_MSG + i] = msg[i]; s[i] = msg[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
-    for (int r = 1; r <= 10; r++) {
-        for (int i = 0; i < 16; i++) { v[i] = sbox[s[i]]; bl[TR_BL_SB + 16 * (r - 1) + i] = v[i]; }
-        for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = v[4 * ((c + rr) & 3) + rr];     // ShiftRows
-        if (r <= 9) {
-            for (int c = 0; c < 4; c++) {
-                uint8_t a[4], xb[4];
-                for (int k = 0; k < 4; k++) { a[k] = u[4 * c + k]; xb[k] = xtime(a[k]); bl[TR_BL_XT + 16 * (r - 1) + 4 * c + k] = xb[k]; }
-                // left-assoc xor chains of src/aes_circuit.rs:391-426
-                const uint8_t term[4][5] = {{xb[0], a[3], a[2], xb[1], a[1]}, {xb[1], a[0], a[3], xb[2], a[2]}, {xb[2], a[1], a[0], xb[3], a[3]}, {xb[3], a[2], a[1], xb[0], a[0]}};
-                for (int o = 0; o < 4; o++) {
-                    uint8_t acc = term[o][0];
-                    for (int q = 1; q < 5; q++) { acc ^= term[o][q]; bl[TR_BL_MP + 64 * (r - 1) + 4 * (4 * c + o) + (q - 1)] = acc; }
-                    v[4 * c + o] = acc;
-                }
-            }
-        } else {
-            for (int i = 0; i < 16; i++) v[i] = u[i];
+    uint8_t s[16];
+    if (CBC) {
+        uint8_t prev[16];
+        for (int i = 0; i < 16; i++) prev[i] = ivs[16 * (size_t)p + i];
+        for (uint32_t j = 0; j < b; j++) {
+            const uint8_t *mj = msgs + ((size_t)p * nblocks + j) * 16;
+            for (int i = 0; i < 16; i++) s[i] = mj[i] ^ prev[i] ^ key[i];
+            aes_block_rounds<false>(s, w, sbox, nullptr);
+            for (int i = 0; i < 16; i++) prev[i] = s[i];
         }
-        for (int i = 0; i < 16; i++) { s[i] = v[i] ^ w[4 * r + i / 4][i % 4]; bl[TR_BL_S + 16 * r + i] = s[i]; }
+        for (int i = 0; i < 16; i++) {
+            uint8_t x = msg[i] ^ prev[i];
+            bl[TR_BL_MSG + i] = msg[i]; tail[TR_CBC_X + 16 * b + i] = x; s[i] = x ^ key[i]; bl[TR_BL_S + i] = s[i];
+        }
+    } else {
+        for (int i = 0; i < 16; i++) { bl[TR_BL_MSG + i] = msg[i]; s[i] = msg[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
     }
+    aes_block_rounds<true>(s, w, sbox, bl);
+}
+template <bool CBC>
+static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s) {
+    uint8_t *g_sbox = sbox_here();
+    if (!g_sbox) throw GpuError(std::string(who) + ": S-box table not uploaded on this device");
+    uint32_t lanes = nproofs * (nblocks + 1);
+    hipLaunchKernelGGL(k_aes_trace<CBC>, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, ivs, nproofs, nblocks, g_sbox);
+    HIP_LAUNCH_CHECK();
 }
 void aes_trace(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, uint32_t nproofs, uint32_t nblocks, stream_t s) {
-    uint8_t *g_sbox = sbox_here();
-    if (!g_sbox) throw GpuError("aes_trace: S-box table not uploaded on this device");
-    uint32_t lanes = nproofs * (nblocks + 1);
-    hipLaunchKernelGGL(k_aes_trace, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, nproofs, nblocks, g_sbox);
-    HIP_LAUNCH_CHECK();
+    launch_aes_trace<false>("aes_trace", trace, stride, msgs, keys, nullptr, nproofs, nblocks, s);
+}
+void aes_trace_cbc(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s) {
+    if (!ivs) throw GpuError("aes_trace_cbc: no IV buffer");
+    if (stride < TR_CBC((size_t)nblocks) + TR_CBC_X + 16 * (size_t)nblocks) throw GpuError("aes_trace_cbc: trace stride is short of the CBC tail");
+    launch_aes_trace<true>("aes_trace_cbc", trace, stride, msgs, keys, ivs, nproofs, nblocks, s);
 }
 
 __global__ void k_witness_expand(uint8_t *__restrict__ z, const uint32_t *__restrict__ desc, uint32_t ncols, const uint8_t *__restrict__ trace,

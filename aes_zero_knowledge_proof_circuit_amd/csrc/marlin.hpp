@@ -73,6 +73,14 @@ class ProvingKey {
     // n independent (message_i, key_i) pairs, each message of the key's plaintext length; keys = n x 16 bytes
     std::vector<Proof> prove_aes_batch(const uint8_t *messages, const uint8_t *keys, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0);
     Proof prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed);
+    // ---- AES-128-CBC (keys of kind CIRCUIT_AES_CBC only; the calls above refuse such a key).  Public input: iv, ciphertext.
+    // one proof; ciphertext_or_null receives len bytes (the host's CBC encryption: the device recomputes the chain from iv alone, so the two check each other through the constraints)
+    Proof prove_aes_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr);
+    // chunk-proofs of a long CBC message: the host chain runs once over the whole message, chunk j is proven under the public chaining value entering it (iv for j = 0, else
+    // the last ciphertext block of chunk j - 1), all contexts side by side as in prove_aes_chunked; iv = the chaining value entering this call's first chunk.  Seeds as there.
+    std::vector<Proof> prove_aes_cbc_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], size_t n_contexts, const uint8_t *zk_seed = nullptr,
+                                             uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr);
+    std::vector<uint8_t> aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]);
     // witness generation only (kernels aes_trace + witness_expand): z = padded instance || witness, one byte per variable
     std::vector<uint8_t> aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]);
     const ProverTimings &last_timings() const;

@@ -13,6 +13,9 @@
 //       +352  XT_r, r = 1..9 : xtime ("b") bytes of the ShiftRows output, src/aes_circuit.rs:366-389   9 x 16
 //       +496  MP_r, r = 1..9 : for each output byte idx, the 4 partial values of its 5-term xor chain
 //                              (src/aes_circuit.rs:391-426); partial 3 is the MixColumns output           9 x 64
+//   CBC keys only, behind the nb blocks (cbc = TR_CBC(nb)); a block's "message block" stays the plaintext M_b and its S_0 is X_b ^ key:
+//       cbc + 0          IV (16)
+//       cbc + 16 + 16 b  X_b = M_b ^ C_{b-1}, C_{-1} = IV: what enters round 0 of block b    nb x 16
 #pragma once
 #define TR_KEY 0
 #define TR_KS_W 16
@@ -25,6 +28,9 @@
 #define TR_BL_SB 192
 #define TR_BL_XT 352
 #define TR_BL_MP 496
+#define TR_CBC(nb) (TR_BLOCK0 + (nb) * TR_BLOCK_STRIDE)
+#define TR_CBC_IV 0
+#define TR_CBC_X 16
 #define TR_SBOX_PER_BLOCK 160
 #define TR_SBOX_KS 40
 

@@ -67,6 +67,7 @@ int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out,
 #define ZKAES_CIRCUIT_AES 0      /* src/lib.rs:176-293 */
 #define ZKAES_CIRCUIT_OPS_XOR 1  /* src/ops.rs:8-18 (as a BLS12-377 Marlin circuit) */
 #define ZKAES_CIRCUIT_OPS_ADD 2  /* src/ops.rs:20-29 */
+#define ZKAES_CIRCUIT_AES_CBC 3  /* AES-128-CBC (no upstream counterpart; section "AES-128-CBC" below); accepted by zkaes_synthesize_keys_ex / _ex2, zkaes_circuit_info, zkaes_circuit_matrix */
 /* as zkaes_synthesize_keys with an explicit circuit kind and universal-SRS literals (generate_universal_srs arguments) */
 int zkaes_synthesize_keys_ex(int circuit_kind, size_t plaintext_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, zkaes_pk **pk,
                              zkaes_vk **vk);
@@ -111,6 +112,34 @@ int zkaes_encrypt_batch_seeded(size_t n, const uint8_t *messages, size_t message
                                const uint8_t *zk_seed32, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
 int zkaes_encrypt_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const zkaes_pk *pk,
                                   const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* ---- AES-128-CBC ---------------------------------------------------------------------------------------------------
+ * Statement of a key synthesized with ZKAES_CIRCUIT_AES_CBC for 16 nb bytes (nb >= 1): public = iv (16 bytes) and ciphertext (16 nb bytes), private = message and
+ * secret_key, with C_-1 = iv and C_b = AES-128(key, M_b ^ C_b-1).  Public-input vector (the instance without the leading One): the 128 IV bits, then the 128 nb
+ * ciphertext bits, every byte as 8 LSB-first bits.  A message of 0 bytes or one that is not whole blocks is an error; there is no padding scheme.
+ * A long message splits into independent chunk-proofs exactly as ECB does: the chaining value entering chunk j is the last ciphertext block of chunk j - 1, which is
+ * public, so each chunk-proof takes its own IV as public input and the verifier derives every chunk's IV from (iv, ciphertext) alone.  Nothing binds the chunk-proofs
+ * of one message to the same key (as in ECB).  The ECB entry points refuse a CBC key and the CBC ones refuse every other key. */
+/* host only, no GPU: ciphertext (message_len bytes) = AES-128-CBC(secret_key, iv, message) */
+int zkaes_cbc_ciphertext(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv[16], uint8_t *ciphertext);
+/* one proof over a CBC key for message_len bytes; zk_seed32 as zkaes_encrypt_seeded (NULL = test_rng seed).  ciphertext_or_null receives message_len bytes */
+int zkaes_encrypt_cbc_seeded(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv[16], const zkaes_pk *pk, const uint8_t *zk_seed32,
+                             uint8_t *ciphertext_or_null, uint8_t **proof, size_t *proof_len);
+/* chunk-proofs of a long CBC message, laid out as zkaes_encrypt_chunked's.  iv = the chaining value entering THIS call's first chunk: a job split over several calls or
+ * ranks takes each call's iv from zkaes_cbc_ciphertext (the 16 ciphertext bytes ahead of the call's first chunk).  The library runs the whole chain on the host first and
+ * then proves the chunks side by side; the device recomputes every chunk's chain from the chunk's IV alone.  Seeds and first_proof_index as in the ECB chunked calls:
+ * the unseeded call draws a fresh OS seed, NULL in the seeded one is the fixed test_rng stream (tests only). */
+int zkaes_encrypt_cbc_chunked(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv[16], const zkaes_pk *pk, uint8_t *ciphertext_or_null,
+                              uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks);
+int zkaes_encrypt_cbc_chunked_seeded_at(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv[16], const zkaes_pk *pk, const uint8_t *zk_seed32,
+                                        uint64_t first_proof_index, uint8_t *ciphertext_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks);
+/* as zkaes_aes_witness for a CBC key */
+int zkaes_aes_witness_cbc(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv[16], uint8_t *z, size_t z_cap, size_t *z_len);
+/* host only: as zkaes_verify_encryption over the public input (iv, ciphertext) */
+int zkaes_verify_encryption_cbc(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[16], const uint8_t *ciphertext, size_t ciphertext_len, int *accepted);
+/* host only, serial: n_chunks proofs (concatenated, proof_lens[j] bytes each) against ciphertext_len = n_chunks x chunk bytes; chunk j is checked under iv (j = 0) or the
+ * 16 ciphertext bytes ahead of its slice.  accepted_each (n_chunks ints) and n_accepted may be NULL; a chunk whose proof bytes do not parse counts as rejected */
+int zkaes_verify_cbc_chunked(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t iv[16], const uint8_t *ciphertext,
+                             size_t ciphertext_len, int *accepted_each, size_t *n_accepted);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

@@ -36,6 +36,20 @@ extern "C" {
     fn zkaes_pk_tables_built(pk: *const zkaes_pk, built: *mut c_int, table_bytes: *mut u64) -> c_int;
     fn zkaes_vk_serialize_ark(vk: *const zkaes_vk, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     fn zkaes_vk_deserialize_ark(bytes: *const u8, len: usize, vk: *mut *mut zkaes_vk) -> c_int;
+    // AES-128-CBC (include/zkaes.h, section "AES-128-CBC"; these declarations and the wrappers below were not compiled: no cargo in the build image)
+    fn zkaes_cbc_ciphertext(message: *const u8, message_len: usize, secret_key: *const u8, iv: *const u8, ciphertext: *mut u8) -> c_int;
+    fn zkaes_encrypt_cbc_seeded(message: *const u8, message_len: usize, secret_key: *const u8, iv: *const u8, pk: *const zkaes_pk, zk_seed32: *const u8,
+                                ciphertext_or_null: *mut u8, proof: *mut *mut u8, proof_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_cbc_chunked(message: *const u8, message_len: usize, secret_key: *const u8, iv: *const u8, pk: *const zkaes_pk, ciphertext_or_null: *mut u8,
+                                 proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize, n_chunks: usize) -> c_int;
+    fn zkaes_encrypt_cbc_chunked_seeded_at(message: *const u8, message_len: usize, secret_key: *const u8, iv: *const u8, pk: *const zkaes_pk, zk_seed32: *const u8,
+                                           first_proof_index: u64, ciphertext_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize,
+                                           n_chunks: usize) -> c_int;
+    fn zkaes_aes_witness_cbc(pk: *const zkaes_pk, message: *const u8, message_len: usize, secret_key: *const u8, iv: *const u8, z: *mut u8, z_cap: usize, z_len: *mut usize) -> c_int;
+    fn zkaes_verify_encryption_cbc(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv: *const u8, ciphertext: *const u8, ciphertext_len: usize,
+                                   accepted: *mut c_int) -> c_int;
+    fn zkaes_verify_cbc_chunked(vk: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, iv: *const u8, ciphertext: *const u8, ciphertext_len: usize,
+                                accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
@@ -193,4 +207,91 @@ pub fn encrypt_chunked(message: &[u8], secret_key: &[u8; 16], proving_key: &Prov
     let mut off = 0;
     for l in lens.iter().take(n) { out.push(blob[off..off + l].to_vec()); off += l; }
     Ok(out)
+}
+
+// ---- AES-128-CBC (not in the reference API; its README names CBC as the mode to follow ECB).  NOT COMPILED: no cargo in the build image.
+/// include/zkaes.h ZKAES_CIRCUIT_AES_CBC
+pub const CIRCUIT_AES_CBC: c_int = 3;
+
+/// A key for CBC chunks of `chunk_len` bytes (a non-zero multiple of 16) over the universal-SRS literals of src/lib.rs:141
+pub fn synthesize_keys_cbc(chunk_len: usize, flags: u32) -> Result<(ProvingKey, VerifyingKey)> {
+    let (mut pk, mut vk) = (std::ptr::null_mut(), std::ptr::null_mut());
+    if unsafe { zkaes_synthesize_keys_ex2(CIRCUIT_AES_CBC, chunk_len, 866_944, 513, 4_062_064, flags as c_uint, &mut pk, &mut vk) } != 0 { return Err(last_error()); }
+    Ok((ProvingKey(Arc::new(PkHandle(pk))), VerifyingKey(Arc::new(VkHandle(vk)))))
+}
+
+/// AES-128-CBC of whole blocks on the host (no GPU): the ciphertext, and the source of each call's `iv` when one job is split over several calls or ranks
+pub fn cbc_ciphertext(message: &[u8], secret_key: &[u8; 16], iv: &[u8; 16]) -> Result<Vec<u8>> {
+    let mut ct = vec![0u8; message.len()];
+    if unsafe { zkaes_cbc_ciphertext(message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), ct.as_mut_ptr()) } != 0 { return Err(last_error()); }
+    Ok(ct)
+}
+
+/// One proof that `ciphertext` is the CBC encryption under `iv` of a hidden message with a hidden key: (ciphertext, proof bytes).  `zk_seed = None`: the fixed test_rng stream
+pub fn encrypt_cbc(message: &[u8], secret_key: &[u8; 16], iv: &[u8; 16], proving_key: &ProvingKey, zk_seed: Option<&[u8; 32]>) -> Result<(Vec<u8>, Vec<u8>)> {
+    let mut ct = vec![0u8; message.len().max(1)];
+    let (mut p, mut n) = (std::ptr::null_mut(), 0usize);
+    let seed = zk_seed.map_or(std::ptr::null(), |s| s.as_ptr());
+    if unsafe { zkaes_encrypt_cbc_seeded(message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), (proving_key.0).0, seed, ct.as_mut_ptr(), &mut p, &mut n) } != 0 {
+        return Err(last_error());
+    }
+    ct.truncate(message.len());
+    Ok((ct, take_bytes(p, n)))
+}
+
+/// Long CBC messages: (ciphertext, chunk-proofs).  `iv` = the chaining value entering this call's first chunk; the chunks are independent statements because every
+/// chaining value is a public ciphertext block, so they are proven side by side exactly as `encrypt_chunked`'s.
+pub fn encrypt_cbc_chunked(message: &[u8], secret_key: &[u8; 16], iv: &[u8; 16], proving_key: &ProvingKey, chunk_len: usize, zk_seed: ZkSeed) -> Result<(Vec<u8>, Vec<Vec<u8>>)> {
+    if chunk_len == 0 || message.is_empty() || message.len() % chunk_len != 0 { return Err(anyhow!("message length must be a non-zero multiple of the key's plaintext length")); }
+    let n = message.len() / chunk_len;
+    let mut ct = vec![0u8; message.len()];
+    let (mut p, mut total) = (std::ptr::null_mut(), 0usize);
+    let mut lens = vec![0usize; n];
+    let (m, k, v, pk) = (message.as_ptr(), secret_key.as_ptr(), iv.as_ptr(), (proving_key.0).0);
+    let rc = match zk_seed {
+        ZkSeed::Fresh => unsafe { zkaes_encrypt_cbc_chunked(m, message.len(), k, v, pk, ct.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr(), n) },
+        ZkSeed::Seeded { seed, first_proof_index } => unsafe {
+            zkaes_encrypt_cbc_chunked_seeded_at(m, message.len(), k, v, pk, seed.as_ptr(), first_proof_index, ct.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr(), n)
+        },
+        ZkSeed::ReferenceParity => unsafe {
+            zkaes_encrypt_cbc_chunked_seeded_at(m, message.len(), k, v, pk, std::ptr::null(), 0, ct.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr(), n)
+        },
+    };
+    if rc != 0 { return Err(last_error()); }
+    let blob = take_bytes(p, total);
+    let mut out = Vec::with_capacity(n);
+    let mut off = 0;
+    for l in lens.iter() { out.push(blob[off..off + l].to_vec()); off += l; }
+    Ok((ct, out))
+}
+
+/// z (padded instance + witness, one byte per variable) of a CBC key
+pub fn aes_witness_cbc(proving_key: &ProvingKey, message: &[u8], secret_key: &[u8; 16], iv: &[u8; 16]) -> Result<Vec<u8>> {
+    let mut n = 0usize;
+    let pk = (proving_key.0).0;
+    if unsafe { zkaes_aes_witness_cbc(pk, message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), std::ptr::null_mut(), 0, &mut n) } != 0 { return Err(last_error()); }
+    let mut z = vec![0u8; n];
+    if unsafe { zkaes_aes_witness_cbc(pk, message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), z.as_mut_ptr(), n, &mut n) } != 0 { return Err(last_error()); }
+    Ok(z)
+}
+
+/// Ok(false) for a wrong IV or ciphertext, Err only for malformed input
+pub fn verify_encryption_cbc(verifying_key: &VerifyingKey, proof: &[u8], iv: &[u8; 16], ciphertext: &[u8]) -> Result<bool> {
+    let mut accepted: c_int = 0;
+    if unsafe { zkaes_verify_encryption_cbc((verifying_key.0).0, proof.as_ptr(), proof.len(), iv.as_ptr(), ciphertext.as_ptr(), ciphertext.len(), &mut accepted) } != 0 {
+        return Err(last_error());
+    }
+    Ok(accepted != 0)
+}
+
+/// One verdict per chunk-proof; chunk j is checked under `iv` (j = 0) or the 16 ciphertext bytes ahead of its slice -- derived here, from public data alone
+pub fn verify_cbc_chunked(verifying_key: &VerifyingKey, proofs: &[Vec<u8>], iv: &[u8; 16], ciphertext: &[u8]) -> Result<Vec<bool>> {
+    let blob: Vec<u8> = proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut each = vec![0 as c_int; proofs.len().max(1)];
+    let mut ok = 0usize;
+    if unsafe { zkaes_verify_cbc_chunked((verifying_key.0).0, blob.as_ptr(), lens.as_ptr(), proofs.len(), iv.as_ptr(), ciphertext.as_ptr(), ciphertext.len(), each.as_mut_ptr(), &mut ok) } != 0 {
+        return Err(last_error());
+    }
+    Ok(each.iter().take(proofs.len()).map(|&a| a != 0).collect())
 }
