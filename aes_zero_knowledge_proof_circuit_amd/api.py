@@ -7,6 +7,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 CIRCUIT_AES, CIRCUIT_OPS_XOR, CIRCUIT_OPS_ADD = 0, 1, 2
 CIRCUIT_AES_CBC = 3                # AES-128-CBC: public input = iv, ciphertext (include/zkaes.h, DESIGN.md "CBC")
+CIRCUIT_AES_CTR = 4                # AES-128-CTR, any byte length >= 1: public input = icb, ciphertext (include/zkaes.h, DESIGN.md "CTR")
 KEY_NO_TABLES = 1                  # zkaes_synthesize_keys_ex2 flag: no fixed-base window tables (saves 10-42 GB per key)
 PARITY = "parity"                  # zk_seed=PARITY: the reference's fixed ark_std::test_rng() stream for every proof (byte-parity tests only)
 
@@ -224,6 +225,41 @@ class ProvingKey:
             off += lens[i]
         return ct.raw[:len(message)], proofs
 
+    def witness_ctr(self, message, secret_key, icb):
+        """z (padded instance + witness, one byte per variable) of a CTR key: One, the 128 icb bits, the ciphertext bits, padding, then the witness"""
+        if len(secret_key) != 16 or len(icb) != 16:
+            raise ZkAesError("secret_key and icb must be 16 bytes")
+        n = C.c_size_t()
+        _check(lib().zkaes_aes_witness_ctr(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().zkaes_aes_witness_ctr(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), buf, n, C.byref(n)))
+        return buf.raw
+
+    def encrypt_ctr_chunked(self, message, secret_key, icb, zk_seed=None, first_proof_index=0):
+        """(ciphertext, chunk-proofs) of a long CTR message over a key for whole blocks; chunk j is proven under icb + j * (the key's blocks).  icb = the counter of this
+        call's first block (a job split over several calls passes ctr_counter_add(icb, blocks before)); zk_seed and first_proof_index as encrypt_chunked"""
+        if len(secret_key) != 16 or len(icb) != 16:
+            raise ZkAesError("secret_key and icb must be 16 bytes")
+        seed = self._seed_arg(zk_seed)
+        chunk = (self.info()["raw_instance"] - 129) // 8        # One + 128 icb bits, then 8 public-input bits per ciphertext byte
+        if chunk <= 0 or len(message) == 0 or len(message) % chunk:
+            raise ZkAesError("message length must be a non-zero multiple of the CTR key's plaintext length")
+        n_chunks = len(message) // chunk
+        lens = (C.c_size_t * n_chunks)()
+        ct = C.create_string_buffer(len(message))
+        out, n = C.c_void_p(), C.c_size_t()
+        if zk_seed is None:
+            _check(lib().zkaes_encrypt_ctr_chunked(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), self._p, ct, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
+        else:
+            _check(lib().zkaes_encrypt_ctr_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), self._p, seed, C.c_uint64(first_proof_index), ct,
+                                                             C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
+        blob = _take(out, n)
+        proofs, off = [], 0
+        for i in range(n_chunks):
+            proofs.append(blob[off:off + lens[i]])
+            off += lens[i]
+        return ct.raw[:len(message)], proofs
+
     def prove_ops(self, x, y, zk_seed=None):
         out, n = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_prove_ops(self._p, C.c_uint32(x), C.c_uint32(y), zk_seed, C.byref(out), C.byref(n)))
@@ -358,6 +394,56 @@ def verify_cbc_chunked(verifying_key, proofs, iv, ciphertext):
     each = (C.c_int * max(n, 1))()
     ok = C.c_size_t()
     _check(lib().zkaes_verify_cbc_chunked(verifying_key._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), bytes(iv), bytes(ciphertext), C.c_size_t(len(ciphertext)), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
+
+
+def ctr_crypt(data, secret_key, icb):
+    """AES-128-CTR of any byte length >= 1 on the host (zkaes_ctr_crypt; no GPU): encrypts and decrypts"""
+    if len(secret_key) != 16 or len(icb) != 16:
+        raise ZkAesError("secret_key and icb must be 16 bytes")
+    out = C.create_string_buffer(max(len(data), 1))
+    _check(lib().zkaes_ctr_crypt(bytes(data), C.c_size_t(len(data)), bytes(secret_key), bytes(icb), out))
+    return out.raw[:len(data)]
+
+
+def ctr_counter_add(icb, n_blocks):
+    """icb + n_blocks mod 2^128, the 16 bytes as one big-endian integer: the counter of the block n_blocks behind icb's"""
+    if len(icb) != 16 or not 0 <= n_blocks < 1 << 64:
+        raise ZkAesError("icb must be 16 bytes and n_blocks a 64-bit count")
+    out = C.create_string_buffer(16)
+    _check(lib().zkaes_ctr_counter_add(bytes(icb), C.c_uint64(n_blocks), out))
+    return out.raw
+
+
+def encrypt_ctr(message, secret_key, icb, proving_key, zk_seed=None):
+    """one proof over a CTR key -> (ciphertext, serialized MarlinProof bytes); zk_seed as encrypt"""
+    if len(secret_key) != 16 or len(icb) != 16:
+        raise ZkAesError("secret_key and icb must be 16 bytes")
+    ct = C.create_string_buffer(max(len(message), 1))
+    out, n = C.c_void_p(), C.c_size_t()
+    _check(lib().zkaes_encrypt_ctr_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), proving_key._p, zk_seed, ct, C.byref(out), C.byref(n)))
+    return ct.raw[:len(message)], _take(out, n)
+
+
+def verify_encryption_ctr(verifying_key, proof, icb, ciphertext):
+    """is `proof` a proof that `ciphertext` is the AES-128-CTR encryption from counter `icb` of a hidden message with a hidden key? -> bool.  A ciphertext whose length is
+    not the key's raises: the length is part of the statement"""
+    if len(icb) != 16:
+        raise ZkAesError("icb must be 16 bytes")
+    acc = C.c_int()
+    _check(lib().zkaes_verify_encryption_ctr(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(icb), bytes(ciphertext), C.c_size_t(len(ciphertext)), C.byref(acc)))
+    return bool(acc.value)
+
+
+def verify_ctr_chunked(verifying_key, proofs, icb, ciphertext):
+    """chunk-proofs of a long CTR message against (icb, ciphertext): chunk j is checked under icb + j * (blocks per chunk), from (icb, j) alone -> list of bools"""
+    if len(icb) != 16:
+        raise ZkAesError("icb must be 16 bytes")
+    n = len(proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each = (C.c_int * max(n, 1))()
+    ok = C.c_size_t()
+    _check(lib().zkaes_verify_ctr_chunked(verifying_key._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), bytes(icb), bytes(ciphertext), C.c_size_t(len(ciphertext)), each, C.byref(ok)))
     return [bool(each[i]) for i in range(n)]
 
 

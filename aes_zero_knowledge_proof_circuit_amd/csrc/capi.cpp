@@ -126,6 +126,45 @@ int zkaes_aes_witness_cbc(const zkaes_pk *pk, const uint8_t *msg, size_t len, co
         if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
     });
 }
+// ---- AES-128-CTR (include/zkaes.h): the prover side; zkaes_ctr_crypt, zkaes_ctr_counter_add and the verifiers are in capi_host.cpp
+int zkaes_encrypt_ctr_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *seed, uint8_t *ciphertext_or_null,
+                             uint8_t **proof, size_t *proof_len) {
+    return guard([&] {
+        if (!pk || !proof || !proof_len || !msg || !key || !icb) throw std::invalid_argument("null argument");
+        std::vector<uint8_t> ct(len ? len : 1);
+        auto b = zk::serialize_proof(pk->pk->prove_aes_ctr(msg, len, key, icb, seed, ct.data()));
+        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+        *proof = give(b); *proof_len = b.size();
+    });
+}
+int zkaes_encrypt_ctr_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
+                                        uint8_t *ciphertext_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || !key || !icb || !msg) throw std::invalid_argument("null argument");
+        if (pk->pk->circuit().kind != zk::CIRCUIT_AES_CTR) throw std::invalid_argument("proving key was not synthesized for the AES-CTR circuit");
+        size_t chunk = pk->pk->circuit().message_bytes;
+        if (chunk == 0 || chunk % 16) throw std::invalid_argument("CTR: a chunked call needs a key for whole blocks");
+        if (len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
+        std::vector<uint8_t> ct(len);
+        auto ps = pk->pk->prove_aes_ctr_chunked(msg, len, key, icb, pk->pk->contexts(), zk_seed32, first_proof_index, ct.data());
+        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+        pack_proofs(ps, proofs, proofs_len, proof_lens);
+    });
+}
+int zkaes_encrypt_ctr_chunked(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, uint8_t *ciphertext_or_null, uint8_t **proofs,
+                              size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
+    uint8_t seed[32];
+    { int rc = guard([&] { zk::os_random_seed(seed); }); if (rc) return rc; }
+    return zkaes_encrypt_ctr_chunked_seeded_at(msg, len, key, icb, pk, seed, 0, ciphertext_or_null, proofs, proofs_len, proof_lens, n_chunks);
+}
+int zkaes_aes_witness_ctr(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *z, size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        auto v = pk->pk->aes_witness_ctr(msg, len, key, icb);
+        if (z_len) *z_len = v.size();
+        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+    });
+}
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *seed, uint8_t **proof, size_t *proof_len) {
     return guard([&] {
         if (!pk || !proof || !proof_len) throw std::invalid_argument("null argument");

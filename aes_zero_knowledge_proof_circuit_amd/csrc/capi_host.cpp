@@ -6,7 +6,7 @@
 namespace {
 thread_local std::string g_err;
 zk::Circuit compile(int kind, size_t len) { return zk::compile_circuit(kind, len); }
-// the CBC instance without the leading One: 128 IV bits, then the ciphertext bits, each byte LSB first
+// the CBC (and CTR) instance without the leading One: 128 bits of the IV (the initial counter block), then the ciphertext bits, each byte LSB first
 std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
     std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 16), c = zk::ciphertext_to_public_input(ct, ct_len);
     pub.insert(pub.end(), c.begin(), c.end());
@@ -73,6 +73,65 @@ int zkaes_verify_cbc_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
             try {
                 zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
                 acc = zk::verify(vk->vk, cbc_public_input(j ? ct + chunk * j - 16 : iv, ct + chunk * j, chunk), p) ? 1 : 0;
+            } catch (const std::runtime_error &) { acc = 0; }
+            if (accepted_each) accepted_each[j] = acc;
+            ok += (size_t)acc;
+            off += proof_lens[j];
+        }
+        if (n_accepted) *n_accepted = ok;
+    });
+}
+// ---- AES-128-CTR.  The public input has the shape of CBC's: 128 bits of the initial counter block, then the ciphertext bits.
+int zkaes_ctr_crypt(const uint8_t *in, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *out) {
+    return guard([&] {
+        if (!in || !key || !icb || !out) throw std::invalid_argument("null argument");
+        if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
+        zk::aes128_ctr_crypt_host(in, len, key, icb, out);
+    });
+}
+int zkaes_ctr_counter_add(const uint8_t icb[16], uint64_t n_blocks, uint8_t out[16]) {
+    return guard([&] {
+        if (!icb || !out) throw std::invalid_argument("null argument");
+        zk::ctr_counter_add(icb, n_blocks, out);
+    });
+}
+namespace {
+// The verifier zero-pads the public input to |X| - 1, so a ciphertext with zero bytes appended would give the same padded vector: the byte length is part of the
+// statement and is checked against the key's own count.  A key that came through the ark transport carries only the padded count (marlin_codec.cpp); for such a key the
+// length is checked as far as |X| tells (zk::verify rejects another |X|) and the caller answers for the exact length.
+void require_ctr_length(const zk::VerifyingKey &vk, size_t ct_len) {
+    if (ct_len == 0) throw std::invalid_argument("CTR: the ciphertext must have at least one byte");
+    bool exact = vk.num_public_inputs + 1 != vk.num_instance;
+    if (exact && vk.num_public_inputs != 128 + 8 * ct_len) throw std::invalid_argument("CTR: the ciphertext length is not the one this key was synthesized for");
+}
+}  // namespace
+int zkaes_verify_encryption_ctr(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t icb[16], const uint8_t *ct, size_t ct_len, int *accepted) {
+    return guard([&] {
+        if (!vk || !proof || !icb || !ct || !accepted) throw std::invalid_argument("null argument");
+        *accepted = 0;
+        require_ctr_length(vk->vk, ct_len);
+        zk::Proof p = zk::deserialize_proof(proof, proof_len);
+        *accepted = zk::verify(vk->vk, cbc_public_input(icb, ct, ct_len), p) ? 1 : 0;
+    });
+}
+// Chunk j is checked against (icb + j nb, its slice of the ciphertext), nb = the chunk's blocks: the counter comes from (icb, j) alone, so any chunk can be checked
+// without the others.  A chunk whose proof bytes do not parse is a rejected chunk, not an error of the call.
+int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t icb[16], const uint8_t *ct, size_t ct_len,
+                             int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (!vk || !proofs || !proof_lens || !icb || !ct) throw std::invalid_argument("null argument");
+        if (n_accepted) *n_accepted = 0;
+        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks || (ct_len / n_chunks) % 16) throw std::invalid_argument("CTR: the ciphertext must be n_chunks x a non-zero multiple of 16 bytes");
+        const size_t chunk = ct_len / n_chunks;
+        require_ctr_length(vk->vk, chunk);
+        size_t off = 0, ok = 0;
+        for (size_t j = 0; j < n_chunks; j++) {
+            int acc = 0;
+            try {
+                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
+                uint8_t counter[16];
+                zk::ctr_counter_add(icb, (uint64_t)j * (chunk / 16), counter);
+                acc = zk::verify(vk->vk, cbc_public_input(counter, ct + chunk * j, chunk), p) ? 1 : 0;
             } catch (const std::runtime_error &) { acc = 0; }
             if (accepted_each) accepted_each[j] = acc;
             ok += (size_t)acc;

@@ -214,7 +214,7 @@ CsrMatrix finalize_matrix(const RawMatrix &m, uint32_t n_inst_padded, size_t row
 // ark-marlin padding (pad_input_for_indexer_and_prover + make_matrices_square) and final column numbering
 Circuit finish(Builder &b, int kind, size_t n_blocks, size_t trace_bytes) {
     Circuit c;
-    c.kind = kind; c.n_blocks = n_blocks; c.trace_bytes = trace_bytes;
+    c.kind = kind; c.n_blocks = n_blocks; c.message_bytes = 16 * n_blocks; c.trace_bytes = trace_bytes;
     c.raw_constraints = b.A.rowptr.size() - 1; c.raw_instance = b.n_instance; c.raw_witness = b.n_witness;
     size_t ninst = 1;
     while (ninst < b.n_instance) ninst <<= 1;
@@ -375,30 +375,78 @@ Circuit compile_aes_cbc_circuit(size_t len) {
     return finish(b, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb);
 }
 
+// Gate order: message and key witnesses, the 16 ICB bytes as inputs, the key schedule, per block (from the second on) the incrementer over the previous block's counter
+// bits, the block's rounds from CTR_b (so S_0 = CTR_b ^ key) and one xor gate per existing message bit, C = M ^ S_10; last the ciphertext inputs.  The instance is One,
+// 128 ICB bits, 8 len ciphertext bits.
+// Incrementer: counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8.  c_0 = 1, y_i = x_i ^ c_i, c_{i+1} = x_i & c_i (none behind i = 127: the sum is mod 2^128).
+// Position 0 folds away (y_0 = !x_0, c_1 = x_0), which leaves 127 xor and 126 and gates per increment.
+Circuit compile_aes_ctr_circuit(size_t len) {
+    if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
+    size_t nb = (len + 15) / 16;
+    const uint32_t ctr = (uint32_t)TR_CTR(nb);
+    auto slot = [&](size_t bi) { return ctr + (uint32_t)(TR_CTR_BLOCK0 + bi * TR_CTR_BLOCK_STRIDE); };
+    Builder b;
+    AesGates g(b);
+    std::vector<Byte> msg = g.alloc_message_and_key(len);
+    std::array<Byte, 16> cnt;
+    for (int i = 0; i < 16; i++) cnt[i] = b.alloc_byte(true, ctr + TR_CTR_ICB + (uint32_t)i);
+    g.key_schedule();
+    std::vector<Byte> ct(len);
+    for (size_t bi = 0; bi < nb; bi++) {
+        if (bi) {
+            std::array<Byte, 16> next;
+            Bit carry = Bit::konst(true);
+            for (int i = 0; i < 128; i++) {
+                uint32_t byte = (uint32_t)(15 - i / 8);
+                Bit x = cnt[byte][i % 8];
+                uint32_t mark = b.n_witness;
+                next[byte][i % 8] = b.bxor(x, carry);
+                b.tag_bytebit(next[byte][i % 8], mark, slot(bi) + TR_CTR_BL_CTR + byte, i % 8);
+                if (i == 127) break;
+                mark = b.n_witness;
+                carry = b.band(x, carry);
+                b.tag_bytebit(carry, mark, slot(bi) + TR_CTR_BL_CARRY + byte, i % 8);
+            }
+            cnt = next;
+        }
+        std::array<Byte, 16> s = g.block_rounds(cnt.data(), bi);
+        for (size_t i = 0; i < 16 && 16 * bi + i < len; i++) ct[16 * bi + i] = b.xor_byte(msg[16 * bi + i], s[i], slot(bi) + TR_CTR_BL_CT + (uint32_t)i);
+    }
+    for (size_t i = 0; i < len; i++) {
+        Byte pi = b.alloc_byte(true, slot(i / 16) + TR_CTR_BL_CT + (uint32_t)(i % 16));
+        for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
+    }
+    Circuit c = finish(b, CIRCUIT_AES_CTR, nb, TR_CTR_BYTES(nb));
+    c.message_bytes = len;
+    return c;
+}
+
 Circuit compile_circuit(int kind, size_t message_len) {
     if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len);
     if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len);
+    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len);
     return compile_ops_circuit(kind);
 }
 
-void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out) {
-    if (len % 16) throw std::invalid_argument("CBC: the message must be a multiple of 16 bytes");
-    uint8_t sb[256];
-    for (int i = 0; i < 256; i++) sb[i] = aes_sbox_value((uint8_t)i);
-    auto xt = [](uint8_t c) { return (uint8_t)((c << 1) ^ ((c >> 7) * 0x1B)); };
-    uint8_t rk[11][16];                                                       // FIPS-197 5.2, round keys as 16 bytes in word order
-    for (int i = 0; i < 16; i++) rk[0][i] = key[i];
-    uint8_t rc = 1;
-    for (int r = 1; r <= 10; r++) {
-        const uint8_t *p = rk[r - 1];
-        uint8_t t[4] = {(uint8_t)(sb[p[13]] ^ rc), sb[p[14]], sb[p[15]], sb[p[12]]};
-        for (int i = 0; i < 16; i++) rk[r][i] = (uint8_t)(p[i] ^ (i < 4 ? t[i] : rk[r][i - 4]));
-        rc = xt(rc);
+namespace {
+// plain byte-wise AES-128 over aes_sbox_value for the host-side modes
+struct HostAes128 {
+    uint8_t sb[256], rk[11][16];                                              // FIPS-197 5.2, round keys as 16 bytes in word order
+    static uint8_t xt(uint8_t c) { return (uint8_t)((c << 1) ^ ((c >> 7) * 0x1B)); }
+    explicit HostAes128(const uint8_t key[16]) {
+        for (int i = 0; i < 256; i++) sb[i] = aes_sbox_value((uint8_t)i);
+        for (int i = 0; i < 16; i++) rk[0][i] = key[i];
+        uint8_t rc = 1;
+        for (int r = 1; r <= 10; r++) {
+            const uint8_t *p = rk[r - 1];
+            uint8_t t[4] = {(uint8_t)(sb[p[13]] ^ rc), sb[p[14]], sb[p[15]], sb[p[12]]};
+            for (int i = 0; i < 16; i++) rk[r][i] = (uint8_t)(p[i] ^ (i < 4 ? t[i] : rk[r][i - 4]));
+            rc = xt(rc);
+        }
     }
-    uint8_t prev[16], s[16], u[16];
-    for (int i = 0; i < 16; i++) prev[i] = iv[i];
-    for (size_t off = 0; off < len; off += 16) {
-        for (int i = 0; i < 16; i++) s[i] = (uint8_t)(msg[off + i] ^ prev[i] ^ rk[0][i]);
+    void encrypt_block(uint8_t s[16]) const {                                 // in place
+        uint8_t u[16];
+        for (int i = 0; i < 16; i++) s[i] ^= rk[0][i];
         for (int r = 1; r <= 10; r++) {
             for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = sb[s[4 * ((c + rr) & 3) + rr]];     // SubBytes + ShiftRows
             for (int c = 0; c < 4; c++) {
@@ -407,7 +455,39 @@ void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[1
                     s[4 * c + k] = (uint8_t)((r <= 9 ? xt(a[k]) ^ xt(a[(k + 1) & 3]) ^ a[(k + 1) & 3] ^ a[(k + 2) & 3] ^ a[(k + 3) & 3] : a[k]) ^ rk[r][4 * c + k]);
             }
         }
+    }
+};
+}  // namespace
+
+void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out) {
+    if (len % 16) throw std::invalid_argument("CBC: the message must be a multiple of 16 bytes");
+    HostAes128 aes(key);
+    uint8_t prev[16], s[16];
+    for (int i = 0; i < 16; i++) prev[i] = iv[i];
+    for (size_t off = 0; off < len; off += 16) {
+        for (int i = 0; i < 16; i++) s[i] = (uint8_t)(msg[off + i] ^ prev[i]);
+        aes.encrypt_block(s);
         for (int i = 0; i < 16; i++) out[off + i] = prev[i] = s[i];
+    }
+}
+
+void ctr_counter_add(const uint8_t counter[16], uint64_t n, uint8_t out[16]) {
+    unsigned carry = 0;
+    for (int i = 15; i >= 0; i--) {
+        unsigned t = counter[i] + (unsigned)(n & 0xff) + carry;
+        out[i] = (uint8_t)t; carry = t >> 8; n >>= 8;
+    }
+}
+
+void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *out) {
+    HostAes128 aes(key);
+    uint8_t ctr[16], s[16];
+    for (int i = 0; i < 16; i++) ctr[i] = icb[i];
+    for (size_t off = 0; off < len; off += 16) {
+        for (int i = 0; i < 16; i++) s[i] = ctr[i];
+        aes.encrypt_block(s);
+        for (size_t i = 0; i < 16 && off + i < len; i++) out[off + i] = (uint8_t)(in[off + i] ^ s[i]);
+        ctr_counter_add(ctr, 1, ctr);
     }
 }
 

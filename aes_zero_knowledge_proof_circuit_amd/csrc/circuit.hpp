@@ -22,11 +22,12 @@ struct CsrMatrix {
     size_t nnz() const { return col.size(); }
 };
 
-enum CircuitKind { CIRCUIT_AES = 0, CIRCUIT_OPS_XOR = 1, CIRCUIT_OPS_ADD = 2, CIRCUIT_AES_CBC = 3 };
+enum CircuitKind { CIRCUIT_AES = 0, CIRCUIT_OPS_XOR = 1, CIRCUIT_OPS_ADD = 2, CIRCUIT_AES_CBC = 3, CIRCUIT_AES_CTR = 4 };
 
 struct Circuit {
     int kind = CIRCUIT_AES;
     size_t n_blocks = 0;
+    size_t message_bytes = 0;            // the statement's byte length: 16 n_blocks, except for a CTR key, whose last block may be partial (0 for the ops kinds)
     // before padding (what debug_constraint_system_status would log, src/helpers/mod.rs:73-81)
     size_t raw_constraints = 0, raw_instance = 0, raw_witness = 0;
     // after ark-marlin padding
@@ -45,10 +46,18 @@ Circuit compile_ops_circuit(int kind);
 // AES-128-CBC over the same gadgets (no upstream counterpart; DESIGN.md "CBC"): public = 16 IV bytes then the ciphertext, private = message and key;
 // per block X_b = M_b ^ C_{b-1} (C_{-1} = IV) ahead of the block's round 0.  message_len must be a non-zero multiple of 16 (else std::invalid_argument)
 Circuit compile_aes_cbc_circuit(size_t message_len);
-// kind = CIRCUIT_AES, CIRCUIT_AES_CBC, or an ops kind (message_len ignored)
+// AES-128-CTR over the same gadgets (DESIGN.md "CTR"): public = the 16 bytes of the initial counter block then the ciphertext, private = message and key;
+// CTR_0 = icb, CTR_b = CTR_{b-1} + 1 mod 2^128 (big-endian, SP 800-38A B.1 with m = 128), C_b = M_b ^ AES(key, CTR_b), the last block cut to the bytes that exist.
+// message_len is any byte count >= 1 (else std::invalid_argument)
+Circuit compile_aes_ctr_circuit(size_t message_len);
+// kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, or an ops kind (message_len ignored)
 Circuit compile_circuit(int kind, size_t message_len);
 uint8_t aes_sbox_value(uint8_t x);   // the lookup table of src/aes_circuit.rs:433-694
 // plain byte-wise AES-128-CBC over aes_sbox_value, host only: out = len bytes, len a multiple of 16
 void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out);
+// AES-128-CTR on the host, encryption and decryption alike: out = len bytes (any len), block b under the counter icb + b
+void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *out);
+// out = counter + n mod 2^128, the 16 bytes read as one big-endian integer (out may alias counter)
+void ctr_counter_add(const uint8_t counter[16], uint64_t n, uint8_t out[16]);
 
 }  // namespace zk

@@ -252,6 +252,9 @@ void upload_sbox(const uint8_t table[256]);
 void aes_trace(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, uint32_t nproofs, uint32_t nblocks, stream_t s);
 // CBC: ivs = nproofs x 16 bytes (device), the chaining value entering each proof's first block; the trace (stride >= the CBC layout's bytes) gains the IV and X_b tail
 void aes_trace_cbc(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s);
+// CTR: icbs = nproofs x 16 bytes (device), each proof's initial counter block; msgs = nproofs x msg_len bytes, packed, msg_len >= 1 and any value (ceil(msg_len / 16)
+// blocks, the last one partial); the trace (stride >= TR_CTR_BYTES) gains the counter tail
+void aes_trace_ctr(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *icbs, uint32_t nproofs, uint32_t msg_len, stream_t s);
 // z[col] (0/1 bytes) for every column, by descriptor
 void witness_expand(uint8_t *z, const uint32_t *desc, uint32_t ncols, const uint8_t *trace, const uint32_t *sbox_in_off, const uint32_t *sbox_tmpl, stream_t s);
 // out[r] = sum_i coeff[i] * z[col[i]] as a field element, rows with no entries give 0 (out has `rows_out` >= rows entries, tail zeroed)

@@ -4,6 +4,8 @@
 // (every UInt8/Boolean op there both allocates a variable and computes its value on the CPU): here
 //   k_aes_trace       one lane per block: plain AES-128 with every intermediate byte the circuit names written to the
 //                     per-proof trace buffer (layout: trace_layout.h); the mode (ECB / CBC) is a template parameter,
+//   k_aes_trace_ctr   the same for AES-128-CTR: a lane derives its block's counter and the incrementer's carries from the
+//                     initial counter block, and the last block of a message may be partial,
 //   k_witness_expand  one lane per column of z: decode the variable's descriptor (compiled once by circuit.cpp) and gather
 //                     its bit -- S-box mux-tree variables are a table lookup S[(node << (level+1)) | (x & mask)],
 //   k_spmv_bits       z_A = A z, z_B = B z over 0/1 assignments with small integer coefficients (ark-marlin prover_init),
@@ -65,6 +67,25 @@ __device__ __forceinline__ void aes_block_rounds(uint8_t s[16], const uint8_t (*
     }
 }
 
+// The key schedule (src/aes_circuit.rs:83-113): words big-endian, RotWord = bytes rotate-left 1.  Every lane needs w; the one lane per proof that owns the key-schedule
+// part of the trace passes `tr` and gets the SubWord bytes and the words ahead of the Rcon xor stored, the others pass null.
+__device__ __forceinline__ void aes_key_schedule(const uint8_t *__restrict__ key, const uint8_t *__restrict__ sbox, uint8_t (*w)[4], uint8_t *__restrict__ tr) {
+    const uint8_t rc[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
+    for (int i = 0; i < 4; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
+    for (int i = 4; i < 44; i++) {
+        if (i % 4 == 0) {
+            int q = i / 4 - 1;
+            uint8_t sub[4], pre[4];
+            for (int k = 0; k < 4; k++) sub[k] = sbox[w[i - 1][(k + 1) & 3]];
+            for (int k = 0; k < 4; k++) { pre[k] = w[i - 4][k] ^ sub[k]; w[i][k] = pre[k]; }
+            w[i][0] ^= rc[q];
+            if (tr) for (int k = 0; k < 4; k++) { tr[TR_KS_SUB + 4 * q + k] = sub[k]; tr[TR_KS_PRE + 4 * q + k] = pre[k]; }
+        } else {
+            for (int k = 0; k < 4; k++) w[i][k] = w[i - 4][k] ^ w[i - 1][k];
+        }
+    }
+}
+
 // grid: nproofs * (nblocks + 1) lanes; lane (p, 0) writes the key schedule part, lane (p, 1 + b) block b.
 // CBC: lane (p, 0) also stores the proof's IV in the trace tail; lane (p, 1 + b) starts from prev = ivs[p], runs plain AES without stores over blocks 0 .. b - 1 to reach
 // its own chaining value (at most nblocks - 1 extra blocks per lane), stores X_b = M_b ^ prev in the tail and goes on from s = X_b ^ key with all the usual stores.  The
@@ -77,22 +98,8 @@ __global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const ui
     uint32_t p = t / (nblocks + 1), which = t % (nblocks + 1);
     uint8_t *tr = trace + (size_t)p * stride;
     const uint8_t *key = keys + 16 * (size_t)p;
-    // key schedule (src/aes_circuit.rs:83-113): words big-endian, RotWord = bytes rotate-left 1
     uint8_t w[44][4];
-    const uint8_t rc[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
-    for (int i = 0; i < 4; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
-    for (int i = 4; i < 44; i++) {
-        if (i % 4 == 0) {
-            int q = i / 4 - 1;
-            uint8_t sub[4], pre[4];
-            for (int k = 0; k < 4; k++) sub[k] = sbox[w[i - 1][(k + 1) & 3]];
-            for (int k = 0; k < 4; k++) { pre[k] = w[i - 4][k] ^ sub[k]; w[i][k] = pre[k]; }
-            w[i][0] ^= rc[q];
-            if (which == 0) for (int k = 0; k < 4; k++) { tr[TR_KS_SUB + 4 * q + k] = sub[k]; tr[TR_KS_PRE + 4 * q + k] = pre[k]; }
-        } else {
-            for (int k = 0; k < 4; k++) w[i][k] = w[i - 4][k] ^ w[i - 1][k];
-        }
-    }
+    aes_key_schedule(key, sbox, w, which == 0 ? tr : nullptr);
     uint8_t *tail = tr + TR_CBC((size_t)nblocks);          // (CBC only)
     if (which == 0) {
         for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
@@ -122,6 +129,50 @@ __global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const ui
     }
     aes_block_rounds<true>(s, w, sbox, bl);
 }
+
+// out = in + n mod 2^128 over 16 big-endian bytes
+__device__ __forceinline__ void ctr_add(const uint8_t *__restrict__ in, uint32_t n, uint8_t out[16]) {
+    uint32_t c = n;
+    for (int i = 15; i >= 0; i--) { uint32_t t = in[i] + (c & 0xff); out[i] = (uint8_t)t; c = (c >> 8) + (t >> 8); }
+}
+
+// CTR: the same grid.  Lane (p, 0) writes the key schedule part and the proof's initial counter block; lane (p, 1 + b) computes CTR_b = icbs[p] + b itself, the carries
+// K_b of CTR_{b-1} + 1 (trace_layout.h), runs the block's rounds from CTR_b ^ key and stores C_b = M_b ^ S_10.  Messages are packed at msg_len bytes per proof,
+// nblocks = ceil(msg_len / 16): the last block's lane reads only the bytes below msg_len and fills the rest of its message and C slots with zeros.  Blocks do not depend
+// on one another, so no lane walks a chain, and the kernel is handed the counter only, never a keystream made on the host.
+__global__ void k_aes_trace_ctr(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ icbs,
+                                uint32_t nproofs, uint32_t nblocks, uint32_t msg_len, const uint8_t *__restrict__ sbox) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nproofs * (nblocks + 1)) return;
+    uint32_t p = t / (nblocks + 1), which = t % (nblocks + 1);
+    uint8_t *tr = trace + (size_t)p * stride;
+    const uint8_t *key = keys + 16 * (size_t)p, *icb = icbs + 16 * (size_t)p;
+    uint8_t w[44][4];
+    aes_key_schedule(key, sbox, w, which == 0 ? tr : nullptr);
+    uint8_t *tail = tr + TR_CTR((size_t)nblocks);
+    if (which == 0) {
+        for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
+        for (int i = 0; i < 44; i++) for (int k = 0; k < 4; k++) tr[TR_KS_W + 4 * i + k] = w[i][k];
+        for (int i = 0; i < 16; i++) tail[TR_CTR_ICB + i] = icb[i];
+        return;
+    }
+    uint32_t b = which - 1;
+    uint8_t *bl = tr + TR_BLOCK0 + (size_t)b * TR_BLOCK_STRIDE, *slot = tail + TR_CTR_BLOCK0 + (size_t)b * TR_CTR_BLOCK_STRIDE;
+    uint8_t ctr[16], carry[16], s[16], m[16];
+    ctr_add(icb, b, ctr);
+    for (int i = 0; i < 16; i++) carry[i] = 0;
+    if (b) {
+        uint8_t prev[16];
+        ctr_add(icb, b - 1, prev);
+        for (int i = 0; i < 128 && ((prev[15 - i / 8] >> (i % 8)) & 1); i++) carry[15 - i / 8] |= (uint8_t)(1u << (i % 8));
+    }
+    uint32_t have = msg_len - 16 * b < 16 ? msg_len - 16 * b : 16;          // (16 b < msg_len: nblocks = ceil(msg_len / 16))
+    const uint8_t *msg = msgs + (size_t)p * msg_len + 16 * (size_t)b;
+    for (uint32_t i = 0; i < 16; i++) m[i] = i < have ? msg[i] : 0;
+    for (int i = 0; i < 16; i++) { slot[TR_CTR_BL_CTR + i] = ctr[i]; slot[TR_CTR_BL_CARRY + i] = carry[i]; bl[TR_BL_MSG + i] = m[i]; s[i] = ctr[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
+    aes_block_rounds<true>(s, w, sbox, bl);
+    for (uint32_t i = 0; i < 16; i++) slot[TR_CTR_BL_CT + i] = i < have ? (uint8_t)(m[i] ^ s[i]) : 0;
+}
 template <bool CBC>
 static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s) {
     uint8_t *g_sbox = sbox_here();
@@ -137,6 +188,17 @@ void aes_trace_cbc(uint8_t *trace, size_t stride, const uint8_t *msgs, const uin
     if (!ivs) throw GpuError("aes_trace_cbc: no IV buffer");
     if (stride < TR_CBC((size_t)nblocks) + TR_CBC_X + 16 * (size_t)nblocks) throw GpuError("aes_trace_cbc: trace stride is short of the CBC tail");
     launch_aes_trace<true>("aes_trace_cbc", trace, stride, msgs, keys, ivs, nproofs, nblocks, s);
+}
+void aes_trace_ctr(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *icbs, uint32_t nproofs, uint32_t msg_len, stream_t s) {
+    if (!icbs) throw GpuError("aes_trace_ctr: no counter buffer");
+    if (msg_len == 0 || msg_len > 0xfffffff0u) throw GpuError("aes_trace_ctr: the message length must be 1 .. 2^32 - 16 bytes");
+    uint32_t nblocks = (msg_len + 15) / 16;
+    if (stride < TR_CTR_BYTES((size_t)nblocks)) throw GpuError("aes_trace_ctr: trace stride is short of the CTR tail");
+    uint8_t *g_sbox = sbox_here();
+    if (!g_sbox) throw GpuError("aes_trace_ctr: S-box table not uploaded on this device");
+    uint32_t lanes = nproofs * (nblocks + 1);
+    hipLaunchKernelGGL(k_aes_trace_ctr, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, icbs, nproofs, nblocks, msg_len, g_sbox);
+    HIP_LAUNCH_CHECK();
 }
 
 __global__ void k_witness_expand(uint8_t *__restrict__ z, const uint32_t *__restrict__ desc, uint32_t ncols, const uint8_t *__restrict__ trace,

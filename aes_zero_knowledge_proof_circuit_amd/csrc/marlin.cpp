@@ -237,7 +237,7 @@ struct ProverContext {
     std::mutex in_use;                                // one proof at a time per context: concurrent callers of one key queue up here
     gpu::StreamGuard stream;
     gpu::WorkspaceGuard msm_ws;
-    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key, d_iv;     // (d_iv: the chaining value entering the proof's first block, CBC keys)
+    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key, d_iv;     // (d_iv: the chaining value entering the proof's first block, CBC keys; the proof's initial counter block, CTR keys)
     DevPtr<void> d_rng;                               // scratch of the device-side ChaCha12 / Fr::rand stream
     DevPtr<int8_t> d_cls[3];                          // small-integer evaluation classes of w, z_A, z_B on H (Lagrange-basis commitments)
     DevPtr<F> za_ev, zb_ev, x_poly, x_tmp, x_evals, tmp_n, ra_ev, ra_poly, zpoly, t_partial;
@@ -658,6 +658,11 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
         if (!iv) throw std::invalid_argument("a CBC proving key needs an IV");
         gpu::h2d(cx.d_iv, iv, 16, s);
         gpu::aes_trace_cbc(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.n_blocks, s);
+    } else if (c.kind == CIRCUIT_AES_CTR) {
+        if (!iv) throw std::invalid_argument("a CTR proving key needs an initial counter block");
+        if (len != c.message_bytes) throw std::invalid_argument("a CTR trace takes exactly the key's message length");
+        gpu::h2d(cx.d_iv, iv, 16, s);
+        gpu::aes_trace_ctr(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, s);
     } else {
         gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s);
     }
@@ -1021,29 +1026,8 @@ std::string ProvingKey::op_lists_json(const uint8_t *message, size_t len, const 
     o += "]}";
     return o;
 }
-std::vector<uint8_t> ProvingKey::aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]) {
-    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
-    if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
-    const Circuit &c = impl->circuit;
-    ProverContext &cx = impl->context(0);
-    std::lock_guard<std::mutex> busy(cx.in_use);
-    gpu::stream_t s = cx.stream;
-    impl->launch_trace(cx, message, len, key, nullptr);
-    gpu::witness_expand(cx.d_z, impl->d_desc, (uint32_t)c.num_variables(), cx.d_trace, impl->d_sbox_in, impl->d_sbox_tmpl, s);
-    std::vector<uint8_t> z(c.num_variables());
-    gpu::d2h(z.data(), cx.d_z, z.size(), s);
-    return z;
-}
-// ---- AES-128-CBC.  The statement, the public-input layout and why chunk-proofs stay independent: DESIGN.md "CBC".
-static void require_cbc_key(const Circuit &c, size_t len) {
-    if (c.kind != CIRCUIT_AES_CBC) throw std::invalid_argument("proving key was not synthesized for the AES-CBC circuit");
-    if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
-}
-std::vector<uint8_t> ProvingKey::aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]) {
-    require_cbc_key(impl->circuit, len);
-    if (!message || !key || !iv) throw std::invalid_argument("null argument");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
+// witness generation only, on context 0: message, key (, IV or counter) -> trace -> z, by the key's mode; the callers have checked the key and the length
+static std::vector<uint8_t> witness_of(ProvingKeyImpl *impl, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *iv) {
     const Circuit &c = impl->circuit;
     ProverContext &cx = impl->context(0);
     std::lock_guard<std::mutex> busy(cx.in_use);
@@ -1054,12 +1038,47 @@ std::vector<uint8_t> ProvingKey::aes_witness_cbc(const uint8_t *message, size_t 
     gpu::d2h(z.data(), cx.d_z, z.size(), s);
     return z;
 }
+std::vector<uint8_t> ProvingKey::aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]) {
+    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
+    if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
+    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
+    return witness_of(impl, message, len, key, nullptr);
+}
+// ---- AES-128-CBC.  The statement, the public-input layout and why chunk-proofs stay independent: DESIGN.md "CBC".
+static void require_cbc_key(const Circuit &c, size_t len) {
+    if (c.kind != CIRCUIT_AES_CBC) throw std::invalid_argument("proving key was not synthesized for the AES-CBC circuit");
+    if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
+}
+std::vector<uint8_t> ProvingKey::aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]) {
+    require_cbc_key(impl->circuit, len);
+    if (!message || !key || !iv) throw std::invalid_argument("null argument");
+    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
+    return witness_of(impl, message, len, key, iv);
+}
 Proof ProvingKey::prove_aes_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null) {
     require_cbc_key(impl->circuit, len);
     if (!message || !key || !iv) throw std::invalid_argument("null argument");
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
     if (ciphertext_or_null) aes128_cbc_encrypt_host(message, len, key, iv, ciphertext_or_null);
     return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, iv);
+}
+// ---- AES-128-CTR.  The statement, the input layout, the incrementer and why chunk-proofs are seekable: DESIGN.md "CTR".
+static void require_ctr_key(const Circuit &c, const uint8_t *message, const uint8_t *key, const uint8_t *icb) {
+    if (c.kind != CIRCUIT_AES_CTR) throw std::invalid_argument("proving key was not synthesized for the AES-CTR circuit");
+    if (!message || !key || !icb) throw std::invalid_argument("null argument");
+}
+std::vector<uint8_t> ProvingKey::aes_witness_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16]) {
+    const Circuit &c = impl->circuit;
+    require_ctr_key(c, message, key, icb);
+    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
+    return witness_of(impl, message, len, key, icb);
+}
+Proof ProvingKey::prove_aes_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null) {
+    const Circuit &c = impl->circuit;
+    require_ctr_key(c, message, key, icb);
+    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
+    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null);
+    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, icb);
 }
 // zero-knowledge randomness of proof i of a chunked / batch call: the caller's seed is domain-separated per proof, Blake2s(seed || (offset + i) as u64 LE),
 // so no two proofs share rho, the KZG hiding coefficients or the mask polynomial -- across calls and ranks too when they pass job-global offsets.
@@ -1079,7 +1098,7 @@ static void derive_zk_seed(uint8_t out[32], const uint8_t *seed32, uint64_t inde
     for (int i = 0; i < 8; i++) buf[32 + i] = (uint8_t)(index >> (8 * i));
     Blake2s::digest(out, buf, sizeof buf);
 }
-// ivs: nullptr (ECB), or n_chunks x 16 bytes -- the chaining value entering each chunk (CBC)
+// ivs: nullptr (ECB), or n_chunks x 16 bytes -- the chaining value entering each chunk (CBC), each chunk's first counter block (CTR)
 static std::vector<Proof> prove_many(ProvingKeyImpl *impl, const uint8_t *messages, const uint8_t *keys, size_t key_stride, size_t n_chunks, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
                                      const uint8_t *ivs) {
     size_t chunk = impl->circuit.n_blocks * 16;
@@ -1136,6 +1155,21 @@ std::vector<Proof> ProvingKey::prove_aes_cbc_chunked(const uint8_t *message, siz
     for (size_t j = 0; j < n_chunks; j++) memcpy(&ivs[16 * j], j ? &ct[chunk * j - 16] : iv, 16);
     std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, ivs.data());
     if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+    return proofs;
+}
+std::vector<Proof> ProvingKey::prove_aes_ctr_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
+                                                     uint8_t *ciphertext_or_null) {
+    const Circuit &c = impl->circuit;
+    require_ctr_key(c, message, key, icb);
+    size_t chunk = c.message_bytes;
+    if (chunk % 16) throw std::invalid_argument("CTR: a chunked call needs a key for whole blocks (this one was synthesized for " + std::to_string(chunk) + " bytes)");
+    if (len == 0 || len % chunk) throw std::invalid_argument("message length must be a non-zero multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
+    // chunk j starts at block j nb of this call, so its counter is icb + j nb: nothing runs ahead of the contexts, and any chunk can be proven from (icb, offset) alone
+    size_t n_chunks = len / chunk;
+    std::vector<uint8_t> icbs(16 * n_chunks);
+    for (size_t j = 0; j < n_chunks; j++) ctr_counter_add(icb, (uint64_t)j * c.n_blocks, &icbs[16 * j]);
+    std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, icbs.data());
+    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null);
     return proofs;
 }
 Proof ProvingKey::prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed) {

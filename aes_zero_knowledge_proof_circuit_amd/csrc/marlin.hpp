@@ -81,6 +81,14 @@ class ProvingKey {
     std::vector<Proof> prove_aes_cbc_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], size_t n_contexts, const uint8_t *zk_seed = nullptr,
                                              uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr);
     std::vector<uint8_t> aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]);
+    // ---- AES-128-CTR (keys of kind CIRCUIT_AES_CTR only; every other call refuses such a key).  Public input: icb, ciphertext; len = the key's byte length, any value >= 1.
+    // one proof; ciphertext_or_null receives len bytes of the host's CTR encryption (the device derives every counter and keystream block from icb alone)
+    Proof prove_aes_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr);
+    // chunk-proofs of a long CTR message over a key for whole blocks: chunk j is proven under icb + j * (the key's blocks); icb = the counter of this call's first block
+    // (a job split over calls or ranks passes ctr_counter_add(icb, blocks before)).  Nothing serial runs ahead of the contexts.  Seeds as prove_aes_chunked.
+    std::vector<Proof> prove_aes_ctr_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], size_t n_contexts, const uint8_t *zk_seed = nullptr,
+                                             uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr);
+    std::vector<uint8_t> aes_witness_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16]);
     // witness generation only (kernels aes_trace + witness_expand): z = padded instance || witness, one byte per variable
     std::vector<uint8_t> aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]);
     const ProverTimings &last_timings() const;

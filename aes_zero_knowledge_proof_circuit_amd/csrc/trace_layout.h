@@ -16,6 +16,12 @@
 //   CBC keys only, behind the nb blocks (cbc = TR_CBC(nb)); a block's "message block" stays the plaintext M_b and its S_0 is X_b ^ key:
 //       cbc + 0          IV (16)
 //       cbc + 16 + 16 b  X_b = M_b ^ C_{b-1}, C_{-1} = IV: what enters round 0 of block b    nb x 16
+//   CTR keys only, at the same base (ctr = TR_CTR(nb)); a block's "message block" is M_b with zeros beyond the message's last byte and its S_0 is CTR_b ^ key:
+//       ctr + 0               ICB, the initial counter block (16)
+//       ctr + 16 + 48 b       CTR_b = ICB + b mod 2^128, big-endian (16)
+//       ctr + 16 + 48 b + 16  K_b (16): the carries of CTR_{b-1} + 1.  Counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8; bit i of K_b, in the same mapping,
+//                             is the carry out of position i, i.e. 1 iff bits 0..i of CTR_{b-1} are all one.  K_0 = 0
+//       ctr + 16 + 48 b + 32  C_b = M_b ^ S_10 (16), zero beyond the message's last byte
 #pragma once
 #define TR_KEY 0
 #define TR_KS_W 16
@@ -31,6 +37,14 @@
 #define TR_CBC(nb) (TR_BLOCK0 + (nb) * TR_BLOCK_STRIDE)
 #define TR_CBC_IV 0
 #define TR_CBC_X 16
+#define TR_CTR(nb) TR_CBC(nb)
+#define TR_CTR_ICB 0
+#define TR_CTR_BLOCK0 16
+#define TR_CTR_BLOCK_STRIDE 48
+#define TR_CTR_BL_CTR 0
+#define TR_CTR_BL_CARRY 16
+#define TR_CTR_BL_CT 32
+#define TR_CTR_BYTES(nb) (TR_CTR(nb) + TR_CTR_BLOCK0 + (nb) * TR_CTR_BLOCK_STRIDE)
 #define TR_SBOX_PER_BLOCK 160
 #define TR_SBOX_KS 40
 

@@ -67,6 +67,7 @@ int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out,
 #define ZKAES_CIRCUIT_AES 0      /* src/lib.rs:176-293 */
 #define ZKAES_CIRCUIT_OPS_XOR 1  /* src/ops.rs:8-18 (as a BLS12-377 Marlin circuit) */
 #define ZKAES_CIRCUIT_OPS_ADD 2  /* src/ops.rs:20-29 */
+#define ZKAES_CIRCUIT_AES_CTR 4  /* AES-128-CTR for any byte length >= 1 (no upstream counterpart; section "AES-128-CTR" below); accepted by the same calls as ZKAES_CIRCUIT_AES_CBC */
 #define ZKAES_CIRCUIT_AES_CBC 3  /* AES-128-CBC (no upstream counterpart; section "AES-128-CBC" below); accepted by zkaes_synthesize_keys_ex / _ex2, zkaes_circuit_info, zkaes_circuit_matrix */
 /* as zkaes_synthesize_keys with an explicit circuit kind and universal-SRS literals (generate_universal_srs arguments) */
 int zkaes_synthesize_keys_ex(int circuit_kind, size_t plaintext_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, zkaes_pk **pk,
@@ -139,6 +140,41 @@ int zkaes_verify_encryption_cbc(const zkaes_vk *vk, const uint8_t *proof, size_t
 /* host only, serial: n_chunks proofs (concatenated, proof_lens[j] bytes each) against ciphertext_len = n_chunks x chunk bytes; chunk j is checked under iv (j = 0) or the
  * 16 ciphertext bytes ahead of its slice.  accepted_each (n_chunks ints) and n_accepted may be NULL; a chunk whose proof bytes do not parse counts as rejected */
 int zkaes_verify_cbc_chunked(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t iv[16], const uint8_t *ciphertext,
+                             size_t ciphertext_len, int *accepted_each, size_t *n_accepted);
+/* ---- AES-128-CTR ---------------------------------------------------------------------------------------------------
+ * Statement of a key synthesized with ZKAES_CIRCUIT_AES_CTR for L bytes (any L >= 1, nb = ceil(L / 16) blocks): public = icb (the 16-byte initial counter block) and
+ * ciphertext (L bytes), private = message (L bytes) and secret_key, with CTR_0 = icb, CTR_b = CTR_b-1 + 1 mod 2^128 and C_b = M_b ^ AES-128(key, CTR_b), the last block
+ * cut to the bytes that exist.  The counter is ONE big-endian 128-bit integer over the 16 bytes (SP 800-38A appendix B.1 with m = 128: what OpenSSL, Go and Python's
+ * cryptography do); it is not GCM's inc32, which wraps the low 32 bits only.  Public-input vector (the instance without the leading One): the 128 icb bits, then the 8 L
+ * ciphertext bits, every byte as 8 LSB-first bits.  Encryption and decryption are the same function.
+ * Blocks are independent, so a long message splits into chunk-proofs that are seekable: chunk j of a key for nb whole blocks is proven and verified under icb + j nb,
+ * from (icb, j) alone, on any rank, with nothing serial ahead of it.  A ragged tail is one more proof under a second key of the tail's length and the advanced counter.
+ * Nothing binds the chunk-proofs of one message to the same key (as in ECB and CBC).  The CTR entry points refuse every other key, and every other entry point refuses
+ * a CTR key.  A verifying key carries no mode: a CBC key for 16 nb bytes takes a public input of the same shape (16 bytes, then the ciphertext), and it is the key
+ * that names the relation a proof is checked against, so a verifier keeps the keys of different modes apart. */
+/* host only, no GPU: out (len bytes, len >= 1) = in ^ keystream(secret_key, icb); encrypts and decrypts */
+int zkaes_ctr_crypt(const uint8_t *in, size_t len, const uint8_t secret_key[16], const uint8_t icb[16], uint8_t *out);
+/* host only: out16 = icb + n_blocks mod 2^128 (big-endian); the counter of the block n_blocks behind icb's.  out16 may be icb */
+int zkaes_ctr_counter_add(const uint8_t icb[16], uint64_t n_blocks, uint8_t out16[16]);
+/* one proof over a CTR key for exactly message_len bytes; zk_seed32 as zkaes_encrypt_seeded (NULL = test_rng seed).  ciphertext_or_null receives message_len bytes */
+int zkaes_encrypt_ctr_seeded(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *zk_seed32,
+                             uint8_t *ciphertext_or_null, uint8_t **proof, size_t *proof_len);
+/* chunk-proofs of a long CTR message, laid out as zkaes_encrypt_chunked's: the key's L must be a multiple of 16 and message_len exactly n_chunks x L, anything else is an
+ * error.  icb = the counter of THIS call's first block: a job split over several calls or ranks passes zkaes_ctr_counter_add(icb, blocks before) and the job-global
+ * first_proof_index.  Seeds as in the ECB chunked calls: the unseeded call draws a fresh OS seed, NULL in the seeded one is the fixed test_rng stream (tests only). */
+int zkaes_encrypt_ctr_chunked(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t icb[16], const zkaes_pk *pk, uint8_t *ciphertext_or_null,
+                              uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks);
+int zkaes_encrypt_ctr_chunked_seeded_at(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *zk_seed32,
+                                        uint64_t first_proof_index, uint8_t *ciphertext_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks);
+/* as zkaes_aes_witness for a CTR key */
+int zkaes_aes_witness_ctr(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t icb[16], uint8_t *z, size_t z_cap, size_t *z_len);
+/* host only: as zkaes_verify_encryption over the public input (icb, ciphertext).  The byte length is part of the statement (the verifier zero-pads the public input, so a
+ * ciphertext with zero bytes appended would pad to the same vector): a ciphertext_len other than the key's is an error.  A key restored by zkaes_vk_deserialize_ark
+ * carries only the padded input count; with such a key the caller answers for the exact length */
+int zkaes_verify_encryption_ctr(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t icb[16], const uint8_t *ciphertext, size_t ciphertext_len, int *accepted);
+/* host only, serial: n_chunks proofs (concatenated, proof_lens[j] bytes each) against ciphertext_len = n_chunks x chunk bytes, chunk a multiple of 16 and the key's length;
+ * chunk j is checked under icb + j * chunk / 16.  accepted_each (n_chunks ints) and n_accepted may be NULL; a chunk whose proof bytes do not parse counts as rejected */
+int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t icb[16], const uint8_t *ciphertext,
                              size_t ciphertext_len, int *accepted_each, size_t *n_accepted);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);

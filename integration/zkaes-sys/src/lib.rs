@@ -50,6 +50,21 @@ extern "C" {
                                    accepted: *mut c_int) -> c_int;
     fn zkaes_verify_cbc_chunked(vk: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, iv: *const u8, ciphertext: *const u8, ciphertext_len: usize,
                                 accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    // AES-128-CTR (include/zkaes.h, section "AES-128-CTR"; these declarations and the wrappers below were not compiled: no cargo in the build image)
+    fn zkaes_ctr_crypt(input: *const u8, len: usize, secret_key: *const u8, icb: *const u8, out: *mut u8) -> c_int;
+    fn zkaes_ctr_counter_add(icb: *const u8, n_blocks: u64, out16: *mut u8) -> c_int;
+    fn zkaes_encrypt_ctr_seeded(message: *const u8, message_len: usize, secret_key: *const u8, icb: *const u8, pk: *const zkaes_pk, zk_seed32: *const u8,
+                                ciphertext_or_null: *mut u8, proof: *mut *mut u8, proof_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_ctr_chunked(message: *const u8, message_len: usize, secret_key: *const u8, icb: *const u8, pk: *const zkaes_pk, ciphertext_or_null: *mut u8,
+                                 proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize, n_chunks: usize) -> c_int;
+    fn zkaes_encrypt_ctr_chunked_seeded_at(message: *const u8, message_len: usize, secret_key: *const u8, icb: *const u8, pk: *const zkaes_pk, zk_seed32: *const u8,
+                                           first_proof_index: u64, ciphertext_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize,
+                                           n_chunks: usize) -> c_int;
+    fn zkaes_aes_witness_ctr(pk: *const zkaes_pk, message: *const u8, message_len: usize, secret_key: *const u8, icb: *const u8, z: *mut u8, z_cap: usize, z_len: *mut usize) -> c_int;
+    fn zkaes_verify_encryption_ctr(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, icb: *const u8, ciphertext: *const u8, ciphertext_len: usize,
+                                   accepted: *mut c_int) -> c_int;
+    fn zkaes_verify_ctr_chunked(vk: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, icb: *const u8, ciphertext: *const u8, ciphertext_len: usize,
+                                accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
@@ -291,6 +306,102 @@ pub fn verify_cbc_chunked(verifying_key: &VerifyingKey, proofs: &[Vec<u8>], iv: 
     let mut each = vec![0 as c_int; proofs.len().max(1)];
     let mut ok = 0usize;
     if unsafe { zkaes_verify_cbc_chunked((verifying_key.0).0, blob.as_ptr(), lens.as_ptr(), proofs.len(), iv.as_ptr(), ciphertext.as_ptr(), ciphertext.len(), each.as_mut_ptr(), &mut ok) } != 0 {
+        return Err(last_error());
+    }
+    Ok(each.iter().take(proofs.len()).map(|&a| a != 0).collect())
+}
+
+// ---- AES-128-CTR (not in the reference API; counter mode is the encryption half of the GCM its README names).  NOT COMPILED: no cargo in the build image.
+/// include/zkaes.h ZKAES_CIRCUIT_AES_CTR
+pub const CIRCUIT_AES_CTR: c_int = 4;
+
+/// A key for CTR statements of `len` bytes (any value >= 1; a multiple of 16 for the chunked call) over the universal-SRS literals of src/lib.rs:141
+pub fn synthesize_keys_ctr(len: usize, flags: u32) -> Result<(ProvingKey, VerifyingKey)> {
+    let (mut pk, mut vk) = (std::ptr::null_mut(), std::ptr::null_mut());
+    if unsafe { zkaes_synthesize_keys_ex2(CIRCUIT_AES_CTR, len, 866_944, 513, 4_062_064, flags as c_uint, &mut pk, &mut vk) } != 0 { return Err(last_error()); }
+    Ok((ProvingKey(Arc::new(PkHandle(pk))), VerifyingKey(Arc::new(VkHandle(vk)))))
+}
+
+/// AES-128-CTR of any length >= 1 on the host (no GPU); encrypts and decrypts.  The counter is one big-endian 128-bit integer (SP 800-38A B.1), not GCM's inc32
+pub fn ctr_crypt(data: &[u8], secret_key: &[u8; 16], icb: &[u8; 16]) -> Result<Vec<u8>> {
+    let mut out = vec![0u8; data.len()];
+    if unsafe { zkaes_ctr_crypt(data.as_ptr(), data.len(), secret_key.as_ptr(), icb.as_ptr(), out.as_mut_ptr()) } != 0 { return Err(last_error()); }
+    Ok(out)
+}
+
+/// icb + n_blocks mod 2^128: the counter of the block `n_blocks` behind icb's, i.e. the `icb` of a call or rank that starts there
+pub fn ctr_counter_add(icb: &[u8; 16], n_blocks: u64) -> Result<[u8; 16]> {
+    let mut out = [0u8; 16];
+    if unsafe { zkaes_ctr_counter_add(icb.as_ptr(), n_blocks, out.as_mut_ptr()) } != 0 { return Err(last_error()); }
+    Ok(out)
+}
+
+/// One proof that `ciphertext` is the CTR encryption from counter `icb` of a hidden message with a hidden key: (ciphertext, proof bytes).  `zk_seed = None`: the fixed test_rng stream
+pub fn encrypt_ctr(message: &[u8], secret_key: &[u8; 16], icb: &[u8; 16], proving_key: &ProvingKey, zk_seed: Option<&[u8; 32]>) -> Result<(Vec<u8>, Vec<u8>)> {
+    let mut ct = vec![0u8; message.len().max(1)];
+    let (mut p, mut n) = (std::ptr::null_mut(), 0usize);
+    let seed = zk_seed.map_or(std::ptr::null(), |s| s.as_ptr());
+    if unsafe { zkaes_encrypt_ctr_seeded(message.as_ptr(), message.len(), secret_key.as_ptr(), icb.as_ptr(), (proving_key.0).0, seed, ct.as_mut_ptr(), &mut p, &mut n) } != 0 {
+        return Err(last_error());
+    }
+    ct.truncate(message.len());
+    Ok((ct, take_bytes(p, n)))
+}
+
+/// Long CTR messages: (ciphertext, chunk-proofs) over a key for `chunk_len` bytes (a multiple of 16).  Chunk j is proven under icb + j * chunk_len / 16; `icb` is the
+/// counter of this call's first block, so any slice of a job can be proven on its own from `ctr_counter_add(icb, blocks before)`.
+pub fn encrypt_ctr_chunked(message: &[u8], secret_key: &[u8; 16], icb: &[u8; 16], proving_key: &ProvingKey, chunk_len: usize, zk_seed: ZkSeed) -> Result<(Vec<u8>, Vec<Vec<u8>>)> {
+    if chunk_len == 0 || chunk_len % 16 != 0 || message.is_empty() || message.len() % chunk_len != 0 {
+        return Err(anyhow!("message length must be a non-zero multiple of the key's plaintext length, itself a multiple of 16"));
+    }
+    let n = message.len() / chunk_len;
+    let mut ct = vec![0u8; message.len()];
+    let (mut p, mut total) = (std::ptr::null_mut(), 0usize);
+    let mut lens = vec![0usize; n];
+    let (m, k, v, pk) = (message.as_ptr(), secret_key.as_ptr(), icb.as_ptr(), (proving_key.0).0);
+    let rc = match zk_seed {
+        ZkSeed::Fresh => unsafe { zkaes_encrypt_ctr_chunked(m, message.len(), k, v, pk, ct.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr(), n) },
+        ZkSeed::Seeded { seed, first_proof_index } => unsafe {
+            zkaes_encrypt_ctr_chunked_seeded_at(m, message.len(), k, v, pk, seed.as_ptr(), first_proof_index, ct.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr(), n)
+        },
+        ZkSeed::ReferenceParity => unsafe {
+            zkaes_encrypt_ctr_chunked_seeded_at(m, message.len(), k, v, pk, std::ptr::null(), 0, ct.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr(), n)
+        },
+    };
+    if rc != 0 { return Err(last_error()); }
+    let blob = take_bytes(p, total);
+    let mut out = Vec::with_capacity(n);
+    let mut off = 0;
+    for l in lens.iter() { out.push(blob[off..off + l].to_vec()); off += l; }
+    Ok((ct, out))
+}
+
+/// z (padded instance + witness, one byte per variable) of a CTR key
+pub fn aes_witness_ctr(proving_key: &ProvingKey, message: &[u8], secret_key: &[u8; 16], icb: &[u8; 16]) -> Result<Vec<u8>> {
+    let mut n = 0usize;
+    let pk = (proving_key.0).0;
+    if unsafe { zkaes_aes_witness_ctr(pk, message.as_ptr(), message.len(), secret_key.as_ptr(), icb.as_ptr(), std::ptr::null_mut(), 0, &mut n) } != 0 { return Err(last_error()); }
+    let mut z = vec![0u8; n];
+    if unsafe { zkaes_aes_witness_ctr(pk, message.as_ptr(), message.len(), secret_key.as_ptr(), icb.as_ptr(), z.as_mut_ptr(), n, &mut n) } != 0 { return Err(last_error()); }
+    Ok(z)
+}
+
+/// Ok(false) for a wrong counter or ciphertext; Err for malformed input, which includes a ciphertext whose length is not the key's (the length is part of the statement)
+pub fn verify_encryption_ctr(verifying_key: &VerifyingKey, proof: &[u8], icb: &[u8; 16], ciphertext: &[u8]) -> Result<bool> {
+    let mut accepted: c_int = 0;
+    if unsafe { zkaes_verify_encryption_ctr((verifying_key.0).0, proof.as_ptr(), proof.len(), icb.as_ptr(), ciphertext.as_ptr(), ciphertext.len(), &mut accepted) } != 0 {
+        return Err(last_error());
+    }
+    Ok(accepted != 0)
+}
+
+/// One verdict per chunk-proof; chunk j is checked under icb + j * (blocks per chunk) -- derived here, from (icb, j) alone
+pub fn verify_ctr_chunked(verifying_key: &VerifyingKey, proofs: &[Vec<u8>], icb: &[u8; 16], ciphertext: &[u8]) -> Result<Vec<bool>> {
+    let blob: Vec<u8> = proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut each = vec![0 as c_int; proofs.len().max(1)];
+    let mut ok = 0usize;
+    if unsafe { zkaes_verify_ctr_chunked((verifying_key.0).0, blob.as_ptr(), lens.as_ptr(), proofs.len(), icb.as_ptr(), ciphertext.as_ptr(), ciphertext.len(), each.as_mut_ptr(), &mut ok) } != 0 {
         return Err(last_error());
     }
     Ok(each.iter().take(proofs.len()).map(|&a| a != 0).collect())
