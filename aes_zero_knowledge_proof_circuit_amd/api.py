@@ -8,6 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CIRCUIT_AES, CIRCUIT_OPS_XOR, CIRCUIT_OPS_ADD = 0, 1, 2
 CIRCUIT_AES_CBC = 3                # AES-128-CBC: public input = iv, ciphertext (include/zkaes.h, DESIGN.md "CBC")
 CIRCUIT_AES_CTR = 4                # AES-128-CTR, any byte length >= 1: public input = icb, ciphertext (include/zkaes.h, DESIGN.md "CTR")
+CIRCUIT_AES_GCM = 5                # AES-128-GCM, 96-bit iv, full tag: public input = iv, aad, ciphertext, tag (include/zkaes.h, DESIGN.md "GCM"); synthesize_keys_gcm
 KEY_NO_TABLES = 1                  # zkaes_synthesize_keys_ex2 flag: no fixed-base window tables (saves 10-42 GB per key)
 PARITY = "parity"                  # zk_seed=PARITY: the reference's fixed ark_std::test_rng() stream for every proof (byte-parity tests only)
 
@@ -260,6 +261,42 @@ class ProvingKey:
             off += lens[i]
         return ct.raw[:len(message)], proofs
 
+    def witness_gcm(self, message, secret_key, iv, aad=b""):
+        """z (padded instance + witness, one byte per variable) of a GCM key: One, the 96 iv bits, the aad, ciphertext and tag bits, padding, then the witness"""
+        _gcm_args(secret_key, iv)
+        n = C.c_size_t()
+        args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)))
+        _check(lib().zkaes_aes_witness_gcm(*args, None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().zkaes_aes_witness_gcm(*args, buf, n, C.byref(n)))
+        return buf.raw
+
+    def encrypt_gcm_batch(self, messages, secret_keys, ivs, aads, zk_seed=None, first_proof_index=0):
+        """n independent GCM records over this key -> (ciphertexts, tags, proofs), three lists.  Every message has the key's plaintext length, every aad the key's aad
+        length, every iv 12 bytes; zk_seed and first_proof_index as encrypt_batch (None = a fresh OS seed for the call)"""
+        n = len(messages)
+        if not (len(secret_keys) == len(ivs) == len(aads) == n):
+            raise ZkAesError("one secret key, one iv and one aad per message")
+        if any(len(k) != 16 for k in secret_keys) or any(len(v) != 12 for v in ivs):
+            raise ZkAesError("secret_key must be 16 bytes and iv 12 bytes")
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        mb, kb = b"".join(bytes(m) for m in messages), b"".join(bytes(k) for k in secret_keys)
+        hb = b"".join(bytes(v) + bytes(a) for v, a in zip(ivs, aads))
+        cts, tags = C.create_string_buffer(max(len(mb), 1)), C.create_string_buffer(max(16 * n, 1))
+        lens = (C.c_size_t * max(n, 1))()
+        out, total = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_gcm_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), self._p, seed, C.c_uint64(first_proof_index),
+                                                       cts, tags, C.byref(out), C.byref(total), lens))
+        blob = _take(out, total)
+        proofs, off = [], 0
+        for i in range(n):
+            proofs.append(blob[off:off + lens[i]])
+            off += lens[i]
+        size = len(mb) // n if n else 0
+        return [cts.raw[size * i:size * (i + 1)] for i in range(n)], [tags.raw[16 * i:16 * i + 16] for i in range(n)], proofs
+
     def prove_ops(self, x, y, zk_seed=None):
         out, n = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_prove_ops(self._p, C.c_uint32(x), C.c_uint32(y), zk_seed, C.byref(out), C.byref(n)))
@@ -447,21 +484,91 @@ def verify_ctr_chunked(verifying_key, proofs, icb, ciphertext):
     return [bool(each[i]) for i in range(n)]
 
 
+def _gcm_args(secret_key, iv):
+    if len(secret_key) != 16:
+        raise ZkAesError("secret_key must be 16 bytes")
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+
+
+def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0):
+    """(ProvingKey, VerifyingKey) for AES-128-GCM records of exactly plaintext_length message bytes (>= 1) and aad_length aad bytes (>= 0).  flags: KEY_NO_TABLES"""
+    pk, vk = C.c_void_p(), C.c_void_p()
+    _check(lib().zkaes_synthesize_keys_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags),
+                                           C.byref(pk), C.byref(vk)))
+    return ProvingKey(pk.value), VerifyingKey(vk.value)
+
+
+def gcm_encrypt(message, secret_key, iv, aad=b""):
+    """AES-128-GCM on the host (zkaes_gcm_encrypt; no GPU), any message and aad length >= 0 -> (ciphertext, tag)"""
+    _gcm_args(secret_key, iv)
+    ct, tag = C.create_string_buffer(max(len(message), 1)), C.create_string_buffer(16)
+    _check(lib().zkaes_gcm_encrypt(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), ct, tag))
+    return ct.raw[:len(message)], tag.raw
+
+
+def gcm_decrypt(ciphertext, secret_key, iv, aad, tag):
+    """the plaintext, or None when the tag does not hold (zkaes_gcm_decrypt: constant-time compare, no plaintext released on failure)"""
+    _gcm_args(secret_key, iv)
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    msg, ok = C.create_string_buffer(max(len(ciphertext), 1)), C.c_int()
+    _check(lib().zkaes_gcm_decrypt(bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(tag), msg, C.byref(ok)))
+    if not ok.value:
+        return None
+    return msg.raw[:len(ciphertext)]
+
+
+def encrypt_gcm(message, secret_key, iv, aad, proving_key, zk_seed=None):
+    """one proof over a GCM key -> (ciphertext, tag, serialized MarlinProof bytes); zk_seed as encrypt"""
+    _gcm_args(secret_key, iv)
+    ct, tag = C.create_string_buffer(max(len(message), 1)), C.create_string_buffer(16)
+    out, n = C.c_void_p(), C.c_size_t()
+    _check(lib().zkaes_encrypt_gcm_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), proving_key._p, zk_seed, ct, tag,
+                                          C.byref(out), C.byref(n)))
+    return ct.raw[:len(message)], tag.raw, _take(out, n)
+
+
+def verify_encryption_gcm(verifying_key, proof, iv, aad, ciphertext, tag):
+    """is `proof` a proof that (ciphertext, tag) is the AES-128-GCM encryption under `iv` and `aad` of a hidden message with a hidden key? -> bool.  Lengths whose sum
+    is not the key's raise: they are part of the statement, and the key pins where the aad ends"""
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    acc = C.c_int()
+    _check(lib().zkaes_verify_encryption_gcm(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext),
+                                             C.c_size_t(len(ciphertext)), bytes(tag), C.byref(acc)))
+    return bool(acc.value)
+
+
 def proof_roundtrip(proof):
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_proof_roundtrip(bytes(proof), C.c_size_t(len(proof)), C.byref(out), C.byref(n)))
     return _take(out, n)
 
 
-def circuit_info(circuit, plaintext_length):
+def circuit_info(circuit, plaintext_length, aad_length=0):
+    """aad_length: GCM circuits only"""
     out = (C.c_uint64 * 12)()
-    _check(lib().zkaes_circuit_info(int(circuit), C.c_size_t(plaintext_length), out))
+    if int(circuit) == CIRCUIT_AES_GCM:
+        _check(lib().zkaes_circuit_info_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), out))
+    else:
+        _check(lib().zkaes_circuit_info(int(circuit), C.c_size_t(plaintext_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix(circuit, plaintext_length, which):
+def circuit_matrix(circuit, plaintext_length, which, aad_length=0):
     rows, nnz = C.c_uint64(), C.c_uint64()
+    if int(circuit) == CIRCUIT_AES_GCM:
+        _check(lib().zkaes_circuit_matrix_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), which, C.byref(rows), C.byref(nnz), None, None, None))
+        rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
+        col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
+        coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
+        _check(lib().zkaes_circuit_matrix_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), which, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                              coeff.ctypes.data_as(C.c_void_p)))
+        return rowptr, col[:nnz.value], coeff[:nnz.value]
     _check(lib().zkaes_circuit_matrix(int(circuit), C.c_size_t(plaintext_length), which, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)

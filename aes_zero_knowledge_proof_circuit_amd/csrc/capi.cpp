@@ -10,16 +10,22 @@ extern "C" {
 void zkaes_pk_free(zkaes_pk *pk) { delete pk; }
 int zkaes_device_count(void) { return zk::gpu::device_count(); }
 
-int zkaes_synthesize_keys_ex2(int kind, size_t len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return guard([&] {
         if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
         zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
-        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u);
+        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len);
         zkaes_vk *v = new zkaes_vk{k->vk()};
         zkaes_pk *p = new zkaes_pk{std::move(k)};
         if (pk) *pk = p; else delete p;
         if (vk) *vk = v; else delete v;
     });
+}
+int zkaes_synthesize_keys_ex2(int kind, size_t len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(kind, len, 0, nc, nv, nnz, flags, pk, vk);
+}
+int zkaes_synthesize_keys_gcm(size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(ZKAES_CIRCUIT_AES_GCM, len, aad_len, nc, nv, nnz, flags, pk, vk);
 }
 int zkaes_synthesize_keys_ex(int kind, size_t len, size_t nc, size_t nv, size_t nnz, zkaes_pk **pk, zkaes_vk **vk) {
     return zkaes_synthesize_keys_ex2(kind, len, nc, nv, nnz, 0u, pk, vk);
@@ -161,6 +167,42 @@ int zkaes_aes_witness_ctr(const zkaes_pk *pk, const uint8_t *msg, size_t len, co
     return guard([&] {
         if (!pk) throw std::invalid_argument("null argument");
         auto v = pk->pk->aes_witness_ctr(msg, len, key, icb);
+        if (z_len) *z_len = v.size();
+        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+    });
+}
+// ---- AES-128-GCM (include/zkaes.h): the prover side; zkaes_gcm_encrypt, zkaes_gcm_decrypt and the verifier are in capi_host.cpp
+int zkaes_encrypt_gcm_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const zkaes_pk *pk, const uint8_t *seed,
+                             uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t **proof, size_t *proof_len) {
+    return guard([&] {
+        if (!pk || !proof || !proof_len || !msg || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
+        std::vector<uint8_t> ct(len ? len : 1);
+        uint8_t tag[16];
+        auto b = zk::serialize_proof(pk->pk->prove_aes_gcm(msg, len, key, iv, aad, aad_len, seed, ct.data(), tag));
+        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+        if (tag_or_null) memcpy(tag_or_null, tag, 16);
+        *proof = give(b); *proof_len = b.size();
+    });
+}
+int zkaes_encrypt_gcm_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                      const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t **proofs,
+                                      size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || (n && (!messages || !secret_keys || !headers))) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (c.kind != zk::CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
+        if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
+        if (secret_keys_len != n * 16) throw std::invalid_argument("secret_keys must hold n x 16 bytes");
+        if (headers_len != n * (12 + c.aad_bytes)) throw std::invalid_argument("headers must hold n x " + std::to_string(12 + c.aad_bytes) + " bytes (iv, then the key's aad length)");
+        pack_proofs(pk->pk->prove_aes_gcm_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null), proofs, proofs_len,
+                    proof_lens);
+    });
+}
+int zkaes_aes_witness_gcm(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *z, size_t z_cap,
+                          size_t *z_len) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        auto v = pk->pk->aes_witness_gcm(msg, len, key, iv, aad, aad_len);
         if (z_len) *z_len = v.size();
         if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
     });

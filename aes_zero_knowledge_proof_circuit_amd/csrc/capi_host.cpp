@@ -5,7 +5,7 @@
 
 namespace {
 thread_local std::string g_err;
-zk::Circuit compile(int kind, size_t len) { return zk::compile_circuit(kind, len); }
+zk::Circuit compile(int kind, size_t len, size_t aad_len = 0) { return zk::compile_circuit(kind, len, aad_len); }
 // the CBC (and CTR) instance without the leading One: 128 bits of the IV (the initial counter block), then the ciphertext bits, each byte LSB first
 std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
     std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 16), c = zk::ciphertext_to_public_input(ct, ct_len);
@@ -140,6 +140,55 @@ int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
         if (n_accepted) *n_accepted = ok;
     });
 }
+// ---- AES-128-GCM.  Public input: 96 iv bits, the aad bits, the ciphertext bits, 128 tag bits.
+int zkaes_gcm_encrypt(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]) {
+    return guard([&] {
+        if (!key || !iv || !tag || (len && (!msg || !ct)) || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        zk::aes128_gcm_encrypt_host(msg, len, key, iv, aad, aad_len, ct, tag);
+    });
+}
+int zkaes_gcm_decrypt(const uint8_t *ct, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t tag[16], uint8_t *msg, int *ok) {
+    return guard([&] {
+        if (!key || !iv || !tag || !ok || (len && (!msg || !ct)) || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        *ok = 0;
+        // GCM's keystream does not depend on the data, so "encrypting" the ciphertext gives the plaintext -- and a tag over that plaintext, not the one wanted: the tag is
+        // GHASH over the CIPHERTEXT, which a second pass computes by encrypting the candidate plaintext back.  Nothing reaches the caller's buffer before the tag holds.
+        std::vector<uint8_t> pt(len ? len : 1), back(len ? len : 1);
+        uint8_t t[16];
+        zk::aes128_gcm_encrypt_host(ct, len, key, iv, aad, aad_len, pt.data(), t);
+        zk::aes128_gcm_encrypt_host(pt.data(), len, key, iv, aad, aad_len, back.data(), t);
+        unsigned diff = 0;
+        for (int i = 0; i < 16; i++) diff |= (unsigned)(t[i] ^ tag[i]);                // no early exit: the time does not tell where the tags differ
+        if (diff) return;
+        if (len) memcpy(msg, pt.data(), len);
+        *ok = 1;
+    });
+}
+namespace {
+// the verifier zero-pads the public input, so the byte lengths are part of the statement (as require_ctr_length); the key pins A + L, and the length block inside its
+// circuit pins the split between the two
+void require_gcm_lengths(const zk::VerifyingKey &vk, size_t aad_len, size_t ct_len) {
+    if (ct_len == 0) throw std::invalid_argument("GCM: the ciphertext must have at least one byte");
+    bool exact = vk.num_public_inputs + 1 != vk.num_instance;
+    if (exact && vk.num_public_inputs != 224 + 8 * (aad_len + ct_len)) throw std::invalid_argument("GCM: aad and ciphertext lengths are not the ones this key was synthesized for");
+}
+}  // namespace
+int zkaes_verify_encryption_gcm(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len,
+                                const uint8_t tag[16], int *accepted) {
+    return guard([&] {
+        if (!vk || !proof || !iv || !ct || !tag || !accepted || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        *accepted = 0;
+        require_gcm_lengths(vk->vk, aad_len, ct_len);
+        zk::Proof p = zk::deserialize_proof(proof, proof_len);
+        std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 12);
+        for (auto part : {std::make_pair(aad, aad_len), std::make_pair(ct, ct_len), std::make_pair(tag, (size_t)16)}) {
+            if (!part.second) continue;
+            std::vector<zk::Fr> bits = zk::ciphertext_to_public_input(part.first, part.second);
+            pub.insert(pub.end(), bits.begin(), bits.end());
+        }
+        *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
+    });
+}
 int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out, size_t *out_len) {
     return guard([&] { auto b = zk::serialize_proof(zk::deserialize_proof(proof, proof_len)); *out = give(b); *out_len = b.size(); });
 }
@@ -211,9 +260,10 @@ int zkaes_vk_from_trapdoor(const uint64_t info[7], const uint8_t *index_comms, c
     });
 }
 int zkaes_circuit_info(int kind, size_t len, uint64_t out[12]) { return guard([&] { fill_info(compile(kind, len), out); }); }
-int zkaes_circuit_matrix(int kind, size_t len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+int zkaes_circuit_info_gcm(size_t len, size_t aad_len, uint64_t out[12]) { return guard([&] { fill_info(compile(zk::CIRCUIT_AES_GCM, len, aad_len), out); }); }
+static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return guard([&] {
-        zk::Circuit c = compile(kind, len);
+        zk::Circuit c = compile(kind, len, aad_len);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -221,6 +271,12 @@ int zkaes_circuit_matrix(int kind, size_t len, int which, uint64_t *n_rows, uint
         if (col) memcpy(col, m.col.data(), m.col.size() * 4);
         if (coeff) memcpy(coeff, m.coeff.data(), m.coeff.size() * 8);
     });
+}
+int zkaes_circuit_matrix(int kind, size_t len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix(kind, len, 0, which, n_rows, nnz, rowptr, col, coeff);
+}
+int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix(zk::CIRCUIT_AES_GCM, len, aad_len, which, n_rows, nnz, rowptr, col, coeff);
 }
 
 }  // extern "C"

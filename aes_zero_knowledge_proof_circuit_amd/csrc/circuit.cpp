@@ -1,4 +1,10 @@
 // csrc/circuit.cpp -- see circuit.hpp.  Host-only C++; no device code.
+#if defined(__GNUC__) && !defined(__clang__)
+// The compilers make a million small allocations here (one LC per constraint).  A g++ build under AddressSanitizer records the caller's stack at every one of them by
+// walking frame pointers; without frame pointers it walks garbage, no two allocations share a stack, and the sanitizer's stack depot turns the compile quadratic
+// (tests/cbc_trace_emu.cpp builds this file with -O2 -fsanitize=address and nothing else).  Ahead of the includes, so that the vector code instantiated here has them too.
+#pragma GCC optimize("no-omit-frame-pointer")
+#endif
 #include "circuit.hpp"
 #include <algorithm>
 #include <array>
@@ -421,7 +427,99 @@ Circuit compile_aes_ctr_circuit(size_t len) {
     return c;
 }
 
-Circuit compile_circuit(int kind, size_t message_len) {
+// Gate order: message and key witnesses, the 12 iv bytes and the aad as inputs, the key schedule, the rounds of the H block (slot nb, round-0 input the constant zero
+// block) and of the J_0 block (slot nb + 1, iv || 00000001), per message block the rounds from iv || be32(b + 2) (the low 32 counter bits are constants: no incrementer),
+// one xor gate per existing message bit, GHASH, the 128 xor gates of the tag, last the ciphertext and the tag inputs.  The instance is One, 96 iv bits, 8 alen aad bits,
+// 8 len ciphertext bits, 128 tag bits.
+// GHASH (SP 800-38D 6.3, 6.4).  Bit k of a block, k = 0 the coefficient of alpha^0, is bit 7 - k % 8 of byte k / 8.  V_0 = H, V_{i+1} = V_i alpha: new[0] = old[127],
+// new[k] = old[k-1] ^ old[127] for k = 1, 2, 7, new[k] = old[k-1] otherwise (3 xor gates a step, 381 for the table, once per proof).  One multiplication Y = X H:
+// p_{i,k} = x_i & V_i[k] (16,384 and gates), then per output bit k a boolean y_k, seven booleans q_{k,0..6} and ONE row (sum_i p_{i,k} - y_k - 2 sum_j 2^j q_{k,j}) * One = 0:
+// y_k is the parity of the 128 products and q_k <= 64 their half.  The difference sits in A, as in enforce_equal, so A's row is 0 on a satisfied witness.  X_1 is the
+// first block itself; X_m = Y_{m-1} ^ block m costs one xor gate per existing bit (zero padding and the constant length block cost none).
+Circuit compile_aes_gcm_circuit(size_t len, size_t alen) {
+    if (len == 0) throw std::invalid_argument("GCM: the message must have at least one byte");
+    if (len > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM: message and aad of one proof are limited to 65536 bytes each");
+    const size_t nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TR_GCM_MULS(na, nb);
+    const uint32_t gcm = (uint32_t)TR_GCM(nb);
+    using Blk = std::array<Bit, 128>;
+    auto to_blk = [](const Byte *bytes) { Blk r; for (int k = 0; k < 128; k++) r[k] = bytes[k / 8][7 - k % 8]; return r; };
+    Builder b;
+    AesGates g(b);
+    std::vector<Byte> msg = g.alloc_message_and_key(len);
+    std::array<Byte, 16> in;
+    for (int i = 0; i < 12; i++) in[i] = b.alloc_byte(true, gcm + TR_GCM_IV + (uint32_t)i);
+    std::vector<Byte> aad(16 * na, Builder::const_byte(0)), ct(16 * nb, Builder::const_byte(0));
+    for (size_t i = 0; i < alen; i++) aad[i] = b.alloc_byte(true, gcm + TR_GCM_AAD + (uint32_t)i);
+    g.key_schedule();
+    std::array<Byte, 16> zero;
+    for (int i = 0; i < 16; i++) zero[i] = Builder::const_byte(0);
+    const std::array<Byte, 16> h_bytes = g.block_rounds(zero.data(), nb);
+    auto counter = [&](uint32_t n) { for (int i = 0; i < 4; i++) in[12 + i] = Builder::const_byte((uint8_t)(n >> (24 - 8 * i))); return in.data(); };
+    const std::array<Byte, 16> ej0 = g.block_rounds(counter(1), nb + 1);
+    std::vector<std::array<Byte, 16>> ks(nb);
+    for (size_t bi = 0; bi < nb; bi++) ks[bi] = g.block_rounds(counter((uint32_t)bi + 2), bi);
+    for (size_t i = 0; i < len; i++) ct[i] = b.xor_byte(msg[i], ks[i / 16][i % 16], gcm + (uint32_t)(TR_GCM_CT(na) + i));
+    // ---- GHASH: the V table
+    std::vector<Blk> V(128);
+    V[0] = to_blk(h_bytes.data());
+    const uint32_t v_off = gcm + (uint32_t)TR_GCM_V(na, nb);
+    for (int i = 1; i < 128; i++) {
+        const Blk &o = V[i - 1];
+        V[i][0] = o[127];
+        for (int k = 1; k < 128; k++) {
+            if (k == 1 || k == 2 || k == 7) { uint32_t mark = b.n_witness; V[i][k] = b.bxor(o[k - 1], o[127]); b.tag_bytebit(V[i][k], mark, v_off + (uint32_t)i, 7 - k); }   // (byte 0 of V_i)
+            else V[i][k] = o[k - 1];
+        }
+    }
+    // ---- the blocks GHASH runs over: the aad, the ciphertext (the bits of the C = M ^ S_10 gates), the length block
+    std::vector<Blk> blocks;
+    for (size_t j = 0; j < na; j++) blocks.push_back(to_blk(&aad[16 * j]));
+    for (size_t j = 0; j < nb; j++) blocks.push_back(to_blk(&ct[16 * j]));
+    {
+        std::array<Byte, 16> lb;
+        for (int i = 0; i < 8; i++) { lb[i] = Builder::const_byte((uint8_t)((uint64_t)(8 * alen) >> (56 - 8 * i))); lb[8 + i] = Builder::const_byte((uint8_t)((uint64_t)(8 * len) >> (56 - 8 * i))); }
+        blocks.push_back(to_blk(lb.data()));
+    }
+    Blk X = blocks[0], Y;
+    std::vector<Bit> p(128 * 128);
+    for (size_t m = 0; m < n_mul; m++) {
+        const uint32_t mul = gcm + (uint32_t)(TR_GCM_MUL0(na, nb) + m * TR_GCM_MUL_STRIDE);
+        if (m) for (int k = 0; k < 128; k++) { uint32_t mark = b.n_witness; X[k] = b.bxor(Y[k], blocks[m][k]); b.tag_bytebit(X[k], mark, mul + TR_GCM_MUL_X + (uint32_t)(k / 8), 7 - k % 8); }
+        for (int i = 0; i < 128; i++) for (int k = 0; k < 128; k++) {
+            uint32_t mark = b.n_witness;
+            p[128 * i + k] = b.band(X[i], V[i][k]);
+            b.tag_bytebit(p[128 * i + k], mark, mul + TR_GCM_MUL_P + (uint32_t)(128 * (k / 8) + i), 7 - k % 8);
+        }
+        for (int k = 0; k < 128; k++) {
+            Y[k] = b.alloc(false, mul + TR_GCM_MUL_Y + (uint32_t)(k / 8), 7 - k % 8);
+            LC d, one, z;
+            for (int i = 0; i < 128; i++) d.add(1, p[128 * i + k]);
+            d.add(-1, Y[k]);
+            for (int j = 0; j < 7; j++) d.add(-(int64_t)(2 << j), b.alloc(false, mul + TR_GCM_MUL_Q + (uint32_t)k, j));
+            one.add(1, 0u);
+            b.enforce(d, one, z);
+        }
+    }
+    // ---- tag = S ^ AES_K(J_0), then the public ciphertext and tag
+    const uint32_t tag_off = gcm + (uint32_t)TR_GCM_TAG(na, nb);
+    std::array<Byte, 16> tag;
+    for (int j = 0; j < 16; j++) { Byte s; for (int bit = 0; bit < 8; bit++) s[bit] = Y[8 * j + 7 - bit]; tag[j] = b.xor_byte(s, ej0[j], tag_off + (uint32_t)j); }
+    for (size_t i = 0; i < len; i++) {
+        Byte pi = b.alloc_byte(true, gcm + (uint32_t)(TR_GCM_CT(na) + i));
+        for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
+    }
+    for (int j = 0; j < 16; j++) {
+        Byte pi = b.alloc_byte(true, tag_off + (uint32_t)j);
+        for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], tag[j][k]);
+    }
+    Circuit c = finish(b, CIRCUIT_AES_GCM, nb, TR_GCM_BYTES(na, nb));
+    c.message_bytes = len; c.aad_bytes = alen;
+    return c;
+}
+
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len) {
+    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len);
+    if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
     if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len);
     if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len);
     if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len);
@@ -489,6 +587,52 @@ void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t key[16],
         for (size_t i = 0; i < 16 && off + i < len; i++) out[off + i] = (uint8_t)(in[off + i] ^ s[i]);
         ctr_counter_add(ctr, 1, ctr);
     }
+}
+
+namespace {
+// a GF(2^128) element in GCM's convention as two words: bit k (the coefficient of alpha^k) is bit 63 - k of hi for k < 64, bit 127 - k of lo behind
+struct Gf128 { uint64_t hi = 0, lo = 0; };
+Gf128 gf_load(const uint8_t b[16]) { Gf128 r; for (int i = 0; i < 8; i++) { r.hi = (r.hi << 8) | b[i]; r.lo = (r.lo << 8) | b[8 + i]; } return r; }
+// SP 800-38D Algorithm 1: Z = X * Y, one conditional xor and one multiplication of V by alpha per bit of X
+Gf128 gf_mul(const Gf128 &x, const Gf128 &y) {
+    Gf128 z, v = y;
+    for (int i = 0; i < 128; i++) {
+        uint64_t xi = i < 64 ? (x.hi >> (63 - i)) & 1 : (x.lo >> (127 - i)) & 1;
+        if (xi) { z.hi ^= v.hi; z.lo ^= v.lo; }
+        uint64_t lsb = v.lo & 1;
+        v.lo = (v.lo >> 1) | (v.hi << 63); v.hi >>= 1;
+        if (lsb) v.hi ^= 0xE100000000000000ull;                                    // R = 11100001 || 0^120
+    }
+    return z;
+}
+}  // namespace
+
+void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]) {
+    HostAes128 aes(key);
+    uint8_t hb[16] = {0}, s[16], blk[16];
+    aes.encrypt_block(hb);
+    const Gf128 h = gf_load(hb);
+    auto counter = [&](uint32_t n) { for (int i = 0; i < 12; i++) s[i] = iv[i]; for (int i = 0; i < 4; i++) s[12 + i] = (uint8_t)(n >> (24 - 8 * i)); aes.encrypt_block(s); };
+    for (size_t off = 0; off < len; off += 16) {
+        counter((uint32_t)(off / 16 + 2));
+        for (size_t i = 0; i < 16 && off + i < len; i++) ct[off + i] = (uint8_t)(msg[off + i] ^ s[i]);
+    }
+    Gf128 y;
+    auto absorb = [&](const uint8_t *data, size_t n) {                             // zero-padded to whole blocks
+        for (size_t off = 0; off < n; off += 16) {
+            for (size_t i = 0; i < 16; i++) blk[i] = off + i < n ? data[off + i] : 0;
+            Gf128 x = gf_load(blk);
+            x.hi ^= y.hi; x.lo ^= y.lo;
+            y = gf_mul(x, h);
+        }
+    };
+    absorb(aad, aad_len);
+    absorb(ct, len);
+    Gf128 x;
+    x.hi = y.hi ^ (uint64_t)aad_len * 8; x.lo = y.lo ^ (uint64_t)len * 8;
+    y = gf_mul(x, h);
+    counter(1);
+    for (int i = 0; i < 8; i++) { tag[i] = (uint8_t)((y.hi >> (56 - 8 * i)) ^ s[i]); tag[8 + i] = (uint8_t)((y.lo >> (56 - 8 * i)) ^ s[8 + i]); }
 }
 
 // src/ops.rs:8-29.  Trace: x (4 B LE) | y (4 B LE) | result (8 B LE)

@@ -6,6 +6,9 @@
 //                     per-proof trace buffer (layout: trace_layout.h); the mode (ECB / CBC) is a template parameter,
 //   k_aes_trace_ctr   the same for AES-128-CTR: a lane derives its block's counter and the incrementer's carries from the
 //                     initial counter block, and the last block of a message may be partial,
+//   k_aes_trace_gcm   AES-128-GCM's nb + 2 AES blocks (the message under inc32 counters, H, the tag mask), and behind it
+//   k_ghash_trace     the GHASH half: the V table of H and, per block, the 16,384 partial products, carries and result of
+//                     one multiplication in GF(2^128), sixteen lanes per multiplication, each re-walking the chain in registers,
 //   k_witness_expand  one lane per column of z: decode the variable's descriptor (compiled once by circuit.cpp) and gather
 //                     its bit -- S-box mux-tree variables are a table lookup S[(node << (level+1)) | (x & mask)],
 //   k_spmv_bits       z_A = A z, z_B = B z over 0/1 assignments with small integer coefficients (ark-marlin prover_init),
@@ -173,6 +176,111 @@ __global__ void k_aes_trace_ctr(uint8_t *__restrict__ trace, size_t stride, cons
     aes_block_rounds<true>(s, w, sbox, bl);
     for (uint32_t i = 0; i < 16; i++) slot[TR_CTR_BL_CT + i] = i < have ? (uint8_t)(m[i] ^ s[i]) : 0;
 }
+
+// GCM, the AES half: nproofs * (nblocks + 3) lanes, nblocks = ceil(msg_len / 16) message blocks, naad = ceil(aad_len / 16).  Lane (p, 0) writes the key schedule part, the
+// proof's iv and its aad (zero-padded to whole blocks); lane (p, 1 + s) is AES slot s: the message blocks under iv || be32(s + 2) for s < nblocks, then H from the zero
+// block, then J_0 = iv || 00000001.  A message lane stores C_s = M_s ^ S_10 for the bytes that exist and zeros behind them.  Messages are packed at msg_len bytes per
+// proof, the public headers (iv, then aad) at 12 + aad_len bytes.  The kernel is handed key, iv, aad and message only.
+__global__ void k_aes_trace_gcm(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ hdrs,
+                                uint32_t nproofs, uint32_t nblocks, uint32_t naad, uint32_t msg_len, uint32_t aad_len, const uint8_t *__restrict__ sbox) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nproofs * (nblocks + 3)) return;
+    uint32_t p = t / (nblocks + 3), which = t % (nblocks + 3);
+    uint8_t *tr = trace + (size_t)p * stride;
+    const uint8_t *key = keys + 16 * (size_t)p, *hdr = hdrs + (size_t)p * (12 + (size_t)aad_len);
+    uint8_t w[44][4];
+    aes_key_schedule(key, sbox, w, which == 0 ? tr : nullptr);
+    uint8_t *tail = tr + TR_GCM((size_t)nblocks);
+    if (which == 0) {
+        for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
+        for (int i = 0; i < 44; i++) for (int k = 0; k < 4; k++) tr[TR_KS_W + 4 * i + k] = w[i][k];
+        for (int i = 0; i < 16; i++) tail[TR_GCM_IV + i] = i < 12 ? hdr[i] : 0;
+        for (uint32_t i = 0; i < 16 * naad; i++) tail[TR_GCM_AAD + i] = i < aad_len ? hdr[12 + i] : 0;
+        return;
+    }
+    uint32_t slot = which - 1;
+    uint8_t *bl = tr + TR_BLOCK0 + (size_t)slot * TR_BLOCK_STRIDE;
+    uint8_t in[16], s[16], m[16];
+    uint32_t ctr = slot < nblocks ? slot + 2 : 1, have = 0;
+    for (int i = 0; i < 16; i++) in[i] = slot == nblocks ? 0 : (i < 12 ? hdr[i] : (uint8_t)(ctr >> (8 * (15 - i))));
+    if (slot < nblocks) have = msg_len - 16 * slot < 16 ? msg_len - 16 * slot : 16;          // (16 slot < msg_len: nblocks = ceil(msg_len / 16))
+    const uint8_t *msg = msgs + (size_t)p * msg_len + 16 * (size_t)(slot < nblocks ? slot : 0);      // (not read by the H and J_0 lanes: have = 0)
+    for (uint32_t i = 0; i < 16; i++) m[i] = i < have ? msg[i] : 0;
+    for (int i = 0; i < 16; i++) { bl[TR_BL_MSG + i] = m[i]; s[i] = in[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
+    aes_block_rounds<true>(s, w, sbox, bl);
+    if (slot < nblocks) for (uint32_t i = 0; i < 16; i++) tail[TR_GCM_CT(naad) + 16 * slot + i] = i < have ? (uint8_t)(m[i] ^ s[i]) : 0;
+}
+
+// GF(2^128) in GCM's convention as two words: bit k (the coefficient of alpha^k) is bit 63 - k of hi for k < 64 and bit 127 - k of lo behind; byte j of the block
+// is bits 8 j .. 8 j + 7, its most significant bit first.
+struct Gf128 { uint64_t hi, lo; };
+struct alignas(16) Bytes16 { uint8_t b[16]; };                 // one 16-byte vector store
+__device__ __forceinline__ Gf128 gf_load(const uint8_t *__restrict__ b) { Gf128 r = {0, 0}; for (int i = 0; i < 8; i++) { r.hi = (r.hi << 8) | b[i]; r.lo = (r.lo << 8) | b[8 + i]; } return r; }
+__device__ __forceinline__ uint8_t gf_byte(const Gf128 &v, uint32_t j) { return (uint8_t)(j < 8 ? v.hi >> (56 - 8 * j) : v.lo >> (56 - 8 * (j - 8))); }
+__device__ __forceinline__ uint32_t gf_bit(const Gf128 &v, int k) { return (uint32_t)(k < 64 ? v.hi >> (63 - k) : v.lo >> (127 - k)) & 1u; }
+__device__ __forceinline__ void gf_times_alpha(Gf128 &v) {     // SP 800-38D Algorithm 1, step 3: V >> 1, xor R = 11100001 || 0^120 if the bit shifted out was set
+    uint64_t lsb = v.lo & 1;
+    v.lo = (v.lo >> 1) | (v.hi << 63); v.hi >>= 1;
+    if (lsb) v.hi ^= 0xE100000000000000ull;
+}
+__device__ __forceinline__ Gf128 gf_mul(const Gf128 &x, Gf128 v) {
+    Gf128 z = {0, 0};
+    for (int i = 0; i < 128; i++) { if (gf_bit(x, i)) { z.hi ^= v.hi; z.lo ^= v.lo; } gf_times_alpha(v); }
+    return z;
+}
+
+// GCM, the GHASH half, launched behind k_aes_trace_gcm on the same stream: it reads H = S_10 of slot nblocks, the aad, every C_b and S_10 of slot nblocks + 1 from the
+// trace.  nproofs * (n_mul + 1) * 16 lanes, n_mul = naad + nblocks + 1.  Lane (p, m, j), m < n_mul, recomputes the chain Y_0 .. Y_{m-1} in registers (two words of
+// state, 128 steps of shift and conditional xor per multiplication, no stores -- the way a CBC lane re-walks its chain), then stores byte j of X_m, byte column j of P_m
+// (128 contiguous bytes, eight 16-byte stores), the q bytes of output bits 8 j .. 8 j + 7 and byte j of Y_m; the lanes of the last multiplication add byte j of the tag.
+// Lane (p, n_mul, j) stores byte column j of the V table.  Every byte of the tail has exactly one writer; no LDS, no barrier, no cross-lane operation.
+__global__ void k_ghash_trace(uint8_t *__restrict__ trace, size_t stride, uint32_t nproofs, uint32_t nblocks, uint32_t naad, uint32_t msg_len, uint32_t aad_len) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n_mul = naad + nblocks + 1, per_proof = (n_mul + 1) * 16;
+    if (t >= nproofs * per_proof) return;
+    uint32_t p = t / per_proof, m = (t % per_proof) / 16, j = t % 16;
+    uint8_t *tr = trace + (size_t)p * stride, *tail = tr + TR_GCM((size_t)nblocks);
+    const Gf128 h = gf_load(tr + TR_BLOCK0 + (size_t)nblocks * TR_BLOCK_STRIDE + TR_BL_S + 160);
+    Gf128 v = h;
+    if (m == n_mul) {
+        uint8_t *col = tail + TR_GCM_V(naad, nblocks) + 128 * j;
+        for (int c = 0; c < 8; c++) {
+            Bytes16 o;
+            for (int u = 0; u < 16; u++) { o.b[u] = gf_byte(v, j); gf_times_alpha(v); }
+            *reinterpret_cast<Bytes16 *>(col + 16 * c) = o;
+        }
+        return;
+    }
+    Gf128 x = {0, 0};
+    for (uint32_t mm = 0;; mm++) {
+        Gf128 blk;
+        if (mm < naad + nblocks) blk = gf_load(tail + TR_GCM_AAD + 16 * (size_t)mm);            // (the C_b lie right behind the aad blocks)
+        else { blk.hi = 8 * (uint64_t)aad_len; blk.lo = 8 * (uint64_t)msg_len; }
+        x.hi ^= blk.hi; x.lo ^= blk.lo;
+        if (mm == m) break;
+        x = gf_mul(x, h);
+    }
+    uint8_t *mul = tail + TR_GCM_MUL0(naad, nblocks) + (size_t)m * TR_GCM_MUL_STRIDE;
+    mul[TR_GCM_MUL_X + j] = gf_byte(x, j);
+    uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};                // how many of the 128 products are set, per bit of byte j
+    for (int c = 0; c < 8; c++) {
+        Bytes16 o;
+        for (int u = 0; u < 16; u++) {
+            uint8_t pb = gf_bit(x, 16 * c + u) ? gf_byte(v, j) : 0;
+            o.b[u] = pb;
+            for (int bit = 0; bit < 8; bit++) cnt[bit] += (pb >> bit) & 1u;
+            gf_times_alpha(v);
+        }
+        *reinterpret_cast<Bytes16 *>(mul + TR_GCM_MUL_P + 128 * j + 16 * c) = o;
+    }
+    uint8_t y = 0;
+    for (int bit = 0; bit < 8; bit++) {                         // output bit k = 8 j + 7 - bit
+        mul[TR_GCM_MUL_Q + 8 * j + 7 - bit] = (uint8_t)(cnt[bit] >> 1);
+        y |= (uint8_t)((cnt[bit] & 1u) << bit);
+    }
+    mul[TR_GCM_MUL_Y + j] = y;
+    if (m + 1 == n_mul) tail[TR_GCM_TAG(naad, nblocks) + j] = y ^ tr[TR_BLOCK0 + (size_t)(nblocks + 1) * TR_BLOCK_STRIDE + TR_BL_S + 160 + j];
+}
 template <bool CBC>
 static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s) {
     uint8_t *g_sbox = sbox_here();
@@ -198,6 +306,31 @@ void aes_trace_ctr(uint8_t *trace, size_t stride, const uint8_t *msgs, const uin
     if (!g_sbox) throw GpuError("aes_trace_ctr: S-box table not uploaded on this device");
     uint32_t lanes = nproofs * (nblocks + 1);
     hipLaunchKernelGGL(k_aes_trace_ctr, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, icbs, nproofs, nblocks, msg_len, g_sbox);
+    HIP_LAUNCH_CHECK();
+}
+// what both GCM entries check: the lengths, and the stride against the tail's size (the GHASH lanes store 16 bytes at a time, so traces are 16-byte aligned)
+static void gcm_shape(const char *who, const uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, uint32_t &nblocks, uint32_t &naad) {
+    if (msg_len == 0 || msg_len > (1u << 16) || aad_len > (1u << 16)) throw GpuError(std::string(who) + ": the message must have 1 .. 65536 bytes, the aad at most 65536");
+    nblocks = (msg_len + 15) / 16; naad = (aad_len + 15) / 16;
+    if (stride < TR_GCM_BYTES((size_t)naad, (size_t)nblocks)) throw GpuError(std::string(who) + ": trace stride is short of the GCM tail");
+    if (stride % 16 || (uintptr_t)trace % 16) throw GpuError(std::string(who) + ": traces must be 16-byte aligned");
+    if (nproofs == 0 || nproofs > (1u << 20)) throw GpuError(std::string(who) + ": 1 .. 2^20 proofs per launch");
+}
+void aes_trace_gcm(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s) {
+    if (!hdrs) throw GpuError("aes_trace_gcm: no iv / aad buffer");
+    uint32_t nblocks, naad;
+    gcm_shape("aes_trace_gcm", trace, stride, nproofs, msg_len, aad_len, nblocks, naad);
+    uint8_t *g_sbox = sbox_here();
+    if (!g_sbox) throw GpuError("aes_trace_gcm: S-box table not uploaded on this device");
+    uint32_t lanes = nproofs * (nblocks + 3);
+    hipLaunchKernelGGL(k_aes_trace_gcm, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, nblocks, naad, msg_len, aad_len, g_sbox);
+    HIP_LAUNCH_CHECK();
+}
+void ghash_trace(uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s) {
+    uint32_t nblocks, naad;
+    gcm_shape("ghash_trace", trace, stride, nproofs, msg_len, aad_len, nblocks, naad);
+    uint32_t lanes = nproofs * (naad + nblocks + 2) * 16;
+    hipLaunchKernelGGL(k_ghash_trace, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
     HIP_LAUNCH_CHECK();
 }
 

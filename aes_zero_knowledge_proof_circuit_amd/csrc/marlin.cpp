@@ -237,7 +237,7 @@ struct ProverContext {
     std::mutex in_use;                                // one proof at a time per context: concurrent callers of one key queue up here
     gpu::StreamGuard stream;
     gpu::WorkspaceGuard msm_ws;
-    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key, d_iv;     // (d_iv: the chaining value entering the proof's first block, CBC keys; the proof's initial counter block, CTR keys)
+    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key, d_iv;     // (d_iv: the chaining value entering the proof's first block, CBC keys; the proof's initial counter block, CTR keys; the proof's iv and aad, 12 + A bytes, GCM keys)
     DevPtr<void> d_rng;                               // scratch of the device-side ChaCha12 / Fr::rand stream
     DevPtr<int8_t> d_cls[3];                          // small-integer evaluation classes of w, z_A, z_B on H (Lagrange-basis commitments)
     DevPtr<F> za_ev, zb_ev, x_poly, x_tmp, x_evals, tmp_n, ra_ev, ra_poly, zpoly, t_partial;
@@ -328,7 +328,7 @@ class ProvingKeyImpl {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
         cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
-        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(16); cx.d_iv.alloc(16);
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(16); cx.d_iv.alloc(std::max<size_t>(16, 12 + c.aad_bytes));
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
@@ -486,7 +486,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -495,14 +495,14 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
     message_len = message_len_;
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
-    circuit = compile_circuit(kind, message_len);
+    circuit = compile_circuit(kind, message_len, aad_len);
     const Circuit &c = circuit;
     // ---- joint matrix (sum_matrices): per-row sorted union of the A, B, C column supports
     size_t rows = c.num_constraints;
@@ -663,6 +663,13 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
         if (len != c.message_bytes) throw std::invalid_argument("a CTR trace takes exactly the key's message length");
         gpu::h2d(cx.d_iv, iv, 16, s);
         gpu::aes_trace_ctr(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, s);
+    } else if (c.kind == CIRCUIT_AES_GCM) {
+        // iv = the proof's public header, 12 iv bytes then the key's A aad bytes.  The GHASH kernel reads H and every C_b from the trace the AES kernel has just written
+        if (!iv) throw std::invalid_argument("a GCM proving key needs an iv and the aad");
+        if (len != c.message_bytes) throw std::invalid_argument("a GCM trace takes exactly the key's message length");
+        gpu::h2d(cx.d_iv, iv, 12 + c.aad_bytes, s);
+        gpu::aes_trace_gcm(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s);
+        gpu::ghash_trace(cx.d_trace, c.trace_bytes, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s);
     } else {
         gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s);
     }
@@ -1098,10 +1105,11 @@ static void derive_zk_seed(uint8_t out[32], const uint8_t *seed32, uint64_t inde
     for (int i = 0; i < 8; i++) buf[32 + i] = (uint8_t)(index >> (8 * i));
     Blake2s::digest(out, buf, sizeof buf);
 }
-// ivs: nullptr (ECB), or n_chunks x 16 bytes -- the chaining value entering each chunk (CBC), each chunk's first counter block (CTR)
+// ivs: nullptr (ECB), or n_chunks x iv_stride bytes -- the chaining value entering each chunk (CBC), each chunk's first counter block (CTR), each record's iv and aad
+// (GCM, iv_stride = 12 + A).  Messages are packed at the key's message length.
 static std::vector<Proof> prove_many(ProvingKeyImpl *impl, const uint8_t *messages, const uint8_t *keys, size_t key_stride, size_t n_chunks, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
-                                     const uint8_t *ivs) {
-    size_t chunk = impl->circuit.n_blocks * 16;
+                                     const uint8_t *ivs, size_t iv_stride = 16) {
+    size_t chunk = impl->circuit.message_bytes;
     if (n_contexts == 0) n_contexts = 1;
     n_contexts = std::min(n_contexts, std::max<size_t>(n_chunks, 1));
     std::vector<Proof> proofs(n_chunks);
@@ -1118,7 +1126,7 @@ static std::vector<Proof> prove_many(ProvingKeyImpl *impl, const uint8_t *messag
                 if (i >= n_chunks) break;
                 uint8_t seed_i[32];
                 if (zk_seed) derive_zk_seed(seed_i, zk_seed, index_offset + (uint64_t)i);
-                proofs[i] = impl->prove(cx, nullptr, messages + i * chunk, chunk, keys + i * key_stride, zk_seed ? seed_i : nullptr, n_chunks > 1, ivs ? ivs + 16 * i : nullptr);   // a multi-proof call is a throughput call
+                proofs[i] = impl->prove(cx, nullptr, messages + i * chunk, chunk, keys + i * key_stride, zk_seed ? seed_i : nullptr, n_chunks > 1, ivs ? ivs + iv_stride * i : nullptr);   // a multi-proof call is a throughput call
             }
         } catch (const std::exception &e) { errors[ci] = e.what(); }
     };
@@ -1171,6 +1179,51 @@ std::vector<Proof> ProvingKey::prove_aes_ctr_chunked(const uint8_t *message, siz
     std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, icbs.data());
     if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null);
     return proofs;
+}
+// ---- AES-128-GCM.  The statement, the input layout, the GHASH gadget and why a long message is a batch of records, not chunk-proofs: DESIGN.md "GCM".
+static void require_gcm_key(const Circuit &c, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *iv, const uint8_t *aad, size_t aad_len) {
+    if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
+    if (!message || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
+    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
+    if (aad_len != c.aad_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.aad_bytes) + " bytes of aad");
+}
+static std::vector<uint8_t> gcm_header(const uint8_t iv[12], const uint8_t *aad, size_t aad_len) {
+    std::vector<uint8_t> h(iv, iv + 12);
+    if (aad_len) h.insert(h.end(), aad, aad + aad_len);
+    return h;
+}
+std::vector<uint8_t> ProvingKey::aes_witness_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len) {
+    require_gcm_key(impl->circuit, message, len, key, iv, aad, aad_len);
+    return witness_of(impl, message, len, key, gcm_header(iv, aad, aad_len).data());
+}
+Proof ProvingKey::prove_aes_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *zk_seed,
+                                uint8_t *ciphertext_or_null, uint8_t *tag_or_null) {
+    require_gcm_key(impl->circuit, message, len, key, iv, aad, aad_len);
+    if (ciphertext_or_null || tag_or_null) {
+        std::vector<uint8_t> ct(len);
+        uint8_t tag[16];
+        aes128_gcm_encrypt_host(message, len, key, iv, aad, aad_len, ct.data(), tag);
+        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+        if (tag_or_null) memcpy(tag_or_null, tag, 16);
+    }
+    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, gcm_header(iv, aad, aad_len).data());
+}
+std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
+                                                   uint8_t *ciphertexts_or_null, uint8_t *tags_or_null) {
+    const Circuit &c = impl->circuit;
+    if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
+    if (n && (!messages || !keys || !headers)) throw std::invalid_argument("null argument");
+    const size_t hs = 12 + c.aad_bytes;
+    if (ciphertexts_or_null || tags_or_null) {
+        std::vector<uint8_t> ct(c.message_bytes);
+        uint8_t tag[16];
+        for (size_t i = 0; i < n; i++) {
+            aes128_gcm_encrypt_host(messages + i * c.message_bytes, c.message_bytes, keys + 16 * i, headers + hs * i, headers + hs * i + 12, c.aad_bytes, ct.data(), tag);
+            if (ciphertexts_or_null) memcpy(ciphertexts_or_null + i * c.message_bytes, ct.data(), c.message_bytes);
+            if (tags_or_null) memcpy(tags_or_null + 16 * i, tag, 16);
+        }
+    }
+    return prove_many(impl, messages, keys, 16, n, n_contexts, zk_seed, index_offset, headers, hs);
 }
 Proof ProvingKey::prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed) {
     if (impl->circuit.kind != CIRCUIT_OPS_XOR && impl->circuit.kind != CIRCUIT_OPS_ADD) throw std::invalid_argument("proving key was synthesized for an AES circuit");
@@ -1285,10 +1338,10 @@ std::vector<uint8_t> ProvingKey::debug_fetch(const std::string &name) const {
     throw std::invalid_argument("debug_fetch: unknown buffer " + name);
 }
 
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags) {
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(circuit_kind, message_len, srs, flags);
+    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len);
     return pk;
 }
 

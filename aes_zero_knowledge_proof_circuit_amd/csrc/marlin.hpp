@@ -89,6 +89,16 @@ class ProvingKey {
     std::vector<Proof> prove_aes_ctr_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], size_t n_contexts, const uint8_t *zk_seed = nullptr,
                                              uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr);
     std::vector<uint8_t> aes_witness_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16]);
+    // ---- AES-128-GCM (keys of kind CIRCUIT_AES_GCM only; every other call refuses such a key).  Public input: iv (12 bytes), aad, ciphertext, tag; len and aad_len are
+    // the key's.  One proof per record: GHASH's chaining value is secret, so there are no chunk-proofs of one message (DESIGN.md "GCM").
+    // ciphertext_or_null (len bytes) and tag_or_null (16) receive the host's GCM encryption; the device is handed key, iv, aad and message only
+    Proof prove_aes_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *zk_seed,
+                        uint8_t *ciphertext_or_null = nullptr, uint8_t *tag_or_null = nullptr);
+    // n independent records over one key: messages = n x L bytes, keys = n x 16, headers = n x (12 + A) bytes (each record's iv, then its aad), all contexts side by side.
+    // Seeds as prove_aes_chunked.  ciphertexts_or_null = n x L bytes, tags_or_null = n x 16
+    std::vector<Proof> prove_aes_gcm_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
+                                           uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr);
+    std::vector<uint8_t> aes_witness_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len);
     // witness generation only (kernels aes_trace + witness_expand): z = padded instance || witness, one byte per variable
     std::vector<uint8_t> aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]);
     const ProverTimings &last_timings() const;
@@ -121,7 +131,7 @@ class ProvingKey {
 // multi-proof calls then run 15 per-window-bucket windows instead of 13 table windows (~9 % fewer blocks/s), and the key fits a GPU that is short of memory.
 // Without the flag the tables are built when memory allows (hipMemGetInfo) and silently skipped otherwise.
 enum : unsigned { KEY_NO_TABLES = 1u };
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0);
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0);      // (aad_len: GCM keys only)
 // hold = true: every universal / Lagrange SRS built (or alive) from now on stays resident after its last key is freed; false: back to "freed with the last key"
 void srs_hold(bool hold);
 // process default of ProvingKey::contexts(): ZKAES_CONTEXTS from the environment (read once), else ZKAES_DEFAULT_CONTEXTS

@@ -22,6 +22,20 @@
 //       ctr + 16 + 48 b + 16  K_b (16): the carries of CTR_{b-1} + 1.  Counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8; bit i of K_b, in the same mapping,
 //                             is the carry out of position i, i.e. 1 iff bits 0..i of CTR_{b-1} are all one.  K_0 = 0
 //       ctr + 16 + 48 b + 32  C_b = M_b ^ S_10 (16), zero beyond the message's last byte
+//   GCM keys only (message of L bytes, nb = ceil(L / 16); AAD of A bytes, na = ceil(A / 16); M = na + nb + 1 GHASH multiplications).  The trace holds nb + 2 AES
+//   blocks: slots 0 .. nb - 1 are the message blocks under the counters iv || be32(b + 2), slot nb is H = AES_K(0^128), slot nb + 1 is AES_K(J_0), J_0 = iv || 00000001;
+//   every slot's S_0 is its input ^ key, a message slot's "message block" is M_b with zeros beyond L.  Behind them, 16-byte aligned (gcm = TR_GCM(nb)):
+//       gcm + 0                    iv (12) and 4 zero bytes
+//       gcm + 16                   the AAD, zero-padded to 16 na bytes
+//       gcm + 16 + 16 na           C_b = M_b ^ S_10, nb x 16, zero beyond L
+//       then the V table (2048):   V_0 = H, V_{i+1} = V_i * alpha in GF(2^128); byte j of V_i at 128 j + i
+//       then per multiplication m = 0 .. M - 1, stride TR_GCM_MUL_STRIDE (Y_m = X_m * H):
+//           +0     X_m (16): X_0 = the first GHASH block, X_m = Y_{m-1} ^ block m (the AAD blocks, the C_b, last the length block be64(8 A) || be64(8 L))
+//           +16    P_m (2048): p_{i,k} = x_i & V_i[k]; byte j of row i (x_i ? byte j of V_i : 0) at 128 j + i, so byte column j is 128 contiguous bytes
+//           +2064  Q_m (128): byte k holds q_k = floor(sum_i p_{i,k} / 2) <= 64 in its bits 0..6
+//           +2192  Y_m (16)
+//       last                       the tag (16) = Y_{M-1} ^ S_10 of slot nb + 1
+//   Bit k of a GHASH block (k = 0 is the coefficient of alpha^0) is bit 7 - k % 8 of byte k / 8 (SP 800-38D 6.3: the leftmost bit of byte 0 first).
 #pragma once
 #define TR_KEY 0
 #define TR_KS_W 16
@@ -45,6 +59,20 @@
 #define TR_CTR_BL_CARRY 16
 #define TR_CTR_BL_CT 32
 #define TR_CTR_BYTES(nb) (TR_CTR(nb) + TR_CTR_BLOCK0 + (nb) * TR_CTR_BLOCK_STRIDE)
+#define TR_GCM(nb) TR_CBC((nb) + 2)
+#define TR_GCM_IV 0
+#define TR_GCM_AAD 16
+#define TR_GCM_CT(na) (16 + 16 * (na))
+#define TR_GCM_V(na, nb) (16 + 16 * (na) + 16 * (nb))
+#define TR_GCM_MUL0(na, nb) (TR_GCM_V(na, nb) + 2048)
+#define TR_GCM_MUL_STRIDE 2208
+#define TR_GCM_MUL_X 0
+#define TR_GCM_MUL_P 16
+#define TR_GCM_MUL_Q 2064
+#define TR_GCM_MUL_Y 2192
+#define TR_GCM_MULS(na, nb) ((na) + (nb) + 1)
+#define TR_GCM_TAG(na, nb) (TR_GCM_MUL0(na, nb) + TR_GCM_MULS(na, nb) * TR_GCM_MUL_STRIDE)
+#define TR_GCM_BYTES(na, nb) (TR_GCM(nb) + TR_GCM_TAG(na, nb) + 16)
 #define TR_SBOX_PER_BLOCK 160
 #define TR_SBOX_KS 40
 

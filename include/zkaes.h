@@ -68,6 +68,7 @@ int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out,
 #define ZKAES_CIRCUIT_OPS_XOR 1  /* src/ops.rs:8-18 (as a BLS12-377 Marlin circuit) */
 #define ZKAES_CIRCUIT_OPS_ADD 2  /* src/ops.rs:20-29 */
 #define ZKAES_CIRCUIT_AES_CTR 4  /* AES-128-CTR for any byte length >= 1 (no upstream counterpart; section "AES-128-CTR" below); accepted by the same calls as ZKAES_CIRCUIT_AES_CBC */
+#define ZKAES_CIRCUIT_AES_GCM 5  /* AES-128-GCM, 96-bit IV, full tag (no upstream code; section "AES-128-GCM" below); zkaes_synthesize_keys_gcm, or _ex / _ex2 for an empty aad */
 #define ZKAES_CIRCUIT_AES_CBC 3  /* AES-128-CBC (no upstream counterpart; section "AES-128-CBC" below); accepted by zkaes_synthesize_keys_ex / _ex2, zkaes_circuit_info, zkaes_circuit_matrix */
 /* as zkaes_synthesize_keys with an explicit circuit kind and universal-SRS literals (generate_universal_srs arguments) */
 int zkaes_synthesize_keys_ex(int circuit_kind, size_t plaintext_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, zkaes_pk **pk,
@@ -176,6 +177,46 @@ int zkaes_verify_encryption_ctr(const zkaes_vk *vk, const uint8_t *proof, size_t
  * chunk j is checked under icb + j * chunk / 16.  accepted_each (n_chunks ints) and n_accepted may be NULL; a chunk whose proof bytes do not parse counts as rejected */
 int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t icb[16], const uint8_t *ciphertext,
                              size_t ciphertext_len, int *accepted_each, size_t *n_accepted);
+/* ---- AES-128-GCM ---------------------------------------------------------------------------------------------------
+ * Statement of a key synthesized with ZKAES_CIRCUIT_AES_GCM for a message of L bytes (any L >= 1) and an AAD of A bytes (any A >= 0), both fixed by the key: public = iv
+ * (12 bytes; other IV lengths are refused), aad (A bytes), ciphertext (L bytes) and tag (16 bytes; full tags only), private = message (L bytes) and secret_key, related as
+ * in SP 800-38D: H = AES_K(0^128), J_0 = iv || 00000001, block b of the message is encrypted under iv || be32(b + 2), the last block cut to the bytes that exist,
+ * S = GHASH_H(aad zero-padded to blocks || ciphertext zero-padded to blocks || be64(8 A) || be64(8 L)), tag = S ^ AES_K(J_0).
+ * Public-input vector (the instance without the leading One): 96 iv bits, 8 A aad bits, 8 L ciphertext bits, 128 tag bits, every byte as 8 LSB-first bits; 224 + 8 A + 8 L
+ * in all.  The vector does not say where the aad ends and the ciphertext begins: the length block is a constant inside the circuit, so it is the key that pins the
+ * split, as it names the mode (a verifying key carries neither).  The verifier refuses a call whose A + L is not the key's.
+ * One proof per (iv, aad, ciphertext, tag).  There are no chunk-proofs of one long GCM message: the chaining value of GHASH is secret, and publishing it would give H
+ * away.  A long job is a batch of records (zkaes_encrypt_gcm_batch_seeded_at), which is where the prover contexts run side by side.  Nothing binds the proofs of a batch
+ * to one key.  The GCM entry points refuse every other key, and every other entry point refuses a GCM key. */
+/* as zkaes_synthesize_keys_ex2 for a GCM key of (plaintext_length, aad_length); _ex / _ex2 with ZKAES_CIRCUIT_AES_GCM give aad_length = 0 */
+int zkaes_synthesize_keys_gcm(size_t plaintext_length, size_t aad_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, unsigned flags,
+                              zkaes_pk **pk, zkaes_vk **vk);
+/* host only, no GPU: ciphertext (message_len bytes) and tag16 of AES-128-GCM; message_len >= 0, aad_len >= 0 (a NULL pointer is fine where the length is 0) */
+int zkaes_gcm_encrypt(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                      uint8_t *ciphertext, uint8_t tag16[16]);
+/* host only: *ok = 1 and message (ciphertext_len bytes) written if the tag holds, else *ok = 0 and message untouched.  The tags are compared in constant time */
+int zkaes_gcm_decrypt(const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t secret_key[16], const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                      const uint8_t tag16[16], uint8_t *message, int *ok);
+/* one proof over a GCM key for exactly (message_len, aad_len); zk_seed32 as zkaes_encrypt_seeded (NULL = test_rng seed).  ciphertext_or_null receives message_len bytes,
+ * tag_or_null 16 */
+int zkaes_encrypt_gcm_seeded(const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                             const zkaes_pk *pk, const uint8_t *zk_seed32, uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t **proof, size_t *proof_len);
+/* n independent records over one GCM key for (L, A): messages = n x L bytes, secret_keys = n x 16, headers = n x (12 + A) bytes (each record's iv, then its aad); the
+ * three lengths are checked.  proofs laid out as zkaes_encrypt_batch's; seeds and first_proof_index as zkaes_encrypt_batch_seeded_at.  ciphertexts_or_null = n x L bytes,
+ * tags_or_null = n x 16 */
+int zkaes_encrypt_gcm_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers,
+                                      size_t headers_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t *ciphertexts_or_null,
+                                      uint8_t *tags_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* as zkaes_aes_witness for a GCM key */
+int zkaes_aes_witness_gcm(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t secret_key[16], const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                          uint8_t *z, size_t z_cap, size_t *z_len);
+/* host only: as zkaes_verify_encryption over the public input (iv, aad, ciphertext, tag).  aad_len + ciphertext_len must be the key's (the verifier zero-pads the input);
+ * a key restored by zkaes_vk_deserialize_ark carries only the padded input count, and with such a key the caller answers for the exact lengths */
+int zkaes_verify_encryption_gcm(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                                const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16], int *accepted);
+/* host only: zkaes_circuit_info / zkaes_circuit_matrix of the GCM circuit for (plaintext_length, aad_length) */
+int zkaes_circuit_info_gcm(size_t plaintext_length, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_gcm(size_t plaintext_length, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

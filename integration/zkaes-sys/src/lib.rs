@@ -65,6 +65,21 @@ extern "C" {
                                    accepted: *mut c_int) -> c_int;
     fn zkaes_verify_ctr_chunked(vk: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, icb: *const u8, ciphertext: *const u8, ciphertext_len: usize,
                                 accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    // AES-128-GCM (include/zkaes.h, section "AES-128-GCM"; these declarations and the wrappers below were not compiled: no cargo in the build image)
+    fn zkaes_synthesize_keys_gcm(plaintext_length: usize, aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize, srs_num_non_zero: usize, flags: c_uint,
+                                 pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_gcm_encrypt(message: *const u8, message_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *mut u8, tag16: *mut u8) -> c_int;
+    fn zkaes_gcm_decrypt(ciphertext: *const u8, ciphertext_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, tag16: *const u8, message: *mut u8,
+                         ok: *mut c_int) -> c_int;
+    fn zkaes_encrypt_gcm_seeded(message: *const u8, message_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, pk: *const zkaes_pk,
+                                zk_seed32: *const u8, ciphertext_or_null: *mut u8, tag_or_null: *mut u8, proof: *mut *mut u8, proof_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_batch_seeded_at(n: usize, messages: *const u8, messages_len: usize, secret_keys: *const u8, secret_keys_len: usize, headers: *const u8, headers_len: usize,
+                                         pk: *const zkaes_pk, zk_seed32: *const u8, first_proof_index: u64, ciphertexts_or_null: *mut u8, tags_or_null: *mut u8,
+                                         proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_aes_witness_gcm(pk: *const zkaes_pk, message: *const u8, message_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, z: *mut u8,
+                             z_cap: usize, z_len: *mut usize) -> c_int;
+    fn zkaes_verify_encryption_gcm(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
+                                   ciphertext_len: usize, tag16: *const u8, accepted: *mut c_int) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
@@ -405,4 +420,95 @@ pub fn verify_ctr_chunked(verifying_key: &VerifyingKey, proofs: &[Vec<u8>], icb:
         return Err(last_error());
     }
     Ok(each.iter().take(proofs.len()).map(|&a| a != 0).collect())
+}
+
+// ---- AES-128-GCM (not in the reference API; its README names the mode).  96-bit IVs and full tags only.  NOT COMPILED: no cargo in the build image.
+/// include/zkaes.h ZKAES_CIRCUIT_AES_GCM
+pub const CIRCUIT_AES_GCM: c_int = 5;
+
+/// A key for GCM records of exactly `len` message bytes (>= 1) and `aad_len` aad bytes (>= 0) over the universal-SRS literals of src/lib.rs:141 (they hold up to 64 bytes)
+pub fn synthesize_keys_gcm(len: usize, aad_len: usize, flags: u32) -> Result<(ProvingKey, VerifyingKey)> {
+    let (mut pk, mut vk) = (std::ptr::null_mut(), std::ptr::null_mut());
+    if unsafe { zkaes_synthesize_keys_gcm(len, aad_len, 866_944, 513, 4_062_064, flags as c_uint, &mut pk, &mut vk) } != 0 { return Err(last_error()); }
+    Ok((ProvingKey(Arc::new(PkHandle(pk))), VerifyingKey(Arc::new(VkHandle(vk)))))
+}
+
+/// AES-128-GCM on the host (no GPU): (ciphertext, tag)
+pub fn gcm_encrypt(message: &[u8], secret_key: &[u8; 16], iv: &[u8; 12], aad: &[u8]) -> Result<(Vec<u8>, [u8; 16])> {
+    let mut ct = vec![0u8; message.len().max(1)];
+    let mut tag = [0u8; 16];
+    if unsafe { zkaes_gcm_encrypt(message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), aad.as_ptr(), aad.len(), ct.as_mut_ptr(), tag.as_mut_ptr()) } != 0 {
+        return Err(last_error());
+    }
+    ct.truncate(message.len());
+    Ok((ct, tag))
+}
+
+/// Ok(None) when the tag does not hold: no plaintext leaves the library then
+pub fn gcm_decrypt(ciphertext: &[u8], secret_key: &[u8; 16], iv: &[u8; 12], aad: &[u8], tag: &[u8; 16]) -> Result<Option<Vec<u8>>> {
+    let mut msg = vec![0u8; ciphertext.len().max(1)];
+    let mut ok: c_int = 0;
+    if unsafe { zkaes_gcm_decrypt(ciphertext.as_ptr(), ciphertext.len(), secret_key.as_ptr(), iv.as_ptr(), aad.as_ptr(), aad.len(), tag.as_ptr(), msg.as_mut_ptr(), &mut ok) } != 0 {
+        return Err(last_error());
+    }
+    msg.truncate(ciphertext.len());
+    Ok(if ok != 0 { Some(msg) } else { None })
+}
+
+/// One proof that (ciphertext, tag) is the GCM encryption under `iv` and `aad` of a hidden message with a hidden key: (ciphertext, tag, proof bytes)
+pub fn encrypt_gcm(message: &[u8], secret_key: &[u8; 16], iv: &[u8; 12], aad: &[u8], proving_key: &ProvingKey, zk_seed: Option<&[u8; 32]>) -> Result<(Vec<u8>, [u8; 16], Vec<u8>)> {
+    let mut ct = vec![0u8; message.len().max(1)];
+    let mut tag = [0u8; 16];
+    let (mut p, mut n) = (std::ptr::null_mut(), 0usize);
+    let seed = zk_seed.map_or(std::ptr::null(), |s| s.as_ptr());
+    if unsafe {
+        zkaes_encrypt_gcm_seeded(message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), aad.as_ptr(), aad.len(), (proving_key.0).0, seed, ct.as_mut_ptr(), tag.as_mut_ptr(), &mut p, &mut n)
+    } != 0 {
+        return Err(last_error());
+    }
+    ct.truncate(message.len());
+    Ok((ct, tag, take_bytes(p, n)))
+}
+
+/// n independent records over one key: `messages` n x L bytes, `secret_keys` n x 16, `headers` n x (12 + A) bytes (each record's iv, then its aad).
+/// Returns (ciphertexts n x L, tags n x 16, proofs).  `seed` and `first_proof_index` as in the ECB batch call
+pub fn encrypt_gcm_batch(n: usize, messages: &[u8], secret_keys: &[u8], headers: &[u8], proving_key: &ProvingKey, seed: &[u8; 32], first_proof_index: u64) -> Result<(Vec<u8>, Vec<u8>, Vec<Vec<u8>>)> {
+    let mut cts = vec![0u8; messages.len().max(1)];
+    let mut tags = vec![0u8; (16 * n).max(1)];
+    let (mut p, mut total) = (std::ptr::null_mut(), 0usize);
+    let mut lens = vec![0usize; n.max(1)];
+    if unsafe {
+        zkaes_encrypt_gcm_batch_seeded_at(n, messages.as_ptr(), messages.len(), secret_keys.as_ptr(), secret_keys.len(), headers.as_ptr(), headers.len(), (proving_key.0).0, seed.as_ptr(),
+                                          first_proof_index, cts.as_mut_ptr(), tags.as_mut_ptr(), &mut p, &mut total, lens.as_mut_ptr())
+    } != 0 {
+        return Err(last_error());
+    }
+    let blob = take_bytes(p, total);
+    let mut out = Vec::with_capacity(n);
+    let mut off = 0;
+    for l in lens.iter().take(n) { out.push(blob[off..off + l].to_vec()); off += l; }
+    cts.truncate(messages.len());
+    tags.truncate(16 * n);
+    Ok((cts, tags, out))
+}
+
+/// z (padded instance + witness, one byte per variable) of a GCM key
+pub fn aes_witness_gcm(proving_key: &ProvingKey, message: &[u8], secret_key: &[u8; 16], iv: &[u8; 12], aad: &[u8]) -> Result<Vec<u8>> {
+    let mut n = 0usize;
+    let pk = (proving_key.0).0;
+    if unsafe { zkaes_aes_witness_gcm(pk, message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), aad.as_ptr(), aad.len(), std::ptr::null_mut(), 0, &mut n) } != 0 { return Err(last_error()); }
+    let mut z = vec![0u8; n];
+    if unsafe { zkaes_aes_witness_gcm(pk, message.as_ptr(), message.len(), secret_key.as_ptr(), iv.as_ptr(), aad.as_ptr(), aad.len(), z.as_mut_ptr(), n, &mut n) } != 0 { return Err(last_error()); }
+    Ok(z)
+}
+
+/// Ok(false) for a wrong iv, aad, ciphertext or tag; Err for malformed input, which includes lengths whose sum is not the key's (they are part of the statement)
+pub fn verify_encryption_gcm(verifying_key: &VerifyingKey, proof: &[u8], iv: &[u8; 12], aad: &[u8], ciphertext: &[u8], tag: &[u8; 16]) -> Result<bool> {
+    let mut accepted: c_int = 0;
+    if unsafe {
+        zkaes_verify_encryption_gcm((verifying_key.0).0, proof.as_ptr(), proof.len(), iv.as_ptr(), aad.as_ptr(), aad.len(), ciphertext.as_ptr(), ciphertext.len(), tag.as_ptr(), &mut accepted)
+    } != 0 {
+        return Err(last_error());
+    }
+    Ok(accepted != 0)
 }
