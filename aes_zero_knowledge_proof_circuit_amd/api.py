@@ -711,6 +711,52 @@ def ntt_scaled(g, data_mont_bytes, n, inverse=False):
     return out.raw
 
 
+# ---- TEST-ONLY: one field / curve operation per launch on raw limbs (include/zkaes.h zkaes_arith_probe, csrc/arith_probe.cuh ZK_PROBE_OPS).
+# ARITH_OPS: name -> (op id, input words per case, output words per case).  tests/test_arith_model.py checks this table against the one compiled into the probes.
+def _arith_ops():
+    t = {}
+    for base, f, n in ((0, "fr377", 8), (16, "fr381", 8), (32, "fq377", 12), (48, "fq381", 12)):
+        for i, (name, nin) in enumerate((("mul", 2 * n), ("add", 2 * n), ("sub", 2 * n), ("neg", n), ("dbl", n), ("inverse", n), ("from_i64", 2), ("pow_u64", n + 2), ("from_raw", n), ("to_raw", n))):
+            t["%s.%s" % (f, name)] = (base + i, nin, n)
+    for base, f in ((64, "fq377x28"), (96, "fq381x28")):
+        ops = [("mul", 28, 14), ("sqr", 14, 14), ("fma2", 56, 14), ("add", 28, 14), ("add_lazy", 28, 14), ("dbl_lazy", 14, 14)]
+        ops += [("sub%d" % k, 28, 14) for k in (2, 3, 4, 5, 6, 7)] + [("sub_lazy%d" % k, 28, 14) for k in (2, 3)]
+        ops += [("canonical", 14, 14), ("product_is_zero", 14, 1), ("is_zero_mod_p", 14, 1), ("from_std", 12, 14), ("to_std", 14, 12)]
+        if f == "fq377x28":
+            ops.append(("mul_biased", 28, 14))
+        for i, (name, nin, nout) in enumerate(ops):
+            t["%s.%s" % (f, name)] = (base + i, nin, nout)
+    for base, f in ((128, "fr377x29"), (160, "fr381x29")):
+        ops = [("mul", 18, 9), ("dot2", 36, 9), ("dot3", 54, 9), ("dot4", 72, 9), ("add", 18, 9), ("add_lazy", 18, 9)]
+        ops += [("sub%d" % k, 18, 9) for k in (1, 2, 4, 8)] + [("sub_lazy2", 18, 9), ("normalized", 9, 9), ("shl5", 9, 9)]
+        ops += [("canonical%d" % k, 9, 9) for k in (0, 1, 4)] + [("reduce_by_top_limb", 9, 9), ("twiddle_from_std", 8, 9), ("split", 8, 9), ("pack", 9, 8)]
+        for i, (name, nin, nout) in enumerate(ops):
+            t["%s.%s" % (f, name)] = (base + i, nin, nout)
+    for i, (name, nin, nout) in enumerate((("te_madd", 98, 56), ("te_add", 112, 56), ("te_dbl", 56, 56), ("te_neg", 56, 56), ("te_to_std_point", 56, 48), ("niels_from_weierstrass", 24, 43),
+                                           ("te_madd_hot", 142, 98), ("te_add_quad", 112, 56), ("te_dbl_quad", 56, 56))):
+        t["te377.%s" % name] = (192 + i, nin, nout)
+    for base, f in ((208, "w377"), (216, "w381")):
+        for i, (name, nin, nout) in enumerate((("madd28", 84, 57), ("add28", 112, 56), ("dbl28", 56, 56), ("neg28", 56, 56), ("to_std_point", 56, 48))):
+            t["%s.%s" % (f, name)] = (base + i, nin, nout)
+    return t
+
+
+ARITH_OPS = _arith_ops()
+ARITH_QUAD_OPS = ("te377.te_add_quad", "te377.te_dbl_quad")      # four lanes per case on the device; no host body
+
+
+def arith_probe(op_name, cases):
+    """cases: bytes of little-endian 32-bit words, a whole number of cases (1 .. 65536) of ARITH_OPS[op_name][1] words each -> the output words as bytes"""
+    op, nin, nout = ARITH_OPS[op_name]
+    cases = bytes(cases)
+    n, rest = divmod(len(cases), 4 * nin)
+    if rest:
+        raise ZkAesError("arith_probe: %s takes %d words per case" % (op_name, nin))
+    out = C.create_string_buffer(4 * nout * n or 1)
+    _check(lib().zkaes_arith_probe(int(op), cases, C.c_size_t(n), out))
+    return out.raw[:4 * nout * n]
+
+
 def msm(curve_id, bases_bytes, scalars_bytes):
     n = len(scalars_bytes) // 32
     out = C.create_string_buffer(96)

@@ -7,7 +7,8 @@
 // 2 * 14^2 = 392 multiply-accumulates and ~100 shifts/masks, no carry chain.
 //
 // Representation: value = sum l[i] 2^(28 i), limbs normalized to < 2^28 after every operation, Montgomery radix R' = 2^392.
-// "Almost Montgomery": R' > 2^13 p, so for inputs < 64 p the product is < 1.2 p and NO conditional subtraction is needed; additions and
+// "Almost Montgomery": a product is < a b / R' + p, and R' / p is 2^15.3 (BLS12-377) / 2^11.3 (BLS12-381), so it is < 1.2 p and needs NO conditional subtraction for inputs
+// < 64 p (377) or with a b < 500 p^2 (381: e.g. both < 22 p; the group law's operands stay below 8.2 p.  tests/arith_model.py asserts the bound per operand pair); additions and
 // subtractions let values grow (sub adds a multiple of p) and callers bound them statically (see madd28 in kernels_msm.hip).
 // Conversion from the library-wide 12x32 form (R = 2^384): split limbs, multiply by 2^8 R' mod p; back: multiply by R mod p... (to_std).
 #pragma once

@@ -80,7 +80,8 @@ ZK_HD Niels28<P> niels_load_signed(const Niels28<P> *rec, bool neg) {
 // at the loop's back edge.  `bias` = FpMsm<P>::hot_loop_bias() taken at kernel entry (ff28.cuh mul_biased: 14 fewer 64-bit adds per product).
 // All four factors of the second level are lazy.  Limb bounds in units of 2^28: E = B + 2p' - A < 3, H = B + A < 2, D = 2 Z1 < 2, U = D + 2p' - C < 4, V = D + C < 3
 // (2p' = kp_spread<2> < 2 per limb).  The widest products, E U and U V, put 14 x 12 x 2^56 into a column, the reduction 13 x 2^56 more: 181 x 2^56 < 2^64
-// (tests/test_ff28_host.py multiplies at exactly those bounds).
+// (tests/test_gpu_arith.py multiplies at exactly those bounds on the device -- mul_biased with the opaque bias, and te_madd_hot itself in chains of seven -- against the
+// big-integer model of tests/arith_model.py; tests/test_ff28_host.py and tests/test_arith_model.py do the same with the host branch).
 template <class P>
 ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *next, bool next_neg, uint64_t bias) {
     using G = FpMsm<P>;
@@ -131,8 +132,14 @@ ZK_EC_FN void te_dbl(AccTE<P> &a) {
     G H = G::zero().template sub<3>(AB);                              // D - B = -(A + B)          < 3 p
     a.x = E * F; a.y = Gg * H; a.t = E * H; a.z = F * Gg;
 }
+// (all-zero limbs -- te_identity's x and t -- stay as they are: 2p - 0 would sit ON the 2 p bound, not below it; tests/arith_model.py NEG_OF_EXACT_ZERO)
 template <class P>
-ZK_HD AccTE<P> te_neg(const AccTE<P> &a) { AccTE<P> r = a; r.x = FpMsm<P>::zero().template sub<2>(a.x); r.t = FpMsm<P>::zero().template sub<2>(a.t); return r; }
+ZK_HD AccTE<P> te_neg(const AccTE<P> &a) {
+    AccTE<P> r = a;
+    if (!a.x.limbs_zero()) r.x = FpMsm<P>::zero().template sub<2>(a.x);
+    if (!a.t.limbs_zero()) r.t = FpMsm<P>::zero().template sub<2>(a.t);
+    return r;
+}
 
 // back to the Weierstrass model WITHOUT an inversion: the XYZZ point (x = X' / ZZ, y = Y' / ZZZ) with Zc = X (Z - Y), ZZ = Zc^2, ZZZ = Zc^3,
 //      X' = [sqrt3 (Z + Y) - (Z - Y)] X^2 (Z - Y),   Y' = sqrt3 f Z (Z + Y) X^2 (Z - Y)^2

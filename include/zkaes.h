@@ -313,6 +313,10 @@ int zkaes_ntt_padded(int field_id, const uint8_t *in, size_t in_len, size_t n, i
 /* the transform on the coset g D of a generator that need not be a root of unity: forward out[i] = p(g w^i) from the in_len coefficients (table of g^i riding on the first
  * pass), inverse the coefficients from such values (table of g^-i at the last store); n = 2 .. 2^28 */
 int zkaes_ntt_scaled(const uint8_t g[32], const uint8_t *in, size_t in_len, size_t n, int inverse, uint8_t *out);
+/* TEST-ONLY: ONE field or curve operation of csrc/ff.cuh, ff28.cuh, ff29.cuh, ec28.cuh, te28.cuh per launch, on raw limbs exactly as the operation sees them (no conversion
+ * in or out, so lazy and non-canonical operands can be passed).  op: an id of csrc/arith_probe.cuh ZK_PROBE_OPS (named by api.py ARITH_OPS, which also holds the words per
+ * case); in: n_cases x input words, out: n_cases x output words; 1 <= n_cases <= 65536.  tests/test_gpu_arith.py compares it with the big-integer model. */
+int zkaes_arith_probe(int op, const uint32_t *in, size_t n_cases, uint32_t *out);
 
 /* ---- MSM ---- */
 /* curve_id 377 / 381.  bases: n x 96 B affine (x||y Montgomery), scalars: n x 32 B Montgomery Fr; out_xy 96 B, *out_inf = 1 if infinity */
