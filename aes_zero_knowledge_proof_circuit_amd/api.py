@@ -124,6 +124,23 @@ class ProvingKey:
     def clone(self):  # device-resident and immutable: a clone is the same handle (benches/benchmark_encrypt.rs:46 clones per call)
         return self
 
+    def key_bytes(self):
+        """the byte length of the AES key this proving key takes: 16, 24 or 32 (synthesize_keys(..., key_bits=))"""
+        n = C.c_size_t()
+        _check(lib().zkaes_pk_key_bytes(self._p, C.byref(n)))
+        return int(n.value)
+
+    def _need_key(self, secret_key, other=None, other_name=None, other_len=16):
+        """the secret key has the length this proving key was synthesized for (and `other`, the iv / icb, its own): the library reads that many bytes from the pointer"""
+        kb = self.key_bytes()
+        if other is None:
+            if len(secret_key) != kb:
+                raise ZkAesError("secret_key must be %d bytes" % kb)
+        elif len(secret_key) != kb or len(other) != other_len:
+            if kb == other_len:
+                raise ZkAesError("secret_key and %s must be %d bytes" % (other_name, kb))
+            raise ZkAesError("secret_key must be %d bytes and %s %d bytes" % (kb, other_name, other_len))
+
     def info(self):
         out = (C.c_uint64 * 12)()
         _check(lib().zkaes_pk_info(self._p, out))
@@ -168,6 +185,7 @@ class ProvingKey:
         """the transforms and MSMs the library ACTUALLY launches for one proof on this key (zkaes_pk_op_lists): dict with "ntt" [[points, transforms per launch], ...] and
         "msm" [[points, kind], ...] + the circuit sizes.  Process-global recorder: no other proof may be in flight."""
         import json
+        self._need_key(secret_key)
         out, n = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_pk_op_lists(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), 1 if throughput_path else 0, C.byref(out), C.byref(n)))
         return json.loads(_take(out, n).decode())
@@ -185,6 +203,7 @@ class ProvingKey:
         _check(lib().zkaes_pk_msm_partial_dev(self._p, bytes(scalars_bytes), C.c_size_t(n), C.c_size_t(offset), C.c_void_p(dev_ptr), C.c_size_t(dev_bytes)))
 
     def witness(self, message, secret_key):
+        self._need_key(secret_key)
         n = C.c_size_t()
         _check(lib().zkaes_aes_witness(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), None, C.c_size_t(0), C.byref(n)))
         buf = C.create_string_buffer(n.value)
@@ -193,8 +212,7 @@ class ProvingKey:
 
     def witness_cbc(self, message, secret_key, iv):
         """z (padded instance + witness, one byte per variable) of a CBC key: One, the 128 IV bits, the ciphertext bits, padding, then the witness"""
-        if len(secret_key) != 16 or len(iv) != 16:
-            raise ZkAesError("secret_key and iv must be 16 bytes")
+        self._need_key(secret_key, iv, "iv")
         n = C.c_size_t()
         _check(lib().zkaes_aes_witness_cbc(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), None, C.c_size_t(0), C.byref(n)))
         buf = C.create_string_buffer(n.value)
@@ -204,8 +222,7 @@ class ProvingKey:
     def encrypt_cbc_chunked(self, message, secret_key, iv, zk_seed=None, first_proof_index=0):
         """(ciphertext, chunk-proofs) of a long CBC message.  iv = the chaining value entering this call's first chunk (a job split over several calls takes each call's
         from cbc_ciphertext); zk_seed and first_proof_index as encrypt_chunked"""
-        if len(secret_key) != 16 or len(iv) != 16:
-            raise ZkAesError("secret_key and iv must be 16 bytes")
+        self._need_key(secret_key, iv, "iv")
         seed = self._seed_arg(zk_seed)
         chunk = (self.info()["raw_instance"] - 129) // 8        # One + 128 IV bits, then 8 public-input bits per ciphertext byte
         if chunk <= 0:
@@ -228,8 +245,7 @@ class ProvingKey:
 
     def witness_ctr(self, message, secret_key, icb):
         """z (padded instance + witness, one byte per variable) of a CTR key: One, the 128 icb bits, the ciphertext bits, padding, then the witness"""
-        if len(secret_key) != 16 or len(icb) != 16:
-            raise ZkAesError("secret_key and icb must be 16 bytes")
+        self._need_key(secret_key, icb, "icb")
         n = C.c_size_t()
         _check(lib().zkaes_aes_witness_ctr(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), None, C.c_size_t(0), C.byref(n)))
         buf = C.create_string_buffer(n.value)
@@ -239,8 +255,7 @@ class ProvingKey:
     def encrypt_ctr_chunked(self, message, secret_key, icb, zk_seed=None, first_proof_index=0):
         """(ciphertext, chunk-proofs) of a long CTR message over a key for whole blocks; chunk j is proven under icb + j * (the key's blocks).  icb = the counter of this
         call's first block (a job split over several calls passes ctr_counter_add(icb, blocks before)); zk_seed and first_proof_index as encrypt_chunked"""
-        if len(secret_key) != 16 or len(icb) != 16:
-            raise ZkAesError("secret_key and icb must be 16 bytes")
+        self._need_key(secret_key, icb, "icb")
         seed = self._seed_arg(zk_seed)
         chunk = (self.info()["raw_instance"] - 129) // 8        # One + 128 icb bits, then 8 public-input bits per ciphertext byte
         if chunk <= 0 or len(message) == 0 or len(message) % chunk:
@@ -263,7 +278,7 @@ class ProvingKey:
 
     def witness_gcm(self, message, secret_key, iv, aad=b""):
         """z (padded instance + witness, one byte per variable) of a GCM key: One, the 96 iv bits, the aad, ciphertext and tag bits, padding, then the witness"""
-        _gcm_args(secret_key, iv)
+        _gcm_args(secret_key, iv, self.key_bytes())
         n = C.c_size_t()
         args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)))
         _check(lib().zkaes_aes_witness_gcm(*args, None, C.c_size_t(0), C.byref(n)))
@@ -277,8 +292,9 @@ class ProvingKey:
         n = len(messages)
         if not (len(secret_keys) == len(ivs) == len(aads) == n):
             raise ZkAesError("one secret key, one iv and one aad per message")
-        if any(len(k) != 16 for k in secret_keys) or any(len(v) != 12 for v in ivs):
-            raise ZkAesError("secret_key must be 16 bytes and iv 12 bytes")
+        kb = self.key_bytes()
+        if any(len(k) != kb for k in secret_keys) or any(len(v) != 12 for v in ivs):
+            raise ZkAesError("secret_key must be %d bytes and iv 12 bytes" % kb)
         if zk_seed is None:
             zk_seed = os.urandom(32)
         seed = self._seed_arg(zk_seed)
@@ -314,8 +330,7 @@ class ProvingKey:
     def encrypt_chunked(self, message, secret_key, zk_seed=None, first_proof_index=0):
         """chunk-proofs of a long ECB message.  zk_seed: None = a fresh OS seed per call, 32 bytes = caller's seed (proof i uses index first_proof_index + i),
         PARITY = the reference's fixed prover randomness for every proof"""
-        if len(secret_key) != 16:
-            raise ZkAesError("secret_key must be 16 bytes")
+        self._need_key(secret_key)
         seed = self._seed_arg(zk_seed)
         chunk = (self.info()["raw_instance"] - 1) // 8          # 8 public-input bits per ciphertext byte
         n_chunks = len(message) // chunk
@@ -334,15 +349,16 @@ class ProvingKey:
         return proofs
 
     def encrypt_batch(self, messages, secret_keys, zk_seed=None, first_proof_index=0):
-        """n independent proofs: messages = list of equal-length byte strings (the key's plaintext length), secret_keys = list of 16-byte keys; zk_seed as encrypt_chunked"""
+        """n independent proofs: messages = list of equal-length byte strings (the key's plaintext length), secret_keys = list of keys of key_bytes() bytes each; zk_seed as encrypt_chunked"""
         n = len(messages)
         chunk = (self.info()["raw_instance"] - 1) // 8
         if len(secret_keys) != n:
             raise ZkAesError("one secret key per message")
         if any(len(m) != chunk for m in messages):
             raise ZkAesError("every message must be %d bytes (the key's plaintext length)" % chunk)
-        if any(len(k) != 16 for k in secret_keys):
-            raise ZkAesError("secret_key must be 16 bytes")
+        kb = self.key_bytes()
+        if any(len(k) != kb for k in secret_keys):
+            raise ZkAesError("secret_key must be %d bytes" % kb)
         seed = self._seed_arg(zk_seed)
         lens = (C.c_size_t * max(n, 1))()
         out, total = C.c_void_p(), C.c_size_t()
@@ -371,17 +387,35 @@ class ProvingKey:
             pass
 
 
-def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0):
-    """zk_aes::synthesize_keys (src/lib.rs:138-174) -> (ProvingKey, VerifyingKey).  flags: KEY_NO_TABLES"""
+def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags):
     pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib().zkaes_synthesize_keys_ex2(int(circuit), C.c_size_t(plaintext_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
+    _check(lib().zkaes_synthesize_keys_ks(int(circuit), C.c_uint(int(key_bits)), C.c_size_t(plaintext_length), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]),
+                                          C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
     return ProvingKey(pk.value), VerifyingKey(vk.value)
+
+
+def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128):
+    """zk_aes::synthesize_keys (src/lib.rs:138-174) -> (ProvingKey, VerifyingKey).  flags: KEY_NO_TABLES.  key_bits: 128 (the reference's AES-128), 192 or 256 for
+    the AES kinds; the proving key then takes secret keys of key_bits / 8 bytes (ProvingKey.key_bytes())"""
+    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags)
+
+
+def _host_key(secret_key):
+    if len(secret_key) not in (16, 24, 32):
+        raise ZkAesError("secret_key must be 16, 24 or 32 bytes")
+
+
+def ecb_ciphertext(message, secret_key):
+    """AES-ECB of whole blocks on the host (zkaes_ecb_ciphertext_ks; no GPU); the key's length, 16, 24 or 32 bytes, selects AES-128, -192 or -256"""
+    _host_key(secret_key)
+    ct = C.create_string_buffer(max(len(message), 1))
+    _check(lib().zkaes_ecb_ciphertext_ks(bytes(message), C.c_size_t(len(message)), bytes(secret_key), C.c_size_t(len(secret_key)), ct))
+    return ct.raw[:len(message)]
 
 
 def encrypt(message, secret_key, proving_key, zk_seed=None):
     """zk_aes::encrypt (src/lib.rs:60-114) -> serialized MarlinProof bytes."""
-    if len(secret_key) != 16:
-        raise ZkAesError("secret_key must be 16 bytes")
+    proving_key._need_key(secret_key)
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_encrypt_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), proving_key._p, zk_seed, C.byref(out), C.byref(n)))
     return _take(out, n)
@@ -395,18 +429,17 @@ def verify_encryption(verifying_key, proof, ciphertext):
 
 
 def cbc_ciphertext(message, secret_key, iv):
-    """AES-128-CBC of whole blocks on the host (zkaes_cbc_ciphertext; no GPU)"""
-    if len(secret_key) != 16 or len(iv) != 16:
-        raise ZkAesError("secret_key and iv must be 16 bytes")
+    """AES-CBC of whole blocks on the host (zkaes_cbc_ciphertext_ks; no GPU); a 16-, 24- or 32-byte key"""
+    if len(secret_key) not in (16, 24, 32) or len(iv) != 16:
+        raise ZkAesError("secret_key must be 16, 24 or 32 bytes and iv 16 bytes")
     ct = C.create_string_buffer(max(len(message), 1))
-    _check(lib().zkaes_cbc_ciphertext(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), ct))
+    _check(lib().zkaes_cbc_ciphertext_ks(bytes(message), C.c_size_t(len(message)), bytes(secret_key), C.c_size_t(len(secret_key)), bytes(iv), ct))
     return ct.raw[:len(message)]
 
 
 def encrypt_cbc(message, secret_key, iv, proving_key, zk_seed=None):
     """one proof over a CBC key -> (ciphertext, serialized MarlinProof bytes); zk_seed as encrypt"""
-    if len(secret_key) != 16 or len(iv) != 16:
-        raise ZkAesError("secret_key and iv must be 16 bytes")
+    proving_key._need_key(secret_key, iv, "iv")
     ct = C.create_string_buffer(max(len(message), 1))
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_encrypt_cbc_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), proving_key._p, zk_seed, ct, C.byref(out), C.byref(n)))
@@ -435,11 +468,11 @@ def verify_cbc_chunked(verifying_key, proofs, iv, ciphertext):
 
 
 def ctr_crypt(data, secret_key, icb):
-    """AES-128-CTR of any byte length >= 1 on the host (zkaes_ctr_crypt; no GPU): encrypts and decrypts"""
-    if len(secret_key) != 16 or len(icb) != 16:
-        raise ZkAesError("secret_key and icb must be 16 bytes")
+    """AES-CTR of any byte length >= 1 on the host (zkaes_ctr_crypt_ks; no GPU): encrypts and decrypts; a 16-, 24- or 32-byte key"""
+    if len(secret_key) not in (16, 24, 32) or len(icb) != 16:
+        raise ZkAesError("secret_key must be 16, 24 or 32 bytes and icb 16 bytes")
     out = C.create_string_buffer(max(len(data), 1))
-    _check(lib().zkaes_ctr_crypt(bytes(data), C.c_size_t(len(data)), bytes(secret_key), bytes(icb), out))
+    _check(lib().zkaes_ctr_crypt_ks(bytes(data), C.c_size_t(len(data)), bytes(secret_key), C.c_size_t(len(secret_key)), bytes(icb), out))
     return out.raw[:len(data)]
 
 
@@ -454,8 +487,7 @@ def ctr_counter_add(icb, n_blocks):
 
 def encrypt_ctr(message, secret_key, icb, proving_key, zk_seed=None):
     """one proof over a CTR key -> (ciphertext, serialized MarlinProof bytes); zk_seed as encrypt"""
-    if len(secret_key) != 16 or len(icb) != 16:
-        raise ZkAesError("secret_key and icb must be 16 bytes")
+    proving_key._need_key(secret_key, icb, "icb")
     ct = C.create_string_buffer(max(len(message), 1))
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_encrypt_ctr_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), proving_key._p, zk_seed, ct, C.byref(out), C.byref(n)))
@@ -484,26 +516,27 @@ def verify_ctr_chunked(verifying_key, proofs, icb, ciphertext):
     return [bool(each[i]) for i in range(n)]
 
 
-def _gcm_args(secret_key, iv):
-    if len(secret_key) != 16:
-        raise ZkAesError("secret_key must be 16 bytes")
+def _gcm_args(secret_key, iv, key_bytes=None):
+    """key_bytes: what a proving key takes; None = the host ciphers, which take any of the three sizes"""
+    if key_bytes is None:
+        _host_key(secret_key)
+    elif len(secret_key) != key_bytes:
+        raise ZkAesError("secret_key must be %d bytes" % key_bytes)
     if len(iv) != 12:
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
 
 
-def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0):
-    """(ProvingKey, VerifyingKey) for AES-128-GCM records of exactly plaintext_length message bytes (>= 1) and aad_length aad bytes (>= 0).  flags: KEY_NO_TABLES"""
-    pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib().zkaes_synthesize_keys_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags),
-                                           C.byref(pk), C.byref(vk)))
-    return ProvingKey(pk.value), VerifyingKey(vk.value)
+def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128):
+    """(ProvingKey, VerifyingKey) for AES-GCM records of exactly plaintext_length message bytes (>= 1) and aad_length aad bytes (>= 0).  flags: KEY_NO_TABLES;
+    key_bits: 128, 192 or 256"""
+    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags)
 
 
 def gcm_encrypt(message, secret_key, iv, aad=b""):
-    """AES-128-GCM on the host (zkaes_gcm_encrypt; no GPU), any message and aad length >= 0 -> (ciphertext, tag)"""
+    """AES-GCM on the host (zkaes_gcm_encrypt_ks; no GPU), any message and aad length >= 0, a 16-, 24- or 32-byte key -> (ciphertext, tag)"""
     _gcm_args(secret_key, iv)
     ct, tag = C.create_string_buffer(max(len(message), 1)), C.create_string_buffer(16)
-    _check(lib().zkaes_gcm_encrypt(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), ct, tag))
+    _check(lib().zkaes_gcm_encrypt_ks(bytes(message), C.c_size_t(len(message)), bytes(secret_key), C.c_size_t(len(secret_key)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), ct, tag))
     return ct.raw[:len(message)], tag.raw
 
 
@@ -513,7 +546,8 @@ def gcm_decrypt(ciphertext, secret_key, iv, aad, tag):
     if len(tag) != 16:
         raise ZkAesError("GCM: only full 16-byte tags are supported")
     msg, ok = C.create_string_buffer(max(len(ciphertext), 1)), C.c_int()
-    _check(lib().zkaes_gcm_decrypt(bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(tag), msg, C.byref(ok)))
+    _check(lib().zkaes_gcm_decrypt_ks(bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(secret_key), C.c_size_t(len(secret_key)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(tag),
+                                      msg, C.byref(ok)))
     if not ok.value:
         return None
     return msg.raw[:len(ciphertext)]
@@ -521,7 +555,7 @@ def gcm_decrypt(ciphertext, secret_key, iv, aad, tag):
 
 def encrypt_gcm(message, secret_key, iv, aad, proving_key, zk_seed=None):
     """one proof over a GCM key -> (ciphertext, tag, serialized MarlinProof bytes); zk_seed as encrypt"""
-    _gcm_args(secret_key, iv)
+    _gcm_args(secret_key, iv, proving_key.key_bytes())
     ct, tag = C.create_string_buffer(max(len(message), 1)), C.create_string_buffer(16)
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_encrypt_gcm_seeded(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), proving_key._p, zk_seed, ct, tag,
@@ -548,33 +582,22 @@ def proof_roundtrip(proof):
     return _take(out, n)
 
 
-def circuit_info(circuit, plaintext_length, aad_length=0):
-    """aad_length: GCM circuits only"""
+def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128):
+    """aad_length: GCM circuits only; key_bits: 128, 192 or 256 for the AES kinds"""
     out = (C.c_uint64 * 12)()
-    if int(circuit) == CIRCUIT_AES_GCM:
-        _check(lib().zkaes_circuit_info_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), out))
-    else:
-        _check(lib().zkaes_circuit_info(int(circuit), C.c_size_t(plaintext_length), out))
+    _check(lib().zkaes_circuit_info_ks(int(circuit), C.c_uint(int(key_bits)), C.c_size_t(plaintext_length), C.c_size_t(aad_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix(circuit, plaintext_length, which, aad_length=0):
+def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    if int(circuit) == CIRCUIT_AES_GCM:
-        _check(lib().zkaes_circuit_matrix_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), which, C.byref(rows), C.byref(nnz), None, None, None))
-        rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
-        col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
-        coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-        _check(lib().zkaes_circuit_matrix_gcm(C.c_size_t(plaintext_length), C.c_size_t(aad_length), which, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
-                                              coeff.ctypes.data_as(C.c_void_p)))
-        return rowptr, col[:nnz.value], coeff[:nnz.value]
-    _check(lib().zkaes_circuit_matrix(int(circuit), C.c_size_t(plaintext_length), which, C.byref(rows), C.byref(nnz), None, None, None))
+    head = (int(circuit), C.c_uint(int(key_bits)), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
+    _check(lib().zkaes_circuit_matrix_ks(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
     coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-    _check(lib().zkaes_circuit_matrix(int(circuit), C.c_size_t(plaintext_length), which, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
-                                      coeff.ctypes.data_as(C.c_void_p)))
+    _check(lib().zkaes_circuit_matrix_ks(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 

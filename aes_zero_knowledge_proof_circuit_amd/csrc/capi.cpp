@@ -10,11 +10,12 @@ extern "C" {
 void zkaes_pk_free(zkaes_pk *pk) { delete pk; }
 int zkaes_device_count(void) { return zk::gpu::device_count(); }
 
-static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128) {
     return guard([&] {
         if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
+        if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("synthesize_keys: key_bits must be 128, 192 or 256");
         zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
-        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len);
+        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len, key_bits);
         zkaes_vk *v = new zkaes_vk{k->vk()};
         zkaes_pk *p = new zkaes_pk{std::move(k)};
         if (pk) *pk = p; else delete p;
@@ -26,6 +27,15 @@ int zkaes_synthesize_keys_ex2(int kind, size_t len, size_t nc, size_t nv, size_t
 }
 int zkaes_synthesize_keys_gcm(size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return synthesize(ZKAES_CIRCUIT_AES_GCM, len, aad_len, nc, nv, nnz, flags, pk, vk);
+}
+int zkaes_synthesize_keys_ks(int kind, unsigned key_bits, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits);      // (compile_circuit refuses aad outside GCM and an ops kind with another key size)
+}
+int zkaes_pk_key_bytes(const zkaes_pk *pk, size_t *n) {
+    return guard([&] {
+        if (!pk || !n) throw std::invalid_argument("null argument");
+        *n = pk->pk->key_bytes();
+    });
 }
 int zkaes_synthesize_keys_ex(int kind, size_t len, size_t nc, size_t nv, size_t nnz, zkaes_pk **pk, zkaes_vk **vk) {
     return zkaes_synthesize_keys_ex2(kind, len, nc, nv, nnz, 0u, pk, vk);
@@ -80,7 +90,7 @@ int zkaes_encrypt_batch_seeded_at(size_t n, const uint8_t *messages, size_t mess
         if (!pk || !proofs || !proofs_len || (n && (!messages || !secret_keys))) throw std::invalid_argument("null argument");
         size_t chunk = pk->pk->circuit().n_blocks * 16;
         if (messages_len != n * chunk) throw std::invalid_argument("messages must hold n x " + std::to_string(chunk) + " bytes (the key's plaintext length)");
-        if (secret_keys_len != n * 16) throw std::invalid_argument("secret_keys must hold n x 16 bytes");
+        if (secret_keys_len != n * pk->pk->key_bytes()) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(pk->pk->key_bytes()) + " bytes");
         pack_proofs(pk->pk->prove_aes_batch(messages, secret_keys, n, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
     });
 }
@@ -92,7 +102,7 @@ int zkaes_encrypt_batch(size_t n, const uint8_t *messages, const uint8_t *secret
     size_t chunk = pk ? pk->pk->circuit().n_blocks * 16 : 0;
     uint8_t seed[32];
     { int rc = guard([&] { zk::os_random_seed(seed); }); if (rc) return rc; }
-    return zkaes_encrypt_batch_seeded_at(n, messages, n * chunk, secret_keys, n * 16, pk, seed, 0, proofs, proofs_len, proof_lens);
+    return zkaes_encrypt_batch_seeded_at(n, messages, n * chunk, secret_keys, n * (pk ? pk->pk->key_bytes() : 16), pk, seed, 0, proofs, proofs_len, proof_lens);
 }
 // ---- AES-128-CBC (include/zkaes.h): the prover side; the host-only calls (zkaes_cbc_ciphertext, the verifiers) are in capi_host.cpp
 int zkaes_encrypt_cbc_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], const zkaes_pk *pk, const uint8_t *seed, uint8_t *ciphertext_or_null,
@@ -192,7 +202,7 @@ int zkaes_encrypt_gcm_batch_seeded_at(size_t n, const uint8_t *messages, size_t 
         const zk::Circuit &c = pk->pk->circuit();
         if (c.kind != zk::CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
         if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
-        if (secret_keys_len != n * 16) throw std::invalid_argument("secret_keys must hold n x 16 bytes");
+        if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
         if (headers_len != n * (12 + c.aad_bytes)) throw std::invalid_argument("headers must hold n x " + std::to_string(12 + c.aad_bytes) + " bytes (iv, then the key's aad length)");
         pack_proofs(pk->pk->prove_aes_gcm_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null), proofs, proofs_len,
                     proof_lens);

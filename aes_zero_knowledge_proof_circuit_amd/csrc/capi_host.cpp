@@ -5,7 +5,8 @@
 
 namespace {
 thread_local std::string g_err;
-zk::Circuit compile(int kind, size_t len, size_t aad_len = 0) { return zk::compile_circuit(kind, len, aad_len); }
+zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128) { return zk::compile_circuit(kind, len, aad_len, key_bits); }
+void require_key_len(size_t key_len) { if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes"); }
 // the CBC (and CTR) instance without the leading One: 128 bits of the IV (the initial counter block), then the ciphertext bits, each byte LSB first
 std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
     std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 16), c = zk::ciphertext_to_public_input(ct, ct_len);
@@ -49,6 +50,22 @@ int zkaes_cbc_ciphertext(const uint8_t *msg, size_t len, const uint8_t key[16], 
         zk::aes128_cbc_encrypt_host(msg, len, key, iv, ct);
     });
 }
+int zkaes_ecb_ciphertext_ks(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, uint8_t *ct) {
+    return guard([&] {
+        if (!msg || !key || !ct) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        if (len == 0 || len % 16) throw std::invalid_argument("ECB: the message must be a non-zero multiple of 16 bytes");
+        zk::aes_ecb_encrypt_host(msg, len, key, key_len, ct);
+    });
+}
+int zkaes_cbc_ciphertext_ks(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[16], uint8_t *ct) {
+    return guard([&] {
+        if (!msg || !key || !iv || !ct) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
+        zk::aes128_cbc_encrypt_host(msg, len, key, iv, ct, key_len);
+    });
+}
 int zkaes_verify_encryption_cbc(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[16], const uint8_t *ct, size_t ct_len, int *accepted) {
     return guard([&] {
         if (!vk || !proof || !iv || !ct || !accepted) throw std::invalid_argument("null argument");
@@ -87,6 +104,14 @@ int zkaes_ctr_crypt(const uint8_t *in, size_t len, const uint8_t key[16], const 
         if (!in || !key || !icb || !out) throw std::invalid_argument("null argument");
         if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
         zk::aes128_ctr_crypt_host(in, len, key, icb, out);
+    });
+}
+int zkaes_ctr_crypt_ks(const uint8_t *in, size_t len, const uint8_t *key, size_t key_len, const uint8_t icb[16], uint8_t *out) {
+    return guard([&] {
+        if (!in || !key || !icb || !out) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
+        zk::aes128_ctr_crypt_host(in, len, key, icb, out, key_len);
     });
 }
 int zkaes_ctr_counter_add(const uint8_t icb[16], uint64_t n_blocks, uint8_t out[16]) {
@@ -141,22 +166,30 @@ int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
     });
 }
 // ---- AES-128-GCM.  Public input: 96 iv bits, the aad bits, the ciphertext bits, 128 tag bits.
-int zkaes_gcm_encrypt(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]) {
+int zkaes_gcm_encrypt_ks(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]) {
     return guard([&] {
         if (!key || !iv || !tag || (len && (!msg || !ct)) || (aad_len && !aad)) throw std::invalid_argument("null argument");
-        zk::aes128_gcm_encrypt_host(msg, len, key, iv, aad, aad_len, ct, tag);
+        require_key_len(key_len);
+        zk::aes128_gcm_encrypt_host(msg, len, key, iv, aad, aad_len, ct, tag, key_len);
     });
 }
+int zkaes_gcm_encrypt(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]) {
+    return zkaes_gcm_encrypt_ks(msg, len, key, 16, iv, aad, aad_len, ct, tag);
+}
 int zkaes_gcm_decrypt(const uint8_t *ct, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t tag[16], uint8_t *msg, int *ok) {
+    return zkaes_gcm_decrypt_ks(ct, len, key, 16, iv, aad, aad_len, tag, msg, ok);
+}
+int zkaes_gcm_decrypt_ks(const uint8_t *ct, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t tag[16], uint8_t *msg, int *ok) {
     return guard([&] {
         if (!key || !iv || !tag || !ok || (len && (!msg || !ct)) || (aad_len && !aad)) throw std::invalid_argument("null argument");
         *ok = 0;
+        require_key_len(key_len);
         // GCM's keystream does not depend on the data, so "encrypting" the ciphertext gives the plaintext -- and a tag over that plaintext, not the one wanted: the tag is
         // GHASH over the CIPHERTEXT, which a second pass computes by encrypting the candidate plaintext back.  Nothing reaches the caller's buffer before the tag holds.
         std::vector<uint8_t> pt(len ? len : 1), back(len ? len : 1);
         uint8_t t[16];
-        zk::aes128_gcm_encrypt_host(ct, len, key, iv, aad, aad_len, pt.data(), t);
-        zk::aes128_gcm_encrypt_host(pt.data(), len, key, iv, aad, aad_len, back.data(), t);
+        zk::aes128_gcm_encrypt_host(ct, len, key, iv, aad, aad_len, pt.data(), t, key_len);
+        zk::aes128_gcm_encrypt_host(pt.data(), len, key, iv, aad, aad_len, back.data(), t, key_len);
         unsigned diff = 0;
         for (int i = 0; i < 16; i++) diff |= (unsigned)(t[i] ^ tag[i]);                // no early exit: the time does not tell where the tags differ
         if (diff) return;
@@ -261,9 +294,10 @@ int zkaes_vk_from_trapdoor(const uint64_t info[7], const uint8_t *index_comms, c
 }
 int zkaes_circuit_info(int kind, size_t len, uint64_t out[12]) { return guard([&] { fill_info(compile(kind, len), out); }); }
 int zkaes_circuit_info_gcm(size_t len, size_t aad_len, uint64_t out[12]) { return guard([&] { fill_info(compile(zk::CIRCUIT_AES_GCM, len, aad_len), out); }); }
-static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+int zkaes_circuit_info_ks(int kind, unsigned key_bits, size_t len, size_t aad_len, uint64_t out[12]) { return guard([&] { fill_info(compile(kind, len, aad_len, key_bits), out); }); }
+static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff, size_t key_bits = 128) {
     return guard([&] {
-        zk::Circuit c = compile(kind, len, aad_len);
+        zk::Circuit c = compile(kind, len, aad_len, key_bits);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -274,6 +308,9 @@ static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint6
 }
 int zkaes_circuit_matrix(int kind, size_t len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(kind, len, 0, which, n_rows, nnz, rowptr, col, coeff);
+}
+int zkaes_circuit_matrix_ks(int kind, unsigned key_bits, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits);
 }
 int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(zk::CIRCUIT_AES_GCM, len, aad_len, which, n_rows, nnz, rowptr, col, coeff);

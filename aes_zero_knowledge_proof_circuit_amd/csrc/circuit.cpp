@@ -218,9 +218,9 @@ CsrMatrix finalize_matrix(const RawMatrix &m, uint32_t n_inst_padded, size_t row
 }
 
 // ark-marlin padding (pad_input_for_indexer_and_prover + make_matrices_square) and final column numbering
-Circuit finish(Builder &b, int kind, size_t n_blocks, size_t trace_bytes) {
+Circuit finish(Builder &b, int kind, size_t n_blocks, size_t trace_bytes, size_t key_bytes = 16) {
     Circuit c;
-    c.kind = kind; c.n_blocks = n_blocks; c.message_bytes = 16 * n_blocks; c.trace_bytes = trace_bytes;
+    c.kind = kind; c.n_blocks = n_blocks; c.key_bytes = key_bytes; c.message_bytes = 16 * n_blocks; c.trace_bytes = trace_bytes;
     c.raw_constraints = b.A.rowptr.size() - 1; c.raw_instance = b.n_instance; c.raw_witness = b.n_witness;
     size_t ninst = 1;
     while (ninst < b.n_instance) ninst <<= 1;
@@ -252,62 +252,72 @@ uint8_t aes_sbox_value(uint8_t x) {   // algebraic S-box (FIPS-197 5.1.1; equals
 
 namespace {
 
-// The gates both AES modes share, in the reference's order: the key schedule once, then per block the ten rounds behind a round-0 input.  ECB feeds the message block,
-// CBC the chained block X_b; everything a block allocates from its round 0 on is the same gate sequence in both.
+// The gates every AES mode shares, in the reference's order: the key schedule once, then per block the Nr rounds behind a round-0 input.  ECB feeds the message block,
+// CBC the chained block X_b; everything a block allocates from its round 0 on is the same gate sequence in both.  nk = the key length in words (4, 6, 8): Nr = nk + 6
+// rounds, 4 (Nr + 1) schedule words (FIPS-197 5.2), the trace laid out by the TRK_* macros of trace_layout.h; at nk = 4 every gate and every offset is the reference's.
 struct AesGates {
     Builder &b;
+    const int nk, nr;
     std::vector<Byte> table;
-    std::array<Byte, 16> key;
-    std::array<std::array<Byte, 4>, 44> w;
-    explicit AesGates(Builder &b_) : b(b_), table(256) {
+    std::vector<Byte> key;
+    std::vector<std::array<Byte, 4>> w;
+    AesGates(Builder &b_, size_t key_bits) : b(b_), nk((int)(key_bits / 32)), nr(nk + 6), table(256), key(4 * (size_t)nk), w(4 * ((size_t)nr + 1)) {
         for (int i = 0; i < 256; i++) table[i] = Builder::const_byte(aes_sbox_value((uint8_t)i));
     }
-    static uint32_t blk(size_t bi) { return (uint32_t)(TR_BLOCK0 + bi * TR_BLOCK_STRIDE); }
+    size_t key_bytes() const { return 4 * (size_t)nk; }
+    uint32_t blk(size_t bi) const { return (uint32_t)(TRK_BLOCK0(nk) + bi * TRK_BLOCK_STRIDE(nk)); }
     // message then key witnesses (src/lib.rs:70-76, 82-88)
     std::vector<Byte> alloc_message_and_key(size_t len) {
         std::vector<Byte> msg(len);
         for (size_t i = 0; i < len; i++) msg[i] = b.alloc_byte(false, blk(i / 16) + TR_BL_MSG + (uint32_t)(i % 16));
-        for (int i = 0; i < 16; i++) key[i] = b.alloc_byte(false, TR_KEY + i);
+        for (int i = 0; i < 4 * nk; i++) key[i] = b.alloc_byte(false, TR_KEY + i);
         return msg;
     }
     // derive_keys (src/aes_circuit.rs:20-129): words are big-endian byte quadruples; UInt32::xor runs LSB-first over the
-    // u32, i.e. byte 3 first (to_u32, :201-212)
+    // u32, i.e. byte 3 first (to_u32, :201-212).  FIPS-197 5.2 for any nk: W_i = W_{i-nk} ^ temp, temp = SubWord(RotWord(W_{i-1})) ^ Rcon at i % nk == 0,
+    // SubWord(W_{i-1}) at i % nk == 4 when nk = 8, else W_{i-1}
     void key_schedule() {
-        for (int i = 0; i < 4; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
+        for (int i = 0; i < nk; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
         static const uint8_t rc[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
-        for (int i = 4; i < 44; i++) {
-            if (i % 4 == 0) {
-                int q = i / 4 - 1;
+        for (int i = nk; i < 4 * (nr + 1); i++) {
+            if (i % nk == 0) {
+                int q = TRK_KS_INST_OF(nk, i);
                 std::array<Byte, 4> sub;
                 for (int k = 0; k < 4; k++) {
                     int src = (k + 1) % 4;                                            // rotate_word: rotate_left(1)
-                    sub[k] = b.sbox(w[i - 1][src], table, (uint32_t)(TR_KS_W + 4 * (i - 1) + src));
+                    sub[k] = b.sbox(w[i - 1][src], table, (uint32_t)(TRK_KS_W(nk) + 4 * (i - 1) + src));
                 }
-                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - 4][k], sub[k], (uint32_t)(TR_KS_PRE + 4 * q + k));
-                w[i][0] = b.xor_byte(w[i][0], Builder::const_byte(rc[q]), 0);         // Rcon: constant operand, free
+                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - nk][k], sub[k], (uint32_t)(TRK_KS_PRE(nk) + 4 * q + k));
+                w[i][0] = b.xor_byte(w[i][0], Builder::const_byte(rc[i / nk - 1]), 0);         // Rcon: constant operand, free
+            } else if (nk == 8 && i % 8 == 4) {
+                int q = TRK_KS_INST_OF(nk, i);                                        // no rotation, no Rcon: the word ahead of the (absent) Rcon xor is W_i itself
+                std::array<Byte, 4> sub;
+                for (int k = 0; k < 4; k++) sub[k] = b.sbox(w[i - 1][k], table, (uint32_t)(TRK_KS_W(nk) + 4 * (i - 1) + k));
+                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - nk][k], sub[k], (uint32_t)(TRK_KS_PRE(nk) + 4 * q + k));
             } else {
-                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - 4][k], w[i - 1][k], (uint32_t)(TR_KS_W + 4 * i + k));
+                for (int k = 3; k >= 0; k--) w[i][k] = b.xor_byte(w[i - nk][k], w[i - 1][k], (uint32_t)(TRK_KS_W(nk) + 4 * i + k));
             }
         }
     }
-    // one block's rounds (src/lib.rs:194-278) from its round-0 input `in`; returns S_10
+    // one block's rounds (src/lib.rs:194-278) from its round-0 input `in`; returns S_Nr
     std::array<Byte, 16> block_rounds(const Byte *in, size_t bi) {
         uint32_t base = blk(bi);
+        const uint32_t xt_off = TRK_BL_XT(nk), mp_off = TRK_BL_MP(nk);
         std::array<Byte, 16> s, t, u;
-        for (int i = 0; i < 16; i++) s[i] = b.xor_byte(in[i], key[i], base + TR_BL_S + i);          // :196 raw key
-        for (int r = 1; r <= 10; r++) {
+        for (int i = 0; i < 16; i++) s[i] = b.xor_byte(in[i], key[i], base + TR_BL_S + i);          // :196 raw key (round key 0 = the first 16 key bytes for every nk)
+        for (int r = 1; r <= nr; r++) {
             for (int i = 0; i < 16; i++) {                                                                      // substitute_bytes
                 t[i] = b.sbox(s[i], table, base + TR_BL_S + 16 * (r - 1) + i);
             }
             for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = t[4 * ((c + rr) % 4) + rr];   // shift_rows
-            if (r <= 9) {                                                                                        // mix_columns
+            if (r <= nr - 1) {                                                                                   // mix_columns
                 for (int c = 0; c < 4; c++) {
                     std::array<Byte, 4> a{u[4 * c], u[4 * c + 1], u[4 * c + 2], u[4 * c + 3]}, xb;
                     for (int k = 0; k < 4; k++) {
                         Byte sh = Builder::shr(a[k], 7), h, one = Builder::const_byte(1);
                         for (int i = 0; i < 8; i++) h[i] = b.band(sh[i], one[i]);
                         Byte m = b.helpers_multiply(h, 0x1B);
-                        xb[k] = b.xor_byte(Builder::shl(a[k], 1), m, base + TR_BL_XT + 16 * (r - 1) + 4 * c + k);
+                        xb[k] = b.xor_byte(Builder::shl(a[k], 1), m, base + xt_off + 16 * (r - 1) + 4 * c + k);
                     }
                     static const int order[4][5][2] = {{{1, 0}, {0, 3}, {0, 2}, {1, 1}, {0, 1}}, {{1, 1}, {0, 0}, {0, 3}, {1, 2}, {0, 2}},
                                                        {{1, 2}, {0, 1}, {0, 0}, {1, 3}, {0, 3}}, {{1, 3}, {0, 2}, {0, 1}, {1, 0}, {0, 0}}};
@@ -315,7 +325,7 @@ struct AesGates {
                         Byte acc = order[o][0][0] ? xb[order[o][0][1]] : a[order[o][0][1]];
                         for (int p = 1; p < 5; p++) {
                             const Byte &x = order[o][p][0] ? xb[order[o][p][1]] : a[order[o][p][1]];
-                            acc = b.xor_byte(acc, x, base + TR_BL_MP + 64 * (r - 1) + 4 * (4 * c + o) + (p - 1));
+                            acc = b.xor_byte(acc, x, base + mp_off + 64 * (r - 1) + 4 * (4 * c + o) + (p - 1));
                         }
                         t[4 * c + o] = acc;
                     }
@@ -334,7 +344,7 @@ struct AesGates {
     // public inputs + equality (src/lib.rs:282-286)
     void ciphertext_inputs(const std::vector<Byte> &ct) {
         for (size_t i = 0; i < ct.size(); i++) {
-            Byte pi = b.alloc_byte(true, blk(i / 16) + TR_BL_S + 160 + (uint32_t)(i % 16));
+            Byte pi = b.alloc_byte(true, blk(i / 16) + (uint32_t)TRK_BL_CT(nk) + (uint32_t)(i % 16));
             for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
         }
     }
@@ -342,11 +352,18 @@ struct AesGates {
 
 }  // namespace
 
-Circuit compile_aes_circuit(size_t len) {
+namespace {
+void require_key_bits(size_t key_bits) {
+    if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("the AES key size must be 128, 192 or 256 bits");
+}
+}  // namespace
+
+Circuit compile_aes_circuit(size_t len, size_t key_bits) {
     if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
+    require_key_bits(key_bits);
     size_t nb = len / 16;
     Builder b;
-    AesGates g(b);
+    AesGates g(b, key_bits);
     std::vector<Byte> msg = g.alloc_message_and_key(len);
     g.key_schedule();
     std::vector<Byte> ct(len);
@@ -355,17 +372,18 @@ Circuit compile_aes_circuit(size_t len) {
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = s[i];
     }
     g.ciphertext_inputs(ct);
-    return finish(b, CIRCUIT_AES, nb, TR_BLOCK0 + nb * TR_BLOCK_STRIDE);
+    return finish(b, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), g.key_bytes());
 }
 
 // Gate order: message and key witnesses, the 16 IV bytes as inputs, the key schedule, per block the 128 xor gates of X_b = M_b ^ prev (prev = the IV bytes, then the
 // previous block's S_10) and the block's rounds from X_b, the ciphertext inputs.  The instance is One, 128 IV bits, 128 nb ciphertext bits.
-Circuit compile_aes_cbc_circuit(size_t len) {
+Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits) {
     if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
+    require_key_bits(key_bits);
     size_t nb = len / 16;
-    const uint32_t cbc = (uint32_t)TR_CBC(nb);
     Builder b;
-    AesGates g(b);
+    AesGates g(b, key_bits);
+    const uint32_t cbc = (uint32_t)TRK_CBC(g.nk, nb);
     std::vector<Byte> msg = g.alloc_message_and_key(len);
     std::array<Byte, 16> prev;
     for (int i = 0; i < 16; i++) prev[i] = b.alloc_byte(true, cbc + TR_CBC_IV + (uint32_t)i);
@@ -378,7 +396,7 @@ Circuit compile_aes_cbc_circuit(size_t len) {
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = prev[i];
     }
     g.ciphertext_inputs(ct);
-    return finish(b, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb);
+    return finish(b, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, g.key_bytes());
 }
 
 // Gate order: message and key witnesses, the 16 ICB bytes as inputs, the key schedule, per block (from the second on) the incrementer over the previous block's counter
@@ -386,13 +404,14 @@ Circuit compile_aes_cbc_circuit(size_t len) {
 // 128 ICB bits, 8 len ciphertext bits.
 // Incrementer: counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8.  c_0 = 1, y_i = x_i ^ c_i, c_{i+1} = x_i & c_i (none behind i = 127: the sum is mod 2^128).
 // Position 0 folds away (y_0 = !x_0, c_1 = x_0), which leaves 127 xor and 126 and gates per increment.
-Circuit compile_aes_ctr_circuit(size_t len) {
+Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits) {
     if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
+    require_key_bits(key_bits);
     size_t nb = (len + 15) / 16;
-    const uint32_t ctr = (uint32_t)TR_CTR(nb);
-    auto slot = [&](size_t bi) { return ctr + (uint32_t)(TR_CTR_BLOCK0 + bi * TR_CTR_BLOCK_STRIDE); };
     Builder b;
-    AesGates g(b);
+    AesGates g(b, key_bits);
+    const uint32_t ctr = (uint32_t)TRK_CTR(g.nk, nb);
+    auto slot = [&](size_t bi) { return ctr + (uint32_t)(TR_CTR_BLOCK0 + bi * TR_CTR_BLOCK_STRIDE); };
     std::vector<Byte> msg = g.alloc_message_and_key(len);
     std::array<Byte, 16> cnt;
     for (int i = 0; i < 16; i++) cnt[i] = b.alloc_byte(true, ctr + TR_CTR_ICB + (uint32_t)i);
@@ -422,7 +441,7 @@ Circuit compile_aes_ctr_circuit(size_t len) {
         Byte pi = b.alloc_byte(true, slot(i / 16) + TR_CTR_BL_CT + (uint32_t)(i % 16));
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
     }
-    Circuit c = finish(b, CIRCUIT_AES_CTR, nb, TR_CTR_BYTES(nb));
+    Circuit c = finish(b, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), g.key_bytes());
     c.message_bytes = len;
     return c;
 }
@@ -436,15 +455,16 @@ Circuit compile_aes_ctr_circuit(size_t len) {
 // p_{i,k} = x_i & V_i[k] (16,384 and gates), then per output bit k a boolean y_k, seven booleans q_{k,0..6} and ONE row (sum_i p_{i,k} - y_k - 2 sum_j 2^j q_{k,j}) * One = 0:
 // y_k is the parity of the 128 products and q_k <= 64 their half.  The difference sits in A, as in enforce_equal, so A's row is 0 on a satisfied witness.  X_1 is the
 // first block itself; X_m = Y_{m-1} ^ block m costs one xor gate per existing bit (zero padding and the constant length block cost none).
-Circuit compile_aes_gcm_circuit(size_t len, size_t alen) {
+Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits) {
+    require_key_bits(key_bits);
     if (len == 0) throw std::invalid_argument("GCM: the message must have at least one byte");
     if (len > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM: message and aad of one proof are limited to 65536 bytes each");
     const size_t nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TR_GCM_MULS(na, nb);
-    const uint32_t gcm = (uint32_t)TR_GCM(nb);
+    const uint32_t gcm = (uint32_t)TRK_GCM(key_bits / 32, nb);
     using Blk = std::array<Bit, 128>;
     auto to_blk = [](const Byte *bytes) { Blk r; for (int k = 0; k < 128; k++) r[k] = bytes[k / 8][7 - k % 8]; return r; };
     Builder b;
-    AesGates g(b);
+    AesGates g(b, key_bits);
     std::vector<Byte> msg = g.alloc_message_and_key(len);
     std::array<Byte, 16> in;
     for (int i = 0; i < 12; i++) in[i] = b.alloc_byte(true, gcm + TR_GCM_IV + (uint32_t)i);
@@ -512,54 +532,72 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen) {
         Byte pi = b.alloc_byte(true, tag_off + (uint32_t)j);
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], tag[j][k]);
     }
-    Circuit c = finish(b, CIRCUIT_AES_GCM, nb, TR_GCM_BYTES(na, nb));
+    Circuit c = finish(b, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), g.key_bytes());
     c.message_bytes = len; c.aad_bytes = alen;
     return c;
 }
 
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len) {
-    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len);
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits) {
+    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len, key_bits);
     if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
-    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len);
-    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len);
-    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len);
+    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits);
+    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits);
+    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits);
+    if (key_bits != 128) throw std::invalid_argument("the ops circuits have no AES key: key_bits must be 128");
     return compile_ops_circuit(kind);
 }
 
 namespace {
-// plain byte-wise AES-128 over aes_sbox_value for the host-side modes
+// plain byte-wise AES over aes_sbox_value for the host-side modes; key_len = 16, 24 or 32 bytes (the name dates from when 16 was the only one)
 struct HostAes128 {
-    uint8_t sb[256], rk[11][16];                                              // FIPS-197 5.2, round keys as 16 bytes in word order
+    uint8_t sb[256], rk[15][16];                                              // FIPS-197 5.2, round keys as 16 bytes in word order: rk[r] = W_4r .. W_4r+3
+    int nr;
     static uint8_t xt(uint8_t c) { return (uint8_t)((c << 1) ^ ((c >> 7) * 0x1B)); }
-    explicit HostAes128(const uint8_t key[16]) {
+    explicit HostAes128(const uint8_t *key, size_t key_len = 16) {
+        if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes");
+        const int nk = (int)(key_len / 4);
+        nr = nk + 6;
         for (int i = 0; i < 256; i++) sb[i] = aes_sbox_value((uint8_t)i);
-        for (int i = 0; i < 16; i++) rk[0][i] = key[i];
+        uint8_t *w = &rk[0][0];                                               // word i at w + 4 i
+        for (size_t i = 0; i < key_len; i++) w[i] = key[i];
         uint8_t rc = 1;
-        for (int r = 1; r <= 10; r++) {
-            const uint8_t *p = rk[r - 1];
-            uint8_t t[4] = {(uint8_t)(sb[p[13]] ^ rc), sb[p[14]], sb[p[15]], sb[p[12]]};
-            for (int i = 0; i < 16; i++) rk[r][i] = (uint8_t)(p[i] ^ (i < 4 ? t[i] : rk[r][i - 4]));
-            rc = xt(rc);
+        for (int i = nk; i < 4 * (nr + 1); i++) {
+            const uint8_t *p = w + 4 * (i - 1);
+            uint8_t t[4] = {p[0], p[1], p[2], p[3]};
+            if (i % nk == 0) { t[0] = (uint8_t)(sb[p[1]] ^ rc); t[1] = sb[p[2]]; t[2] = sb[p[3]]; t[3] = sb[p[0]]; rc = xt(rc); }
+            else if (nk == 8 && i % 8 == 4) for (int k = 0; k < 4; k++) t[k] = sb[p[k]];
+            for (int k = 0; k < 4; k++) w[4 * i + k] = (uint8_t)(w[4 * (i - nk) + k] ^ t[k]);
         }
     }
     void encrypt_block(uint8_t s[16]) const {                                 // in place
         uint8_t u[16];
         for (int i = 0; i < 16; i++) s[i] ^= rk[0][i];
-        for (int r = 1; r <= 10; r++) {
+        for (int r = 1; r <= nr; r++) {
             for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = sb[s[4 * ((c + rr) & 3) + rr]];     // SubBytes + ShiftRows
             for (int c = 0; c < 4; c++) {
                 const uint8_t *a = u + 4 * c;
                 for (int k = 0; k < 4; k++)
-                    s[4 * c + k] = (uint8_t)((r <= 9 ? xt(a[k]) ^ xt(a[(k + 1) & 3]) ^ a[(k + 1) & 3] ^ a[(k + 2) & 3] ^ a[(k + 3) & 3] : a[k]) ^ rk[r][4 * c + k]);
+                    s[4 * c + k] = (uint8_t)((r < nr ? xt(a[k]) ^ xt(a[(k + 1) & 3]) ^ a[(k + 1) & 3] ^ a[(k + 2) & 3] ^ a[(k + 3) & 3] : a[k]) ^ rk[r][4 * c + k]);
             }
         }
     }
 };
 }  // namespace
 
-void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out) {
+void aes_ecb_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, uint8_t *out) {
+    if (len % 16) throw std::invalid_argument("ECB: the message must be a multiple of 16 bytes");
+    HostAes128 aes(key, key_len);
+    uint8_t s[16];
+    for (size_t off = 0; off < len; off += 16) {
+        for (int i = 0; i < 16; i++) s[i] = msg[off + i];
+        aes.encrypt_block(s);
+        for (int i = 0; i < 16; i++) out[off + i] = s[i];
+    }
+}
+
+void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[16], uint8_t *out, size_t key_len) {
     if (len % 16) throw std::invalid_argument("CBC: the message must be a multiple of 16 bytes");
-    HostAes128 aes(key);
+    HostAes128 aes(key, key_len);
     uint8_t prev[16], s[16];
     for (int i = 0; i < 16; i++) prev[i] = iv[i];
     for (size_t off = 0; off < len; off += 16) {
@@ -577,8 +615,8 @@ void ctr_counter_add(const uint8_t counter[16], uint64_t n, uint8_t out[16]) {
     }
 }
 
-void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *out) {
-    HostAes128 aes(key);
+void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t *key, const uint8_t icb[16], uint8_t *out, size_t key_len) {
+    HostAes128 aes(key, key_len);
     uint8_t ctr[16], s[16];
     for (int i = 0; i < 16; i++) ctr[i] = icb[i];
     for (size_t off = 0; off < len; off += 16) {
@@ -607,8 +645,8 @@ Gf128 gf_mul(const Gf128 &x, const Gf128 &y) {
 }
 }  // namespace
 
-void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]) {
-    HostAes128 aes(key);
+void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16], size_t key_len) {
+    HostAes128 aes(key, key_len);
     uint8_t hb[16] = {0}, s[16], blk[16];
     aes.encrypt_block(hb);
     const Gf128 h = gf_load(hb);

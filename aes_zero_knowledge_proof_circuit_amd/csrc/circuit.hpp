@@ -28,6 +28,7 @@ struct Circuit {
     int kind = CIRCUIT_AES;
     size_t n_blocks = 0;
     size_t message_bytes = 0;            // the statement's byte length: 16 n_blocks, except for a CTR key, or GCM key, whose last block may be partial (0 for the ops kinds)
+    size_t key_bytes = 16;               // the AES key's byte length: 16, 24 or 32 (AES-128, -192, -256); the trace is laid out for it (trace_layout.h TRK_*)
     size_t aad_bytes = 0;                // GCM keys: the byte length of the additional authenticated data, part of the statement like message_bytes
     // before padding (what debug_constraint_system_status would log, src/helpers/mod.rs:73-81)
     size_t raw_constraints = 0, raw_instance = 0, raw_witness = 0;
@@ -42,29 +43,35 @@ struct Circuit {
 };
 
 // message_len must be a multiple of 16 (else throws std::invalid_argument with the reference's message)
-Circuit compile_aes_circuit(size_t message_len);
+// Every AES compiler takes the key size in bits, 128 (the reference's, and the default), 192 or 256; anything else is std::invalid_argument.  The statement, the
+// public input and the gate order inside a round, the schedule and each mode do not depend on it; the round count (Nk + 6) and the schedule (FIPS-197 5.2) do.
+Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128);
 Circuit compile_ops_circuit(int kind);
 // AES-128-CBC over the same gadgets (no upstream counterpart; DESIGN.md "CBC"): public = 16 IV bytes then the ciphertext, private = message and key;
 // per block X_b = M_b ^ C_{b-1} (C_{-1} = IV) ahead of the block's round 0.  message_len must be a non-zero multiple of 16 (else std::invalid_argument)
-Circuit compile_aes_cbc_circuit(size_t message_len);
+Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128);
 // AES-128-CTR over the same gadgets (DESIGN.md "CTR"): public = the 16 bytes of the initial counter block then the ciphertext, private = message and key;
 // CTR_0 = icb, CTR_b = CTR_{b-1} + 1 mod 2^128 (big-endian, SP 800-38A B.1 with m = 128), C_b = M_b ^ AES(key, CTR_b), the last block cut to the bytes that exist.
 // message_len is any byte count >= 1 (else std::invalid_argument)
-Circuit compile_aes_ctr_circuit(size_t message_len);
+Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128);
 // AES-128-GCM (SP 800-38D, 96-bit IV, full tag; DESIGN.md "GCM"): public = iv (12 bytes), aad (aad_len bytes), ciphertext (message_len bytes), tag (16 bytes), private =
 // message and key.  The trace holds nb + 2 AES blocks (the message blocks under iv || be32(b + 2), H = AES_K(0), AES_K(iv || 1)), the V table of H and, per GHASH block,
 // one multiplication by H as 16,384 and gates and 128 parity rows.  message_len >= 1, aad_len >= 0; both are fixed by the key (else std::invalid_argument)
-Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len);
-// kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0);
+Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128);
+// kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
+// 128 for the ops kinds
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128);
 uint8_t aes_sbox_value(uint8_t x);   // the lookup table of src/aes_circuit.rs:433-694
 // plain byte-wise AES-128-CBC over aes_sbox_value, host only: out = len bytes, len a multiple of 16
-void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *out);
+// (the host ciphers keep their names; key_len = 16, 24 or 32 bytes selects AES-128, -192 or -256, anything else is std::invalid_argument)
+void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[16], uint8_t *out, size_t key_len = 16);
+// plain AES-ECB of whole blocks on the host
+void aes_ecb_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, uint8_t *out);
 // AES-128-CTR on the host, encryption and decryption alike: out = len bytes (any len), block b under the counter icb + b
-void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *out);
+void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t *key, const uint8_t icb[16], uint8_t *out, size_t key_len = 16);
 // out = counter + n mod 2^128, the 16 bytes read as one big-endian integer (out may alias counter)
 void ctr_counter_add(const uint8_t counter[16], uint64_t n, uint8_t out[16]);
 // AES-128-GCM encryption on the host (SP 800-38D 7.1 with a 96-bit IV): ct = len bytes (any len >= 0), tag = 16 bytes; GHASH by Algorithm 1, bit by bit
-void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16]);
+void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16], size_t key_len = 16);
 
 }  // namespace zk

@@ -249,17 +249,19 @@ void f_evals_from_tables(F *out, const F *va, const F *vb, const F *vc, const F 
 // ---- witness generation + sparse products
 void upload_sbox(const uint8_t table[256]);
 // one thread per ECB block (+ the key schedule): fills the trace of `nproofs` chunk-proofs of `nblocks` blocks each
-void aes_trace(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, uint32_t nproofs, uint32_t nblocks, stream_t s);
+// key_bytes (here and in the four launchers below) = 16, 24 or 32: AES-128, -192, -256.  keys = nproofs x key_bytes bytes (device), and the trace is laid out for that
+// key size (trace_layout.h TRK_*): every launcher checks trace_stride against that layout's byte count first and throws GpuError on a mismatch, before any lane runs
+void aes_trace(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, uint32_t nproofs, uint32_t nblocks, stream_t s, size_t key_bytes = 16);
 // CBC: ivs = nproofs x 16 bytes (device), the chaining value entering each proof's first block; the trace (stride >= the CBC layout's bytes) gains the IV and X_b tail
-void aes_trace_cbc(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s);
+void aes_trace_cbc(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s, size_t key_bytes = 16);
 // CTR: icbs = nproofs x 16 bytes (device), each proof's initial counter block; msgs = nproofs x msg_len bytes, packed, msg_len >= 1 and any value (ceil(msg_len / 16)
 // blocks, the last one partial); the trace (stride >= TR_CTR_BYTES) gains the counter tail
-void aes_trace_ctr(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *icbs, uint32_t nproofs, uint32_t msg_len, stream_t s);
+void aes_trace_ctr(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *icbs, uint32_t nproofs, uint32_t msg_len, stream_t s, size_t key_bytes = 16);
 // GCM: hdrs = nproofs x (12 + aad_len) bytes (device), each proof's iv then its aad; msgs = nproofs x msg_len bytes, packed, msg_len >= 1.  aes_trace_gcm fills the
 // nb + 2 AES blocks (message blocks, H, the tag mask), iv, aad and the C_b of the tail; ghash_trace, launched behind it on the same stream, reads H and the C_b from
 // the trace and fills the V table, every multiplication's X, P, q and Y and the tag.  stride >= TR_GCM_BYTES, a multiple of 16; trace 16-byte aligned
-void aes_trace_gcm(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s);
-void ghash_trace(uint8_t *trace, size_t trace_stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s);
+void aes_trace_gcm(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes = 16);
+void ghash_trace(uint8_t *trace, size_t trace_stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes = 16);
 // z[col] (0/1 bytes) for every column, by descriptor
 void witness_expand(uint8_t *z, const uint32_t *desc, uint32_t ncols, const uint8_t *trace, const uint32_t *sbox_in_off, const uint32_t *sbox_tmpl, stream_t s);
 // out[r] = sum_i coeff[i] * z[col[i]] as a field element, rows with no entries give 0 (out has `rows_out` >= rows entries, tail zeroed)

@@ -2,17 +2,19 @@
 //
 // Replaces the value side of the gadget synthesis in /root/reference/src/lib.rs:176-293 and src/aes_circuit.rs:20-427
 // (every UInt8/Boolean op there both allocates a variable and computes its value on the CPU): here
-//   k_aes_trace       one lane per block: plain AES-128 with every intermediate byte the circuit names written to the
+//   k_aes_trace       one lane per block: plain AES with every intermediate byte the circuit names written to the
 //                     per-proof trace buffer (layout: trace_layout.h); the mode (ECB / CBC) is a template parameter,
-//   k_aes_trace_ctr   the same for AES-128-CTR: a lane derives its block's counter and the incrementer's carries from the
+//   k_aes_trace_ctr   the same for AES-CTR: a lane derives its block's counter and the incrementer's carries from the
 //                     initial counter block, and the last block of a message may be partial,
-//   k_aes_trace_gcm   AES-128-GCM's nb + 2 AES blocks (the message under inc32 counters, H, the tag mask), and behind it
+//   k_aes_trace_gcm   AES-GCM's nb + 2 AES blocks (the message under inc32 counters, H, the tag mask), and behind it
 //   k_ghash_trace     the GHASH half: the V table of H and, per block, the 16,384 partial products, carries and result of
 //                     one multiplication in GF(2^128), sixteen lanes per multiplication, each re-walking the chain in registers,
 //   k_witness_expand  one lane per column of z: decode the variable's descriptor (compiled once by circuit.cpp) and gather
 //                     its bit -- S-box mux-tree variables are a table lookup S[(node << (level+1)) | (x & mask)],
 //   k_spmv_bits       z_A = A z, z_B = B z over 0/1 assignments with small integer coefficients (ark-marlin prover_init),
 //   k_t_evals         the round-2 "t" accumulation through a column-bucketed copy of A, B, C.
+// The trace kernels are templates on NK, the key length in words (4, 6, 8: AES-128, -192, -256), last and with default 4, so that a call without it is AES-128: NK sets
+// the schedule (FIPS-197 5.2), the round count NK + 6 and, through the TRK_* macros, where everything lies in the trace.
 #include <mutex>
 #include "hip_util.hpp"
 #include "trace_layout.h"
@@ -41,77 +43,97 @@ void upload_sbox(const uint8_t table[256]) {
     HIP_CHECK(hipMemcpy(g_sbox_dev[d], table, 256, hipMemcpyHostToDevice));
 }
 
+// the launchers' view of the key size: 16, 24 or 32 key bytes -> NK, and the trace size that belongs to it
+static int trace_nk(const char *who, size_t key_bytes) {
+    if (key_bytes != 16 && key_bytes != 24 && key_bytes != 32) throw GpuError(std::string(who) + ": the AES key must have 16, 24 or 32 bytes");
+    return (int)(key_bytes / 4);
+}
+static size_t trace_bytes_of(int nk, size_t b4, size_t b6, size_t b8) { return nk == 4 ? b4 : nk == 6 ? b6 : b8; }
+
 __device__ __forceinline__ uint8_t xtime(uint8_t c) { return (uint8_t)((c << 1) ^ (((c >> 7) & 1) * 0x1B)); }
 
-// One block's ten rounds from s = its state after round 0.  STORE: write every intermediate the circuit names into the block's trace slot `bl`; without it the
+// One block's NK + 6 rounds from s = its state after round 0.  STORE: write every intermediate the circuit names into the block's trace slot `bl`; without it the
 // lane only wants the ciphertext block left in s (a CBC lane walking to its chaining value).
-template <bool STORE>
+template <bool STORE, int NK = 4>
 __device__ __forceinline__ void aes_block_rounds(uint8_t s[16], const uint8_t (*w)[4], const uint8_t *__restrict__ sbox, uint8_t *__restrict__ bl) {
     uint8_t u[16], v[16];
-    for (int r = 1; r <= 10; r++) {
-        for (int i = 0; i < 16; i++) { v[i] = sbox[s[i]]; if (STORE) bl[TR_BL_SB + 16 * (r - 1) + i] = v[i]; }
+    for (int r = 1; r <= TRK_NR(NK); r++) {
+        for (int i = 0; i < 16; i++) { v[i] = sbox[s[i]]; if (STORE) bl[TRK_BL_SB(NK) + 16 * (r - 1) + i] = v[i]; }
         for (int c = 0; c < 4; c++) for (int rr = 0; rr < 4; rr++) u[4 * c + rr] = v[4 * ((c + rr) & 3) + rr];     // ShiftRows
-        if (r <= 9) {
+        if (r <= TRK_NR(NK) - 1) {
             for (int c = 0; c < 4; c++) {
                 uint8_t a[4], xb[4];
-                for (int k = 0; k < 4; k++) { a[k] = u[4 * c + k]; xb[k] = xtime(a[k]); if (STORE) bl[TR_BL_XT + 16 * (r - 1) + 4 * c + k] = xb[k]; }
+                for (int k = 0; k < 4; k++) { a[k] = u[4 * c + k]; xb[k] = xtime(a[k]); if (STORE) bl[TRK_BL_XT(NK) + 16 * (r - 1) + 4 * c + k] = xb[k]; }
                 // left-assoc xor chains of src/aes_circuit.rs:391-426
                 const uint8_t term[4][5] = {{xb[0], a[3], a[2], xb[1], a[1]}, {xb[1], a[0], a[3], xb[2], a[2]}, {xb[2], a[1], a[0], xb[3], a[3]}, {xb[3], a[2], a[1], xb[0], a[0]}};
                 for (int o = 0; o < 4; o++) {
                     uint8_t acc = term[o][0];
-                    for (int q = 1; q < 5; q++) { acc ^= term[o][q]; if (STORE) bl[TR_BL_MP + 64 * (r - 1) + 4 * (4 * c + o) + (q - 1)] = acc; }
+                    for (int q = 1; q < 5; q++) { acc ^= term[o][q]; if (STORE) bl[TRK_BL_MP(NK) + 64 * (r - 1) + 4 * (4 * c + o) + (q - 1)] = acc; }
                     v[4 * c + o] = acc;
                 }
             }
         } else {
             for (int i = 0; i < 16; i++) v[i] = u[i];
         }
-        for (int i = 0; i < 16; i++) { s[i] = v[i] ^ w[4 * r + i / 4][i % 4]; if (STORE) bl[TR_BL_S + 16 * r + i] = s[i]; }
+        for (int i = 0; i < 16; i++) { s[i] = v[i] ^ w[4 * r + i / 4][i % 4]; if (STORE) bl[TRK_BL_S(NK) + 16 * r + i] = s[i]; }
     }
 }
 
-// The key schedule (src/aes_circuit.rs:83-113): words big-endian, RotWord = bytes rotate-left 1.  Every lane needs w; the one lane per proof that owns the key-schedule
-// part of the trace passes `tr` and gets the SubWord bytes and the words ahead of the Rcon xor stored, the others pass null.
+// The key schedule (src/aes_circuit.rs:83-113; FIPS-197 5.2 for NK words): words big-endian, RotWord = bytes rotate-left 1.  Every lane needs w; the one lane per proof
+// that owns the key-schedule part of the trace passes `tr` and gets the SubWord bytes and the words ahead of the Rcon xor stored, the others pass null.  NK = 8 has a
+// second kind of SubWord instance at i % 8 == 4, without rotation and Rcon: its word "ahead of the Rcon xor" is W_i itself (trace_layout.h TRK_KS_INST_OF).
+template <int NK = 4>
 __device__ __forceinline__ void aes_key_schedule(const uint8_t *__restrict__ key, const uint8_t *__restrict__ sbox, uint8_t (*w)[4], uint8_t *__restrict__ tr) {
     const uint8_t rc[10] = {0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
-    for (int i = 0; i < 4; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
-    for (int i = 4; i < 44; i++) {
-        if (i % 4 == 0) {
-            int q = i / 4 - 1;
+    for (int i = 0; i < NK; i++) for (int k = 0; k < 4; k++) w[i][k] = key[4 * i + k];
+    for (int i = NK; i < TRK_KS_WORDS(NK); i++) {
+        if (i % NK == 0) {
+            int q = TRK_KS_INST_OF(NK, i);
             uint8_t sub[4], pre[4];
             for (int k = 0; k < 4; k++) sub[k] = sbox[w[i - 1][(k + 1) & 3]];
-            for (int k = 0; k < 4; k++) { pre[k] = w[i - 4][k] ^ sub[k]; w[i][k] = pre[k]; }
-            w[i][0] ^= rc[q];
-            if (tr) for (int k = 0; k < 4; k++) { tr[TR_KS_SUB + 4 * q + k] = sub[k]; tr[TR_KS_PRE + 4 * q + k] = pre[k]; }
+            for (int k = 0; k < 4; k++) { pre[k] = w[i - NK][k] ^ sub[k]; w[i][k] = pre[k]; }
+            w[i][0] ^= rc[i / NK - 1];
+            if (tr) for (int k = 0; k < 4; k++) { tr[TRK_KS_SUB(NK) + 4 * q + k] = sub[k]; tr[TRK_KS_PRE(NK) + 4 * q + k] = pre[k]; }
+        } else if (NK == 8 && i % 8 == 4) {
+            int q = TRK_KS_INST_OF(NK, i);
+            uint8_t sub[4];
+            for (int k = 0; k < 4; k++) sub[k] = sbox[w[i - 1][k]];
+            for (int k = 0; k < 4; k++) w[i][k] = w[i - NK][k] ^ sub[k];
+            if (tr) for (int k = 0; k < 4; k++) { tr[TRK_KS_SUB(NK) + 4 * q + k] = sub[k]; tr[TRK_KS_PRE(NK) + 4 * q + k] = w[i][k]; }
         } else {
-            for (int k = 0; k < 4; k++) w[i][k] = w[i - 4][k] ^ w[i - 1][k];
+            for (int k = 0; k < 4; k++) w[i][k] = w[i - NK][k] ^ w[i - 1][k];
         }
     }
+}
+// what the lane that owns the key-schedule part stores ahead of its mode's tail: the key and every schedule word
+template <int NK = 4>
+__device__ __forceinline__ void aes_store_schedule(uint8_t *__restrict__ tr, const uint8_t *__restrict__ key, const uint8_t (*w)[4]) {
+    for (int i = 0; i < TRK_KEY_BYTES(NK); i++) tr[TR_KEY + i] = key[i];
+    for (int i = 0; i < TRK_KS_WORDS(NK); i++) for (int k = 0; k < 4; k++) tr[TRK_KS_W(NK) + 4 * i + k] = w[i][k];
 }
 
 // grid: nproofs * (nblocks + 1) lanes; lane (p, 0) writes the key schedule part, lane (p, 1 + b) block b.
 // CBC: lane (p, 0) also stores the proof's IV in the trace tail; lane (p, 1 + b) starts from prev = ivs[p], runs plain AES without stores over blocks 0 .. b - 1 to reach
 // its own chaining value (at most nblocks - 1 extra blocks per lane), stores X_b = M_b ^ prev in the tail and goes on from s = X_b ^ key with all the usual stores.  The
 // kernel is handed the chunk's IV only, never a chain made on the host.  ivs is not read in the ECB instantiation.
-template <bool CBC>
+template <bool CBC, int NK = 4>
 __global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ ivs,
                             uint32_t nproofs, uint32_t nblocks, const uint8_t *__restrict__ sbox) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nproofs * (nblocks + 1)) return;
     uint32_t p = t / (nblocks + 1), which = t % (nblocks + 1);
     uint8_t *tr = trace + (size_t)p * stride;
-    const uint8_t *key = keys + 16 * (size_t)p;
-    uint8_t w[44][4];
-    aes_key_schedule(key, sbox, w, which == 0 ? tr : nullptr);
-    uint8_t *tail = tr + TR_CBC((size_t)nblocks);          // (CBC only)
+    const uint8_t *key = keys + TRK_KEY_BYTES(NK) * (size_t)p;
+    uint8_t w[TRK_KS_WORDS(NK)][4];
+    aes_key_schedule<NK>(key, sbox, w, which == 0 ? tr : nullptr);
+    uint8_t *tail = tr + TRK_CBC(NK, (size_t)nblocks);          // (CBC only)
     if (which == 0) {
-        for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
-        for (int i = 0; i < 44; i++) for (int k = 0; k < 4; k++) tr[TR_KS_W + 4 * i + k] = w[i][k];
+        aes_store_schedule<NK>(tr, key, w);
         if (CBC) for (int i = 0; i < 16; i++) tail[TR_CBC_IV + i] = ivs[16 * (size_t)p + i];
         return;
     }
     uint32_t b = which - 1;
-    uint8_t *bl = tr + TR_BLOCK0 + (size_t)b * TR_BLOCK_STRIDE;
+    uint8_t *bl = tr + TRK_BLOCK0(NK) + (size_t)b * TRK_BLOCK_STRIDE(NK);
     const uint8_t *msg = msgs + ((size_t)p * nblocks + b) * 16;
     uint8_t s[16];
     if (CBC) {
@@ -120,7 +142,7 @@ __global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const ui
         for (uint32_t j = 0; j < b; j++) {
             const uint8_t *mj = msgs + ((size_t)p * nblocks + j) * 16;
             for (int i = 0; i < 16; i++) s[i] = mj[i] ^ prev[i] ^ key[i];
-            aes_block_rounds<false>(s, w, sbox, nullptr);
+            aes_block_rounds<false, NK>(s, w, sbox, nullptr);
             for (int i = 0; i < 16; i++) prev[i] = s[i];
         }
         for (int i = 0; i < 16; i++) {
@@ -130,7 +152,7 @@ __global__ void k_aes_trace(uint8_t *__restrict__ trace, size_t stride, const ui
     } else {
         for (int i = 0; i < 16; i++) { bl[TR_BL_MSG + i] = msg[i]; s[i] = msg[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
     }
-    aes_block_rounds<true>(s, w, sbox, bl);
+    aes_block_rounds<true, NK>(s, w, sbox, bl);
 }
 
 // out = in + n mod 2^128 over 16 big-endian bytes
@@ -143,24 +165,24 @@ __device__ __forceinline__ void ctr_add(const uint8_t *__restrict__ in, uint32_t
 // K_b of CTR_{b-1} + 1 (trace_layout.h), runs the block's rounds from CTR_b ^ key and stores C_b = M_b ^ S_10.  Messages are packed at msg_len bytes per proof,
 // nblocks = ceil(msg_len / 16): the last block's lane reads only the bytes below msg_len and fills the rest of its message and C slots with zeros.  Blocks do not depend
 // on one another, so no lane walks a chain, and the kernel is handed the counter only, never a keystream made on the host.
+template <int NK = 4>
 __global__ void k_aes_trace_ctr(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ icbs,
                                 uint32_t nproofs, uint32_t nblocks, uint32_t msg_len, const uint8_t *__restrict__ sbox) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nproofs * (nblocks + 1)) return;
     uint32_t p = t / (nblocks + 1), which = t % (nblocks + 1);
     uint8_t *tr = trace + (size_t)p * stride;
-    const uint8_t *key = keys + 16 * (size_t)p, *icb = icbs + 16 * (size_t)p;
-    uint8_t w[44][4];
-    aes_key_schedule(key, sbox, w, which == 0 ? tr : nullptr);
-    uint8_t *tail = tr + TR_CTR((size_t)nblocks);
+    const uint8_t *key = keys + TRK_KEY_BYTES(NK) * (size_t)p, *icb = icbs + 16 * (size_t)p;
+    uint8_t w[TRK_KS_WORDS(NK)][4];
+    aes_key_schedule<NK>(key, sbox, w, which == 0 ? tr : nullptr);
+    uint8_t *tail = tr + TRK_CTR(NK, (size_t)nblocks);
     if (which == 0) {
-        for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
-        for (int i = 0; i < 44; i++) for (int k = 0; k < 4; k++) tr[TR_KS_W + 4 * i + k] = w[i][k];
+        aes_store_schedule<NK>(tr, key, w);
         for (int i = 0; i < 16; i++) tail[TR_CTR_ICB + i] = icb[i];
         return;
     }
     uint32_t b = which - 1;
-    uint8_t *bl = tr + TR_BLOCK0 + (size_t)b * TR_BLOCK_STRIDE, *slot = tail + TR_CTR_BLOCK0 + (size_t)b * TR_CTR_BLOCK_STRIDE;
+    uint8_t *bl = tr + TRK_BLOCK0(NK) + (size_t)b * TRK_BLOCK_STRIDE(NK), *slot = tail + TR_CTR_BLOCK0 + (size_t)b * TR_CTR_BLOCK_STRIDE;
     uint8_t ctr[16], carry[16], s[16], m[16];
     ctr_add(icb, b, ctr);
     for (int i = 0; i < 16; i++) carry[i] = 0;
@@ -173,7 +195,7 @@ __global__ void k_aes_trace_ctr(uint8_t *__restrict__ trace, size_t stride, cons
     const uint8_t *msg = msgs + (size_t)p * msg_len + 16 * (size_t)b;
     for (uint32_t i = 0; i < 16; i++) m[i] = i < have ? msg[i] : 0;
     for (int i = 0; i < 16; i++) { slot[TR_CTR_BL_CTR + i] = ctr[i]; slot[TR_CTR_BL_CARRY + i] = carry[i]; bl[TR_BL_MSG + i] = m[i]; s[i] = ctr[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
-    aes_block_rounds<true>(s, w, sbox, bl);
+    aes_block_rounds<true, NK>(s, w, sbox, bl);
     for (uint32_t i = 0; i < 16; i++) slot[TR_CTR_BL_CT + i] = i < have ? (uint8_t)(m[i] ^ s[i]) : 0;
 }
 
@@ -181,25 +203,25 @@ __global__ void k_aes_trace_ctr(uint8_t *__restrict__ trace, size_t stride, cons
 // proof's iv and its aad (zero-padded to whole blocks); lane (p, 1 + s) is AES slot s: the message blocks under iv || be32(s + 2) for s < nblocks, then H from the zero
 // block, then J_0 = iv || 00000001.  A message lane stores C_s = M_s ^ S_10 for the bytes that exist and zeros behind them.  Messages are packed at msg_len bytes per
 // proof, the public headers (iv, then aad) at 12 + aad_len bytes.  The kernel is handed key, iv, aad and message only.
+template <int NK = 4>
 __global__ void k_aes_trace_gcm(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ hdrs,
                                 uint32_t nproofs, uint32_t nblocks, uint32_t naad, uint32_t msg_len, uint32_t aad_len, const uint8_t *__restrict__ sbox) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nproofs * (nblocks + 3)) return;
     uint32_t p = t / (nblocks + 3), which = t % (nblocks + 3);
     uint8_t *tr = trace + (size_t)p * stride;
-    const uint8_t *key = keys + 16 * (size_t)p, *hdr = hdrs + (size_t)p * (12 + (size_t)aad_len);
-    uint8_t w[44][4];
-    aes_key_schedule(key, sbox, w, which == 0 ? tr : nullptr);
-    uint8_t *tail = tr + TR_GCM((size_t)nblocks);
+    const uint8_t *key = keys + TRK_KEY_BYTES(NK) * (size_t)p, *hdr = hdrs + (size_t)p * (12 + (size_t)aad_len);
+    uint8_t w[TRK_KS_WORDS(NK)][4];
+    aes_key_schedule<NK>(key, sbox, w, which == 0 ? tr : nullptr);
+    uint8_t *tail = tr + TRK_GCM(NK, (size_t)nblocks);
     if (which == 0) {
-        for (int i = 0; i < 16; i++) tr[TR_KEY + i] = key[i];
-        for (int i = 0; i < 44; i++) for (int k = 0; k < 4; k++) tr[TR_KS_W + 4 * i + k] = w[i][k];
+        aes_store_schedule<NK>(tr, key, w);
         for (int i = 0; i < 16; i++) tail[TR_GCM_IV + i] = i < 12 ? hdr[i] : 0;
         for (uint32_t i = 0; i < 16 * naad; i++) tail[TR_GCM_AAD + i] = i < aad_len ? hdr[12 + i] : 0;
         return;
     }
     uint32_t slot = which - 1;
-    uint8_t *bl = tr + TR_BLOCK0 + (size_t)slot * TR_BLOCK_STRIDE;
+    uint8_t *bl = tr + TRK_BLOCK0(NK) + (size_t)slot * TRK_BLOCK_STRIDE(NK);
     uint8_t in[16], s[16], m[16];
     uint32_t ctr = slot < nblocks ? slot + 2 : 1, have = 0;
     for (int i = 0; i < 16; i++) in[i] = slot == nblocks ? 0 : (i < 12 ? hdr[i] : (uint8_t)(ctr >> (8 * (15 - i))));
@@ -207,7 +229,7 @@ __global__ void k_aes_trace_gcm(uint8_t *__restrict__ trace, size_t stride, cons
     const uint8_t *msg = msgs + (size_t)p * msg_len + 16 * (size_t)(slot < nblocks ? slot : 0);      // (not read by the H and J_0 lanes: have = 0)
     for (uint32_t i = 0; i < 16; i++) m[i] = i < have ? msg[i] : 0;
     for (int i = 0; i < 16; i++) { bl[TR_BL_MSG + i] = m[i]; s[i] = in[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
-    aes_block_rounds<true>(s, w, sbox, bl);
+    aes_block_rounds<true, NK>(s, w, sbox, bl);
     if (slot < nblocks) for (uint32_t i = 0; i < 16; i++) tail[TR_GCM_CT(naad) + 16 * slot + i] = i < have ? (uint8_t)(m[i] ^ s[i]) : 0;
 }
 
@@ -229,18 +251,19 @@ __device__ __forceinline__ Gf128 gf_mul(const Gf128 &x, Gf128 v) {
     return z;
 }
 
-// GCM, the GHASH half, launched behind k_aes_trace_gcm on the same stream: it reads H = S_10 of slot nblocks, the aad, every C_b and S_10 of slot nblocks + 1 from the
+// GCM, the GHASH half, launched behind k_aes_trace_gcm on the same stream: it reads H = S_Nr of slot nblocks, the aad, every C_b and S_Nr of slot nblocks + 1 from the
 // trace.  nproofs * (n_mul + 1) * 16 lanes, n_mul = naad + nblocks + 1.  Lane (p, m, j), m < n_mul, recomputes the chain Y_0 .. Y_{m-1} in registers (two words of
 // state, 128 steps of shift and conditional xor per multiplication, no stores -- the way a CBC lane re-walks its chain), then stores byte j of X_m, byte column j of P_m
 // (128 contiguous bytes, eight 16-byte stores), the q bytes of output bits 8 j .. 8 j + 7 and byte j of Y_m; the lanes of the last multiplication add byte j of the tag.
 // Lane (p, n_mul, j) stores byte column j of the V table.  Every byte of the tail has exactly one writer; no LDS, no barrier, no cross-lane operation.
+template <int NK = 4>
 __global__ void k_ghash_trace(uint8_t *__restrict__ trace, size_t stride, uint32_t nproofs, uint32_t nblocks, uint32_t naad, uint32_t msg_len, uint32_t aad_len) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t n_mul = naad + nblocks + 1, per_proof = (n_mul + 1) * 16;
     if (t >= nproofs * per_proof) return;
     uint32_t p = t / per_proof, m = (t % per_proof) / 16, j = t % 16;
-    uint8_t *tr = trace + (size_t)p * stride, *tail = tr + TR_GCM((size_t)nblocks);
-    const Gf128 h = gf_load(tr + TR_BLOCK0 + (size_t)nblocks * TR_BLOCK_STRIDE + TR_BL_S + 160);
+    uint8_t *tr = trace + (size_t)p * stride, *tail = tr + TRK_GCM(NK, (size_t)nblocks);
+    const Gf128 h = gf_load(tr + TRK_BLOCK0(NK) + (size_t)nblocks * TRK_BLOCK_STRIDE(NK) + TRK_BL_CT(NK));
     Gf128 v = h;
     if (m == n_mul) {
         uint8_t *col = tail + TR_GCM_V(naad, nblocks) + 128 * j;
@@ -279,58 +302,79 @@ __global__ void k_ghash_trace(uint8_t *__restrict__ trace, size_t stride, uint32
         y |= (uint8_t)((cnt[bit] & 1u) << bit);
     }
     mul[TR_GCM_MUL_Y + j] = y;
-    if (m + 1 == n_mul) tail[TR_GCM_TAG(naad, nblocks) + j] = y ^ tr[TR_BLOCK0 + (size_t)(nblocks + 1) * TR_BLOCK_STRIDE + TR_BL_S + 160 + j];
+    if (m + 1 == n_mul) tail[TR_GCM_TAG(naad, nblocks) + j] = y ^ tr[TRK_BLOCK0(NK) + (size_t)(nblocks + 1) * TRK_BLOCK_STRIDE(NK) + TRK_BL_CT(NK) + j];
 }
 template <bool CBC>
-static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s) {
+static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, size_t key_bytes, stream_t s) {
+    // the stride must hold the trace of THIS key size: a caller that sized its buffer for another one gets an error here, never lanes that store past a trace
+    const int nk = trace_nk(who, key_bytes);
+    const size_t need = CBC ? trace_bytes_of(nk, TRK_CBC_BYTES(4, (size_t)nblocks), TRK_CBC_BYTES(6, (size_t)nblocks), TRK_CBC_BYTES(8, (size_t)nblocks))
+                            : trace_bytes_of(nk, TRK_ECB_BYTES(4, (size_t)nblocks), TRK_ECB_BYTES(6, (size_t)nblocks), TRK_ECB_BYTES(8, (size_t)nblocks));
+    if (stride < need) throw GpuError(std::string(who) + ": trace stride " + std::to_string(stride) + " is short of the " + std::to_string(need) + " bytes a " + std::to_string(8 * key_bytes) + "-bit key's trace takes");
     uint8_t *g_sbox = sbox_here();
     if (!g_sbox) throw GpuError(std::string(who) + ": S-box table not uploaded on this device");
     uint32_t lanes = nproofs * (nblocks + 1);
-    hipLaunchKernelGGL(k_aes_trace<CBC>, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, ivs, nproofs, nblocks, g_sbox);
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL((k_aes_trace<CBC, 4>), grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, ivs, nproofs, nblocks, g_sbox);
+    else if (nk == 6) hipLaunchKernelGGL((k_aes_trace<CBC, 6>), grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, ivs, nproofs, nblocks, g_sbox);
+    else hipLaunchKernelGGL((k_aes_trace<CBC, 8>), grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, ivs, nproofs, nblocks, g_sbox);
     HIP_LAUNCH_CHECK();
 }
-void aes_trace(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, uint32_t nproofs, uint32_t nblocks, stream_t s) {
-    launch_aes_trace<false>("aes_trace", trace, stride, msgs, keys, nullptr, nproofs, nblocks, s);
+void aes_trace(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, uint32_t nproofs, uint32_t nblocks, stream_t s, size_t key_bytes) {
+    launch_aes_trace<false>("aes_trace", trace, stride, msgs, keys, nullptr, nproofs, nblocks, key_bytes, s);
 }
-void aes_trace_cbc(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s) {
+void aes_trace_cbc(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, stream_t s, size_t key_bytes) {
     if (!ivs) throw GpuError("aes_trace_cbc: no IV buffer");
-    if (stride < TR_CBC((size_t)nblocks) + TR_CBC_X + 16 * (size_t)nblocks) throw GpuError("aes_trace_cbc: trace stride is short of the CBC tail");
-    launch_aes_trace<true>("aes_trace_cbc", trace, stride, msgs, keys, ivs, nproofs, nblocks, s);
+    launch_aes_trace<true>("aes_trace_cbc", trace, stride, msgs, keys, ivs, nproofs, nblocks, key_bytes, s);
 }
-void aes_trace_ctr(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *icbs, uint32_t nproofs, uint32_t msg_len, stream_t s) {
+void aes_trace_ctr(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *icbs, uint32_t nproofs, uint32_t msg_len, stream_t s, size_t key_bytes) {
     if (!icbs) throw GpuError("aes_trace_ctr: no counter buffer");
     if (msg_len == 0 || msg_len > 0xfffffff0u) throw GpuError("aes_trace_ctr: the message length must be 1 .. 2^32 - 16 bytes");
+    const int nk = trace_nk("aes_trace_ctr", key_bytes);
     uint32_t nblocks = (msg_len + 15) / 16;
-    if (stride < TR_CTR_BYTES((size_t)nblocks)) throw GpuError("aes_trace_ctr: trace stride is short of the CTR tail");
+    if (stride < trace_bytes_of(nk, TRK_CTR_BYTES(4, (size_t)nblocks), TRK_CTR_BYTES(6, (size_t)nblocks), TRK_CTR_BYTES(8, (size_t)nblocks))) throw GpuError("aes_trace_ctr: trace stride is short of the CTR tail");
     uint8_t *g_sbox = sbox_here();
     if (!g_sbox) throw GpuError("aes_trace_ctr: S-box table not uploaded on this device");
     uint32_t lanes = nproofs * (nblocks + 1);
-    hipLaunchKernelGGL(k_aes_trace_ctr, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, icbs, nproofs, nblocks, msg_len, g_sbox);
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL(k_aes_trace_ctr<4>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, icbs, nproofs, nblocks, msg_len, g_sbox);
+    else if (nk == 6) hipLaunchKernelGGL(k_aes_trace_ctr<6>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, icbs, nproofs, nblocks, msg_len, g_sbox);
+    else hipLaunchKernelGGL(k_aes_trace_ctr<8>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, icbs, nproofs, nblocks, msg_len, g_sbox);
     HIP_LAUNCH_CHECK();
 }
-// what both GCM entries check: the lengths, and the stride against the tail's size (the GHASH lanes store 16 bytes at a time, so traces are 16-byte aligned)
-static void gcm_shape(const char *who, const uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, uint32_t &nblocks, uint32_t &naad) {
+// what both GCM entries check: the key size, the lengths, and the stride against the trace's size for that key size (the GHASH lanes store 16 bytes at a time, so traces
+// are 16-byte aligned)
+static int gcm_shape(const char *who, const uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, size_t key_bytes, uint32_t &nblocks, uint32_t &naad) {
+    const int nk = trace_nk(who, key_bytes);
     if (msg_len == 0 || msg_len > (1u << 16) || aad_len > (1u << 16)) throw GpuError(std::string(who) + ": the message must have 1 .. 65536 bytes, the aad at most 65536");
     nblocks = (msg_len + 15) / 16; naad = (aad_len + 15) / 16;
-    if (stride < TR_GCM_BYTES((size_t)naad, (size_t)nblocks)) throw GpuError(std::string(who) + ": trace stride is short of the GCM tail");
+    const size_t na = naad, nb = nblocks;
+    if (stride < trace_bytes_of(nk, TRK_GCM_BYTES(4, na, nb), TRK_GCM_BYTES(6, na, nb), TRK_GCM_BYTES(8, na, nb))) throw GpuError(std::string(who) + ": trace stride is short of the GCM tail");
     if (stride % 16 || (uintptr_t)trace % 16) throw GpuError(std::string(who) + ": traces must be 16-byte aligned");
     if (nproofs == 0 || nproofs > (1u << 20)) throw GpuError(std::string(who) + ": 1 .. 2^20 proofs per launch");
+    return nk;
 }
-void aes_trace_gcm(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s) {
+void aes_trace_gcm(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes) {
     if (!hdrs) throw GpuError("aes_trace_gcm: no iv / aad buffer");
     uint32_t nblocks, naad;
-    gcm_shape("aes_trace_gcm", trace, stride, nproofs, msg_len, aad_len, nblocks, naad);
+    const int nk = gcm_shape("aes_trace_gcm", trace, stride, nproofs, msg_len, aad_len, key_bytes, nblocks, naad);
     uint8_t *g_sbox = sbox_here();
     if (!g_sbox) throw GpuError("aes_trace_gcm: S-box table not uploaded on this device");
     uint32_t lanes = nproofs * (nblocks + 3);
-    hipLaunchKernelGGL(k_aes_trace_gcm, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, nblocks, naad, msg_len, aad_len, g_sbox);
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL(k_aes_trace_gcm<4>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, nblocks, naad, msg_len, aad_len, g_sbox);
+    else if (nk == 6) hipLaunchKernelGGL(k_aes_trace_gcm<6>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, nblocks, naad, msg_len, aad_len, g_sbox);
+    else hipLaunchKernelGGL(k_aes_trace_gcm<8>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, nblocks, naad, msg_len, aad_len, g_sbox);
     HIP_LAUNCH_CHECK();
 }
-void ghash_trace(uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s) {
+void ghash_trace(uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes) {
     uint32_t nblocks, naad;
-    gcm_shape("ghash_trace", trace, stride, nproofs, msg_len, aad_len, nblocks, naad);
+    const int nk = gcm_shape("ghash_trace", trace, stride, nproofs, msg_len, aad_len, key_bytes, nblocks, naad);
     uint32_t lanes = nproofs * (naad + nblocks + 2) * 16;
-    hipLaunchKernelGGL(k_ghash_trace, dim3((lanes + 63) / 64), dim3(64), 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL(k_ghash_trace<4>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
+    else if (nk == 6) hipLaunchKernelGGL(k_ghash_trace<6>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
+    else hipLaunchKernelGGL(k_ghash_trace<8>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
     HIP_LAUNCH_CHECK();
 }
 

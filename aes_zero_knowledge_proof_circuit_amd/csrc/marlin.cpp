@@ -328,7 +328,7 @@ class ProvingKeyImpl {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
         cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
-        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(16); cx.d_iv.alloc(std::max<size_t>(16, 12 + c.aad_bytes));
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, 12 + c.aad_bytes));
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
@@ -486,7 +486,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -495,14 +495,14 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
     message_len = message_len_;
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
-    circuit = compile_circuit(kind, message_len, aad_len);
+    circuit = compile_circuit(kind, message_len, aad_len, key_bits);
     const Circuit &c = circuit;
     // ---- joint matrix (sum_matrices): per-row sorted union of the A, B, C column supports
     size_t rows = c.num_constraints;
@@ -653,25 +653,25 @@ Fr ProvingKeyImpl::sample_outside_h(FiatShamirRng &fs) const { Fr t; do { t = fs
 void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv) {
     const Circuit &c = circuit;
     gpu::stream_t s = cx.stream;
-    gpu::h2d(cx.d_msg, msg, len, s); gpu::h2d(cx.d_key, key, 16, s);
+    gpu::h2d(cx.d_msg, msg, len, s); gpu::h2d(cx.d_key, key, c.key_bytes, s);
     if (c.kind == CIRCUIT_AES_CBC) {
         if (!iv) throw std::invalid_argument("a CBC proving key needs an IV");
         gpu::h2d(cx.d_iv, iv, 16, s);
-        gpu::aes_trace_cbc(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.n_blocks, s);
+        gpu::aes_trace_cbc(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.n_blocks, s, c.key_bytes);
     } else if (c.kind == CIRCUIT_AES_CTR) {
         if (!iv) throw std::invalid_argument("a CTR proving key needs an initial counter block");
         if (len != c.message_bytes) throw std::invalid_argument("a CTR trace takes exactly the key's message length");
         gpu::h2d(cx.d_iv, iv, 16, s);
-        gpu::aes_trace_ctr(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, s);
+        gpu::aes_trace_ctr(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, s, c.key_bytes);
     } else if (c.kind == CIRCUIT_AES_GCM) {
         // iv = the proof's public header, 12 iv bytes then the key's A aad bytes.  The GHASH kernel reads H and every C_b from the trace the AES kernel has just written
         if (!iv) throw std::invalid_argument("a GCM proving key needs an iv and the aad");
         if (len != c.message_bytes) throw std::invalid_argument("a GCM trace takes exactly the key's message length");
         gpu::h2d(cx.d_iv, iv, 12 + c.aad_bytes, s);
-        gpu::aes_trace_gcm(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s);
-        gpu::ghash_trace(cx.d_trace, c.trace_bytes, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s);
+        gpu::aes_trace_gcm(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
+        gpu::ghash_trace(cx.d_trace, c.trace_bytes, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
     } else {
-        gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s);
+        gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s, c.key_bytes);
     }
 }
 
@@ -1066,7 +1066,7 @@ Proof ProvingKey::prove_aes_cbc(const uint8_t *message, size_t len, const uint8_
     require_cbc_key(impl->circuit, len);
     if (!message || !key || !iv) throw std::invalid_argument("null argument");
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
-    if (ciphertext_or_null) aes128_cbc_encrypt_host(message, len, key, iv, ciphertext_or_null);
+    if (ciphertext_or_null) aes128_cbc_encrypt_host(message, len, key, iv, ciphertext_or_null, impl->circuit.key_bytes);
     return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, iv);
 }
 // ---- AES-128-CTR.  The statement, the input layout, the incrementer and why chunk-proofs are seekable: DESIGN.md "CTR".
@@ -1084,7 +1084,7 @@ Proof ProvingKey::prove_aes_ctr(const uint8_t *message, size_t len, const uint8_
     const Circuit &c = impl->circuit;
     require_ctr_key(c, message, key, icb);
     if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
-    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null);
+    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null, c.key_bytes);
     return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, icb);
 }
 // zero-knowledge randomness of proof i of a chunked / batch call: the caller's seed is domain-separated per proof, Blake2s(seed || (offset + i) as u64 LE),
@@ -1147,7 +1147,7 @@ std::vector<Proof> ProvingKey::prove_aes_chunked(const uint8_t *message, size_t 
 std::vector<Proof> ProvingKey::prove_aes_batch(const uint8_t *messages, const uint8_t *keys, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
     if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
     if (impl->circuit.n_blocks == 0) throw std::invalid_argument("proving key has an empty plaintext");
-    return prove_many(impl, messages, keys, 16, n, n_contexts, zk_seed, index_offset, nullptr);
+    return prove_many(impl, messages, keys, impl->circuit.key_bytes, n, n_contexts, zk_seed, index_offset, nullptr);
 }
 std::vector<Proof> ProvingKey::prove_aes_cbc_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
                                                      uint8_t *ciphertext_or_null) {
@@ -1157,7 +1157,7 @@ std::vector<Proof> ProvingKey::prove_aes_cbc_chunked(const uint8_t *message, siz
     if (len % chunk) throw std::invalid_argument("message length must be a multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
     // the whole chain once on the host (plain AES: milliseconds); every chaining value is public, so the chunk-proofs below are independent and run side by side
     std::vector<uint8_t> ct(len);
-    aes128_cbc_encrypt_host(message, len, key, iv, ct.data());
+    aes128_cbc_encrypt_host(message, len, key, iv, ct.data(), impl->circuit.key_bytes);
     size_t n_chunks = len / chunk;
     std::vector<uint8_t> ivs(16 * n_chunks);
     for (size_t j = 0; j < n_chunks; j++) memcpy(&ivs[16 * j], j ? &ct[chunk * j - 16] : iv, 16);
@@ -1177,7 +1177,7 @@ std::vector<Proof> ProvingKey::prove_aes_ctr_chunked(const uint8_t *message, siz
     std::vector<uint8_t> icbs(16 * n_chunks);
     for (size_t j = 0; j < n_chunks; j++) ctr_counter_add(icb, (uint64_t)j * c.n_blocks, &icbs[16 * j]);
     std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, icbs.data());
-    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null);
+    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null, c.key_bytes);
     return proofs;
 }
 // ---- AES-128-GCM.  The statement, the input layout, the GHASH gadget and why a long message is a batch of records, not chunk-proofs: DESIGN.md "GCM".
@@ -1202,7 +1202,7 @@ Proof ProvingKey::prove_aes_gcm(const uint8_t *message, size_t len, const uint8_
     if (ciphertext_or_null || tag_or_null) {
         std::vector<uint8_t> ct(len);
         uint8_t tag[16];
-        aes128_gcm_encrypt_host(message, len, key, iv, aad, aad_len, ct.data(), tag);
+        aes128_gcm_encrypt_host(message, len, key, iv, aad, aad_len, ct.data(), tag, impl->circuit.key_bytes);
         if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
         if (tag_or_null) memcpy(tag_or_null, tag, 16);
     }
@@ -1218,12 +1218,12 @@ std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, cons
         std::vector<uint8_t> ct(c.message_bytes);
         uint8_t tag[16];
         for (size_t i = 0; i < n; i++) {
-            aes128_gcm_encrypt_host(messages + i * c.message_bytes, c.message_bytes, keys + 16 * i, headers + hs * i, headers + hs * i + 12, c.aad_bytes, ct.data(), tag);
+            aes128_gcm_encrypt_host(messages + i * c.message_bytes, c.message_bytes, keys + c.key_bytes * i, headers + hs * i, headers + hs * i + 12, c.aad_bytes, ct.data(), tag, c.key_bytes);
             if (ciphertexts_or_null) memcpy(ciphertexts_or_null + i * c.message_bytes, ct.data(), c.message_bytes);
             if (tags_or_null) memcpy(tags_or_null + 16 * i, tag, 16);
         }
     }
-    return prove_many(impl, messages, keys, 16, n, n_contexts, zk_seed, index_offset, headers, hs);
+    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, hs);
 }
 Proof ProvingKey::prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed) {
     if (impl->circuit.kind != CIRCUIT_OPS_XOR && impl->circuit.kind != CIRCUIT_OPS_ADD) throw std::invalid_argument("proving key was synthesized for an AES circuit");
@@ -1338,10 +1338,12 @@ std::vector<uint8_t> ProvingKey::debug_fetch(const std::string &name) const {
     throw std::invalid_argument("debug_fetch: unknown buffer " + name);
 }
 
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len) {
+size_t ProvingKey::key_bytes() const { return impl->circuit.key_bytes; }
+
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len);
+    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits);
     return pk;
 }
 

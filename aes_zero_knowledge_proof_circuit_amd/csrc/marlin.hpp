@@ -62,6 +62,9 @@ class ProvingKey {
     ~ProvingKey();
     const VerifyingKey &vk() const;
     const Circuit &circuit() const;
+    // the byte length of the AES key this proving key was synthesized for: 16, 24 or 32.  EVERY `key` argument below -- written key[16] from when 16 was the only size --
+    // points to key_bytes() bytes, and the batch calls take n x key_bytes() key bytes
+    size_t key_bytes() const;
     // encrypt(): message length must equal the length the key was synthesized for; zk_seed = 32-byte StdRng seed or nullptr for
     // ark_std::test_rng()'s (what simpleworks::marlin::generate_rand() returns)
     Proof prove_aes(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t *zk_seed);
@@ -70,7 +73,7 @@ class ProvingKey {
     // split one job over several calls / ranks pass the job-global index of their first proof and reuse one seed.  nullptr = the reference's fixed
     // test_rng seed for every proof (byte-parity mode for tests; NOT zero-knowledge across proofs)
     std::vector<Proof> prove_aes_chunked(const uint8_t *message, size_t len, const uint8_t key[16], size_t n_contexts, const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0);
-    // n independent (message_i, key_i) pairs, each message of the key's plaintext length; keys = n x 16 bytes
+    // n independent (message_i, key_i) pairs, each message of the key's plaintext length; keys = n x key_bytes() bytes
     std::vector<Proof> prove_aes_batch(const uint8_t *messages, const uint8_t *keys, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0);
     Proof prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed);
     // ---- AES-128-CBC (keys of kind CIRCUIT_AES_CBC only; the calls above refuse such a key).  Public input: iv, ciphertext.
@@ -94,7 +97,7 @@ class ProvingKey {
     // ciphertext_or_null (len bytes) and tag_or_null (16) receive the host's GCM encryption; the device is handed key, iv, aad and message only
     Proof prove_aes_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *zk_seed,
                         uint8_t *ciphertext_or_null = nullptr, uint8_t *tag_or_null = nullptr);
-    // n independent records over one key: messages = n x L bytes, keys = n x 16, headers = n x (12 + A) bytes (each record's iv, then its aad), all contexts side by side.
+    // n independent records over one key: messages = n x L bytes, keys = n x key_bytes(), headers = n x (12 + A) bytes (each record's iv, then its aad), all contexts side by side.
     // Seeds as prove_aes_chunked.  ciphertexts_or_null = n x L bytes, tags_or_null = n x 16
     std::vector<Proof> prove_aes_gcm_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
                                            uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr);
@@ -131,7 +134,7 @@ class ProvingKey {
 // multi-proof calls then run 15 per-window-bucket windows instead of 13 table windows (~9 % fewer blocks/s), and the key fits a GPU that is short of memory.
 // Without the flag the tables are built when memory allows (hipMemGetInfo) and silently skipped otherwise.
 enum : unsigned { KEY_NO_TABLES = 1u };
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0);      // (aad_len: GCM keys only)
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, the AES kinds only)
 // hold = true: every universal / Lagrange SRS built (or alive) from now on stays resident after its last key is freed; false: back to "freed with the last key"
 void srs_hold(bool hold);
 // process default of ProvingKey::contexts(): ZKAES_CONTEXTS from the environment (read once), else ZKAES_DEFAULT_CONTEXTS

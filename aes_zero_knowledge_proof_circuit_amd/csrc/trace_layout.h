@@ -76,6 +76,49 @@
 #define TR_SBOX_PER_BLOCK 160
 #define TR_SBOX_KS 40
 
+// ---- the same layout for every key size, nk = the key length in 32-bit words (4, 6, 8 for AES-128, -192, -256); Nr = nk + 6 rounds, 4 (Nr + 1) schedule words
+// (FIPS-197 5.2).  The order of the parts is the one above; what moves is where each begins:
+//   key (4 nk) | W_0 .. W_{4 Nr + 3} | SubWord bytes, 4 per instance | the word ahead of the Rcon xor, 4 per instance | blocks | the mode's tail
+// A SubWord instance is every schedule index i >= nk with i % nk == 0 (SubWord(RotWord(W_{i-1})), then the Rcon xor) and, for nk = 8, also every i with i % 8 == 4
+// (SubWord(W_{i-1}): no rotation and no Rcon, so that instance's "pre" word is W_i itself): 10, 8, 13 instances, numbered in the order of i (TRK_KS_INST_OF).
+// A block slot is the message (16), S_0 .. S_Nr, SB_1 .. SB_Nr, XT_1 .. XT_{Nr-1}, MP_1 .. MP_{Nr-1}: 16 + 16 (Nr + 1) + 16 Nr + 16 (Nr - 1) + 64 (Nr - 1) = 112 Nr - 48 bytes.
+// The CBC, CTR and GCM tails keep their inner layout (the TR_CBC_*, TR_CTR_*, TR_GCM_* offsets above) behind the blocks of the chosen stride; the GCM tail begins at the
+// next multiple of 16 (at nk = 4 the blocks end on one).
+#define TRK_NR(nk) ((nk) + 6)
+#define TRK_KS_WORDS(nk) (4 * (TRK_NR(nk) + 1))
+#define TRK_KEY_BYTES(nk) (4 * (nk))
+#define TRK_KS_INST(nk) ((nk) == 8 ? 13 : (nk) == 6 ? 8 : 10)
+#define TRK_KS_W(nk) TRK_KEY_BYTES(nk)
+#define TRK_KS_SUB(nk) (TRK_KS_W(nk) + 4 * TRK_KS_WORDS(nk))
+#define TRK_KS_PRE(nk) (TRK_KS_SUB(nk) + 4 * TRK_KS_INST(nk))
+#define TRK_BLOCK0(nk) (TRK_KS_PRE(nk) + 4 * TRK_KS_INST(nk))
+#define TRK_BLOCK_STRIDE(nk) (112 * TRK_NR(nk) - 48)
+#define TRK_BL_S(nk) 16
+#define TRK_BL_SB(nk) (TRK_BL_S(nk) + 16 * (TRK_NR(nk) + 1))
+#define TRK_BL_XT(nk) (TRK_BL_SB(nk) + 16 * TRK_NR(nk))
+#define TRK_BL_MP(nk) (TRK_BL_XT(nk) + 16 * (TRK_NR(nk) - 1))
+#define TRK_BL_CT(nk) (TRK_BL_S(nk) + 16 * TRK_NR(nk))                 // S_Nr, the block's ciphertext, inside its slot
+// the instance number of schedule index i (only for an i that is one): i / nk - 1, and for nk = 8 the i % 8 == 4 instances interleave
+#define TRK_KS_INST_OF(nk, i) ((nk) == 8 ? (i) / 4 - 2 : (i) / (nk) - 1)
+#define TRK_ECB_BYTES(nk, nb) (TRK_BLOCK0(nk) + (nb) * TRK_BLOCK_STRIDE(nk))
+#define TRK_CBC(nk, nb) TRK_ECB_BYTES(nk, nb)
+#define TRK_CBC_BYTES(nk, nb) (TRK_CBC(nk, nb) + TR_CBC_X + 16 * (nb))
+#define TRK_CTR(nk, nb) TRK_CBC(nk, nb)
+#define TRK_CTR_BYTES(nk, nb) (TRK_CTR(nk, nb) + TR_CTR_BLOCK0 + (nb) * TR_CTR_BLOCK_STRIDE)
+#define TRK_GCM(nk, nb) ((TRK_CBC(nk, (nb) + 2) + 15) / 16 * 16)             // (the GHASH lanes store 16 bytes at a time: the blocks begin at 296 and 376 for nk = 6, 8, so 8 bytes of padding)
+#define TRK_GCM_BYTES(nk, na, nb) (TRK_GCM(nk, nb) + TR_GCM_TAG(na, nb) + 16)
+#define TRK_SBOX_PER_BLOCK(nk) (16 * TRK_NR(nk))
+#define TRK_SBOX_KS(nk) (4 * TRK_KS_INST(nk))
+// at nk = 4 every parametrised macro is the constant above: an AES-128 trace is byte for byte what it was
+static_assert(TRK_KS_W(4) == TR_KS_W && TRK_KS_SUB(4) == TR_KS_SUB && TRK_KS_PRE(4) == TR_KS_PRE && TRK_BLOCK0(4) == TR_BLOCK0, "AES-128 key-schedule layout moved");
+static_assert(TRK_BLOCK_STRIDE(4) == TR_BLOCK_STRIDE && TRK_BL_S(4) == TR_BL_S && TRK_BL_SB(4) == TR_BL_SB && TRK_BL_XT(4) == TR_BL_XT && TRK_BL_MP(4) == TR_BL_MP, "AES-128 block slot moved");
+static_assert(TRK_BL_CT(4) == TR_BL_S + 160 && TRK_BL_MP(4) + 64 * (TRK_NR(4) - 1) == TR_BLOCK_STRIDE, "AES-128 block slot moved");
+static_assert(TRK_CBC(4, 3) == TR_CBC(3) && TRK_CTR_BYTES(4, 3) == TR_CTR_BYTES(3) && TRK_GCM(4, 3) == TR_GCM(3) && TRK_GCM_BYTES(4, 2, 3) == TR_GCM_BYTES(2, 3), "AES-128 mode tails moved");
+static_assert(TRK_SBOX_PER_BLOCK(4) == TR_SBOX_PER_BLOCK && TRK_SBOX_KS(4) == TR_SBOX_KS && TRK_KS_WORDS(4) == 44 && TRK_KS_INST_OF(4, 40) == 9, "AES-128 counts moved");
+static_assert(TRK_BLOCK_STRIDE(6) == 1296 && TRK_BLOCK_STRIDE(8) == 1520 && TRK_KS_WORDS(6) == 52 && TRK_KS_WORDS(8) == 60, "block strides of AES-192 / -256");
+static_assert(TRK_KS_INST_OF(6, 48) == 7 && TRK_KS_INST_OF(8, 8) == 0 && TRK_KS_INST_OF(8, 12) == 1 && TRK_KS_INST_OF(8, 56) == 12, "SubWord instance numbering");
+static_assert(TRK_GCM(6, 1) % 16 == 0 && TRK_GCM(8, 1) % 16 == 0 && TRK_GCM(6, 1) == TRK_CBC(6, 3) + 8 && TRK_GCM(8, 2) == TRK_CBC(8, 4) + 8 && TRK_GCM_BYTES(6, 1, 2) % 16 == 0, "the GCM tail must stay 16-byte aligned");
+
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30
 #define WD_BYTEBIT 0u   // [29:4] trace offset, [3:1] bit, [0] neg

@@ -217,6 +217,35 @@ int zkaes_verify_encryption_gcm(const zkaes_vk *vk, const uint8_t *proof, size_t
 /* host only: zkaes_circuit_info / zkaes_circuit_matrix of the GCM circuit for (plaintext_length, aad_length) */
 int zkaes_circuit_info_gcm(size_t plaintext_length, size_t aad_length, uint64_t out[12]);
 int zkaes_circuit_matrix_gcm(size_t plaintext_length, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+/* ---- AES-192 and AES-256 ---------------------------------------------------------------------------------------------
+ * Every mode above exists for the three key sizes of FIPS-197: key_bits = 128 (what every synthesizer above makes), 192 or 256.  The statement of a mode, its public-input
+ * vector and its verifier do not change: the key size only changes the private key's length (key_bits / 8 bytes), the round count (10, 12, 14) and the key schedule inside
+ * the circuit.
+ * A proving key remembers its key size (zkaes_pk_key_bytes: 16, 24 or 32).  No existing function changes signature: `secret_key[16]` is a plain pointer in C, and EVERY
+ * proving and witness entry point above reads zkaes_pk_key_bytes(pk) bytes from it -- 16 for every key made by zkaes_synthesize_keys, _ex, _ex2 and _gcm.  The checked
+ * batch calls (zkaes_encrypt_batch_seeded*, zkaes_encrypt_gcm_batch_seeded_at) require secret_keys_len == n x zkaes_pk_key_bytes(pk); zkaes_encrypt_batch reads that many.
+ * The verify functions are unchanged.  A verifying key carries no key size, just as it carries no mode (see the remark under AES-128-CTR): the public input of an AES-256
+ * statement has the shape of the AES-128 one for the same lengths, and it is the key that names the relation a proof is checked against.  A proof made under a key of one
+ * size does not verify under the key of another; a verifier keeps the keys of different key sizes apart as it does those of different modes. */
+/* as zkaes_synthesize_keys_ex2 / _gcm with the key size: key_bits = 128, 192 or 256, anything else is an error; an ops kind takes 128 only; aad_length != 0 outside
+ * ZKAES_CIRCUIT_AES_GCM is an error */
+int zkaes_synthesize_keys_ks(int circuit_kind, unsigned key_bits, size_t plaintext_length, size_t aad_length, size_t srs_num_constraints, size_t srs_num_variables,
+                             size_t srs_num_non_zero, unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* *n = the byte length of the AES key this proving key takes: 16, 24 or 32 (16 for the ops kinds, which take none) */
+int zkaes_pk_key_bytes(const zkaes_pk *pk, size_t *n);
+/* host only: zkaes_circuit_info / zkaes_circuit_matrix for any kind, key size and (for GCM) aad length; the same refusals as zkaes_synthesize_keys_ks */
+int zkaes_circuit_info_ks(int circuit_kind, unsigned key_bits, size_t plaintext_length, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_ks(int circuit_kind, unsigned key_bits, size_t plaintext_length, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr,
+                            uint32_t *col, int64_t *coeff);
+/* host only, no GPU: the ciphers above with the key's byte length, key_len = 16, 24 or 32 (anything else is an error).  zkaes_ecb_ciphertext_ks and _cbc_ take whole
+ * blocks (a non-zero multiple of 16 bytes), _ctr_ any length >= 1, the GCM pair any length >= 0, as their AES-128 namesakes */
+int zkaes_ecb_ciphertext_ks(const uint8_t *message, size_t message_len, const uint8_t *secret_key, size_t key_len, uint8_t *ciphertext);
+int zkaes_cbc_ciphertext_ks(const uint8_t *message, size_t message_len, const uint8_t *secret_key, size_t key_len, const uint8_t iv[16], uint8_t *ciphertext);
+int zkaes_ctr_crypt_ks(const uint8_t *in, size_t len, const uint8_t *secret_key, size_t key_len, const uint8_t icb[16], uint8_t *out);
+int zkaes_gcm_encrypt_ks(const uint8_t *message, size_t message_len, const uint8_t *secret_key, size_t key_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                         uint8_t *ciphertext, uint8_t tag16[16]);
+int zkaes_gcm_decrypt_ks(const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t *secret_key, size_t key_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                         const uint8_t tag16[16], uint8_t *message, int *ok);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

@@ -80,6 +80,20 @@ extern "C" {
                              z_cap: usize, z_len: *mut usize) -> c_int;
     fn zkaes_verify_encryption_gcm(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
                                    ciphertext_len: usize, tag16: *const u8, accepted: *mut c_int) -> c_int;
+    // AES-192 / AES-256 (include/zkaes.h, section "AES-192 and AES-256"; these declarations and the wrappers at the end of the file were not compiled: no cargo in the build image)
+    fn zkaes_synthesize_keys_ks(circuit_kind: c_int, key_bits: c_uint, plaintext_length: usize, aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize,
+                                srs_num_non_zero: usize, flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_pk_key_bytes(pk: *const zkaes_pk, n: *mut usize) -> c_int;
+    fn zkaes_circuit_info_ks(circuit_kind: c_int, key_bits: c_uint, plaintext_length: usize, aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_ks(circuit_kind: c_int, key_bits: c_uint, plaintext_length: usize, aad_length: usize, which: c_int, n_rows: *mut u64, nnz: *mut u64, rowptr: *mut u32,
+                               col: *mut u32, coeff: *mut i64) -> c_int;
+    fn zkaes_ecb_ciphertext_ks(message: *const u8, message_len: usize, secret_key: *const u8, key_len: usize, ciphertext: *mut u8) -> c_int;
+    fn zkaes_cbc_ciphertext_ks(message: *const u8, message_len: usize, secret_key: *const u8, key_len: usize, iv: *const u8, ciphertext: *mut u8) -> c_int;
+    fn zkaes_ctr_crypt_ks(input: *const u8, len: usize, secret_key: *const u8, key_len: usize, icb: *const u8, out: *mut u8) -> c_int;
+    fn zkaes_gcm_encrypt_ks(message: *const u8, message_len: usize, secret_key: *const u8, key_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *mut u8,
+                            tag16: *mut u8) -> c_int;
+    fn zkaes_gcm_decrypt_ks(ciphertext: *const u8, ciphertext_len: usize, secret_key: *const u8, key_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, tag16: *const u8,
+                            message: *mut u8, ok: *mut c_int) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
@@ -511,4 +525,52 @@ pub fn verify_encryption_gcm(verifying_key: &VerifyingKey, proof: &[u8], iv: &[u
         return Err(last_error());
     }
     Ok(accepted != 0)
+}
+
+
+// ---- AES-192 / AES-256 (include/zkaes.h "AES-192 and AES-256").  NOT COMPILED: no cargo in the build image.
+// The wrappers above take `secret_key: &[u8; 16]` and stay as they are for AES-128 keys.  The library reads key_bytes(pk) bytes from the pointer, so a caller with a
+// 24- or 32-byte key goes through a key from synthesize_keys_ks and passes a slice of exactly proving_key.key_bytes() bytes to the `_ks` wrappers below (ECB shown; the
+// other modes follow the same pattern over the same C entry points).
+/// key_bits = 128, 192 or 256; aad_len must be 0 outside CIRCUIT_AES_GCM
+pub fn synthesize_keys_ks(circuit_kind: c_int, key_bits: u32, len: usize, aad_len: usize, flags: u32) -> Result<(ProvingKey, VerifyingKey)> {
+    let (mut pk, mut vk) = (std::ptr::null_mut(), std::ptr::null_mut());
+    if unsafe { zkaes_synthesize_keys_ks(circuit_kind, key_bits as c_uint, len, aad_len, 866_944, 513, 4_062_064, flags as c_uint, &mut pk, &mut vk) } != 0 { return Err(last_error()); }
+    Ok((ProvingKey(Arc::new(PkHandle(pk))), VerifyingKey(Arc::new(VkHandle(vk)))))
+}
+
+impl ProvingKey {
+    /// the byte length of the AES key this proving key takes: 16, 24 or 32
+    pub fn key_bytes(&self) -> Result<usize> {
+        let mut n = 0usize;
+        if unsafe { zkaes_pk_key_bytes((self.0).0, &mut n) } != 0 { return Err(last_error()); }
+        Ok(n)
+    }
+}
+
+/// `encrypt` for a key of any size: secret_key.len() must be proving_key.key_bytes()
+pub fn encrypt_ks(message: &[u8], secret_key: &[u8], proving_key: &ProvingKey) -> Result<Vec<u8>> {
+    if secret_key.len() != proving_key.key_bytes()? { return Err(anyhow!("secret_key must be {} bytes", proving_key.key_bytes()?)); }
+    let (mut p, mut n) = (std::ptr::null_mut(), 0usize);
+    if unsafe { zkaes_encrypt(message.as_ptr(), message.len(), secret_key.as_ptr(), (proving_key.0).0, &mut p, &mut n) } != 0 { return Err(last_error()); }
+    Ok(take_bytes(p, n))
+}
+
+/// AES-ECB of whole blocks on the host; the key's length (16, 24, 32) selects AES-128, -192, -256
+pub fn ecb_ciphertext(message: &[u8], secret_key: &[u8]) -> Result<Vec<u8>> {
+    let mut ct = vec![0u8; message.len().max(1)];
+    if unsafe { zkaes_ecb_ciphertext_ks(message.as_ptr(), message.len(), secret_key.as_ptr(), secret_key.len(), ct.as_mut_ptr()) } != 0 { return Err(last_error()); }
+    ct.truncate(message.len());
+    Ok(ct)
+}
+
+/// AES-GCM on the host with a 16-, 24- or 32-byte key: (ciphertext, tag)
+pub fn gcm_encrypt_ks(message: &[u8], secret_key: &[u8], iv: &[u8; 12], aad: &[u8]) -> Result<(Vec<u8>, [u8; 16])> {
+    let mut ct = vec![0u8; message.len().max(1)];
+    let mut tag = [0u8; 16];
+    if unsafe { zkaes_gcm_encrypt_ks(message.as_ptr(), message.len(), secret_key.as_ptr(), secret_key.len(), iv.as_ptr(), aad.as_ptr(), aad.len(), ct.as_mut_ptr(), tag.as_mut_ptr()) } != 0 {
+        return Err(last_error());
+    }
+    ct.truncate(message.len());
+    Ok((ct, tag))
 }
