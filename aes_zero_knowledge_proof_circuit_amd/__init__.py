@@ -9,4 +9,5 @@ from .api import (ZkAesError, ProvingKey, VerifyingKey, synthesize_keys, encrypt
                   cbc_ciphertext, encrypt_cbc, verify_encryption_cbc, verify_cbc_chunked,
                   CIRCUIT_AES_CTR, ctr_crypt, ctr_counter_add, encrypt_ctr, verify_encryption_ctr, verify_ctr_chunked,
                   CIRCUIT_AES_GCM, synthesize_keys_gcm, gcm_encrypt, gcm_decrypt, encrypt_gcm, verify_encryption_gcm,
-                  ecb_ciphertext, circuit_info, circuit_matrix)
+                  ecb_ciphertext, circuit_info, circuit_matrix,
+                  key_tag, verify_chunked_tagged, verify_encryption_gcm_tagged)

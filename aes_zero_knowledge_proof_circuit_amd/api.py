@@ -130,6 +130,17 @@ class ProvingKey:
         _check(lib().zkaes_pk_key_bytes(self._p, C.byref(n)))
         return int(n.value)
 
+    def key_tag_blocks(self):
+        """T = 0, 1 or 2: the key-tag blocks this proving key was synthesized with (synthesize_keys(..., key_tag_blocks=)); the last 128 T public-input bits of every proof
+        it makes are key_tag(secret_key, T)"""
+        n = C.c_size_t()
+        _check(lib().zkaes_pk_key_tag_blocks(self._p, C.byref(n)))
+        return int(n.value)
+
+    def _message_bytes(self, header_bits):
+        """the key's plaintext length: the public input is One, header_bits bits of iv / counter, 8 bits per ciphertext byte, then 128 bits per key-tag block"""
+        return (self.info()["raw_instance"] - 1 - header_bits - 128 * self.key_tag_blocks()) // 8
+
     def _need_key(self, secret_key, other=None, other_name=None, other_len=16):
         """the secret key has the length this proving key was synthesized for (and `other`, the iv / icb, its own): the library reads that many bytes from the pointer"""
         kb = self.key_bytes()
@@ -224,7 +235,7 @@ class ProvingKey:
         from cbc_ciphertext); zk_seed and first_proof_index as encrypt_chunked"""
         self._need_key(secret_key, iv, "iv")
         seed = self._seed_arg(zk_seed)
-        chunk = (self.info()["raw_instance"] - 129) // 8        # One + 128 IV bits, then 8 public-input bits per ciphertext byte
+        chunk = self._message_bytes(128)
         if chunk <= 0:
             raise ZkAesError("proving key was not synthesized for the AES-CBC circuit")
         n_chunks = len(message) // chunk
@@ -257,7 +268,7 @@ class ProvingKey:
         call's first block (a job split over several calls passes ctr_counter_add(icb, blocks before)); zk_seed and first_proof_index as encrypt_chunked"""
         self._need_key(secret_key, icb, "icb")
         seed = self._seed_arg(zk_seed)
-        chunk = (self.info()["raw_instance"] - 129) // 8        # One + 128 icb bits, then 8 public-input bits per ciphertext byte
+        chunk = self._message_bytes(128)
         if chunk <= 0 or len(message) == 0 or len(message) % chunk:
             raise ZkAesError("message length must be a non-zero multiple of the CTR key's plaintext length")
         n_chunks = len(message) // chunk
@@ -332,7 +343,7 @@ class ProvingKey:
         PARITY = the reference's fixed prover randomness for every proof"""
         self._need_key(secret_key)
         seed = self._seed_arg(zk_seed)
-        chunk = (self.info()["raw_instance"] - 1) // 8          # 8 public-input bits per ciphertext byte
+        chunk = self._message_bytes(0)
         n_chunks = len(message) // chunk
         lens = (C.c_size_t * max(n_chunks, 1))()
         out, n = C.c_void_p(), C.c_size_t()
@@ -351,7 +362,7 @@ class ProvingKey:
     def encrypt_batch(self, messages, secret_keys, zk_seed=None, first_proof_index=0):
         """n independent proofs: messages = list of equal-length byte strings (the key's plaintext length), secret_keys = list of keys of key_bytes() bytes each; zk_seed as encrypt_chunked"""
         n = len(messages)
-        chunk = (self.info()["raw_instance"] - 1) // 8
+        chunk = self._message_bytes(0)
         if len(secret_keys) != n:
             raise ZkAesError("one secret key per message")
         if any(len(m) != chunk for m in messages):
@@ -387,17 +398,52 @@ class ProvingKey:
             pass
 
 
-def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags):
+def _tag_blocks(key_tag_blocks):
+    if key_tag_blocks not in (0, 1, 2):
+        raise ZkAesError("key_tag_blocks must be 0, 1 or 2")
+    return C.c_uint(int(key_tag_blocks))
+
+
+def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks=0):
     pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib().zkaes_synthesize_keys_ks(int(circuit), C.c_uint(int(key_bits)), C.c_size_t(plaintext_length), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]),
-                                          C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
+    _check(lib().zkaes_synthesize_keys_kt(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), C.c_size_t(plaintext_length), C.c_size_t(aad_length), C.c_size_t(srs[0]),
+                                          C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
     return ProvingKey(pk.value), VerifyingKey(vk.value)
 
 
-def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128):
+def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0):
     """zk_aes::synthesize_keys (src/lib.rs:138-174) -> (ProvingKey, VerifyingKey).  flags: KEY_NO_TABLES.  key_bits: 128 (the reference's AES-128), 192 or 256 for
-    the AES kinds; the proving key then takes secret keys of key_bits / 8 bytes (ProvingKey.key_bytes())"""
-    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags)
+    the AES kinds; the proving key then takes secret keys of key_bits / 8 bytes (ProvingKey.key_bytes()).  key_tag_blocks: 0 (no key tag, the default), 1 or 2: every
+    proof of the key also exposes key_tag(secret_key, key_tag_blocks) as public input, and is checked with verify_chunked_tagged"""
+    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags, key_tag_blocks)
+
+
+def key_tag(secret_key, blocks=2):
+    """the key tag on the host (zkaes_key_tag; no GPU): AES_K(D_0) (|| AES_K(D_1)), D_t = b"zkaes-keyta" + bytes([t, 0, 0, 0, 0]); 16 * blocks bytes, blocks = 1 or 2"""
+    _host_key(secret_key)
+    if blocks not in (1, 2):
+        raise ZkAesError("a key tag has 1 or 2 blocks")
+    out = C.create_string_buffer(16 * blocks)
+    _check(lib().zkaes_key_tag(bytes(secret_key), C.c_size_t(len(secret_key)), C.c_size_t(blocks), out))
+    return out.raw
+
+
+def verify_chunked_tagged(verifying_key, circuit, proofs, ciphertext, key_tag, iv=None):
+    """the chunk-proofs of one ECB, CBC or CTR job (circuit = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR) against ONE key tag -> list of bools.  iv: None for ECB, the
+    IV for CBC, the initial counter block for CTR; chunk j is checked as verify_encryption / verify_cbc_chunked / verify_ctr_chunked check it, with the tag bits behind
+    its ciphertext bits.  One proof is the lone-proof form (and the only one for a CTR length that is not whole blocks).  A key_tag that is not 16 or 32 bytes raises, as
+    do lengths the key was not synthesized for"""
+    if len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    if iv is not None and len(iv) != 16:
+        raise ZkAesError("iv / icb must be 16 bytes")
+    n = len(proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each = (C.c_int * max(n, 1))()
+    ok = C.c_size_t()
+    _check(lib().zkaes_verify_chunked_kt(verifying_key._p, int(circuit), b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), None if iv is None else bytes(iv), bytes(ciphertext),
+                                         C.c_size_t(len(ciphertext)), bytes(key_tag), C.c_size_t(len(key_tag)), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
 
 
 def _host_key(secret_key):
@@ -526,10 +572,10 @@ def _gcm_args(secret_key, iv, key_bytes=None):
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
 
 
-def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128):
+def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0):
     """(ProvingKey, VerifyingKey) for AES-GCM records of exactly plaintext_length message bytes (>= 1) and aad_length aad bytes (>= 0).  flags: KEY_NO_TABLES;
-    key_bits: 128, 192 or 256"""
-    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags)
+    key_bits: 128, 192 or 256; key_tag_blocks: 0, 1 or 2 as synthesize_keys (records are then checked with verify_encryption_gcm_tagged)"""
+    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks)
 
 
 def gcm_encrypt(message, secret_key, iv, aad=b""):
@@ -576,28 +622,42 @@ def verify_encryption_gcm(verifying_key, proof, iv, aad, ciphertext, tag):
     return bool(acc.value)
 
 
+def verify_encryption_gcm_tagged(verifying_key, proof, iv, aad, ciphertext, tag, key_tag):
+    """verify_encryption_gcm for a key with key-tag blocks: the record against its own GCM tag AND the key tag (16 or 32 bytes) every record of the session shares"""
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    if len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    acc = C.c_int()
+    _check(lib().zkaes_verify_encryption_gcm_kt(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext),
+                                                C.c_size_t(len(ciphertext)), bytes(tag), bytes(key_tag), C.c_size_t(len(key_tag)), C.byref(acc)))
+    return bool(acc.value)
+
+
 def proof_roundtrip(proof):
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_proof_roundtrip(bytes(proof), C.c_size_t(len(proof)), C.byref(out), C.byref(n)))
     return _take(out, n)
 
 
-def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128):
-    """aad_length: GCM circuits only; key_bits: 128, 192 or 256 for the AES kinds"""
+def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128, key_tag_blocks=0):
+    """aad_length: GCM circuits only; key_bits: 128, 192 or 256 and key_tag_blocks: 0, 1 or 2 for the AES kinds"""
     out = (C.c_uint64 * 12)()
-    _check(lib().zkaes_circuit_info_ks(int(circuit), C.c_uint(int(key_bits)), C.c_size_t(plaintext_length), C.c_size_t(aad_length), out))
+    _check(lib().zkaes_circuit_info_kt(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), C.c_size_t(plaintext_length), C.c_size_t(aad_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128):
+def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128, key_tag_blocks=0):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    head = (int(circuit), C.c_uint(int(key_bits)), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
-    _check(lib().zkaes_circuit_matrix_ks(*head, C.byref(rows), C.byref(nnz), None, None, None))
+    head = (int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
+    _check(lib().zkaes_circuit_matrix_kt(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
     coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-    _check(lib().zkaes_circuit_matrix_ks(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
+    _check(lib().zkaes_circuit_matrix_kt(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 

@@ -10,12 +10,13 @@ extern "C" {
 void zkaes_pk_free(zkaes_pk *pk) { delete pk; }
 int zkaes_device_count(void) { return zk::gpu::device_count(); }
 
-static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128) {
+static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128, size_t key_tag_blocks = 0) {
     return guard([&] {
         if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
         if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("synthesize_keys: key_bits must be 128, 192 or 256");
+        if (key_tag_blocks > 2) throw std::invalid_argument("synthesize_keys: key_tag_blocks must be 0, 1 or 2");
         zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
-        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len, key_bits);
+        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len, key_bits, key_tag_blocks);
         zkaes_vk *v = new zkaes_vk{k->vk()};
         zkaes_pk *p = new zkaes_pk{std::move(k)};
         if (pk) *pk = p; else delete p;
@@ -30,6 +31,15 @@ int zkaes_synthesize_keys_gcm(size_t len, size_t aad_len, size_t nc, size_t nv, 
 }
 int zkaes_synthesize_keys_ks(int kind, unsigned key_bits, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits);      // (compile_circuit refuses aad outside GCM and an ops kind with another key size)
+}
+int zkaes_synthesize_keys_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks);
+}
+int zkaes_pk_key_tag_blocks(const zkaes_pk *pk, size_t *n) {
+    return guard([&] {
+        if (!pk || !n) throw std::invalid_argument("null argument");
+        *n = pk->pk->key_tag_blocks();
+    });
 }
 int zkaes_pk_key_bytes(const zkaes_pk *pk, size_t *n) {
     return guard([&] {

@@ -5,7 +5,7 @@
 
 namespace {
 thread_local std::string g_err;
-zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128) { return zk::compile_circuit(kind, len, aad_len, key_bits); }
+zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0) { return zk::compile_circuit(kind, len, aad_len, key_bits, key_tag_blocks); }
 void require_key_len(size_t key_len) { if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes"); }
 // the CBC (and CTR) instance without the leading One: 128 bits of the IV (the initial counter block), then the ciphertext bits, each byte LSB first
 std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
@@ -222,6 +222,82 @@ int zkaes_verify_encryption_gcm(const zkaes_vk *vk, const uint8_t *proof, size_t
         *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
     });
 }
+// ---- key tags (include/zkaes.h): the tag on the host, and the verifiers that check every proof of a job against ONE tag
+int zkaes_key_tag(const uint8_t *secret_key, size_t key_len, size_t tag_blocks, uint8_t *out) {
+    return guard([&] {
+        if (!secret_key || !out) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        zk::aes_key_tag_host(secret_key, key_len, tag_blocks, out);
+    });
+}
+namespace {
+void require_key_tag_len(size_t key_tag_len) { if (key_tag_len != 16 && key_tag_len != 32) throw std::invalid_argument("key_tag_len must be 16 or 32 (one or two tag blocks)"); }
+// Does a public input of n_bits bits fit this key?  Where the key carries its exact count a mismatch raises (the verifier zero-pads, so a wrong tag length must never
+// reach it); a key from the ark transport carries only |X|, so there the answer is "rejected" unless the padded counts agree, and the caller answers for the rest
+bool fits_key(const zk::VerifyingKey &vk, size_t n_bits, const char *what) {
+    bool exact = vk.num_public_inputs + 1 != vk.num_instance;
+    if (exact && vk.num_public_inputs != n_bits) throw std::invalid_argument(std::string(what) + ": the ciphertext and key-tag lengths are not the ones this key was synthesized for");
+    return next_pow2(n_bits + 1) == vk.num_instance;
+}
+void append_bits(std::vector<zk::Fr> &pub, const uint8_t *bytes, size_t n) {
+    std::vector<zk::Fr> b = zk::ciphertext_to_public_input(bytes, n);
+    pub.insert(pub.end(), b.begin(), b.end());
+}
+}  // namespace
+// Chunk j's public input is what zkaes_verify_encryption (ECB), zkaes_verify_cbc_chunked or zkaes_verify_ctr_chunked derive for it, with the tag bits appended.  n_chunks = 1
+// is the lone-proof form, and the only one that takes a CTR ciphertext that is not whole blocks
+int zkaes_verify_chunked_kt(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len,
+                            const uint8_t *key_tag, size_t key_tag_len, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t j = 0; j < n_chunks; j++) accepted_each[j] = 0;
+        if (!vk || !proofs || !proof_lens || !ct || !key_tag) throw std::invalid_argument("null argument");
+        const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
+        if (!ecb && !cbc && !ctr) throw std::invalid_argument("verify_chunked_kt: circuit_kind must be ECB, CBC or CTR (GCM records go through zkaes_verify_encryption_gcm_kt)");
+        if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument("verify_chunked_kt: an iv or initial counter block for CBC and CTR, NULL for ECB");
+        require_key_tag_len(key_tag_len);
+        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument("verify_chunked_kt: the ciphertext must be n_chunks equal, non-empty slices");
+        const size_t chunk = ct_len / n_chunks;
+        if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument("verify_chunked_kt: every slice must be whole blocks (a lone CTR proof takes any length)");
+        if (!fits_key(vk->vk, (ecb ? 0 : 128) + 8 * chunk + 8 * key_tag_len, "verify_chunked_kt")) return;      // every chunk rejected
+        size_t off = 0, ok = 0;
+        for (size_t j = 0; j < n_chunks; j++) {
+            int acc = 0;
+            try {
+                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
+                std::vector<zk::Fr> pub;
+                uint8_t counter[16];
+                if (cbc) append_bits(pub, j ? ct + chunk * j - 16 : iv_or_icb, 16);
+                if (ctr) { zk::ctr_counter_add(iv_or_icb, (uint64_t)j * (chunk / 16), counter); append_bits(pub, counter, 16); }
+                append_bits(pub, ct + chunk * j, chunk);
+                append_bits(pub, key_tag, key_tag_len);
+                acc = zk::verify(vk->vk, pub, p) ? 1 : 0;
+            } catch (const std::runtime_error &) { acc = 0; }
+            if (accepted_each) accepted_each[j] = acc;
+            ok += (size_t)acc;
+            off += proof_lens[j];
+        }
+        if (n_accepted) *n_accepted = ok;
+    });
+}
+int zkaes_verify_encryption_gcm_kt(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len,
+                                   const uint8_t tag[16], const uint8_t *key_tag, size_t key_tag_len, int *accepted) {
+    return guard([&] {
+        if (accepted) *accepted = 0;
+        if (!vk || !proof || !iv || !ct || !tag || !key_tag || !accepted || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        require_key_tag_len(key_tag_len);
+        if (ct_len == 0) throw std::invalid_argument("GCM: the ciphertext must have at least one byte");
+        if (!fits_key(vk->vk, 224 + 8 * (aad_len + ct_len) + 8 * key_tag_len, "GCM")) return;
+        zk::Proof p = zk::deserialize_proof(proof, proof_len);
+        std::vector<zk::Fr> pub;
+        append_bits(pub, iv, 12);
+        if (aad_len) append_bits(pub, aad, aad_len);
+        append_bits(pub, ct, ct_len);
+        append_bits(pub, tag, 16);
+        append_bits(pub, key_tag, key_tag_len);
+        *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
+    });
+}
 int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out, size_t *out_len) {
     return guard([&] { auto b = zk::serialize_proof(zk::deserialize_proof(proof, proof_len)); *out = give(b); *out_len = b.size(); });
 }
@@ -295,9 +371,13 @@ int zkaes_vk_from_trapdoor(const uint64_t info[7], const uint8_t *index_comms, c
 int zkaes_circuit_info(int kind, size_t len, uint64_t out[12]) { return guard([&] { fill_info(compile(kind, len), out); }); }
 int zkaes_circuit_info_gcm(size_t len, size_t aad_len, uint64_t out[12]) { return guard([&] { fill_info(compile(zk::CIRCUIT_AES_GCM, len, aad_len), out); }); }
 int zkaes_circuit_info_ks(int kind, unsigned key_bits, size_t len, size_t aad_len, uint64_t out[12]) { return guard([&] { fill_info(compile(kind, len, aad_len, key_bits), out); }); }
-static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff, size_t key_bits = 128) {
+int zkaes_circuit_info_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, size_t len, size_t aad_len, uint64_t out[12]) {
+    return guard([&] { fill_info(compile(kind, len, aad_len, key_bits, key_tag_blocks), out); });
+}
+static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff, size_t key_bits = 128,
+                          size_t key_tag_blocks = 0) {
     return guard([&] {
-        zk::Circuit c = compile(kind, len, aad_len, key_bits);
+        zk::Circuit c = compile(kind, len, aad_len, key_bits, key_tag_blocks);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -311,6 +391,10 @@ int zkaes_circuit_matrix(int kind, size_t len, int which, uint64_t *n_rows, uint
 }
 int zkaes_circuit_matrix_ks(int kind, unsigned key_bits, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits);
+}
+int zkaes_circuit_matrix_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col,
+                            int64_t *coeff) {
+    return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits, key_tag_blocks);
 }
 int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(zk::CIRCUIT_AES_GCM, len, aad_len, which, n_rows, nnz, rowptr, col, coeff);

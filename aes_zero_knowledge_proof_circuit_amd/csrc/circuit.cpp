@@ -299,9 +299,9 @@ struct AesGates {
             }
         }
     }
-    // one block's rounds (src/lib.rs:194-278) from its round-0 input `in`; returns S_Nr
-    std::array<Byte, 16> block_rounds(const Byte *in, size_t bi) {
-        uint32_t base = blk(bi);
+    // one block's rounds (src/lib.rs:194-278) from its round-0 input `in`; returns S_Nr.  The block's slot is number bi behind TRK_BLOCK0, or lies at any trace base
+    std::array<Byte, 16> block_rounds(const Byte *in, size_t bi) { return block_rounds_at(in, blk(bi)); }
+    std::array<Byte, 16> block_rounds_at(const Byte *in, uint32_t base) {
         const uint32_t xt_off = TRK_BL_XT(nk), mp_off = TRK_BL_MP(nk);
         std::array<Byte, 16> s, t, u;
         for (int i = 0; i < 16; i++) s[i] = b.xor_byte(in[i], key[i], base + TR_BL_S + i);          // :196 raw key (round key 0 = the first 16 key bytes for every nk)
@@ -348,6 +348,24 @@ struct AesGates {
             for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
         }
     }
+    // The key tag, behind everything the mode emits: per tag block the rounds of the constant block D_t -- round 0 is constant ^ key and costs no gate, as for
+    // GCM's H block; its S_0 bits are key bits, negated where D_t has a one -- in the slot at mode_bytes rounded up to 16 plus t strides, then 128 inputs equal to its S_Nr.
+    // Returns the trace length with the slots
+    size_t key_tag(size_t tag_blocks, size_t mode_bytes) {
+        for (size_t t = 0; t < tag_blocks; t++) {
+            const uint32_t base = (uint32_t)TRK_KT_SLOT(nk, mode_bytes, t);
+            uint8_t d[16];
+            aes_key_tag_block(t, d);
+            std::array<Byte, 16> in;
+            for (int i = 0; i < 16; i++) in[i] = Builder::const_byte(d[i]);
+            const std::array<Byte, 16> s = block_rounds_at(in.data(), base);
+            for (int i = 0; i < 16; i++) {
+                Byte pi = b.alloc_byte(true, base + (uint32_t)TRK_BL_CT(nk) + (uint32_t)i);
+                for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], s[i][k]);
+            }
+        }
+        return TRK_KT_BYTES(nk, mode_bytes, tag_blocks);
+    }
 };
 
 }  // namespace
@@ -356,11 +374,22 @@ namespace {
 void require_key_bits(size_t key_bits) {
     if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("the AES key size must be 128, 192 or 256 bits");
 }
+void require_key_tag_blocks(size_t key_tag_blocks) {
+    if (key_tag_blocks > 2) throw std::invalid_argument("key_tag_blocks must be 0, 1 or 2");
+}
+// finish() for a mode whose own trace takes mode_bytes: the key-tag blocks go behind it
+Circuit finish_aes(Builder &b, AesGates &g, int kind, size_t n_blocks, size_t mode_bytes, size_t key_tag_blocks) {
+    const size_t trace_bytes = g.key_tag(key_tag_blocks, mode_bytes);
+    Circuit c = finish(b, kind, n_blocks, trace_bytes, g.key_bytes());
+    c.key_tag_blocks = key_tag_blocks; c.key_tag_off = key_tag_blocks ? TRK_KT(mode_bytes) : 0;
+    return c;
+}
 }  // namespace
 
-Circuit compile_aes_circuit(size_t len, size_t key_bits) {
+Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) {
     if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
     require_key_bits(key_bits);
+    require_key_tag_blocks(key_tag_blocks);
     size_t nb = len / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -372,14 +401,15 @@ Circuit compile_aes_circuit(size_t len, size_t key_bits) {
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = s[i];
     }
     g.ciphertext_inputs(ct);
-    return finish(b, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), g.key_bytes());
+    return finish_aes(b, g, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), key_tag_blocks);
 }
 
 // Gate order: message and key witnesses, the 16 IV bytes as inputs, the key schedule, per block the 128 xor gates of X_b = M_b ^ prev (prev = the IV bytes, then the
 // previous block's S_10) and the block's rounds from X_b, the ciphertext inputs.  The instance is One, 128 IV bits, 128 nb ciphertext bits.
-Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits) {
+Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) {
     if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
     require_key_bits(key_bits);
+    require_key_tag_blocks(key_tag_blocks);
     size_t nb = len / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -396,7 +426,7 @@ Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits) {
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = prev[i];
     }
     g.ciphertext_inputs(ct);
-    return finish(b, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, g.key_bytes());
+    return finish_aes(b, g, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, key_tag_blocks);
 }
 
 // Gate order: message and key witnesses, the 16 ICB bytes as inputs, the key schedule, per block (from the second on) the incrementer over the previous block's counter
@@ -404,9 +434,10 @@ Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits) {
 // 128 ICB bits, 8 len ciphertext bits.
 // Incrementer: counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8.  c_0 = 1, y_i = x_i ^ c_i, c_{i+1} = x_i & c_i (none behind i = 127: the sum is mod 2^128).
 // Position 0 folds away (y_0 = !x_0, c_1 = x_0), which leaves 127 xor and 126 and gates per increment.
-Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits) {
+Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) {
     if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
     require_key_bits(key_bits);
+    require_key_tag_blocks(key_tag_blocks);
     size_t nb = (len + 15) / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -441,7 +472,7 @@ Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits) {
         Byte pi = b.alloc_byte(true, slot(i / 16) + TR_CTR_BL_CT + (uint32_t)(i % 16));
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
     }
-    Circuit c = finish(b, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), g.key_bytes());
+    Circuit c = finish_aes(b, g, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), key_tag_blocks);
     c.message_bytes = len;
     return c;
 }
@@ -455,8 +486,9 @@ Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits) {
 // p_{i,k} = x_i & V_i[k] (16,384 and gates), then per output bit k a boolean y_k, seven booleans q_{k,0..6} and ONE row (sum_i p_{i,k} - y_k - 2 sum_j 2^j q_{k,j}) * One = 0:
 // y_k is the parity of the 128 products and q_k <= 64 their half.  The difference sits in A, as in enforce_equal, so A's row is 0 on a satisfied witness.  X_1 is the
 // first block itself; X_m = Y_{m-1} ^ block m costs one xor gate per existing bit (zero padding and the constant length block cost none).
-Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits) {
+Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t key_tag_blocks) {
     require_key_bits(key_bits);
+    require_key_tag_blocks(key_tag_blocks);
     if (len == 0) throw std::invalid_argument("GCM: the message must have at least one byte");
     if (len > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM: message and aad of one proof are limited to 65536 bytes each");
     const size_t nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TR_GCM_MULS(na, nb);
@@ -532,18 +564,19 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits) {
         Byte pi = b.alloc_byte(true, tag_off + (uint32_t)j);
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], tag[j][k]);
     }
-    Circuit c = finish(b, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), g.key_bytes());
+    Circuit c = finish_aes(b, g, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), key_tag_blocks);
     c.message_bytes = len; c.aad_bytes = alen;
     return c;
 }
 
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits) {
-    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len, key_bits);
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks) {
+    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks);
     if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
-    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits);
-    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits);
-    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits);
+    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks);
+    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits, key_tag_blocks);
+    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits, key_tag_blocks);
     if (key_bits != 128) throw std::invalid_argument("the ops circuits have no AES key: key_bits must be 128");
+    if (key_tag_blocks) throw std::invalid_argument("the ops circuits have no AES key: key_tag_blocks must be 0");
     return compile_ops_circuit(kind);
 }
 
@@ -593,6 +626,19 @@ void aes_ecb_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, si
         aes.encrypt_block(s);
         for (int i = 0; i < 16; i++) out[off + i] = s[i];
     }
+}
+
+void aes_key_tag_block(size_t t, uint8_t out[16]) {
+    static const char prefix[] = TRK_KT_D_PREFIX;
+    for (int i = 0; i < 11; i++) out[i] = (uint8_t)prefix[i];
+    out[11] = (uint8_t)t;
+    for (int i = 12; i < 16; i++) out[i] = 0;
+}
+
+void aes_key_tag_host(const uint8_t *key, size_t key_len, size_t tag_blocks, uint8_t *out) {
+    if (tag_blocks != 1 && tag_blocks != 2) throw std::invalid_argument("a key tag has 1 or 2 blocks");
+    HostAes128 aes(key, key_len);
+    for (size_t t = 0; t < tag_blocks; t++) { aes_key_tag_block(t, out + 16 * t); aes.encrypt_block(out + 16 * t); }
 }
 
 void aes128_cbc_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[16], uint8_t *out, size_t key_len) {

@@ -39,28 +39,36 @@ struct Circuit {
     std::vector<uint32_t> sbox_in_off;   // trace offset of the input byte of every S-box instance
     std::vector<uint32_t> sbox_tmpl;     // (level, node, bit) of every allocated variable of one S-box
     size_t trace_bytes = 0;
+    size_t key_tag_blocks = 0;           // T = 0, 1 or 2 key-tag blocks: the last 128 T instance bits are AES_K(D_0) (, AES_K(D_1))
+    size_t key_tag_off = 0;              // trace offset of tag slot 0 (trace_layout.h TRK_KT), 0 when T = 0
     size_t num_variables() const { return num_instance + num_witness; }
 };
 
 // message_len must be a multiple of 16 (else throws std::invalid_argument with the reference's message)
 // Every AES compiler takes the key size in bits, 128 (the reference's, and the default), 192 or 256; anything else is std::invalid_argument.  The statement, the
 // public input and the gate order inside a round, the schedule and each mode do not depend on it; the round count (Nk + 6) and the schedule (FIPS-197 5.2) do.
-Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128);
+// key_tag_blocks (every AES compiler, default 0 = the circuit as it was): T = 1 or 2 appends, behind everything the mode emits, per t < T the rounds of the constant block
+// D_t = "zkaes-keyta" || t || 00000000 under the same key and 128 public input bits equal to its S_Nr; anything but 0, 1, 2 is std::invalid_argument
+Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
 Circuit compile_ops_circuit(int kind);
 // AES-128-CBC over the same gadgets (no upstream counterpart; DESIGN.md "CBC"): public = 16 IV bytes then the ciphertext, private = message and key;
 // per block X_b = M_b ^ C_{b-1} (C_{-1} = IV) ahead of the block's round 0.  message_len must be a non-zero multiple of 16 (else std::invalid_argument)
-Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128);
+Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
 // AES-128-CTR over the same gadgets (DESIGN.md "CTR"): public = the 16 bytes of the initial counter block then the ciphertext, private = message and key;
 // CTR_0 = icb, CTR_b = CTR_{b-1} + 1 mod 2^128 (big-endian, SP 800-38A B.1 with m = 128), C_b = M_b ^ AES(key, CTR_b), the last block cut to the bytes that exist.
 // message_len is any byte count >= 1 (else std::invalid_argument)
-Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128);
+Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
 // AES-128-GCM (SP 800-38D, 96-bit IV, full tag; DESIGN.md "GCM"): public = iv (12 bytes), aad (aad_len bytes), ciphertext (message_len bytes), tag (16 bytes), private =
 // message and key.  The trace holds nb + 2 AES blocks (the message blocks under iv || be32(b + 2), H = AES_K(0), AES_K(iv || 1)), the V table of H and, per GHASH block,
 // one multiplication by H as 16,384 and gates and 128 parity rows.  message_len >= 1, aad_len >= 0; both are fixed by the key (else std::invalid_argument)
-Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128);
+Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
-// 128 for the ops kinds
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128);
+// 128 and key_tag_blocks 0 for the ops kinds
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0);
+// the key tag itself on the host: out = 16 tag_blocks bytes, AES_K(D_0) (|| AES_K(D_1)); key_len = 16, 24 or 32, tag_blocks = 1 or 2 (else std::invalid_argument)
+void aes_key_tag_host(const uint8_t *key, size_t key_len, size_t tag_blocks, uint8_t *out);
+// D_t, the constant block behind tag block t
+void aes_key_tag_block(size_t t, uint8_t out[16]);
 uint8_t aes_sbox_value(uint8_t x);   // the lookup table of src/aes_circuit.rs:433-694
 // plain byte-wise AES-128-CBC over aes_sbox_value, host only: out = len bytes, len a multiple of 16
 // (the host ciphers keep their names; key_len = 16, 24 or 32 bytes selects AES-128, -192 or -256, anything else is std::invalid_argument)

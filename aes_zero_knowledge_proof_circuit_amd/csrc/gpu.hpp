@@ -262,6 +262,10 @@ void aes_trace_ctr(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, con
 // the trace and fills the V table, every multiplication's X, P, q and Y and the tag.  stride >= TR_GCM_BYTES, a multiple of 16; trace 16-byte aligned
 void aes_trace_gcm(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes = 16);
 void ghash_trace(uint8_t *trace, size_t trace_stride, uint32_t nproofs, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes = 16);
+// Key tags, any mode: fills the tag_blocks (1 or 2) tag slots of each proof's trace at tag_off (trace_layout.h TRK_KT of the mode's own trace length) from the keys
+// alone; launched behind the mode's kernel(s) on the same stream, it writes bytes disjoint from theirs.  stride >= tag_off + tag_blocks block strides; stride, tag_off
+// and the trace 16-byte aligned
+void key_tag_trace(uint8_t *trace, size_t trace_stride, size_t tag_off, const uint8_t *keys, uint32_t nproofs, uint32_t tag_blocks, stream_t s, size_t key_bytes = 16);
 // z[col] (0/1 bytes) for every column, by descriptor
 void witness_expand(uint8_t *z, const uint32_t *desc, uint32_t ncols, const uint8_t *trace, const uint32_t *sbox_in_off, const uint32_t *sbox_tmpl, stream_t s);
 // out[r] = sum_i coeff[i] * z[col[i]] as a field element, rows with no entries give 0 (out has `rows_out` >= rows entries, tail zeroed)

@@ -9,6 +9,7 @@
 //   k_aes_trace_gcm   AES-GCM's nb + 2 AES blocks (the message under inc32 counters, H, the tag mask), and behind it
 //   k_ghash_trace     the GHASH half: the V table of H and, per block, the 16,384 partial products, carries and result of
 //                     one multiplication in GF(2^128), sixteen lanes per multiplication, each re-walking the chain in registers,
+//   k_key_tag_trace   for a key with key-tag blocks, behind any of the above: AES of the constant blocks D_t under the proof's key into the slots behind the mode's tail,
 //   k_witness_expand  one lane per column of z: decode the variable's descriptor (compiled once by circuit.cpp) and gather
 //                     its bit -- S-box mux-tree variables are a table lookup S[(node << (level+1)) | (x & mask)],
 //   k_spmv_bits       z_A = A z, z_B = B z over 0/1 assignments with small integer coefficients (ark-marlin prover_init),
@@ -304,6 +305,29 @@ __global__ void k_ghash_trace(uint8_t *__restrict__ trace, size_t stride, uint32
     mul[TR_GCM_MUL_Y + j] = y;
     if (m + 1 == n_mul) tail[TR_GCM_TAG(naad, nblocks) + j] = y ^ tr[TRK_BLOCK0(NK) + (size_t)(nblocks + 1) * TRK_BLOCK_STRIDE(NK) + TRK_BL_CT(NK) + j];
 }
+
+// The key tag (trace_layout.h TRK_KT), for every mode, launched behind the mode's own kernel(s) on the same stream: nproofs * ntags lanes, ntags = 1 or 2.
+// Lane (p, t) runs the key schedule in registers (no schedule stores: that part of the trace belongs to the mode's lane (p, 0)), builds D_t = "zkaes-keyta" || t ||
+// 00000000 and fills tag slot t at tag_off + t strides like any block slot: D_t in the message field, S_0 = D_t ^ key, every round's intermediates, S_Nr = the tag.  It is
+// handed the keys only, never a tag made on the host.  Every byte of the slots has exactly one writer and no byte ahead of tag_off is touched; no LDS, no barrier, no
+// cross-lane operation.
+template <int NK = 4>
+__global__ void k_key_tag_trace(uint8_t *__restrict__ trace, size_t stride, size_t tag_off, const uint8_t *__restrict__ keys, uint32_t nproofs, uint32_t ntags, const uint8_t *__restrict__ sbox) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nproofs * ntags) return;
+    uint32_t p = t / ntags, which = t % ntags;
+    const uint8_t *key = keys + TRK_KEY_BYTES(NK) * (size_t)p;
+    uint8_t w[TRK_KS_WORDS(NK)][4];
+    aes_key_schedule<NK>(key, sbox, w, nullptr);
+    uint8_t *bl = trace + (size_t)p * stride + tag_off + (size_t)which * TRK_BLOCK_STRIDE(NK);
+    const char prefix[] = TRK_KT_D_PREFIX;
+    uint8_t s[16];
+    for (int i = 0; i < 16; i++) {
+        uint8_t d = i < 11 ? (uint8_t)prefix[i] : i == 11 ? (uint8_t)which : 0;
+        bl[TR_BL_MSG + i] = d; s[i] = d ^ key[i]; bl[TR_BL_S + i] = s[i];
+    }
+    aes_block_rounds<true, NK>(s, w, sbox, bl);
+}
 template <bool CBC>
 static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, size_t key_bytes, stream_t s) {
     // the stride must hold the trace of THIS key size: a caller that sized its buffer for another one gets an error here, never lanes that store past a trace
@@ -375,6 +399,26 @@ void ghash_trace(uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_l
     if (nk == 4) hipLaunchKernelGGL(k_ghash_trace<4>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
     else if (nk == 6) hipLaunchKernelGGL(k_ghash_trace<6>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
     else hipLaunchKernelGGL(k_ghash_trace<8>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
+    HIP_LAUNCH_CHECK();
+}
+// what the entry checks before any lane runs: T, the slots inside the stride, and 16-byte alignment of slot 0 and of every trace (as the GCM entries: tagged traces are
+// 16-byte multiples for every mode and key size)
+void key_tag_trace(uint8_t *trace, size_t stride, size_t tag_off, const uint8_t *keys, uint32_t nproofs, uint32_t tag_blocks, stream_t s, size_t key_bytes) {
+    const int nk = trace_nk("key_tag_trace", key_bytes);
+    if (!trace || !keys) throw GpuError("key_tag_trace: no trace or key buffer");
+    if (tag_blocks != 1 && tag_blocks != 2) throw GpuError("key_tag_trace: 1 or 2 tag blocks");
+    const size_t slot = trace_bytes_of(nk, TRK_BLOCK_STRIDE(4), TRK_BLOCK_STRIDE(6), TRK_BLOCK_STRIDE(8));
+    if (tag_off < trace_bytes_of(nk, TRK_BLOCK0(4), TRK_BLOCK0(6), TRK_BLOCK0(8)) || tag_off > stride || stride - tag_off < tag_blocks * slot)
+        throw GpuError("key_tag_trace: trace stride " + std::to_string(stride) + " does not hold " + std::to_string(tag_blocks) + " tag slots of " + std::to_string(slot) + " bytes at offset " + std::to_string(tag_off));
+    if (tag_off % 16 || stride % 16 || (uintptr_t)trace % 16) throw GpuError("key_tag_trace: tagged traces and the tag offset must be 16-byte aligned");
+    if (nproofs == 0 || nproofs > (1u << 20)) throw GpuError("key_tag_trace: 1 .. 2^20 proofs per launch");
+    uint8_t *g_sbox = sbox_here();
+    if (!g_sbox) throw GpuError("key_tag_trace: S-box table not uploaded on this device");
+    uint32_t lanes = nproofs * tag_blocks;
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL(k_key_tag_trace<4>, grid, block, 0, (hipStream_t)s, trace, stride, tag_off, keys, nproofs, tag_blocks, g_sbox);
+    else if (nk == 6) hipLaunchKernelGGL(k_key_tag_trace<6>, grid, block, 0, (hipStream_t)s, trace, stride, tag_off, keys, nproofs, tag_blocks, g_sbox);
+    else hipLaunchKernelGGL(k_key_tag_trace<8>, grid, block, 0, (hipStream_t)s, trace, stride, tag_off, keys, nproofs, tag_blocks, g_sbox);
     HIP_LAUNCH_CHECK();
 }
 

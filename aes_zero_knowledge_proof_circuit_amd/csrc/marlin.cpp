@@ -486,7 +486,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -495,14 +495,14 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
     message_len = message_len_;
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
-    circuit = compile_circuit(kind, message_len, aad_len, key_bits);
+    circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks);
     const Circuit &c = circuit;
     // ---- joint matrix (sum_matrices): per-row sorted union of the A, B, C column supports
     size_t rows = c.num_constraints;
@@ -673,6 +673,8 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
     } else {
         gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s, c.key_bytes);
     }
+    // a key with key-tag blocks: the tag slots behind the mode's tail, from the key alone (bytes disjoint from those the kernels above write)
+    if (c.key_tag_blocks) gpu::key_tag_trace(cx.d_trace, c.trace_bytes, c.key_tag_off, cx.d_key, 1, (uint32_t)c.key_tag_blocks, s, c.key_bytes);
 }
 
 void ProvingKeyImpl::prove_round1(ProofRun &R) {
@@ -1339,11 +1341,12 @@ std::vector<uint8_t> ProvingKey::debug_fetch(const std::string &name) const {
 }
 
 size_t ProvingKey::key_bytes() const { return impl->circuit.key_bytes; }
+size_t ProvingKey::key_tag_blocks() const { return impl->circuit.key_tag_blocks; }
 
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits) {
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits);
+    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks);
     return pk;
 }
 

@@ -65,6 +65,9 @@ class ProvingKey {
     // the byte length of the AES key this proving key was synthesized for: 16, 24 or 32.  EVERY `key` argument below -- written key[16] from when 16 was the only size --
     // points to key_bytes() bytes, and the batch calls take n x key_bytes() key bytes
     size_t key_bytes() const;
+    // T = 0, 1 or 2: the key-tag blocks this key was synthesized with.  Every proving and witness call below takes a tagged key as it is: the last 128 T
+    // public-input bits of each proof are AES_K(D_0) (, AES_K(D_1)) for that proof's key, filled from the trace like every other column
+    size_t key_tag_blocks() const;
     // encrypt(): message length must equal the length the key was synthesized for; zk_seed = 32-byte StdRng seed or nullptr for
     // ark_std::test_rng()'s (what simpleworks::marlin::generate_rand() returns)
     Proof prove_aes(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t *zk_seed);
@@ -134,7 +137,8 @@ class ProvingKey {
 // multi-proof calls then run 15 per-window-bucket windows instead of 13 table windows (~9 % fewer blocks/s), and the key fits a GPU that is short of memory.
 // Without the flag the tables are built when memory allows (hipMemGetInfo) and silently skipped otherwise.
 enum : unsigned { KEY_NO_TABLES = 1u };
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, the AES kinds only)
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128,
+                                            size_t key_tag_blocks = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, the AES kinds only)
 // hold = true: every universal / Lagrange SRS built (or alive) from now on stays resident after its last key is freed; false: back to "freed with the last key"
 void srs_hold(bool hold);
 // process default of ProvingKey::contexts(): ZKAES_CONTEXTS from the environment (read once), else ZKAES_DEFAULT_CONTEXTS

@@ -119,6 +119,20 @@ static_assert(TRK_BLOCK_STRIDE(6) == 1296 && TRK_BLOCK_STRIDE(8) == 1520 && TRK_
 static_assert(TRK_KS_INST_OF(6, 48) == 7 && TRK_KS_INST_OF(8, 8) == 0 && TRK_KS_INST_OF(8, 12) == 1 && TRK_KS_INST_OF(8, 56) == 12, "SubWord instance numbering");
 static_assert(TRK_GCM(6, 1) % 16 == 0 && TRK_GCM(8, 1) % 16 == 0 && TRK_GCM(6, 1) == TRK_CBC(6, 3) + 8 && TRK_GCM(8, 2) == TRK_CBC(8, 4) + 8 && TRK_GCM_BYTES(6, 1, 2) % 16 == 0, "the GCM tail must stay 16-byte aligned");
 
+// ---- key tags: a key synthesized with T = 1 or 2 key-tag blocks proves tag_t = AES_K(D_t), t < T, beside its mode's statement, D_t = "zkaes-keyta" || t ||
+// 00 00 00 00.  The T tag slots lie BEHIND the mode's tail, so no offset above moves: `bytes` = the mode's own trace length (TRK_ECB_BYTES, TRK_CBC_BYTES, TRK_CTR_BYTES,
+// TRK_GCM_BYTES), TRK_KT(bytes) = that length rounded up to 16 is slot 0, slot t follows at t block strides, and a slot has the ordinary block-slot layout: D_t in the
+// "message" field, S_0 = D_t ^ key, ..., S_Nr = tag_t.  With T = 0 a trace is what it was.
+#define TRK_KT(bytes) (((bytes) + 15) / 16 * 16)
+#define TRK_KT_SLOT(nk, bytes, t) (TRK_KT(bytes) + (t) * TRK_BLOCK_STRIDE(nk))
+#define TRK_KT_BYTES(nk, bytes, T) ((T) ? TRK_KT_SLOT(nk, bytes, T) : (bytes))
+#define TRK_KT_D_PREFIX "zkaes-keyta"      // 11 bytes, none of them zero; byte 11 is t, bytes 12 .. 15 are zero
+static_assert(TRK_KT_BYTES(4, TRK_ECB_BYTES(4, 1), 0) == TR_BLOCK0 + TR_BLOCK_STRIDE && TRK_KT_BYTES(8, TRK_CTR_BYTES(8, 2), 0) == TRK_CTR_BYTES(8, 2), "without key tags a trace keeps its length");
+static_assert(TRK_KT(TRK_ECB_BYTES(4, 1)) == TRK_ECB_BYTES(4, 1) && TRK_KT(TRK_ECB_BYTES(6, 1)) == TRK_ECB_BYTES(6, 1) + 8 && TRK_KT(TRK_ECB_BYTES(8, 2)) == TRK_ECB_BYTES(8, 2) + 8, "tag slot 0 begins on the next multiple of 16");
+static_assert(TRK_KT_SLOT(8, TRK_ECB_BYTES(8, 2), 1) == 3424 + 1520 && TRK_KT_BYTES(8, TRK_ECB_BYTES(8, 2), 2) == 3424 + 2 * 1520 && TRK_KT_BYTES(4, TRK_CTR_BYTES(4, 2), 1) == 2528 + 1072, "tag slots at the block stride");
+static_assert(TRK_BLOCK_STRIDE(4) % 16 == 0 && TRK_BLOCK_STRIDE(6) % 16 == 0 && TRK_BLOCK_STRIDE(8) % 16 == 0 && TRK_KT_BYTES(6, TRK_GCM_BYTES(6, 1, 2), 1) % 16 == 0 && TRK_KT(TRK_GCM_BYTES(8, 1, 2)) == TRK_GCM_BYTES(8, 1, 2), "tagged traces are 16-byte multiples");
+static_assert(sizeof(TRK_KT_D_PREFIX) == 12, "D_t = 11 prefix bytes, t, four zero bytes");
+
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30
 #define WD_BYTEBIT 0u   // [29:4] trace offset, [3:1] bit, [0] neg

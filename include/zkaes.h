@@ -246,6 +246,40 @@ int zkaes_gcm_encrypt_ks(const uint8_t *message, size_t message_len, const uint8
                          uint8_t *ciphertext, uint8_t tag16[16]);
 int zkaes_gcm_decrypt_ks(const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t *secret_key, size_t key_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
                          const uint8_t tag16[16], uint8_t *message, int *ok);
+/* ---- Key tags: bind every chunk-proof and record of a job to one AES key ---------------------------------------------------
+ * A chunk-proof says "some key encrypts this slice"; nothing above ties the chunk-proofs of one message, or the GCM records of one session, to the SAME key.  A key
+ * synthesized with key_tag_blocks = T, T = 1 or 2 (0 = every key above: nothing changes), proves beside its mode's statement
+ *     tag_t = AES_K(D_t),   D_t = 7a 6b 61 65 73 2d 6b 65 79 74 61 || t || 00 00 00 00   ("zkaes-keyta", the byte t, four zero bytes),   t = 0 .. T - 1
+ * and exposes the 128 T tag bits as public input BEHIND everything the mode puts there (bytes as 8 LSB-first bits, as everywhere).  Two proofs with equal tags were made
+ * under the same key (ideal-cipher heuristic: about 2^64 work to break at one block, 2^128 at two); a verifier checks every chunk against ONE tag.  The tag is
+ * deterministic -- a public name for the key -- and, like any known plaintext / ciphertext pair, lets anyone test a guessed key.  D_t ends in four zero bytes, so it is no
+ * GCM counter block of a 96-bit IV (those end in 1, 2, ...), and begins with non-zero bytes, so it is not the block behind H.  A prover who feeds D_t to ECB, CBC or CTR
+ * as a message or counter block publishes their own tag material; like nonce reuse that is the prover's business and is not policed.
+ * No new proving entry points: every encrypt, chunked, batch and witness function above takes a tagged proving key as it is.  A verifying key carries no T, as it carries
+ * no mode and no key size; its transport layouts do not change.  The untagged verifiers above never accept a proof of a tagged key (they raise where the key carries its
+ * exact public-input count and the lengths disagree, and reject otherwise), and the tagged verifiers never accept a proof of an untagged key. */
+/* as zkaes_synthesize_keys_ks with key_tag_blocks = 0, 1 or 2 (anything else, or non-zero for an ops kind, is an error) */
+int zkaes_synthesize_keys_kt(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, size_t plaintext_length, size_t aad_length, size_t srs_num_constraints,
+                             size_t srs_num_variables, size_t srs_num_non_zero, unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* *n = the key-tag blocks of this proving key: 0, 1 or 2 */
+int zkaes_pk_key_tag_blocks(const zkaes_pk *pk, size_t *n);
+/* host only: out = 16 tag_blocks bytes, AES_K(D_0) (|| AES_K(D_1)): what a verifier is given once per key.  key_len = 16, 24 or 32, tag_blocks = 1 or 2 */
+int zkaes_key_tag(const uint8_t *secret_key, size_t key_len, size_t tag_blocks, uint8_t *out);
+/* host only: zkaes_circuit_info_ks / zkaes_circuit_matrix_ks with key_tag_blocks; at 0 they return what those return */
+int zkaes_circuit_info_kt(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, size_t plaintext_length, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_kt(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, size_t plaintext_length, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz,
+                            uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+/* host only: the chunk-proofs of one ECB, CBC or CTR job (circuit_kind = ZKAES_CIRCUIT_AES, _AES_CBC, _AES_CTR) against ONE key tag.  Chunk j's public input is what
+ * zkaes_verify_encryption, zkaes_verify_cbc_chunked and zkaes_verify_ctr_chunked derive for it (iv_or_icb: NULL for ECB, the IV for CBC, the initial counter block for
+ * CTR), then the tag bits.  n_chunks = 1 is the lone-proof form, and the only one that takes a CTR ciphertext that is not whole blocks.  key_tag_len = 16 or 32, anything
+ * else is an error.  Lengths that do not fit the key's public-input count are an error where the key carries that count (every key but one read from the ark transport);
+ * otherwise every chunk is rejected -- a tagged verifier never accepts on a mismatched length.  A proof that does not parse is a rejected chunk, not an error.
+ * accepted_each (n_chunks ints) and n_accepted may be NULL */
+int zkaes_verify_chunked_kt(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ciphertext,
+                            size_t ciphertext_len, const uint8_t *key_tag, size_t key_tag_len, int *accepted_each, size_t *n_accepted);
+/* host only: zkaes_verify_encryption_gcm with the key tag behind the GCM tag */
+int zkaes_verify_encryption_gcm_kt(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext,
+                                   size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *key_tag, size_t key_tag_len, int *accepted);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

@@ -94,6 +94,18 @@ extern "C" {
                             tag16: *mut u8) -> c_int;
     fn zkaes_gcm_decrypt_ks(ciphertext: *const u8, ciphertext_len: usize, secret_key: *const u8, key_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, tag16: *const u8,
                             message: *mut u8, ok: *mut c_int) -> c_int;
+    // key tags (include/zkaes.h, section "Key tags"; these declarations and the wrappers at the end of the file were not compiled: no cargo in the build image)
+    fn zkaes_synthesize_keys_kt(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, plaintext_length: usize, aad_length: usize, srs_num_constraints: usize,
+                                srs_num_variables: usize, srs_num_non_zero: usize, flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_pk_key_tag_blocks(pk: *const zkaes_pk, n: *mut usize) -> c_int;
+    fn zkaes_key_tag(secret_key: *const u8, key_len: usize, tag_blocks: usize, out: *mut u8) -> c_int;
+    fn zkaes_circuit_info_kt(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, plaintext_length: usize, aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_kt(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, plaintext_length: usize, aad_length: usize, which: c_int, n_rows: *mut u64, nnz: *mut u64,
+                               rowptr: *mut u32, col: *mut u32, coeff: *mut i64) -> c_int;
+    fn zkaes_verify_chunked_kt(vk: *const zkaes_vk, circuit_kind: c_int, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, iv_or_icb: *const u8, ciphertext: *const u8,
+                               ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    fn zkaes_verify_encryption_gcm_kt(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
+                                      ciphertext_len: usize, tag16: *const u8, key_tag: *const u8, key_tag_len: usize, accepted: *mut c_int) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
@@ -573,4 +585,54 @@ pub fn gcm_encrypt_ks(message: &[u8], secret_key: &[u8], iv: &[u8; 12], aad: &[u
     }
     ct.truncate(message.len());
     Ok((ct, tag))
+}
+
+// ---- Key tags: every chunk-proof and record of a job bound to one AES key (include/zkaes.h, section "Key tags").  NOT COMPILED: no cargo in the build image.
+/// `synthesize_keys_ks` with key_tag_blocks = 0 (no tag), 1 or 2: every proof of the key also exposes `key_tag(secret_key, key_tag_blocks)` as public input
+pub fn synthesize_keys_kt(circuit_kind: c_int, key_bits: u32, key_tag_blocks: u32, len: usize, aad_len: usize, flags: u32) -> Result<(ProvingKey, VerifyingKey)> {
+    let (mut pk, mut vk) = (std::ptr::null_mut(), std::ptr::null_mut());
+    if unsafe { zkaes_synthesize_keys_kt(circuit_kind, key_bits as c_uint, key_tag_blocks as c_uint, len, aad_len, 866_944, 513, 4_062_064, flags as c_uint, &mut pk, &mut vk) } != 0 {
+        return Err(last_error());
+    }
+    Ok((ProvingKey(Arc::new(PkHandle(pk))), VerifyingKey(Arc::new(VkHandle(vk)))))
+}
+
+impl ProvingKey {
+    /// the key-tag blocks this proving key was synthesized with: 0, 1 or 2
+    pub fn key_tag_blocks(&self) -> Result<usize> {
+        let mut n = 0usize;
+        if unsafe { zkaes_pk_key_tag_blocks((self.0).0, &mut n) } != 0 { return Err(last_error()); }
+        Ok(n)
+    }
+}
+
+/// the key tag on the host: AES_K(D_0) (|| AES_K(D_1)), D_t = "zkaes-keyta" || t || 00 00 00 00; 16 * blocks bytes, blocks = 1 or 2
+pub fn key_tag(secret_key: &[u8], blocks: usize) -> Result<Vec<u8>> {
+    let mut out = vec![0u8; 16 * blocks.max(1)];
+    if unsafe { zkaes_key_tag(secret_key.as_ptr(), secret_key.len(), blocks, out.as_mut_ptr()) } != 0 { return Err(last_error()); }
+    Ok(out)
+}
+
+/// the chunk-proofs of one ECB, CBC or CTR job against ONE key tag (16 or 32 bytes); iv_or_icb: None for ECB, the IV for CBC, the initial counter block for CTR
+pub fn verify_chunked_tagged(verifying_key: &VerifyingKey, circuit_kind: c_int, proofs: &[Vec<u8>], iv_or_icb: Option<&[u8; 16]>, ciphertext: &[u8], key_tag: &[u8]) -> Result<Vec<bool>> {
+    let blob: Vec<u8> = proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut each = vec![0 as c_int; proofs.len().max(1)];
+    let mut ok = 0usize;
+    let iv = iv_or_icb.map_or(std::ptr::null(), |v| v.as_ptr());
+    if unsafe { zkaes_verify_chunked_kt((verifying_key.0).0, circuit_kind, blob.as_ptr(), lens.as_ptr(), proofs.len(), iv, ciphertext.as_ptr(), ciphertext.len(), key_tag.as_ptr(), key_tag.len(),
+                                        each.as_mut_ptr(), &mut ok) } != 0 {
+        return Err(last_error());
+    }
+    Ok(each.iter().take(proofs.len()).map(|&a| a != 0).collect())
+}
+
+/// `verify_encryption_gcm` for a key with key-tag blocks: the record against its own GCM tag and the key tag every record of the session shares
+pub fn verify_encryption_gcm_tagged(verifying_key: &VerifyingKey, proof: &[u8], iv: &[u8; 12], aad: &[u8], ciphertext: &[u8], tag: &[u8; 16], key_tag: &[u8]) -> Result<bool> {
+    let mut acc: c_int = 0;
+    if unsafe { zkaes_verify_encryption_gcm_kt((verifying_key.0).0, proof.as_ptr(), proof.len(), iv.as_ptr(), aad.as_ptr(), aad.len(), ciphertext.as_ptr(), ciphertext.len(), tag.as_ptr(),
+                                               key_tag.as_ptr(), key_tag.len(), &mut acc) } != 0 {
+        return Err(last_error());
+    }
+    Ok(acc != 0)
 }
