@@ -900,6 +900,54 @@ def msm_table(curve_id, bases_bytes, scalars_bytes, window_bits, srs=False):
     return out.raw, bool(inf.value)
 
 
+# ---- TEST / DEBUG: the MSM forms the prover calls (include/zkaes.h; BLS12-377).  bases: 96-byte standard affine points as bytes or a C-contiguous uint8 numpy array
+# (a million tiled points need no copy); scalars: 32-byte Montgomery limbs; edwards=True is the prover's law.  Points come back as (xy bytes, is_infinity).
+def _host(buf):
+    if isinstance(buf, np.ndarray):
+        if not buf.flags["C_CONTIGUOUS"]:
+            raise ValueError("array arguments must be C-contiguous")
+        return buf.ctypes.data_as(C.c_void_p)
+    return bytes(buf)
+
+
+def _nbytes(buf):
+    return buf.nbytes if isinstance(buf, np.ndarray) else len(buf)
+
+
+def class_sum(bases, vals, edwards=True, prior_msm_points=0):
+    """vals: 1..8 int8 arrays of one length n = len(bases) / 96 -> [(accepted, xy, is_inf), ...], the vectors summed one after the other on one workspace"""
+    n, count = _nbytes(bases) // 96, len(vals)
+    v = np.ascontiguousarray(np.stack([np.asarray(x, dtype=np.int8) for x in vals])) if count else np.zeros((0, n), dtype=np.int8)
+    if count and v.shape[1] != n:
+        raise ValueError("every value vector needs one value per base")
+    ok, inf, out = (C.c_int * max(count, 1))(), (C.c_int * max(count, 1))(), C.create_string_buffer(96 * max(count, 1))
+    _check(lib().zkaes_class_sum(_host(bases), C.c_size_t(n), v.ctypes.data_as(C.c_void_p), int(count), 1 if edwards else 0, C.c_size_t(prior_msm_points), ok, out, inf))
+    return [(bool(ok[i]), out.raw[96 * i:96 * i + 96], bool(inf[i])) for i in range(count)]
+
+
+def msm_pair(bases, scal1, scal2, val_off2, edwards=True):
+    """sum scal1[i] bases[i] + sum scal2[j] bases[val_off2 + j] as ONE per-window Pippenger instance"""
+    out, inf = C.create_string_buffer(96), C.c_int()
+    _check(lib().zkaes_msm_pair(_host(bases), C.c_size_t(_nbytes(bases) // 96), bytes(scal1), C.c_size_t(len(scal1) // 32), bytes(scal2), C.c_size_t(len(scal2) // 32), C.c_size_t(val_off2),
+                                1 if edwards else 0, out, C.byref(inf)))
+    return out.raw, bool(inf.value)
+
+
+def msm_table_pair(bases, scal1, off1, scal2, off2, window_bits, edwards=True):
+    """the same in table mode: window tables over ALL the bases (the stride), the vectors over the ranges starting at off1 and off2"""
+    out, inf = C.create_string_buffer(96), C.c_int()
+    _check(lib().zkaes_msm_table_pair(_host(bases), C.c_size_t(_nbytes(bases) // 96), bytes(scal1), C.c_size_t(len(scal1) // 32), C.c_size_t(off1), bytes(scal2), C.c_size_t(len(scal2) // 32),
+                                      C.c_size_t(off2), int(window_bits), 1 if edwards else 0, out, C.byref(inf)))
+    return out.raw, bool(inf.value)
+
+
+def msm_second_bases(bases, scalars, off, shift, window_bits=0):
+    """one digit pass, two base ranges (Edwards law): [sum scalars[i] bases[off + i], sum scalars[i] bases[off + shift + i]]; window_bits = 0: per-window buckets"""
+    out, inf = C.create_string_buffer(192), (C.c_int * 2)()
+    _check(lib().zkaes_msm_second_bases(_host(bases), C.c_size_t(_nbytes(bases) // 96), bytes(scalars), C.c_size_t(len(scalars) // 32), C.c_size_t(off), C.c_size_t(shift), int(window_bits), out, inf))
+    return [(out.raw[96 * i:96 * i + 96], bool(inf[i])) for i in range(2)]
+
+
 def msm_bench(curve_id, bases_bytes, scalars_bytes, reps=3):
     n = len(scalars_bytes) // 32
     t, a = C.c_double(), C.c_double()

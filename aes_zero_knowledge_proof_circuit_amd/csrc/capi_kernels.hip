@@ -2,6 +2,7 @@
 #include "../../include/zkaes.h"
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "hip_util.hpp"
 #include "marlin.hpp"
@@ -240,9 +241,157 @@ template <class Fr> void run_ntt_padded(const uint8_t *in, size_t in_len, size_t
     else zk::gpu::ntt<Fr>(b, a, in_len, lg, inverse != 0, s);
     zk::gpu::d2h(out, b, n * sizeof(Fr), s);
 }
+
+// ---- the MSM forms the PROVER calls (marlin.cpp), which zkaes_msm / zkaes_msm_table do not reach: class sums, two scalar vectors in one Pippenger instance, one prepared
+// state against two base arrays, and table mode over a sub-range of a longer table.  BLS12-377; EDWARDS selects the prover's law (Niels28 records on the twisted Edwards
+// model), otherwise Affine28 bases on the Weierstrass model.  Standard affine bases and Montgomery scalars in, as zkaes_msm takes them (tests/test_gpu_msm_forms.py).
+using MC = zk::Bls377;
+using MFq = zk::Fq377;
+using MFr = zk::Fr377;
+using MP = zk::Fq377P;
+constexpr size_t MSM_FORM_MAX = (size_t)1 << 26;       // bases per call (6 GB of standard affine points)
+template <bool EDWARDS> using MsmBase = typename std::conditional<EDWARDS, zk::Niels28<MP>, zk::Affine28<MP>>::type;
+template <bool EDWARDS> DevPtr<MsmBase<EDWARDS>> law_bases(const zk::Affine<MFq> *src, size_t n, zk::gpu::stream_t s) {
+    DevPtr<MsmBase<EDWARDS>> d(n ? n : 1);
+    if constexpr (EDWARDS) zk::gpu::convert_bases_te<MC>(d, src, n, s); else zk::gpu::convert_bases<MC>(d, src, n, s);
+    zk::gpu::sync(s);        // the caller may release `src` at once
+    return d;
+}
+DevPtr<zk::Affine<MFq>> upload_points(const uint8_t *host, size_t count, size_t room, zk::gpu::stream_t s) {
+    DevPtr<zk::Affine<MFq>> d(room ? room : 1);
+    zk::gpu::h2d(d, host, count * 96, s);
+    return d;
+}
+DevPtr<MFr> upload_scalars(const uint8_t *host, size_t count, zk::gpu::stream_t s) {
+    DevPtr<MFr> d(count ? count : 1);
+    zk::gpu::h2d(d, host, count * 32, s);
+    return d;
+}
+void check_table_bits(int c, size_t stride, const char *who) {
+    if (c < 2 || c > 22) throw std::invalid_argument("window bits must be in [2, 22]");
+    need((uint64_t)zk::gpu::table_windows<MC>(c) * stride < (1ull << 30), who, "stride x table copies exceeds the 2^30 base indices of one MSM");
+}
+template <bool EDWARDS>
+void run_class_sum(const uint8_t *bases, size_t n, const int8_t *vals, int count, size_t prior, int *ok_out, uint8_t *out_xy, int *out_inf) {
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<zk::Affine<MFq>> db = upload_points(bases, n, n, s);
+    DevPtr<MsmBase<EDWARDS>> dl = law_bases<EDWARDS>(db, n, s);
+    db.reset();              // (a million points: give the standard-form copy back before the class sums grow their scratch)
+    DevPtr<int8_t> dv((size_t)count * n);
+    zk::gpu::h2d(dv, vals, (size_t)count * n, s);
+    WorkspaceGuard ws;
+    if (prior) {       // a generic MSM first: the class sums then carve their scratch from a bucket array that MSM sized (a prover context's second proof)
+        std::vector<MFr> sc(prior);
+        uint64_t x = 88172645463325252ull;
+        for (size_t i = 0; i < prior; i++) { for (int k = 0; k < 8; k += 2) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; sc[i].l[k] = (uint32_t)x; sc[i].l[k + 1] = (uint32_t)(x >> 32); } sc[i].l[7] &= 0x0fffffffu; }
+        DevPtr<MFr> ds = upload_scalars((const uint8_t *)sc.data(), prior, s);
+        zk::gpu::sync(s);
+        (void)zk::gpu::msm<MC>(ws, (const MsmBase<EDWARDS> *)dl.get(), (const MFr *)ds.get(), prior, s);
+    }
+    for (int v = 0; v < count; v++) {
+        zk::XYZZ<MFq> r;
+        const bool ok = zk::gpu::class_sum<MC>(ws, (const MsmBase<EDWARDS> *)dl.get(), (const int8_t *)dv.get() + (size_t)v * n, n, &r, s);
+        ok_out[v] = ok ? 1 : 0;
+        if (ok) give_affine(r.to_affine(), out_xy + 96 * (size_t)v, out_inf + v);
+        else { memset(out_xy + 96 * (size_t)v, 0, 96); out_inf[v] = 0; }
+    }
+}
+template <bool EDWARDS>
+void run_msm_pair(const uint8_t *bases, size_t nbases, const uint8_t *scal1, size_t n1, const uint8_t *scal2, size_t n2, size_t val_off2, uint8_t *out_xy, int *out_inf) {
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<zk::Affine<MFq>> db = upload_points(bases, nbases, nbases, s);
+    DevPtr<MsmBase<EDWARDS>> dl = law_bases<EDWARDS>(db, nbases, s);
+    DevPtr<MFr> d1 = upload_scalars(scal1, n1, s), d2 = upload_scalars(scal2, n2, s);
+    zk::gpu::sync(s);
+    WorkspaceGuard ws;
+    zk::gpu::msm_prepare<MC>(ws, d1, n1, n2 ? d2.get() : nullptr, n2, n2 ? val_off2 : 0, s);
+    give_affine(zk::gpu::msm_finish<MC>(ws, (const MsmBase<EDWARDS> *)dl.get(), s).to_affine(), out_xy, out_inf);
+}
+// window tables over all `stride` bases in the law's form: copy j at j * stride
+template <bool EDWARDS> DevPtr<MsmBase<EDWARDS>> law_tables(const uint8_t *bases, size_t stride, int c, zk::gpu::stream_t s) {
+    const size_t nt = (size_t)zk::gpu::table_windows<MC>(c);
+    DevPtr<zk::Affine<MFq>> tab = upload_points(bases, stride, nt * stride, s);
+    zk::gpu::build_window_tables<MC>(tab, stride, c, s);
+    return law_bases<EDWARDS>(tab, nt * stride, s);
+}
+template <bool EDWARDS>
+void run_msm_table_pair(const uint8_t *bases, size_t stride, const uint8_t *scal1, size_t n1, size_t off1, const uint8_t *scal2, size_t n2, size_t off2, int c, uint8_t *out_xy, int *out_inf) {
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<MsmBase<EDWARDS>> tabs = law_tables<EDWARDS>(bases, stride, c, s);
+    DevPtr<MFr> d1 = upload_scalars(scal1, n1, s), d2 = upload_scalars(scal2, n2, s);
+    zk::gpu::sync(s);
+    WorkspaceGuard ws;
+    zk::gpu::msm_prepare_table<MC>(ws, d1, n1, off1, n2 ? d2.get() : nullptr, n2, n2 ? off2 : 0, c, stride, s);
+    give_affine(zk::gpu::msm_finish<MC>(ws, (const MsmBase<EDWARDS> *)tabs.get(), s).to_affine(), out_xy, out_inf);
+}
+void run_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t n, size_t off, size_t shift, int c, uint8_t *out_xy, int *out_inf) {
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<MFr> ds = upload_scalars(scalars, n, s);
+    WorkspaceGuard ws;
+    zk::XYZZ<MFq> r[2];
+    if (c == 0) {
+        DevPtr<zk::Affine<MFq>> db = upload_points(bases, nbases, nbases, s);
+        DevPtr<zk::Niels28<MP>> dl = law_bases<true>(db, nbases, s);
+        zk::gpu::msm_prepare<MC>(ws, ds, n, nullptr, 0, 0, s);
+        zk::gpu::msm_finish2<MC>(ws, dl.get() + off, dl.get() + off + shift, r, s);
+    } else {
+        DevPtr<zk::Niels28<MP>> tabs = law_tables<true>(bases, nbases, c, s);
+        zk::gpu::msm_prepare_table<MC>(ws, ds, n, off, nullptr, 0, 0, c, nbases, s);
+        zk::gpu::msm_finish2<MC>(ws, tabs.get(), tabs.get() + shift, r, s);
+    }
+    for (int i = 0; i < 2; i++) give_affine(r[i].to_affine(), out_xy + 96 * i, out_inf + i);
+}
 }  // namespace
 
 extern "C" {
+// ---- kernel-level entry points of the MSM forms the prover calls (include/zkaes.h): every argument is checked before anything is allocated
+int zkaes_class_sum(const uint8_t *bases, size_t n, const int8_t *vals, int count, int edwards, size_t prior_msm_points, int *ok_out, uint8_t *out_xy, int *out_inf) {
+    return guardk([&] {
+        const char *who = "zkaes_class_sum";
+        need(count >= 1 && count <= 8, who, "1..8 value vectors");
+        need(bases && vals && ok_out && out_xy && out_inf, who, "null argument");
+        need(n >= 1 && n <= MSM_FORM_MAX, who, "n out of range");
+        need(prior_msm_points <= n, who, "the prior MSM runs over the same bases: at most n points");
+        if (edwards) run_class_sum<true>(bases, n, vals, count, prior_msm_points, ok_out, out_xy, out_inf);
+        else run_class_sum<false>(bases, n, vals, count, prior_msm_points, ok_out, out_xy, out_inf);
+    });
+}
+int zkaes_msm_pair(const uint8_t *bases, size_t nbases, const uint8_t *scal1, size_t n1, const uint8_t *scal2, size_t n2, size_t val_off2, int edwards, uint8_t *out_xy, int *out_inf) {
+    return guardk([&] {
+        const char *who = "zkaes_msm_pair";
+        need(out_xy && out_inf && (bases || !nbases) && (scal1 || !n1) && (scal2 || !n2), who, "null argument");
+        need(nbases <= MSM_FORM_MAX, who, "too many bases");
+        need(n1 <= nbases && val_off2 <= nbases && n2 <= nbases - val_off2, who, "range exceeds the bases");
+        if (edwards) run_msm_pair<true>(bases, nbases, scal1, n1, scal2, n2, val_off2, out_xy, out_inf);
+        else run_msm_pair<false>(bases, nbases, scal1, n1, scal2, n2, val_off2, out_xy, out_inf);
+    });
+}
+int zkaes_msm_table_pair(const uint8_t *bases, size_t stride, const uint8_t *scal1, size_t n1, size_t off1, const uint8_t *scal2, size_t n2, size_t off2, int window_bits, int edwards,
+                         uint8_t *out_xy, int *out_inf) {
+    return guardk([&] {
+        const char *who = "zkaes_msm_table_pair";
+        need(out_xy && out_inf && (bases || !stride) && (scal1 || !n1) && (scal2 || !n2), who, "null argument");
+        need(stride <= MSM_FORM_MAX, who, "too many bases");
+        check_table_bits(window_bits, stride, who);
+        if (off1 > stride || n1 > stride - off1 || off2 > stride || n2 > stride - off2) throw std::invalid_argument("msm_table: range exceeds the table");
+        if (edwards) run_msm_table_pair<true>(bases, stride, scal1, n1, off1, scal2, n2, off2, window_bits, out_xy, out_inf);
+        else run_msm_table_pair<false>(bases, stride, scal1, n1, off1, scal2, n2, off2, window_bits, out_xy, out_inf);
+    });
+}
+int zkaes_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t n, size_t off, size_t shift, int window_bits, uint8_t *out_xy, int *out_inf) {
+    return guardk([&] {
+        const char *who = "zkaes_msm_second_bases";
+        need(out_xy && out_inf && (bases || !nbases) && (scalars || !n), who, "null argument");
+        need(nbases <= MSM_FORM_MAX, who, "too many bases");
+        if (window_bits) check_table_bits(window_bits, nbases, who);
+        if (off > nbases || shift > nbases - off || n > nbases - off - shift) throw std::invalid_argument(window_bits ? "msm_table: range exceeds the table" : "zkaes_msm_second_bases: range exceeds the bases");
+        run_msm_second_bases(bases, nbases, scalars, n, off, shift, window_bits, out_xy, out_inf);
+    });
+}
 int zkaes_msm_sharded_plan(int curve_id, size_t n_total, int *window_bits, int *n_windows, size_t *bytes_per_rank) {
     return guardk([&] {
         int c = 0, w = 0;

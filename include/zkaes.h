@@ -376,6 +376,27 @@ int zkaes_ntt_padded(int field_id, const uint8_t *in, size_t in_len, size_t n, i
 /* the transform on the coset g D of a generator that need not be a root of unity: forward out[i] = p(g w^i) from the in_len coefficients (table of g^i riding on the first
  * pass), inverse the coefficients from such values (table of g^-i at the last store); n = 2 .. 2^28 */
 int zkaes_ntt_scaled(const uint8_t g[32], const uint8_t *in, size_t in_len, size_t n, int inverse, uint8_t *out);
+/* ---- the MSM forms the prover calls (csrc/marlin.cpp), none of which zkaes_msm / zkaes_msm_table reach; test and debug entry points (tests/test_gpu_msm_forms.py).
+ * BLS12-377 only.  bases: standard affine points (96 B each, Montgomery coordinates), scalars: Montgomery Fr (32 B each), as zkaes_msm takes them; every call converts the
+ * bases (and builds the window tables) on the device, allocates, copies and waits.  edwards != 0: the prover's law (twisted Edwards records; the bases MUST lie in the
+ * prime-order subgroup), 0: the Weierstrass law.  Results: affine x, y (96 B) + an infinity flag per point.  Null pointers, ranges outside the bases, a count outside
+ * 1..8 and window bits outside [2, 22] are refused before anything is allocated. */
+/* sum_i vals[v][i] * bases[i] for `count` (1..8) vectors of n int8 values (vals: count x n bytes), one after the other on ONE workspace and stream -- the Lagrange-basis
+ * commitments of w, z_A, z_B.  ok_out[v] = 1 and the sum in out_xy[v], out_inf[v] when class_sum accepted vector v; 0 (outputs zeroed) when it declined: a value outside
+ * [-2, 2], or on the Weierstrass law an addition of a point to itself or its negative inside a chunk.  prior_msm_points > 0 (<= n): a generic MSM over that many of the
+ * same bases runs on the workspace first, so that the class sums carve their scratch from a bucket array another MSM sized (a prover context's second proof). */
+int zkaes_class_sum(const uint8_t *bases, size_t n, const int8_t *vals, int count, int edwards, size_t prior_msm_points, int *ok_out, uint8_t *out_xy, int *out_inf);
+/* per-window Pippenger over TWO scalar vectors in one instance (the opening witness over plain + shifted powers): sum_i scal1[i] bases[i] + sum_j scal2[j] bases[val_off2 + j];
+ * n1 <= nbases, val_off2 + n2 <= nbases; either length may be 0 */
+int zkaes_msm_pair(const uint8_t *bases, size_t nbases, const uint8_t *scal1, size_t n1, const uint8_t *scal2, size_t n2, size_t val_off2, int edwards, uint8_t *out_xy, int *out_inf);
+/* the same in table mode over a table LONGER than the vectors: window tables of all `stride` bases, sum_i scal1[i] bases[off1 + i] + sum_j scal2[j] bases[off2 + j];
+ * off1 + n1 <= stride, off2 + n2 <= stride (else "msm_table: range exceeds the table"); n2 = 0 with off1 > 0 is the single-vector offset case */
+int zkaes_msm_table_pair(const uint8_t *bases, size_t stride, const uint8_t *scal1, size_t n1, size_t off1, const uint8_t *scal2, size_t n2, size_t off2, int window_bits, int edwards,
+                         uint8_t *out_xy, int *out_inf);
+/* ONE digit pass, two base ranges (a degree-bounded commitment: plain + shifted powers), Edwards law: out[0] = sum_i scalars[i] bases[off + i], out[1] = sum_i scalars[i]
+ * bases[off + shift + i]; off + shift + n <= nbases.  window_bits = 0: per-window buckets (sequential when the two sets of window sums exceed one reduction's 64),
+ * > 0: window tables of stride nbases.  out_xy: 2 x 96 B, out_inf: 2 flags */
+int zkaes_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t n, size_t off, size_t shift, int window_bits, uint8_t *out_xy, int *out_inf);
 /* TEST-ONLY: ONE field or curve operation of csrc/ff.cuh, ff28.cuh, ff29.cuh, ec28.cuh, te28.cuh per launch, on raw limbs exactly as the operation sees them (no conversion
  * in or out, so lazy and non-canonical operands can be passed).  op: an id of csrc/arith_probe.cuh ZK_PROBE_OPS (named by api.py ARITH_OPS, which also holds the words per
  * case); in: n_cases x input words, out: n_cases x output words; 1 <= n_cases <= 65536.  tests/test_gpu_arith.py compares it with the big-integer model. */
