@@ -948,6 +948,76 @@ def msm_second_bases(bases, scalars, off, shift, window_bits=0):
     return [(out.raw[96 * i:96 * i + 96], bool(inf[i])) for i in range(2)]
 
 
+# ---- TEST SURFACE, not product API: the prover's R1CS and randomness kernels, one entry per kernel group (include/zkaes.h; tests/test_gpu_r1cs.py).  Field elements are
+# 32-byte Montgomery limbs; a matrix is a CSR triple (rowptr uint32[rows + 1], col uint32[nnz], coeff int64[nnz]).  Arguments are passed on as they are: the C side refuses.
+def _csr(rowptr, col, coeff):
+    """C-contiguous arrays of the ABI's types (never empty, so that their pointers are valid); the caller keeps them alive"""
+    fix = lambda a, t: np.ascontiguousarray(a, dtype=t) if len(a) else np.zeros(1, dtype=t)
+    return fix(rowptr, np.uint32), fix(col, np.uint32), fix(coeff, np.int64)
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def spmv_bits(rowptr, col, coeff, rows, rows_out, z, want_small=True):
+    """(field sums: 32 rows_out bytes, int8 classes clamped to +-127 or None)"""
+    rp, cl, co = _csr(rowptr, col, coeff)
+    zz = np.ascontiguousarray(z, dtype=np.uint8)
+    out = C.create_string_buffer(32 * max(rows_out, 1))
+    small = np.zeros(max(rows_out, 1), dtype=np.int8) if want_small else None
+    _check(lib().zkaes_spmv_bits(_p(rp), _p(cl), _p(co), C.c_size_t(rows), C.c_size_t(rows_out), _p(zz) if len(zz) else None, C.c_size_t(len(zz)), out, _p(small) if want_small else None))
+    return out.raw[:32 * rows_out], (small[:rows_out] if want_small else None)
+
+
+def w_maps(z, n, m, num_witness, x_evals):
+    """(w_classes int8[n], w_evals, z_evals_h, bits_to_field(z, m)) for z = m instance bits then num_witness witness bits"""
+    zz = np.ascontiguousarray(z, dtype=np.uint8)
+    classes = np.zeros(max(n, 1), dtype=np.int8)
+    w, zh, xf = C.create_string_buffer(32 * max(n, 1)), C.create_string_buffer(32 * max(n, 1)), C.create_string_buffer(32 * max(m, 1))
+    _check(lib().zkaes_w_maps(_p(zz), C.c_size_t(n), C.c_size_t(m), C.c_size_t(num_witness), bytes(x_evals), _p(classes), w, zh, xf))
+    return classes[:n], w.raw[:32 * n], zh.raw[:32 * n], xf.raw[:32 * m]
+
+
+def t_evals(n, m, rows, mats, r_alpha, eta_a, eta_b, eta_c):
+    """mats = the CSR triples of A, B, C -> (t on H: 32 n bytes, {"nseg", "n_heavy", "max_segments"} of the tables built by the prover's own builder)"""
+    held = [_csr(*t) for t in mats]
+    ptrs = [(C.c_void_p * 3)(*[h[j].ctypes.data for h in held]) for j in range(3)]
+    out, stats = C.create_string_buffer(32 * max(n, 1)), (C.c_uint64 * 3)()
+    _check(lib().zkaes_t_evals(C.c_size_t(n), C.c_size_t(m), C.c_size_t(rows), ptrs[0], ptrs[1], ptrs[2], bytes(r_alpha), bytes(eta_a) + bytes(eta_b) + bytes(eta_c), out, stats))
+    return out.raw[:32 * n], dict(zip(("nseg", "n_heavy", "max_segments"), (int(x) for x in stats)))
+
+
+def lagrange_scalars(lg_n, lg_m, beta):
+    """(L_k(beta), the same over v_X(beta) and zero on X) on the domain of size 2^lg_n"""
+    size = 32 << lg_n if 0 <= lg_n <= 24 else 32
+    lag, lag_w = C.create_string_buffer(size), C.create_string_buffer(size)
+    _check(lib().zkaes_lagrange_scalars(int(lg_n), int(lg_m), bytes(beta), lag, lag_w))
+    return lag.raw, lag_w.raw
+
+
+def f_evals_from_tables(va, vb, vc, ea, eb, ec, ra, rb, ri, ci):
+    k, n = len(va) // 32, len(ra) // 32
+    ria, cia = np.ascontiguousarray(ri, dtype=np.uint32), np.ascontiguousarray(ci, dtype=np.uint32)
+    out = C.create_string_buffer(32 * max(k, 1))
+    _check(lib().zkaes_f_evals_from_tables(bytes(va), bytes(vb), bytes(vc), bytes(ea), bytes(eb), bytes(ec), bytes(ra), bytes(rb), _p(ria), _p(cia), C.c_size_t(k), C.c_size_t(n), out))
+    return out.raw[:32 * k]
+
+
+def chacha_field_stream(key_words, rounds, word_pos, count, max_cand=0):
+    """(count field elements as bytes, the stream position in words after the last accepted candidate)"""
+    key = (C.c_uint32 * 8)(*key_words)
+    out, nxt = C.create_string_buffer(32 * max(count, 1)), C.c_uint64()
+    _check(lib().zkaes_chacha_field_stream(key, int(rounds), C.c_uint64(word_pos), C.c_size_t(count), C.c_uint32(max_cand), out, C.byref(nxt)))
+    return out.raw[:32 * count], int(nxt.value)
+
+
+def mask_fixup(p, n):
+    buf = C.create_string_buffer(bytes(p), max(len(p), 1))
+    _check(lib().zkaes_mask_fixup(buf, C.c_size_t(n)))
+    return buf.raw[:len(p)]
+
+
 def msm_bench(curve_id, bases_bytes, scalars_bytes, reps=3):
     n = len(scalars_bytes) // 32
     t, a = C.c_double(), C.c_double()

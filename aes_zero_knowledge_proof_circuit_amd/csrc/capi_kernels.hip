@@ -6,6 +6,7 @@
 #include <vector>
 #include "hip_util.hpp"
 #include "marlin.hpp"
+#include "marlin_host.hpp"
 #include "te28.cuh"
 #include <algorithm>
 #include <chrono>
@@ -345,6 +346,32 @@ void run_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *sc
     }
     for (int i = 0; i < 2; i++) give_affine(r[i].to_affine(), out_xy + 96 * i, out_inf + i);
 }
+
+// ---- the prover's R1CS and randomness kernels (kernels_witness.hip, kernels_poly.hip), which run only inside whole proofs otherwise (tests/test_gpu_r1cs.py).  Every
+// output and scratch buffer is filled with 0xAB bytes on the device before the call, so that a slot a kernel fails to write shows up as a mismatch.
+template <class T> DevPtr<T> poisoned(size_t count, zk::gpu::stream_t s) {
+    DevPtr<T> d(count ? count : 1);
+    HIP_CHECK(hipMemsetAsync(d.get(), 0xAB, (count ? count : 1) * zk::gpu::DevElem<T>::bytes, (hipStream_t)s));
+    return d;
+}
+template <class T> DevPtr<T> upload_as(const T *host, size_t count, zk::gpu::stream_t s) {
+    DevPtr<T> d(count ? count : 1);
+    zk::gpu::h2d(d, host, count * sizeof(T), s);
+    return d;
+}
+constexpr size_t R1CS_MAX = (size_t)1 << 24;           // rows, columns, entries and elements a kernel-level R1CS call accepts
+// a CSR triple as the caller states it: rowptr[0] = 0, rowptr non-decreasing over rows + 1 entries, every column below ncols; returns the entry count
+size_t check_csr(const uint32_t *rowptr, const uint32_t *col, const int64_t *coeff, size_t rows, size_t ncols, const char *who) {
+    need(rowptr != nullptr, who, "null rowptr");
+    need(rowptr[0] == 0, who, "rowptr must start at 0");
+    for (size_t r = 0; r < rows; r++) need(rowptr[r] <= rowptr[r + 1], who, "rowptr must not decrease");
+    const size_t nnz = rowptr[rows];
+    need(nnz <= R1CS_MAX, who, "too many entries");
+    need(!nnz || (col && coeff), who, "null entries");
+    for (size_t i = 0; i < nnz; i++) need(col[i] < ncols, who, "column index out of range");
+    return nnz;
+}
+bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 }  // namespace
 
 extern "C" {
@@ -610,6 +637,147 @@ int zkaes_z_poly_from_w(const uint8_t *w, size_t wlen, const uint8_t *x_poly, ui
         DevPtr<PF> dw = upload(w, wlen, s), dx = upload(x_poly, m, s), dz(n + 1);
         zk::gpu::z_poly_from_w(dz, dw, wlen, dx, m, n, s);
         zk::gpu::d2h(zp, dz, (n + 1) * sizeof(PF), s);
+    });
+}
+// ---- kernel-level entry points of the prover's R1CS and randomness kernels (include/zkaes.h): every argument is checked before anything is allocated or launched
+int zkaes_spmv_bits(const uint32_t *rowptr, const uint32_t *col, const int64_t *coeff, size_t rows, size_t rows_out, const uint8_t *z, size_t ncols, uint8_t *out_field, int8_t *out_small_or_null) {
+    return guardk([&] {
+        const char *who = "zkaes_spmv_bits";
+        need(rows_out >= 1 && rows_out <= R1CS_MAX, who, "rows_out out of range");
+        need(rows <= rows_out, who, "rows must not exceed rows_out");
+        need(ncols <= R1CS_MAX, who, "too many columns");
+        need(out_field && (z || !ncols), who, "null argument");
+        const size_t nnz = check_csr(rowptr, col, coeff, rows, ncols, who);
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<uint32_t> drp = upload_as(rowptr, rows + 1, s), dcol = upload_as(col, nnz, s);
+        DevPtr<int64_t> dco = upload_as(coeff, nnz, s);
+        DevPtr<uint8_t> dz = upload_as(z, ncols, s);
+        DevPtr<PF> dout = poisoned<PF>(rows_out, s);
+        DevPtr<int8_t> dsmall = poisoned<int8_t>(rows_out, s);
+        zk::gpu::spmv_bits(dout, out_small_or_null ? dsmall.get() : nullptr, rows_out, drp, dcol, dco, rows, dz, s);
+        zk::gpu::d2h(out_field, dout, rows_out * sizeof(PF), s);
+        if (out_small_or_null) zk::gpu::d2h(out_small_or_null, dsmall, rows_out, s);
+    });
+}
+int zkaes_w_maps(const uint8_t *z, size_t n, size_t m, size_t num_witness, const uint8_t *x_evals, int8_t *out_classes, uint8_t *out_w_evals, uint8_t *out_z_evals_h, uint8_t *out_x_field) {
+    return guardk([&] {
+        const char *who = "zkaes_w_maps";
+        need(is_pow2(n) && is_pow2(m), who, "n and m must be powers of two");
+        need(n <= R1CS_MAX, who, "n out of range");
+        need(m < n, who, "m must be below n");
+        need(num_witness <= n - m, who, "num_witness must not exceed n - m");
+        need(z && x_evals && out_classes && out_w_evals && out_z_evals_h && out_x_field, who, "null argument");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<uint8_t> dz = upload_as(z, m + num_witness, s);
+        DevPtr<PF> dx = upload(x_evals, n, s), dw = poisoned<PF>(n, s), dzh = poisoned<PF>(n, s), dxf = poisoned<PF>(m, s);
+        DevPtr<int8_t> dcl = poisoned<int8_t>(n, s);
+        zk::gpu::w_classes(dcl, dz, (uint32_t)n, (uint32_t)m, (uint32_t)num_witness, s);
+        zk::gpu::w_evals(dw, dz, dx, (uint32_t)n, (uint32_t)m, (uint32_t)num_witness, s);
+        zk::gpu::z_evals_h(dzh, dz, (uint32_t)n, (uint32_t)m, (uint32_t)num_witness, s);
+        zk::gpu::bits_to_field(dxf, dz, m, s);
+        zk::gpu::d2h(out_classes, dcl, n, s);
+        zk::gpu::d2h(out_w_evals, dw, n * sizeof(PF), s);
+        zk::gpu::d2h(out_z_evals_h, dzh, n * sizeof(PF), s);
+        zk::gpu::d2h(out_x_field, dxf, m * sizeof(PF), s);
+    });
+}
+int zkaes_t_evals(size_t n, size_t m, size_t rows, const uint32_t *const rowptr[3], const uint32_t *const col[3], const int64_t *const coeff[3], const uint8_t *r_alpha,
+                  const uint8_t etas[96], uint8_t *out, uint64_t stats[3]) {
+    return guardk([&] {
+        const char *who = "zkaes_t_evals";
+        need(is_pow2(n) && is_pow2(m), who, "n and m must be powers of two");
+        need(n <= R1CS_MAX, who, "n out of range");
+        need(m < n, who, "m must be below n");
+        need(rows <= n, who, "rows must not exceed n");
+        need(rowptr && col && coeff && r_alpha && etas && out && stats, who, "null argument");
+        zk::CsrMatrix M[3];
+        size_t total = 0;
+        for (int q = 0; q < 3; q++) {
+            const size_t nnz = check_csr(rowptr[q], col[q], coeff[q], rows, n, who);
+            total += nnz;
+            M[q].rowptr.assign(rowptr[q], rowptr[q] + rows + 1);
+            if (nnz) { M[q].col.assign(col[q], col[q] + nnz); M[q].coeff.assign(coeff[q], coeff[q] + nnz); }
+        }
+        need(total <= R1CS_MAX, who, "too many entries");
+        PF eta[3];
+        for (int q = 0; q < 3; q++) eta[q] = load_f(etas + 32 * q, who);
+        const zk::hostx::TTables T = zk::hostx::build_t_tables(n, m, rows, M[0], M[1], M[2], zk::gpu::T_SEG, zk::gpu::T_HEAVY_SEGMENTS);       // the tables the prover's key holds
+        uint32_t widest = 0;
+        for (size_t h = 0; h < n; h++) widest = std::max(widest, T.col_seg_ptr[h + 1] - T.col_seg_ptr[h]);
+        stats[0] = T.nseg; stats[1] = T.n_heavy; stats[2] = widest;
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<uint32_t> dcsp = upload_as(T.col_seg_ptr.data(), T.col_seg_ptr.size(), s), dss = upload_as(T.seg_start.data(), T.seg_start.size(), s),
+                         dse = upload_as(T.seg_end.data(), T.seg_end.size(), s), dheavy = upload_as(T.heavy.data(), T.heavy.size(), s), drow = upload_as(T.trow.data(), T.trow.size(), s);
+        DevPtr<uint8_t> dmat = upload_as(T.tmat.data(), T.tmat.size(), s);
+        DevPtr<int64_t> dco = upload_as(T.tcoef.data(), T.tcoef.size(), s);
+        DevPtr<PF> dra = upload(r_alpha, n, s), dout = poisoned<PF>(n, s), dpartial = poisoned<PF>(T.nseg, s);
+        zk::gpu::t_evals(dout, (uint32_t)n, dpartial, T.nseg, dcsp, dss, dse, dheavy, T.n_heavy, drow, dmat, dco, dra, eta[0], eta[1], eta[2], s);
+        zk::gpu::d2h(out, dout, n * sizeof(PF), s);
+    });
+}
+int zkaes_lagrange_scalars(int lg_n, int lg_m, const uint8_t beta[32], uint8_t *out_lag, uint8_t *out_lag_w) {
+    return guardk([&] {
+        const char *who = "zkaes_lagrange_scalars";
+        need(lg_n >= 1 && lg_n <= FR377_TWO_ADICITY, who, "lg_n must be in [1, the field's 2-adicity]");
+        need(lg_m >= 0 && lg_m < lg_n, who, "lg_m must be in [0, lg_n)");
+        need(lg_n <= 24, who, "lg_n must not exceed 24");
+        need(out_lag && out_lag_w, who, "null argument");
+        const PF b = load_f(beta, who);
+        const size_t n = (size_t)1 << lg_n;
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dlag = poisoned<PF>(n, s), dlagw = poisoned<PF>(n, s);
+        zk::gpu::lagrange_scalars(dlag, dlagw, zk::gpu::domain_elements<zk::Fr377>(lg_n), b, (uint32_t)n, 1u << lg_m, s);
+        zk::gpu::d2h(out_lag, dlag, n * sizeof(PF), s);
+        zk::gpu::d2h(out_lag_w, dlagw, n * sizeof(PF), s);
+    });
+}
+int zkaes_f_evals_from_tables(const uint8_t *va, const uint8_t *vb, const uint8_t *vc, const uint8_t ea[32], const uint8_t eb[32], const uint8_t ec[32], const uint8_t *ra, const uint8_t *rb,
+                              const uint32_t *ri, const uint32_t *ci, size_t k, size_t n, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_f_evals_from_tables";
+        need(k >= 1 && k <= R1CS_MAX && n >= 1 && n <= R1CS_MAX, who, "k or n out of range");
+        need(va && vb && vc && ra && rb && ri && ci && out, who, "null argument");
+        const PF fa = load_f(ea, who), fb = load_f(eb, who), fc = load_f(ec, who);
+        for (size_t i = 0; i < k; i++) need(ri[i] < n && ci[i] < n, who, "index out of range");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dva = upload(va, k, s), dvb = upload(vb, k, s), dvc = upload(vc, k, s), dra = upload(ra, n, s), drb = upload(rb, n, s), dout = poisoned<PF>(k, s);
+        DevPtr<uint32_t> dri = upload_as(ri, k, s), dci = upload_as(ci, k, s);
+        zk::gpu::f_evals_from_tables(dout, dva, dvb, dvc, fa, fb, fc, dra, drb, dri, dci, k, s);
+        zk::gpu::d2h(out, dout, k * sizeof(PF), s);
+    });
+}
+int zkaes_chacha_field_stream(const uint32_t key_words[8], int rounds, uint64_t word_pos, size_t count, uint32_t max_cand, uint8_t *out, uint64_t *next_word_pos) {
+    return guardk([&] {
+        const char *who = "zkaes_chacha_field_stream";
+        need(key_words && next_word_pos && (out || !count), who, "null argument");
+        need(rounds == 8 || rounds == 12 || rounds == 20, who, "rounds must be 8, 12 or 20");
+        need(count <= R1CS_MAX, who, "count out of range");
+        need(word_pos <= ~(uint64_t)0 - 64 * (uint64_t)R1CS_MAX, who, "word_pos too close to the end of the stream");
+        zk::gpu::require_device();
+        StreamGuard s;
+        // chacha_field_stream: a batch has at most count / 0.58 * 1.02 + 4096 candidates of 8 words, its blocks, a flag and a position per candidate and 1 MB for the scan
+        const size_t ncand = 2 * count + 8192, scratch_bytes = (ncand * 8 / 16 + 4) * 64 + ncand * 8 + ((size_t)4 << 20);
+        DevPtr<void> scratch = poisoned<void>(scratch_bytes, s);
+        DevPtr<PF> dout = poisoned<PF>(count, s);
+        *next_word_pos = zk::gpu::chacha_field_stream(dout, count, key_words, rounds, word_pos, scratch, scratch_bytes, s, max_cand);
+        zk::gpu::d2h(out, dout, count * sizeof(PF), s);
+    });
+}
+int zkaes_mask_fixup(uint8_t *p, size_t n) {
+    return guardk([&] {
+        const char *who = "zkaes_mask_fixup";
+        need(n >= 1 && n <= R1CS_MAX, who, "n out of range");
+        need(p != nullptr, who, "null argument");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<PF> dp = upload(p, 3 * n, s);
+        zk::gpu::mask_fixup(dp, n, s);
+        zk::gpu::d2h(p, dp, 3 * n * sizeof(PF), s);
     });
 }
 int zkaes_ntt_padded(int field_id, const uint8_t *in, size_t in_len, size_t n, int inverse, int coset_c, int lg_big, uint8_t *out) {

@@ -289,7 +289,9 @@ void t_evals(F *out, uint32_t n, F *partial, uint32_t nseg, const uint32_t *col_
 // counter, word stream) positioned at word `word_pos`: 8 words per candidate, top bits shaved, candidates >= p rejected, limbs used AS the
 // Montgomery form.  Candidates are generated and filtered in parallel (flag + exclusive scan + compaction).  Returns the stream position
 // (in words) after the last accepted candidate so the host RNG can continue from there.  scratch: >= 2.2 * count * 9 words.
-uint64_t chacha_field_stream(F *out, size_t count, const uint32_t key[8], int rounds, uint64_t word_pos, void *scratch, size_t scratch_bytes, stream_t s);
+// max_cand = 0: one batch sized to hold `count` accepted candidates (a second one only if it falls short); > 0 caps the candidates per batch (the kernel-level tests
+// pass it to run the refill branch; the prover does not)
+uint64_t chacha_field_stream(F *out, size_t count, const uint32_t key[8], int rounds, uint64_t word_pos, void *scratch, size_t scratch_bytes, stream_t s, uint32_t max_cand = 0);
 // mask-polynomial fix-up of ark-marlin: p[0] -= p[0] + p[n] + p[2n]
 void mask_fixup(F *p, size_t n, stream_t s);
 // Round 2 on cosets of H (marlin.cpp second round): out[i] = r[i] (eta_a A + eta_b B + eta_c A B) - t[i] Z with A = za[i] + ca, B = zb[i] + cb, Z = z[i] + cz (the constants are

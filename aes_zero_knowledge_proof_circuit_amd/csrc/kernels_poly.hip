@@ -554,7 +554,7 @@ __global__ void k_rand_compact(const uint32_t *__restrict__ words, uint32_t word
     out[q] = v;
     if (q + 1 == count) *last_cand = j;
 }
-uint64_t chacha_field_stream(F *out, size_t count, const uint32_t key[8], int rounds, uint64_t word_pos, void *scratch, size_t scratch_bytes, stream_t s_) {
+uint64_t chacha_field_stream(F *out, size_t count, const uint32_t key[8], int rounds, uint64_t word_pos, void *scratch, size_t scratch_bytes, stream_t s_, uint32_t max_cand) {
     hipStream_t s = (hipStream_t)s_;
     if (count == 0) return word_pos;
     // acceptance probability p / 2^BITS; oversample, and loop in the (practically impossible) case the batch falls short
@@ -564,6 +564,7 @@ uint64_t chacha_field_stream(F *out, size_t count, const uint32_t key[8], int ro
     while (done < count) {
         size_t want = count - done;
         uint32_t ncand = (uint32_t)((double)want / accept * 1.02) + 4096;
+        if (max_cand && ncand > max_cand) ncand = max_cand;        // (tests only: small batches, so that the refill branch below runs)
         uint64_t first_block = pos_words / 16;
         uint32_t word_off = (uint32_t)(pos_words % 16);
         uint32_t nblocks = (uint32_t)(((uint64_t)word_off + 8ull * ncand + 15) / 16);

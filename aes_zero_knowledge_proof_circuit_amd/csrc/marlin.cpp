@@ -577,37 +577,12 @@ void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lit
     d_a_coeff = upload(c.A.coeff.empty() ? std::vector<int64_t>{0} : c.A.coeff, stream);
     d_b_rowptr = upload(c.B.rowptr, stream); d_b_col = upload(c.B.col.empty() ? std::vector<uint32_t>{0} : c.B.col, stream);
     d_b_coeff = upload(c.B.coeff.empty() ? std::vector<int64_t>{0} : c.B.coeff, stream);
-    {   // column-bucketed copy of A, B, C for the round-2 t accumulation (calculate_t)
-        std::vector<uint32_t> colptr(n + 1, 0), trow;
-        std::vector<uint8_t> tmat;
-        std::vector<int64_t> tcoef;
-        const CsrMatrix *M[3] = {&c.A, &c.B, &c.C};
-        for (int q = 0; q < 3; q++) for (uint32_t col : M[q]->col) colptr[reindex_by_subdomain(n, m, col) + 1]++;
-        for (size_t i = 0; i < n; i++) colptr[i + 1] += colptr[i];
-        size_t total = colptr[n];
-        trow.resize(total ? total : 1); tmat.resize(total ? total : 1); tcoef.resize(total ? total : 1);
-        std::vector<uint32_t> fill(colptr.begin(), colptr.end() - 1);
-        for (int q = 0; q < 3; q++)
-            for (size_t r = 0; r < rows; r++)
-                for (uint32_t i = M[q]->rowptr[r]; i < M[q]->rowptr[r + 1]; i++) {
-                    uint32_t pos = fill[reindex_by_subdomain(n, m, M[q]->col[i])]++;
-                    trow[pos] = (uint32_t)r; tmat[pos] = (uint8_t)q; tcoef[pos] = M[q]->coeff[i];
-                }
-        std::vector<uint32_t> col_seg_ptr(n + 1, 0), seg_start, seg_end;
-        for (size_t h = 0; h < n; h++) {
-            for (uint32_t st = colptr[h]; st < colptr[h + 1]; st += gpu::T_SEG) { seg_start.push_back(st); seg_end.push_back(std::min(st + gpu::T_SEG, colptr[h + 1])); }
-            col_seg_ptr[h + 1] = (uint32_t)seg_start.size();
-        }
-        t_nseg = (uint32_t)seg_start.size();
-        std::vector<uint32_t> heavy;
-        for (size_t h = 0; h < n; h++) if (col_seg_ptr[h + 1] - col_seg_ptr[h] > gpu::T_HEAVY_SEGMENTS) heavy.push_back((uint32_t)h);
-        t_nheavy = (uint32_t)heavy.size();
-        if (heavy.empty()) heavy.push_back(0);
-        d_t_heavy = upload(heavy, stream);
-        if (seg_start.empty()) { seg_start.push_back(0); seg_end.push_back(0); }
-        d_t_colptr = upload(col_seg_ptr, stream); d_t_seg_start = upload(seg_start, stream); d_t_seg_end = upload(seg_end, stream);
-        d_t_row = upload(trow, stream); d_t_mat = upload(tmat, stream); d_t_coeff = upload(tcoef, stream);
-
+    {   // column-bucketed copy of A, B, C for the round-2 t accumulation (calculate_t): marlin_host.hpp build_t_tables
+        const TTables T = build_t_tables(n, m, rows, c.A, c.B, c.C, gpu::T_SEG, gpu::T_HEAVY_SEGMENTS);
+        t_nseg = T.nseg; t_nheavy = T.n_heavy;
+        d_t_heavy = upload(T.heavy, stream);
+        d_t_colptr = upload(T.col_seg_ptr, stream); d_t_seg_start = upload(T.seg_start, stream); d_t_seg_end = upload(T.seg_end, stream);
+        d_t_row = upload(T.trow, stream); d_t_mat = upload(T.tmat, stream); d_t_coeff = upload(T.tcoef, stream);
     }
     // ---- index polynomials on the GPU
     for (int i = 0; i < 6; i++) { ix_ev[i].alloc(k); ix_co[i].alloc(k); }

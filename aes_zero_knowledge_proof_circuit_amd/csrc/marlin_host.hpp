@@ -30,6 +30,46 @@ inline size_t ahp_max_degree(size_t nc, size_t nv, size_t nnz) {                
     size_t h = next_pow2(std::max(nc, nv)), k = next_pow2(nnz);
     return std::max({2 * h - 1, 3 * h - 1, h, 3 * k - 3});
 }
+// Column-bucketed copy of A, B, C for the round-2 t accumulation (calculate_t; gpu.hpp t_evals): entry e of column bucket h = reindex_by_subdomain(n, m, col) sits at
+// colptr[h] <= e < colptr[h + 1] with its row, its matrix (0 / 1 / 2 = A / B / C) and its coefficient; every bucket is cut into segments of at most t_seg entries
+// (seg_start / seg_end, segments col_seg_ptr[h] .. col_seg_ptr[h + 1] of column h); heavy = the columns with MORE than t_heavy_segments segments.  The arrays the device
+// reads are never empty: trow / tmat / tcoef, seg_start / seg_end and heavy hold one dummy element when there is nothing to hold (nseg and n_heavy count the real ones).
+// t_seg, t_heavy_segments: gpu.hpp's T_SEG, T_HEAVY_SEGMENTS (arguments, so that this header stays free of device headers).  The prover's key constructor and the
+// kernel-level test entry zkaes_t_evals both build their tables here.
+struct TTables {
+    std::vector<uint32_t> colptr, trow;
+    std::vector<uint8_t> tmat;
+    std::vector<int64_t> tcoef;
+    std::vector<uint32_t> col_seg_ptr, seg_start, seg_end, heavy;
+    uint32_t nseg = 0, n_heavy = 0;
+};
+inline TTables build_t_tables(size_t n, size_t m, size_t rows, const CsrMatrix &A, const CsrMatrix &B, const CsrMatrix &C, uint32_t t_seg, uint32_t t_heavy_segments) {
+    TTables T;
+    T.colptr.assign(n + 1, 0);
+    const CsrMatrix *M[3] = {&A, &B, &C};
+    for (int q = 0; q < 3; q++) for (uint32_t col : M[q]->col) T.colptr[reindex_by_subdomain(n, m, col) + 1]++;
+    for (size_t i = 0; i < n; i++) T.colptr[i + 1] += T.colptr[i];
+    size_t total = T.colptr[n];
+    T.trow.resize(total ? total : 1); T.tmat.resize(total ? total : 1); T.tcoef.resize(total ? total : 1);
+    std::vector<uint32_t> fill(T.colptr.begin(), T.colptr.end() - 1);
+    for (int q = 0; q < 3; q++)
+        for (size_t r = 0; r < rows; r++)
+            for (uint32_t i = M[q]->rowptr[r]; i < M[q]->rowptr[r + 1]; i++) {
+                uint32_t pos = fill[reindex_by_subdomain(n, m, M[q]->col[i])]++;
+                T.trow[pos] = (uint32_t)r; T.tmat[pos] = (uint8_t)q; T.tcoef[pos] = M[q]->coeff[i];
+            }
+    T.col_seg_ptr.assign(n + 1, 0);
+    for (size_t h = 0; h < n; h++) {
+        for (uint32_t st = T.colptr[h]; st < T.colptr[h + 1]; st += t_seg) { T.seg_start.push_back(st); T.seg_end.push_back(std::min(st + t_seg, T.colptr[h + 1])); }
+        T.col_seg_ptr[h + 1] = (uint32_t)T.seg_start.size();
+    }
+    T.nseg = (uint32_t)T.seg_start.size();
+    for (size_t h = 0; h < n; h++) if (T.col_seg_ptr[h + 1] - T.col_seg_ptr[h] > t_heavy_segments) T.heavy.push_back((uint32_t)h);
+    T.n_heavy = (uint32_t)T.heavy.size();
+    if (T.heavy.empty()) T.heavy.push_back(0);
+    if (T.seg_start.empty()) { T.seg_start.push_back(0); T.seg_end.push_back(0); }
+    return T;
+}
 inline G1A mul_affine(const G1A &p, const Fr &k) { return mul_fr(XYZZ<Fq377>::from_affine(p), k).to_affine(); }
 
 // Host-side fixed-base scalar multiplication for the handful of points every proof multiplies by fresh blinding scalars (gamma_g powers for the

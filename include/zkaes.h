@@ -397,6 +397,35 @@ int zkaes_msm_table_pair(const uint8_t *bases, size_t stride, const uint8_t *sca
  * bases[off + shift + i]; off + shift + n <= nbases.  window_bits = 0: per-window buckets (sequential when the two sets of window sums exceed one reduction's 64),
  * > 0: window tables of stride nbases.  out_xy: 2 x 96 B, out_inf: 2 flags */
 int zkaes_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t n, size_t off, size_t shift, int window_bits, uint8_t *out_xy, int *out_inf);
+/* ---- kernel-level entry points of the prover's R1CS and randomness kernels (csrc/kernels_witness.hip, csrc/kernels_poly.hip): TEST SURFACE, not product API -- the layer
+ * between the AES trace and the polynomials, which otherwise runs only inside whole proofs (tests/test_gpu_r1cs.py compares each with the big-integer model of
+ * tests/r1cs_model.py).  BLS12-377 Fr; field elements are 32-byte Montgomery limbs, canonical (< r), not checked one by one.  Every call uploads, launches, copies back and
+ * waits; every output and scratch buffer is filled with 0xAB bytes on the device first, so a slot a kernel does not write is visible.  All arguments are checked before
+ * anything is allocated or launched. */
+/* k_spmv_bits: out_field[r] = sum_i coeff[i] z[col[i]] over row r of the CSR triple (rowptr: rows + 1 entries from 0, non-decreasing; col[i] < ncols) for r < rows, zero for
+ * rows <= r < rows_out; out_small (rows_out int8, may be NULL) = the same sums clamped to [-127, 127].  z: ncols bytes, 0 or 1.  |sum| must stay below 2^62. */
+int zkaes_spmv_bits(const uint32_t *rowptr, const uint32_t *col, const int64_t *coeff, size_t rows, size_t rows_out, const uint8_t *z, size_t ncols, uint8_t *out_field, int8_t *out_small_or_null);
+/* the index map "position on H -> instance / witness variable" in its three kernels and k_bits_to_field: z = m instance bytes then num_witness witness bytes (0 / 1),
+ * x_evals = n elements.  out_classes (n int8) = w_classes, out_w_evals (n elements) = w_evals, out_z_evals_h (n elements) = z_evals_h, out_x_field (m elements) =
+ * bits_to_field(z, m).  n, m powers of two, m < n, num_witness <= n - m. */
+int zkaes_w_maps(const uint8_t *z, size_t n, size_t m, size_t num_witness, const uint8_t *x_evals, int8_t *out_classes, uint8_t *out_w_evals, uint8_t *out_z_evals_h, uint8_t *out_x_field);
+/* round 2's t on H: the matrices A, B, C (index 0, 1, 2 of the three arrays; CSR triples of `rows` rows, columns < n) go through the SAME table builder as a proving key
+ * (csrc/marlin_host.hpp build_t_tables), then k_t_partials / k_t_columns / k_t_heavy.  out[h] = sum over entries of column reindex(h) of eta_M coeff r_alpha[row]
+ * (r_alpha: n elements, etas: eta_a, eta_b, eta_c).  stats = {segments, heavy columns, the largest segment count of one column} of the tables built. */
+int zkaes_t_evals(size_t n, size_t m, size_t rows, const uint32_t *const rowptr[3], const uint32_t *const col[3], const int64_t *const coeff[3], const uint8_t *r_alpha,
+                  const uint8_t etas[96], uint8_t *out, uint64_t stats[3]);
+/* lagrange_scalars: out_lag[k] = L_k(beta) on the domain of size 2^lg_n, out_lag_w[k] = 0 at the multiples of 2^(lg_n - lg_m), else L_k(beta) / (beta^(2^lg_m) - 1).
+ * 0 <= lg_m < lg_n <= 24.  beta^(2^lg_m) = 1 is outside the contract of out_lag_w (the inverse of zero is taken). */
+int zkaes_lagrange_scalars(int lg_n, int lg_m, const uint8_t beta[32], uint8_t *out_lag, uint8_t *out_lag_w);
+/* k_f_from_tables: out[i] = (ea va[i] + eb vb[i] + ec vc[i]) rb[ci[i]] ra[ri[i]] for i < k; va, vb, vc: k elements, ra, rb: n elements, ri[i], ci[i] < n */
+int zkaes_f_evals_from_tables(const uint8_t *va, const uint8_t *vb, const uint8_t *vc, const uint8_t ea[32], const uint8_t eb[32], const uint8_t ec[32], const uint8_t *ra, const uint8_t *rb,
+                              const uint32_t *ri, const uint32_t *ci, size_t k, size_t n, uint8_t *out);
+/* chacha_field_stream: `count` field elements drawn as ark-ff's Fp::rand draws them from the ChaCha word stream of `key_words` (rounds 8, 12 or 20; 64-bit block counter)
+ * from word `word_pos` on; *next_word_pos = the word after the last accepted candidate.  max_cand = 0: the prover's batch size; > 0: at most that many candidates per
+ * batch, so that the refill branch runs (the results must not depend on it). */
+int zkaes_chacha_field_stream(const uint32_t key_words[8], int rounds, uint64_t word_pos, size_t count, uint32_t max_cand, uint8_t *out, uint64_t *next_word_pos);
+/* k_mask_fixup, in place on 3 n elements: p[0] -= p[0] + p[n] + p[2n] */
+int zkaes_mask_fixup(uint8_t *p, size_t n);
 /* TEST-ONLY: ONE field or curve operation of csrc/ff.cuh, ff28.cuh, ff29.cuh, ec28.cuh, te28.cuh per launch, on raw limbs exactly as the operation sees them (no conversion
  * in or out, so lazy and non-canonical operands can be passed).  op: an id of csrc/arith_probe.cuh ZK_PROBE_OPS (named by api.py ARITH_OPS, which also holds the words per
  * case); in: n_cases x input words, out: n_cases x output words; 1 <= n_cases <= 65536.  tests/test_gpu_arith.py compares it with the big-integer model. */
