@@ -137,9 +137,118 @@ class ProvingKey:
         _check(lib().zkaes_pk_key_tag_blocks(self._p, C.byref(n)))
         return int(n.value)
 
+    def digest_info(self):
+        """{"kind": None | "chain" | "final", "prefix": P, "compressions": SHA-256 compressions per proof, "offset": the digest region's offset in a trace} of this key
+        (synthesize_keys(..., digest=, digest_prefix=)); zeros and None for a key without a digest"""
+        out = (C.c_uint64 * 4)()
+        _check(lib().zkaes_pk_digest_info(self._p, out))
+        return {"kind": _DIGEST_NAMES[int(out[0])], "prefix": int(out[1]), "compressions": int(out[2]), "offset": int(out[3])}
+
     def _message_bytes(self, header_bits):
-        """the key's plaintext length: the public input is One, header_bits bits of iv / counter, 8 bits per ciphertext byte, then 128 bits per key-tag block"""
-        return (self.info()["raw_instance"] - 1 - header_bits - 128 * self.key_tag_blocks()) // 8
+        """the key's plaintext length: the public input is One, header_bits bits of iv / counter, 8 bits per ciphertext byte, then 128 bits per key-tag block and, for a
+        key with a digest, the 512 bits of H_in and H_out"""
+        digest_bits = 512 if self.digest_info()["kind"] else 0
+        return (self.info()["raw_instance"] - 1 - header_bits - 128 * self.key_tag_blocks() - digest_bits) // 8
+
+    def _digest_header_bytes(self, header):
+        """how long the mode's public header is for this digest key, learned from the header itself: None or b"" (ECB), 16 bytes (CBC, CTR), 12 + aad (GCM); the library
+        checks it against the key"""
+        return b"" if header is None else bytes(header)
+
+    def witness_digest(self, message, secret_key, header=None, h_in=None):
+        """z (padded instance + witness, one byte per variable) of a digest key of any mode.  header: None for ECB, the iv (CBC) or initial counter block (CTR), iv + aad
+        for GCM; h_in: 32 bytes, None = SHA-256's initial value.  The last 512 instance bits are h_in and the H_out the device computed"""
+        self._need_key(secret_key)
+        if h_in is not None and len(h_in) != 32:
+            raise ZkAesError("h_in must be 32 bytes")
+        hdr = self._digest_header_bytes(header)
+        self._need_header(hdr)
+        n = C.c_size_t()
+        args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in))
+        _check(lib().zkaes_aes_witness_pd(*args, None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().zkaes_aes_witness_pd(*args, buf, n, C.byref(n)))
+        return buf.raw
+
+    def _need_header(self, hdr):
+        """the mode's header has the length this key reads from the pointer: the public input is One, the header bits, the ciphertext bits (one byte per message byte,
+        which the caller's message fixes), GCM's tag, the key tag, H_in and H_out -- so only 0, 16 or 12 + aad bytes can be right, and info() tells which"""
+        want = self.header_bytes()
+        if len(hdr) != want:
+            raise ZkAesError("this key's mode takes a public header of %d bytes" % want)
+
+    def header_bytes(self):
+        """the byte length of the public header a proof of this key's mode carries: 0 (ECB), 16 (CBC, CTR), 12 + aad (GCM)"""
+        return self.mode()[1]
+
+    def mode(self):
+        """(circuit kind, header bytes) of this key: CIRCUIT_AES .. CIRCUIT_AES_GCM or an ops kind, and the public header a proof of that mode carries"""
+        kind, n = C.c_int(), C.c_size_t()
+        _check(lib().zkaes_pk_mode(self._p, C.byref(kind), C.byref(n)))
+        return int(kind.value), int(n.value)
+
+    def encrypt_digest_batch(self, messages, secret_keys, headers=None, h_ins=None, zk_seed=None, first_proof_index=0):
+        """n independent proofs over a digest key of any mode -> (ciphertexts, gcm_tags, h_outs, proofs), four lists (gcm_tags holds None for every mode but GCM).
+        headers: None for ECB, else one per message (iv / initial counter block / iv + aad); h_ins: None (every proof starts from the initial value) or one 32-byte state
+        per message.  zk_seed and first_proof_index as encrypt_batch (None = a fresh OS seed for the call)"""
+        n = len(messages)
+        hb = self.header_bytes()
+        if headers is None:
+            headers = [b""] * n
+        if not (len(secret_keys) == len(headers) == n) or (h_ins is not None and len(h_ins) != n):
+            raise ZkAesError("one secret key, one header and one h_in per message")
+        kb = self.key_bytes()
+        if any(len(k) != kb for k in secret_keys) or any(len(h) != hb for h in headers):
+            raise ZkAesError("secret_key must be %d bytes and every header %d bytes" % (kb, hb))
+        if h_ins is not None and any(len(h) != 32 for h in h_ins):
+            raise ZkAesError("h_in must be 32 bytes")
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        mb, kbuf, hbuf = b"".join(bytes(m) for m in messages), b"".join(bytes(k) for k in secret_keys), b"".join(bytes(h) for h in headers)
+        cts, tags, outs = C.create_string_buffer(max(len(mb), 1)), C.create_string_buffer(max(16 * n, 1)), C.create_string_buffer(max(32 * n, 1))
+        lens = (C.c_size_t * max(n, 1))()
+        out, total = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_digest_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kbuf, C.c_size_t(len(kbuf)), hbuf or None, C.c_size_t(len(hbuf)),
+                                                          None if h_ins is None else b"".join(bytes(h) for h in h_ins), self._p, seed, C.c_uint64(first_proof_index), cts, tags, outs,
+                                                          C.byref(out), C.byref(total), lens))
+        blob = _take(out, total)
+        proofs, off = [], 0
+        for i in range(n):
+            proofs.append(blob[off:off + lens[i]])
+            off += lens[i]
+        size = len(mb) // n if n else 0
+        gcm = self.mode()[0] == CIRCUIT_AES_GCM
+        return ([cts.raw[size * i:size * (i + 1)] for i in range(n)], [tags.raw[16 * i:16 * i + 16] if gcm else None for i in range(n)],
+                [outs.raw[32 * i:32 * i + 32] for i in range(n)], proofs)
+
+    def encrypt_digest_chunked(self, message, secret_key, header=None, h_in=None, zk_seed=None, first_proof_index=0):
+        """chunk-proofs of one ECB, CBC or CTR message over a chain key -> (ciphertext, states, proofs): states is the list of the n + 1 SHA-256 states, states[0] = h_in
+        (None = the initial value), and chunk j is proven under (states[j], states[j + 1]).  header: None for ECB, the iv / initial counter block entering this call's
+        first chunk otherwise.  A job split over calls passes the previous call's last state as h_in.  zk_seed and first_proof_index as encrypt_chunked"""
+        self._need_key(secret_key)
+        if h_in is not None and len(h_in) != 32:
+            raise ZkAesError("h_in must be 32 bytes")
+        hdr = self._digest_header_bytes(header)
+        self._need_header(hdr)
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        chunk = self._message_bytes(8 * len(hdr))
+        if chunk == 0 or len(message) == 0 or len(message) % chunk:
+            raise ZkAesError("message length must be a non-zero multiple of the key's plaintext length (%d bytes)" % chunk)
+        n_chunks = len(message) // chunk
+        ct, states = C.create_string_buffer(len(message)), C.create_string_buffer(32 * (n_chunks + 1))
+        lens = (C.c_size_t * n_chunks)()
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_digest_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in), self._p, seed,
+                                                            C.c_uint64(first_proof_index), ct, states, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
+        blob = _take(out, n)
+        proofs, off = [], 0
+        for i in range(n_chunks):
+            proofs.append(blob[off:off + lens[i]])
+            off += lens[i]
+        return ct.raw[:len(message)], [states.raw[32 * j:32 * j + 32] for j in range(n_chunks + 1)], proofs
 
     def _need_key(self, secret_key, other=None, other_name=None, other_len=16):
         """the secret key has the length this proving key was synthesized for (and `other`, the iv / icb, its own): the library reads that many bytes from the pointer"""
@@ -404,18 +513,75 @@ def _tag_blocks(key_tag_blocks):
     return C.c_uint(int(key_tag_blocks))
 
 
-def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks=0):
+_DIGEST_NAMES = (None, "chain", "final")
+
+
+def _digest_args(digest, digest_prefix):
+    """(digest kind, digest prefix) as the C ABI takes them: digest = None, "chain" or "final" """
+    if digest not in _DIGEST_NAMES:
+        raise ZkAesError('digest must be None, "chain" or "final"')
+    if int(digest_prefix) < 0:
+        raise ZkAesError("digest_prefix must not be negative")
+    return C.c_uint(_DIGEST_NAMES.index(digest)), C.c_uint64(int(digest_prefix))
+
+
+def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks=0, digest=None, digest_prefix=0):
     pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib().zkaes_synthesize_keys_kt(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), C.c_size_t(plaintext_length), C.c_size_t(aad_length), C.c_size_t(srs[0]),
-                                          C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
+    _check(lib().zkaes_synthesize_keys_pd(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_size_t(plaintext_length),
+                                          C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
     return ProvingKey(pk.value), VerifyingKey(vk.value)
 
 
-def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0):
+def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
     """zk_aes::synthesize_keys (src/lib.rs:138-174) -> (ProvingKey, VerifyingKey).  flags: KEY_NO_TABLES.  key_bits: 128 (the reference's AES-128), 192 or 256 for
     the AES kinds; the proving key then takes secret keys of key_bits / 8 bytes (ProvingKey.key_bytes()).  key_tag_blocks: 0 (no key tag, the default), 1 or 2: every
-    proof of the key also exposes key_tag(secret_key, key_tag_blocks) as public input, and is checked with verify_chunked_tagged"""
-    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags, key_tag_blocks)
+    proof of the key also exposes key_tag(secret_key, key_tag_blocks) as public input, and is checked with verify_chunked_tagged.  digest: None (the
+    default), "chain" or "final": every proof of the key also proves the SHA-256 compressions of its hidden message from a public H_in to a public H_out -- "chain" over
+    the message's 64-byte blocks, "final" over the message with SHA-256's padding for digest_prefix + plaintext_length bytes -- is made through encrypt_digest_chunked /
+    encrypt_digest_batch and checked with verify_digest_chunked"""
+    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags, key_tag_blocks, digest, digest_prefix)
+
+
+def sha256_chain(data, h_in=None):
+    """SHA-256's compression function over data's 64-byte blocks from the state h_in (32 bytes; None = the initial value), no padding (zkaes_sha256_chain; no GPU) -> 32 bytes"""
+    if h_in is not None and len(h_in) != 32:
+        raise ZkAesError("h_in must be 32 bytes")
+    out = C.create_string_buffer(32)
+    _check(lib().zkaes_sha256_chain(None if h_in is None else bytes(h_in), bytes(data), C.c_size_t(len(data)), out))
+    return out.raw
+
+
+def sha256_finish(h_in, prefix_bytes, tail):
+    """the digest of a message whose first prefix_bytes bytes (a multiple of 64) led to the state h_in (None = the initial value) and which ends in `tail`
+    (zkaes_sha256_finish; no GPU): sha256_finish(None, 0, m) == hashlib.sha256(m).digest()"""
+    if h_in is not None and len(h_in) != 32:
+        raise ZkAesError("h_in must be 32 bytes")
+    out = C.create_string_buffer(32)
+    _check(lib().zkaes_sha256_finish(None if h_in is None else bytes(h_in), C.c_uint64(int(prefix_bytes)), bytes(tail), C.c_size_t(len(tail)), out))
+    return out.raw
+
+
+def verify_digest_chunked(verifying_key, circuit, proofs, ciphertext, states, header=None, key_tag=None):
+    """the chunk-proofs of one ECB, CBC or CTR job over a digest key against ONE array of states -> (list of bools, digest or None).  states: n + 1 states of 32 bytes;
+    chunk j is checked as verify_chunked_tagged checks it (without tag bits when key_tag is None), with states[j] and states[j + 1] behind.  The digest is
+    sha256_finish(states[-1], total bytes, b""): what the whole message hashes to if every chunk was accepted over a chain key from the initial value; None when a chunk
+    was rejected.  One proof is the lone form (states = [h_in, h_out]); for a lone proof of a FINAL key states[-1] is already the digest and the second value returned
+    is not meaningful"""
+    n = len(proofs)
+    if len(states) != n + 1 or any(len(st) != 32 for st in states):
+        raise ZkAesError("states must be one 32-byte state more than there are proofs")
+    if key_tag is not None and len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    if header is not None and len(header) != 16:
+        raise ZkAesError("iv / icb must be 16 bytes")
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each = (C.c_int * max(n, 1))()
+    ok = C.c_size_t()
+    _check(lib().zkaes_verify_digest_chunked(verifying_key._p, int(circuit), b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), None if header is None else bytes(header), bytes(ciphertext),
+                                             C.c_size_t(len(ciphertext)), None if key_tag is None else bytes(key_tag), C.c_size_t(0 if key_tag is None else len(key_tag)),
+                                             b"".join(bytes(st) for st in states), each, C.byref(ok)))
+    accepted = [bool(each[i]) for i in range(n)]
+    return accepted, (sha256_finish(states[-1], len(ciphertext), b"") if n and all(accepted) and len(ciphertext) % 64 == 0 else None)
 
 
 def key_tag(secret_key, blocks=2):
@@ -572,10 +738,11 @@ def _gcm_args(secret_key, iv, key_bytes=None):
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
 
 
-def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0):
+def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
     """(ProvingKey, VerifyingKey) for AES-GCM records of exactly plaintext_length message bytes (>= 1) and aad_length aad bytes (>= 0).  flags: KEY_NO_TABLES;
-    key_bits: 128, 192 or 256; key_tag_blocks: 0, 1 or 2 as synthesize_keys (records are then checked with verify_encryption_gcm_tagged)"""
-    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks)
+    key_bits: 128, 192 or 256; key_tag_blocks: 0, 1 or 2 as synthesize_keys (records are then checked with verify_encryption_gcm_tagged); digest and digest_prefix as
+    synthesize_keys (records are then made with encrypt_digest_batch and checked with verify_encryption_gcm_digest)"""
+    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks, digest, digest_prefix)
 
 
 def gcm_encrypt(message, secret_key, iv, aad=b""):
@@ -636,28 +803,47 @@ def verify_encryption_gcm_tagged(verifying_key, proof, iv, aad, ciphertext, tag,
     return bool(acc.value)
 
 
+def verify_encryption_gcm_digest(verifying_key, proof, iv, aad, ciphertext, tag, h_out, h_in=None, key_tag=None):
+    """verify_encryption_gcm for a key with a digest: the record against its GCM tag, the key tag (None for a key without tag blocks) and the SHA-256 states
+    (h_in, None = the initial value; h_out) of its hidden plaintext"""
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    if key_tag is not None and len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    if len(h_out) != 32 or (h_in is not None and len(h_in) != 32):
+        raise ZkAesError("h_in and h_out must be 32 bytes")
+    acc = C.c_int()
+    _check(lib().zkaes_verify_encryption_gcm_digest(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext),
+                                                    C.c_size_t(len(ciphertext)), bytes(tag), None if key_tag is None else bytes(key_tag), C.c_size_t(0 if key_tag is None else len(key_tag)),
+                                                    None if h_in is None else bytes(h_in), bytes(h_out), C.byref(acc)))
+    return bool(acc.value)
+
+
 def proof_roundtrip(proof):
     out, n = C.c_void_p(), C.c_size_t()
     _check(lib().zkaes_proof_roundtrip(bytes(proof), C.c_size_t(len(proof)), C.byref(out), C.byref(n)))
     return _take(out, n)
 
 
-def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128, key_tag_blocks=0):
-    """aad_length: GCM circuits only; key_bits: 128, 192 or 256 and key_tag_blocks: 0, 1 or 2 for the AES kinds"""
+def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
+    """aad_length: GCM circuits only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2 and digest: None, "chain" or "final" (with digest_prefix) for the AES kinds"""
     out = (C.c_uint64 * 12)()
-    _check(lib().zkaes_circuit_info_kt(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), C.c_size_t(plaintext_length), C.c_size_t(aad_length), out))
+    _check(lib().zkaes_circuit_info_pd(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_size_t(plaintext_length),
+                                       C.c_size_t(aad_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128, key_tag_blocks=0):
+def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    head = (int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
-    _check(lib().zkaes_circuit_matrix_kt(*head, C.byref(rows), C.byref(nnz), None, None, None))
+    head = (int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
+    _check(lib().zkaes_circuit_matrix_pd(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
     coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-    _check(lib().zkaes_circuit_matrix_kt(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
+    _check(lib().zkaes_circuit_matrix_pd(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 

@@ -10,13 +10,15 @@ extern "C" {
 void zkaes_pk_free(zkaes_pk *pk) { delete pk; }
 int zkaes_device_count(void) { return zk::gpu::device_count(); }
 
-static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128, size_t key_tag_blocks = 0) {
+static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128, size_t key_tag_blocks = 0,
+                      unsigned digest_kind = 0, uint64_t digest_prefix = 0) {
     return guard([&] {
         if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
         if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("synthesize_keys: key_bits must be 128, 192 or 256");
         if (key_tag_blocks > 2) throw std::invalid_argument("synthesize_keys: key_tag_blocks must be 0, 1 or 2");
+        if (digest_kind > 2) throw std::invalid_argument("synthesize_keys: digest_kind must be 0 (none), 1 (chain) or 2 (final)");
         zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
-        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len, key_bits, key_tag_blocks);
+        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix);
         zkaes_vk *v = new zkaes_vk{k->vk()};
         zkaes_pk *p = new zkaes_pk{std::move(k)};
         if (pk) *pk = p; else delete p;
@@ -39,6 +41,17 @@ int zkaes_pk_key_tag_blocks(const zkaes_pk *pk, size_t *n) {
     return guard([&] {
         if (!pk || !n) throw std::invalid_argument("null argument");
         *n = pk->pk->key_tag_blocks();
+    });
+}
+int zkaes_synthesize_keys_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz,
+                             unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+}
+int zkaes_pk_digest_info(const zkaes_pk *pk, uint64_t out[4]) {
+    return guard([&] {
+        if (!pk || !out) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        out[0] = (uint64_t)c.digest_kind; out[1] = c.digest_prefix; out[2] = c.digest_blocks; out[3] = c.digest_off;
     });
 }
 int zkaes_pk_key_bytes(const zkaes_pk *pk, size_t *n) {
@@ -225,6 +238,47 @@ int zkaes_aes_witness_gcm(const zkaes_pk *pk, const uint8_t *msg, size_t len, co
         auto v = pk->pk->aes_witness_gcm(msg, len, key, iv, aad, aad_len);
         if (z_len) *z_len = v.size();
         if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+    });
+}
+int zkaes_pk_mode(const zkaes_pk *pk, int *circuit_kind, size_t *header_bytes) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        if (circuit_kind) *circuit_kind = pk->pk->circuit().kind;
+        if (header_bytes) *header_bytes = zk::mode_header_bytes(pk->pk->circuit());
+    });
+}
+// ---- plaintext digests (include/zkaes.h): the prover side; zkaes_sha256_chain, zkaes_sha256_finish and the verifiers are in capi_host.cpp
+int zkaes_aes_witness_pd(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *z, size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        auto v = pk->pk->aes_witness_digest(msg, len, key, hdr, h_in);
+        if (z_len) *z_len = v.size();
+        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+    });
+}
+int zkaes_encrypt_digest_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                         const uint8_t *h_ins, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null,
+                                         uint8_t *h_outs_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || (n && (!messages || !secret_keys))) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (!c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
+        const size_t hb = zk::mode_header_bytes(c);
+        if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
+        if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
+        if (headers_len != n * hb || (n && hb && !headers)) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (the mode's public header)");
+        pack_proofs(pk->pk->prove_digest_batch(messages, secret_keys, hb ? headers : nullptr, h_ins, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null,
+                                               h_outs_or_null), proofs, proofs_len, proof_lens);
+    });
+}
+int zkaes_encrypt_digest_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, const zkaes_pk *pk, const uint8_t *zk_seed32,
+                                           uint64_t first_proof_index, uint8_t *ciphertext_or_null, uint8_t *states_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens,
+                                           size_t n_chunks) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || !key || !msg) throw std::invalid_argument("null argument");
+        const size_t chunk = pk->pk->circuit().message_bytes;
+        if (chunk == 0 || len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
+        pack_proofs(pk->pk->prove_digest_chunked(msg, len, key, hdr, h_in, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null, states_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *seed, uint8_t **proof, size_t *proof_len) {

@@ -5,7 +5,9 @@
 
 namespace {
 thread_local std::string g_err;
-zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0) { return zk::compile_circuit(kind, len, aad_len, key_bits, key_tag_blocks); }
+zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0) {
+    return zk::compile_circuit(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+}
 void require_key_len(size_t key_len) { if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes"); }
 // the CBC (and CTR) instance without the leading One: 128 bits of the IV (the initial counter block), then the ciphertext bits, each byte LSB first
 std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
@@ -298,6 +300,81 @@ int zkaes_verify_encryption_gcm_kt(const zkaes_vk *vk, const uint8_t *proof, siz
         *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
     });
 }
+// ---- plaintext digests (include/zkaes.h): SHA-256 on the host, and the verifiers that check every proof of a job against ONE array of states
+int zkaes_sha256_chain(const uint8_t *h_in, const uint8_t *data, size_t len, uint8_t h_out[32]) {
+    return guard([&] {
+        if (!h_out || (!data && len)) throw std::invalid_argument("null argument");
+        zk::sha256_chain(h_in, data, len, h_out);
+    });
+}
+int zkaes_sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *tail, size_t tail_len, uint8_t digest[32]) {
+    return guard([&] {
+        if (!digest || (!tail && tail_len)) throw std::invalid_argument("null argument");
+        zk::sha256_finish(h_in, prefix_bytes, tail, tail_len, digest);
+    });
+}
+namespace {
+void require_opt_key_tag(const uint8_t *key_tag, size_t key_tag_len) {
+    if (key_tag ? (key_tag_len != 16 && key_tag_len != 32) : key_tag_len != 0) throw std::invalid_argument("key_tag_len must be 16 or 32 with a key tag, 0 with NULL");
+}
+}  // namespace
+int zkaes_verify_digest_chunked(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len,
+                                const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t j = 0; j < n_chunks; j++) accepted_each[j] = 0;
+        if (!vk || !proofs || !proof_lens || !ct || !states) throw std::invalid_argument("null argument");
+        const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
+        if (!ecb && !cbc && !ctr) throw std::invalid_argument("verify_digest_chunked: circuit_kind must be ECB, CBC or CTR (GCM records go through zkaes_verify_encryption_gcm_digest)");
+        if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument("verify_digest_chunked: an iv or initial counter block for CBC and CTR, NULL for ECB");
+        require_opt_key_tag(key_tag, key_tag_len);
+        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument("verify_digest_chunked: the ciphertext must be n_chunks equal, non-empty slices");
+        const size_t chunk = ct_len / n_chunks;
+        if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument("verify_digest_chunked: every slice must be whole blocks (a lone CTR proof takes any length)");
+        if (!fits_key(vk->vk, (ecb ? 0 : 128) + 8 * chunk + 8 * key_tag_len + 512, "verify_digest_chunked")) return;      // every chunk rejected
+        size_t off = 0, ok = 0;
+        for (size_t j = 0; j < n_chunks; j++) {
+            int acc = 0;
+            try {
+                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
+                std::vector<zk::Fr> pub;
+                uint8_t counter[16];
+                if (cbc) append_bits(pub, j ? ct + chunk * j - 16 : iv_or_icb, 16);
+                if (ctr) { zk::ctr_counter_add(iv_or_icb, (uint64_t)j * (chunk / 16), counter); append_bits(pub, counter, 16); }
+                append_bits(pub, ct + chunk * j, chunk);
+                if (key_tag) append_bits(pub, key_tag, key_tag_len);
+                append_bits(pub, states + 32 * j, 64);                                               // states[j] is H_in, states[j + 1] H_out
+                acc = zk::verify(vk->vk, pub, p) ? 1 : 0;
+            } catch (const std::runtime_error &) { acc = 0; }
+            if (accepted_each) accepted_each[j] = acc;
+            ok += (size_t)acc;
+            off += proof_lens[j];
+        }
+        if (n_accepted) *n_accepted = ok;
+    });
+}
+int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len,
+                                       const uint8_t tag[16], const uint8_t *key_tag, size_t key_tag_len, const uint8_t *h_in, const uint8_t h_out[32], int *accepted) {
+    return guard([&] {
+        if (accepted) *accepted = 0;
+        if (!vk || !proof || !iv || !ct || !tag || !h_out || !accepted || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        require_opt_key_tag(key_tag, key_tag_len);
+        if (ct_len == 0) throw std::invalid_argument("GCM: the ciphertext must have at least one byte");
+        if (!fits_key(vk->vk, 224 + 8 * (aad_len + ct_len) + 8 * key_tag_len + 512, "GCM")) return;
+        zk::Proof p = zk::deserialize_proof(proof, proof_len);
+        uint8_t iv0[32];
+        zk::sha256_chain(nullptr, nullptr, 0, iv0);
+        std::vector<zk::Fr> pub;
+        append_bits(pub, iv, 12);
+        if (aad_len) append_bits(pub, aad, aad_len);
+        append_bits(pub, ct, ct_len);
+        append_bits(pub, tag, 16);
+        if (key_tag) append_bits(pub, key_tag, key_tag_len);
+        append_bits(pub, h_in ? h_in : iv0, 32);
+        append_bits(pub, h_out, 32);
+        *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
+    });
+}
 int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out, size_t *out_len) {
     return guard([&] { auto b = zk::serialize_proof(zk::deserialize_proof(proof, proof_len)); *out = give(b); *out_len = b.size(); });
 }
@@ -374,10 +451,13 @@ int zkaes_circuit_info_ks(int kind, unsigned key_bits, size_t len, size_t aad_le
 int zkaes_circuit_info_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, size_t len, size_t aad_len, uint64_t out[12]) {
     return guard([&] { fill_info(compile(kind, len, aad_len, key_bits, key_tag_blocks), out); });
 }
+int zkaes_circuit_info_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, uint64_t out[12]) {
+    return guard([&] { fill_info(compile(kind, len, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix), out); });
+}
 static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff, size_t key_bits = 128,
-                          size_t key_tag_blocks = 0) {
+                          size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0) {
     return guard([&] {
-        zk::Circuit c = compile(kind, len, aad_len, key_bits, key_tag_blocks);
+        zk::Circuit c = compile(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -395,6 +475,10 @@ int zkaes_circuit_matrix_ks(int kind, unsigned key_bits, size_t len, size_t aad_
 int zkaes_circuit_matrix_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col,
                             int64_t *coeff) {
     return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits, key_tag_blocks);
+}
+int zkaes_circuit_matrix_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, int which, uint64_t *n_rows,
+                            uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix);
 }
 int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(zk::CIRCUIT_AES_GCM, len, aad_len, which, n_rows, nnz, rowptr, col, coeff);

@@ -368,6 +368,114 @@ struct AesGates {
     }
 };
 
+// FIPS 180-4 4.2.2 and 5.3.3
+const uint32_t SHA256_K[64] = {
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+const uint32_t SHA256_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+
+// The SHA-256 compression function over the Builder's booleans.  A word is 32 Bits, bit i of weight 2^i; rotations and shifts are re-wirings.  Every xor and
+// select result is tagged with its bit of the compression's trace slot (trace_layout.h TRD_*).  An addition mod 2^32 of n words (a constant counts as one) is 32 allocated
+// result bits r_i, ceil(log2 n) allocated carry bits c_j and ONE row (sum_i 2^i operands - sum_i 2^i r_i - 2^32 sum_j 2^j c_j) * One = 0 with the difference in A, as in
+// the GHASH parity rows.  The carry widths are 1, 2, 3, 3 bits for n = 2, 4, 6, 7 operands: the operands' sum stays below n 2^32 <= 7 2^32 and the right-hand side below
+// 9 2^32, both far below the field's modulus r ~ 2^253, so the row holds over the integers, where result and carry of a sum are unique.  An addition whose operands are
+// all constants (the schedule of a block that holds padding only) is a constant and costs nothing.
+struct Sha256Gates {
+    Builder &b;
+    explicit Sha256Gates(Builder &b_) : b(b_) {}
+    static Word const_word(uint32_t v) { Word r; for (int i = 0; i < 32; i++) r[i] = Bit::konst((v >> i) & 1); return r; }
+    static Word rotr(const Word &x, int n) { Word r; for (int i = 0; i < 32; i++) r[i] = x[(i + n) % 32]; return r; }
+    static Word shr(const Word &x, int n) { Word r; for (int i = 0; i < 32; i++) r[i] = i + n < 32 ? x[i + n] : Bit::konst(false); return r; }
+    // word k of 4 big-endian bytes: bit i is bit i % 8 of byte 3 - i / 8
+    static Word be_word(const Byte *bytes) { Word r; for (int i = 0; i < 32; i++) r[i] = bytes[3 - i / 8][i % 8]; return r; }
+    Word xor_word(const Word &x, const Word &y, uint32_t off) {
+        Word r;
+        for (int i = 0; i < 32; i++) { uint32_t mark = b.n_witness; r[i] = b.bxor(x[i], y[i]); b.tag_bytebit(r[i], mark, off + (uint32_t)(i / 8), i % 8); }
+        return r;
+    }
+    Word select_word(const Word &c, const Word &t, const Word &f, uint32_t off) {
+        Word r;
+        for (int i = 0; i < 32; i++) { uint32_t mark = b.n_witness; r[i] = b.select(c[i], t[i], f[i]); b.tag_bytebit(r[i], mark, off + (uint32_t)(i / 8), i % 8); }
+        return r;
+    }
+    Word add(std::initializer_list<const Word *> ops, uint32_t konst, bool with_konst, int carry_bits, uint32_t off_r, uint32_t off_c) {
+        bool all_const = true;
+        for (const Word *w : ops) for (int i = 0; i < 32; i++) all_const = all_const && (*w)[i].is_const();
+        if (all_const) {
+            uint32_t v = with_konst ? konst : 0;
+            for (const Word *w : ops) for (int i = 0; i < 32; i++) if ((*w)[i].cval()) v += 1u << i;
+            return const_word(v);
+        }
+        LC d, one, z;
+        for (const Word *w : ops) for (int i = 0; i < 32; i++) d.add((int64_t)1 << i, (*w)[i]);
+        if (with_konst) d.add((int64_t)konst, 0u);
+        Word r;
+        for (int i = 0; i < 32; i++) { r[i] = b.alloc(false, off_r + (uint32_t)(i / 8), i % 8); d.add(-((int64_t)1 << i), r[i]); }
+        for (int j = 0; j < carry_bits; j++) d.add(-((int64_t)1 << (32 + j)), b.alloc(false, off_c, j));
+        one.add(1, 0u);
+        b.enforce(d, one, z);
+        return r;
+    }
+    // one compression from `st` (a .. h) over the block's 16 words, into the slot at trace offset `slot`; returns the feed-forward
+    std::array<Word, 8> compress(const std::array<Word, 8> &st, const std::array<Word, 16> &block, uint32_t slot) {
+        std::vector<Word> w(block.begin(), block.end());
+        w.resize(64);
+        for (int t = 16; t < 64; t++) {
+            const uint32_t e = slot + TRD_SCH + (uint32_t)(TRD_SCH_STRIDE * (t - 16));
+            const Word &x = w[t - 15], &y = w[t - 2];
+            Word s0 = xor_word(xor_word(rotr(x, 7), rotr(x, 18), e + TRD_SCH_S0X), shr(x, 3), e + TRD_SCH_S0);
+            Word s1 = xor_word(xor_word(rotr(y, 17), rotr(y, 19), e + TRD_SCH_S1X), shr(y, 10), e + TRD_SCH_S1);
+            w[t] = add({&s1, &w[t - 7], &s0, &w[t - 16]}, 0, false, 2, e + TRD_SCH_W, e + TRD_SCH_CARRY);
+        }
+        Word a = st[0], bb = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+        for (int t = 0; t < 64; t++) {
+            const uint32_t o = slot + TRD_RND + (uint32_t)(TRD_RND_STRIDE * t);
+            Word S1 = xor_word(xor_word(rotr(e, 6), rotr(e, 11), o + TRD_RND_S1X), rotr(e, 25), o + TRD_RND_S1);
+            Word ch = select_word(e, f, g, o + TRD_RND_CH);
+            Word S0 = xor_word(xor_word(rotr(a, 2), rotr(a, 13), o + TRD_RND_S0X), rotr(a, 22), o + TRD_RND_S0);
+            Word ab = xor_word(a, bb, o + TRD_RND_AB);
+            Word maj = select_word(ab, c, a, o + TRD_RND_MAJ);
+            Word e2 = add({&d, &h, &S1, &ch, &w[t]}, SHA256_K[t], true, 3, o + TRD_RND_E, o + TRD_RND_CE);
+            Word a2 = add({&h, &S1, &ch, &w[t], &S0, &maj}, SHA256_K[t], true, 3, o + TRD_RND_A, o + TRD_RND_CA);
+            h = g; g = f; f = e; e = e2; d = c; c = bb; bb = a; a = a2;
+        }
+        const Word out[8] = {a, bb, c, d, e, f, g, h};
+        std::array<Word, 8> r;
+        for (int k = 0; k < 8; k++) r[k] = add({&st[k], &out[k]}, 0, false, 1, slot + TRD_FF + 4 * (uint32_t)k, slot + TRD_FF + TRD_FF_CARRY + 4 * (uint32_t)k);
+        return r;
+    }
+    // The whole digest part of a key, behind everything else it emits: 256 inputs H_in, the compressions over msg (and, for a final key, the padding constants), 256
+    // inputs H_out equal to the last feed-forward.  Message word t of block j, bit i, is bit i % 8 of byte 64 j + 4 t + 3 - i / 8: a re-wiring of the message witnesses.
+    // `bytes` = the trace length ahead of the region; returns the length with it
+    size_t digest(const std::vector<Byte> &msg, int kind, uint64_t prefix, size_t bytes) {
+        const size_t len = msg.size(), nblk = TRD_BLOCKS(kind, len);
+        const uint32_t dg = (uint32_t)TRD(bytes);
+        std::vector<Byte> padded(msg);
+        if (kind == DIGEST_FINAL) {
+            padded.push_back(Builder::const_byte(0x80));
+            padded.resize(64 * nblk, Builder::const_byte(0));
+            const uint64_t bits = 8 * (prefix + (uint64_t)len);
+            for (int i = 0; i < 8; i++) padded[64 * nblk - 8 + i] = Builder::const_byte((uint8_t)(bits >> (56 - 8 * i)));
+        }
+        std::array<Byte, 32> hin;
+        for (int j = 0; j < 32; j++) hin[j] = b.alloc_byte(true, dg + TRD_HIN + (uint32_t)j);
+        std::array<Word, 8> st;
+        for (int k = 0; k < 8; k++) st[k] = be_word(&hin[4 * k]);
+        for (size_t j = 0; j < nblk; j++) {
+            std::array<Word, 16> block;
+            for (int t = 0; t < 16; t++) block[t] = be_word(&padded[64 * j + 4 * t]);
+            st = compress(st, block, dg + TRD_SLOT0 + (uint32_t)(j * TRD_SLOT_STRIDE));
+        }
+        for (int j = 0; j < 32; j++) {
+            Byte pi = b.alloc_byte(true, dg + TRD_HOUT + (uint32_t)j);
+            for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], st[j / 4][8 * (3 - j % 4) + k]);
+        }
+        return TRD_BYTES(bytes, kind, nblk);
+    }
+};
+
 }  // namespace
 
 namespace {
@@ -377,19 +485,31 @@ void require_key_bits(size_t key_bits) {
 void require_key_tag_blocks(size_t key_tag_blocks) {
     if (key_tag_blocks > 2) throw std::invalid_argument("key_tag_blocks must be 0, 1 or 2");
 }
-// finish() for a mode whose own trace takes mode_bytes: the key-tag blocks go behind it
-Circuit finish_aes(Builder &b, AesGates &g, int kind, size_t n_blocks, size_t mode_bytes, size_t key_tag_blocks) {
-    const size_t trace_bytes = g.key_tag(key_tag_blocks, mode_bytes);
+// what every AES compiler checks about its digest arguments before it emits a gate
+void require_digest(int digest_kind, uint64_t digest_prefix, size_t len) {
+    if (digest_kind != DIGEST_NONE && digest_kind != DIGEST_CHAIN && digest_kind != DIGEST_FINAL) throw std::invalid_argument("digest_kind must be 0 (none), 1 (chain) or 2 (final)");
+    if (digest_kind != DIGEST_FINAL && digest_prefix) throw std::invalid_argument("digest_prefix belongs to a final digest key only");
+    if (digest_kind == DIGEST_CHAIN && (len == 0 || len % 64)) throw std::invalid_argument("a chain digest key takes a message of a non-zero multiple of 64 bytes");
+    if (digest_kind == DIGEST_FINAL && (digest_prefix % 64 || digest_prefix >= ((uint64_t)1 << 61) || (uint64_t)len >= ((uint64_t)1 << 61) - digest_prefix))
+        throw std::invalid_argument("digest_prefix must be a multiple of 64 with digest_prefix + the message length below 2^61");
+}
+// finish() for a mode whose own trace takes mode_bytes: the key-tag blocks go behind it, the digest region behind them
+Circuit finish_aes(Builder &b, AesGates &g, int kind, size_t n_blocks, size_t mode_bytes, size_t key_tag_blocks, const std::vector<Byte> &msg, int digest_kind, uint64_t digest_prefix) {
+    size_t trace_bytes = g.key_tag(key_tag_blocks, mode_bytes);
+    const size_t digest_off = digest_kind ? TRD(trace_bytes) : 0;
+    if (digest_kind) { Sha256Gates sha(b); trace_bytes = sha.digest(msg, digest_kind, digest_prefix, trace_bytes); }
     Circuit c = finish(b, kind, n_blocks, trace_bytes, g.key_bytes());
     c.key_tag_blocks = key_tag_blocks; c.key_tag_off = key_tag_blocks ? TRK_KT(mode_bytes) : 0;
+    c.digest_kind = digest_kind; c.digest_prefix = digest_prefix; c.digest_blocks = TRD_BLOCKS(digest_kind, msg.size()); c.digest_off = digest_off;
     return c;
 }
 }  // namespace
 
-Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) {
+Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
     if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
+    require_digest(digest_kind, digest_prefix, len);
     size_t nb = len / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -401,15 +521,16 @@ Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) 
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = s[i];
     }
     g.ciphertext_inputs(ct);
-    return finish_aes(b, g, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), key_tag_blocks);
+    return finish_aes(b, g, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), key_tag_blocks, msg, digest_kind, digest_prefix);
 }
 
 // Gate order: message and key witnesses, the 16 IV bytes as inputs, the key schedule, per block the 128 xor gates of X_b = M_b ^ prev (prev = the IV bytes, then the
 // previous block's S_10) and the block's rounds from X_b, the ciphertext inputs.  The instance is One, 128 IV bits, 128 nb ciphertext bits.
-Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) {
+Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
     if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
+    require_digest(digest_kind, digest_prefix, len);
     size_t nb = len / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -426,7 +547,7 @@ Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = prev[i];
     }
     g.ciphertext_inputs(ct);
-    return finish_aes(b, g, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, key_tag_blocks);
+    return finish_aes(b, g, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, key_tag_blocks, msg, digest_kind, digest_prefix);
 }
 
 // Gate order: message and key witnesses, the 16 ICB bytes as inputs, the key schedule, per block (from the second on) the incrementer over the previous block's counter
@@ -434,10 +555,11 @@ Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
 // 128 ICB bits, 8 len ciphertext bits.
 // Incrementer: counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8.  c_0 = 1, y_i = x_i ^ c_i, c_{i+1} = x_i & c_i (none behind i = 127: the sum is mod 2^128).
 // Position 0 folds away (y_0 = !x_0, c_1 = x_0), which leaves 127 xor and 126 and gates per increment.
-Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_blocks) {
+Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
     if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
+    require_digest(digest_kind, digest_prefix, len);
     size_t nb = (len + 15) / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -472,7 +594,7 @@ Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
         Byte pi = b.alloc_byte(true, slot(i / 16) + TR_CTR_BL_CT + (uint32_t)(i % 16));
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
     }
-    Circuit c = finish_aes(b, g, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), key_tag_blocks);
+    Circuit c = finish_aes(b, g, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), key_tag_blocks, msg, digest_kind, digest_prefix);
     c.message_bytes = len;
     return c;
 }
@@ -486,9 +608,10 @@ Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
 // p_{i,k} = x_i & V_i[k] (16,384 and gates), then per output bit k a boolean y_k, seven booleans q_{k,0..6} and ONE row (sum_i p_{i,k} - y_k - 2 sum_j 2^j q_{k,j}) * One = 0:
 // y_k is the parity of the 128 products and q_k <= 64 their half.  The difference sits in A, as in enforce_equal, so A's row is 0 on a satisfied witness.  X_1 is the
 // first block itself; X_m = Y_{m-1} ^ block m costs one xor gate per existing bit (zero padding and the constant length block cost none).
-Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t key_tag_blocks) {
+Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
+    require_digest(digest_kind, digest_prefix, len);
     if (len == 0) throw std::invalid_argument("GCM: the message must have at least one byte");
     if (len > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM: message and aad of one proof are limited to 65536 bytes each");
     const size_t nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TR_GCM_MULS(na, nb);
@@ -564,17 +687,18 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
         Byte pi = b.alloc_byte(true, tag_off + (uint32_t)j);
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], tag[j][k]);
     }
-    Circuit c = finish_aes(b, g, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), key_tag_blocks);
+    Circuit c = finish_aes(b, g, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), key_tag_blocks, msg, digest_kind, digest_prefix);
     c.message_bytes = len; c.aad_bytes = alen;
     return c;
 }
 
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks) {
-    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks);
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
+    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
     if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
-    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks);
-    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits, key_tag_blocks);
-    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits, key_tag_blocks);
+    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    if (digest_kind || digest_prefix) throw std::invalid_argument("the ops circuits have no message: digest_kind must be 0");
     if (key_bits != 128) throw std::invalid_argument("the ops circuits have no AES key: key_bits must be 128");
     if (key_tag_blocks) throw std::invalid_argument("the ops circuits have no AES key: key_tag_blocks must be 0");
     return compile_ops_circuit(kind);
@@ -740,6 +864,58 @@ Circuit compile_ops_circuit(int kind) {
         b.enforce(z, z, lc);
     }
     return finish(b, kind, 0, 16);
+}
+
+namespace {
+inline uint32_t rotr32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+void sha256_compress(uint32_t st[8], const uint8_t blk[64]) {
+    uint32_t w[64];
+    for (int t = 0; t < 16; t++) w[t] = (uint32_t)blk[4 * t] << 24 | (uint32_t)blk[4 * t + 1] << 16 | (uint32_t)blk[4 * t + 2] << 8 | blk[4 * t + 3];
+    for (int t = 16; t < 64; t++) {
+        uint32_t s0 = rotr32(w[t - 15], 7) ^ rotr32(w[t - 15], 18) ^ (w[t - 15] >> 3), s1 = rotr32(w[t - 2], 17) ^ rotr32(w[t - 2], 19) ^ (w[t - 2] >> 10);
+        w[t] = s1 + w[t - 7] + s0 + w[t - 16];
+    }
+    uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+    for (int t = 0; t < 64; t++) {
+        uint32_t t1 = h + (rotr32(e, 6) ^ rotr32(e, 11) ^ rotr32(e, 25)) + ((e & f) ^ (~e & g)) + SHA256_K[t] + w[t];
+        uint32_t t2 = (rotr32(a, 2) ^ rotr32(a, 13) ^ rotr32(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+        h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+    }
+    st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+void sha256_load(uint32_t st[8], const uint8_t *h_in) {
+    for (int k = 0; k < 8; k++) st[k] = h_in ? (uint32_t)h_in[4 * k] << 24 | (uint32_t)h_in[4 * k + 1] << 16 | (uint32_t)h_in[4 * k + 2] << 8 | h_in[4 * k + 3] : SHA256_IV[k];
+}
+void sha256_store(const uint32_t st[8], uint8_t out[32]) { for (int k = 0; k < 8; k++) for (int i = 0; i < 4; i++) out[4 * k + i] = (uint8_t)(st[k] >> (24 - 8 * i)); }
+}  // namespace
+
+void sha256_chain(const uint8_t *h_in, const uint8_t *data, size_t len, uint8_t h_out[32]) {
+    if (len % 64) throw std::invalid_argument("sha256_chain: the data must be a multiple of 64 bytes");
+    uint32_t st[8];
+    sha256_load(st, h_in);
+    for (size_t off = 0; off < len; off += 64) sha256_compress(st, data + off);
+    sha256_store(st, h_out);
+}
+
+void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *tail, size_t tail_len, uint8_t digest[32]) {
+    if (prefix_bytes % 64 || prefix_bytes >= ((uint64_t)1 << 61) || (uint64_t)tail_len >= ((uint64_t)1 << 61) - prefix_bytes)
+        throw std::invalid_argument("sha256_finish: prefix_bytes must be a multiple of 64 with prefix_bytes + tail_len below 2^61");
+    uint32_t st[8];
+    sha256_load(st, h_in);
+    size_t off = 0;
+    for (; off + 64 <= tail_len; off += 64) sha256_compress(st, tail + off);
+    uint8_t blk[128] = {0};
+    const size_t rest = tail_len - off, n = rest + 9 <= 64 ? 64 : 128;
+    for (size_t i = 0; i < rest; i++) blk[i] = tail[off + i];
+    blk[rest] = 0x80;
+    const uint64_t bits = 8 * (prefix_bytes + (uint64_t)tail_len);
+    for (int i = 0; i < 8; i++) blk[n - 8 + i] = (uint8_t)(bits >> (56 - 8 * i));
+    for (size_t o = 0; o < n; o += 64) sha256_compress(st, blk + o);
+    sha256_store(st, digest);
+}
+
+size_t mode_header_bytes(const Circuit &c) {
+    return c.kind == CIRCUIT_AES_GCM ? 12 + c.aad_bytes : (c.kind == CIRCUIT_AES_CBC || c.kind == CIRCUIT_AES_CTR) ? 16 : 0;
 }
 
 }  // namespace zk

@@ -41,6 +41,10 @@ struct Circuit {
     size_t trace_bytes = 0;
     size_t key_tag_blocks = 0;           // T = 0, 1 or 2 key-tag blocks: the last 128 T instance bits are AES_K(D_0) (, AES_K(D_1))
     size_t key_tag_off = 0;              // trace offset of tag slot 0 (trace_layout.h TRK_KT), 0 when T = 0
+    int digest_kind = 0;                 // D = 0 (none), 1 (chain) or 2 (final): the last 512 instance bits are H_in, H_out of the SHA-256 compressions over the hidden message
+    uint64_t digest_prefix = 0;          // final keys: P, the message bytes hashed ahead of this proof's (a multiple of 64); the padding's length field is 8 (P + message_bytes)
+    size_t digest_blocks = 0;            // compressions per proof (trace_layout.h TRD_BLOCKS), 0 when D = 0
+    size_t digest_off = 0;               // trace offset of the digest region (trace_layout.h TRD), 0 when D = 0
     size_t num_variables() const { return num_instance + num_witness; }
 };
 
@@ -49,22 +53,34 @@ struct Circuit {
 // public input and the gate order inside a round, the schedule and each mode do not depend on it; the round count (Nk + 6) and the schedule (FIPS-197 5.2) do.
 // key_tag_blocks (every AES compiler, default 0 = the circuit as it was): T = 1 or 2 appends, behind everything the mode emits, per t < T the rounds of the constant block
 // D_t = "zkaes-keyta" || t || 00000000 under the same key and 128 public input bits equal to its S_Nr; anything but 0, 1, 2 is std::invalid_argument
-Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
+// digest_kind (every AES compiler, default DIGEST_NONE = the circuit as it was): DIGEST_CHAIN appends, behind the key tag, 256 inputs H_in, the SHA-256 compressions
+// (FIPS 180-4 6.2.2) of the hidden message's 64-byte blocks from H_in, and 256 inputs H_out equal to the last feed-forward; the message must then be a non-zero multiple
+// of 64 bytes.  DIGEST_FINAL does the same over message || 0x80 || zeros || be64(8 (digest_prefix + message_len)) for any message length the mode allows; digest_prefix
+// is a multiple of 64 with digest_prefix + message_len < 2^61, and 0 for the other kinds.  Anything else is std::invalid_argument
+enum DigestKind { DIGEST_NONE = 0, DIGEST_CHAIN = 1, DIGEST_FINAL = 2 };
+Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
 Circuit compile_ops_circuit(int kind);
 // AES-128-CBC over the same gadgets (no upstream counterpart; DESIGN.md "CBC"): public = 16 IV bytes then the ciphertext, private = message and key;
 // per block X_b = M_b ^ C_{b-1} (C_{-1} = IV) ahead of the block's round 0.  message_len must be a non-zero multiple of 16 (else std::invalid_argument)
-Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
+Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
 // AES-128-CTR over the same gadgets (DESIGN.md "CTR"): public = the 16 bytes of the initial counter block then the ciphertext, private = message and key;
 // CTR_0 = icb, CTR_b = CTR_{b-1} + 1 mod 2^128 (big-endian, SP 800-38A B.1 with m = 128), C_b = M_b ^ AES(key, CTR_b), the last block cut to the bytes that exist.
 // message_len is any byte count >= 1 (else std::invalid_argument)
-Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
+Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
 // AES-128-GCM (SP 800-38D, 96-bit IV, full tag; DESIGN.md "GCM"): public = iv (12 bytes), aad (aad_len bytes), ciphertext (message_len bytes), tag (16 bytes), private =
 // message and key.  The trace holds nb + 2 AES blocks (the message blocks under iv || be32(b + 2), H = AES_K(0), AES_K(iv || 1)), the V table of H and, per GHASH block,
 // one multiplication by H as 16,384 and gates and 128 parity rows.  message_len >= 1, aad_len >= 0; both are fixed by the key (else std::invalid_argument)
-Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128, size_t key_tag_blocks = 0);
+Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
-// 128 and key_tag_blocks 0 for the ops kinds
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0);
+// 128, key_tag_blocks 0 and digest_kind 0 for the ops kinds
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+// SHA-256 on the host (FIPS 180-4), for the verifier and the prover's chaining alike.  A state is 32 bytes, the eight words in big-endian serialisation; h_in = nullptr is
+// the initial value.  sha256_chain: h_out = the compressions of data's len / 64 blocks from h_in, no padding; len must be a multiple of 64 (else std::invalid_argument).
+// sha256_finish: digest = the chain from h_in over tail || 0x80 || zeros || be64(8 (prefix_bytes + tail_len)); prefix_bytes a multiple of 64, prefix_bytes + tail_len < 2^61
+void sha256_chain(const uint8_t *h_in, const uint8_t *data, size_t len, uint8_t h_out[32]);
+void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *tail, size_t tail_len, uint8_t digest[32]);
+// the bytes of the per-proof public header a key's mode takes ahead of a digest key's H_in: 0 (ECB), 16 (CBC, CTR), 12 + aad_bytes (GCM)
+size_t mode_header_bytes(const Circuit &c);
 // the key tag itself on the host: out = 16 tag_blocks bytes, AES_K(D_0) (|| AES_K(D_1)); key_len = 16, 24 or 32, tag_blocks = 1 or 2 (else std::invalid_argument)
 void aes_key_tag_host(const uint8_t *key, size_t key_len, size_t tag_blocks, uint8_t *out);
 // D_t, the constant block behind tag block t

@@ -266,6 +266,12 @@ void ghash_trace(uint8_t *trace, size_t trace_stride, uint32_t nproofs, uint32_t
 // alone; launched behind the mode's kernel(s) on the same stream, it writes bytes disjoint from theirs.  stride >= tag_off + tag_blocks block strides; stride, tag_off
 // and the trace 16-byte aligned
 void key_tag_trace(uint8_t *trace, size_t trace_stride, size_t tag_off, const uint8_t *keys, uint32_t nproofs, uint32_t tag_blocks, stream_t s, size_t key_bytes = 16);
+// Plaintext digests, any mode (kernels_digest.hip): fills the digest region of each proof's trace at digest_off (trace_layout.h TRD) -- H_in, H_out and one slot per
+// SHA-256 compression of the proof's message (digest_kind 1: the message's 64-byte blocks; 2: the message with SHA-256's padding for digest_prefix + msg_len bytes) --
+// from the messages and each proof's H_in, the 32 bytes at hin_off of its header (hdrs = nproofs x hdr_stride bytes).  Launched behind the mode's kernel(s) and the tag
+// kernel on the same stream, it writes bytes disjoint from theirs.  stride >= digest_off + 64 + compressions x 4032; stride, digest_off and the trace 16-byte aligned
+void sha256_trace(uint8_t *trace, size_t trace_stride, size_t digest_off, const uint8_t *msgs, const uint8_t *hdrs, size_t hdr_stride, size_t hin_off, uint32_t nproofs, size_t msg_len, int digest_kind,
+                  uint64_t digest_prefix, stream_t s);
 // z[col] (0/1 bytes) for every column, by descriptor
 void witness_expand(uint8_t *z, const uint32_t *desc, uint32_t ncols, const uint8_t *trace, const uint32_t *sbox_in_off, const uint32_t *sbox_tmpl, stream_t s);
 // out[r] = sum_i coeff[i] * z[col[i]] as a field element, rows with no entries give 0 (out has `rows_out` >= rows entries, tail zeroed)

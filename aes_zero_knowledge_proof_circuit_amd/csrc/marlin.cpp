@@ -328,7 +328,7 @@ class ProvingKeyImpl {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
         cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
-        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, 12 + c.aad_bytes));
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, 12 + c.aad_bytes) + (c.digest_kind ? 32 : 0));      // (a digest key's header carries H_in behind the mode's own)
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
@@ -486,7 +486,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -495,14 +495,14 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
     message_len = message_len_;
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
-    circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks);
+    circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
     const Circuit &c = circuit;
     // ---- joint matrix (sum_matrices): per-row sorted union of the A, B, C column supports
     size_t rows = c.num_constraints;
@@ -650,6 +650,14 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
     }
     // a key with key-tag blocks: the tag slots behind the mode's tail, from the key alone (bytes disjoint from those the kernels above write)
     if (c.key_tag_blocks) gpu::key_tag_trace(cx.d_trace, c.trace_bytes, c.key_tag_off, cx.d_key, 1, (uint32_t)c.key_tag_blocks, s, c.key_bytes);
+    // a key with a digest: the proof's header carries H_in behind the mode's own bytes; the digest region behind the tag slots, from the message and H_in alone
+    if (c.digest_kind) {
+        if (!iv) throw std::invalid_argument("a digest proving key needs a header that ends in H_in");
+        if (len != c.message_bytes) throw std::invalid_argument("a digest trace takes exactly the key's message length");
+        const size_t hb = mode_header_bytes(c);
+        gpu::h2d(cx.d_iv.p + hb, iv + hb, 32, s);
+        gpu::sha256_trace(cx.d_trace, c.trace_bytes, c.digest_off, cx.d_msg, cx.d_iv, hb + 32, hb, 1, c.message_bytes, c.digest_kind, c.digest_prefix, s);
+    }
 }
 
 void ProvingKeyImpl::prove_round1(ProofRun &R) {
@@ -981,7 +989,12 @@ void ProvingKey::msm_powers_partial_device(const uint8_t *scalars, size_t n_loca
     if (n_local) gpu::h2d(cx.acc.p, scalars, n_local * sizeof(F), cx.stream);
     gpu::msm_table_sum_device<Bls377>(cx.msm_ws, impl->d_powers, impl->srs_stride, offset, impl->table_c, cx.acc.p, n_local, (XYZZ<Fq377> *)dev_out, cx.stream);
 }
+// every entry point from before the digest keys: such a key's proofs carry H_in and H_out, which these calls have no argument for
+static void refuse_digest_key(const Circuit &c) {
+    if (c.digest_kind) throw std::invalid_argument("this proving key carries a plaintext digest: use the _digest_ entry points (zkaes_encrypt_digest_batch_seeded_at, zkaes_encrypt_digest_chunked_seeded_at, zkaes_aes_witness_pd)");
+}
 Proof ProvingKey::prove_aes(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t *zk_seed) {
+    refuse_digest_key(impl->circuit);
     if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
     if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
@@ -996,7 +1009,9 @@ std::string ProvingKey::op_lists_json(const uint8_t *message, size_t len, const 
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
     gpu::OpRecord rec;
     gpu::oplog_begin();
-    try { impl->prove(impl->context(0), nullptr, message, len, key, nullptr, throughput_path); }
+    uint8_t h_in[32];                                                              // an ECB key with a digest: its header is H_in alone; the recorded proof starts from the initial value
+    sha256_chain(nullptr, nullptr, 0, h_in);
+    try { impl->prove(impl->context(0), nullptr, message, len, key, nullptr, throughput_path, impl->circuit.digest_kind ? h_in : nullptr); }
     catch (...) { gpu::oplog_end(); throw; }
     rec = gpu::oplog_end();
     const Circuit &c = impl->circuit;
@@ -1023,6 +1038,7 @@ static std::vector<uint8_t> witness_of(ProvingKeyImpl *impl, const uint8_t *mess
     return z;
 }
 std::vector<uint8_t> ProvingKey::aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]) {
+    refuse_digest_key(impl->circuit);
     if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
     if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
@@ -1034,12 +1050,14 @@ static void require_cbc_key(const Circuit &c, size_t len) {
     if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
 }
 std::vector<uint8_t> ProvingKey::aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]) {
+    refuse_digest_key(impl->circuit);
     require_cbc_key(impl->circuit, len);
     if (!message || !key || !iv) throw std::invalid_argument("null argument");
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
     return witness_of(impl, message, len, key, iv);
 }
 Proof ProvingKey::prove_aes_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null) {
+    refuse_digest_key(impl->circuit);
     require_cbc_key(impl->circuit, len);
     if (!message || !key || !iv) throw std::invalid_argument("null argument");
     if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
@@ -1052,12 +1070,14 @@ static void require_ctr_key(const Circuit &c, const uint8_t *message, const uint
     if (!message || !key || !icb) throw std::invalid_argument("null argument");
 }
 std::vector<uint8_t> ProvingKey::aes_witness_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16]) {
+    refuse_digest_key(impl->circuit);
     const Circuit &c = impl->circuit;
     require_ctr_key(c, message, key, icb);
     if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
     return witness_of(impl, message, len, key, icb);
 }
 Proof ProvingKey::prove_aes_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null) {
+    refuse_digest_key(impl->circuit);
     const Circuit &c = impl->circuit;
     require_ctr_key(c, message, key, icb);
     if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
@@ -1116,18 +1136,21 @@ static std::vector<Proof> prove_many(ProvingKeyImpl *impl, const uint8_t *messag
     return proofs;
 }
 std::vector<Proof> ProvingKey::prove_aes_chunked(const uint8_t *message, size_t len, const uint8_t key[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
+    refuse_digest_key(impl->circuit);
     if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
     size_t chunk = impl->circuit.n_blocks * 16;
     if (chunk == 0 || len % chunk) throw std::invalid_argument("message length must be a multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
     return prove_many(impl, message, key, 0, len / chunk, n_contexts, zk_seed, index_offset, nullptr);
 }
 std::vector<Proof> ProvingKey::prove_aes_batch(const uint8_t *messages, const uint8_t *keys, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
+    refuse_digest_key(impl->circuit);
     if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
     if (impl->circuit.n_blocks == 0) throw std::invalid_argument("proving key has an empty plaintext");
     return prove_many(impl, messages, keys, impl->circuit.key_bytes, n, n_contexts, zk_seed, index_offset, nullptr);
 }
 std::vector<Proof> ProvingKey::prove_aes_cbc_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
                                                      uint8_t *ciphertext_or_null) {
+    refuse_digest_key(impl->circuit);
     require_cbc_key(impl->circuit, len);
     if (!message || !key || !iv) throw std::invalid_argument("null argument");
     size_t chunk = impl->circuit.n_blocks * 16;
@@ -1144,6 +1167,7 @@ std::vector<Proof> ProvingKey::prove_aes_cbc_chunked(const uint8_t *message, siz
 }
 std::vector<Proof> ProvingKey::prove_aes_ctr_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
                                                      uint8_t *ciphertext_or_null) {
+    refuse_digest_key(impl->circuit);
     const Circuit &c = impl->circuit;
     require_ctr_key(c, message, key, icb);
     size_t chunk = c.message_bytes;
@@ -1170,11 +1194,13 @@ static std::vector<uint8_t> gcm_header(const uint8_t iv[12], const uint8_t *aad,
     return h;
 }
 std::vector<uint8_t> ProvingKey::aes_witness_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len) {
+    refuse_digest_key(impl->circuit);
     require_gcm_key(impl->circuit, message, len, key, iv, aad, aad_len);
     return witness_of(impl, message, len, key, gcm_header(iv, aad, aad_len).data());
 }
 Proof ProvingKey::prove_aes_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *zk_seed,
                                 uint8_t *ciphertext_or_null, uint8_t *tag_or_null) {
+    refuse_digest_key(impl->circuit);
     require_gcm_key(impl->circuit, message, len, key, iv, aad, aad_len);
     if (ciphertext_or_null || tag_or_null) {
         std::vector<uint8_t> ct(len);
@@ -1187,6 +1213,7 @@ Proof ProvingKey::prove_aes_gcm(const uint8_t *message, size_t len, const uint8_
 }
 std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
                                                    uint8_t *ciphertexts_or_null, uint8_t *tags_or_null) {
+    refuse_digest_key(impl->circuit);
     const Circuit &c = impl->circuit;
     if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
     if (n && (!messages || !keys || !headers)) throw std::invalid_argument("null argument");
@@ -1201,6 +1228,85 @@ std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, cons
         }
     }
     return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, hs);
+}
+// ---- plaintext digests.  A proof's header is the mode's own bytes, then the 32 bytes of H_in
+static void require_digest_key(const Circuit &c) {
+    if (!c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
+}
+// the host's side of one proof: ciphertext (and GCM tag) by the key's mode, H_out by plain SHA-256
+static void digest_host_side(const Circuit &c, const uint8_t *msg, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *ct_or_null, uint8_t *tag_or_null, uint8_t *h_out_or_null) {
+    const size_t L = c.message_bytes;
+    if (ct_or_null || tag_or_null) {
+        std::vector<uint8_t> ct(L);
+        uint8_t tag[16];
+        if (c.kind == CIRCUIT_AES) aes_ecb_encrypt_host(msg, L, key, c.key_bytes, ct.data());
+        else if (c.kind == CIRCUIT_AES_CBC) aes128_cbc_encrypt_host(msg, L, key, hdr, ct.data(), c.key_bytes);
+        else if (c.kind == CIRCUIT_AES_CTR) aes128_ctr_crypt_host(msg, L, key, hdr, ct.data(), c.key_bytes);
+        else aes128_gcm_encrypt_host(msg, L, key, hdr, hdr + 12, c.aad_bytes, ct.data(), tag, c.key_bytes);
+        if (ct_or_null) memcpy(ct_or_null, ct.data(), L);
+        if (tag_or_null && c.kind == CIRCUIT_AES_GCM) memcpy(tag_or_null, tag, 16);
+    }
+    if (h_out_or_null) {
+        if (c.digest_kind == DIGEST_CHAIN) sha256_chain(h_in, msg, L, h_out_or_null);
+        else sha256_finish(h_in, c.digest_prefix, msg, L, h_out_or_null);
+    }
+}
+static void digest_header(const Circuit &c, const uint8_t *hdr, const uint8_t *h_in, uint8_t *out) {
+    const size_t hb = mode_header_bytes(c);
+    if (hb) memcpy(out, hdr, hb);
+    if (h_in) memcpy(out + hb, h_in, 32); else sha256_chain(nullptr, nullptr, 0, out + hb);        // (no blocks: the initial value)
+}
+std::vector<uint8_t> ProvingKey::aes_witness_digest(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in) {
+    const Circuit &c = impl->circuit;
+    require_digest_key(c);
+    if (!message || !key || (!hdr && mode_header_bytes(c))) throw std::invalid_argument("null argument");
+    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
+    std::vector<uint8_t> h(mode_header_bytes(c) + 32);
+    digest_header(c, hdr, h_in, h.data());
+    return witness_of(impl, message, len, key, h.data());
+}
+std::vector<Proof> ProvingKey::prove_digest_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins, size_t n, size_t n_contexts, const uint8_t *zk_seed,
+                                                  uint64_t index_offset, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null) {
+    const Circuit &c = impl->circuit;
+    require_digest_key(c);
+    const size_t hb = mode_header_bytes(c), L = c.message_bytes;
+    if (n && (!messages || !keys || (!headers && hb))) throw std::invalid_argument("null argument");
+    std::vector<uint8_t> hs((hb + 32) * n);
+    for (size_t i = 0; i < n; i++) {
+        uint8_t *h = &hs[(hb + 32) * i];
+        digest_header(c, headers ? headers + hb * i : nullptr, h_ins ? h_ins + 32 * i : nullptr, h);
+        digest_host_side(c, messages + L * i, keys + c.key_bytes * i, h, h + hb, ciphertexts_or_null ? ciphertexts_or_null + L * i : nullptr, tags_or_null ? tags_or_null + 16 * i : nullptr,
+                         h_outs_or_null ? h_outs_or_null + 32 * i : nullptr);
+    }
+    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, hs.data(), hb + 32);
+}
+std::vector<Proof> ProvingKey::prove_digest_chunked(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, size_t n_contexts, const uint8_t *zk_seed,
+                                                    uint64_t index_offset, uint8_t *ciphertext_or_null, uint8_t *states_or_null) {
+    const Circuit &c = impl->circuit;
+    require_digest_key(c);
+    if (c.digest_kind != DIGEST_CHAIN) throw std::invalid_argument("a chunked digest job takes a chain key (a final key proves one lone tail: zkaes_encrypt_digest_batch_seeded_at)");
+    if (c.kind != CIRCUIT_AES && c.kind != CIRCUIT_AES_CBC && c.kind != CIRCUIT_AES_CTR) throw std::invalid_argument("a chunked digest job takes an ECB, CBC or CTR key (GCM records go through the batch entry)");
+    const size_t hb = mode_header_bytes(c), chunk = c.message_bytes;
+    if (!message || !key || (hb ? !hdr : hdr != nullptr)) throw std::invalid_argument("a chunked digest job takes an iv or initial counter block for CBC and CTR, NULL for ECB");
+    if (len == 0 || len % chunk) throw std::invalid_argument("message length must be a non-zero multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
+    const size_t n_chunks = len / chunk;
+    // the cipher and the hash once on the host: every chaining value of either is public, so the chunk-proofs are independent and run side by side
+    std::vector<uint8_t> ct(len), hs((hb + 32) * n_chunks), states(32 * (n_chunks + 1));
+    if (c.kind == CIRCUIT_AES) aes_ecb_encrypt_host(message, len, key, c.key_bytes, ct.data());
+    else if (c.kind == CIRCUIT_AES_CBC) aes128_cbc_encrypt_host(message, len, key, hdr, ct.data(), c.key_bytes);
+    else aes128_ctr_crypt_host(message, len, key, hdr, ct.data(), c.key_bytes);
+    if (h_in) memcpy(states.data(), h_in, 32); else sha256_chain(nullptr, nullptr, 0, states.data());
+    for (size_t j = 0; j < n_chunks; j++) {
+        uint8_t *h = &hs[(hb + 32) * j];
+        if (c.kind == CIRCUIT_AES_CBC) memcpy(h, j ? &ct[chunk * j - 16] : hdr, 16);
+        if (c.kind == CIRCUIT_AES_CTR) ctr_counter_add(hdr, (uint64_t)j * c.n_blocks, h);
+        memcpy(h + hb, &states[32 * j], 32);
+        sha256_chain(&states[32 * j], message + chunk * j, chunk, &states[32 * (j + 1)]);
+    }
+    std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, hs.data(), hb + 32);
+    if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+    if (states_or_null) memcpy(states_or_null, states.data(), states.size());
+    return proofs;
 }
 Proof ProvingKey::prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed) {
     if (impl->circuit.kind != CIRCUIT_OPS_XOR && impl->circuit.kind != CIRCUIT_OPS_ADD) throw std::invalid_argument("proving key was synthesized for an AES circuit");
@@ -1318,10 +1424,11 @@ std::vector<uint8_t> ProvingKey::debug_fetch(const std::string &name) const {
 size_t ProvingKey::key_bytes() const { return impl->circuit.key_bytes; }
 size_t ProvingKey::key_tag_blocks() const { return impl->circuit.key_tag_blocks; }
 
-std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks) {
+std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind,
+                                            uint64_t digest_prefix) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks);
+    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
     return pk;
 }
 

@@ -68,6 +68,22 @@ class ProvingKey {
     // T = 0, 1 or 2: the key-tag blocks this key was synthesized with.  Every proving and witness call below takes a tagged key as it is: the last 128 T
     // public-input bits of each proof are AES_K(D_0) (, AES_K(D_1)) for that proof's key, filled from the trace like every other column
     size_t key_tag_blocks() const;
+    // ---- plaintext digests (circuit().digest_kind != 0).  Every proving and witness call of this class other than the three below refuses a digest
+    // key, and these three refuse a key without one (op_lists_json takes either: its proof of a digest key starts from the initial value).  A proof's public header is what its mode takes -- nothing (ECB), the 16 bytes of the iv (CBC) or the initial counter
+    // block (CTR), iv (12) then aad (GCM) -- and hdr_stride below is that length; a state (h_in, h_out) is 32 bytes, SHA-256's big-endian word serialisation, and a null
+    // h_in(s) is the initial value.  The device is handed message, key, header and H_in; H_out reaches the instance from the trace, and the host's own hash (sha256_chain /
+    // sha256_finish) meets it in the constraints.
+    // witness generation only: z = padded instance || witness
+    std::vector<uint8_t> aes_witness_digest(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr_or_null, const uint8_t *h_in_or_null);
+    // n independent proofs of any mode: messages n x L, keys n x key_bytes(), headers n x hdr_stride (null for ECB), h_ins n x 32 or null.  Receives on request the host's
+    // ciphertexts (n x L), GCM tags (n x 16, GCM keys only) and every proof's H_out (n x 32).  Seeds as prove_aes_chunked
+    std::vector<Proof> prove_digest_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins_or_null, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
+                                          uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr, uint8_t *h_outs_or_null = nullptr);
+    // chunk-proofs of one message under one key over a CHAIN key of ECB, CBC or CTR: the host runs plain SHA-256 (and, for CBC, the cipher chain) over the message once,
+    // chunk j is proven under its mode header (as prove_aes_cbc_chunked / prove_aes_ctr_chunked derive it from hdr, the header entering this call's first chunk) and under
+    // (states[j], states[j + 1]), states[0] = h_in.  states_or_null receives the n + 1 states (32 bytes each), ciphertext_or_null len bytes
+    std::vector<Proof> prove_digest_chunked(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr_or_null, const uint8_t *h_in_or_null, size_t n_contexts,
+                                            const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr, uint8_t *states_or_null = nullptr);
     // encrypt(): message length must equal the length the key was synthesized for; zk_seed = 32-byte StdRng seed or nullptr for
     // ark_std::test_rng()'s (what simpleworks::marlin::generate_rand() returns)
     Proof prove_aes(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t *zk_seed);
@@ -138,7 +154,7 @@ class ProvingKey {
 // Without the flag the tables are built when memory allows (hipMemGetInfo) and silently skipped otherwise.
 enum : unsigned { KEY_NO_TABLES = 1u };
 std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128,
-                                            size_t key_tag_blocks = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, the AES kinds only)
+                                            size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, digest_kind: 0, 1 or 2 (circuit.hpp DigestKind), the AES kinds only)
 // hold = true: every universal / Lagrange SRS built (or alive) from now on stays resident after its last key is freed; false: back to "freed with the last key"
 void srs_hold(bool hold);
 // process default of ProvingKey::contexts(): ZKAES_CONTEXTS from the environment (read once), else ZKAES_DEFAULT_CONTEXTS

@@ -133,6 +133,53 @@ static_assert(TRK_KT_SLOT(8, TRK_ECB_BYTES(8, 2), 1) == 3424 + 1520 && TRK_KT_BY
 static_assert(TRK_BLOCK_STRIDE(4) % 16 == 0 && TRK_BLOCK_STRIDE(6) % 16 == 0 && TRK_BLOCK_STRIDE(8) % 16 == 0 && TRK_KT_BYTES(6, TRK_GCM_BYTES(6, 1, 2), 1) % 16 == 0 && TRK_KT(TRK_GCM_BYTES(8, 1, 2)) == TRK_GCM_BYTES(8, 1, 2), "tagged traces are 16-byte multiples");
 static_assert(sizeof(TRK_KT_D_PREFIX) == 12, "D_t = 11 prefix bytes, t, four zero bytes");
 
+// ---- plaintext digests: a key synthesized with a digest kind D = 1 (chain) or 2 (final) also proves H_out = the SHA-256 compressions of its hidden message
+// from H_in.  The digest region lies BEHIND the key-tag slots, so no offset above moves: `bytes` = the trace length with the tag slots (TRK_KT_BYTES), TRD(bytes) = that
+// length rounded up to 16 is the region's base dg, and with D = 0 a trace is what it was.
+//   dg + 0    H_in  (32): the eight words a proof's first compression starts from, in SHA-256's big-endian word serialisation (word k bit i = bit i % 8 of byte 4 k + 3 - i / 8)
+//   dg + 32   H_out (32): the same for the last compression's feed-forward
+//   dg + 64   one slot per compression, stride TRD_SLOT_STRIDE.  Every entry is a 32-bit word stored little-endian, so bit i of a word at `off` is (off + i / 8, i % 8):
+//       +0     per schedule word t = 16 .. 63, 24 bytes: rotr7 ^ rotr18 of W_{t-15} | sigma_0(W_{t-15}) | rotr17 ^ rotr19 of W_{t-2} | sigma_1(W_{t-2}) | W_t | carry (2 bits)
+//       +1152  per round t = 0 .. 63, 44 bytes: rotr6 ^ rotr11 of e | Sigma_1(e) | Ch | rotr2 ^ rotr13 of a | Sigma_0(a) | a ^ b | Maj | e' | a' | carry of e' (3 bits) |
+//              carry of a' (3 bits)
+//       +3968  the eight feed-forward sums (32), then their carries (8 words of one bit)
+#define TRD(bytes) (((bytes) + 15) / 16 * 16)
+#define TRD_HIN 0
+#define TRD_HOUT 32
+#define TRD_SLOT0 64
+#define TRD_SCH 0
+#define TRD_SCH_STRIDE 24
+#define TRD_SCH_S0X 0
+#define TRD_SCH_S0 4
+#define TRD_SCH_S1X 8
+#define TRD_SCH_S1 12
+#define TRD_SCH_W 16
+#define TRD_SCH_CARRY 20
+#define TRD_RND (TRD_SCH + 48 * TRD_SCH_STRIDE)
+#define TRD_RND_STRIDE 44
+#define TRD_RND_S1X 0
+#define TRD_RND_S1 4
+#define TRD_RND_CH 8
+#define TRD_RND_S0X 12
+#define TRD_RND_S0 16
+#define TRD_RND_AB 20
+#define TRD_RND_MAJ 24
+#define TRD_RND_E 28
+#define TRD_RND_A 32
+#define TRD_RND_CE 36
+#define TRD_RND_CA 40
+#define TRD_FF (TRD_RND + 64 * TRD_RND_STRIDE)
+#define TRD_FF_CARRY 32
+#define TRD_SLOT_STRIDE (TRD_FF + 64)
+#define TRD_BYTES(bytes, D, n) ((D) ? TRD(bytes) + TRD_SLOT0 + (n) * TRD_SLOT_STRIDE : (bytes))
+// compressions of a proof: L / 64 for a chain key, ceil((L + 9) / 64) for a final key (the padding 0x80, zeros, be64(8 (P + L)))
+#define TRD_BLOCKS(D, L) ((D) == 1 ? (L) / 64 : (D) == 2 ? ((L) + 9 + 63) / 64 : 0)
+static_assert(TRD_BYTES(TRK_KT_BYTES(4, TRK_ECB_BYTES(4, 1), 0), 0, 0) == TR_BLOCK0 + TR_BLOCK_STRIDE && TRD_BYTES(TRK_KT_BYTES(8, TRK_CTR_BYTES(8, 2), 2), 0, 0) == TRK_KT_BYTES(8, TRK_CTR_BYTES(8, 2), 2) &&
+              TRD_BYTES(TRK_GCM_BYTES(6, 1, 2), 0, 0) == TRK_GCM_BYTES(6, 1, 2), "without a digest a trace keeps its length");
+static_assert(TRD_RND == 1152 && TRD_FF == 3968 && TRD_SLOT_STRIDE == 4032 && TRD_SLOT_STRIDE % 16 == 0 && TRD_SLOT0 % 16 == 0, "the digest slot");
+static_assert(TRD(TRK_ECB_BYTES(6, 1)) == TRK_ECB_BYTES(6, 1) + 8 && TRD(TRK_CTR_BYTES(4, 2)) % 16 == 0 && TRD_BYTES(TRK_ECB_BYTES(8, 4), 1, 1) % 16 == 0, "the digest region begins and ends on a multiple of 16");
+static_assert(TRD_BLOCKS(1, 128) == 2 && TRD_BLOCKS(2, 55) == 1 && TRD_BLOCKS(2, 56) == 2 && TRD_BLOCKS(2, 17) == 1 && TRD_BLOCKS(0, 64) == 0, "compressions per proof");
+
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30
 #define WD_BYTEBIT 0u   // [29:4] trace offset, [3:1] bit, [0] neg

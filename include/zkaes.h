@@ -280,6 +280,67 @@ int zkaes_verify_chunked_kt(const zkaes_vk *vk, int circuit_kind, const uint8_t 
 /* host only: zkaes_verify_encryption_gcm with the key tag behind the GCM tag */
 int zkaes_verify_encryption_gcm_kt(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext,
                                    size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *key_tag, size_t key_tag_len, int *accepted);
+/* ---- plaintext digests.
+ * Every proof above says "some hidden message encrypts to this ciphertext"; nothing binds the message.  A key synthesized with digest_kind = ZKAES_DIGEST_CHAIN or
+ * ZKAES_DIGEST_FINAL (ZKAES_DIGEST_NONE = every key above: nothing changes) proves beside its mode's statement and its key tag
+ *     chain:  H_out = C(... C(C(H_in, M[0:64]), M[64:128]) ...)   over the hidden message M, C = SHA-256's compression function (FIPS 180-4 6.2.2), no padding; the
+ *             plaintext length must be a non-zero multiple of 64
+ *     final:  the same over M || 80 || 00 .. || be64(8 (digest_prefix + L)), ceil((L + 9) / 64) compressions, for any plaintext length L the mode allows; digest_prefix
+ *             is a multiple of 64 fixed by the key (the bytes hashed ahead of this proof), digest_prefix + L < 2^61.  With H_in = the initial value and digest_prefix = 0,
+ *             H_out = SHA-256(M)
+ * and exposes H_in then H_out, 32 bytes each in SHA-256's big-endian word serialisation (a final H_out is the digest's byte string), as the LAST 512 public-input bits,
+ * bytes as 8 LSB-first bits as everywhere.  States between the compressions of one proof are witnesses.  A chunked job runs plain SHA-256 over the message on the host
+ * and proves chunk j under (states[j], states[j + 1]); a verifier who checks chunk j against those two entries of ONE array has checked the chain, and finishes the digest
+ * on the host with zkaes_sha256_finish(states[n], total bytes, NULL, 0, ..).  Every public state is the unpadded hash of a prefix of the message: given states[j], a
+ * low-entropy chunk j can be guessed and tested, as the final digest allows for the whole message. */
+#define ZKAES_DIGEST_NONE 0
+#define ZKAES_DIGEST_CHAIN 1
+#define ZKAES_DIGEST_FINAL 2
+/* as zkaes_synthesize_keys_kt with digest_kind and digest_prefix (digest_prefix must be 0 unless digest_kind is ZKAES_DIGEST_FINAL; at digest_kind 0 the same key) */
+int zkaes_synthesize_keys_pd(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t plaintext_length, size_t aad_length,
+                             size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* host only: zkaes_circuit_info_kt with the digest arguments; at digest_kind 0 it returns what that returns */
+int zkaes_circuit_info_pd(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t plaintext_length, size_t aad_length,
+                          uint64_t out[12]);
+/* host only: zkaes_circuit_matrix_kt with the digest arguments */
+int zkaes_circuit_matrix_pd(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t plaintext_length, size_t aad_length,
+                            int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+/* out = {digest kind, digest prefix, compressions per proof, offset of the digest region in a trace}; all zero for a key without a digest */
+int zkaes_pk_digest_info(const zkaes_pk *pk, uint64_t out[4]);
+/* *circuit_kind = the ZKAES_CIRCUIT_* this proving key was synthesized for, *header_bytes = the public header a proof of that mode carries ahead of a digest key's H_in:
+ * 0 (ECB, the ops kinds), 16 (CBC, CTR), 12 + the key's aad length (GCM).  Either pointer may be NULL */
+int zkaes_pk_mode(const zkaes_pk *pk, int *circuit_kind, size_t *header_bytes);
+/* host only: h_out (32 bytes) = the compressions of data's len / 64 blocks from h_in (32 bytes, NULL = SHA-256's initial value); len must be a multiple of 64 */
+int zkaes_sha256_chain(const uint8_t *h_in, const uint8_t *data, size_t len, uint8_t h_out[32]);
+/* host only: digest (32 bytes) = the chain from h_in (NULL = the initial value) over tail || 80 || 00 .. || be64(8 (prefix_bytes + tail_len)); prefix_bytes a multiple of 64.
+ * zkaes_sha256_finish(NULL, 0, m, len, d) is SHA-256(m) */
+int zkaes_sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *tail, size_t tail_len, uint8_t digest[32]);
+/* witness generation only, for a digest key of any mode: hdr = the mode's public header (NULL for ECB, the 16 bytes of the iv or initial counter block for CBC and CTR,
+ * iv (12) then the key's aad for GCM), h_in = 32 bytes or NULL for the initial value.  z as zkaes_aes_witness */
+int zkaes_aes_witness_pd(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *secret_key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *z, size_t z_cap, size_t *z_len);
+/* n independent proofs over a digest key of any mode: messages = n x the key's plaintext length, secret_keys = n x its key bytes, headers = n x the mode's header bytes
+ * (0 for ECB: pass NULL and headers_len 0; 16 for CBC and CTR; 12 + the key's aad length for GCM), h_ins = n x 32 bytes or NULL (every proof starts from the initial
+ * value).  Receives, where the pointer is not NULL, the ciphertexts (n x plaintext length), the GCM tags (n x 16, GCM keys only) and every proof's H_out (n x 32).  Seed
+ * and index as zkaes_encrypt_batch_seeded_at */
+int zkaes_encrypt_digest_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                         const uint8_t *h_ins, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null,
+                                         uint8_t *h_outs_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* the chunk-proofs of one ECB, CBC or CTR message over a CHAIN key: hdr = the header entering this call's first chunk (NULL for ECB), h_in = the state entering it (NULL =
+ * the initial value); every chunk's header and state are computed on the host.  states_or_null receives the n_chunks + 1 states, 32 bytes each (states[0] = h_in); a job
+ * split over calls passes the previous call's last state, the CBC chaining value or zkaes_ctr_counter_add(icb, blocks before).  Seed and index as
+ * zkaes_encrypt_chunked_seeded_at */
+int zkaes_encrypt_digest_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t *secret_key, const uint8_t *hdr, const uint8_t *h_in, const zkaes_pk *pk, const uint8_t *zk_seed32,
+                                           uint64_t first_proof_index, uint8_t *ciphertext_or_null, uint8_t *states_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens,
+                                           size_t n_chunks);
+/* host only: the chunk-proofs of one ECB, CBC or CTR job over a digest key.  Chunk j's public input is what zkaes_verify_chunked_kt derives for it (without tag bits when
+ * key_tag is NULL and key_tag_len 0), then states[j] and states[j + 1]; states = (n_chunks + 1) x 32 bytes.  n_chunks = 1 is the lone-proof form: (states[0], states[1]) =
+ * (H_in, H_out), and a CTR ciphertext may then have any length.  Lengths that do not fit the key's public-input count are an error where the key carries that count,
+ * otherwise every chunk is rejected.  A proof that does not parse is a rejected chunk, not an error.  accepted_each (n_chunks ints) and n_accepted may be NULL */
+int zkaes_verify_digest_chunked(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ciphertext,
+                                size_t ciphertext_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, int *accepted_each, size_t *n_accepted);
+/* host only: zkaes_verify_encryption_gcm_kt (key_tag NULL and key_tag_len 0 for a key without tag blocks) with h_in (NULL = the initial value) and h_out behind it */
+int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext,
+                                       size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *key_tag, size_t key_tag_len, const uint8_t *h_in, const uint8_t h_out[32], int *accepted);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

@@ -106,6 +106,29 @@ extern "C" {
                                ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
     fn zkaes_verify_encryption_gcm_kt(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
                                       ciphertext_len: usize, tag16: *const u8, key_tag: *const u8, key_tag_len: usize, accepted: *mut c_int) -> c_int;
+    // plaintext digests (include/zkaes.h, section "plaintext digests"; declarations only, no wrappers yet, and not compiled: no cargo in the build image).  digest_kind: 0 none,
+    // 1 chain, 2 final; a state (h_in, h_out, an entry of states) is 32 bytes and a null h_in is SHA-256's initial value
+    fn zkaes_synthesize_keys_pd(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, digest_kind: c_uint, digest_prefix: u64, plaintext_length: usize, aad_length: usize,
+                                srs_num_constraints: usize, srs_num_variables: usize, srs_num_non_zero: usize, flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_circuit_info_pd(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, digest_kind: c_uint, digest_prefix: u64, plaintext_length: usize, aad_length: usize,
+                             out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_pd(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, digest_kind: c_uint, digest_prefix: u64, plaintext_length: usize, aad_length: usize,
+                               which: c_int, n_rows: *mut u64, nnz: *mut u64, rowptr: *mut u32, col: *mut u32, coeff: *mut i64) -> c_int;
+    fn zkaes_pk_digest_info(pk: *const zkaes_pk, out: *mut u64) -> c_int;
+    fn zkaes_pk_mode(pk: *const zkaes_pk, circuit_kind: *mut c_int, header_bytes: *mut usize) -> c_int;
+    fn zkaes_sha256_chain(h_in: *const u8, data: *const u8, len: usize, h_out: *mut u8) -> c_int;
+    fn zkaes_sha256_finish(h_in: *const u8, prefix_bytes: u64, tail: *const u8, tail_len: usize, digest: *mut u8) -> c_int;
+    fn zkaes_aes_witness_pd(pk: *const zkaes_pk, msg: *const u8, len: usize, secret_key: *const u8, hdr: *const u8, h_in: *const u8, z: *mut u8, z_cap: usize, z_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_digest_batch_seeded_at(n: usize, messages: *const u8, messages_len: usize, secret_keys: *const u8, secret_keys_len: usize, headers: *const u8, headers_len: usize,
+                                            h_ins: *const u8, pk: *const zkaes_pk, zk_seed32: *const u8, first_proof_index: u64, ciphertexts_or_null: *mut u8, tags_or_null: *mut u8,
+                                            h_outs_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_encrypt_digest_chunked_seeded_at(msg: *const u8, len: usize, secret_key: *const u8, hdr: *const u8, h_in: *const u8, pk: *const zkaes_pk, zk_seed32: *const u8,
+                                              first_proof_index: u64, ciphertext_or_null: *mut u8, states_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize,
+                                              proof_lens: *mut usize, n_chunks: usize) -> c_int;
+    fn zkaes_verify_digest_chunked(vk: *const zkaes_vk, circuit_kind: c_int, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, iv_or_icb: *const u8, ciphertext: *const u8,
+                                   ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize, states: *const u8, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    fn zkaes_verify_encryption_gcm_digest(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
+                                          ciphertext_len: usize, tag16: *const u8, key_tag: *const u8, key_tag_len: usize, h_in: *const u8, h_out: *const u8, accepted: *mut c_int) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
