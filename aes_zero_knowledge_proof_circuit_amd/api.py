@@ -406,6 +406,45 @@ class ProvingKey:
         _check(lib().zkaes_aes_witness_gcm(*args, buf, n, C.byref(n)))
         return buf.raw
 
+    def segment_info(self):
+        """None for a key that is no GCM segment key, else {"role", "blocks", "message_bytes", "aad_bytes"}"""
+        out = (C.c_uint64 * 4)()
+        _check(lib().zkaes_pk_segment_info(self._p, out))
+        if not out[0]:
+            return None
+        return {"role": ("head", "mid", "tail")[out[0] - 1], "blocks": int(out[1]), "message_bytes": int(out[2]), "aad_bytes": int(out[3])}
+
+    def witness_gcm_segment(self, message, secret_key, header):
+        """z (padded instance + witness, one byte per variable) of a segment key; header = gcm_segment_header(...)"""
+        self._need_key(secret_key)
+        n = C.c_size_t()
+        args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(header), C.c_size_t(len(header)))
+        _check(lib().zkaes_aes_witness_gcm_seg(*args, None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(lib().zkaes_aes_witness_gcm_seg(*args, buf, n, C.byref(n)))
+        return buf.raw
+
+    def encrypt_gcm_segment_batch(self, messages, secret_keys, headers, zk_seed=None, first_proof_index=0):
+        """n independent proofs over this segment key, each under its own gcm_segment_header -> the proofs; the caller answers for what the headers say
+        (encrypt_gcm_segments derives them from one record).  zk_seed and first_proof_index as encrypt_batch"""
+        n = len(messages)
+        if not len(secret_keys) == len(headers) == n:
+            raise ZkAesError("one secret key and one header per message")
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        mb, kb, hb = b"".join(bytes(m) for m in messages), b"".join(bytes(k) for k in secret_keys), b"".join(bytes(h) for h in headers)
+        lens = (C.c_size_t * max(n, 1))()
+        out, total = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_gcm_segment_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), self._p, seed,
+                                                               C.c_uint64(first_proof_index), C.byref(out), C.byref(total), lens))
+        blob = _take(out, total)
+        proofs, off = [], 0
+        for i in range(n):
+            proofs.append(blob[off:off + lens[i]])
+            off += lens[i]
+        return proofs
+
     def encrypt_gcm_batch(self, messages, secret_keys, ivs, aads, zk_seed=None, first_proof_index=0):
         """n independent GCM records over this key -> (ciphertexts, tags, proofs), three lists.  Every message has the key's plaintext length, every aad the key's aad
         length, every iv 12 bytes; zk_seed and first_proof_index as encrypt_batch (None = a fresh OS seed for the call)"""
@@ -819,6 +858,155 @@ def verify_encryption_gcm_digest(verifying_key, proof, iv, aad, ciphertext, tag,
                                                     C.c_size_t(len(ciphertext)), bytes(tag), None if key_tag is None else bytes(key_tag), C.c_size_t(0 if key_tag is None else len(key_tag)),
                                                     None if h_in is None else bytes(h_in), bytes(h_out), C.byref(acc)))
     return bool(acc.value)
+
+
+# ---- GCM records longer than one proof: segment-proofs over hidden commitments (include/zkaes.h)
+CIRCUIT_AES_GCM_SEG = 6            # what ProvingKey.mode() reports for a segment key
+SEG_HEAD, SEG_MID, SEG_TAIL = 0, 1, 2
+_SEG_ROLES = {"head": SEG_HEAD, "mid": SEG_MID, "tail": SEG_TAIL, SEG_HEAD: SEG_HEAD, SEG_MID: SEG_MID, SEG_TAIL: SEG_TAIL}
+# the largest c (data blocks per segment) at which all three roles stay inside the default SRS literal, per key size (tests/test_gcm_segments_host.py)
+GCM_SEGMENT_DEFAULT_C = {128: 4, 192: 3, 256: 2}
+
+
+def _seg_role(role):
+    if role not in _SEG_ROLES:
+        raise ZkAesError('role must be "head", "mid" or "tail"')
+    return _SEG_ROLES[role]
+
+
+def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128):
+    """(ProvingKey, VerifyingKey) of one segment role.  role: "head", "mid" or "tail"; units: c, the data blocks per segment, for a head or mid, and Lt, the bytes of
+    the record's last segment (1 .. 16 c), for a tail; aad_length: the record's whole aad, head only.  flags and key_bits as synthesize_keys; no key tag, no digest"""
+    pk, vk = C.c_void_p(), C.c_void_p()
+    _check(lib().zkaes_synthesize_keys_gcm_seg(_seg_role(role), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]),
+                                               C.c_uint(flags), C.byref(pk), C.byref(vk)))
+    return ProvingKey(pk.value), VerifyingKey(vk.value)
+
+
+def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128):
+    out = (C.c_uint64 * 12)()
+    _check(lib().zkaes_circuit_info_gcm_seg(_seg_role(role), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), out))
+    keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
+    return dict(zip(keys, out))
+
+
+def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128):
+    rows, nnz = C.c_uint64(), C.c_uint64()
+    head = (_seg_role(role), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), which)
+    _check(lib().zkaes_circuit_matrix_gcm_seg(*head, C.byref(rows), C.byref(nnz), None, None, None))
+    rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
+    col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
+    coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
+    _check(lib().zkaes_circuit_matrix_gcm_seg(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
+    return rowptr, col[:nnz.value], coeff[:nnz.value]
+
+
+def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128):
+    """how a record of `length` bytes splits into segments of c data blocks (None = GCM_SEGMENT_DEFAULT_C[key_bits]) -> {"n", "c", "aad", "tail_bytes", "segments"};
+    a segment is {"role", "offset", "bytes", "ctr0"}.  The keys the record needs: head (c, aad_length), mid (c) when n > 2, tail (tail_bytes)"""
+    if c is None:
+        c = GCM_SEGMENT_DEFAULT_C[key_bits]
+    if c < 1 or not 1 <= length <= 1 << 20 or not 0 <= aad_length <= 1 << 16:
+        raise ZkAesError("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block")
+    nb = (length + 15) // 16
+    n = (nb + c - 1) // c
+    if n < 2:
+        raise ZkAesError("GCM segments: this record fits one segment; a record that fits one proof goes through synthesize_keys_gcm")
+    segs = [{"role": "head" if s == 0 else "tail" if s == n - 1 else "mid", "offset": 16 * c * s, "bytes": min(16 * c, length - 16 * c * s), "ctr0": 2 + s * c} for s in range(n)]
+    return {"n": n, "c": c, "aad": aad_length, "tail_bytes": segs[-1]["bytes"], "segments": segs}
+
+
+def gcm_boundaries(message, secret_key, iv, aad, c):
+    """Y_0 .. Y_{n-2}: the record's GHASH accumulator behind the last block of every segment but the last (host only)"""
+    _gcm_args(secret_key, iv)
+    n = C.c_size_t()
+    args = (bytes(message), C.c_size_t(len(message)), bytes(secret_key), C.c_size_t(len(secret_key)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), C.c_size_t(c))
+    _check(lib().zkaes_gcm_boundaries(*args, None, C.c_size_t(0), C.byref(n)))
+    ys = C.create_string_buffer(max(16 * (n.value - 1), 1))
+    _check(lib().zkaes_gcm_boundaries(*args, ys, C.c_size_t(16 * (n.value - 1)), C.byref(n)))
+    return [ys.raw[16 * s:16 * s + 16] for s in range(n.value - 1)]
+
+
+def gcm_commit(secret_key, y, salt):
+    """the boundary commitment: one SHA-256 compression from the initial value over key || zeros to 32 bytes || y || salt (host only)"""
+    _host_key(secret_key)
+    if len(y) != 16 or len(salt) != 16:
+        raise ZkAesError("y and salt must be 16 bytes")
+    out = C.create_string_buffer(32)
+    _check(lib().zkaes_gcm_commit(bytes(secret_key), C.c_size_t(len(secret_key)), bytes(y), bytes(salt), out))
+    return out.raw
+
+
+def gcm_length_block(aad_length, length):
+    return (8 * aad_length).to_bytes(8, "big") + (8 * length).to_bytes(8, "big")
+
+
+def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_block=None, aad=b""):
+    """the 80 + A bytes a segment witness takes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad; a field the role does not use may stay None"""
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    parts = [bytes(iv), int(ctr0).to_bytes(4, "big")]
+    for field in (y_in, salt_in, salt_out, length_block):
+        field = bytes(16) if field is None else bytes(field)
+        if len(field) != 16:
+            raise ZkAesError("Y_in, the salts and the length block are 16 bytes each")
+        parts.append(field)
+    return b"".join(parts) + bytes(aad)
+
+
+def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_segment=0, count=None, zk_seed=None):
+    """segments [first_segment, first_segment + count) of one record as segment-proofs -> (ciphertext, tag, commitments, proofs): the WHOLE record's ciphertext and tag,
+    its n - 1 commitments (32 bytes each) and the call's proofs.  keys = (head, mid or None, tail) proving keys; count None = to the record's end; salts = n - 1 strings
+    of 16 bytes or None for os.urandom (a job split over calls passes them: every call must make the same commitments); zk_seed as encrypt_batch, segment s drawing at
+    index s whichever call proves it"""
+    head, mid, tail = keys
+    _gcm_args(secret_key, iv, head.key_bytes())
+    info = head.segment_info()
+    if info is None:
+        raise ZkAesError("the head key is not a GCM segment key: the segment entry points take keys of synthesize_keys_gcm_segment (a lone record goes through encrypt_gcm, zkaes_encrypt_gcm_seeded)")
+    c = info["blocks"]
+    n = gcm_segment_plan(len(message), len(aad), c)["n"]
+    if count is None:
+        count = n - first_segment
+    if salts is None:
+        salts = [os.urandom(16) for _ in range(n - 1)]
+    if len(salts) != n - 1 or any(len(s) != 16 for s in salts):
+        raise ZkAesError("salts: one 16-byte salt per boundary, %d for this record" % (n - 1))
+    if zk_seed is None:
+        zk_seed = os.urandom(32)
+    seed = ProvingKey._seed_arg(zk_seed)
+    ct, tag, coms = C.create_string_buffer(len(message)), C.create_string_buffer(16), C.create_string_buffer(32 * (n - 1))
+    lens = (C.c_size_t * max(count, 1))()
+    out, total = C.c_void_p(), C.c_size_t()
+    _check(lib().zkaes_encrypt_gcm_segments_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), head._p,
+                                                      None if mid is None else mid._p, tail._p, b"".join(bytes(s) for s in salts), seed, C.c_size_t(first_segment), C.c_size_t(count), ct, tag,
+                                                      coms, C.byref(out), C.byref(total), lens))
+    blob = _take(out, total)
+    proofs, off = [], 0
+    for i in range(count):
+        proofs.append(blob[off:off + lens[i]])
+        off += lens[i]
+    return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], proofs
+
+
+def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c):
+    """the n segment-proofs of one record against ONE list of n - 1 commitments -> a list of n bools.  vks = (head, mid or None, tail) verifying keys; c = the data
+    blocks per segment.  The verifier sets every segment's ctr0 = 2 + s c, cuts the ciphertext, builds the length block from the lengths it sees and hands the tag to
+    the tail alone; lengths that do not fit the keys, the proof count or the commitment count raise"""
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    if any(len(x) != 32 for x in commitments):
+        raise ZkAesError("a commitment is 32 bytes")
+    head, mid, tail = vks
+    n = len(proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each, ok = (C.c_int * max(n, 1))(), C.c_size_t()
+    coms = b"".join(bytes(x) for x in commitments)
+    _check(lib().zkaes_verify_gcm_segments(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad),
+                                           C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
 
 
 def proof_roundtrip(proof):

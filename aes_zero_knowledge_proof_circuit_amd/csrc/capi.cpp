@@ -223,6 +223,7 @@ int zkaes_encrypt_gcm_batch_seeded_at(size_t n, const uint8_t *messages, size_t 
     return guard([&] {
         if (!pk || !proofs || !proofs_len || (n && (!messages || !secret_keys || !headers))) throw std::invalid_argument("null argument");
         const zk::Circuit &c = pk->pk->circuit();
+        if (c.kind == zk::CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("this proving key is a GCM segment key: use the segment entry points (zkaes_encrypt_gcm_segments_seeded_at, zkaes_aes_witness_gcm_seg)");
         if (c.kind != zk::CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
         if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
         if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
@@ -238,6 +239,55 @@ int zkaes_aes_witness_gcm(const zkaes_pk *pk, const uint8_t *msg, size_t len, co
         auto v = pk->pk->aes_witness_gcm(msg, len, key, iv, aad, aad_len);
         if (z_len) *z_len = v.size();
         if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+    });
+}
+// ---- GCM segments (include/zkaes.h): the prover side; zkaes_gcm_boundaries, zkaes_gcm_commit, the circuit queries and the verifier are in capi_host.cpp
+int zkaes_synthesize_keys_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return guard([&] {
+        if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
+        zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
+        auto k = zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u);
+        zkaes_vk *v = new zkaes_vk{k->vk()};
+        zkaes_pk *p = new zkaes_pk{std::move(k)};
+        if (pk) *pk = p; else delete p;
+        if (vk) *vk = v; else delete v;
+    });
+}
+int zkaes_pk_segment_info(const zkaes_pk *pk, uint64_t out[4]) {
+    return guard([&] {
+        if (!pk || !out) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        out[0] = c.kind == zk::CIRCUIT_AES_GCM_SEG ? 1 + (uint64_t)c.seg_role : 0; out[1] = c.n_blocks; out[2] = c.message_bytes; out[3] = c.aad_bytes;
+    });
+}
+int zkaes_aes_witness_gcm_seg(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, uint8_t *z, size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        auto v = pk->pk->aes_witness_gcm_segment(msg, len, key, header, header_len);
+        if (z_len) *z_len = v.size();
+        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+    });
+}
+int zkaes_encrypt_gcm_segment_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                              const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (c.kind != zk::CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("the key is not a GCM segment key: the segment entry points take keys of zkaes_synthesize_keys_gcm_seg (lone records go through zkaes_encrypt_gcm_batch_seeded_at)");
+        const size_t hb = zk::mode_header_bytes(c);
+        if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
+        if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
+        if (headers_len != n * hb) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad)");
+        pack_proofs(pk->pk->prove_gcm_segment_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
+    });
+}
+int zkaes_encrypt_gcm_segments_seeded_at(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const zkaes_pk *head,
+                                         const zkaes_pk *mid_or_null, const zkaes_pk *tail, const uint8_t *salts_or_null, const uint8_t *zk_seed32, size_t first_segment, size_t count,
+                                         uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t *commitments_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!head || !tail || !proofs || !proofs_len) throw std::invalid_argument("null argument");
+        pack_proofs(zk::prove_gcm_segments(head->pk.get(), mid_or_null ? mid_or_null->pk.get() : nullptr, tail->pk.get(), msg, len, key, iv, aad, aad_len, salts_or_null, first_segment, count,
+                                           zk_seed32, ciphertext_or_null, tag_or_null, commitments_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_pk_mode(const zkaes_pk *pk, int *circuit_kind, size_t *header_bytes) {

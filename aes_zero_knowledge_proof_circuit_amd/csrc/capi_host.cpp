@@ -224,6 +224,79 @@ int zkaes_verify_encryption_gcm(const zkaes_vk *vk, const uint8_t *proof, size_t
         *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
     });
 }
+// ---- GCM segments (include/zkaes.h): Y at the boundaries and a commitment on the host, and the verifier of a record's n segment-proofs
+int zkaes_gcm_boundaries(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, uint8_t *ys, size_t ys_cap,
+                         size_t *n_segments) {
+    return guard([&] {
+        if (!msg || !key || !iv || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        if (len == 0 || len > ((size_t)1 << 20) || c == 0) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes and a segment at least one block");
+        const size_t nb = (len + 15) / 16, n = (nb + c - 1) / c;
+        if (n_segments) *n_segments = n;
+        if (!ys) return;
+        if (ys_cap < 16 * (n - 1)) throw std::invalid_argument("ys buffer too small: 16 bytes per boundary");
+        zk::gcm_boundaries_host(msg, len, key, key_len, iv, aad, aad_len, c, ys);
+    });
+}
+int zkaes_gcm_commit(const uint8_t *key, size_t key_len, const uint8_t y[16], const uint8_t salt[16], uint8_t com[32]) {
+    return guard([&] {
+        if (!key || !y || !salt || !com) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        zk::gcm_commit_host(key, key_len, y, salt, com);
+    });
+}
+// Segment s is checked against (iv, ctr0 = 2 + s c, its slice of the ciphertext) and its role's further inputs: the aad and commitments[0] (head), commitments[s - 1]
+// and commitments[s] (mid), the length block built from the aad and ciphertext lengths seen HERE, the tag and commitments[n - 2] (tail).  One array of n - 1 commitments
+// serves both sides of every boundary.  A segment whose proof bytes do not parse is a rejected segment, not an error of the call
+int zkaes_verify_gcm_segments(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                              const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
+                              int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+        if (!head || !tail || !proofs || !proof_lens || !iv || !ct || !tag || !commitments || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        if (c == 0 || ct_len == 0 || ct_len > ((size_t)1 << 20) || aad_len > ((size_t)1 << 16)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block");
+        const size_t nb = (ct_len + 15) / 16, n = (nb + c - 1) / c;
+        if (n < 2) throw std::invalid_argument("GCM segments: this record fits one segment; a record that fits one proof is checked with zkaes_verify_encryption_gcm");
+        if (n_segments != n) throw std::invalid_argument("GCM segments: the record has " + std::to_string(n) + " segments of " + std::to_string(c) + " blocks");
+        if (commitments_len != 32 * (n - 1)) throw std::invalid_argument("GCM segments: one 32-byte commitment per boundary, " + std::to_string(32 * (n - 1)) + " bytes for this record");
+        if (n > 2 && !mid_or_null) throw std::invalid_argument("GCM segments: a record of more than two segments needs the mid key");
+        const size_t lt = ct_len - 16 * c * (n - 1);
+        // the verifier zero-pads the public input, so the lengths are part of the statement (as require_gcm_lengths): a key that knows its exact count pins them
+        auto exact = [](const zk::VerifyingKey &vk, size_t bits, const char *name) {
+            if (vk.num_public_inputs + 1 != vk.num_instance && vk.num_public_inputs != bits) throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths");
+        };
+        exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, "head");
+        if (n > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, "mid");
+        exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, "tail");
+        uint8_t lenblk[16];
+        for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); }
+        size_t off = 0, ok = 0;
+        for (size_t s = 0; s < n; s++) {
+            int acc = 0;
+            try {
+                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[s]);
+                uint8_t hd[16];
+                memcpy(hd, iv, 12);
+                const uint32_t ctr0 = (uint32_t)(2 + s * c);
+                for (int i = 0; i < 4; i++) hd[12 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
+                std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(hd, 16);
+                auto put = [&](const uint8_t *d, size_t len) { if (!len) return; std::vector<zk::Fr> bits = zk::ciphertext_to_public_input(d, len); pub.insert(pub.end(), bits.begin(), bits.end()); };
+                const bool first = s == 0, last = s + 1 == n;
+                if (first) put(aad, aad_len);
+                put(ct + 16 * c * s, last ? lt : 16 * c);
+                if (last) { put(lenblk, 16); put(tag, 16); }
+                if (!first) put(commitments + 32 * (s - 1), 32);
+                if (!last) put(commitments + 32 * s, 32);
+                acc = zk::verify(first ? head->vk : last ? tail->vk : mid_or_null->vk, pub, p) ? 1 : 0;
+            } catch (const std::runtime_error &) { acc = 0; }
+            if (accepted_each) accepted_each[s] = acc;
+            ok += (size_t)acc;
+            off += proof_lens[s];
+        }
+        if (n_accepted) *n_accepted = ok;
+    });
+}
 // ---- key tags (include/zkaes.h): the tag on the host, and the verifiers that check every proof of a job against ONE tag
 int zkaes_key_tag(const uint8_t *secret_key, size_t key_len, size_t tag_blocks, uint8_t *out) {
     return guard([&] {
@@ -482,6 +555,42 @@ int zkaes_circuit_matrix_pd(int kind, unsigned key_bits, unsigned key_tag_blocks
 }
 int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(zk::CIRCUIT_AES_GCM, len, aad_len, which, n_rows, nnz, rowptr, col, coeff);
+}
+// (this query also fills out[9 .. 11]: the non-zeros of the joint matrix -- the positions where A, B or C has an entry, as the indexer merges them -- and |H|, |K|, so
+// that a caller can size a record's segments against an SRS without a device)
+int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, uint64_t out[12]) {
+    return guard([&] {
+        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits);
+        fill_info(c, out);
+        uint64_t joint = 0;
+        for (size_t r = 0; r < c.num_constraints; r++) {
+            uint32_t ia = c.A.rowptr[r], ib = c.B.rowptr[r], ic = c.C.rowptr[r];
+            const uint32_t ea = c.A.rowptr[r + 1], eb = c.B.rowptr[r + 1], ec = c.C.rowptr[r + 1];
+            for (;;) {                                                                   // the per-row sorted union of the three column supports
+                uint32_t best = 0xffffffffu;
+                if (ia < ea) best = std::min(best, c.A.col[ia]);
+                if (ib < eb) best = std::min(best, c.B.col[ib]);
+                if (ic < ec) best = std::min(best, c.C.col[ic]);
+                if (best == 0xffffffffu) break;
+                joint++;
+                if (ia < ea && c.A.col[ia] == best) ia++;
+                if (ib < eb && c.B.col[ib] == best) ib++;
+                if (ic < ec && c.C.col[ic] == best) ic++;
+            }
+        }
+        out[9] = joint; out[10] = next_pow2(c.num_constraints); out[11] = next_pow2(joint);
+    });
+}
+int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return guard([&] {
+        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits);
+        const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
+        if (n_rows) *n_rows = m.rows();
+        if (nnz) *nnz = m.nnz();
+        if (rowptr) memcpy(rowptr, m.rowptr.data(), m.rowptr.size() * 4);
+        if (col) memcpy(col, m.col.data(), m.col.size() * 4);
+        if (coeff) memcpy(coeff, m.coeff.data(), m.coeff.size() * 8);
+    });
 }
 
 }  // extern "C"

@@ -608,6 +608,52 @@ Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
 // p_{i,k} = x_i & V_i[k] (16,384 and gates), then per output bit k a boolean y_k, seven booleans q_{k,0..6} and ONE row (sum_i p_{i,k} - y_k - 2 sum_j 2^j q_{k,j}) * One = 0:
 // y_k is the parity of the 128 products and q_k <= 64 their half.  The difference sits in A, as in enforce_equal, so A's row is 0 on a satisfied witness.  X_1 is the
 // first block itself; X_m = Y_{m-1} ^ block m costs one xor gate per existing bit (zero padding and the constant length block cost none).
+namespace {
+// what the lone GCM compiler and the segment compiler share of GHASH.  Bit k of a block is bit 7 - k % 8 of byte k / 8
+using Blk = std::array<Bit, 128>;
+Blk to_blk(const Byte *bytes) { Blk r; for (int k = 0; k < 128; k++) r[k] = bytes[k / 8][7 - k % 8]; return r; }
+// the V table of H at trace offset v_off: 3 xor gates a step
+std::vector<Blk> ghash_v_table(Builder &b, const std::array<Byte, 16> &h_bytes, uint32_t v_off) {
+    std::vector<Blk> V(128);
+    V[0] = to_blk(h_bytes.data());
+    for (int i = 1; i < 128; i++) {
+        const Blk &o = V[i - 1];
+        V[i][0] = o[127];
+        for (int k = 1; k < 128; k++) {
+            if (k == 1 || k == 2 || k == 7) { uint32_t mark = b.n_witness; V[i][k] = b.bxor(o[k - 1], o[127]); b.tag_bytebit(V[i][k], mark, v_off + (uint32_t)i, 7 - k); }   // (byte 0 of V_i)
+            else V[i][k] = o[k - 1];
+        }
+    }
+    return V;
+}
+// X = prev ^ blk, one xor gate per non-constant bit pair, tagged as the X of the multiplication at trace offset mul
+Blk ghash_chain_xor(Builder &b, const Blk &prev, const Blk &blk, uint32_t mul) {
+    Blk X;
+    for (int k = 0; k < 128; k++) { uint32_t mark = b.n_witness; X[k] = b.bxor(prev[k], blk[k]); b.tag_bytebit(X[k], mark, mul + TR_GCM_MUL_X + (uint32_t)(k / 8), 7 - k % 8); }
+    return X;
+}
+// Y = X H: the products, then per output bit y, seven q and the parity row
+Blk ghash_multiply(Builder &b, const Blk &X, const std::vector<Blk> &V, uint32_t mul) {
+    std::vector<Bit> p(128 * 128);
+    Blk Y;
+    for (int i = 0; i < 128; i++) for (int k = 0; k < 128; k++) {
+        uint32_t mark = b.n_witness;
+        p[128 * i + k] = b.band(X[i], V[i][k]);
+        b.tag_bytebit(p[128 * i + k], mark, mul + TR_GCM_MUL_P + (uint32_t)(128 * (k / 8) + i), 7 - k % 8);
+    }
+    for (int k = 0; k < 128; k++) {
+        Y[k] = b.alloc(false, mul + TR_GCM_MUL_Y + (uint32_t)(k / 8), 7 - k % 8);
+        LC d, one, z;
+        for (int i = 0; i < 128; i++) d.add(1, p[128 * i + k]);
+        d.add(-1, Y[k]);
+        for (int j = 0; j < 7; j++) d.add(-(int64_t)(2 << j), b.alloc(false, mul + TR_GCM_MUL_Q + (uint32_t)k, j));
+        one.add(1, 0u);
+        b.enforce(d, one, z);
+    }
+    return Y;
+}
+}  // namespace
+
 Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
@@ -616,8 +662,6 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
     if (len > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM: message and aad of one proof are limited to 65536 bytes each");
     const size_t nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TR_GCM_MULS(na, nb);
     const uint32_t gcm = (uint32_t)TRK_GCM(key_bits / 32, nb);
-    using Blk = std::array<Bit, 128>;
-    auto to_blk = [](const Byte *bytes) { Blk r; for (int k = 0; k < 128; k++) r[k] = bytes[k / 8][7 - k % 8]; return r; };
     Builder b;
     AesGates g(b, key_bits);
     std::vector<Byte> msg = g.alloc_message_and_key(len);
@@ -635,17 +679,7 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
     for (size_t bi = 0; bi < nb; bi++) ks[bi] = g.block_rounds(counter((uint32_t)bi + 2), bi);
     for (size_t i = 0; i < len; i++) ct[i] = b.xor_byte(msg[i], ks[i / 16][i % 16], gcm + (uint32_t)(TR_GCM_CT(na) + i));
     // ---- GHASH: the V table
-    std::vector<Blk> V(128);
-    V[0] = to_blk(h_bytes.data());
-    const uint32_t v_off = gcm + (uint32_t)TR_GCM_V(na, nb);
-    for (int i = 1; i < 128; i++) {
-        const Blk &o = V[i - 1];
-        V[i][0] = o[127];
-        for (int k = 1; k < 128; k++) {
-            if (k == 1 || k == 2 || k == 7) { uint32_t mark = b.n_witness; V[i][k] = b.bxor(o[k - 1], o[127]); b.tag_bytebit(V[i][k], mark, v_off + (uint32_t)i, 7 - k); }   // (byte 0 of V_i)
-            else V[i][k] = o[k - 1];
-        }
-    }
+    const std::vector<Blk> V = ghash_v_table(b, h_bytes, gcm + (uint32_t)TR_GCM_V(na, nb));
     // ---- the blocks GHASH runs over: the aad, the ciphertext (the bits of the C = M ^ S_10 gates), the length block
     std::vector<Blk> blocks;
     for (size_t j = 0; j < na; j++) blocks.push_back(to_blk(&aad[16 * j]));
@@ -656,24 +690,10 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
         blocks.push_back(to_blk(lb.data()));
     }
     Blk X = blocks[0], Y;
-    std::vector<Bit> p(128 * 128);
     for (size_t m = 0; m < n_mul; m++) {
         const uint32_t mul = gcm + (uint32_t)(TR_GCM_MUL0(na, nb) + m * TR_GCM_MUL_STRIDE);
-        if (m) for (int k = 0; k < 128; k++) { uint32_t mark = b.n_witness; X[k] = b.bxor(Y[k], blocks[m][k]); b.tag_bytebit(X[k], mark, mul + TR_GCM_MUL_X + (uint32_t)(k / 8), 7 - k % 8); }
-        for (int i = 0; i < 128; i++) for (int k = 0; k < 128; k++) {
-            uint32_t mark = b.n_witness;
-            p[128 * i + k] = b.band(X[i], V[i][k]);
-            b.tag_bytebit(p[128 * i + k], mark, mul + TR_GCM_MUL_P + (uint32_t)(128 * (k / 8) + i), 7 - k % 8);
-        }
-        for (int k = 0; k < 128; k++) {
-            Y[k] = b.alloc(false, mul + TR_GCM_MUL_Y + (uint32_t)(k / 8), 7 - k % 8);
-            LC d, one, z;
-            for (int i = 0; i < 128; i++) d.add(1, p[128 * i + k]);
-            d.add(-1, Y[k]);
-            for (int j = 0; j < 7; j++) d.add(-(int64_t)(2 << j), b.alloc(false, mul + TR_GCM_MUL_Q + (uint32_t)k, j));
-            one.add(1, 0u);
-            b.enforce(d, one, z);
-        }
+        if (m) X = ghash_chain_xor(b, Y, blocks[m], mul);
+        Y = ghash_multiply(b, X, V, mul);
     }
     // ---- tag = S ^ AES_K(J_0), then the public ciphertext and tag
     const uint32_t tag_off = gcm + (uint32_t)TR_GCM_TAG(na, nb);
@@ -692,8 +712,120 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
     return c;
 }
 
+// One segment of a GCM record.  Gate order: message and key witnesses; the 12 iv bytes, the 4 ctr0 bytes and (head) the aad as inputs; the Y_in, salt_in
+// (mid, tail) and salt_out (head, mid) witnesses; the key schedule; the rounds of the H block (slot nb) and, for a tail, of the J_0 block (slot nb + 1); per data block
+// from the second on the incrementer over the previous block's low 32 counter bits (position 0 folds away as in CTR: 31 xor and 30 and gates, no carry out of
+// position 31) and the block's rounds from iv || counter; one xor gate per existing message bit; the ciphertext inputs and (tail) the 128 length-block inputs; the V
+// table; GHASH -- a head starts at its first block as the lone circuit does, a mid or tail with X_0 = Y_in ^ C_0, and a tail's last multiplication runs over the
+// length-block INPUTS; (tail) the tag's xor gates and inputs; last com_in (mid, tail), then com_out (head, mid): 256 inputs each, one compression from the constant
+// initial value over key || zeros || Y || salt, 256 equalities.
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits) {
+    require_key_bits(key_bits);
+    if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw std::invalid_argument("GCM segment: the role must be 0 (head), 1 (mid) or 2 (tail)");
+    if (units == 0) throw std::invalid_argument("GCM segment: a head or mid has at least one data block, a tail at least one byte");
+    if (role != TRS_HEAD && alen) throw std::invalid_argument("GCM segment: only the head segment takes the aad");
+    if (units > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM segment: message and aad of one proof are limited to 65536 bytes each");
+    const bool begins = role == TRS_HEAD, ends = role == TRS_TAIL;
+    const size_t len = ends ? units : 16 * units, nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TRS_MULS(role, na, nb);
+    const int nk = (int)(key_bits / 32);
+    const uint32_t gcm = (uint32_t)TRS_GCM(nk, role, nb), sg = gcm + (uint32_t)TRS_SEG(role, na, nb);
+    Builder b;
+    AesGates g(b, key_bits);
+    std::vector<Byte> msg = g.alloc_message_and_key(len);
+    std::array<Byte, 16> in, yin, salt_in, salt_out;
+    for (int i = 0; i < 16; i++) in[i] = b.alloc_byte(true, gcm + TR_GCM_IV + (uint32_t)i);          // iv, then ctr0
+    std::vector<Byte> aad(16 * na, Builder::const_byte(0)), ct(16 * nb, Builder::const_byte(0));
+    for (size_t i = 0; i < alen; i++) aad[i] = b.alloc_byte(true, gcm + TR_GCM_AAD + (uint32_t)i);
+    if (!begins) for (int i = 0; i < 16; i++) yin[i] = b.alloc_byte(false, sg + TRS_YIN + (uint32_t)i);
+    if (!begins) for (int i = 0; i < 16; i++) salt_in[i] = b.alloc_byte(false, sg + TRS_SALT_IN + (uint32_t)i);
+    if (!ends) for (int i = 0; i < 16; i++) salt_out[i] = b.alloc_byte(false, sg + TRS_SALT_OUT + (uint32_t)i);
+    g.key_schedule();
+    std::array<Byte, 16> zero, j0 = in;
+    for (int i = 0; i < 16; i++) zero[i] = Builder::const_byte(0);
+    const std::array<Byte, 16> h_bytes = g.block_rounds(zero.data(), nb);
+    std::array<Byte, 16> ej0;
+    if (ends) {
+        for (int i = 0; i < 4; i++) j0[12 + i] = Builder::const_byte(i == 3 ? 1 : 0);
+        ej0 = g.block_rounds(j0.data(), nb + 1);
+    }
+    for (size_t bi = 0; bi < nb; bi++) {
+        if (bi) {
+            const uint32_t slot = sg + (uint32_t)(TRS_BLOCK_CTR0 + bi * TRS_BLOCK_CTR_STRIDE);
+            std::array<Byte, 16> next = in;
+            Bit carry = Bit::konst(true);
+            for (int i = 0; i < 32; i++) {
+                const uint32_t byte = (uint32_t)(3 - i / 8);
+                Bit x = in[12 + byte][i % 8];
+                uint32_t mark = b.n_witness;
+                next[12 + byte][i % 8] = b.bxor(x, carry);
+                b.tag_bytebit(next[12 + byte][i % 8], mark, slot + TRS_BL_CTR + byte, i % 8);
+                if (i == 31) break;
+                mark = b.n_witness;
+                carry = b.band(x, carry);
+                b.tag_bytebit(carry, mark, slot + TRS_BL_CARRY + byte, i % 8);
+            }
+            in = next;
+        }
+        const std::array<Byte, 16> ks = g.block_rounds(in.data(), bi);
+        for (size_t i = 0; i < 16 && 16 * bi + i < len; i++) ct[16 * bi + i] = b.xor_byte(msg[16 * bi + i], ks[i], gcm + (uint32_t)(TR_GCM_CT(na) + 16 * bi + i));
+    }
+    for (size_t i = 0; i < len; i++) {
+        Byte pi = b.alloc_byte(true, gcm + (uint32_t)(TR_GCM_CT(na) + i));
+        for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
+    }
+    std::array<Byte, 16> lb;
+    if (ends) for (int i = 0; i < 16; i++) lb[i] = b.alloc_byte(true, sg + TRS_LEN + (uint32_t)i);
+    // ---- GHASH
+    const std::vector<Blk> V = ghash_v_table(b, h_bytes, gcm + (uint32_t)TR_GCM_V(na, nb));
+    std::vector<Blk> blocks;
+    for (size_t j = 0; j < na; j++) blocks.push_back(to_blk(&aad[16 * j]));
+    for (size_t j = 0; j < nb; j++) blocks.push_back(to_blk(&ct[16 * j]));
+    if (ends) blocks.push_back(to_blk(lb.data()));
+    Blk X, Y;
+    if (!begins) Y = to_blk(yin.data());
+    for (size_t m = 0; m < n_mul; m++) {
+        const uint32_t mul = gcm + (uint32_t)(TR_GCM_MUL0(na, nb) + m * TR_GCM_MUL_STRIDE);
+        if (m || !begins) X = ghash_chain_xor(b, Y, blocks[m], mul); else X = blocks[0];
+        Y = ghash_multiply(b, X, V, mul);
+    }
+    if (ends) {
+        const uint32_t tag_off = gcm + (uint32_t)TRS_TAG(role, na, nb);
+        std::array<Byte, 16> tag;
+        for (int j = 0; j < 16; j++) { Byte s; for (int bit = 0; bit < 8; bit++) s[bit] = Y[8 * j + 7 - bit]; tag[j] = b.xor_byte(s, ej0[j], tag_off + (uint32_t)j); }
+        for (int j = 0; j < 16; j++) {
+            Byte pi = b.alloc_byte(true, tag_off + (uint32_t)j);
+            for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], tag[j][k]);
+        }
+    }
+    // ---- the boundary commitments
+    Sha256Gates sha(b);
+    auto commit = [&](const std::array<Byte, 16> &y, const std::array<Byte, 16> &salt, uint32_t com_off, uint32_t slot) {
+        std::array<Byte, 64> blk;
+        for (size_t i = 0; i < 32; i++) blk[i] = i < g.key_bytes() ? g.key[i] : Builder::const_byte(0);
+        for (int i = 0; i < 16; i++) { blk[32 + i] = y[i]; blk[48 + i] = salt[i]; }
+        std::array<Byte, 32> pi;
+        for (int j = 0; j < 32; j++) pi[j] = b.alloc_byte(true, com_off + (uint32_t)j);
+        std::array<Word, 8> st;
+        for (int k = 0; k < 8; k++) st[k] = Sha256Gates::const_word(SHA256_IV[k]);
+        std::array<Word, 16> words;
+        for (int t = 0; t < 16; t++) words[t] = Sha256Gates::be_word(&blk[4 * t]);
+        st = sha.compress(st, words, slot);
+        for (int j = 0; j < 32; j++) for (int k = 0; k < 8; k++) b.enforce_equal(pi[j][k], st[j / 4][8 * (3 - j % 4) + k]);
+    };
+    if (!begins) commit(yin, salt_in, sg + TRS_COM_IN, sg + (uint32_t)TRS_SLOT_IN(nb));
+    if (!ends) {
+        std::array<Byte, 16> yout;
+        for (int j = 0; j < 16; j++) for (int bit = 0; bit < 8; bit++) yout[j][bit] = Y[8 * j + 7 - bit];
+        commit(yout, salt_out, sg + TRS_COM_OUT, sg + (uint32_t)TRS_SLOT_OUT(nb));
+    }
+    Circuit c = finish(b, CIRCUIT_AES_GCM_SEG, nb, TRS_BYTES(nk, role, na, nb), g.key_bytes());
+    c.message_bytes = len; c.aad_bytes = alen; c.seg_role = role; c.seg_off = sg;
+    return c;
+}
+
 Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
-    if (kind == CIRCUIT_AES_GCM) return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    if (kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment circuit has a role: use the _gcm_seg entry points (zkaes_circuit_info_gcm_seg, zkaes_synthesize_keys_gcm_seg)");
+    if (kind == CIRCUIT_AES_GCM)return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
     if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
     if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
     if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
@@ -843,6 +975,40 @@ void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key,
     for (int i = 0; i < 8; i++) { tag[i] = (uint8_t)((y.hi >> (56 - 8 * i)) ^ s[i]); tag[8 + i] = (uint8_t)((y.lo >> (56 - 8 * i)) ^ s[8 + i]); }
 }
 
+void gcm_boundaries_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, uint8_t *ys) {
+    if (len == 0 || c == 0) throw std::invalid_argument("gcm_boundaries: the record must have at least one byte and a segment at least one block");
+    std::vector<uint8_t> ct(len);
+    uint8_t tag[16], hb[16] = {0}, blk[16];
+    aes128_gcm_encrypt_host(msg, len, key, iv, aad, aad_len, ct.data(), tag, key_len);
+    HostAes128 aes(key, key_len);
+    aes.encrypt_block(hb);
+    const Gf128 h = gf_load(hb);
+    Gf128 y;
+    for (size_t off = 0; off < aad_len; off += 16) {
+        for (size_t i = 0; i < 16; i++) blk[i] = off + i < aad_len ? aad[off + i] : 0;
+        Gf128 x = gf_load(blk);
+        x.hi ^= y.hi; x.lo ^= y.lo;
+        y = gf_mul(x, h);
+    }
+    const size_t nb = (len + 15) / 16, n = (nb + c - 1) / c;
+    for (size_t bi = 0; bi < nb; bi++) {
+        for (size_t i = 0; i < 16; i++) blk[i] = 16 * bi + i < len ? ct[16 * bi + i] : 0;
+        Gf128 x = gf_load(blk);
+        x.hi ^= y.hi; x.lo ^= y.lo;
+        y = gf_mul(x, h);
+        if ((bi + 1) % c == 0 && (bi + 1) / c < n)                                  // the last block of segment s = (bi + 1) / c - 1 < n - 1
+            for (int i = 0; i < 8; i++) { ys[16 * ((bi + 1) / c - 1) + i] = (uint8_t)(y.hi >> (56 - 8 * i)); ys[16 * ((bi + 1) / c - 1) + 8 + i] = (uint8_t)(y.lo >> (56 - 8 * i)); }
+    }
+}
+
+void gcm_commit_host(const uint8_t *key, size_t key_len, const uint8_t y[16], const uint8_t salt[16], uint8_t com[32]) {
+    if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes");
+    uint8_t blk[64] = {0};
+    for (size_t i = 0; i < key_len; i++) blk[i] = key[i];
+    for (int i = 0; i < 16; i++) { blk[32 + i] = y[i]; blk[48 + i] = salt[i]; }
+    sha256_chain(nullptr, blk, 64, com);
+}
+
 // src/ops.rs:8-29.  Trace: x (4 B LE) | y (4 B LE) | result (8 B LE)
 Circuit compile_ops_circuit(int kind) {
     Builder b;
@@ -915,7 +1081,7 @@ void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *ta
 }
 
 size_t mode_header_bytes(const Circuit &c) {
-    return c.kind == CIRCUIT_AES_GCM ? 12 + c.aad_bytes : (c.kind == CIRCUIT_AES_CBC || c.kind == CIRCUIT_AES_CTR) ? 16 : 0;
+    return c.kind == CIRCUIT_AES_GCM_SEG ? TRS_HDR_BYTES(c.aad_bytes) : c.kind == CIRCUIT_AES_GCM ? 12 + c.aad_bytes : (c.kind == CIRCUIT_AES_CBC || c.kind == CIRCUIT_AES_CTR) ? 16 : 0;
 }
 
 }  // namespace zk

@@ -22,7 +22,7 @@ struct CsrMatrix {
     size_t nnz() const { return col.size(); }
 };
 
-enum CircuitKind { CIRCUIT_AES = 0, CIRCUIT_OPS_XOR = 1, CIRCUIT_OPS_ADD = 2, CIRCUIT_AES_CBC = 3, CIRCUIT_AES_CTR = 4, CIRCUIT_AES_GCM = 5 };
+enum CircuitKind { CIRCUIT_AES = 0, CIRCUIT_OPS_XOR = 1, CIRCUIT_OPS_ADD = 2, CIRCUIT_AES_CBC = 3, CIRCUIT_AES_CTR = 4, CIRCUIT_AES_GCM = 5, CIRCUIT_AES_GCM_SEG = 6 };
 
 struct Circuit {
     int kind = CIRCUIT_AES;
@@ -45,6 +45,8 @@ struct Circuit {
     uint64_t digest_prefix = 0;          // final keys: P, the message bytes hashed ahead of this proof's (a multiple of 64); the padding's length field is 8 (P + message_bytes)
     size_t digest_blocks = 0;            // compressions per proof (trace_layout.h TRD_BLOCKS), 0 when D = 0
     size_t digest_off = 0;               // trace offset of the digest region (trace_layout.h TRD), 0 when D = 0
+    int seg_role = -1;                   // a GCM segment key (kind CIRCUIT_AES_GCM_SEG): 0 head, 1 mid, 2 tail (trace_layout.h TRS_*); -1 for every other key
+    size_t seg_off = 0;                  // trace offset of the segment region (trace_layout.h TRS_SEG), 0 for every other key
     size_t num_variables() const { return num_instance + num_witness; }
 };
 
@@ -71,6 +73,13 @@ Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128, size_
 // message and key.  The trace holds nb + 2 AES blocks (the message blocks under iv || be32(b + 2), H = AES_K(0), AES_K(iv || 1)), the V table of H and, per GHASH block,
 // one multiplication by H as 16,384 and gates and 128 parity rows.  message_len >= 1, aad_len >= 0; both are fixed by the key (else std::invalid_argument)
 Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+// One segment of a GCM record longer than one proof.  role = 0 head, 1 mid, 2 tail; units = c, the data blocks of a head or mid segment, or Lt, the
+// 1 .. 16 c bytes of a tail; aad_len = the record's whole aad (head only, else 0).  Public input, in order: iv (12 bytes), ctr0 (4, big-endian: the counter of the
+// segment's first data block), head: aad, ciphertext, com_out (32); mid: ciphertext, com_in, com_out; tail: ciphertext, the length block be64(8 A) || be64(8 L) of the
+// whole record (16), tag (16), com_in.  Private: message, key, Y_in (the GHASH accumulator entering a mid or tail), the salts.  A commitment is ONE SHA-256 compression
+// from the initial value over key || zeros to 32 bytes || Y || salt.  Block b runs under iv || (ctr0 + b mod 2^32), by CTR's xor/and incrementer over the low 32 bits.
+// No key tag and no digest; anything out of range is std::invalid_argument
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
 // 128, key_tag_blocks 0 and digest_kind 0 for the ops kinds
 Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
@@ -79,7 +88,8 @@ Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t
 // sha256_finish: digest = the chain from h_in over tail || 0x80 || zeros || be64(8 (prefix_bytes + tail_len)); prefix_bytes a multiple of 64, prefix_bytes + tail_len < 2^61
 void sha256_chain(const uint8_t *h_in, const uint8_t *data, size_t len, uint8_t h_out[32]);
 void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *tail, size_t tail_len, uint8_t digest[32]);
-// the bytes of the per-proof public header a key's mode takes ahead of a digest key's H_in: 0 (ECB), 16 (CBC, CTR), 12 + aad_bytes (GCM)
+// the bytes of the per-proof public header a key's mode takes ahead of a digest key's H_in: 0 (ECB), 16 (CBC, CTR), 12 + aad_bytes (GCM); for a GCM segment key the
+// 80 + aad_bytes of a segment header (trace_layout.h TRS_HDR_*), which also carries that proof's witnesses Y_in and the salts
 size_t mode_header_bytes(const Circuit &c);
 // the key tag itself on the host: out = 16 tag_blocks bytes, AES_K(D_0) (|| AES_K(D_1)); key_len = 16, 24 or 32, tag_blocks = 1 or 2 (else std::invalid_argument)
 void aes_key_tag_host(const uint8_t *key, size_t key_len, size_t tag_blocks, uint8_t *out);
@@ -97,5 +107,10 @@ void aes128_ctr_crypt_host(const uint8_t *in, size_t len, const uint8_t *key, co
 void ctr_counter_add(const uint8_t counter[16], uint64_t n, uint8_t out[16]);
 // AES-128-GCM encryption on the host (SP 800-38D 7.1 with a 96-bit IV): ct = len bytes (any len >= 0), tag = 16 bytes; GHASH by Algorithm 1, bit by bit
 void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *ct, uint8_t tag[16], size_t key_len = 16);
+// GCM segments on the host.  gcm_boundaries_host: ys = 16 (n - 1) bytes, Y_s = the GHASH accumulator of the record after the last data block of segment
+// s < n - 1, n = ceil(len / (16 c)) segments of c data blocks; len >= 1, c >= 1.  gcm_commit_host: com = the one SHA-256 compression from the initial value over
+// key || zeros to 32 bytes || y || salt
+void gcm_boundaries_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, uint8_t *ys);
+void gcm_commit_host(const uint8_t *key, size_t key_len, const uint8_t y[16], const uint8_t salt[16], uint8_t com[32]);
 
 }  // namespace zk

@@ -272,6 +272,16 @@ void key_tag_trace(uint8_t *trace, size_t trace_stride, size_t tag_off, const ui
 // kernel on the same stream, it writes bytes disjoint from theirs.  stride >= digest_off + 64 + compressions x 4032; stride, digest_off and the trace 16-byte aligned
 void sha256_trace(uint8_t *trace, size_t trace_stride, size_t digest_off, const uint8_t *msgs, const uint8_t *hdrs, size_t hdr_stride, size_t hin_off, uint32_t nproofs, size_t msg_len, int digest_kind,
                   uint64_t digest_prefix, stream_t s);
+// GCM segments (trace_layout.h TRS_*): role = 0 head, 1 mid, 2 tail; msg_len = 16 c for a head or mid, 1 .. 16 c for a tail; aad_len = 0 except for a
+// head; hdrs = nproofs x TRS_HDR_BYTES(aad_len) bytes (iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad).  aes_trace_gcm_seg fills the AES slots, the header
+// part of the tail and of the segment region and the per-block counters; ghash_trace_seg behind it the V table, the multiplications from Y_in on and a tail's tag;
+// commit_trace behind that (seg_off = the region's offset, yout_off = the last multiplication's Y) the commitments and their compression slots.  stride >= TRS_BYTES,
+// stride and trace 16-byte aligned
+void aes_trace_gcm_seg(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, stream_t s,
+                       size_t key_bytes = 16);
+void ghash_trace_seg(uint8_t *trace, size_t trace_stride, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes = 16);
+void commit_trace(uint8_t *trace, size_t trace_stride, size_t seg_off, size_t yout_off, const uint8_t *keys, size_t key_bytes, const uint8_t *hdrs, size_t hdr_stride, uint32_t nproofs, int role,
+                  uint32_t nblocks, stream_t s);
 // z[col] (0/1 bytes) for every column, by descriptor
 void witness_expand(uint8_t *z, const uint32_t *desc, uint32_t ncols, const uint8_t *trace, const uint32_t *sbox_in_off, const uint32_t *sbox_tmpl, stream_t s);
 // out[r] = sum_i coeff[i] * z[col[i]] as a field element, rows with no entries give 0 (out has `rows_out` >= rows entries, tail zeroed)

@@ -5,6 +5,8 @@
 //                    proof's public header, re-walks compressions 0 .. c - 1 in registers without a store -- the way a CBC lane re-walks its chain -- then runs
 //                    compression c and stores every word of its slot.  Lane c = 0 also stores H_in, the last lane H_out.  The kernel is handed message and H_in only, never
 //                    a state made on the host: the host's hash and the device's meet in the constraints.
+//   k_commit_trace   the boundary commitments of a GCM segment: one lane per commitment, ONE compression from the initial value over key || zeros || Y ||
+//                    salt through the same sha_compress, into the segment region's slots.
 // Every byte of the region has exactly one writer and no byte ahead of it is touched; no LDS, no barrier, no cross-lane operation.  The 16-word schedule ring and the
 // eight state words live in registers: the 64 rounds are fully unrolled, so every index into the ring is a constant.
 #include "hip_util.hpp"
@@ -109,6 +111,39 @@ __global__ void k_sha256_trace(uint8_t *__restrict__ trace, size_t stride, size_
     }
 }
 
+// The boundary commitments of a GCM segment (trace_layout.h TRS_*), launched behind the segment's GHASH kernel on the same stream: com_out needs Y_out,
+// the Y of the segment's last multiplication, which it reads from the trace at yout_off.  nproofs * ncom lanes, ncom = 2 for a mid (com_in, then com_out) and 1 for a
+// head (com_out) or a tail (com_in).  A lane builds the one 64-byte block key || zeros to 32 bytes || Y || salt -- the key from the key buffer, Y_in and the salts from
+// the proof's header -- runs the compression of k_sha256_trace from the initial value with every store into its slot, and stores the 32 commitment bytes.  It is never
+// handed a commitment made on the host.  One writer per byte, no byte ahead of the segment region touched; no LDS, no barrier, no cross-lane operation.
+__global__ void k_commit_trace(uint8_t *__restrict__ trace, size_t stride, size_t seg_off, size_t yout_off, const uint8_t *__restrict__ keys, uint32_t key_bytes, const uint8_t *__restrict__ hdrs,
+                               size_t hdr_stride, uint32_t nproofs, uint32_t role, uint32_t nblocks) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t ncom = role == TRS_MID ? 2 : 1;
+    if (t >= nproofs * ncom) return;
+    const uint32_t p = t / ncom;
+    const bool out = role == TRS_HEAD || (role == TRS_MID && t % ncom == 1);
+    uint8_t *tr = trace + (size_t)p * stride, *sg = tr + seg_off;
+    const uint8_t *key = keys + (size_t)key_bytes * p, *hdr = hdrs + hdr_stride * p;
+    const uint8_t *y = out ? tr + yout_off : hdr + TRS_HDR_YIN, *salt = hdr + (out ? TRS_HDR_SALT_OUT : TRS_HDR_SALT_IN);
+    uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19}, w[16];      // FIPS 180-4 5.3.3
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t at = 4 * (uint32_t)q + (uint32_t)i;
+            const uint32_t byte = at < 32 ? (at < key_bytes ? key[at] : 0) : at < 48 ? y[at - 32] : salt[at - 48];
+            v = (v << 8) | byte;
+        }
+        w[q] = v;
+    }
+    sha_compress<true>(st, w, reinterpret_cast<uint32_t *>(sg + (out ? TRS_SLOT_OUT((size_t)nblocks) : TRS_SLOT_IN((size_t)nblocks))));
+    uint32_t *o = reinterpret_cast<uint32_t *>(sg + (out ? TRS_COM_OUT : TRS_COM_IN));
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = __builtin_bswap32(st[k]);                     // the big-endian serialisation, as H_in and H_out of a digest
+}
+
 // what the entry checks before any lane runs: the digest kind, the prefix, the message length against the kind, the slots inside the stride, and 16-byte alignment of the
 // region and of every trace
 void sha256_trace(uint8_t *trace, size_t stride, size_t digest_off, const uint8_t *msgs, const uint8_t *hdrs, size_t hdr_stride, size_t hin_off, uint32_t nproofs, size_t msg_len, int digest_kind,
@@ -128,6 +163,25 @@ void sha256_trace(uint8_t *trace, size_t stride, size_t digest_off, const uint8_
     const dim3 grid((lanes + 63) / 64), block(64);
     hipLaunchKernelGGL(k_sha256_trace, grid, block, 0, (hipStream_t)s, trace, stride, digest_off, msgs, hdrs, hdr_stride, hin_off, nproofs, (uint32_t)nblk, (uint32_t)msg_len, (uint32_t)digest_kind,
                        8 * (digest_prefix + (uint64_t)msg_len));
+    HIP_LAUNCH_CHECK();
+}
+
+// the commitment entry's checks ahead of the launch: the role, the key size, the segment region and Y_out inside the stride, the header stride, 16-byte alignment
+void commit_trace(uint8_t *trace, size_t stride, size_t seg_off, size_t yout_off, const uint8_t *keys, size_t key_bytes, const uint8_t *hdrs, size_t hdr_stride, uint32_t nproofs, int role,
+                  uint32_t nblocks, stream_t s) {
+    if (!trace || !keys || !hdrs) throw GpuError("commit_trace: no trace, key or header buffer");
+    if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw GpuError("commit_trace: the role must be 0 (head), 1 (mid) or 2 (tail)");
+    if (key_bytes != 16 && key_bytes != 24 && key_bytes != 32) throw GpuError("commit_trace: the AES key must have 16, 24 or 32 bytes");
+    if (nblocks == 0 || nblocks > (1u << 12)) throw GpuError("commit_trace: 1 .. 4096 data blocks per segment");
+    if (hdr_stride < TRS_HDR_BYTES(0)) throw GpuError("commit_trace: the header stride does not hold Y_in and the salts");
+    const size_t need = TRS_SEG_BYTES((size_t)nblocks);
+    if (seg_off > stride || stride - seg_off < need || yout_off > seg_off || seg_off - yout_off < 16)
+        throw GpuError("commit_trace: trace stride " + std::to_string(stride) + " does not hold a segment region of " + std::to_string(need) + " bytes at offset " + std::to_string(seg_off));
+    if (seg_off % 16 || stride % 16 || (uintptr_t)trace % 16) throw GpuError("commit_trace: segment traces and the region's offset must be 16-byte aligned");
+    if (nproofs == 0 || nproofs > (1u << 20)) throw GpuError("commit_trace: 1 .. 2^20 proofs per launch");
+    const uint32_t lanes = nproofs * (role == TRS_MID ? 2u : 1u);
+    const dim3 grid((lanes + 63) / 64), block(64);
+    hipLaunchKernelGGL(k_commit_trace, grid, block, 0, (hipStream_t)s, trace, stride, seg_off, yout_off, keys, (uint32_t)key_bytes, hdrs, hdr_stride, nproofs, (uint32_t)role, nblocks);
     HIP_LAUNCH_CHECK();
 }
 

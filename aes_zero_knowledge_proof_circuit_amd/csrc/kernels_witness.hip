@@ -9,6 +9,8 @@
 //   k_aes_trace_gcm   AES-GCM's nb + 2 AES blocks (the message under inc32 counters, H, the tag mask), and behind it
 //   k_ghash_trace     the GHASH half: the V table of H and, per block, the 16,384 partial products, carries and result of
 //                     one multiplication in GF(2^128), sixteen lanes per multiplication, each re-walking the chain in registers,
+//   k_aes_trace_gcm_seg, k_ghash_trace_seg   the same two for one segment of a GCM record longer than one proof: counters from a public ctr0 with their
+//                     carries, the chain from a hidden Y_in, a tail's last multiplication over the public length block; k_commit_trace (kernels_digest.hip) follows,
 //   k_key_tag_trace   for a key with key-tag blocks, behind any of the above: AES of the constant blocks D_t under the proof's key into the slots behind the mode's tail,
 //   k_witness_expand  one lane per column of z: decode the variable's descriptor (compiled once by circuit.cpp) and gather
 //                     its bit -- S-box mux-tree variables are a table lookup S[(node << (level+1)) | (x & mask)],
@@ -328,6 +330,107 @@ __global__ void k_key_tag_trace(uint8_t *__restrict__ trace, size_t stride, size
     }
     aes_block_rounds<true, NK>(s, w, sbox, bl);
 }
+
+// GCM segments (trace_layout.h TRS_*), the AES half, in the shape of k_aes_trace_gcm.  role = TRS_HEAD, TRS_MID or TRS_TAIL; nslots = nblocks + 1 AES
+// slots, one more for a tail.  nproofs * (nslots + 1) lanes.  Lane (p, 0) writes the key schedule part and the proof's header: iv and ctr0 into the tail's iv slot,
+// the aad (head), and Y_in, the two salts and the length block into the segment region.  Lane (p, 1 + s) is AES slot s: data block s < nblocks under
+// iv || be32(ctr0 + s mod 2^32), with its counter and carry bytes stored in the segment region, then H from the zero block, then (tail) J_0 = iv || 00000001.  A data
+// lane stores C_s = M_s ^ S_Nr for the bytes that exist and zeros behind them.  hdrs: nproofs x TRS_HDR_BYTES(aad_len) bytes; the kernel is handed key, iv, ctr0, aad,
+// message, Y_in, the salts and the length block only.
+template <int NK = 4>
+__global__ void k_aes_trace_gcm_seg(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ hdrs,
+                                    uint32_t nproofs, uint32_t role, uint32_t nblocks, uint32_t naad, uint32_t msg_len, uint32_t aad_len, const uint8_t *__restrict__ sbox) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nslots = TRS_SLOTS(role, nblocks);
+    if (t >= nproofs * (nslots + 1)) return;
+    uint32_t p = t / (nslots + 1), which = t % (nslots + 1);
+    uint8_t *tr = trace + (size_t)p * stride;
+    const uint8_t *key = keys + TRK_KEY_BYTES(NK) * (size_t)p, *hdr = hdrs + (size_t)p * TRS_HDR_BYTES((size_t)aad_len);
+    uint8_t w[TRK_KS_WORDS(NK)][4];
+    aes_key_schedule<NK>(key, sbox, w, which == 0 ? tr : nullptr);
+    uint8_t *tail = tr + TRS_GCM(NK, role, (size_t)nblocks), *sg = tail + TRS_SEG(role, (size_t)naad, (size_t)nblocks);
+    if (which == 0) {
+        aes_store_schedule<NK>(tr, key, w);
+        for (int i = 0; i < 16; i++) tail[TR_GCM_IV + i] = hdr[TRS_HDR_IV + i];                  // (iv, then ctr0)
+        for (uint32_t i = 0; i < 16 * naad; i++) tail[TR_GCM_AAD + i] = i < aad_len ? hdr[TRS_HDR_AAD + i] : 0;
+        for (int i = 0; i < 16; i++) {
+            sg[TRS_YIN + i] = hdr[TRS_HDR_YIN + i]; sg[TRS_SALT_IN + i] = hdr[TRS_HDR_SALT_IN + i];
+            sg[TRS_SALT_OUT + i] = hdr[TRS_HDR_SALT_OUT + i]; sg[TRS_LEN + i] = hdr[TRS_HDR_LEN + i];
+        }
+        return;
+    }
+    uint32_t slot = which - 1;
+    uint8_t *bl = tr + TRK_BLOCK0(NK) + (size_t)slot * TRK_BLOCK_STRIDE(NK);
+    uint8_t in[16], s[16], m[16];
+    const uint32_t ctr0 = (uint32_t)hdr[TRS_HDR_CTR0] << 24 | (uint32_t)hdr[TRS_HDR_CTR0 + 1] << 16 | (uint32_t)hdr[TRS_HDR_CTR0 + 2] << 8 | hdr[TRS_HDR_CTR0 + 3];
+    uint32_t ctr = slot < nblocks ? ctr0 + slot : 1, have = 0;
+    for (int i = 0; i < 16; i++) in[i] = slot == nblocks ? 0 : (i < 12 ? hdr[TRS_HDR_IV + i] : (uint8_t)(ctr >> (8 * (15 - i))));
+    if (slot < nblocks) {
+        have = msg_len - 16 * slot < 16 ? msg_len - 16 * slot : 16;                                  // (16 slot < msg_len: nblocks = ceil(msg_len / 16))
+        uint8_t *cs = sg + TRS_BLOCK_CTR0 + (size_t)slot * TRS_BLOCK_CTR_STRIDE;
+        const uint32_t prev = ctr - 1;
+        uint32_t carry = 0;
+        if (slot) for (int i = 0; i < 31 && ((prev >> i) & 1); i++) carry |= 1u << i;              // (no carry out of position 31: the sum is mod 2^32)
+        for (int i = 0; i < 4; i++) { cs[TRS_BL_CTR + i] = (uint8_t)(ctr >> (24 - 8 * i)); cs[TRS_BL_CARRY + i] = (uint8_t)(carry >> (24 - 8 * i)); }
+    }
+    const uint8_t *msg = msgs + (size_t)p * msg_len + 16 * (size_t)(slot < nblocks ? slot : 0);      // (not read by the H and J_0 lanes: have = 0)
+    for (uint32_t i = 0; i < 16; i++) m[i] = i < have ? msg[i] : 0;
+    for (int i = 0; i < 16; i++) { bl[TR_BL_MSG + i] = m[i]; s[i] = in[i] ^ key[i]; bl[TR_BL_S + i] = s[i]; }
+    aes_block_rounds<true, NK>(s, w, sbox, bl);
+    if (slot < nblocks) for (uint32_t i = 0; i < 16; i++) tail[TR_GCM_CT(naad) + 16 * slot + i] = i < have ? (uint8_t)(m[i] ^ s[i]) : 0;
+}
+
+// GCM segments, the GHASH half, in the shape of k_ghash_trace and launched behind k_aes_trace_gcm_seg on the same stream: it reads H, the aad, every C_b, Y_in, the
+// length block and (tail) S_Nr of the J_0 slot from the trace.  nproofs * (n_mul + 1) * 16 lanes, n_mul = TRS_MULS.  The chain starts from zero for a head and from Y_in
+// otherwise; the blocks are the aad (head), the C_b and, as a tail's last, the length block.  Only the lanes of a tail's last multiplication store a tag byte.  Every
+// byte has exactly one writer; no LDS, no barrier, no cross-lane operation.
+template <int NK = 4>
+__global__ void k_ghash_trace_seg(uint8_t *__restrict__ trace, size_t stride, uint32_t nproofs, uint32_t role, uint32_t nblocks, uint32_t naad) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n_mul = TRS_MULS(role, naad, nblocks), per_proof = (n_mul + 1) * 16;
+    if (t >= nproofs * per_proof) return;
+    uint32_t p = t / per_proof, m = (t % per_proof) / 16, j = t % 16;
+    uint8_t *tr = trace + (size_t)p * stride, *tail = tr + TRS_GCM(NK, role, (size_t)nblocks), *sg = tail + TRS_SEG(role, (size_t)naad, (size_t)nblocks);
+    const Gf128 h = gf_load(tr + TRK_BLOCK0(NK) + (size_t)nblocks * TRK_BLOCK_STRIDE(NK) + TRK_BL_CT(NK));
+    Gf128 v = h;
+    if (m == n_mul) {
+        uint8_t *col = tail + TR_GCM_V(naad, nblocks) + 128 * j;
+        for (int c = 0; c < 8; c++) {
+            Bytes16 o;
+            for (int u = 0; u < 16; u++) { o.b[u] = gf_byte(v, j); gf_times_alpha(v); }
+            *reinterpret_cast<Bytes16 *>(col + 16 * c) = o;
+        }
+        return;
+    }
+    Gf128 x = {0, 0};
+    if (role != TRS_HEAD) x = gf_load(sg + TRS_YIN);
+    for (uint32_t mm = 0;; mm++) {
+        const Gf128 blk = gf_load(mm < naad + nblocks ? tail + TR_GCM_AAD + 16 * (size_t)mm : sg + TRS_LEN);       // (the C_b lie right behind the aad blocks)
+        x.hi ^= blk.hi; x.lo ^= blk.lo;
+        if (mm == m) break;
+        x = gf_mul(x, h);
+    }
+    uint8_t *mul = tail + TR_GCM_MUL0(naad, nblocks) + (size_t)m * TR_GCM_MUL_STRIDE;
+    mul[TR_GCM_MUL_X + j] = gf_byte(x, j);
+    uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};                // how many of the 128 products are set, per bit of byte j
+    for (int c = 0; c < 8; c++) {
+        Bytes16 o;
+        for (int u = 0; u < 16; u++) {
+            uint8_t pb = gf_bit(x, 16 * c + u) ? gf_byte(v, j) : 0;
+            o.b[u] = pb;
+            for (int bit = 0; bit < 8; bit++) cnt[bit] += (pb >> bit) & 1u;
+            gf_times_alpha(v);
+        }
+        *reinterpret_cast<Bytes16 *>(mul + TR_GCM_MUL_P + 128 * j + 16 * c) = o;
+    }
+    uint8_t y = 0;
+    for (int bit = 0; bit < 8; bit++) {                         // output bit k = 8 j + 7 - bit
+        mul[TR_GCM_MUL_Q + 8 * j + 7 - bit] = (uint8_t)(cnt[bit] >> 1);
+        y |= (uint8_t)((cnt[bit] & 1u) << bit);
+    }
+    mul[TR_GCM_MUL_Y + j] = y;
+    if (role == TRS_TAIL && m + 1 == n_mul) tail[TRS_TAG(role, naad, nblocks) + j] = y ^ tr[TRK_BLOCK0(NK) + (size_t)(nblocks + 1) * TRK_BLOCK_STRIDE(NK) + TRK_BL_CT(NK) + j];
+}
 template <bool CBC>
 static void launch_aes_trace(const char *who, uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *ivs, uint32_t nproofs, uint32_t nblocks, size_t key_bytes, stream_t s) {
     // the stride must hold the trace of THIS key size: a caller that sized its buffer for another one gets an error here, never lanes that store past a trace
@@ -399,6 +502,44 @@ void ghash_trace(uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_l
     if (nk == 4) hipLaunchKernelGGL(k_ghash_trace<4>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
     else if (nk == 6) hipLaunchKernelGGL(k_ghash_trace<6>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
     else hipLaunchKernelGGL(k_ghash_trace<8>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, nblocks, naad, msg_len, aad_len);
+    HIP_LAUNCH_CHECK();
+}
+// what the segment entries check before any lane runs: the role, the key size, the lengths by role, and the stride and alignment against the segment trace's size
+static int gcm_seg_shape(const char *who, const uint8_t *trace, size_t stride, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, size_t key_bytes, uint32_t &nblocks, uint32_t &naad) {
+    const int nk = trace_nk(who, key_bytes);
+    if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw GpuError(std::string(who) + ": the role must be 0 (head), 1 (mid) or 2 (tail)");
+    if (msg_len == 0 || msg_len > (1u << 16) || aad_len > (1u << 16)) throw GpuError(std::string(who) + ": the message must have 1 .. 65536 bytes, the aad at most 65536");
+    if (role != TRS_TAIL && msg_len % 16) throw GpuError(std::string(who) + ": a head or mid segment takes whole blocks");
+    if (role != TRS_HEAD && aad_len) throw GpuError(std::string(who) + ": only a head segment takes aad");
+    if (!trace) throw GpuError(std::string(who) + ": no trace buffer");
+    nblocks = (msg_len + 15) / 16; naad = (aad_len + 15) / 16;
+    const size_t na = naad, nb = nblocks;
+    if (stride < trace_bytes_of(nk, TRS_BYTES(4, role, na, nb), TRS_BYTES(6, role, na, nb), TRS_BYTES(8, role, na, nb))) throw GpuError(std::string(who) + ": trace stride is short of the segment region");
+    if (stride % 16 || (uintptr_t)trace % 16) throw GpuError(std::string(who) + ": traces must be 16-byte aligned");
+    if (nproofs == 0 || nproofs > (1u << 20)) throw GpuError(std::string(who) + ": 1 .. 2^20 proofs per launch");
+    return nk;
+}
+void aes_trace_gcm_seg(uint8_t *trace, size_t stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes) {
+    if (!msgs || !keys || !hdrs) throw GpuError("aes_trace_gcm_seg: no message, key or header buffer");
+    uint32_t nblocks, naad;
+    const int nk = gcm_seg_shape("aes_trace_gcm_seg", trace, stride, nproofs, role, msg_len, aad_len, key_bytes, nblocks, naad);
+    uint8_t *g_sbox = sbox_here();
+    if (!g_sbox) throw GpuError("aes_trace_gcm_seg: S-box table not uploaded on this device");
+    uint32_t lanes = nproofs * (TRS_SLOTS(role, nblocks) + 1);
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL(k_aes_trace_gcm_seg<4>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, (uint32_t)role, nblocks, naad, msg_len, aad_len, g_sbox);
+    else if (nk == 6) hipLaunchKernelGGL(k_aes_trace_gcm_seg<6>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, (uint32_t)role, nblocks, naad, msg_len, aad_len, g_sbox);
+    else hipLaunchKernelGGL(k_aes_trace_gcm_seg<8>, grid, block, 0, (hipStream_t)s, trace, stride, msgs, keys, hdrs, nproofs, (uint32_t)role, nblocks, naad, msg_len, aad_len, g_sbox);
+    HIP_LAUNCH_CHECK();
+}
+void ghash_trace_seg(uint8_t *trace, size_t stride, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes) {
+    uint32_t nblocks, naad;
+    const int nk = gcm_seg_shape("ghash_trace_seg", trace, stride, nproofs, role, msg_len, aad_len, key_bytes, nblocks, naad);
+    uint32_t lanes = nproofs * (TRS_MULS(role, naad, nblocks) + 1) * 16;
+    const dim3 grid((lanes + 63) / 64), block(64);
+    if (nk == 4) hipLaunchKernelGGL(k_ghash_trace_seg<4>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, (uint32_t)role, nblocks, naad);
+    else if (nk == 6) hipLaunchKernelGGL(k_ghash_trace_seg<6>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, (uint32_t)role, nblocks, naad);
+    else hipLaunchKernelGGL(k_ghash_trace_seg<8>, grid, block, 0, (hipStream_t)s, trace, stride, nproofs, (uint32_t)role, nblocks, naad);
     HIP_LAUNCH_CHECK();
 }
 // what the entry checks before any lane runs: T, the slots inside the stride, and 16-byte alignment of slot 0 and of every trace (as the GCM entries: tagged traces are

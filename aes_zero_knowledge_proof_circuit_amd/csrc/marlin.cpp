@@ -237,7 +237,7 @@ struct ProverContext {
     std::mutex in_use;                                // one proof at a time per context: concurrent callers of one key queue up here
     gpu::StreamGuard stream;
     gpu::WorkspaceGuard msm_ws;
-    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key, d_iv;     // (d_iv: the chaining value entering the proof's first block, CBC keys; the proof's initial counter block, CTR keys; the proof's iv and aad, 12 + A bytes, GCM keys)
+    DevPtr<uint8_t> d_trace, d_z, d_msg, d_key, d_iv;     // (d_iv: the chaining value entering the proof's first block, CBC keys; the proof's initial counter block, CTR keys; the proof's iv and aad, 12 + A bytes, GCM keys; the segment header, 80 + A bytes, GCM segment keys)
     DevPtr<void> d_rng;                               // scratch of the device-side ChaCha12 / Fr::rand stream
     DevPtr<int8_t> d_cls[3];                          // small-integer evaluation classes of w, z_A, z_B on H (Lagrange-basis commitments)
     DevPtr<F> za_ev, zb_ev, x_poly, x_tmp, x_evals, tmp_n, ra_ev, ra_poly, zpoly, t_partial;
@@ -328,7 +328,7 @@ class ProvingKeyImpl {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
         cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
-        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, 12 + c.aad_bytes) + (c.digest_kind ? 32 : 0));      // (a digest key's header carries H_in behind the mode's own)
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, mode_header_bytes(c)) + (c.digest_kind ? 32 : 0));      // (a digest key's header carries H_in behind the mode's own)
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
@@ -486,7 +486,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role = -1);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -495,14 +495,17 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
     message_len = message_len_;
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
-    circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    if (kind == CIRCUIT_AES_GCM_SEG) {                                             // message_len_ = the segment's units: c data blocks (head, mid) or Lt bytes (tail)
+        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits);
+        message_len = circuit.message_bytes;
+    } else circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
     const Circuit &c = circuit;
     // ---- joint matrix (sum_matrices): per-row sorted union of the A, B, C column supports
     size_t rows = c.num_constraints;
@@ -645,6 +648,16 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
         gpu::h2d(cx.d_iv, iv, 12 + c.aad_bytes, s);
         gpu::aes_trace_gcm(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
         gpu::ghash_trace(cx.d_trace, c.trace_bytes, 1, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
+    } else if (c.kind == CIRCUIT_AES_GCM_SEG) {
+        // iv = the segment proof's header (trace_layout.h TRS_HDR_*).  The GHASH kernel reads what the AES kernel has just written, the commitment kernel Y_out behind it
+        if (!iv) throw std::invalid_argument("a GCM segment proving key needs the segment's header");
+        if (len != c.message_bytes) throw std::invalid_argument("a GCM segment trace takes exactly the key's message length");
+        const size_t na = (c.aad_bytes + 15) / 16, nb = c.n_blocks, n_mul = TRS_MULS(c.seg_role, na, nb);
+        const size_t yout_off = c.seg_off - TRS_SEG(c.seg_role, na, nb) + TR_GCM_MUL0(na, nb) + (n_mul - 1) * TR_GCM_MUL_STRIDE + TR_GCM_MUL_Y;
+        gpu::h2d(cx.d_iv, iv, TRS_HDR_BYTES(c.aad_bytes), s);
+        gpu::aes_trace_gcm_seg(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, c.seg_role, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
+        gpu::ghash_trace_seg(cx.d_trace, c.trace_bytes, 1, c.seg_role, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
+        gpu::commit_trace(cx.d_trace, c.trace_bytes, c.seg_off, yout_off, cx.d_key, c.key_bytes, cx.d_iv, TRS_HDR_BYTES(c.aad_bytes), 1, c.seg_role, (uint32_t)nb, s);
     } else {
         gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s, c.key_bytes);
     }
@@ -1182,7 +1195,11 @@ std::vector<Proof> ProvingKey::prove_aes_ctr_chunked(const uint8_t *message, siz
     return proofs;
 }
 // ---- AES-128-GCM.  The statement, the input layout, the GHASH gadget and why a long message is a batch of records, not chunk-proofs: DESIGN.md "GCM".
+static void refuse_segment_key(const Circuit &c) {
+    if (c.kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("this proving key is a GCM segment key: use the segment entry points (zkaes_encrypt_gcm_segments_seeded_at, zkaes_aes_witness_gcm_seg)");
+}
 static void require_gcm_key(const Circuit &c, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *iv, const uint8_t *aad, size_t aad_len) {
+    refuse_segment_key(c);
     if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
     if (!message || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
     if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
@@ -1215,6 +1232,7 @@ std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, cons
                                                    uint8_t *ciphertexts_or_null, uint8_t *tags_or_null) {
     refuse_digest_key(impl->circuit);
     const Circuit &c = impl->circuit;
+    refuse_segment_key(c);
     if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
     if (n && (!messages || !keys || !headers)) throw std::invalid_argument("null argument");
     const size_t hs = 12 + c.aad_bytes;
@@ -1228,6 +1246,89 @@ std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, cons
         }
     }
     return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, hs);
+}
+// ---- GCM segments.  A segment proof's header is TRS_HDR_BYTES(A) bytes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad
+static const Circuit &require_segment_key(const ProvingKey *pk, int role, const char *name) {
+    if (!pk) throw std::invalid_argument(std::string("null ") + name + " segment key");
+    const Circuit &c = pk->impl->circuit;
+    if (c.kind != CIRCUIT_AES_GCM_SEG) throw std::invalid_argument(std::string("the ") + name + " key is not a GCM segment key: the segment entry points take keys of zkaes_synthesize_keys_gcm_seg (a lone record goes through zkaes_encrypt_gcm_seeded)");
+    if (role >= 0 && c.seg_role != role) throw std::invalid_argument(std::string("the ") + name + " key was synthesized for another segment role");
+    return c;
+}
+std::vector<uint8_t> ProvingKey::aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len) {
+    const Circuit &c = require_segment_key(this, -1, "proving");
+    if (!message || !key || !header) throw std::invalid_argument("null argument");
+    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
+    if (header_len != TRS_HDR_BYTES(c.aad_bytes)) throw std::invalid_argument("a segment header of this key has " + std::to_string(TRS_HDR_BYTES(c.aad_bytes)) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad)");
+    return witness_of(impl, message, len, key, header);
+}
+std::vector<Proof> ProvingKey::prove_gcm_segment_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
+    const Circuit &c = require_segment_key(this, -1, "proving");
+    if (n && (!messages || !keys || !headers)) throw std::invalid_argument("null argument");
+    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, TRS_HDR_BYTES(c.aad_bytes));
+}
+std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad,
+                                      size_t aad_len, const uint8_t *salts_or_null, size_t first_segment, size_t count, const uint8_t *zk_seed, uint8_t *ciphertext_or_null, uint8_t *tag_or_null,
+                                      uint8_t *commitments_or_null) {
+    const Circuit &ch = require_segment_key(head, TRS_HEAD, "head"), &ct_ = require_segment_key(tail, TRS_TAIL, "tail");
+    if (!message || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
+    const size_t c = ch.n_blocks, kb = ch.key_bytes;
+    if (len == 0 || len > ((size_t)1 << 20)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes");
+    const size_t nb = (len + 15) / 16, n = (nb + c - 1) / c;
+    if (n < 2) throw std::invalid_argument("GCM segments: this record fits one segment of the head key; a record that fits one proof goes through a lone GCM key (zkaes_encrypt_gcm_seeded)");
+    const size_t lt = len - 16 * c * (n - 1);
+    if (aad_len != ch.aad_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: the head key was synthesized for " + std::to_string(ch.aad_bytes) + " bytes of aad");
+    if (ct_.message_bytes != lt) throw std::invalid_argument("InstanceDoesNotMatchIndex: the record's last segment has " + std::to_string(lt) + " bytes, the tail key was synthesized for " + std::to_string(ct_.message_bytes));
+    if (ct_.key_bytes != kb) throw std::invalid_argument("the segment keys were synthesized for different AES key sizes");
+    if (n > 2) {
+        const Circuit &cm = require_segment_key(mid_or_null, TRS_MID, "mid");
+        if (cm.n_blocks != c) throw std::invalid_argument("head and mid keys were synthesized for different segment lengths");
+        if (cm.key_bytes != kb) throw std::invalid_argument("the segment keys were synthesized for different AES key sizes");
+    }
+    if (first_segment > n || count > n - first_segment) throw std::invalid_argument("GCM segments: first_segment + count exceeds the record's " + std::to_string(n) + " segments");
+    if (!salts_or_null && (first_segment != 0 || count != n)) throw std::invalid_argument("GCM segments: a job split over calls passes its salts, so that every call makes the same commitments");
+    // ---- the host's side: the record's GCM encryption, Y at every boundary, the salts and the commitments
+    std::vector<uint8_t> ct(len), ys(16 * (n - 1)), salts(16 * (n - 1)), coms(32 * (n - 1));
+    uint8_t tag[16], lenblk[16];
+    aes128_gcm_encrypt_host(message, len, key, iv, aad, aad_len, ct.data(), tag, kb);
+    gcm_boundaries_host(message, len, key, kb, iv, aad, aad_len, c, ys.data());
+    if (salts_or_null) memcpy(salts.data(), salts_or_null, salts.size());
+    else for (size_t off = 0; off < salts.size(); off += 32) { uint8_t r[32]; os_random_seed(r); memcpy(&salts[off], r, std::min<size_t>(32, salts.size() - off)); }
+    for (size_t s = 0; s + 1 < n; s++) gcm_commit_host(key, kb, &ys[16 * s], &salts[16 * s], &coms[32 * s]);
+    for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * len) >> (56 - 8 * i)); }
+    if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+    if (tag_or_null) memcpy(tag_or_null, tag, 16);
+    if (commitments_or_null) memcpy(commitments_or_null, coms.data(), coms.size());
+    auto header = [&](size_t s, size_t A) {
+        std::vector<uint8_t> h(TRS_HDR_BYTES(A), 0);
+        memcpy(&h[TRS_HDR_IV], iv, 12);
+        const uint32_t ctr0 = (uint32_t)(2 + s * c);
+        for (int i = 0; i < 4; i++) h[TRS_HDR_CTR0 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
+        if (s) { memcpy(&h[TRS_HDR_YIN], &ys[16 * (s - 1)], 16); memcpy(&h[TRS_HDR_SALT_IN], &salts[16 * (s - 1)], 16); }
+        if (s + 1 < n) memcpy(&h[TRS_HDR_SALT_OUT], &salts[16 * s], 16);
+        memcpy(&h[TRS_HDR_LEN], lenblk, 16);
+        if (A) memcpy(&h[TRS_HDR_AAD], aad, A);
+        return h;
+    };
+    // ---- the proofs: segment s draws from the job's seed at index s, whichever call proves it; the middle segments run side by side over the mid key's contexts
+    std::vector<Proof> proofs(count);
+    auto lone = [&](ProvingKey *pk, size_t s, size_t A) {
+        uint8_t seed_s[32];
+        if (zk_seed) derive_zk_seed(seed_s, zk_seed, (uint64_t)s);
+        const size_t seg_len = s + 1 < n ? 16 * c : lt;
+        proofs[s - first_segment] = pk->impl->prove(pk->impl->context(0), nullptr, message + 16 * c * s, seg_len, key, zk_seed ? seed_s : nullptr, false, header(s, A).data());
+    };
+    const size_t last = first_segment + count;
+    if (count && first_segment == 0) lone(head, 0, aad_len);
+    const size_t m0 = std::max<size_t>(first_segment, 1), m1 = std::min(last, n - 1);
+    if (m0 < m1) {
+        std::vector<uint8_t> hs;
+        for (size_t s = m0; s < m1; s++) { const std::vector<uint8_t> h = header(s, 0); hs.insert(hs.end(), h.begin(), h.end()); }
+        std::vector<Proof> mids = prove_many(mid_or_null->impl, message + 16 * c * m0, key, 0, m1 - m0, mid_or_null->contexts(), zk_seed, (uint64_t)m0, hs.data(), TRS_HDR_BYTES(0));
+        for (size_t s = m0; s < m1; s++) proofs[s - first_segment] = mids[s - m0];
+    }
+    if (count && last == n) lone(tail, n - 1, 0);
+    return proofs;
 }
 // ---- plaintext digests.  A proof's header is the mode's own bytes, then the 32 bytes of H_in
 static void require_digest_key(const Circuit &c) {
@@ -1426,9 +1527,16 @@ size_t ProvingKey::key_tag_blocks() const { return impl->circuit.key_tag_blocks;
 
 std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind,
                                             uint64_t digest_prefix) {
+    if (circuit_kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment key has a role: use synthesize_keys_gcm_segment (zkaes_synthesize_keys_gcm_seg)");
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
     pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    return pk;
+}
+std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags) {
+    std::unique_ptr<ProvingKey> pk(new ProvingKey());
+    pk->impl = new ProvingKeyImpl();
+    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, 0, 0, 0, role);
     return pk;
 }
 

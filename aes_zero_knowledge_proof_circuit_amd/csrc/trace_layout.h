@@ -180,6 +180,56 @@ static_assert(TRD_RND == 1152 && TRD_FF == 3968 && TRD_SLOT_STRIDE == 4032 && TR
 static_assert(TRD(TRK_ECB_BYTES(6, 1)) == TRK_ECB_BYTES(6, 1) + 8 && TRD(TRK_CTR_BYTES(4, 2)) % 16 == 0 && TRD_BYTES(TRK_ECB_BYTES(8, 4), 1, 1) % 16 == 0, "the digest region begins and ends on a multiple of 16");
 static_assert(TRD_BLOCKS(1, 128) == 2 && TRD_BLOCKS(2, 55) == 1 && TRD_BLOCKS(2, 56) == 2 && TRD_BLOCKS(2, 17) == 1 && TRD_BLOCKS(0, 64) == 0, "compressions per proof");
 
+// ---- GCM segments: a record longer than one proof is n >= 2 segment-proofs, role head / mid / tail.  A segment key's trace keeps the GCM tail's inner
+// layout (the TR_GCM_* offsets) behind its AES slots -- the nb data blocks, then H, then (tail only) J_0 -- with these differences: the four bytes behind the iv hold
+// ctr0, big-endian, the 32-bit counter of the segment's first data block; only a head has aad (na = 0 otherwise); the multiplications are na + nb (head), nb (mid),
+// nb + 1 (tail: the last over the length block); the 16 tag bytes behind them are written by a tail only.  BEHIND the tag lies the segment region sg, 16-byte aligned:
+//   sg + 0     Y_in (16): the GHASH accumulator entering the segment (mid, tail)
+//   sg + 16    salt_in (16), sg + 32 salt_out (16): the salts of the commitments behind the previous segment and behind this one
+//   sg + 48    the length block be64(8 A) || be64(8 L) of the whole record (16; tail)
+//   sg + 64    com_in (32), sg + 96 com_out (32): the boundary commitments in SHA-256's big-endian word serialisation
+//   sg + 128   per data block b, 8 bytes: the low 32 counter bits ctr0 + b mod 2^32, big-endian (4), then the carries of (ctr0 + b - 1) + 1 (4) in the CTR tail's
+//              mapping: counter bit i is bit i % 8 of byte 3 - i / 8, carry bit i = 1 iff bits 0 .. i of the previous counter are all one, i <= 30
+//   then, 16-byte aligned, two compression slots of TRD_SLOT_STRIDE: com_in's, com_out's (the layout of a digest slot, TRD_SCH / TRD_RND / TRD_FF)
+// No offset above moves, and a lone GCM key's trace is what it was.
+#define TRS_HEAD 0
+#define TRS_MID 1
+#define TRS_TAIL 2
+#define TRS_SLOTS(role, nb) ((nb) + 1 + ((role) == TRS_TAIL ? 1 : 0))
+#define TRS_GCM(nk, role, nb) ((TRK_CBC(nk, TRS_SLOTS(role, nb)) + 15) / 16 * 16)
+#define TRS_MULS(role, na, nb) ((role) == TRS_HEAD ? (na) + (nb) : (role) == TRS_MID ? (nb) : (nb) + 1)
+#define TRS_CTR0 12                                                       // inside the tail's iv slot
+#define TRS_TAG(role, na, nb) (TR_GCM_MUL0(na, nb) + TRS_MULS(role, na, nb) * TR_GCM_MUL_STRIDE)
+#define TRS_SEG(role, na, nb) (TRS_TAG(role, na, nb) + 16)               // sg, relative to the tail's base TRS_GCM
+#define TRS_YIN 0
+#define TRS_SALT_IN 16
+#define TRS_SALT_OUT 32
+#define TRS_LEN 48
+#define TRS_COM_IN 64
+#define TRS_COM_OUT 96
+#define TRS_BLOCK_CTR0 128
+#define TRS_BLOCK_CTR_STRIDE 8
+#define TRS_BL_CTR 0
+#define TRS_BL_CARRY 4
+#define TRS_SLOT_IN(nb) (TRS_BLOCK_CTR0 + (TRS_BLOCK_CTR_STRIDE * (nb) + 15) / 16 * 16)
+#define TRS_SLOT_OUT(nb) (TRS_SLOT_IN(nb) + TRD_SLOT_STRIDE)
+#define TRS_SEG_BYTES(nb) (TRS_SLOT_OUT(nb) + TRD_SLOT_STRIDE)
+#define TRS_BYTES(nk, role, na, nb) (TRS_GCM(nk, role, nb) + TRS_SEG(role, na, nb) + TRS_SEG_BYTES(nb))
+// a segment proof's header, as the prover hands it to the trace kernels: iv (12), ctr0 (4, big-endian), Y_in (16), salt_in (16), salt_out (16), the length block (16),
+// then the aad (head); a field its role does not use is ignored
+#define TRS_HDR_IV 0
+#define TRS_HDR_CTR0 12
+#define TRS_HDR_YIN 16
+#define TRS_HDR_SALT_IN 32
+#define TRS_HDR_SALT_OUT 48
+#define TRS_HDR_LEN 64
+#define TRS_HDR_AAD 80
+#define TRS_HDR_BYTES(A) (80 + (A))
+static_assert(TRS_GCM(4, TRS_TAIL, 3) == TRK_GCM(4, 3) && TRS_GCM(8, TRS_TAIL, 2) == TRK_GCM(8, 2) && TRS_TAG(TRS_TAIL, 0, 3) == TR_GCM_TAG(0, 3), "a tail segment's AES slots and GCM tail are a lone key's without aad");
+static_assert(TRS_SEG(TRS_TAIL, 0, 3) == TR_GCM_BYTES(0, 3) - TR_GCM(3) && TRS_BYTES(4, TRS_TAIL, 0, 3) == TRK_GCM_BYTES(4, 0, 3) + TRS_SEG_BYTES(3), "the segment region lies behind the GCM tail: no offset ahead of it moves");
+static_assert(TRS_GCM(6, TRS_MID, 1) % 16 == 0 && TRS_SEG(TRS_HEAD, 1, 2) % 16 == 0 && TRS_SLOT_IN(1) == 144 && TRS_SLOT_IN(2) == 144 && TRS_SLOT_IN(3) == 160 && TRS_SEG_BYTES(4) % 16 == 0, "the segment region and its compression slots are 16-byte aligned");
+static_assert(TRS_MULS(TRS_HEAD, 1, 4) == 5 && TRS_MULS(TRS_MID, 0, 4) == 4 && TRS_MULS(TRS_TAIL, 0, 4) == 5 && TRS_SLOTS(TRS_MID, 4) == 5 && TRS_SLOTS(TRS_TAIL, 4) == 6, "multiplications and AES slots per role");
+
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30
 #define WD_BYTEBIT 0u   // [29:4] trace offset, [3:1] bit, [0] neg

@@ -341,6 +341,57 @@ int zkaes_verify_digest_chunked(const zkaes_vk *vk, int circuit_kind, const uint
 /* host only: zkaes_verify_encryption_gcm_kt (key_tag NULL and key_tag_len 0 for a key without tag blocks) with h_in (NULL = the initial value) and h_out behind it */
 int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext,
                                        size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *key_tag, size_t key_tag_len, const uint8_t *h_in, const uint8_t h_out[32], int *accepted);
+/* ---- GCM records longer than one proof: segment-proofs --------------------------------------------------
+ * A record (iv, aad, ciphertext, tag) of L bytes whose ceil(L / 16) data blocks do not fit one proof is proven as n = ceil(ceil(L / 16) / c) >= 2 segment-proofs, c data
+ * blocks each, the last with Lt = L - 16 c (n - 1) bytes.  Three roles, each with its own key: role 0 = head (fixed by c and A, the whole aad), 1 = mid (c), 2 = tail
+ * (Lt).  Behind segment s < n - 1 stands the boundary commitment com_s = ONE SHA-256 compression from the initial value over key || zeros to 32 bytes || Y_s || salt_s,
+ * Y_s = the GHASH accumulator after the segment's last block, salt_s = 16 random bytes: public input of segment s (com_out) and of segment s + 1 (com_in), so all n proofs
+ * speak of one key and one GHASH chain, and together they are the lone GCM statement for the whole record.  Hiding of Y and the key rests on the salt.  Public-input
+ * vector of a segment: 96 iv bits, 32 bits of ctr0 (big-endian bytes, the verifier sets 2 + s c), then head: 8 A aad bits, 128 c ciphertext bits, 256 com_out bits;
+ * mid: 128 c ciphertext bits, com_in, com_out; tail: 8 Lt ciphertext bits, the 128 bits of the length block be64(8 A) || be64(8 L), the 128 tag bits, com_in.  L <= 2^20,
+ * A <= 65536 and inside the head; 96-bit IVs and full tags only; no key tag and no digest on a segment key.  Every older GCM entry point refuses a segment key and the
+ * segment entry points refuse every other key. */
+#define ZKAES_CIRCUIT_AES_GCM_SEG 6   /* what zkaes_pk_mode reports for a segment key; synthesized by zkaes_synthesize_keys_gcm_seg only */
+#define ZKAES_SEG_HEAD 0
+#define ZKAES_SEG_MID 1
+#define ZKAES_SEG_TAIL 2
+/* units = c (head, mid) or Lt (tail); aad_length = A for a head, 0 otherwise; the rest as zkaes_synthesize_keys_ks */
+int zkaes_synthesize_keys_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, unsigned flags,
+                                  zkaes_pk **pk, zkaes_vk **vk);
+/* out = {0 for a key that is no segment key, else 1 + role; data blocks; message bytes; aad bytes} */
+int zkaes_pk_segment_info(const zkaes_pk *pk, uint64_t out[4]);
+/* host only: zkaes_circuit_info / zkaes_circuit_matrix of a segment circuit.  The info query also fills out[9] = the joint matrix's non-zeros, out[10] = |H| and
+ * out[11] = |K| (which zkaes_circuit_info leaves 0), so that segments can be sized against an SRS without a device */
+int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+/* host only: *n_segments = n for segments of c blocks; ys (NULL = the count only) receives Y_0 .. Y_{n-2}, 16 bytes each, ys_cap >= 16 (n - 1) */
+int zkaes_gcm_boundaries(const uint8_t *message, size_t message_len, const uint8_t *secret_key, size_t key_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, size_t c,
+                         uint8_t *ys, size_t ys_cap, size_t *n_segments);
+/* host only: the boundary commitment of (key, y, salt) */
+int zkaes_gcm_commit(const uint8_t *secret_key, size_t key_len, const uint8_t y16[16], const uint8_t salt16[16], uint8_t commitment32[32]);
+/* as zkaes_aes_witness for a segment key.  header = 80 + A bytes: iv (12), ctr0 (4, big-endian), Y_in (16), salt_in (16), salt_out (16), the length block (16), the aad
+ * (head); a field the key's role does not use is ignored */
+int zkaes_aes_witness_gcm_seg(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t *secret_key, const uint8_t *header, size_t header_len, uint8_t *z, size_t z_cap,
+                              size_t *z_len);
+/* n independent segment proofs over one segment key, each under its own header (n x (80 + A) bytes, as zkaes_aes_witness_gcm_seg), side by side over the key's prover
+ * contexts; seeds and first_proof_index as zkaes_encrypt_batch_seeded_at.  The caller answers for what the headers say (zkaes_gcm_boundaries, zkaes_gcm_commit give
+ * the values of a real record): this is the building block for a record spread over processes or GPUs, and what the cost tool times */
+int zkaes_encrypt_gcm_segment_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                              const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* Segments [first_segment, first_segment + count) of one record, so that a record can be split over calls, ranks or GPUs; mid_or_null may be NULL when n = 2.  salts =
+ * 16 (n - 1) bytes or NULL for OS randomness -- NULL only when the call covers the whole record, since every call of a split job must make the same commitments.
+ * Segment s draws its zero-knowledge randomness from zk_seed32 at index s (NULL = the test_rng seed for every proof, as zkaes_encrypt_chunked_seeded).  The middle
+ * segments run side by side over the mid key's prover contexts.  Receives, where the pointer is not NULL, the whole record's ciphertext (message_len), tag (16) and
+ * commitments (32 (n - 1)); *proofs holds the call's `count` proofs back to back, proof_lens their lengths */
+int zkaes_encrypt_gcm_segments_seeded_at(const uint8_t *message, size_t message_len, const uint8_t *secret_key, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const zkaes_pk *head,
+                                         const zkaes_pk *mid_or_null, const zkaes_pk *tail, const uint8_t *salts_or_null, const uint8_t *zk_seed32, size_t first_segment, size_t count,
+                                         uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t *commitments_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* host only: the n segment-proofs of one record against ONE array of n - 1 commitments.  The verifier sets every ctr0, cuts the ciphertext, builds the length block
+ * from aad_len and ciphertext_len as it sees them, and hands the tag to the tail alone.  accepted_each[s] per segment; a proof that does not parse is a rejected
+ * segment; lengths that do not fit the keys, n_segments or commitments_len are an error of the call */
+int zkaes_verify_gcm_segments(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                              const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *commitments,
+                              size_t commitments_len, int *accepted_each, size_t *n_accepted);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

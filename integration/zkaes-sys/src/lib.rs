@@ -129,6 +129,28 @@ extern "C" {
                                    ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize, states: *const u8, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
     fn zkaes_verify_encryption_gcm_digest(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
                                           ciphertext_len: usize, tag16: *const u8, key_tag: *const u8, key_tag_len: usize, h_in: *const u8, h_out: *const u8, accepted: *mut c_int) -> c_int;
+    // GCM records longer than one proof (include/zkaes.h, section "segment-proofs"; declarations only, no wrappers yet, and not compiled: no cargo in the build image).  role: 0 head,
+    // 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); a commitment is 32 bytes, a Y and a salt 16; a segment header is 80 + A bytes
+    fn zkaes_synthesize_keys_gcm_seg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize, srs_num_non_zero: usize,
+                                     flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_pk_segment_info(pk: *const zkaes_pk, out: *mut u64) -> c_int;
+    fn zkaes_circuit_info_gcm_seg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_gcm_seg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, which: c_int, n_rows: *mut u64, nnz: *mut u64, rowptr: *mut u32, col: *mut u32,
+                                    coeff: *mut i64) -> c_int;
+    fn zkaes_gcm_boundaries(message: *const u8, message_len: usize, secret_key: *const u8, key_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, c: usize, ys: *mut u8,
+                            ys_cap: usize, n_segments: *mut usize) -> c_int;
+    fn zkaes_gcm_commit(secret_key: *const u8, key_len: usize, y16: *const u8, salt16: *const u8, commitment32: *mut u8) -> c_int;
+    fn zkaes_aes_witness_gcm_seg(pk: *const zkaes_pk, message: *const u8, message_len: usize, secret_key: *const u8, header: *const u8, header_len: usize, z: *mut u8, z_cap: usize,
+                                 z_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_segment_batch_seeded_at(n: usize, messages: *const u8, messages_len: usize, secret_keys: *const u8, secret_keys_len: usize, headers: *const u8, headers_len: usize,
+                                                 pk: *const zkaes_pk, zk_seed32: *const u8, first_proof_index: u64, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_segments_seeded_at(message: *const u8, message_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, head: *const zkaes_pk,
+                                            mid_or_null: *const zkaes_pk, tail: *const zkaes_pk, salts_or_null: *const u8, zk_seed32: *const u8, first_segment: usize, count: usize,
+                                            ciphertext_or_null: *mut u8, tag_or_null: *mut u8, commitments_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize,
+                                            proof_lens: *mut usize) -> c_int;
+    fn zkaes_verify_gcm_segments(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize, c: usize,
+                                 iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8, commitments: *const u8,
+                                 commitments_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
