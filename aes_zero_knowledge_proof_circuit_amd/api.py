@@ -1392,6 +1392,74 @@ def mask_fixup(p, n):
     return buf.raw[:len(p)]
 
 
+# ---- TEST SURFACE, not product API: the kernels that build a key (include/zkaes.h; tests/test_gpu_keysynth.py).  A point is 96 bytes of standard affine x || y, infinity 96 zero
+# bytes, in and out; counts and chunks are passed on as they are: the C side refuses.
+def fixed_base_powers(curve_id, base_xy, beta, start, count, chunk=0):
+    """beta^(start + i) * base for i < count -> 96 count bytes; chunk = points per launch (0: key synthesis's 2^20)"""
+    out = C.create_string_buffer(96 * count if 0 < count <= 1 << 20 else 1)
+    _check(lib().zkaes_fixed_base_powers(int(curve_id), bytes(base_xy), bytes(beta), C.c_uint64(start), C.c_size_t(count), C.c_size_t(chunk), out))
+    return out.raw[:96 * count]
+
+
+def fixed_base_scalars(base_xy, scalars, chunk=0):
+    """BLS12-377: scalars[i] * base -> 96 bytes per scalar"""
+    count = len(scalars) // 32
+    out = C.create_string_buffer(96 * count if 0 < count <= 1 << 20 else 1)
+    _check(lib().zkaes_fixed_base_scalars(bytes(base_xy), bytes(scalars), C.c_size_t(count), C.c_size_t(chunk), out))
+    return out.raw[:96 * count]
+
+
+def table_next(curve_id, prev, window_bits, j):
+    """window-table copy j from copy j - 1: 2^(width of window j - 1) * prev[i]"""
+    count = len(prev) // 96
+    out = C.create_string_buffer(96 * count or 1)
+    _check(lib().zkaes_table_next(int(curve_id), bytes(prev), C.c_size_t(count), int(window_bits), int(j), out))
+    return out.raw[:96 * count]
+
+
+def table_windows(curve_id, window_bits):
+    """the number of window-table copies: ceil((bits of r + 1) / window_bits)"""
+    return -(-({377: 253, 381: 255}[int(curve_id)] + 1) // int(window_bits))
+
+
+def build_window_tables(curve_id, bases, window_bits):
+    """all window-table copies of the bases, copy j at 96 n j"""
+    n = len(bases) // 96
+    total = n * table_windows(curve_id, window_bits) if int(curve_id) in (377, 381) and 2 <= int(window_bits) <= 22 and n <= 1 << 20 else 0
+    out = C.create_string_buffer(96 * total or 1)
+    _check(lib().zkaes_build_window_tables(int(curve_id), bytes(bases), C.c_size_t(n), int(window_bits), out))
+    return out.raw[:96 * total]
+
+
+NIELS_RECORD_BYTES = 192
+
+
+def convert_bases_te(points):
+    """BLS12-377: the Niels records of the points -> [(y - x, y + x, 2 d x y), ...], each coordinate a list of fourteen 28-bit limbs as stored; the records' padding is ignored"""
+    n = len(points) // 96
+    out = C.create_string_buffer(NIELS_RECORD_BYTES * n if 0 < n <= 1 << 20 else 1)
+    _check(lib().zkaes_convert_bases_te(bytes(points), C.c_size_t(n), out))
+    words = np.frombuffer(out.raw[:NIELS_RECORD_BYTES * n], dtype="<u4").reshape(n, NIELS_RECORD_BYTES // 4)
+    return [tuple([int(x) for x in rec[14 * i:14 * i + 14]] for i in range(3)) for rec in words]
+
+
+INDEX_EVALS_TAIL = 64
+
+
+def index_evals(ci, ri, ca, cb, cc, lg_k, lg_n):
+    """the index polynomials' values on K of a joint matrix of len(ci) entries -> {"row", "col", "row_col", "val_a", "val_b", "val_c", "u_inv": 32 k bytes each,
+    "tails": what the kernels left of the poison fill behind the seven arrays (INDEX_EVALS_TAIL elements each, all 0xAB unless a kernel wrote out of its range)}"""
+    cnt = len(ci)
+    idx = [np.ascontiguousarray(a, dtype=np.uint32) if cnt else np.zeros(1, dtype=np.uint32) for a in (ci, ri)]
+    co = [np.ascontiguousarray(a, dtype=np.int64) if cnt else np.zeros(1, dtype=np.int64) for a in (ca, cb, cc)]
+    k = 1 << lg_k if 0 <= lg_k <= 20 else 0
+    outs = [C.create_string_buffer(32 * (k + INDEX_EVALS_TAIL)) for _ in range(7)]
+    _check(lib().zkaes_index_evals(_p(idx[0]), _p(idx[1]), _p(co[0]), _p(co[1]), _p(co[2]), C.c_size_t(cnt), int(lg_k), int(lg_n), *outs))
+    res = {name: o.raw[:32 * k] for name, o in zip(("row", "col", "row_col", "val_a", "val_b", "val_c", "u_inv"), outs)}
+    res["tails"] = b"".join(o.raw[32 * k:] for o in outs)
+    return res
+
+
 def msm_bench(curve_id, bases_bytes, scalars_bytes, reps=3):
     n = len(scalars_bytes) // 32
     t, a = C.c_double(), C.c_double()

@@ -372,6 +372,45 @@ size_t check_csr(const uint32_t *rowptr, const uint32_t *col, const int64_t *coe
     return nnz;
 }
 bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
+
+// ---- the kernels that build a key (kernels_msm.hip k_power_scalars, k_fixed_base, k_table_next, k_convert_bases_te; kernels_poly.hip k_index_rowcol, k_index_vals), which
+// otherwise run once per SRS or per key inside key synthesis (tests/test_gpu_keysynth.py).  Points cross as 96-byte standard affine x || y, infinity as 96 zero bytes --
+// the library's own encoding, copied as it is.  Every output buffer is poisoned first.
+constexpr size_t KEYSYNTH_MAX = (size_t)1 << 20;       // points or elements a kernel-level key-synthesis call accepts
+template <class Fq> zk::Affine<Fq> load_point(const uint8_t *xy) { zk::Affine<Fq> a; memcpy(a.x.l, xy, 48); memcpy(a.y.l, xy + 48, 48); return a; }
+template <class Curve> void run_fixed_base_powers(const uint8_t *base_xy, const uint8_t *beta, uint64_t from, size_t count, size_t chunk, uint8_t *out) {
+    using Fq = typename Curve::Fq; using Fr = typename Curve::Fr;
+    Fr b; memcpy(b.l, beta, 32);
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<zk::Affine<Fq>> d = poisoned<zk::Affine<Fq>>(count, s);
+    zk::gpu::fixed_base_powers<Curve>(d, load_point<Fq>(base_xy), b, (size_t)from, count, s, chunk);
+    zk::gpu::d2h(out, d, count * 96, s);
+}
+template <class Curve> void run_table_next(const uint8_t *prev, size_t count, int c, int j, uint8_t *out) {
+    using Fq = typename Curve::Fq;
+    zk::gpu::require_device();
+    StreamGuard s;
+    DevPtr<zk::Affine<Fq>> dp(count), dn = poisoned<zk::Affine<Fq>>(count, s);
+    zk::gpu::h2d(dp, prev, count * 96, s);
+    zk::gpu::table_next<Curve>(dn, dp, count, c, j, s);
+    zk::gpu::d2h(out, dn, count * 96, s);
+}
+template <class Curve> void run_build_window_tables(const uint8_t *bases, size_t n, int c, uint8_t *out) {
+    using Fq = typename Curve::Fq;
+    zk::gpu::require_device();
+    const size_t nt = (size_t)zk::gpu::table_windows<Curve>(c);
+    StreamGuard s;
+    DevPtr<zk::Affine<Fq>> tab = poisoned<zk::Affine<Fq>>(nt * n, s);
+    zk::gpu::h2d(tab, bases, n * 96, s);
+    zk::gpu::build_window_tables<Curve>(tab, n, c, s);
+    zk::gpu::d2h(out, tab, nt * n * 96, s);
+}
+void check_curve_table_args(int curve_id, int c, size_t count, const char *who) {
+    need(curve_id == 377 || curve_id == 381, who, "curve_id must be 377 or 381");
+    if (c < 2 || c > 22) throw std::invalid_argument("window bits must be in [2, 22]");
+    need(count >= 1 && count <= KEYSYNTH_MAX, who, "count out of range");
+}
 }  // namespace
 
 extern "C" {
@@ -778,6 +817,84 @@ int zkaes_mask_fixup(uint8_t *p, size_t n) {
         DevPtr<PF> dp = upload(p, 3 * n, s);
         zk::gpu::mask_fixup(dp, n, s);
         zk::gpu::d2h(p, dp, 3 * n * sizeof(PF), s);
+    });
+}
+// ---- kernel-level entry points of the kernels that build a key (include/zkaes.h): every argument is checked before anything is allocated or launched
+int zkaes_fixed_base_powers(int curve_id, const uint8_t base_xy[96], const uint8_t beta[32], uint64_t from, size_t count, size_t chunk, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_fixed_base_powers";
+        need(curve_id == 377 || curve_id == 381, who, "curve_id must be 377 or 381");
+        need(base_xy && beta && (out || !count), who, "null argument");
+        need(count <= KEYSYNTH_MAX && chunk <= KEYSYNTH_MAX, who, "count or chunk out of range");
+        need(from <= ~(uint64_t)0 - KEYSYNTH_MAX, who, "from too close to 2^64");
+        if (!count) return;
+        if (curve_id == 377) run_fixed_base_powers<zk::Bls377>(base_xy, beta, from, count, chunk, out); else run_fixed_base_powers<zk::Bls381>(base_xy, beta, from, count, chunk, out);
+    });
+}
+int zkaes_fixed_base_scalars(const uint8_t base_xy[96], const uint8_t *scalars, size_t count, size_t chunk, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_fixed_base_scalars";
+        need(base_xy && (scalars || !count) && (out || !count), who, "null argument");
+        need(count <= KEYSYNTH_MAX && chunk <= KEYSYNTH_MAX, who, "count or chunk out of range");
+        if (!count) return;
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<MFr> ds = upload_scalars(scalars, count, s);
+        DevPtr<zk::Affine<MFq>> d = poisoned<zk::Affine<MFq>>(count, s);
+        zk::gpu::fixed_base_scalars<MC>(d, load_point<MFq>(base_xy), ds, count, s, chunk);
+        zk::gpu::d2h(out, d, count * 96, s);
+    });
+}
+int zkaes_table_next(int curve_id, const uint8_t *prev, size_t count, int window_bits, int j, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_table_next";
+        check_curve_table_args(curve_id, window_bits, count, who);
+        need(prev && out, who, "null argument");
+        const int nt = curve_id == 377 ? zk::gpu::table_windows<zk::Bls377>(window_bits) : zk::gpu::table_windows<zk::Bls381>(window_bits);
+        need(j >= 1 && j < nt, who, "j must be in [1, table copies)");
+        if (curve_id == 377) run_table_next<zk::Bls377>(prev, count, window_bits, j, out); else run_table_next<zk::Bls381>(prev, count, window_bits, j, out);
+    });
+}
+int zkaes_build_window_tables(int curve_id, const uint8_t *bases, size_t n, int window_bits, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_build_window_tables";
+        check_curve_table_args(curve_id, window_bits, n, who);
+        need(bases && out, who, "null argument");
+        if (curve_id == 377) run_build_window_tables<zk::Bls377>(bases, n, window_bits, out); else run_build_window_tables<zk::Bls381>(bases, n, window_bits, out);
+    });
+}
+int zkaes_convert_bases_te(const uint8_t *src, size_t n, uint8_t *out) {
+    return guardk([&] {
+        const char *who = "zkaes_convert_bases_te";
+        static_assert(sizeof(zk::Niels28<MP>) == ZKAES_NIELS_RECORD_BYTES, "the record size the header states");
+        need(n >= 1 && n <= KEYSYNTH_MAX, who, "n out of range");
+        need(src && out, who, "null argument");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<zk::Affine<MFq>> db = upload_points(src, n, n, s);
+        DevPtr<zk::Niels28<MP>> dn = poisoned<zk::Niels28<MP>>(n, s);
+        zk::gpu::convert_bases_te<MC>(dn, db, n, s);
+        zk::gpu::d2h(out, dn, n * sizeof(zk::Niels28<MP>), s);
+    });
+}
+int zkaes_index_evals(const uint32_t *ci, const uint32_t *ri, const int64_t *ca, const int64_t *cb, const int64_t *cc, size_t cnt, int lg_k, int lg_n, uint8_t *row, uint8_t *col, uint8_t *rowcol,
+                      uint8_t *va, uint8_t *vb, uint8_t *vc, uint8_t *uinv_or_null) {
+    return guardk([&] {
+        const char *who = "zkaes_index_evals";
+        need(lg_n >= 0 && lg_n <= 20 && lg_k >= 0 && lg_k <= 20, who, "lg_n and lg_k must be in [0, 20]");
+        const size_t k = (size_t)1 << lg_k, n = (size_t)1 << lg_n, room = k + ZKAES_INDEX_EVALS_TAIL;
+        need(cnt <= k, who, "cnt must not exceed k");
+        need(row && col && rowcol && va && vb && vc && (!cnt || (ci && ri && ca && cb && cc)), who, "null argument");
+        for (size_t i = 0; i < cnt; i++) need(ci[i] < n && ri[i] < n, who, "index out of range");
+        zk::gpu::require_device();
+        StreamGuard s;
+        DevPtr<uint32_t> dci = upload_as(ci, cnt, s), dri = upload_as(ri, cnt, s);
+        DevPtr<int64_t> dca = upload_as(ca, cnt, s), dcb = upload_as(cb, cnt, s), dcc = upload_as(cc, cnt, s);
+        DevPtr<PF> d[7];
+        for (int i = 0; i < 7; i++) d[i] = poisoned<PF>(room, s);
+        zk::gpu::index_evals(d[0], d[1], d[2], d[3], d[4], d[5], d[6], dci, dri, dca, dcb, dcc, cnt, k, zk::gpu::domain_elements<zk::Fr377>(lg_n), (uint32_t)n, s);
+        uint8_t *outs[7] = {row, col, rowcol, va, vb, vc, uinv_or_null};
+        for (int i = 0; i < 7; i++) if (outs[i]) zk::gpu::d2h(outs[i], d[i], room * sizeof(PF), s);
     });
 }
 int zkaes_ntt_padded(int field_id, const uint8_t *in, size_t in_len, size_t n, int inverse, int coset_c, int lg_big, uint8_t *out) {

@@ -195,11 +195,12 @@ void msm_prepare_table(MsmWorkspace *ws, const typename Curve::Fr *scal1, size_t
 template <class Curve>
 XYZZ<typename Curve::Fq> msm_table(MsmWorkspace *ws, const Affine28<typename Curve::FqP> *tables, size_t stride, size_t off, int c, const typename Curve::Fr *scalars, size_t n, stream_t s);
 // out[i] = (beta^(from+i)) * base for i < count   (KZG powers; fixed-base windows)   -- device output
+// chunk: points per launch, 0 = 2^20 (what every caller of the library uses); a test passes a small one so that the chunk loop runs more than once at a few hundred points
 template <class Curve>
-void fixed_base_powers(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr &beta, size_t from, size_t count, stream_t s);
+void fixed_base_powers(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr &beta, size_t from, size_t count, stream_t s, size_t chunk = 0);
 // out[i] = scalars[i] * base for device-resident scalars
 template <class Curve>
-void fixed_base_scalars(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr *scalars, size_t count, stream_t s);
+void fixed_base_scalars(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr *scalars, size_t count, stream_t s, size_t chunk = 0);
 // sum_i vals[i] * bases[i] for small integers |vals[i]| <= 2 (commitments of 0/1-valued evaluation vectors in a Lagrange-basis SRS): about one
 // mixed add per non-zero entry instead of one per window.  Returns false (result unusable) if a value is out of range or an addition
 // degenerates -- callers then use the generic MSM.  Synchronizes the stream.

@@ -1560,16 +1560,22 @@ DevPtr<Affine<typename Curve::Fq>> upload_fixed_base_table(const Affine<typename
     sync((stream_t)s);
     return d_table;
 }
+// points per launch: 2^20 unless a test asks for less (so that the chunk loop runs more than once at a count of a few hundred); never more
+size_t fixed_base_chunk(size_t chunk) {
+    const size_t CH = (size_t)1 << 20;
+    if (chunk > CH) throw GpuError("fixed_base: chunk must not exceed 2^20 points");
+    return chunk ? chunk : CH;
+}
 }  // namespace
 
 template <class Curve>
-void fixed_base_powers(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr &beta, size_t from, size_t count, stream_t s_) {
+void fixed_base_powers(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr &beta, size_t from, size_t count, stream_t s_, size_t chunk) {
     using Fq = typename Curve::Fq;
     using Fr = typename Curve::Fr;
     hipStream_t s = (hipStream_t)s_;
     if (!count) return;
     DevPtr<Affine<Fq>> d_table = upload_fixed_base_table<Curve>(base, s);
-    const size_t CH = 1 << 20;
+    const size_t CH = fixed_base_chunk(chunk);
     DevPtr<Fr> d_sc(CH);
     for (size_t off = 0; off < count; off += CH) {
         uint32_t m = (uint32_t)((count - off) < CH ? (count - off) : CH);
@@ -1582,13 +1588,13 @@ void fixed_base_powers(Affine<typename Curve::Fq> *out, const Affine<typename Cu
 }
 // out[i] = scalars[i] * base for device-resident scalars (Lagrange-basis SRS points)
 template <class Curve>
-void fixed_base_scalars(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr *scalars, size_t count, stream_t s_) {
+void fixed_base_scalars(Affine<typename Curve::Fq> *out, const Affine<typename Curve::Fq> &base, const typename Curve::Fr *scalars, size_t count, stream_t s_, size_t chunk) {
     using Fq = typename Curve::Fq;
     using Fr = typename Curve::Fr;
     hipStream_t s = (hipStream_t)s_;
     if (!count) return;
     DevPtr<Affine<Fq>> d_table = upload_fixed_base_table<Curve>(base, s);
-    const size_t CH = 1 << 20;
+    const size_t CH = fixed_base_chunk(chunk);
     for (size_t off = 0; off < count; off += CH) {
         uint32_t m = (uint32_t)((count - off) < CH ? (count - off) : CH);
         hipLaunchKernelGGL((k_fixed_base<Fq, Fr>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq> *)d_table.get(), scalars + off, m, out + off);
@@ -1769,10 +1775,10 @@ template XYZZ<Fq377> msm_finish<Bls377>(MsmWorkspace *, const Affine28<Fq377P> *
 template XYZZ<Fq381> msm_finish<Bls381>(MsmWorkspace *, const Affine28<Fq381P> *, stream_t);
 template XYZZ<Fq377> msm<Bls377>(MsmWorkspace *, const Affine28<Fq377P> *, const Fr377 *, size_t, stream_t);
 template XYZZ<Fq381> msm<Bls381>(MsmWorkspace *, const Affine28<Fq381P> *, const Fr381 *, size_t, stream_t);
-template void fixed_base_scalars<Bls377>(Affine<Fq377> *, const Affine<Fq377> &, const Fr377 *, size_t, stream_t);
+template void fixed_base_scalars<Bls377>(Affine<Fq377> *, const Affine<Fq377> &, const Fr377 *, size_t, stream_t, size_t);
 template bool class_sum<Bls377>(MsmWorkspace *, const Affine28<Fq377P> *, const int8_t *, size_t, XYZZ<Fq377> *, stream_t);
-template void fixed_base_powers<Bls377>(Affine<Fq377> *, const Affine<Fq377> &, const Fr377 &, size_t, size_t, stream_t);
-template void fixed_base_powers<Bls381>(Affine<Fq381> *, const Affine<Fq381> &, const Fr381 &, size_t, size_t, stream_t);
+template void fixed_base_powers<Bls377>(Affine<Fq377> *, const Affine<Fq377> &, const Fr377 &, size_t, size_t, stream_t, size_t);
+template void fixed_base_powers<Bls381>(Affine<Fq381> *, const Affine<Fq381> &, const Fr381 &, size_t, size_t, stream_t, size_t);
 
 }  // namespace gpu
 }  // namespace zk

@@ -328,6 +328,9 @@ class ProvingKeyImpl {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
         cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
+        // the layout's alignment padding (ahead of the GCM tail, the key-tag slots and the digest region) is written by no kernel and read by no variable: zeroed once, on the
+        // stream every trace kernel of this context runs on, so that the trace a debug fetch returns depends on the inputs only and not on what the allocation held before
+        gpu::dzero(cx.d_trace, c.trace_bytes + 64, cx.stream);
         cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, mode_header_bytes(c)) + (c.digest_kind ? 32 : 0));      // (a digest key's header carries H_in behind the mode's own)
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }

@@ -538,6 +538,33 @@ int zkaes_f_evals_from_tables(const uint8_t *va, const uint8_t *vb, const uint8_
 int zkaes_chacha_field_stream(const uint32_t key_words[8], int rounds, uint64_t word_pos, size_t count, uint32_t max_cand, uint8_t *out, uint64_t *next_word_pos);
 /* k_mask_fixup, in place on 3 n elements: p[0] -= p[0] + p[n] + p[2n] */
 int zkaes_mask_fixup(uint8_t *p, size_t n);
+/* ---- kernel-level entry points of the kernels that BUILD A KEY (csrc/kernels_msm.hip k_power_scalars, k_fixed_base, k_table_next, k_convert_bases_te; csrc/kernels_poly.hip
+ * k_index_rowcol, k_index_vals): TEST SURFACE, not product API -- they run once per SRS or per key inside key synthesis and everything proved afterwards rests on their output
+ * (tests/test_gpu_keysynth.py compares each with the CPU oracle and the integer model of tests/keysynth_model.py).  Field elements are 32-byte Montgomery limbs, canonical; a
+ * point is 96 bytes of standard affine x || y (Montgomery coordinates) and the point at infinity is 96 ZERO bytes, in and out.  curve_id: 377 or 381.  Every call uploads,
+ * launches, copies back and waits; every output buffer is filled with 0xAB bytes on the device first.  All arguments are checked before anything is allocated or launched;
+ * counts are limited to 2^20. */
+/* fixed_base_powers: out[i] = beta^(from + i) * base for i < count.  chunk: points per launch, 0 = the 2^20 of key synthesis; a smaller one makes the chunk loop run more than
+ * once (the result must not depend on it). */
+int zkaes_fixed_base_powers(int curve_id, const uint8_t base_xy[96], const uint8_t beta[32], uint64_t from, size_t count, size_t chunk, uint8_t *out);
+/* fixed_base_scalars (BLS12-377): out[i] = scalars[i] * base; chunk as above */
+int zkaes_fixed_base_scalars(const uint8_t base_xy[96], const uint8_t *scalars, size_t count, size_t chunk, uint8_t *out);
+/* table_next: out[i] = 2^(width of window j - 1) * prev[i], window-table copy j from copy j - 1 under window_bits (2..22); 1 <= j < the number of copies */
+int zkaes_table_next(int curve_id, const uint8_t *prev, size_t count, int window_bits, int j, uint8_t *out);
+/* build_window_tables: out = all copies, copy j (n points) at out + 96 n j: copy 0 = bases, copy j = 2^(offset of window j) * bases */
+int zkaes_build_window_tables(int curve_id, const uint8_t *bases, size_t n, int window_bits, uint8_t *out);
+/* convert_bases_te (BLS12-377): out = n raw Niels28 records of ZKAES_NIELS_RECORD_BYTES each -- (y - x, y + x, 2 d x y) of the point on the twisted Edwards model as three
+ * vectors of 14 little-endian 32-bit words holding 28-bit limbs (Montgomery form, radix 2^392), then padding.  Infinity gives the identity (1, 1, 0); a point of order 2 or 4
+ * is refused. */
+#define ZKAES_NIELS_RECORD_BYTES 192
+int zkaes_convert_bases_te(const uint8_t *src, size_t n, uint8_t *out);
+/* index_evals over the library's own table of the size-2^lg_n domain: entry i < cnt of the joint matrix sits at column ci[i], row ri[i] (both < 2^lg_n) with the coefficients
+ * ca[i], cb[i], cc[i]; entries cnt <= i < k = 2^lg_k are padding.  Each output holds k + ZKAES_INDEX_EVALS_TAIL elements: the k values, then what the kernels left of the 0xAB
+ * fill behind them (all of it, unless a kernel wrote out of its range).  uinv_or_null: the scratch vector after the batch inversion, 1 / u_H(x, x) per entry and zero on the
+ * padding. */
+#define ZKAES_INDEX_EVALS_TAIL 64
+int zkaes_index_evals(const uint32_t *ci, const uint32_t *ri, const int64_t *ca, const int64_t *cb, const int64_t *cc, size_t cnt, int lg_k, int lg_n, uint8_t *row, uint8_t *col, uint8_t *rowcol,
+                      uint8_t *va, uint8_t *vb, uint8_t *vc, uint8_t *uinv_or_null);
 /* TEST-ONLY: ONE field or curve operation of csrc/ff.cuh, ff28.cuh, ff29.cuh, ec28.cuh, te28.cuh per launch, on raw limbs exactly as the operation sees them (no conversion
  * in or out, so lazy and non-canonical operands can be passed).  op: an id of csrc/arith_probe.cuh ZK_PROBE_OPS (named by api.py ARITH_OPS, which also holds the words per
  * case); in: n_cases x input words, out: n_cases x output words; 1 <= n_cases <= 65536.  tests/test_gpu_arith.py compares it with the big-integer model. */

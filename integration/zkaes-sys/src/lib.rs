@@ -151,6 +151,16 @@ extern "C" {
     fn zkaes_verify_gcm_segments(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize, c: usize,
                                  iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8, commitments: *const u8,
                                  commitments_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    // kernel-level entries of the kernels that build a key (include/zkaes.h, "kernels that BUILD A KEY": test surface, not product API; declarations only, no wrappers, and
+    // not compiled: no cargo in the build image).  A point is 96 bytes of affine x || y in Montgomery form, infinity 96 zero bytes; a field element 32 bytes; a Niels record
+    // 192 bytes; every output of zkaes_index_evals holds 2^lg_k + 64 elements
+    fn zkaes_fixed_base_powers(curve_id: c_int, base_xy: *const u8, beta: *const u8, from: u64, count: usize, chunk: usize, out: *mut u8) -> c_int;
+    fn zkaes_fixed_base_scalars(base_xy: *const u8, scalars: *const u8, count: usize, chunk: usize, out: *mut u8) -> c_int;
+    fn zkaes_table_next(curve_id: c_int, prev: *const u8, count: usize, window_bits: c_int, j: c_int, out: *mut u8) -> c_int;
+    fn zkaes_build_window_tables(curve_id: c_int, bases: *const u8, n: usize, window_bits: c_int, out: *mut u8) -> c_int;
+    fn zkaes_convert_bases_te(src: *const u8, n: usize, out: *mut u8) -> c_int;
+    fn zkaes_index_evals(ci: *const u32, ri: *const u32, ca: *const i64, cb: *const i64, cc: *const i64, cnt: usize, lg_k: c_int, lg_n: c_int, row: *mut u8, col: *mut u8,
+                         rowcol: *mut u8, va: *mut u8, vb: *mut u8, vc: *mut u8, uinv_or_null: *mut u8) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
