@@ -11,4 +11,5 @@ from .api import (ZkAesError, ProvingKey, VerifyingKey, synthesize_keys, encrypt
                   CIRCUIT_AES_GCM, synthesize_keys_gcm, gcm_encrypt, gcm_decrypt, encrypt_gcm, verify_encryption_gcm,
                   ecb_ciphertext, circuit_info, circuit_matrix,
                   key_tag, verify_chunked_tagged, verify_encryption_gcm_tagged,
-                  sha256_chain, sha256_finish, verify_digest_chunked, verify_encryption_gcm_digest)
+                  sha256_chain, sha256_finish, verify_digest_chunked, verify_encryption_gcm_digest,
+                  verify_batch, chunk_public_inputs, verify_chunked_batch)

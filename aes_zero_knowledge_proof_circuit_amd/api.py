@@ -108,6 +108,10 @@ class VerifyingKey:
         _check(lib().zkaes_verify(self._p, bytes(proof), C.c_size_t(len(proof)), bits, C.c_size_t(len(bits)), C.byref(acc)))
         return bool(acc.value)
 
+    def verify_batch(self, proofs, public_inputs, device=True):
+        """n proofs under this key, one public-input row each -> list of bools (api.verify_batch)"""
+        return verify_batch(self, proofs, public_inputs, device=device)
+
     def __del__(self):
         try:
             if self._p:
@@ -649,6 +653,86 @@ def verify_chunked_tagged(verifying_key, circuit, proofs, ciphertext, key_tag, i
     _check(lib().zkaes_verify_chunked_kt(verifying_key._p, int(circuit), b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), None if iv is None else bytes(iv), bytes(ciphertext),
                                          C.c_size_t(len(ciphertext)), bytes(key_tag), C.c_size_t(len(key_tag)), each, C.byref(ok)))
     return [bool(each[i]) for i in range(n)]
+
+
+def verify_batch(verifying_key, proofs, public_inputs, device=True):
+    """n >= 1 proofs under ONE verifying key, each with its own public input (one 0/1 byte per variable, as VerifyingKey.verify takes it; all rows equally long)
+    -> list of bools, the answers n calls of verify would give for the cost of two MSMs and ONE pairing product (include/zkaes.h).  Proof bytes that do
+    not parse are a rejected proof, never an exception.  device=True runs the point checks, the public-input evaluation and the MSMs on the GPU (zkaes_verify_batch_gpu;
+    no proving key needed); device=False everything on the host (zkaes_verify_batch; no GPU needed)"""
+    n = len(proofs)
+    if n == 0 or len(public_inputs) != n:
+        raise ZkAesError("verify_batch takes at least one proof and one public-input row per proof")
+    rows = [bytes(r) for r in public_inputs]
+    n_bits = len(rows[0])
+    if any(len(r) != n_bits for r in rows):
+        raise ZkAesError("verify_batch: every public-input row must have the same length")
+    lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+    each = (C.c_int * n)()
+    ok = C.c_size_t()
+    fn = lib().zkaes_verify_batch_gpu if device else lib().zkaes_verify_batch
+    _check(fn(verifying_key._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), b"".join(rows) if n_bits else None, C.c_size_t(n_bits), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
+
+
+def verify_batch_timings():
+    """where this thread's last verify_batch spent its time (zkaes_verify_batch_timings): ms per stage and the number of (sub-)batches checked"""
+    out = (C.c_double * 8)()
+    _check(lib().zkaes_verify_batch_timings(out))
+    names = ("parse_ms", "decompress_ms", "transcripts_ms", "xhat_ms", "msm_ms", "pairing_ms", "total_ms")
+    d = {k: out[i] for i, k in enumerate(names)}
+    d["sub_batches"] = int(out[7])
+    return d
+
+
+def chunk_public_inputs(circuit, ciphertext, header=None, key_tag=None, states=None, n_chunks=None):
+    """the public-input rows of a chunked ECB, CBC or CTR job, one bytes object of 0/1 per chunk: exactly what verify_encryption / verify_cbc_chunked / verify_ctr_chunked /
+    verify_chunked_tagged / verify_digest_chunked derive for chunk j (zkaes_chunk_public_inputs; no GPU).  header: None for ECB, the IV for CBC, the initial counter block
+    for CTR; key_tag: 16 or 32 bytes or None; states: the n + 1 digest states or None; n_chunks: default len(states) - 1 with states, else 1"""
+    if n_chunks is None:
+        n_chunks = len(states) - 1 if states is not None else 1
+    if states is not None and (len(states) != n_chunks + 1 or any(len(st) != 32 for st in states)):
+        raise ZkAesError("states must be one 32-byte state more than there are chunks")
+    if header is not None and len(header) != 16:
+        raise ZkAesError("iv / icb must be 16 bytes")
+    args = (int(circuit), C.c_size_t(n_chunks), None if header is None else bytes(header), bytes(ciphertext), C.c_size_t(len(ciphertext)), None if key_tag is None else bytes(key_tag),
+            C.c_size_t(0 if key_tag is None else len(key_tag)), None if states is None else b"".join(bytes(st) for st in states))
+    n_bits = C.c_size_t()
+    _check(lib().zkaes_chunk_public_inputs(*args, None, C.byref(n_bits)))
+    out = C.create_string_buffer(max(1, n_chunks * n_bits.value))
+    _check(lib().zkaes_chunk_public_inputs(*args, out, C.byref(n_bits)))
+    return [out.raw[j * n_bits.value:(j + 1) * n_bits.value] for j in range(n_chunks)]
+
+
+def verify_chunked_batch(verifying_key, circuit, proofs, ciphertext, header=None, key_tag=None, states=None, device=True):
+    """the chunk-proofs of one ECB, CBC or CTR job through the batch verifier -> list of bools: chunk_public_inputs for the rows, verify_batch for the proofs"""
+    return verify_batch(verifying_key, proofs, chunk_public_inputs(circuit, ciphertext, header, key_tag, states, n_chunks=len(proofs)), device=device)
+
+
+def g1_decompress_batch(points48):
+    """kernel probe (zkaes_g1_decompress_batch): compressed BLS12-377 G1 points (n x 48 bytes) -> (n x 96 bytes x, y Montgomery limbs, list of status codes: 0 ok,
+    1 infinity encoding, 2 not on the curve, 3 not in the prime-order subgroup, 4 malformed)"""
+    n = len(points48) // 48
+    out, st = C.create_string_buffer(96 * max(n, 1)), C.create_string_buffer(max(n, 1))
+    _check(lib().zkaes_g1_decompress_batch(bytes(points48), C.c_size_t(n), out, st))
+    return out.raw[:96 * n], list(st.raw[:n])
+
+
+def fq_sqrt_batch(elements):
+    """kernel probe (zkaes_fq_sqrt_batch): BLS12-377 base-field elements (n x 48 bytes, Montgomery limbs) -> (n x 48 bytes of roots, list of is_square flags)"""
+    n = len(elements) // 48
+    out, sq = C.create_string_buffer(48 * max(n, 1)), C.create_string_buffer(max(n, 1))
+    _check(lib().zkaes_fq_sqrt_batch(bytes(elements), C.c_size_t(n), out, sq))
+    return out.raw[:48 * n], list(sq.raw[:n])
+
+
+def public_input_eval(lg_m, betas, bits_rows):
+    """kernel probe (zkaes_public_input_eval): x^(beta_i) over the domain of size 2^lg_m for x = [1, row i (0/1 bytes), zeros]; betas n x 32 bytes Montgomery -> n x 32"""
+    rows = [bytes(r) for r in bits_rows]
+    n, n_bits = len(rows), len(rows[0]) if rows else 0
+    out = C.create_string_buffer(32 * max(n, 1))
+    _check(lib().zkaes_public_input_eval(int(lg_m), bytes(betas), b"".join(rows) if n_bits else None, C.c_size_t(n), C.c_size_t(n_bits), out))
+    return out.raw[:32 * n]
 
 
 def _host_key(secret_key):

@@ -2,6 +2,7 @@
 #include "capi_common.hpp"
 #include <algorithm>
 #include "gpu.hpp"
+#include "fq_sqrt.cuh"
 
 using zk::capi::guard; using zk::capi::give; using zk::capi::fill_info; using zk::capi::next_pow2;
 
@@ -404,6 +405,64 @@ int zkaes_aes_witness(const zkaes_pk *pk, const uint8_t *msg, size_t len, const 
 }
 int zkaes_pk_timings(const zkaes_pk *pk, double out[6]) {
     return guard([&] { const auto &t = pk->pk->last_timings(); out[0] = t.witness_ms; out[1] = t.round1_ms; out[2] = t.round2_ms; out[3] = t.round3_ms; out[4] = t.open_ms; out[5] = t.total_ms; });
+}
+// ---- batch verification on the device (include/zkaes.h); the host back end, zkaes_verify_batch_timings and zkaes_chunk_public_inputs are in capi_host.cpp
+int zkaes_verify_batch_gpu(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each,
+                           size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        zk::capi::verify_batch_call(vk, proofs, proof_lens, n, public_input_bits, n_bits, accepted_each, n_accepted, *be);
+    });
+}
+// the three kernels behind it, one launch per call (tests/test_gpu_verify_batch.py)
+int zkaes_g1_decompress_batch(const uint8_t *points48, size_t n, uint8_t *out_xy, uint8_t *status) {
+    return guard([&] {
+        if (!points48 || !out_xy || !status) throw std::invalid_argument("null argument");
+        if (n == 0 || n > ((size_t)1 << 24)) throw std::invalid_argument("zkaes_g1_decompress_batch: 1 .. 2^24 points");
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        std::vector<zk::G1Compressed> todo;
+        std::vector<size_t> where;
+        memset(out_xy, 0, 96 * n);
+        for (size_t i = 0; i < n; i++) {
+            zk::G1Compressed c;
+            bool inf = false;
+            if (!zk::g1_parse_compressed(points48 + 48 * i, c, &inf)) status[i] = zk::G1_MALFORMED;
+            else if (inf) status[i] = zk::G1_INFINITY;
+            else { todo.push_back(c); where.push_back(i); }
+        }
+        if (todo.empty()) return;
+        std::vector<zk::G1A> pts(todo.size());
+        std::vector<uint8_t> st(todo.size());
+        be->decompress(todo.data(), todo.size(), pts.data(), st.data());
+        for (size_t j = 0; j < todo.size(); j++) { status[where[j]] = st[j]; memcpy(out_xy + 96 * where[j], pts[j].x.l, 48); memcpy(out_xy + 96 * where[j] + 48, pts[j].y.l, 48); }
+    });
+}
+int zkaes_fq_sqrt_batch(const uint8_t *in, size_t n, uint8_t *out, uint8_t *is_square) {
+    return guard([&] {
+        if (!in || !out || !is_square) throw std::invalid_argument("null argument");
+        if (n == 0 || n > ((size_t)1 << 24)) throw std::invalid_argument("zkaes_fq_sqrt_batch: 1 .. 2^24 elements");
+        for (size_t i = 0; i < n; i++) { uint32_t l[12]; memcpy(l, in + 48 * i, 48); if (zk::Fq377::geq_mod(l)) throw std::invalid_argument("zkaes_fq_sqrt_batch: limbs not below the modulus"); }
+        zk::gpu::require_device();
+        zk::gpu::StreamGuard s;
+        zk::gpu::DevPtr<zk::Fq377> d_in(n), d_out(n);
+        zk::gpu::DevPtr<uint8_t> d_ok(n);
+        zk::gpu::h2d(d_in, in, 48 * n, s);
+        zk::gpu::fq_sqrt_batch(d_in, n, d_out, d_ok, s);
+        zk::gpu::d2h(out, d_out, 48 * n, s);
+        zk::gpu::d2h(is_square, d_ok, n, s);
+    });
+}
+int zkaes_public_input_eval(int lg_m, const uint8_t *betas, const uint8_t *bits, size_t n, size_t n_bits, uint8_t *out) {
+    return guard([&] {
+        if (!betas || !out || (n_bits && !bits)) throw std::invalid_argument("null argument");
+        if (lg_m < 0 || lg_m > 30 || n == 0 || n > ((size_t)1 << 20) || n_bits >= ((size_t)1 << lg_m)) throw std::invalid_argument("zkaes_public_input_eval: 1 .. 2^20 rows of fewer than 2^lg_m bits, lg_m <= 30");
+        std::vector<zk::Fr> b(n), o(n);
+        for (size_t i = 0; i < n; i++) { memcpy(b[i].l, betas + 32 * i, 32); if (zk::Fr::geq_mod(b[i].l)) throw std::invalid_argument("zkaes_public_input_eval: limbs not below the modulus"); }
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        be->public_input_eval(lg_m, b.data(), bits, n, n_bits, o.data());
+        memcpy(out, o.data(), 32 * n);
+    });
 }
 int zkaes_msm_stats(double out[5], int reset) {
     return guard([&] {

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "marlin.hpp"
+#include "verify_batch.hpp"
 
 struct zkaes_pk { std::unique_ptr<zk::ProvingKey> pk; };
 struct zkaes_vk { zk::VerifyingKey vk; };
@@ -33,6 +34,22 @@ inline void fill_info(const Circuit &c, uint64_t out[12]) {
     out[0] = c.raw_constraints; out[1] = c.raw_instance; out[2] = c.raw_witness;
     out[3] = c.A.nnz(); out[4] = c.B.nnz(); out[5] = c.C.nnz();
     out[6] = c.num_constraints; out[7] = c.num_instance; out[8] = c.num_witness; out[9] = 0; out[10] = 0; out[11] = 0;
+}
+// zkaes_verify_batch and zkaes_verify_batch_gpu: the same call over the two back ends (verify_batch.hpp)
+void set_last_batch_timings(const BatchTimings &t);      // the calling thread's zkaes_verify_batch_timings() (capi_host.cpp)
+inline void verify_batch_call(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *bits, size_t n_bits, int *accepted_each, size_t *n_accepted,
+                              BatchBackend &be) {
+    if (n_accepted) *n_accepted = 0;
+    if (accepted_each) for (size_t i = 0; i < n; i++) accepted_each[i] = 0;
+    if (!vk || !proofs || !proof_lens || (n_bits && !bits)) throw std::invalid_argument("null argument");
+    if (n == 0) throw std::invalid_argument("verify_batch: at least one proof");
+    if (n_bits >= ((size_t)1 << 46)) throw std::invalid_argument("verify_batch: n_bits out of range");
+    BatchTimings t;
+    std::vector<uint8_t> acc = verify_batch(vk->vk, proofs, proof_lens, n, bits, n_bits, be, &t);
+    set_last_batch_timings(t);
+    size_t ok = 0;
+    for (size_t i = 0; i < n; i++) { if (accepted_each) accepted_each[i] = acc[i]; ok += acc[i]; }
+    if (n_accepted) *n_accepted = ok;
 }
 inline size_t next_pow2(size_t n) { if (n > ((size_t)1 << 62)) throw std::length_error("size out of range"); size_t p = 1; while (p < n) p <<= 1; return p; }
 }  // namespace capi

@@ -15,12 +15,28 @@ std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, si
     pub.insert(pub.end(), c.begin(), c.end());
     return pub;
 }
+// Chunk j's public input without the leading One, as every chunked verifier and zkaes_chunk_public_inputs derive it: the mode header (ECB none; CBC the chaining value
+// entering the chunk -- iv, or the 16 ciphertext bytes ahead of the slice; CTR icb + j x the chunk's blocks), the chunk's ciphertext bits, the key tag's when there is
+// one, and (states[j], states[j + 1]) when there are states
+std::vector<zk::Fr> chunk_public_input(int circuit_kind, size_t j, size_t chunk, const uint8_t *iv_or_icb, const uint8_t *ct, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states) {
+    std::vector<zk::Fr> pub;
+    auto append = [&](const uint8_t *bytes, size_t n) { std::vector<zk::Fr> b = zk::ciphertext_to_public_input(bytes, n); pub.insert(pub.end(), b.begin(), b.end()); };
+    uint8_t counter[16];
+    if (circuit_kind == zk::CIRCUIT_AES_CBC) append(j ? ct + chunk * j - 16 : iv_or_icb, 16);
+    if (circuit_kind == zk::CIRCUIT_AES_CTR) { zk::ctr_counter_add(iv_or_icb, (uint64_t)j * (chunk / 16), counter); append(counter, 16); }
+    append(ct + chunk * j, chunk);
+    if (key_tag) append(key_tag, key_tag_len);
+    if (states) append(states + 32 * j, 64);                                               // states[j] is H_in, states[j + 1] H_out
+    return pub;
+}
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
 // image of the struct: reading it back from untrusted bytes put arbitrary limbs into field elements and an arbitrary byte into a bool, and skipped the curve / subgroup
 // checks the ark path makes -- found while writing the fuzz target (tests/fuzz_host.cpp).  v2 goes through deserialize_vk_ark and inherits every check.
 constexpr uint8_t VK_MAGIC[4] = {'Z', 'V', 'K', '2'};
 }  // namespace
 namespace zk { void capi_set_error(const std::string &m) { g_err = m; } }
+namespace { thread_local zk::BatchTimings g_batch_timings; }
+namespace zk { namespace capi { void set_last_batch_timings(const BatchTimings &t) { g_batch_timings = t; } } }
 using zk::capi::guard; using zk::capi::give; using zk::capi::fill_info; using zk::capi::next_pow2;
 
 extern "C" {
@@ -91,7 +107,7 @@ int zkaes_verify_cbc_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
             int acc = 0;
             try {
                 zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                acc = zk::verify(vk->vk, cbc_public_input(j ? ct + chunk * j - 16 : iv, ct + chunk * j, chunk), p) ? 1 : 0;
+                acc = zk::verify(vk->vk, chunk_public_input(zk::CIRCUIT_AES_CBC, j, chunk, iv, ct, nullptr, 0, nullptr), p) ? 1 : 0;
             } catch (const std::runtime_error &) { acc = 0; }
             if (accepted_each) accepted_each[j] = acc;
             ok += (size_t)acc;
@@ -156,9 +172,7 @@ int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
             int acc = 0;
             try {
                 zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                uint8_t counter[16];
-                zk::ctr_counter_add(icb, (uint64_t)j * (chunk / 16), counter);
-                acc = zk::verify(vk->vk, cbc_public_input(counter, ct + chunk * j, chunk), p) ? 1 : 0;
+                acc = zk::verify(vk->vk, chunk_public_input(zk::CIRCUIT_AES_CTR, j, chunk, icb, ct, nullptr, 0, nullptr), p) ? 1 : 0;
             } catch (const std::runtime_error &) { acc = 0; }
             if (accepted_each) accepted_each[j] = acc;
             ok += (size_t)acc;
@@ -340,13 +354,7 @@ int zkaes_verify_chunked_kt(const zkaes_vk *vk, int circuit_kind, const uint8_t 
             int acc = 0;
             try {
                 zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                std::vector<zk::Fr> pub;
-                uint8_t counter[16];
-                if (cbc) append_bits(pub, j ? ct + chunk * j - 16 : iv_or_icb, 16);
-                if (ctr) { zk::ctr_counter_add(iv_or_icb, (uint64_t)j * (chunk / 16), counter); append_bits(pub, counter, 16); }
-                append_bits(pub, ct + chunk * j, chunk);
-                append_bits(pub, key_tag, key_tag_len);
-                acc = zk::verify(vk->vk, pub, p) ? 1 : 0;
+                acc = zk::verify(vk->vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, nullptr), p) ? 1 : 0;
             } catch (const std::runtime_error &) { acc = 0; }
             if (accepted_each) accepted_each[j] = acc;
             ok += (size_t)acc;
@@ -410,14 +418,7 @@ int zkaes_verify_digest_chunked(const zkaes_vk *vk, int circuit_kind, const uint
             int acc = 0;
             try {
                 zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                std::vector<zk::Fr> pub;
-                uint8_t counter[16];
-                if (cbc) append_bits(pub, j ? ct + chunk * j - 16 : iv_or_icb, 16);
-                if (ctr) { zk::ctr_counter_add(iv_or_icb, (uint64_t)j * (chunk / 16), counter); append_bits(pub, counter, 16); }
-                append_bits(pub, ct + chunk * j, chunk);
-                if (key_tag) append_bits(pub, key_tag, key_tag_len);
-                append_bits(pub, states + 32 * j, 64);                                               // states[j] is H_in, states[j + 1] H_out
-                acc = zk::verify(vk->vk, pub, p) ? 1 : 0;
+                acc = zk::verify(vk->vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states), p) ? 1 : 0;
             } catch (const std::runtime_error &) { acc = 0; }
             if (accepted_each) accepted_each[j] = acc;
             ok += (size_t)acc;
@@ -579,6 +580,40 @@ int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t
             }
         }
         out[9] = joint; out[10] = next_pow2(c.num_constraints); out[11] = next_pow2(joint);
+    });
+}
+// ---- batch verification (include/zkaes.h): the host back end; zkaes_verify_batch_gpu and the kernel probes are in capi.cpp
+int zkaes_verify_batch(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        std::unique_ptr<zk::BatchBackend> be = zk::make_host_batch_backend();
+        zk::capi::verify_batch_call(vk, proofs, proof_lens, n, public_input_bits, n_bits, accepted_each, n_accepted, *be);
+    });
+}
+int zkaes_verify_batch_timings(double out[8]) {
+    return guard([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        const zk::BatchTimings &t = g_batch_timings;
+        out[0] = t.parse_ms; out[1] = t.decompress_ms; out[2] = t.transcripts_ms; out[3] = t.xhat_ms; out[4] = t.msm_ms; out[5] = t.pairing_ms; out[6] = t.total_ms; out[7] = (double)t.sub_batches;
+    });
+}
+int zkaes_chunk_public_inputs(int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states,
+                              uint8_t *out_bits, size_t *n_bits) {
+    return guard([&] {
+        if (!ct) throw std::invalid_argument("null argument");
+        const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
+        if (!ecb && !cbc && !ctr) throw std::invalid_argument("chunk_public_inputs: circuit_kind must be ECB, CBC or CTR");
+        if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument("chunk_public_inputs: an iv or initial counter block for CBC and CTR, NULL for ECB");
+        require_opt_key_tag(key_tag, key_tag_len);
+        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument("chunk_public_inputs: the ciphertext must be n_chunks equal, non-empty slices");
+        const size_t chunk = ct_len / n_chunks;
+        if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument("chunk_public_inputs: every slice must be whole blocks (a lone CTR proof takes any length)");
+        const size_t row = (ecb ? 0 : 128) + 8 * chunk + 8 * key_tag_len + (states ? 512 : 0);
+        if (n_bits) *n_bits = row;
+        if (!out_bits) return;
+        for (size_t j = 0; j < n_chunks; j++) {
+            std::vector<zk::Fr> pub = chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states);
+            for (size_t i = 0; i < row; i++) out_bits[j * row + i] = pub[i].is_zero() ? 0 : 1;
+        }
     });
 }
 int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {

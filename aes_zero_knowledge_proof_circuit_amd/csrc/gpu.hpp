@@ -216,8 +216,19 @@ MsmStats msm_stats(bool reset);   // process-wide totals (thread-safe)
 // =====================================================================================================================
 // Marlin-side kernels over the BLS12-377 scalar field (kernels_poly.hip, kernels_witness.hip)
 namespace zk {
+struct G1Compressed;      // verify_batch.hpp
 namespace gpu {
 using F = Fr377;
+
+// ---- batch verifier (kernels_verify.hip; verify_batch.hpp).  All pointers device pointers
+// pts[i] = canonical x limbs + sign flag of a compressed BLS12-377 G1 point (never the infinity encoding): status[i] = fq_sqrt.cuh's G1_OK / G1_NOT_ON_CURVE /
+// G1_NOT_IN_SUBGROUP, out[i] = the affine point (Montgomery limbs) when OK, else (0, 0).  One lane per point
+void g1_decompress_check(const G1Compressed *pts, size_t n, Affine<Fq377> *out, uint8_t *status, stream_t s);
+// out[i] = a square root of in[i] (Montgomery limbs), ok[i] = 1; ok[i] = 0 and out[i] = 0 for a non-residue
+void fq_sqrt_batch(const Fq377 *in, size_t n, Fq377 *out, uint8_t *ok, stream_t s);
+// out[i] = x^(betas[i]) over the domain of size 2^lg_m (generator gx), x = [1, row i's n_bits bits, zeros]; bits = n rows of `words` 32-bit words, LSB first.  One
+// workgroup per row; takes the indicator branch when a beta lies in the domain
+void public_input_eval(F *out, const F *betas, const uint32_t *bits, size_t words, size_t n, size_t n_bits, int lg_m, const F &gx, stream_t s);
 
 void poly_set_at(F *p, size_t idx, const F &val, stream_t s);                 // p[idx] = val
 void poly_add_at(F *p, size_t idx, const F &val, stream_t s);                 // p[idx] += val

@@ -21,6 +21,7 @@
 #include "trace_layout.h"
 #include "transcript.hpp"
 #include "marlin_host.hpp"
+#include "verify_batch.hpp"
 
 namespace zk {
 namespace {
@@ -1541,6 +1542,77 @@ std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, 
     pk->impl = new ProvingKeyImpl();
     pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, 0, 0, 0, role);
     return pk;
+}
+
+// =====================================================================================================================
+// batch verifier, device back end (verify_batch.hpp): the protocol is marlin_codec.cpp's; the points are decompressed and checked, the public inputs
+// evaluated and the two MSMs of every (sub-)batch run on the GPU.  No proving key and no SRS: a process that holds a verifying key alone can use it.  The bases of a
+// batch are uploaded once; a sub-batch of the bisection is a RANGE of them -- msm_prepare's two-vector form puts the range's own scalars and the key's ten into one
+// Pippenger instance -- on the Weierstrass law, whose accumulation replays P = +-Q additions with the complete formulas and skips infinity bases: the points are the
+// prover's, not ours
+namespace {
+struct DeviceBatchBackend : BatchBackend {
+    gpu::StreamGuard s;
+    gpu::WorkspaceGuard ws;
+    gpu::DevPtr<Affine28<Fq377P>> bases28, w28;      // np x VB_OWN own points then the key's VB_SHARED | W_beta, W_gamma of every proof
+    gpu::DevPtr<F> d_own, d_shared, d_w;
+    const Fr *own_up = nullptr, *w_up = nullptr;     // the host arrays d_own / d_w hold
+    size_t np = 0;
+    void decompress(const G1Compressed *pts, size_t n, G1A *out, uint8_t *status) override {
+        gpu::DevPtr<G1Compressed> d_pts(n);
+        gpu::DevPtr<G1A> d_out(n);
+        gpu::DevPtr<uint8_t> d_st(n);
+        gpu::h2d(d_pts, pts, n * sizeof(G1Compressed), s);
+        gpu::g1_decompress_check(d_pts, n, d_out, d_st, s);
+        gpu::d2h(out, d_out, n * sizeof(G1A), s);
+        gpu::d2h(status, d_st, n, s);
+    }
+    void public_input_eval(int lg_m, const Fr *betas, const uint8_t *bits, size_t n, size_t n_bits, Fr *out) override {
+        const size_t words = (n_bits + 31) / 32;
+        std::vector<uint32_t> packed(n * words + 1, 0);
+        for (size_t i = 0; i < n; i++) for (size_t j = 0; j < n_bits; j++) if (bits[i * n_bits + j]) packed[i * words + (j >> 5)] |= 1u << (j & 31);
+        gpu::DevPtr<uint32_t> d_bits(packed.size());
+        gpu::DevPtr<F> d_betas(n), d_out(n);
+        gpu::h2d(d_bits, packed.data(), packed.size() * 4, s);
+        gpu::h2d(d_betas, betas, n * sizeof(F), s);
+        gpu::public_input_eval(d_out, d_betas, d_bits, words, n, n_bits, lg_m, domain_gen(lg_m), s);
+        gpu::d2h(out, d_out, n * sizeof(F), s);
+    }
+    void set_bases(const G1A *own, size_t np_, const G1A *shared) override {
+        np = np_;
+        const size_t nb = np * VB_OWN + VB_SHARED;
+        std::vector<G1A> w(2 * np);
+        for (size_t i = 0; i < np; i++) { w[2 * i] = own[i * VB_OWN + 11]; w[2 * i + 1] = own[i * VB_OWN + 12]; }
+        gpu::DevPtr<G1A> tmp(nb + 2 * np);
+        gpu::h2d(tmp, own, np * VB_OWN * sizeof(G1A), s);
+        gpu::h2d(tmp + np * VB_OWN, shared, VB_SHARED * sizeof(G1A), s);
+        gpu::h2d(tmp + nb, w.data(), w.size() * sizeof(G1A), s);
+        bases28.alloc(nb); w28.alloc(2 * np);
+        gpu::convert_bases<Bls377>(bases28, tmp, nb, s);
+        gpu::convert_bases<Bls377>(w28, tmp + nb, 2 * np, s);
+        d_own.alloc(np * VB_OWN); d_shared.alloc(VB_SHARED); d_w.alloc(2 * np);
+        own_up = w_up = nullptr;
+        gpu::sync(s);
+    }
+    XYZZ<Fq377> msm_main(const Fr *own_scalars, size_t lo, size_t hi, const Fr *shared_scalars) override {
+        if (lo >= hi || hi > np) throw std::invalid_argument("verify_batch: bad sub-batch range");
+        if (own_up != own_scalars) { gpu::h2d(d_own, own_scalars, np * VB_OWN * sizeof(F), s); own_up = own_scalars; }
+        gpu::h2d(d_shared, shared_scalars, VB_SHARED * sizeof(F), s);
+        gpu::sync(s);
+        // bases index from the range's first point: the key's ten sit (np - lo) x VB_OWN further on
+        gpu::msm_prepare<Bls377>(ws, d_own + lo * VB_OWN, (hi - lo) * VB_OWN, d_shared, VB_SHARED, (np - lo) * VB_OWN, s);
+        return gpu::msm_finish<Bls377>(ws, bases28 + lo * VB_OWN, s);
+    }
+    XYZZ<Fq377> msm_w(const Fr *w_scalars, size_t lo, size_t hi) override {
+        if (lo >= hi || hi > np) throw std::invalid_argument("verify_batch: bad sub-batch range");
+        if (w_up != w_scalars) { gpu::h2d(d_w, w_scalars, 2 * np * sizeof(F), s); w_up = w_scalars; gpu::sync(s); }
+        return gpu::msm<Bls377>(ws, w28 + 2 * lo, d_w + 2 * lo, 2 * (hi - lo), s);
+    }
+};
+}  // namespace
+std::unique_ptr<BatchBackend> make_device_batch_backend() {
+    gpu::require_device();
+    return std::unique_ptr<BatchBackend>(new DeviceBatchBackend());
 }
 
 }  // namespace zk

@@ -2,51 +2,22 @@
 // Marlin verifier (src/lib.rs:116-136 -> simpleworks verify_proof -> ark-marlin verify).  Takes UNTRUSTED bytes (proofs, verifying keys): built a second time with
 // -fsanitize=address,undefined,fuzzer and driven by tests/fuzz_host.cpp (tests/test_fuzz_host.py); no HIP header is included here.
 #include "marlin_host.hpp"
+#include <chrono>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
+#include <memory>
 #include <stdexcept>
 #include "transcript.hpp"
+#include "fq_sqrt.cuh"
+#include "verify_batch.hpp"
 
 namespace zk {
 namespace {
 using namespace hostx;
 
-// Fq square root (Tonelli-Shanks; q - 1 = 2^46 * t) for point decompression
-struct SqrtConsts {
-    uint32_t t_limbs[12], tp1h_limbs[12], half_limbs[12];
-    Fq377 z_t;   // nonresidue^t
-    int S = 0;
-    SqrtConsts() {
-        uint32_t qm1[12];
-        for (int i = 0; i < 12; i++) qm1[i] = FQ377_P[i];
-        qm1[0] -= 1;
-        auto shr1 = [](uint32_t *v) { for (int i = 0; i < 12; i++) v[i] = (v[i] >> 1) | (i < 11 ? v[i + 1] << 31 : 0); };
-        memcpy(half_limbs, qm1, sizeof qm1); shr1(half_limbs);
-        memcpy(t_limbs, qm1, sizeof qm1);
-        while (!(t_limbs[0] & 1)) { shr1(t_limbs); S++; }
-        memcpy(tp1h_limbs, t_limbs, sizeof t_limbs);
-        tp1h_limbs[0] += 1;   // t odd -> no carry beyond limb 0 unless 0xffffffff
-        shr1(tp1h_limbs);
-        Fq377 minus_one = Fq377::one().neg();
-        for (uint64_t c = 2;; c++) { Fq377 cand = Fq377::from_u64(c); if (cand.pow(half_limbs, 12) == minus_one) { z_t = cand.pow(t_limbs, 12); break; } }
-    }
-};
-bool fq_sqrt(const Fq377 &a, Fq377 &out) {
-    if (a.is_zero()) { out = a; return true; }
-    static const SqrtConsts K;          // C++11 magic static: initialised exactly once, also when the first callers race (verifier-only processes, several threads)
-    if (!(a.pow(K.half_limbs, 12) == Fq377::one())) return false;
-    Fq377 c = K.z_t, x = a.pow(K.tp1h_limbs, 12), b = a.pow(K.t_limbs, 12);
-    int m = K.S;
-    while (!(b == Fq377::one())) {
-        int i = 0;
-        Fq377 bb = b;
-        while (!(bb == Fq377::one())) { bb = bb.sqr(); i++; }
-        Fq377 g = c;
-        for (int k = 0; k < m - i - 1; k++) g = g.sqr();
-        x = x * g; c = g.sqr(); b = b * c; m = i;
-    }
-    out = x;
-    return true;
-}
+// Fq square root for point decompression: fq_sqrt.cuh, shared with the device
+bool fq_sqrt(const Fq377 &a, Fq377 &out) { return zk::fq_sqrt(sqrt_consts(), a, out); }
 
 struct Reader {
     const uint8_t *p; size_t n, off = 0;
@@ -75,17 +46,14 @@ struct Reader {
             for (int i = 0; i < 12; i++) if (raw[i]) throw std::runtime_error("deserialize_proof: point at infinity with a non-zero x coordinate");   // one encoding per point
             return G1A::inf();
         }
-        G1A a; a.x = Fq377::from_raw(raw);
-        Fq377 y;
-        if (!fq_sqrt(a.x.sqr() * a.x + Bls377::b(), y)) throw std::runtime_error("deserialize_proof: x is not on the curve");
-        uint32_t yr[12], nyr[12];
-        y.to_raw(yr); y.neg().to_raw(nyr);
-        bool gt = false;
-        for (int i = 11; i >= 0; i--) if (yr[i] != nyr[i]) { gt = yr[i] > nyr[i]; break; }
-        a.y = (gt == y_gt) ? y : y.neg();
+        G1A a;
         // ark-ec 0.3 GroupAffine::deserialize: is_in_correct_subgroup_assuming_on_curve, i.e. [r]P == O (the curve has cofactor (x-1)^2/3: a
         // small-order component would survive the pairing check and make proofs malleable)
-        if (!XYZZ<Fq377>::from_affine(a).mul_raw(FR377_P, 8).is_inf()) throw std::runtime_error("deserialize_proof: point is not in the prime-order subgroup");
+        switch (g1_decompress_check(sqrt_consts(), raw, y_gt, a)) {
+            case G1_NOT_ON_CURVE: throw std::runtime_error("deserialize_proof: x is not on the curve");
+            case G1_NOT_IN_SUBGROUP: throw std::runtime_error("deserialize_proof: point is not in the prime-order subgroup");
+            default: break;
+        }
         return a;
     }
 };
@@ -429,6 +397,364 @@ bool verify(const VerifyingKey &vk, const std::vector<Fr> &public_input_in, cons
     G1A Ps[2] = {total_w.neg().to_affine(), total_c.to_affine()};
     pairing::G2Affine Qs[2] = {vk.beta_h, vk.h};
     return pairing::pairing_product_is_one(Ps, Qs, 2);
+}
+
+// =====================================================================================================================
+// batch verifier (verify_batch.hpp): what verify() above does per proof up to its two Items, kept as scalars over base points; a random linear
+// combination of all 2n opening equations; two MSMs and one product of two pairings per (sub-)batch
+bool g1_parse_compressed(const uint8_t bytes[48], G1Compressed &out, bool *inf_out) {
+    uint8_t buf[48];
+    memcpy(buf, bytes, 48);
+    const bool inf = buf[47] & (1 << 6), y_gt = buf[47] & (1 << 7);
+    if (inf && y_gt) return false;
+    buf[47] &= 0x3f;
+    for (int i = 0; i < 12; i++) out.x[i] = (uint32_t)buf[4 * i] | (uint32_t)buf[4 * i + 1] << 8 | (uint32_t)buf[4 * i + 2] << 16 | (uint32_t)buf[4 * i + 3] << 24;
+    out.y_gt = y_gt ? 1 : 0;
+    if (Fq377::geq_mod(out.x)) return false;
+    if (inf) for (int i = 0; i < 12; i++) if (out.x[i]) return false;
+    *inf_out = inf;
+    return true;
+}
+
+namespace {
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+// a proof's bytes with its 13 points still compressed; the layout and every check of deserialize_proof, the has_shifted shapes of verify()
+struct RawProof {
+    G1Compressed pts[VB_OWN];
+    bool inf[VB_OWN];
+    Fr evals[4], random_v_beta;
+};
+bool parse_raw_proof(const uint8_t *bytes, size_t len, RawProof &p) {
+    size_t off = 0;
+    auto u8 = [&](uint8_t &v) { if (off + 1 > len) return false; v = bytes[off++]; return true; };
+    auto u64 = [&](uint64_t &v) { if (len - off < 8 || off > len) return false; v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)bytes[off + i] << (8 * i); off += 8; return true; };
+    auto expect64 = [&](uint64_t want) { uint64_t v; return u64(v) && v == want; };
+    auto expect8 = [&](uint8_t want) { uint8_t v; return u8(v) && v == want; };
+    auto fr = [&](Fr &v) {
+        if (len - off < 32) return false;
+        uint32_t raw[8];
+        for (int i = 0; i < 8; i++) raw[i] = (uint32_t)bytes[off + 4 * i] | (uint32_t)bytes[off + 4 * i + 1] << 8 | (uint32_t)bytes[off + 4 * i + 2] << 16 | (uint32_t)bytes[off + 4 * i + 3] << 24;
+        off += 32;
+        if (Fr::geq_mod(raw)) return false;
+        v = Fr::from_raw(raw);
+        return true;
+    };
+    auto g1 = [&](int slot) {
+        if (len - off < 48) return false;
+        bool ok = g1_parse_compressed(bytes + off, p.pts[slot], &p.inf[slot]);
+        off += 48;
+        return ok;
+    };
+    static const uint64_t round_len[3] = {4, 3, 2};
+    if (!expect64(3)) return false;
+    int ci = 0, slot = 0;
+    for (int rd = 0; rd < 3; rd++) {
+        if (!expect64(round_len[rd])) return false;
+        for (uint64_t i = 0; i < round_len[rd]; i++, ci++) {
+            if (!g1(slot++)) return false;
+            uint8_t tag;
+            if (!u8(tag) || tag != ((ci == 5 || ci == 7) ? 1 : 0)) return false;      // a bad Option tag, or a degree-bound shape verify() rejects
+            if (tag && !g1(slot++)) return false;
+        }
+    }
+    if (!expect64(4)) return false;
+    for (int i = 0; i < 4; i++) if (!fr(p.evals[i])) return false;
+    if (!expect64(3)) return false;
+    for (int i = 0; i < 3; i++) if (!expect8(0)) return false;
+    if (!expect64(2)) return false;
+    if (!g1(11) || !expect8(1) || !fr(p.random_v_beta)) return false;
+    if (!g1(12) || !expect8(0) || !expect8(0)) return false;
+    return off == len;
+}
+
+// the slots of a proof's own bases
+enum { S_W = 0, S_ZA, S_ZB, S_MASK, S_T, S_G1, S_G1S, S_H1, S_G2, S_G2S, S_H2, S_WB, S_WG };
+// ... and of the key's
+enum { K_IX = 0, K_SP = 6, K_G = 8, K_GG = 9 };
+
+struct Challenges { Fr alpha, eta_a, eta_b, eta_c, beta, gamma, ch; };
+struct Rows { Fr own[VB_OWN], shared[VB_SHARED], w[2]; };
+
+// the per-key part of the transcript's first message
+Bytes transcript_prefix(const VerifyingKey &vk) {
+    Bytes o;
+    o.put("MARLIN-2019", 11);
+    o.u64(vk.num_variables); o.u64(vk.num_constraints); o.u64(vk.num_non_zero);
+    for (int i = 0; i < 6; i++) { Commitment ic; ic.comm = vk.index_comms[i]; o.commitment_tobytes(ic); }
+    return o;
+}
+Challenges run_transcript(const Bytes &prefix, size_t n, size_t m, const uint8_t *bits, size_t n_bits, const G1A *own, const Fr *evals) {
+    Challenges c;
+    FiatShamirRng fs;
+    {
+        Bytes o = prefix;
+        Bytes enc[2];
+        enc[0].field(Fr::zero()); enc[1].field(Fr::one());
+        o.b.reserve(o.b.size() + 32 * m);
+        for (size_t i = 0; i + 1 < m; i++) { const Bytes &e = enc[i < n_bits && bits[i] ? 1 : 0]; o.b.insert(o.b.end(), e.b.begin(), e.b.end()); }
+        fs.initialize(o.b);
+    }
+    auto comm = [&](int slot, int shifted_slot) { Commitment k; k.comm = own[slot]; if (shifted_slot >= 0) { k.has_shifted = true; k.shifted = own[shifted_slot]; } return k; };
+    auto absorb = [&](std::initializer_list<Commitment> cs) { Bytes o; for (auto &k : cs) o.commitment_tobytes(k); fs.absorb(o.b); };
+    auto sample_outside_h = [&]() { Fr t; do { t = fs.rng().rand_field<Fr>(); } while (eval_vanishing(n, t).is_zero()); return t; };
+    absorb({comm(S_W, -1), comm(S_ZA, -1), comm(S_ZB, -1), comm(S_MASK, -1)});
+    c.alpha = sample_outside_h();
+    c.eta_a = fs.rng().rand_field<Fr>(); c.eta_b = fs.rng().rand_field<Fr>(); c.eta_c = fs.rng().rand_field<Fr>();
+    absorb({comm(S_T, -1), comm(S_G1, S_G1S), comm(S_H1, -1)});
+    c.beta = sample_outside_h();
+    absorb({comm(S_G2, S_G2S), comm(S_H2, -1)});
+    c.gamma = fs.rng().rand_field<Fr>();
+    { Bytes o; for (int i = 0; i < 4; i++) o.field(evals[i]); fs.absorb(o.b); }
+    { uint64_t lo = fs.rng().next_u64(), hi = fs.rng().next_u64(); uint32_t raw[8] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32), 0, 0, 0, 0}; c.ch = Fr::from_raw(raw); }
+    return c;
+}
+// verify()'s construct_linear_combinations and combine_and_normalize as scalars: equation beta weighted by rb, equation gamma by rg
+Rows scalar_rows(const VerifyingKey &vk, size_t n, size_t m, size_t k, const Challenges &c, const Fr &x_at_beta, const Fr *evals, const Fr &random_v_beta, const Fr &rb, const Fr &rg) {
+    Rows R;
+    for (auto &v : R.own) v = Fr::zero();
+    for (auto &v : R.shared) v = Fr::zero();
+    const Fr &alpha = c.alpha, &beta = c.beta, &gamma = c.gamma;
+    const Fr g1_b = evals[0], g2_g = evals[1], t_b = evals[2], zb_b = evals[3];
+    Fr vh_alpha = eval_vanishing(n, alpha), vh_beta = eval_vanishing(n, beta), vx_beta = eval_vanishing(m, beta), vk_gamma = eval_vanishing(k, gamma);
+    Fr r_alpha_at_beta = (vh_alpha - vh_beta) * (alpha - beta).inverse();
+    Fr bmul = gamma * g2_g + t_b * Fr::from_u64(k).inverse();
+    Fr vv = vh_alpha * vh_beta;
+    Fr outer_eval = Fr::zero() - (r_alpha_at_beta * c.eta_b * zb_b) - ((t_b * x_at_beta).neg()) - ((beta * g1_b).neg());
+    Fr inner_eval = Fr::zero() - ((alpha * beta * bmul).neg());
+    Fr chp[5]; chp[0] = Fr::one(); for (int i = 1; i < 5; i++) chp[i] = chp[i - 1] * c.ch;
+    auto sp = [&](size_t bound) { return K_SP + (bound == vk.degree_bounds[0] ? 0 : 1); };
+    // beta: g_1 (ch^0, shifted ch^1), outer_sumcheck (ch^2), t (ch^3), z_b (ch^4)
+    const Fr ob = rb * chp[2];
+    R.own[S_G1] = rb; R.own[S_G1S] = rb * chp[1];
+    R.shared[sp(n - 2)] = R.shared[sp(n - 2)] - rb * chp[1] * g1_b;
+    R.own[S_MASK] = ob;
+    R.own[S_ZA] = ob * r_alpha_at_beta * (c.eta_a + c.eta_c * zb_b);
+    R.own[S_W] = ob * (t_b * vx_beta).neg();
+    R.own[S_H1] = ob * vh_beta.neg();
+    R.own[S_T] = rb * chp[3];
+    R.own[S_ZB] = rb * chp[4];
+    Fr val_b = g1_b + outer_eval * chp[2] + t_b * chp[3] + zb_b * chp[4];
+    // gamma: g_2 (ch^0, shifted ch^1), inner_sumcheck (ch^2)
+    const Fr og = rg * chp[2];
+    R.own[S_G2] = rg; R.own[S_G2S] = rg * chp[1];
+    R.shared[sp(k - 2)] = R.shared[sp(k - 2)] - rg * chp[1] * g2_g;
+    R.shared[K_IX + 2] = og * c.eta_a * vv; R.shared[K_IX + 3] = og * c.eta_b * vv; R.shared[K_IX + 4] = og * c.eta_c * vv;
+    R.shared[K_IX + 0] = og * alpha * bmul; R.shared[K_IX + 1] = og * beta * bmul; R.shared[K_IX + 5] = og * bmul.neg();
+    R.own[S_H2] = og * vk_gamma.neg();
+    Fr val_g = g2_g + inner_eval * chp[2];
+    // z W + C - v g - rv gamma_g on the h side, -W on the beta_h side
+    R.own[S_WB] = rb * beta; R.own[S_WG] = rg * gamma;
+    R.shared[K_G] = (rb * val_b + rg * val_g).neg();
+    R.shared[K_GG] = (rb * random_v_beta).neg();
+    R.w[0] = rb; R.w[1] = rg;
+    return R;
+}
+
+// x^(beta) as verify() computes it
+Fr host_public_input_eval(int lg_m, const Fr &beta, const uint8_t *bits, size_t n_bits) {
+    const size_t m = (size_t)1 << lg_m;
+    auto xi = [&](size_t i) { return i == 0 || (i - 1 < n_bits && bits[i - 1]); };
+    Fr gx = domain_gen(lg_m), vx_beta = eval_vanishing(m, beta), acc = Fr::zero();
+    if (vx_beta.is_zero()) {                                   // beta in X: the Lagrange basis is an indicator
+        Fr e = Fr::one();
+        for (size_t i = 0; i < m; i++) { if (e == beta) acc = xi(i) ? Fr::one() : Fr::zero(); e = e * gx; }
+        return acc;
+    }
+    // L_i(beta) = v_X(beta) * g^i / (m * (beta - g^i)), one inversion for all of them
+    std::vector<Fr> den(m), pre(m);
+    Fr e = Fr::one(), accp = Fr::one();
+    for (size_t i = 0; i < m; i++) { den[i] = beta - e; e = e * gx; pre[i] = accp; accp = accp * den[i]; }
+    Fr inv = accp.inverse();
+    for (size_t i = m; i-- > 0;) { Fr d = den[i]; den[i] = inv * pre[i]; inv = inv * d; }
+    e = Fr::one();
+    for (size_t i = 0; i < m; i++) { if (xi(i)) acc = acc + e * den[i]; e = e * gx; }
+    return acc * vx_beta * Fr::from_u64(m).inverse();
+}
+
+// bucket method on the host's XYZZ code (complete: madd covers P = +-Q and infinity bases); `bits` = the scalars' width
+XYZZ<Fq377> host_msm(const G1A *bases, const Fr *scalars, size_t n, int bits) {
+    using X = XYZZ<Fq377>;
+    std::vector<uint32_t> raw(8 * n);
+    for (size_t i = 0; i < n; i++) scalars[i].to_raw(&raw[8 * i]);
+    const int c = n < 8 ? 2 : n < 64 ? 4 : n < 1024 ? 6 : n < 16384 ? 9 : 12, nwin = (bits + c - 1) / c;
+    std::vector<X> buckets(((size_t)1 << c) - 1);
+    X total = X::inf();
+    for (int w = nwin - 1; w >= 0; w--) {
+        for (int j = 0; j < c; j++) total = total.dbl();
+        for (auto &b : buckets) b = X::inf();
+        const int bit = w * c;
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t *r = &raw[8 * i];
+            uint64_t two = (uint64_t)r[bit >> 5] | ((bit >> 5) + 1 < 8 ? (uint64_t)r[(bit >> 5) + 1] << 32 : 0);
+            uint32_t d = (uint32_t)(two >> (bit & 31)) & ((1u << c) - 1);
+            if (d) buckets[d - 1].madd(bases[i]);
+        }
+        X run = X::inf(), sum = X::inf();
+        for (size_t d = buckets.size(); d-- > 0;) { run.add(buckets[d]); sum.add(run); }
+        total.add(sum);
+    }
+    return total;
+}
+
+struct HostBatchBackend : BatchBackend {
+    std::vector<G1A> bases;      // np x VB_OWN own points, then the key's VB_SHARED
+    size_t np = 0;
+    void decompress(const G1Compressed *pts, size_t n, G1A *out, uint8_t *status) override {
+        for (size_t i = 0; i < n; i++) status[i] = g1_decompress_check(sqrt_consts(), pts[i].x, pts[i].y_gt != 0, out[i]);
+    }
+    void public_input_eval(int lg_m, const Fr *betas, const uint8_t *bits, size_t n, size_t n_bits, Fr *out) override {
+        for (size_t i = 0; i < n; i++) out[i] = host_public_input_eval(lg_m, betas[i], bits + i * n_bits, n_bits);
+    }
+    void set_bases(const G1A *own, size_t np_, const G1A *shared) override {
+        np = np_;
+        bases.assign(own, own + np * VB_OWN);
+        bases.insert(bases.end(), shared, shared + VB_SHARED);
+    }
+    XYZZ<Fq377> msm_main(const Fr *own_scalars, size_t lo, size_t hi, const Fr *shared_scalars) override {
+        XYZZ<Fq377> r = host_msm(&bases[lo * VB_OWN], own_scalars + lo * VB_OWN, (hi - lo) * VB_OWN, Fr::BITS);
+        r.add(host_msm(&bases[np * VB_OWN], shared_scalars, VB_SHARED, Fr::BITS));
+        return r;
+    }
+    XYZZ<Fq377> msm_w(const Fr *w_scalars, size_t lo, size_t hi) override {
+        std::vector<G1A> w(2 * (hi - lo));
+        for (size_t i = lo; i < hi; i++) { w[2 * (i - lo)] = bases[i * VB_OWN + S_WB]; w[2 * (i - lo) + 1] = bases[i * VB_OWN + S_WG]; }
+        return host_msm(w.data(), w_scalars + 2 * lo, w.size(), 128);
+    }
+};
+}  // namespace
+std::unique_ptr<BatchBackend> make_host_batch_backend() { return std::unique_ptr<BatchBackend>(new HostBatchBackend()); }
+
+std::vector<uint8_t> verify_batch(const VerifyingKey &vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *bits, size_t n_bits, BatchBackend &be,
+                                  BatchTimings *timings) {
+    BatchTimings T;
+    const auto t_all = Clock::now();
+    std::vector<uint8_t> accepted(n, 0);
+    const size_t m = next_pow2(n_bits + 1);
+    if (m != vk.num_instance) { if (timings) *timings = T; return accepted; }      // InvalidPublicInputLength / the instance does not match the index: every proof rejected
+    const size_t nh = next_pow2(vk.num_constraints), nk = next_pow2(vk.num_non_zero);
+    // ---- parse; the points stay compressed
+    auto t0 = Clock::now();
+    std::vector<size_t> offs(n + 1, 0);
+    for (size_t i = 0; i < n; i++) offs[i + 1] = offs[i] + proof_lens[i];
+    std::vector<RawProof> raw(n);
+    std::vector<size_t> alive;               // proofs still in the batch
+    for (size_t i = 0; i < n; i++) if (parse_raw_proof(proofs + offs[i], proof_lens[i], raw[i])) alive.push_back(i);
+    T.parse_ms = ms_since(t0);
+    // ---- decompression and subgroup checks, every point of every parsed proof in one call
+    t0 = Clock::now();
+    std::vector<G1A> own;                    // alive.size() x VB_OWN
+    {
+        std::vector<G1Compressed> todo;
+        std::vector<size_t> where;
+        for (size_t a = 0; a < alive.size(); a++) for (size_t s = 0; s < VB_OWN; s++) if (!raw[alive[a]].inf[s]) { todo.push_back(raw[alive[a]].pts[s]); where.push_back(a * VB_OWN + s); }
+        std::vector<G1A> pts(todo.size() ? todo.size() : 1);
+        std::vector<uint8_t> st(todo.size() ? todo.size() : 1, 0);
+        if (!todo.empty()) be.decompress(todo.data(), todo.size(), pts.data(), st.data());
+        std::vector<G1A> all(alive.size() * VB_OWN, G1A::inf());
+        std::vector<uint8_t> bad(alive.size(), 0);
+        for (size_t j = 0; j < todo.size(); j++) { if (st[j] != G1_OK) bad[where[j] / VB_OWN] = 1; else all[where[j]] = pts[j]; }
+        std::vector<size_t> keep;
+        for (size_t a = 0; a < alive.size(); a++) if (!bad[a]) { keep.push_back(alive[a]); own.insert(own.end(), all.begin() + a * VB_OWN, all.begin() + (a + 1) * VB_OWN); }
+        alive.swap(keep);
+    }
+    T.decompress_ms = ms_since(t0);
+    const size_t np = alive.size();
+    if (np == 0) { T.total_ms = ms_since(t_all); if (timings) *timings = T; return accepted; }
+    // ---- transcripts
+    t0 = Clock::now();
+    const Bytes prefix = transcript_prefix(vk);
+    std::vector<Challenges> ch(np);
+    std::vector<Fr> betas(np);
+    std::vector<uint8_t> rows_bits(np * (n_bits ? n_bits : 1));
+    for (size_t a = 0; a < np; a++) {
+        const uint8_t *b = bits + alive[a] * n_bits;
+        if (n_bits) memcpy(&rows_bits[a * n_bits], b, n_bits);
+        ch[a] = run_transcript(prefix, nh, m, b, n_bits, &own[a * VB_OWN], raw[alive[a]].evals);
+        betas[a] = ch[a].beta;
+    }
+    T.transcripts_ms = ms_since(t0);
+    // ---- x^(beta_i)
+    t0 = Clock::now();
+    std::vector<Fr> xhat(np);
+    be.public_input_eval(log2_exact(m), betas.data(), rows_bits.data(), np, n_bits, xhat.data());
+    T.xhat_ms = ms_since(t0);
+    // ---- randomizers: ChaCha20 keyed with SHA-256 over the key, the batch size and every proof with its public input -- fixed only once the whole batch is
+    t0 = Clock::now();
+    ChaChaRng rrng;
+    {
+        Bytes d;
+        static const char domain[] = "zkaes verify_batch v1";
+        d.put(domain, sizeof domain);
+        std::vector<uint8_t> ark = serialize_vk_ark(vk);
+        d.u64(ark.size()); d.put(ark.data(), ark.size());
+        d.u64(n); d.u64(n_bits);
+        for (size_t i = 0; i < n; i++) {
+            d.u64(proof_lens[i]); d.put(proofs + offs[i], proof_lens[i]);
+            for (size_t j = 0; j < n_bits; j++) d.u8(bits[i * n_bits + j] ? 1 : 0);
+        }
+        const size_t whole = d.b.size() / 64 * 64;
+        uint8_t h[32], seed[32];
+        sha256_chain(nullptr, d.b.data(), whole, h);
+        sha256_finish(h, whole, d.b.data() + whole, d.b.size() - whole, seed);
+        rrng.reseed(seed, 20);
+    }
+    auto draw128 = [&]() {
+        for (;;) {
+            uint64_t lo = rrng.next_u64(), hi = rrng.next_u64();
+            if (!(lo | hi)) continue;          // a zero weight would take its equation out of the check
+            uint32_t r[8] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32), 0, 0, 0, 0};
+            return Fr::from_raw(r);
+        }
+    };
+    std::vector<Fr> rnd(2 * n);               // drawn for every proof of the call, in order, whether it is still in the batch or not
+    for (auto &r : rnd) r = draw128();
+    std::vector<Fr> own_sc(np * VB_OWN), w_sc(2 * np);
+    std::vector<Rows> rows(np);
+    for (size_t a = 0; a < np; a++) {
+        const size_t i = alive[a];
+        rows[a] = scalar_rows(vk, nh, m, nk, ch[a], xhat[a], raw[i].evals, raw[i].random_v_beta, rnd[2 * i], rnd[2 * i + 1]);
+        for (size_t s = 0; s < VB_OWN; s++) own_sc[a * VB_OWN + s] = rows[a].own[s];
+        w_sc[2 * a] = rows[a].w[0]; w_sc[2 * a + 1] = rows[a].w[1];
+    }
+    T.transcripts_ms += ms_since(t0);
+    G1A shared[VB_SHARED];
+    for (int i = 0; i < 6; i++) shared[K_IX + i] = vk.index_comms[i];
+    shared[K_SP] = vk.shift_powers[0]; shared[K_SP + 1] = vk.shift_powers[1]; shared[K_G] = vk.g; shared[K_GG] = vk.gamma_g;
+    t0 = Clock::now();
+    be.set_bases(own.data(), np, shared);
+    T.msm_ms += ms_since(t0);
+    // ---- the batch equation over proofs [lo, hi) of the survivors
+    auto holds = [&](size_t lo, size_t hi) {
+        auto t1 = Clock::now();
+        Fr sh[VB_SHARED];
+        for (auto &v : sh) v = Fr::zero();
+        for (size_t a = lo; a < hi; a++) for (size_t s = 0; s < VB_SHARED; s++) sh[s] = sh[s] + rows[a].shared[s];
+        XYZZ<Fq377> total_c = be.msm_main(own_sc.data(), lo, hi, sh), total_w = be.msm_w(w_sc.data(), lo, hi);
+        T.msm_ms += ms_since(t1);
+        t1 = Clock::now();
+        G1A Ps[2] = {total_w.neg().to_affine(), total_c.to_affine()};
+        pairing::G2Affine Qs[2] = {vk.beta_h, vk.h};
+        bool ok = pairing::pairing_product_is_one(Ps, Qs, 2);
+        T.pairing_ms += ms_since(t1);
+        T.sub_batches++;
+        return ok;
+    };
+    // bisection: a range that holds is accepted whole; one that fails is halved, and a lone proof's answer is its own two equations under its own randomizers.
+    // When the left half of a failing range holds, the right half is known to fail and is not checked again as a whole
+    std::function<bool(size_t, size_t, bool)> solve = [&](size_t lo, size_t hi, bool known_bad) {
+        if (!known_bad && holds(lo, hi)) { for (size_t a = lo; a < hi; a++) accepted[alive[a]] = 1; return true; }
+        if (hi - lo == 1) return false;
+        const size_t mid = lo + (hi - lo) / 2;
+        const bool left = solve(lo, mid, false);
+        solve(mid, hi, left);
+        return false;
+    };
+    solve(0, np, false);
+    T.total_ms = ms_since(t_all);
+    if (timings) *timings = T;
+    return accepted;
 }
 
 }  // namespace zk

@@ -647,6 +647,49 @@ int zkaes_stream_copy_bench(size_t bytes, int reps, double *gb_per_s);
  * production launch shape over an L2-resident table (the kernel with its gathers made free), out[3] = its shader clock, out[4] = its shader cycles per addition per wave
  * (three waves share a SIMD); out[5] = rounds measured.  Medians over the rounds. */
 int zkaes_int_rate_bench(double seconds, double out[8]);
+/* ---- Batch verification: n >= 1 proofs under ONE verifying key, each with its own public input, for the cost of two multi-scalar multiplications and
+ * ONE product of two pairings instead of n.  proofs = the n proofs' bytes back to back, proof_lens their lengths; public_input_bits = n rows of n_bits bytes, one 0/1
+ * byte per variable as zkaes_verify takes them (row i belongs to proof i; NULL when n_bits = 0).  accepted_each[i] (may be NULL) = 1 / 0, *n_accepted (may be NULL)
+ * their sum: the answers n calls of zkaes_verify would give, except that bytes which do not parse are a rejected proof here, never an error of the call (as in the
+ * chunked verifiers).
+ *
+ * For proof i the verifier redoes what zkaes_verify does up to its two KZG opening equations (at beta and at gamma) -- transcript, challenges, shape checks, the
+ * combined commitments and values -- but keeps both as SCALARS over base points: 11 over the proof's commitments, 2 over its opening proofs W, and scalars over the
+ * key's 6 index commitments, 2 shift powers, g and gamma_g.  With two 128-bit randomizers r per proof it accepts the batch iff
+ *     e(-sum r W, beta h) * e(sum r (z W + C) - (sum r v) g - (sum r rv) gamma_g, h) = 1,
+ * two MSMs (2n bases with 128-bit scalars; 13n + 10 bases with 253-bit scalars) and one pairing product.  The randomizers come from ChaCha20 keyed with SHA-256 over a
+ * domain string, the key's ark-serialize bytes, n, and every proof's length, bytes and public-input bits: they are fixed only once the whole batch is.  A batch accept
+ * implies each of the 2n equations with error about 2n / 2^128; zkaes_verify combines its two equations under upstream's FIXED test seed, which is weaker, so the two
+ * can differ only on proofs crafted against that seed (which the batch rejects).
+ *
+ * Rejected on their own, before the batch, and contributing nothing to it: bytes that do not parse, a non-canonical field element, a point off the curve or outside
+ * the prime-order subgroup, wrong degree-bound shapes; a public-input count that does not fit the key rejects every proof.  If the batch equation fails the survivors
+ * are halved and each half checked again over the prepared scalars, down to single proofs: one bad proof costs at most 2 ceil(log2 n) further sub-batches whose sizes
+ * halve, i.e. less than the work of two more full batches.
+ *
+ * zkaes_verify_batch runs everything on the host (no device needed); zkaes_verify_batch_gpu decompresses and checks the 13n points, evaluates the public inputs and
+ * runs the MSMs on the GPU (transcripts and the pairing stay on the host).  It needs no proving key. */
+int zkaes_verify_batch(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each,
+                       size_t *n_accepted);
+int zkaes_verify_batch_gpu(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each,
+                           size_t *n_accepted);
+/* where the calling thread's last batch call spent its time, in ms: out = {parse, decompress + subgroup checks, transcripts + scalar rows, public-input evaluation,
+ * MSMs (with the upload of the bases), pairings, whole call, number of (sub-)batches checked} */
+int zkaes_verify_batch_timings(double out[8]);
+/* The public-input rows of a chunked job, for the batch verifier: row j (n_bits bytes, 0/1) is exactly what zkaes_verify_encryption (ECB), zkaes_verify_cbc_chunked,
+ * zkaes_verify_ctr_chunked, zkaes_verify_chunked_kt and zkaes_verify_digest_chunked derive for chunk j -- the mode header (none; the chaining value entering the chunk;
+ * icb + j x the chunk's blocks), the chunk's ciphertext bits LSB first per byte, the key tag's bits when key_tag != NULL (key_tag_len 16 or 32, else 0), and
+ * (states[j], states[j + 1]) when states != NULL (32 (n_chunks + 1) bytes).  *n_bits (may be NULL) receives the row length; out_bits = NULL only asks for it. */
+int zkaes_chunk_public_inputs(int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t *key_tag, size_t key_tag_len,
+                              const uint8_t *states, uint8_t *out_bits, size_t *n_bits);
+/* The batch verifier's kernels, one launch per call (tests).  zkaes_g1_decompress_batch: n compressed BLS12-377 G1 points (48 bytes each, ark-serialize) ->
+ * out_xy (96 bytes each: x, y as Montgomery limbs; zeros unless status is 0) and status: 0 ok (on the curve, in the prime-order subgroup), 1 the infinity encoding,
+ * 2 x is not on the curve, 3 not in the subgroup, 4 malformed (both flags set, x >= q, infinity flag over a non-zero x; decided on the host).
+ * zkaes_fq_sqrt_batch: n base-field elements (48 bytes, Montgomery limbs) -> a square root each and is_square = 1, or zeros and 0.
+ * zkaes_public_input_eval: out[i] = x^(betas[i]) (32 bytes, Montgomery limbs) over the domain of size 2^lg_m for x = [1, row i of bits (n_bits 0/1 bytes), zeros]. */
+int zkaes_g1_decompress_batch(const uint8_t *points48, size_t n, uint8_t *out_xy, uint8_t *status);
+int zkaes_fq_sqrt_batch(const uint8_t *in, size_t n, uint8_t *out, uint8_t *is_square);
+int zkaes_public_input_eval(int lg_m, const uint8_t *betas, const uint8_t *bits, size_t n, size_t n_bits, uint8_t *out);
 /* AES witness only: fills z (padded instance + witness, one byte per variable) for a message under the key's circuit */
 int zkaes_aes_witness(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t secret_key[16], uint8_t *z, size_t z_cap, size_t *z_len);
 
