@@ -51,6 +51,15 @@ def _take(ptr, n):
     return data
 
 
+def _split(blob, lens, n):
+    """the n proofs packed one behind the other in blob, proof i lens[i] bytes long"""
+    proofs, off = [], 0
+    for i in range(n):
+        proofs.append(blob[off:off + lens[i]])
+        off += lens[i]
+    return proofs
+
+
 def device_count():
     return lib().zkaes_device_count()
 
@@ -123,7 +132,36 @@ class VerifyingKey:
 
 class ProvingKey:
     def __init__(self, ptr):
-        self._p = C.c_void_p(ptr)
+        self._handle = C.c_void_p(ptr)
+
+    @property
+    def _p(self):
+        """the library's handle, for every call that takes this key: a key that was freed raises instead of handing the library a null pointer"""
+        if not self._handle:
+            raise ZkAesError("this proving key has been freed")
+        return self._handle
+
+    def _witness(self, fn, *args):
+        """z of one of the library's witness entries: asked for its size, then filled"""
+        n = C.c_size_t()
+        _check(fn(self._p, *args, None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        _check(fn(self._p, *args, buf, n, C.byref(n)))
+        return buf.raw
+
+    def _encrypt_chunked(self, mode, message, secret_key, header, zk_seed, first_proof_index, n_chunks):
+        """the chunked entry of mode "" (ECB, header None), "cbc_" or "ctr_" (header = the iv / initial counter block) -> (ciphertext or None for ECB, chunk-proofs)"""
+        seed = self._seed_arg(zk_seed)
+        lens = (C.c_size_t * max(n_chunks, 1))()
+        ct = None if header is None else C.create_string_buffer(max(len(message), 1))
+        out, n = C.c_void_p(), C.c_size_t()
+        head = (bytes(message), C.c_size_t(len(message)), bytes(secret_key)) + (() if header is None else (bytes(header),)) + (self._p,)
+        tail = (() if ct is None else (ct,)) + (C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks))
+        if zk_seed is None:
+            _check(getattr(lib(), "zkaes_encrypt_%schunked" % mode)(*head, *tail))
+        else:
+            _check(getattr(lib(), "zkaes_encrypt_%schunked_seeded_at" % mode)(*head, seed, C.c_uint64(first_proof_index), *tail))
+        return None if ct is None else ct.raw[:len(message)], _split(_take(out, n), lens, n_chunks)
 
     def clone(self):  # device-resident and immutable: a clone is the same handle (benches/benchmark_encrypt.rs:46 clones per call)
         return self
@@ -167,12 +205,7 @@ class ProvingKey:
             raise ZkAesError("h_in must be 32 bytes")
         hdr = self._digest_header_bytes(header)
         self._need_header(hdr)
-        n = C.c_size_t()
-        args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in))
-        _check(lib().zkaes_aes_witness_pd(*args, None, C.c_size_t(0), C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().zkaes_aes_witness_pd(*args, buf, n, C.byref(n)))
-        return buf.raw
+        return self._witness(lib().zkaes_aes_witness_pd, bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in))
 
     def _need_header(self, hdr):
         """the mode's header has the length this key reads from the pointer: the public input is One, the header bits, the ciphertext bits (one byte per message byte,
@@ -216,11 +249,7 @@ class ProvingKey:
         _check(lib().zkaes_encrypt_digest_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kbuf, C.c_size_t(len(kbuf)), hbuf or None, C.c_size_t(len(hbuf)),
                                                           None if h_ins is None else b"".join(bytes(h) for h in h_ins), self._p, seed, C.c_uint64(first_proof_index), cts, tags, outs,
                                                           C.byref(out), C.byref(total), lens))
-        blob = _take(out, total)
-        proofs, off = [], 0
-        for i in range(n):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
+        proofs = _split(_take(out, total), lens, n)
         size = len(mb) // n if n else 0
         gcm = self.mode()[0] == CIRCUIT_AES_GCM
         return ([cts.raw[size * i:size * (i + 1)] for i in range(n)], [tags.raw[16 * i:16 * i + 16] if gcm else None for i in range(n)],
@@ -247,12 +276,7 @@ class ProvingKey:
         out, n = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_encrypt_digest_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in), self._p, seed,
                                                             C.c_uint64(first_proof_index), ct, states, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
-        blob = _take(out, n)
-        proofs, off = [], 0
-        for i in range(n_chunks):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
-        return ct.raw[:len(message)], [states.raw[32 * j:32 * j + 32] for j in range(n_chunks + 1)], proofs
+        return ct.raw[:len(message)], [states.raw[32 * j:32 * j + 32] for j in range(n_chunks + 1)], _split(_take(out, n), lens, n_chunks)
 
     def _need_key(self, secret_key, other=None, other_name=None, other_len=16):
         """the secret key has the length this proving key was synthesized for (and `other`, the iv / icb, its own): the library reads that many bytes from the pointer"""
@@ -328,87 +352,40 @@ class ProvingKey:
 
     def witness(self, message, secret_key):
         self._need_key(secret_key)
-        n = C.c_size_t()
-        _check(lib().zkaes_aes_witness(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), None, C.c_size_t(0), C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().zkaes_aes_witness(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), buf, n, C.byref(n)))
-        return buf.raw
+        return self._witness(lib().zkaes_aes_witness, bytes(message), C.c_size_t(len(message)), bytes(secret_key))
 
     def witness_cbc(self, message, secret_key, iv):
         """z (padded instance + witness, one byte per variable) of a CBC key: One, the 128 IV bits, the ciphertext bits, padding, then the witness"""
         self._need_key(secret_key, iv, "iv")
-        n = C.c_size_t()
-        _check(lib().zkaes_aes_witness_cbc(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), None, C.c_size_t(0), C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().zkaes_aes_witness_cbc(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), buf, n, C.byref(n)))
-        return buf.raw
+        return self._witness(lib().zkaes_aes_witness_cbc, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv))
 
     def encrypt_cbc_chunked(self, message, secret_key, iv, zk_seed=None, first_proof_index=0):
         """(ciphertext, chunk-proofs) of a long CBC message.  iv = the chaining value entering this call's first chunk (a job split over several calls takes each call's
         from cbc_ciphertext); zk_seed and first_proof_index as encrypt_chunked"""
         self._need_key(secret_key, iv, "iv")
-        seed = self._seed_arg(zk_seed)
         chunk = self._message_bytes(128)
         if chunk <= 0:
             raise ZkAesError("proving key was not synthesized for the AES-CBC circuit")
-        n_chunks = len(message) // chunk
-        lens = (C.c_size_t * max(n_chunks, 1))()
-        ct = C.create_string_buffer(max(len(message), 1))
-        out, n = C.c_void_p(), C.c_size_t()
-        if zk_seed is None:
-            _check(lib().zkaes_encrypt_cbc_chunked(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), self._p, ct, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
-        else:
-            _check(lib().zkaes_encrypt_cbc_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), self._p, seed, C.c_uint64(first_proof_index), ct,
-                                                             C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
-        blob = _take(out, n)
-        proofs, off = [], 0
-        for i in range(n_chunks):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
-        return ct.raw[:len(message)], proofs
+        return self._encrypt_chunked("cbc_", message, secret_key, iv, zk_seed, first_proof_index, len(message) // chunk)
 
     def witness_ctr(self, message, secret_key, icb):
         """z (padded instance + witness, one byte per variable) of a CTR key: One, the 128 icb bits, the ciphertext bits, padding, then the witness"""
         self._need_key(secret_key, icb, "icb")
-        n = C.c_size_t()
-        _check(lib().zkaes_aes_witness_ctr(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), None, C.c_size_t(0), C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().zkaes_aes_witness_ctr(self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), buf, n, C.byref(n)))
-        return buf.raw
+        return self._witness(lib().zkaes_aes_witness_ctr, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb))
 
     def encrypt_ctr_chunked(self, message, secret_key, icb, zk_seed=None, first_proof_index=0):
         """(ciphertext, chunk-proofs) of a long CTR message over a key for whole blocks; chunk j is proven under icb + j * (the key's blocks).  icb = the counter of this
         call's first block (a job split over several calls passes ctr_counter_add(icb, blocks before)); zk_seed and first_proof_index as encrypt_chunked"""
         self._need_key(secret_key, icb, "icb")
-        seed = self._seed_arg(zk_seed)
         chunk = self._message_bytes(128)
         if chunk <= 0 or len(message) == 0 or len(message) % chunk:
             raise ZkAesError("message length must be a non-zero multiple of the CTR key's plaintext length")
-        n_chunks = len(message) // chunk
-        lens = (C.c_size_t * n_chunks)()
-        ct = C.create_string_buffer(len(message))
-        out, n = C.c_void_p(), C.c_size_t()
-        if zk_seed is None:
-            _check(lib().zkaes_encrypt_ctr_chunked(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), self._p, ct, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
-        else:
-            _check(lib().zkaes_encrypt_ctr_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(icb), self._p, seed, C.c_uint64(first_proof_index), ct,
-                                                             C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
-        blob = _take(out, n)
-        proofs, off = [], 0
-        for i in range(n_chunks):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
-        return ct.raw[:len(message)], proofs
+        return self._encrypt_chunked("ctr_", message, secret_key, icb, zk_seed, first_proof_index, len(message) // chunk)
 
     def witness_gcm(self, message, secret_key, iv, aad=b""):
         """z (padded instance + witness, one byte per variable) of a GCM key: One, the 96 iv bits, the aad, ciphertext and tag bits, padding, then the witness"""
         _gcm_args(secret_key, iv, self.key_bytes())
-        n = C.c_size_t()
-        args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)))
-        _check(lib().zkaes_aes_witness_gcm(*args, None, C.c_size_t(0), C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().zkaes_aes_witness_gcm(*args, buf, n, C.byref(n)))
-        return buf.raw
+        return self._witness(lib().zkaes_aes_witness_gcm, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)))
 
     def segment_info(self):
         """None for a key that is no GCM segment key, else {"role", "blocks", "message_bytes", "aad_bytes"}"""
@@ -421,12 +398,7 @@ class ProvingKey:
     def witness_gcm_segment(self, message, secret_key, header):
         """z (padded instance + witness, one byte per variable) of a segment key; header = gcm_segment_header(...)"""
         self._need_key(secret_key)
-        n = C.c_size_t()
-        args = (self._p, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(header), C.c_size_t(len(header)))
-        _check(lib().zkaes_aes_witness_gcm_seg(*args, None, C.c_size_t(0), C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().zkaes_aes_witness_gcm_seg(*args, buf, n, C.byref(n)))
-        return buf.raw
+        return self._witness(lib().zkaes_aes_witness_gcm_seg, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(header), C.c_size_t(len(header)))
 
     def encrypt_gcm_segment_batch(self, messages, secret_keys, headers, zk_seed=None, first_proof_index=0):
         """n independent proofs over this segment key, each under its own gcm_segment_header -> the proofs; the caller answers for what the headers say
@@ -442,12 +414,7 @@ class ProvingKey:
         out, total = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_encrypt_gcm_segment_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), self._p, seed,
                                                                C.c_uint64(first_proof_index), C.byref(out), C.byref(total), lens))
-        blob = _take(out, total)
-        proofs, off = [], 0
-        for i in range(n):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
-        return proofs
+        return _split(_take(out, total), lens, n)
 
     def encrypt_gcm_batch(self, messages, secret_keys, ivs, aads, zk_seed=None, first_proof_index=0):
         """n independent GCM records over this key -> (ciphertexts, tags, proofs), three lists.  Every message has the key's plaintext length, every aad the key's aad
@@ -468,13 +435,8 @@ class ProvingKey:
         out, total = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_encrypt_gcm_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), self._p, seed, C.c_uint64(first_proof_index),
                                                        cts, tags, C.byref(out), C.byref(total), lens))
-        blob = _take(out, total)
-        proofs, off = [], 0
-        for i in range(n):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
         size = len(mb) // n if n else 0
-        return [cts.raw[size * i:size * (i + 1)] for i in range(n)], [tags.raw[16 * i:16 * i + 16] for i in range(n)], proofs
+        return [cts.raw[size * i:size * (i + 1)] for i in range(n)], [tags.raw[16 * i:16 * i + 16] for i in range(n)], _split(_take(out, total), lens, n)
 
     def prove_ops(self, x, y, zk_seed=None):
         out, n = C.c_void_p(), C.c_size_t()
@@ -494,22 +456,7 @@ class ProvingKey:
         """chunk-proofs of a long ECB message.  zk_seed: None = a fresh OS seed per call, 32 bytes = caller's seed (proof i uses index first_proof_index + i),
         PARITY = the reference's fixed prover randomness for every proof"""
         self._need_key(secret_key)
-        seed = self._seed_arg(zk_seed)
-        chunk = self._message_bytes(0)
-        n_chunks = len(message) // chunk
-        lens = (C.c_size_t * max(n_chunks, 1))()
-        out, n = C.c_void_p(), C.c_size_t()
-        if zk_seed is None:
-            _check(lib().zkaes_encrypt_chunked(bytes(message), C.c_size_t(len(message)), bytes(secret_key), self._p, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
-        else:
-            _check(lib().zkaes_encrypt_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), self._p, seed, C.c_uint64(first_proof_index), C.byref(out), C.byref(n), lens,
-                                                         C.c_size_t(n_chunks)))
-        blob = _take(out, n)
-        proofs, off = [], 0
-        for i in range(n_chunks):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
-        return proofs
+        return self._encrypt_chunked("", message, secret_key, None, zk_seed, first_proof_index, len(message) // self._message_bytes(0))[1]
 
     def encrypt_batch(self, messages, secret_keys, zk_seed=None, first_proof_index=0):
         """n independent proofs: messages = list of equal-length byte strings (the key's plaintext length), secret_keys = list of keys of key_bytes() bytes each; zk_seed as encrypt_chunked"""
@@ -530,18 +477,13 @@ class ProvingKey:
             _check(lib().zkaes_encrypt_batch(C.c_size_t(n), mb, kb, self._p, C.byref(out), C.byref(total), lens))
         else:
             _check(lib().zkaes_encrypt_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), self._p, seed, C.c_uint64(first_proof_index), C.byref(out), C.byref(total), lens))
-        blob = _take(out, total)
-        proofs, off = [], 0
-        for i in range(n):
-            proofs.append(blob[off:off + lens[i]])
-            off += lens[i]
-        return proofs
+        return _split(_take(out, total), lens, n)
 
     def free(self):
         """release the key now (device memory: index, prover contexts, and the universal SRS if this was its last key) instead of at garbage collection"""
-        if self._p:
-            lib().zkaes_pk_free(self._p)
-            self._p = None
+        if self._handle:
+            lib().zkaes_pk_free(self._handle)
+            self._handle = None
 
     def __del__(self):
         try:
@@ -1065,12 +1007,7 @@ def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_s
     _check(lib().zkaes_encrypt_gcm_segments_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), head._p,
                                                       None if mid is None else mid._p, tail._p, b"".join(bytes(s) for s in salts), seed, C.c_size_t(first_segment), C.c_size_t(count), ct, tag,
                                                       coms, C.byref(out), C.byref(total), lens))
-    blob = _take(out, total)
-    proofs, off = [], 0
-    for i in range(count):
-        proofs.append(blob[off:off + lens[i]])
-        off += lens[i]
-    return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], proofs
+    return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], _split(_take(out, total), lens, count)
 
 
 def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c):

@@ -6,26 +6,74 @@
 
 using zk::capi::guard; using zk::capi::give; using zk::capi::fill_info; using zk::capi::next_pow2;
 
+namespace {
+enum { ECB = zk::CIRCUIT_AES, CBC = zk::CIRCUIT_AES_CBC, CTR = zk::CIRCUIT_AES_CTR, GCM = zk::CIRCUIT_AES_GCM, ANY = zk::ProvingKey::ANY_AES_KIND };
+// a fresh key pair to the caller's handles
+void give_keys(std::unique_ptr<zk::ProvingKey> k, zkaes_pk **pk, zkaes_vk **vk) {
+    zkaes_vk *v = new zkaes_vk{k->vk()};
+    zkaes_pk *p = new zkaes_pk{std::move(k)};
+    if (pk) *pk = p; else delete p;
+    if (vk) *vk = v; else delete v;
+}
+unsigned key_flags(unsigned flags) {
+    if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
+    return (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u;
+}
+zk::SrsLiterals srs_literals(size_t nc, size_t nv, size_t nnz) { zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz; return srs; }
+int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128, size_t key_tag_blocks = 0,
+               unsigned digest_kind = 0, uint64_t digest_prefix = 0) {
+    return guard([&] {
+        const unsigned f = key_flags(flags);
+        if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("synthesize_keys: key_bits must be 128, 192 or 256");
+        if (key_tag_blocks > 2) throw std::invalid_argument("synthesize_keys: key_tag_blocks must be 0, 1 or 2");
+        if (digest_kind > 2) throw std::invalid_argument("synthesize_keys: digest_kind must be 0 (none), 1 (chain) or 2 (final)");
+        give_keys(zk::synthesize_keys(kind, len, srs_literals(nc, nv, nnz), f, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix), pk, vk);
+    });
+}
+// the unseeded multi-proof entry points draw a fresh seed from the OS per call and go on as their _seeded_at form.  The reference's fixed ark_std::test_rng() stream for
+// every proof (byte parity with the oracle; NOT zero-knowledge across proofs) is reachable only explicitly, through the *_seeded entry points with a NULL seed -- no
+// environment variable downgrades a caller
+template <class Seeded> int with_os_seed(Seeded &&seeded) {
+    uint8_t seed[32];
+    int rc = guard([&] { zk::os_random_seed(seed); });
+    return rc ? rc : seeded(seed);
+}
+// a witness to the caller: its length always, its bytes where there is a buffer
+void give_witness(const std::vector<uint8_t> &v, uint8_t *z, size_t z_cap, size_t *z_len) {
+    if (z_len) *z_len = v.size();
+    if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+}
+void give_proof(const zk::Proof &p, uint8_t **proof, size_t *proof_len) {
+    auto b = zk::serialize_proof(p);
+    *proof = give(b); *proof_len = b.size();
+}
+void pack_proofs(const std::vector<zk::Proof> &ps, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    std::vector<uint8_t> all;
+    for (size_t i = 0; i < ps.size(); i++) {
+        auto b = zk::serialize_proof(ps[i]);
+        if (proof_lens) proof_lens[i] = b.size();
+        all.insert(all.end(), b.begin(), b.end());
+    }
+    *proofs = give(all); *proofs_len = all.size();
+}
+// the packed arrays of a batch call hold n of what the key takes each
+void require_packed(const zk::Circuit &c, size_t n, size_t messages_len, size_t secret_keys_len) {
+    if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
+    if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
+}
+// a GCM record's header as the prover takes it: iv, then aad
+std::vector<uint8_t> gcm_header(const uint8_t iv[12], const uint8_t *aad, size_t aad_len) {
+    std::vector<uint8_t> h(iv, iv + 12);
+    if (aad_len) h.insert(h.end(), aad, aad + aad_len);
+    return h;
+}
+}  // namespace
+
 extern "C" {
 
 void zkaes_pk_free(zkaes_pk *pk) { delete pk; }
 int zkaes_device_count(void) { return zk::gpu::device_count(); }
 
-static int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128, size_t key_tag_blocks = 0,
-                      unsigned digest_kind = 0, uint64_t digest_prefix = 0) {
-    return guard([&] {
-        if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
-        if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("synthesize_keys: key_bits must be 128, 192 or 256");
-        if (key_tag_blocks > 2) throw std::invalid_argument("synthesize_keys: key_tag_blocks must be 0, 1 or 2");
-        if (digest_kind > 2) throw std::invalid_argument("synthesize_keys: digest_kind must be 0 (none), 1 (chain) or 2 (final)");
-        zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
-        auto k = zk::synthesize_keys(kind, len, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix);
-        zkaes_vk *v = new zkaes_vk{k->vk()};
-        zkaes_pk *p = new zkaes_pk{std::move(k)};
-        if (pk) *pk = p; else delete p;
-        if (vk) *vk = v; else delete v;
-    });
-}
 int zkaes_synthesize_keys_ex2(int kind, size_t len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return synthesize(kind, len, 0, nc, nv, nnz, flags, pk, vk);
 }
@@ -38,15 +86,22 @@ int zkaes_synthesize_keys_ks(int kind, unsigned key_bits, size_t len, size_t aad
 int zkaes_synthesize_keys_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks);
 }
+int zkaes_synthesize_keys_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz,
+                             unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+}
+int zkaes_synthesize_keys_ex(int kind, size_t len, size_t nc, size_t nv, size_t nnz, zkaes_pk **pk, zkaes_vk **vk) {
+    return zkaes_synthesize_keys_ex2(kind, len, nc, nv, nnz, 0u, pk, vk);
+}
+int zkaes_synthesize_keys(size_t len, zkaes_pk **pk, zkaes_vk **vk) {
+    zk::SrsLiterals d;
+    return zkaes_synthesize_keys_ex(ZKAES_CIRCUIT_AES, len, d.num_constraints, d.num_variables, d.num_non_zero, pk, vk);
+}
 int zkaes_pk_key_tag_blocks(const zkaes_pk *pk, size_t *n) {
     return guard([&] {
         if (!pk || !n) throw std::invalid_argument("null argument");
         *n = pk->pk->key_tag_blocks();
     });
-}
-int zkaes_synthesize_keys_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz,
-                             unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
-    return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks, digest_kind, digest_prefix);
 }
 int zkaes_pk_digest_info(const zkaes_pk *pk, uint64_t out[4]) {
     return guard([&] {
@@ -61,42 +116,38 @@ int zkaes_pk_key_bytes(const zkaes_pk *pk, size_t *n) {
         *n = pk->pk->key_bytes();
     });
 }
-int zkaes_synthesize_keys_ex(int kind, size_t len, size_t nc, size_t nv, size_t nnz, zkaes_pk **pk, zkaes_vk **vk) {
-    return zkaes_synthesize_keys_ex2(kind, len, nc, nv, nnz, 0u, pk, vk);
+int zkaes_pk_mode(const zkaes_pk *pk, int *circuit_kind, size_t *header_bytes) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        if (circuit_kind) *circuit_kind = pk->pk->circuit().kind;
+        if (header_bytes) *header_bytes = zk::mode_header_bytes(pk->pk->circuit());
+    });
 }
-int zkaes_synthesize_keys(size_t len, zkaes_pk **pk, zkaes_vk **vk) {
-    zk::SrsLiterals d;
-    return zkaes_synthesize_keys_ex(ZKAES_CIRCUIT_AES, len, d.num_constraints, d.num_variables, d.num_non_zero, pk, vk);
-}
+// ---- The prover's entry points: argument checks, then the one call of the shape -- witness, lone, batch, chunked -- with the mode the entry is for (marlin.hpp).  The
+// host-only calls of every mode (the host ciphers, zkaes_ctr_counter_add, zkaes_sha256_*, the verifiers) are in capi_host.cpp
+// -- AES-ECB
 int zkaes_encrypt_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const zkaes_pk *pk, const uint8_t *seed, uint8_t **proof, size_t *proof_len) {
     return guard([&] {
         if (!pk || !proof || !proof_len) throw std::invalid_argument("null argument");
-        zk::Proof p = pk->pk->prove_aes(msg, len, key, seed);
-        auto b = zk::serialize_proof(p);
-        *proof = give(b); *proof_len = b.size();
+        give_proof(pk->pk->prove_lone(ECB, msg, len, key, nullptr, 0, seed), proof, proof_len);
     });
 }
 int zkaes_encrypt(const uint8_t *msg, size_t len, const uint8_t key[16], const zkaes_pk *pk, uint8_t **proof, size_t *proof_len) {
     return zkaes_encrypt_seeded(msg, len, key, pk, nullptr, proof, proof_len);
 }
-static void pack_proofs(const std::vector<zk::Proof> &ps, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
-    std::vector<uint8_t> all;
-    for (size_t i = 0; i < ps.size(); i++) {
-        auto b = zk::serialize_proof(ps[i]);
-        if (proof_lens) proof_lens[i] = b.size();
-        all.insert(all.end(), b.begin(), b.end());
-    }
-    *proofs = give(all); *proofs_len = all.size();
+int zkaes_aes_witness(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], uint8_t *z, size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        give_witness(pk->pk->witness(ECB, false, msg, len, key, nullptr), z, z_cap, z_len);
+    });
 }
-// the unseeded multi-proof entry points draw a fresh seed from the OS per call.  The reference's fixed ark_std::test_rng() stream for every proof (byte parity with the
-// oracle; NOT zero-knowledge across proofs) is reachable only explicitly, through the *_seeded entry points with a NULL seed -- no environment variable downgrades a caller.
 int zkaes_encrypt_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t key[16], const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs,
                                     size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
     return guard([&] {
         if (!pk || !proofs || !proofs_len || !key || (!msg && len)) throw std::invalid_argument("null argument");
         size_t chunk = pk->pk->circuit().n_blocks * 16;
         if (chunk == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
-        pack_proofs(pk->pk->prove_aes_chunked(msg, len, key, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
+        pack_proofs(pk->pk->prove_chunked(ECB, false, msg, len, key, nullptr, nullptr, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_encrypt_chunked_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const zkaes_pk *pk, const uint8_t *zk_seed32, uint8_t **proofs, size_t *proofs_len,
@@ -104,18 +155,14 @@ int zkaes_encrypt_chunked_seeded(const uint8_t *msg, size_t len, const uint8_t k
     return zkaes_encrypt_chunked_seeded_at(msg, len, key, pk, zk_seed32, 0, proofs, proofs_len, proof_lens, n_chunks);
 }
 int zkaes_encrypt_chunked(const uint8_t *msg, size_t len, const uint8_t key[16], const zkaes_pk *pk, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
-    uint8_t seed[32];
-    { int rc = guard([&] { zk::os_random_seed(seed); }); if (rc) return rc; }
-    return zkaes_encrypt_chunked_seeded_at(msg, len, key, pk, seed, 0, proofs, proofs_len, proof_lens, n_chunks);
+    return with_os_seed([&](const uint8_t *seed) { return zkaes_encrypt_chunked_seeded_at(msg, len, key, pk, seed, 0, proofs, proofs_len, proof_lens, n_chunks); });
 }
 int zkaes_encrypt_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const zkaes_pk *pk,
                                   const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
     return guard([&] {
         if (!pk || !proofs || !proofs_len || (n && (!messages || !secret_keys))) throw std::invalid_argument("null argument");
-        size_t chunk = pk->pk->circuit().n_blocks * 16;
-        if (messages_len != n * chunk) throw std::invalid_argument("messages must hold n x " + std::to_string(chunk) + " bytes (the key's plaintext length)");
-        if (secret_keys_len != n * pk->pk->key_bytes()) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(pk->pk->key_bytes()) + " bytes");
-        pack_proofs(pk->pk->prove_aes_batch(messages, secret_keys, n, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
+        require_packed(pk->pk->circuit(), n, messages_len, secret_keys_len);
+        pack_proofs(pk->pk->prove_batch(ECB, false, messages, secret_keys, nullptr, nullptr, n, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_encrypt_batch_seeded(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const zkaes_pk *pk,
@@ -123,21 +170,24 @@ int zkaes_encrypt_batch_seeded(size_t n, const uint8_t *messages, size_t message
     return zkaes_encrypt_batch_seeded_at(n, messages, messages_len, secret_keys, secret_keys_len, pk, zk_seed32, 0, proofs, proofs_len, proof_lens);
 }
 int zkaes_encrypt_batch(size_t n, const uint8_t *messages, const uint8_t *secret_keys, const zkaes_pk *pk, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
-    size_t chunk = pk ? pk->pk->circuit().n_blocks * 16 : 0;
-    uint8_t seed[32];
-    { int rc = guard([&] { zk::os_random_seed(seed); }); if (rc) return rc; }
-    return zkaes_encrypt_batch_seeded_at(n, messages, n * chunk, secret_keys, n * (pk ? pk->pk->key_bytes() : 16), pk, seed, 0, proofs, proofs_len, proof_lens);
+    const size_t chunk = pk ? pk->pk->circuit().n_blocks * 16 : 0, kb = pk ? pk->pk->key_bytes() : 16;      // (this form takes the caller's word for the packed lengths)
+    return with_os_seed([&](const uint8_t *seed) { return zkaes_encrypt_batch_seeded_at(n, messages, n * chunk, secret_keys, n * kb, pk, seed, 0, proofs, proofs_len, proof_lens); });
 }
-// ---- AES-128-CBC (include/zkaes.h): the prover side; the host-only calls (zkaes_cbc_ciphertext, the verifiers) are in capi_host.cpp
+// -- AES-CBC and AES-CTR: one public header of 16 bytes, the iv or the initial counter block
+static int encrypt_lone_16(int kind, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const zkaes_pk *pk, const uint8_t *seed, uint8_t *ciphertext_or_null, uint8_t **proof,
+                           size_t *proof_len) {
+    return guard([&] {
+        if (!pk || !proof || !proof_len || !msg || !key || !hdr) throw std::invalid_argument("null argument");
+        give_proof(pk->pk->prove_lone(kind, msg, len, key, hdr, 0, seed, ciphertext_or_null), proof, proof_len);
+    });
+}
 int zkaes_encrypt_cbc_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], const zkaes_pk *pk, const uint8_t *seed, uint8_t *ciphertext_or_null,
                              uint8_t **proof, size_t *proof_len) {
-    return guard([&] {
-        if (!pk || !proof || !proof_len || !msg || !key || !iv) throw std::invalid_argument("null argument");
-        std::vector<uint8_t> ct(len ? len : 1);
-        auto b = zk::serialize_proof(pk->pk->prove_aes_cbc(msg, len, key, iv, seed, ct.data()));
-        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-        *proof = give(b); *proof_len = b.size();
-    });
+    return encrypt_lone_16(CBC, msg, len, key, iv, pk, seed, ciphertext_or_null, proof, proof_len);
+}
+int zkaes_encrypt_ctr_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *seed, uint8_t *ciphertext_or_null,
+                             uint8_t **proof, size_t *proof_len) {
+    return encrypt_lone_16(CTR, msg, len, key, icb, pk, seed, ciphertext_or_null, proof, proof_len);
 }
 int zkaes_encrypt_cbc_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
                                         uint8_t *ciphertext_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
@@ -146,36 +196,12 @@ int zkaes_encrypt_cbc_chunked_seeded_at(const uint8_t *msg, size_t len, const ui
         if (pk->pk->circuit().kind != zk::CIRCUIT_AES_CBC) throw std::invalid_argument("proving key was not synthesized for the AES-CBC circuit");
         size_t chunk = pk->pk->circuit().n_blocks * 16;
         if (chunk == 0 || len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
-        std::vector<uint8_t> ct(len);
-        auto ps = pk->pk->prove_aes_cbc_chunked(msg, len, key, iv, pk->pk->contexts(), zk_seed32, first_proof_index, ct.data());
-        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-        pack_proofs(ps, proofs, proofs_len, proof_lens);
+        pack_proofs(pk->pk->prove_chunked(CBC, false, msg, len, key, iv, nullptr, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_encrypt_cbc_chunked(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], const zkaes_pk *pk, uint8_t *ciphertext_or_null, uint8_t **proofs,
                               size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
-    uint8_t seed[32];
-    { int rc = guard([&] { zk::os_random_seed(seed); }); if (rc) return rc; }
-    return zkaes_encrypt_cbc_chunked_seeded_at(msg, len, key, iv, pk, seed, 0, ciphertext_or_null, proofs, proofs_len, proof_lens, n_chunks);
-}
-int zkaes_aes_witness_cbc(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *z, size_t z_cap, size_t *z_len) {
-    return guard([&] {
-        if (!pk) throw std::invalid_argument("null argument");
-        auto v = pk->pk->aes_witness_cbc(msg, len, key, iv);
-        if (z_len) *z_len = v.size();
-        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
-    });
-}
-// ---- AES-128-CTR (include/zkaes.h): the prover side; zkaes_ctr_crypt, zkaes_ctr_counter_add and the verifiers are in capi_host.cpp
-int zkaes_encrypt_ctr_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *seed, uint8_t *ciphertext_or_null,
-                             uint8_t **proof, size_t *proof_len) {
-    return guard([&] {
-        if (!pk || !proof || !proof_len || !msg || !key || !icb) throw std::invalid_argument("null argument");
-        std::vector<uint8_t> ct(len ? len : 1);
-        auto b = zk::serialize_proof(pk->pk->prove_aes_ctr(msg, len, key, icb, seed, ct.data()));
-        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-        *proof = give(b); *proof_len = b.size();
-    });
+    return with_os_seed([&](const uint8_t *seed) { return zkaes_encrypt_cbc_chunked_seeded_at(msg, len, key, iv, pk, seed, 0, ciphertext_or_null, proofs, proofs_len, proof_lens, n_chunks); });
 }
 int zkaes_encrypt_ctr_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
                                         uint8_t *ciphertext_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
@@ -185,37 +211,31 @@ int zkaes_encrypt_ctr_chunked_seeded_at(const uint8_t *msg, size_t len, const ui
         size_t chunk = pk->pk->circuit().message_bytes;
         if (chunk == 0 || chunk % 16) throw std::invalid_argument("CTR: a chunked call needs a key for whole blocks");
         if (len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
-        std::vector<uint8_t> ct(len);
-        auto ps = pk->pk->prove_aes_ctr_chunked(msg, len, key, icb, pk->pk->contexts(), zk_seed32, first_proof_index, ct.data());
-        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-        pack_proofs(ps, proofs, proofs_len, proof_lens);
+        pack_proofs(pk->pk->prove_chunked(CTR, false, msg, len, key, icb, nullptr, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_encrypt_ctr_chunked(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], const zkaes_pk *pk, uint8_t *ciphertext_or_null, uint8_t **proofs,
                               size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
-    uint8_t seed[32];
-    { int rc = guard([&] { zk::os_random_seed(seed); }); if (rc) return rc; }
-    return zkaes_encrypt_ctr_chunked_seeded_at(msg, len, key, icb, pk, seed, 0, ciphertext_or_null, proofs, proofs_len, proof_lens, n_chunks);
+    return with_os_seed([&](const uint8_t *seed) { return zkaes_encrypt_ctr_chunked_seeded_at(msg, len, key, icb, pk, seed, 0, ciphertext_or_null, proofs, proofs_len, proof_lens, n_chunks); });
+}
+int zkaes_aes_witness_cbc(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[16], uint8_t *z, size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        give_witness(pk->pk->witness(CBC, false, msg, len, key, iv), z, z_cap, z_len);
+    });
 }
 int zkaes_aes_witness_ctr(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t icb[16], uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {
         if (!pk) throw std::invalid_argument("null argument");
-        auto v = pk->pk->aes_witness_ctr(msg, len, key, icb);
-        if (z_len) *z_len = v.size();
-        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+        give_witness(pk->pk->witness(CTR, false, msg, len, key, icb), z, z_cap, z_len);
     });
 }
-// ---- AES-128-GCM (include/zkaes.h): the prover side; zkaes_gcm_encrypt, zkaes_gcm_decrypt and the verifier are in capi_host.cpp
+// -- AES-GCM: the public header is iv, then aad
 int zkaes_encrypt_gcm_seeded(const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const zkaes_pk *pk, const uint8_t *seed,
                              uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t **proof, size_t *proof_len) {
     return guard([&] {
         if (!pk || !proof || !proof_len || !msg || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
-        std::vector<uint8_t> ct(len ? len : 1);
-        uint8_t tag[16];
-        auto b = zk::serialize_proof(pk->pk->prove_aes_gcm(msg, len, key, iv, aad, aad_len, seed, ct.data(), tag));
-        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-        if (tag_or_null) memcpy(tag_or_null, tag, 16);
-        *proof = give(b); *proof_len = b.size();
+        give_proof(pk->pk->prove_lone(GCM, msg, len, key, gcm_header(iv, aad, aad_len).data(), aad_len, seed, ciphertext_or_null, tag_or_null), proof, proof_len);
     });
 }
 int zkaes_encrypt_gcm_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
@@ -226,32 +246,24 @@ int zkaes_encrypt_gcm_batch_seeded_at(size_t n, const uint8_t *messages, size_t 
         const zk::Circuit &c = pk->pk->circuit();
         if (c.kind == zk::CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("this proving key is a GCM segment key: use the segment entry points (zkaes_encrypt_gcm_segments_seeded_at, zkaes_aes_witness_gcm_seg)");
         if (c.kind != zk::CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
-        if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
-        if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
+        require_packed(c, n, messages_len, secret_keys_len);
         if (headers_len != n * (12 + c.aad_bytes)) throw std::invalid_argument("headers must hold n x " + std::to_string(12 + c.aad_bytes) + " bytes (iv, then the key's aad length)");
-        pack_proofs(pk->pk->prove_aes_gcm_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null), proofs, proofs_len,
-                    proof_lens);
+        pack_proofs(pk->pk->prove_batch(GCM, false, messages, secret_keys, headers, nullptr, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null), proofs,
+                    proofs_len, proof_lens);
     });
 }
 int zkaes_aes_witness_gcm(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, uint8_t *z, size_t z_cap,
                           size_t *z_len) {
     return guard([&] {
-        if (!pk) throw std::invalid_argument("null argument");
-        auto v = pk->pk->aes_witness_gcm(msg, len, key, iv, aad, aad_len);
-        if (z_len) *z_len = v.size();
-        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+        if (!pk || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
+        give_witness(pk->pk->witness(GCM, false, msg, len, key, gcm_header(iv, aad, aad_len).data(), aad_len), z, z_cap, z_len);
     });
 }
-// ---- GCM segments (include/zkaes.h): the prover side; zkaes_gcm_boundaries, zkaes_gcm_commit, the circuit queries and the verifier are in capi_host.cpp
+// -- GCM segments
 int zkaes_synthesize_keys_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return guard([&] {
-        if (flags & ~(unsigned)ZKAES_KEY_NO_TABLES) throw std::invalid_argument("synthesize_keys: unknown flag bits");
-        zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz;
-        auto k = zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs, (flags & ZKAES_KEY_NO_TABLES) ? (unsigned)zk::KEY_NO_TABLES : 0u);
-        zkaes_vk *v = new zkaes_vk{k->vk()};
-        zkaes_pk *p = new zkaes_pk{std::move(k)};
-        if (pk) *pk = p; else delete p;
-        if (vk) *vk = v; else delete v;
+        const unsigned f = key_flags(flags);
+        give_keys(zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs_literals(nc, nv, nnz), f), pk, vk);
     });
 }
 int zkaes_pk_segment_info(const zkaes_pk *pk, uint64_t out[4]) {
@@ -264,9 +276,7 @@ int zkaes_pk_segment_info(const zkaes_pk *pk, uint64_t out[4]) {
 int zkaes_aes_witness_gcm_seg(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {
         if (!pk) throw std::invalid_argument("null argument");
-        auto v = pk->pk->aes_witness_gcm_segment(msg, len, key, header, header_len);
-        if (z_len) *z_len = v.size();
-        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+        give_witness(pk->pk->aes_witness_gcm_segment(msg, len, key, header, header_len), z, z_cap, z_len);
     });
 }
 int zkaes_encrypt_gcm_segment_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
@@ -276,8 +286,7 @@ int zkaes_encrypt_gcm_segment_batch_seeded_at(size_t n, const uint8_t *messages,
         const zk::Circuit &c = pk->pk->circuit();
         if (c.kind != zk::CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("the key is not a GCM segment key: the segment entry points take keys of zkaes_synthesize_keys_gcm_seg (lone records go through zkaes_encrypt_gcm_batch_seeded_at)");
         const size_t hb = zk::mode_header_bytes(c);
-        if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
-        if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
+        require_packed(c, n, messages_len, secret_keys_len);
         if (headers_len != n * hb) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad)");
         pack_proofs(pk->pk->prove_gcm_segment_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
     });
@@ -291,20 +300,11 @@ int zkaes_encrypt_gcm_segments_seeded_at(const uint8_t *msg, size_t len, const u
                                            zk_seed32, ciphertext_or_null, tag_or_null, commitments_or_null), proofs, proofs_len, proof_lens);
     });
 }
-int zkaes_pk_mode(const zkaes_pk *pk, int *circuit_kind, size_t *header_bytes) {
-    return guard([&] {
-        if (!pk) throw std::invalid_argument("null argument");
-        if (circuit_kind) *circuit_kind = pk->pk->circuit().kind;
-        if (header_bytes) *header_bytes = zk::mode_header_bytes(pk->pk->circuit());
-    });
-}
-// ---- plaintext digests (include/zkaes.h): the prover side; zkaes_sha256_chain, zkaes_sha256_finish and the verifiers are in capi_host.cpp
+// -- plaintext digests: every mode through one set of entries; hdr = the mode's public header, NULL for ECB
 int zkaes_aes_witness_pd(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {
         if (!pk) throw std::invalid_argument("null argument");
-        auto v = pk->pk->aes_witness_digest(msg, len, key, hdr, h_in);
-        if (z_len) *z_len = v.size();
-        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+        give_witness(pk->pk->witness(ANY, true, msg, len, key, hdr, zk::ProvingKey::KEY_AAD, h_in), z, z_cap, z_len);
     });
 }
 int zkaes_encrypt_digest_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
@@ -315,11 +315,10 @@ int zkaes_encrypt_digest_batch_seeded_at(size_t n, const uint8_t *messages, size
         const zk::Circuit &c = pk->pk->circuit();
         if (!c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
         const size_t hb = zk::mode_header_bytes(c);
-        if (messages_len != n * c.message_bytes) throw std::invalid_argument("messages must hold n x " + std::to_string(c.message_bytes) + " bytes (the key's plaintext length)");
-        if (secret_keys_len != n * c.key_bytes) throw std::invalid_argument("secret_keys must hold n x " + std::to_string(c.key_bytes) + " bytes");
+        require_packed(c, n, messages_len, secret_keys_len);
         if (headers_len != n * hb || (n && hb && !headers)) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (the mode's public header)");
-        pack_proofs(pk->pk->prove_digest_batch(messages, secret_keys, hb ? headers : nullptr, h_ins, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null,
-                                               h_outs_or_null), proofs, proofs_len, proof_lens);
+        pack_proofs(pk->pk->prove_batch(ANY, true, messages, secret_keys, hb ? headers : nullptr, h_ins, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null, tags_or_null,
+                                        h_outs_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_encrypt_digest_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, const zkaes_pk *pk, const uint8_t *zk_seed32,
@@ -329,18 +328,18 @@ int zkaes_encrypt_digest_chunked_seeded_at(const uint8_t *msg, size_t len, const
         if (!pk || !proofs || !proofs_len || !key || !msg) throw std::invalid_argument("null argument");
         const size_t chunk = pk->pk->circuit().message_bytes;
         if (chunk == 0 || len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
-        pack_proofs(pk->pk->prove_digest_chunked(msg, len, key, hdr, h_in, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null, states_or_null), proofs, proofs_len, proof_lens);
+        pack_proofs(pk->pk->prove_chunked(ANY, true, msg, len, key, hdr, h_in, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null, states_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *seed, uint8_t **proof, size_t *proof_len) {
     return guard([&] {
         if (!pk || !proof || !proof_len) throw std::invalid_argument("null argument");
-        auto b = zk::serialize_proof(pk->pk->prove_ops(x, y, seed));
-        *proof = give(b); *proof_len = b.size();
+        give_proof(pk->pk->prove_ops(x, y, seed), proof, proof_len);
     });
 }
 int zkaes_pk_info(const zkaes_pk *pk, uint64_t out[12]) {
     return guard([&] {
+        if (!pk || !out) throw std::invalid_argument("null argument");
         fill_info(pk->pk->circuit(), out);
         out[9] = pk->pk->vk().num_non_zero; out[10] = next_pow2(pk->pk->vk().num_constraints); out[11] = next_pow2(pk->pk->vk().num_non_zero);
     });
@@ -394,17 +393,16 @@ int zkaes_pk_msm_partial_dev(const zkaes_pk *pk, const uint8_t *scalars, size_t 
     });
 }
 int zkaes_pk_debug_fetch(const zkaes_pk *pk, const char *name, uint8_t **out, size_t *len) {
-    return guard([&] { auto b = pk->pk->debug_fetch(name); *out = give(b); *len = b.size(); });
-}
-int zkaes_aes_witness(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t key[16], uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {
-        auto v = pk->pk->aes_witness(msg, len, key);
-        if (z_len) *z_len = v.size();
-        if (z) { if (z_cap < v.size()) throw std::invalid_argument("z buffer too small"); memcpy(z, v.data(), v.size()); }
+        if (!pk || !name || !out || !len) throw std::invalid_argument("null argument");
+        auto b = pk->pk->debug_fetch(name); *out = give(b); *len = b.size();
     });
 }
 int zkaes_pk_timings(const zkaes_pk *pk, double out[6]) {
-    return guard([&] { const auto &t = pk->pk->last_timings(); out[0] = t.witness_ms; out[1] = t.round1_ms; out[2] = t.round2_ms; out[3] = t.round3_ms; out[4] = t.open_ms; out[5] = t.total_ms; });
+    return guard([&] {
+        if (!pk || !out) throw std::invalid_argument("null argument");
+        const auto &t = pk->pk->last_timings(); out[0] = t.witness_ms; out[1] = t.round1_ms; out[2] = t.round2_ms; out[3] = t.round3_ms; out[4] = t.open_ms; out[5] = t.total_ms;
+    });
 }
 // ---- batch verification on the device (include/zkaes.h); the host back end, zkaes_verify_batch_timings and zkaes_chunk_public_inputs are in capi_host.cpp
 int zkaes_verify_batch_gpu(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each,

@@ -2,6 +2,7 @@
 // No device, no HIP header: this file, marlin_codec.cpp and circuit.cpp are also built with -fsanitize=address,undefined,fuzzer (tests/fuzz_host.cpp).
 #include "capi_common.hpp"
 #include <algorithm>
+#include "statement.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -9,25 +10,39 @@ zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 
     return zk::compile_circuit(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
 }
 void require_key_len(size_t key_len) { if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes"); }
-// the CBC (and CTR) instance without the leading One: 128 bits of the IV (the initial counter block), then the ciphertext bits, each byte LSB first
-std::vector<zk::Fr> cbc_public_input(const uint8_t iv[16], const uint8_t *ct, size_t ct_len) {
-    std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 16), c = zk::ciphertext_to_public_input(ct, ct_len);
-    pub.insert(pub.end(), c.begin(), c.end());
-    return pub;
-}
-// Chunk j's public input without the leading One, as every chunked verifier and zkaes_chunk_public_inputs derive it: the mode header (ECB none; CBC the chaining value
-// entering the chunk -- iv, or the 16 ciphertext bytes ahead of the slice; CTR icb + j x the chunk's blocks), the chunk's ciphertext bits, the key tag's when there is
-// one, and (states[j], states[j + 1]) when there are states
+// Chunk j's public input without the leading One, as every chunked verifier and zkaes_chunk_public_inputs derive it: the header entering the chunk (statement.hpp, the
+// prover's own rule), the chunk's ciphertext bits, the key tag's when there is one, and (states[j], states[j + 1]) when there are states
 std::vector<zk::Fr> chunk_public_input(int circuit_kind, size_t j, size_t chunk, const uint8_t *iv_or_icb, const uint8_t *ct, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states) {
-    std::vector<zk::Fr> pub;
-    auto append = [&](const uint8_t *bytes, size_t n) { std::vector<zk::Fr> b = zk::ciphertext_to_public_input(bytes, n); pub.insert(pub.end(), b.begin(), b.end()); };
-    uint8_t counter[16];
-    if (circuit_kind == zk::CIRCUIT_AES_CBC) append(j ? ct + chunk * j - 16 : iv_or_icb, 16);
-    if (circuit_kind == zk::CIRCUIT_AES_CTR) { zk::ctr_counter_add(iv_or_icb, (uint64_t)j * (chunk / 16), counter); append(counter, 16); }
-    append(ct + chunk * j, chunk);
-    if (key_tag) append(key_tag, key_tag_len);
-    if (states) append(states + 32 * j, 64);                                               // states[j] is H_in, states[j + 1] H_out
-    return pub;
+    uint8_t hdr[16];
+    const size_t hb = zk::chunk_mode_header(circuit_kind, j, chunk, iv_or_icb, ct, hdr);
+    return zk::public_input_of({{hdr, hb}, {ct + chunk * j, chunk}, {key_tag, key_tag_len}, {states ? states + 32 * j : nullptr, 64}});      // states[j] is H_in, states[j + 1] H_out
+}
+// a GCM record's public input without the leading One: iv, aad, ciphertext, tag, then the key tag and (h_in, h_out) of the keys that carry them (null otherwise)
+std::vector<zk::Fr> gcm_public_input(const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *key_tag, size_t key_tag_len,
+                                     const uint8_t *h_in, const uint8_t *h_out) {
+    return zk::public_input_of({{iv, 12}, {aad, aad_len}, {ct, ct_len}, {tag, 16}, {key_tag, key_tag_len}, {h_in, 32}, {h_out, 32}});
+}
+// n proofs packed one behind the other, each checked by accept(j, proof): a proof whose bytes do not parse is a rejected proof, not an error of the call
+template <class Accept> void verify_each(const uint8_t *proofs, const size_t *proof_lens, size_t n, int *accepted_each, size_t *n_accepted, Accept &&accept) {
+    size_t off = 0, ok = 0;
+    for (size_t j = 0; j < n; j++) {
+        int acc = 0;
+        try {
+            zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
+            acc = accept(j, p) ? 1 : 0;
+        } catch (const std::runtime_error &) { acc = 0; }
+        if (accepted_each) accepted_each[j] = acc;
+        ok += (size_t)acc;
+        off += proof_lens[j];
+    }
+    if (n_accepted) *n_accepted = ok;
+}
+// the chunk-proofs of one ECB, CBC or CTR job of n_chunks slices of `chunk` bytes, chunk j against chunk_public_input(j)
+void verify_chunks(const zk::VerifyingKey &vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, size_t chunk, const uint8_t *iv_or_icb, const uint8_t *ct,
+                   const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, int *accepted_each, size_t *n_accepted) {
+    verify_each(proofs, proof_lens, n_chunks, accepted_each, n_accepted, [&](size_t j, const zk::Proof &p) {
+        return zk::verify(vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states), p);
+    });
 }
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
 // image of the struct: reading it back from untrusted bytes put arbitrary limbs into field elements and an arbitrary byte into a bool, and skipped the curve / subgroup
@@ -90,7 +105,7 @@ int zkaes_verify_encryption_cbc(const zkaes_vk *vk, const uint8_t *proof, size_t
         *accepted = 0;
         if (ct_len == 0 || ct_len % 16) throw std::invalid_argument("CBC: the ciphertext must be a non-zero multiple of 16 bytes");
         zk::Proof p = zk::deserialize_proof(proof, proof_len);
-        *accepted = zk::verify(vk->vk, cbc_public_input(iv, ct, ct_len), p) ? 1 : 0;
+        *accepted = zk::verify(vk->vk, zk::public_input_of({{iv, 16}, {ct, ct_len}}), p) ? 1 : 0;
     });
 }
 // Chunk j is checked against (IV_j, its slice of the ciphertext), IV_0 = iv and IV_j = the 16 ciphertext bytes ahead of the slice: all of it public, so the
@@ -101,19 +116,7 @@ int zkaes_verify_cbc_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
         if (!vk || !proofs || !proof_lens || !iv || !ct) throw std::invalid_argument("null argument");
         if (n_accepted) *n_accepted = 0;
         if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks || (ct_len / n_chunks) % 16) throw std::invalid_argument("CBC: the ciphertext must be n_chunks x a non-zero multiple of 16 bytes");
-        const size_t chunk = ct_len / n_chunks;
-        size_t off = 0, ok = 0;
-        for (size_t j = 0; j < n_chunks; j++) {
-            int acc = 0;
-            try {
-                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                acc = zk::verify(vk->vk, chunk_public_input(zk::CIRCUIT_AES_CBC, j, chunk, iv, ct, nullptr, 0, nullptr), p) ? 1 : 0;
-            } catch (const std::runtime_error &) { acc = 0; }
-            if (accepted_each) accepted_each[j] = acc;
-            ok += (size_t)acc;
-            off += proof_lens[j];
-        }
-        if (n_accepted) *n_accepted = ok;
+        verify_chunks(vk->vk, zk::CIRCUIT_AES_CBC, proofs, proof_lens, n_chunks, ct_len / n_chunks, iv, ct, nullptr, 0, nullptr, accepted_each, n_accepted);
     });
 }
 // ---- AES-128-CTR.  The public input has the shape of CBC's: 128 bits of the initial counter block, then the ciphertext bits.
@@ -154,7 +157,7 @@ int zkaes_verify_encryption_ctr(const zkaes_vk *vk, const uint8_t *proof, size_t
         *accepted = 0;
         require_ctr_length(vk->vk, ct_len);
         zk::Proof p = zk::deserialize_proof(proof, proof_len);
-        *accepted = zk::verify(vk->vk, cbc_public_input(icb, ct, ct_len), p) ? 1 : 0;
+        *accepted = zk::verify(vk->vk, zk::public_input_of({{icb, 16}, {ct, ct_len}}), p) ? 1 : 0;
     });
 }
 // Chunk j is checked against (icb + j nb, its slice of the ciphertext), nb = the chunk's blocks: the counter comes from (icb, j) alone, so any chunk can be checked
@@ -167,18 +170,7 @@ int zkaes_verify_ctr_chunked(const zkaes_vk *vk, const uint8_t *proofs, const si
         if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks || (ct_len / n_chunks) % 16) throw std::invalid_argument("CTR: the ciphertext must be n_chunks x a non-zero multiple of 16 bytes");
         const size_t chunk = ct_len / n_chunks;
         require_ctr_length(vk->vk, chunk);
-        size_t off = 0, ok = 0;
-        for (size_t j = 0; j < n_chunks; j++) {
-            int acc = 0;
-            try {
-                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                acc = zk::verify(vk->vk, chunk_public_input(zk::CIRCUIT_AES_CTR, j, chunk, icb, ct, nullptr, 0, nullptr), p) ? 1 : 0;
-            } catch (const std::runtime_error &) { acc = 0; }
-            if (accepted_each) accepted_each[j] = acc;
-            ok += (size_t)acc;
-            off += proof_lens[j];
-        }
-        if (n_accepted) *n_accepted = ok;
+        verify_chunks(vk->vk, zk::CIRCUIT_AES_CTR, proofs, proof_lens, n_chunks, chunk, icb, ct, nullptr, 0, nullptr, accepted_each, n_accepted);
     });
 }
 // ---- AES-128-GCM.  Public input: 96 iv bits, the aad bits, the ciphertext bits, 128 tag bits.
@@ -229,13 +221,7 @@ int zkaes_verify_encryption_gcm(const zkaes_vk *vk, const uint8_t *proof, size_t
         *accepted = 0;
         require_gcm_lengths(vk->vk, aad_len, ct_len);
         zk::Proof p = zk::deserialize_proof(proof, proof_len);
-        std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(iv, 12);
-        for (auto part : {std::make_pair(aad, aad_len), std::make_pair(ct, ct_len), std::make_pair(tag, (size_t)16)}) {
-            if (!part.second) continue;
-            std::vector<zk::Fr> bits = zk::ciphertext_to_public_input(part.first, part.second);
-            pub.insert(pub.end(), bits.begin(), bits.end());
-        }
-        *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
+        *accepted = zk::verify(vk->vk, gcm_public_input(iv, aad, aad_len, ct, ct_len, tag, nullptr, 0, nullptr, nullptr), p) ? 1 : 0;
     });
 }
 // ---- GCM segments (include/zkaes.h): Y at the boundaries and a commitment on the host, and the verifier of a record's n segment-proofs
@@ -285,30 +271,16 @@ int zkaes_verify_gcm_segments(const zkaes_vk *head, const zkaes_vk *mid_or_null,
         exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, "tail");
         uint8_t lenblk[16];
         for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); }
-        size_t off = 0, ok = 0;
-        for (size_t s = 0; s < n; s++) {
-            int acc = 0;
-            try {
-                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[s]);
-                uint8_t hd[16];
-                memcpy(hd, iv, 12);
-                const uint32_t ctr0 = (uint32_t)(2 + s * c);
-                for (int i = 0; i < 4; i++) hd[12 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
-                std::vector<zk::Fr> pub = zk::ciphertext_to_public_input(hd, 16);
-                auto put = [&](const uint8_t *d, size_t len) { if (!len) return; std::vector<zk::Fr> bits = zk::ciphertext_to_public_input(d, len); pub.insert(pub.end(), bits.begin(), bits.end()); };
-                const bool first = s == 0, last = s + 1 == n;
-                if (first) put(aad, aad_len);
-                put(ct + 16 * c * s, last ? lt : 16 * c);
-                if (last) { put(lenblk, 16); put(tag, 16); }
-                if (!first) put(commitments + 32 * (s - 1), 32);
-                if (!last) put(commitments + 32 * s, 32);
-                acc = zk::verify(first ? head->vk : last ? tail->vk : mid_or_null->vk, pub, p) ? 1 : 0;
-            } catch (const std::runtime_error &) { acc = 0; }
-            if (accepted_each) accepted_each[s] = acc;
-            ok += (size_t)acc;
-            off += proof_lens[s];
-        }
-        if (n_accepted) *n_accepted = ok;
+        verify_each(proofs, proof_lens, n, accepted_each, n_accepted, [&](size_t s, const zk::Proof &p) {
+            uint8_t hd[16];
+            memcpy(hd, iv, 12);
+            const uint32_t ctr0 = (uint32_t)(2 + s * c);
+            for (int i = 0; i < 4; i++) hd[12 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
+            const bool first = s == 0, last = s + 1 == n;
+            std::vector<zk::Fr> pub = zk::public_input_of({{hd, 16}, {first ? aad : nullptr, aad_len}, {ct + 16 * c * s, last ? lt : 16 * c}, {last ? lenblk : nullptr, 16}, {last ? tag : nullptr, 16},
+                                                           {first ? nullptr : commitments + 32 * (s - 1), 32}, {last ? nullptr : commitments + 32 * s, 32}});
+            return zk::verify(first ? head->vk : last ? tail->vk : mid_or_null->vk, pub, p);
+        });
     });
 }
 // ---- key tags (include/zkaes.h): the tag on the host, and the verifiers that check every proof of a job against ONE tag
@@ -328,9 +300,21 @@ bool fits_key(const zk::VerifyingKey &vk, size_t n_bits, const char *what) {
     if (exact && vk.num_public_inputs != n_bits) throw std::invalid_argument(std::string(what) + ": the ciphertext and key-tag lengths are not the ones this key was synthesized for");
     return next_pow2(n_bits + 1) == vk.num_instance;
 }
-void append_bits(std::vector<zk::Fr> &pub, const uint8_t *bytes, size_t n) {
-    std::vector<zk::Fr> b = zk::ciphertext_to_public_input(bytes, n);
-    pub.insert(pub.end(), b.begin(), b.end());
+void require_opt_key_tag(const uint8_t *key_tag, size_t key_tag_len) {
+    if (key_tag ? (key_tag_len != 16 && key_tag_len != 32) : key_tag_len != 0) throw std::invalid_argument("key_tag_len must be 16 or 32 with a key tag, 0 with NULL");
+}
+// The shape of a chunked ECB, CBC or CTR job as zkaes_verify_chunked_kt, zkaes_verify_digest_chunked and zkaes_chunk_public_inputs take it -> the slice's byte length.
+// `entry` opens every message; gcm_entry names where GCM records go instead (null: not said); a key tag is optional unless tag_required
+size_t require_slices(const std::string &entry, const char *gcm_entry, int circuit_kind, const uint8_t *iv_or_icb, size_t n_chunks, size_t ct_len, const uint8_t *key_tag, size_t key_tag_len,
+                      bool tag_required) {
+    const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
+    if (!ecb && !cbc && !ctr) throw std::invalid_argument(entry + ": circuit_kind must be ECB, CBC or CTR" + (gcm_entry ? std::string(" (GCM records go through ") + gcm_entry + ")" : std::string()));
+    if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument(entry + ": an iv or initial counter block for CBC and CTR, NULL for ECB");
+    if (tag_required) require_key_tag_len(key_tag_len); else require_opt_key_tag(key_tag, key_tag_len);
+    if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument(entry + ": the ciphertext must be n_chunks equal, non-empty slices");
+    const size_t chunk = ct_len / n_chunks;
+    if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument(entry + ": every slice must be whole blocks (a lone CTR proof takes any length)");
+    return chunk;
 }
 }  // namespace
 // Chunk j's public input is what zkaes_verify_encryption (ECB), zkaes_verify_cbc_chunked or zkaes_verify_ctr_chunked derive for it, with the tag bits appended.  n_chunks = 1
@@ -341,26 +325,9 @@ int zkaes_verify_chunked_kt(const zkaes_vk *vk, int circuit_kind, const uint8_t 
         if (n_accepted) *n_accepted = 0;
         if (accepted_each) for (size_t j = 0; j < n_chunks; j++) accepted_each[j] = 0;
         if (!vk || !proofs || !proof_lens || !ct || !key_tag) throw std::invalid_argument("null argument");
-        const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
-        if (!ecb && !cbc && !ctr) throw std::invalid_argument("verify_chunked_kt: circuit_kind must be ECB, CBC or CTR (GCM records go through zkaes_verify_encryption_gcm_kt)");
-        if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument("verify_chunked_kt: an iv or initial counter block for CBC and CTR, NULL for ECB");
-        require_key_tag_len(key_tag_len);
-        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument("verify_chunked_kt: the ciphertext must be n_chunks equal, non-empty slices");
-        const size_t chunk = ct_len / n_chunks;
-        if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument("verify_chunked_kt: every slice must be whole blocks (a lone CTR proof takes any length)");
-        if (!fits_key(vk->vk, (ecb ? 0 : 128) + 8 * chunk + 8 * key_tag_len, "verify_chunked_kt")) return;      // every chunk rejected
-        size_t off = 0, ok = 0;
-        for (size_t j = 0; j < n_chunks; j++) {
-            int acc = 0;
-            try {
-                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                acc = zk::verify(vk->vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, nullptr), p) ? 1 : 0;
-            } catch (const std::runtime_error &) { acc = 0; }
-            if (accepted_each) accepted_each[j] = acc;
-            ok += (size_t)acc;
-            off += proof_lens[j];
-        }
-        if (n_accepted) *n_accepted = ok;
+        const size_t chunk = require_slices("verify_chunked_kt", "zkaes_verify_encryption_gcm_kt", circuit_kind, iv_or_icb, n_chunks, ct_len, key_tag, key_tag_len, true);
+        if (!fits_key(vk->vk, (iv_or_icb ? 128 : 0) + 8 * chunk + 8 * key_tag_len, "verify_chunked_kt")) return;      // every chunk rejected
+        verify_chunks(vk->vk, circuit_kind, proofs, proof_lens, n_chunks, chunk, iv_or_icb, ct, key_tag, key_tag_len, nullptr, accepted_each, n_accepted);
     });
 }
 int zkaes_verify_encryption_gcm_kt(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len,
@@ -372,13 +339,7 @@ int zkaes_verify_encryption_gcm_kt(const zkaes_vk *vk, const uint8_t *proof, siz
         if (ct_len == 0) throw std::invalid_argument("GCM: the ciphertext must have at least one byte");
         if (!fits_key(vk->vk, 224 + 8 * (aad_len + ct_len) + 8 * key_tag_len, "GCM")) return;
         zk::Proof p = zk::deserialize_proof(proof, proof_len);
-        std::vector<zk::Fr> pub;
-        append_bits(pub, iv, 12);
-        if (aad_len) append_bits(pub, aad, aad_len);
-        append_bits(pub, ct, ct_len);
-        append_bits(pub, tag, 16);
-        append_bits(pub, key_tag, key_tag_len);
-        *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
+        *accepted = zk::verify(vk->vk, gcm_public_input(iv, aad, aad_len, ct, ct_len, tag, key_tag, key_tag_len, nullptr, nullptr), p) ? 1 : 0;
     });
 }
 // ---- plaintext digests (include/zkaes.h): SHA-256 on the host, and the verifiers that check every proof of a job against ONE array of states
@@ -394,37 +355,15 @@ int zkaes_sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_
         zk::sha256_finish(h_in, prefix_bytes, tail, tail_len, digest);
     });
 }
-namespace {
-void require_opt_key_tag(const uint8_t *key_tag, size_t key_tag_len) {
-    if (key_tag ? (key_tag_len != 16 && key_tag_len != 32) : key_tag_len != 0) throw std::invalid_argument("key_tag_len must be 16 or 32 with a key tag, 0 with NULL");
-}
-}  // namespace
 int zkaes_verify_digest_chunked(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len,
                                 const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, int *accepted_each, size_t *n_accepted) {
     return guard([&] {
         if (n_accepted) *n_accepted = 0;
         if (accepted_each) for (size_t j = 0; j < n_chunks; j++) accepted_each[j] = 0;
         if (!vk || !proofs || !proof_lens || !ct || !states) throw std::invalid_argument("null argument");
-        const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
-        if (!ecb && !cbc && !ctr) throw std::invalid_argument("verify_digest_chunked: circuit_kind must be ECB, CBC or CTR (GCM records go through zkaes_verify_encryption_gcm_digest)");
-        if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument("verify_digest_chunked: an iv or initial counter block for CBC and CTR, NULL for ECB");
-        require_opt_key_tag(key_tag, key_tag_len);
-        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument("verify_digest_chunked: the ciphertext must be n_chunks equal, non-empty slices");
-        const size_t chunk = ct_len / n_chunks;
-        if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument("verify_digest_chunked: every slice must be whole blocks (a lone CTR proof takes any length)");
-        if (!fits_key(vk->vk, (ecb ? 0 : 128) + 8 * chunk + 8 * key_tag_len + 512, "verify_digest_chunked")) return;      // every chunk rejected
-        size_t off = 0, ok = 0;
-        for (size_t j = 0; j < n_chunks; j++) {
-            int acc = 0;
-            try {
-                zk::Proof p = zk::deserialize_proof(proofs + off, proof_lens[j]);
-                acc = zk::verify(vk->vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states), p) ? 1 : 0;
-            } catch (const std::runtime_error &) { acc = 0; }
-            if (accepted_each) accepted_each[j] = acc;
-            ok += (size_t)acc;
-            off += proof_lens[j];
-        }
-        if (n_accepted) *n_accepted = ok;
+        const size_t chunk = require_slices("verify_digest_chunked", "zkaes_verify_encryption_gcm_digest", circuit_kind, iv_or_icb, n_chunks, ct_len, key_tag, key_tag_len, false);
+        if (!fits_key(vk->vk, (iv_or_icb ? 128 : 0) + 8 * chunk + 8 * key_tag_len + 512, "verify_digest_chunked")) return;      // every chunk rejected
+        verify_chunks(vk->vk, circuit_kind, proofs, proof_lens, n_chunks, chunk, iv_or_icb, ct, key_tag, key_tag_len, states, accepted_each, n_accepted);
     });
 }
 int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len,
@@ -438,15 +377,7 @@ int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof,
         zk::Proof p = zk::deserialize_proof(proof, proof_len);
         uint8_t iv0[32];
         zk::sha256_chain(nullptr, nullptr, 0, iv0);
-        std::vector<zk::Fr> pub;
-        append_bits(pub, iv, 12);
-        if (aad_len) append_bits(pub, aad, aad_len);
-        append_bits(pub, ct, ct_len);
-        append_bits(pub, tag, 16);
-        if (key_tag) append_bits(pub, key_tag, key_tag_len);
-        append_bits(pub, h_in ? h_in : iv0, 32);
-        append_bits(pub, h_out, 32);
-        *accepted = zk::verify(vk->vk, pub, p) ? 1 : 0;
+        *accepted = zk::verify(vk->vk, gcm_public_input(iv, aad, aad_len, ct, ct_len, tag, key_tag, key_tag_len, h_in ? h_in : iv0, h_out), p) ? 1 : 0;
     });
 }
 int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out, size_t *out_len) {
@@ -600,14 +531,8 @@ int zkaes_chunk_public_inputs(int circuit_kind, size_t n_chunks, const uint8_t *
                               uint8_t *out_bits, size_t *n_bits) {
     return guard([&] {
         if (!ct) throw std::invalid_argument("null argument");
-        const bool ecb = circuit_kind == zk::CIRCUIT_AES, cbc = circuit_kind == zk::CIRCUIT_AES_CBC, ctr = circuit_kind == zk::CIRCUIT_AES_CTR;
-        if (!ecb && !cbc && !ctr) throw std::invalid_argument("chunk_public_inputs: circuit_kind must be ECB, CBC or CTR");
-        if (ecb ? iv_or_icb != nullptr : iv_or_icb == nullptr) throw std::invalid_argument("chunk_public_inputs: an iv or initial counter block for CBC and CTR, NULL for ECB");
-        require_opt_key_tag(key_tag, key_tag_len);
-        if (n_chunks == 0 || ct_len == 0 || ct_len % n_chunks) throw std::invalid_argument("chunk_public_inputs: the ciphertext must be n_chunks equal, non-empty slices");
-        const size_t chunk = ct_len / n_chunks;
-        if (chunk % 16 && !(ctr && n_chunks == 1)) throw std::invalid_argument("chunk_public_inputs: every slice must be whole blocks (a lone CTR proof takes any length)");
-        const size_t row = (ecb ? 0 : 128) + 8 * chunk + 8 * key_tag_len + (states ? 512 : 0);
+        const size_t chunk = require_slices("chunk_public_inputs", nullptr, circuit_kind, iv_or_icb, n_chunks, ct_len, key_tag, key_tag_len, false);
+        const size_t row = (iv_or_icb ? 128 : 0) + 8 * chunk + 8 * key_tag_len + (states ? 512 : 0);
         if (n_bits) *n_bits = row;
         if (!out_bits) return;
         for (size_t j = 0; j < n_chunks; j++) {

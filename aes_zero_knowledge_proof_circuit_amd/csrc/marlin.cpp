@@ -1,5 +1,6 @@
 // csrc/marlin.cpp -- see marlin.hpp.  Host orchestration of the GPU prover + the host verifier.
 #include "marlin.hpp"
+#include "statement.hpp"
 #include "../../include/zkaes.h"   // ZKAES_DEFAULT_CONTEXTS
 #include <algorithm>
 #include <cstdio>
@@ -1006,24 +1007,30 @@ void ProvingKey::msm_powers_partial_device(const uint8_t *scalars, size_t n_loca
     if (n_local) gpu::h2d(cx.acc.p, scalars, n_local * sizeof(F), cx.stream);
     gpu::msm_table_sum_device<Bls377>(cx.msm_ws, impl->d_powers, impl->srs_stride, offset, impl->table_c, cx.acc.p, n_local, (XYZZ<Fq377> *)dev_out, cx.stream);
 }
-// every entry point from before the digest keys: such a key's proofs carry H_in and H_out, which these calls have no argument for
-static void refuse_digest_key(const Circuit &c) {
-    if (c.digest_kind) throw std::invalid_argument("this proving key carries a plaintext digest: use the _digest_ entry points (zkaes_encrypt_digest_batch_seeded_at, zkaes_encrypt_digest_chunked_seeded_at, zkaes_aes_witness_pd)");
-}
-Proof ProvingKey::prove_aes(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t *zk_seed) {
-    refuse_digest_key(impl->circuit);
-    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
-    if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
-    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed);
+// ---- The statement layer: every mode is "message, key, a public header of mode_header_bytes(c) bytes, H_in where the key has a digest" (statement.hpp), so there is one
+// body per shape of call -- witness, lone proof, batch, chunked job -- and none per mode.  DESIGN.md has the statements: "CBC", "CTR", "GCM", 9e (key tags), 9f (digests).
+// Is this the key the entry point is for?  kind: the mode the entry names, or ANY_AES_KIND (the _digest_ entries take every mode); digest: does the entry carry H_in and
+// H_out -- a digest key's proofs do, which the entries from before have no argument for; len: the message's; aad_len: the aad's, or KEY_AAD where the entry takes the
+// header whole
+static void require_key(const Circuit &c, int kind, bool digest, size_t len, size_t aad_len) {
+    if (digest && !c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
+    if (!digest && c.digest_kind) throw std::invalid_argument("this proving key carries a plaintext digest: use the _digest_ entry points (zkaes_encrypt_digest_batch_seeded_at, zkaes_encrypt_digest_chunked_seeded_at, zkaes_aes_witness_pd)");
+    if (kind != ProvingKey::ANY_AES_KIND) {
+        static const char *const names[] = {"AES", "", "", "AES-CBC", "AES-CTR", "AES-GCM"};
+        if (kind == CIRCUIT_AES_GCM && c.kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("this proving key is a GCM segment key: use the segment entry points (zkaes_encrypt_gcm_segments_seeded_at, zkaes_aes_witness_gcm_seg)");
+        if (c.kind != kind) throw std::invalid_argument(std::string("proving key was not synthesized for the ") + names[kind] + " circuit");
+        if (kind == CIRCUIT_AES && len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
+        if (kind == CIRCUIT_AES_CBC && (len == 0 || len % 16)) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
+    }
+    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
+    if (aad_len != ProvingKey::KEY_AAD && aad_len != c.aad_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.aad_bytes) + " bytes of aad");
 }
 // One proof with the library's op recorder open (gpu.hpp oplog_*): the transforms and MSMs it ACTUALLY launched, as JSON --
 //   {"h":..,"k":..,"x":..,"variables":..,"constraints":..,"nnz":[a,b,c],"blocks":..,"path":"throughput"|"lone","ntt":[[points, transforms in the launch],..],
 //    "msm":[[points,"buckets"|"second_bases"|"class_sum"],..]}
 // -- what bench.py computes the whole-proof roofline of SURVEY.md 8(d) from.  Process-global recorder: call with no other proof in flight.
 std::string ProvingKey::op_lists_json(const uint8_t *message, size_t len, const uint8_t key[16], bool throughput_path) {
-    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
+    require_key(impl->circuit, CIRCUIT_AES, impl->circuit.digest_kind != 0, len, KEY_AAD);      // (an ECB key with or without a digest)
     gpu::OpRecord rec;
     gpu::oplog_begin();
     uint8_t h_in[32];                                                              // an ECB key with a digest: its header is H_in alone; the recorded proof starts from the initial value
@@ -1053,53 +1060,6 @@ static std::vector<uint8_t> witness_of(ProvingKeyImpl *impl, const uint8_t *mess
     std::vector<uint8_t> z(c.num_variables());
     gpu::d2h(z.data(), cx.d_z, z.size(), s);
     return z;
-}
-std::vector<uint8_t> ProvingKey::aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]) {
-    refuse_digest_key(impl->circuit);
-    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
-    if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
-    return witness_of(impl, message, len, key, nullptr);
-}
-// ---- AES-128-CBC.  The statement, the public-input layout and why chunk-proofs stay independent: DESIGN.md "CBC".
-static void require_cbc_key(const Circuit &c, size_t len) {
-    if (c.kind != CIRCUIT_AES_CBC) throw std::invalid_argument("proving key was not synthesized for the AES-CBC circuit");
-    if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
-}
-std::vector<uint8_t> ProvingKey::aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]) {
-    refuse_digest_key(impl->circuit);
-    require_cbc_key(impl->circuit, len);
-    if (!message || !key || !iv) throw std::invalid_argument("null argument");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
-    return witness_of(impl, message, len, key, iv);
-}
-Proof ProvingKey::prove_aes_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null) {
-    refuse_digest_key(impl->circuit);
-    require_cbc_key(impl->circuit, len);
-    if (!message || !key || !iv) throw std::invalid_argument("null argument");
-    if (len != impl->circuit.n_blocks * 16) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(impl->circuit.n_blocks * 16) + " bytes");
-    if (ciphertext_or_null) aes128_cbc_encrypt_host(message, len, key, iv, ciphertext_or_null, impl->circuit.key_bytes);
-    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, iv);
-}
-// ---- AES-128-CTR.  The statement, the input layout, the incrementer and why chunk-proofs are seekable: DESIGN.md "CTR".
-static void require_ctr_key(const Circuit &c, const uint8_t *message, const uint8_t *key, const uint8_t *icb) {
-    if (c.kind != CIRCUIT_AES_CTR) throw std::invalid_argument("proving key was not synthesized for the AES-CTR circuit");
-    if (!message || !key || !icb) throw std::invalid_argument("null argument");
-}
-std::vector<uint8_t> ProvingKey::aes_witness_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16]) {
-    refuse_digest_key(impl->circuit);
-    const Circuit &c = impl->circuit;
-    require_ctr_key(c, message, key, icb);
-    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
-    return witness_of(impl, message, len, key, icb);
-}
-Proof ProvingKey::prove_aes_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null) {
-    refuse_digest_key(impl->circuit);
-    const Circuit &c = impl->circuit;
-    require_ctr_key(c, message, key, icb);
-    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
-    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null, c.key_bytes);
-    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, icb);
 }
 // zero-knowledge randomness of proof i of a chunked / batch call: the caller's seed is domain-separated per proof, Blake2s(seed || (offset + i) as u64 LE),
 // so no two proofs share rho, the KZG hiding coefficients or the mask polynomial -- across calls and ranks too when they pass job-global offsets.
@@ -1152,104 +1112,84 @@ static std::vector<Proof> prove_many(ProvingKeyImpl *impl, const uint8_t *messag
     for (auto &e : errors) if (!e.empty()) throw std::runtime_error(e);
     return proofs;
 }
-std::vector<Proof> ProvingKey::prove_aes_chunked(const uint8_t *message, size_t len, const uint8_t key[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
-    refuse_digest_key(impl->circuit);
-    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
-    size_t chunk = impl->circuit.n_blocks * 16;
-    if (chunk == 0 || len % chunk) throw std::invalid_argument("message length must be a multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
-    return prove_many(impl, message, key, 0, len / chunk, n_contexts, zk_seed, index_offset, nullptr);
+// what a trace kernel reads beside message and key, at out: the mode's header, then -- for a digest key -- H_in, null being SHA-256's initial value
+static void trace_header(const Circuit &c, const uint8_t *hdr, const uint8_t *h_in, uint8_t *out) {
+    const size_t hb = mode_header_bytes(c);
+    if (hb) memcpy(out, hdr, hb);
+    if (!c.digest_kind) return;
+    if (h_in) memcpy(out + hb, h_in, 32); else sha256_chain(nullptr, nullptr, 0, out + hb);        // (no blocks: the initial value)
 }
-std::vector<Proof> ProvingKey::prove_aes_batch(const uint8_t *messages, const uint8_t *keys, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
-    refuse_digest_key(impl->circuit);
-    if (impl->circuit.kind != CIRCUIT_AES) throw std::invalid_argument("proving key was not synthesized for the AES circuit");
-    if (impl->circuit.n_blocks == 0) throw std::invalid_argument("proving key has an empty plaintext");
-    return prove_many(impl, messages, keys, impl->circuit.key_bytes, n, n_contexts, zk_seed, index_offset, nullptr);
+static size_t trace_header_bytes(const Circuit &c) { return mode_header_bytes(c) + (c.digest_kind ? 32 : 0); }
+// the host's side of one statement into whichever buffers the caller gave: the ciphertext, GCM's tag
+static void host_side(const Circuit &c, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, uint8_t *ct_or_null, uint8_t *tag_or_null) {
+    if (!ct_or_null && !(tag_or_null && c.kind == CIRCUIT_AES_GCM)) return;
+    std::vector<uint8_t> unwanted(ct_or_null ? 0 : len);
+    host_encrypt(c, msg, len, key, hdr, ct_or_null ? ct_or_null : unwanted.data(), tag_or_null);
 }
-std::vector<Proof> ProvingKey::prove_aes_cbc_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
-                                                     uint8_t *ciphertext_or_null) {
-    refuse_digest_key(impl->circuit);
-    require_cbc_key(impl->circuit, len);
-    if (!message || !key || !iv) throw std::invalid_argument("null argument");
-    size_t chunk = impl->circuit.n_blocks * 16;
-    if (len % chunk) throw std::invalid_argument("message length must be a multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
-    // the whole chain once on the host (plain AES: milliseconds); every chaining value is public, so the chunk-proofs below are independent and run side by side
-    std::vector<uint8_t> ct(len);
-    aes128_cbc_encrypt_host(message, len, key, iv, ct.data(), impl->circuit.key_bytes);
-    size_t n_chunks = len / chunk;
-    std::vector<uint8_t> ivs(16 * n_chunks);
-    for (size_t j = 0; j < n_chunks; j++) memcpy(&ivs[16 * j], j ? &ct[chunk * j - 16] : iv, 16);
-    std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, ivs.data());
-    if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-    return proofs;
-}
-std::vector<Proof> ProvingKey::prove_aes_ctr_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
-                                                     uint8_t *ciphertext_or_null) {
-    refuse_digest_key(impl->circuit);
+std::vector<uint8_t> ProvingKey::witness(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *h_in) {
     const Circuit &c = impl->circuit;
-    require_ctr_key(c, message, key, icb);
-    size_t chunk = c.message_bytes;
+    require_key(c, kind, digest, len, aad_len);
+    if (!message || !key || (!hdr && mode_header_bytes(c))) throw std::invalid_argument("null argument");
+    std::vector<uint8_t> h(trace_header_bytes(c));
+    trace_header(c, hdr, h_in, h.data());
+    return witness_of(impl, message, len, key, h.empty() ? nullptr : h.data());
+}
+Proof ProvingKey::prove_lone(int kind, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *zk_seed, uint8_t *ciphertext_or_null,
+                             uint8_t *tag_or_null) {
+    const Circuit &c = impl->circuit;
+    require_key(c, kind, false, len, aad_len);
+    if (!message || !key || (!hdr && mode_header_bytes(c))) throw std::invalid_argument("null argument");
+    host_side(c, message, len, key, hdr, ciphertext_or_null, tag_or_null);
+    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, hdr);
+}
+std::vector<Proof> ProvingKey::prove_batch(int kind, bool digest, const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins, size_t n, size_t n_contexts,
+                                           const uint8_t *zk_seed, uint64_t index_offset, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null) {
+    const Circuit &c = impl->circuit;
+    require_key(c, kind, digest, c.message_bytes, KEY_AAD);                  // (the entry points check the packed lengths against the key)
+    if (c.message_bytes == 0) throw std::invalid_argument("proving key has an empty plaintext");
+    const size_t hb = mode_header_bytes(c), stride = trace_header_bytes(c), L = c.message_bytes;
+    if (n && (!messages || !keys || (!headers && hb))) throw std::invalid_argument("null argument");
+    std::vector<uint8_t> hs(stride * n);
+    for (size_t i = 0; i < n; i++) {
+        uint8_t *h = hs.data() + stride * i;
+        trace_header(c, hb ? headers + hb * i : nullptr, h_ins ? h_ins + 32 * i : nullptr, h);
+        host_side(c, messages + L * i, L, keys + c.key_bytes * i, h, ciphertexts_or_null ? ciphertexts_or_null + L * i : nullptr, tags_or_null ? tags_or_null + 16 * i : nullptr);
+        if (!digest || !h_outs_or_null) continue;                            // H_out by plain SHA-256: the device's own meets it in the constraints
+        if (c.digest_kind == DIGEST_CHAIN) sha256_chain(h + hb, messages + L * i, L, h_outs_or_null + 32 * i);
+        else sha256_finish(h + hb, c.digest_prefix, messages + L * i, L, h_outs_or_null + 32 * i);
+    }
+    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, stride ? hs.data() : nullptr, stride);
+}
+// The cipher (where it is asked for, or chains) and the hash run once on the host: every chaining value of either is public, so the chunk-proofs are independent and run
+// side by side.  Chunk j is proven under chunk_mode_header(j) -- any chunk from (hdr, j) alone for CTR -- and, over a chain key, under (states[j], states[j + 1])
+std::vector<Proof> ProvingKey::prove_chunked(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, size_t n_contexts,
+                                             const uint8_t *zk_seed, uint64_t index_offset, uint8_t *ciphertext_or_null, uint8_t *states_or_null) {
+    const Circuit &c = impl->circuit;
+    require_key(c, kind, digest, c.message_bytes, KEY_AAD);                  // (the job's length: below)
+    if (digest && c.digest_kind != DIGEST_CHAIN) throw std::invalid_argument("a chunked digest job takes a chain key (a final key proves one lone tail: zkaes_encrypt_digest_batch_seeded_at)");
+    if (c.kind != CIRCUIT_AES && c.kind != CIRCUIT_AES_CBC && c.kind != CIRCUIT_AES_CTR) throw std::invalid_argument("a chunked digest job takes an ECB, CBC or CTR key (GCM records go through the batch entry)");
+    const size_t hb = mode_header_bytes(c), stride = trace_header_bytes(c), chunk = c.message_bytes;
+    if ((!message && len) || !key || (hb ? !hdr : hdr != nullptr)) throw std::invalid_argument(digest ? "a chunked digest job takes an iv or initial counter block for CBC and CTR, NULL for ECB" : "null argument");
     if (chunk % 16) throw std::invalid_argument("CTR: a chunked call needs a key for whole blocks (this one was synthesized for " + std::to_string(chunk) + " bytes)");
-    if (len == 0 || len % chunk) throw std::invalid_argument("message length must be a non-zero multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
-    // chunk j starts at block j nb of this call, so its counter is icb + j nb: nothing runs ahead of the contexts, and any chunk can be proven from (icb, offset) alone
-    size_t n_chunks = len / chunk;
-    std::vector<uint8_t> icbs(16 * n_chunks);
-    for (size_t j = 0; j < n_chunks; j++) ctr_counter_add(icb, (uint64_t)j * c.n_blocks, &icbs[16 * j]);
-    std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, icbs.data());
-    if (ciphertext_or_null) aes128_ctr_crypt_host(message, len, key, icb, ciphertext_or_null, c.key_bytes);
+    const bool may_be_empty = c.kind == CIRCUIT_AES && !digest;              // (an empty ECB job is no proofs)
+    if (chunk == 0 || len % chunk || (len == 0 && !may_be_empty))
+        throw std::invalid_argument(std::string("message length must be a ") + (may_be_empty ? "" : "non-zero ") + "multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
+    const size_t n_chunks = len / chunk;
+    std::vector<uint8_t> ct, hs(stride * n_chunks), states(digest ? 32 * (n_chunks + 1) : 0);
+    if (ciphertext_or_null || c.kind == CIRCUIT_AES_CBC) { ct.resize(len); host_encrypt(c, message, len, key, hdr, ct.data(), nullptr); }
+    if (digest && h_in) memcpy(states.data(), h_in, 32);                     // states[0] = H_in
+    else if (digest) sha256_chain(nullptr, nullptr, 0, states.data());       // (no blocks: the initial value)
+    for (size_t j = 0; j < n_chunks; j++) {
+        uint8_t *h = hs.data() + stride * j;
+        chunk_mode_header(c.kind, j, chunk, hdr, ct.data(), h);
+        if (!digest) continue;
+        memcpy(h + hb, &states[32 * j], 32);
+        sha256_chain(&states[32 * j], message + chunk * j, chunk, &states[32 * (j + 1)]);
+    }
+    std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, stride ? hs.data() : nullptr, stride);
+    if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+    if (states_or_null) memcpy(states_or_null, states.data(), states.size());
     return proofs;
-}
-// ---- AES-128-GCM.  The statement, the input layout, the GHASH gadget and why a long message is a batch of records, not chunk-proofs: DESIGN.md "GCM".
-static void refuse_segment_key(const Circuit &c) {
-    if (c.kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("this proving key is a GCM segment key: use the segment entry points (zkaes_encrypt_gcm_segments_seeded_at, zkaes_aes_witness_gcm_seg)");
-}
-static void require_gcm_key(const Circuit &c, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *iv, const uint8_t *aad, size_t aad_len) {
-    refuse_segment_key(c);
-    if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
-    if (!message || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
-    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
-    if (aad_len != c.aad_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.aad_bytes) + " bytes of aad");
-}
-static std::vector<uint8_t> gcm_header(const uint8_t iv[12], const uint8_t *aad, size_t aad_len) {
-    std::vector<uint8_t> h(iv, iv + 12);
-    if (aad_len) h.insert(h.end(), aad, aad + aad_len);
-    return h;
-}
-std::vector<uint8_t> ProvingKey::aes_witness_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len) {
-    refuse_digest_key(impl->circuit);
-    require_gcm_key(impl->circuit, message, len, key, iv, aad, aad_len);
-    return witness_of(impl, message, len, key, gcm_header(iv, aad, aad_len).data());
-}
-Proof ProvingKey::prove_aes_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *zk_seed,
-                                uint8_t *ciphertext_or_null, uint8_t *tag_or_null) {
-    refuse_digest_key(impl->circuit);
-    require_gcm_key(impl->circuit, message, len, key, iv, aad, aad_len);
-    if (ciphertext_or_null || tag_or_null) {
-        std::vector<uint8_t> ct(len);
-        uint8_t tag[16];
-        aes128_gcm_encrypt_host(message, len, key, iv, aad, aad_len, ct.data(), tag, impl->circuit.key_bytes);
-        if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-        if (tag_or_null) memcpy(tag_or_null, tag, 16);
-    }
-    return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, gcm_header(iv, aad, aad_len).data());
-}
-std::vector<Proof> ProvingKey::prove_aes_gcm_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
-                                                   uint8_t *ciphertexts_or_null, uint8_t *tags_or_null) {
-    refuse_digest_key(impl->circuit);
-    const Circuit &c = impl->circuit;
-    refuse_segment_key(c);
-    if (c.kind != CIRCUIT_AES_GCM) throw std::invalid_argument("proving key was not synthesized for the AES-GCM circuit");
-    if (n && (!messages || !keys || !headers)) throw std::invalid_argument("null argument");
-    const size_t hs = 12 + c.aad_bytes;
-    if (ciphertexts_or_null || tags_or_null) {
-        std::vector<uint8_t> ct(c.message_bytes);
-        uint8_t tag[16];
-        for (size_t i = 0; i < n; i++) {
-            aes128_gcm_encrypt_host(messages + i * c.message_bytes, c.message_bytes, keys + c.key_bytes * i, headers + hs * i, headers + hs * i + 12, c.aad_bytes, ct.data(), tag, c.key_bytes);
-            if (ciphertexts_or_null) memcpy(ciphertexts_or_null + i * c.message_bytes, ct.data(), c.message_bytes);
-            if (tags_or_null) memcpy(tags_or_null + 16 * i, tag, 16);
-        }
-    }
-    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, hs);
 }
 // ---- GCM segments.  A segment proof's header is TRS_HDR_BYTES(A) bytes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad
 static const Circuit &require_segment_key(const ProvingKey *pk, int role, const char *name) {
@@ -1332,85 +1272,6 @@ std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null,
         for (size_t s = m0; s < m1; s++) proofs[s - first_segment] = mids[s - m0];
     }
     if (count && last == n) lone(tail, n - 1, 0);
-    return proofs;
-}
-// ---- plaintext digests.  A proof's header is the mode's own bytes, then the 32 bytes of H_in
-static void require_digest_key(const Circuit &c) {
-    if (!c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
-}
-// the host's side of one proof: ciphertext (and GCM tag) by the key's mode, H_out by plain SHA-256
-static void digest_host_side(const Circuit &c, const uint8_t *msg, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *ct_or_null, uint8_t *tag_or_null, uint8_t *h_out_or_null) {
-    const size_t L = c.message_bytes;
-    if (ct_or_null || tag_or_null) {
-        std::vector<uint8_t> ct(L);
-        uint8_t tag[16];
-        if (c.kind == CIRCUIT_AES) aes_ecb_encrypt_host(msg, L, key, c.key_bytes, ct.data());
-        else if (c.kind == CIRCUIT_AES_CBC) aes128_cbc_encrypt_host(msg, L, key, hdr, ct.data(), c.key_bytes);
-        else if (c.kind == CIRCUIT_AES_CTR) aes128_ctr_crypt_host(msg, L, key, hdr, ct.data(), c.key_bytes);
-        else aes128_gcm_encrypt_host(msg, L, key, hdr, hdr + 12, c.aad_bytes, ct.data(), tag, c.key_bytes);
-        if (ct_or_null) memcpy(ct_or_null, ct.data(), L);
-        if (tag_or_null && c.kind == CIRCUIT_AES_GCM) memcpy(tag_or_null, tag, 16);
-    }
-    if (h_out_or_null) {
-        if (c.digest_kind == DIGEST_CHAIN) sha256_chain(h_in, msg, L, h_out_or_null);
-        else sha256_finish(h_in, c.digest_prefix, msg, L, h_out_or_null);
-    }
-}
-static void digest_header(const Circuit &c, const uint8_t *hdr, const uint8_t *h_in, uint8_t *out) {
-    const size_t hb = mode_header_bytes(c);
-    if (hb) memcpy(out, hdr, hb);
-    if (h_in) memcpy(out + hb, h_in, 32); else sha256_chain(nullptr, nullptr, 0, out + hb);        // (no blocks: the initial value)
-}
-std::vector<uint8_t> ProvingKey::aes_witness_digest(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in) {
-    const Circuit &c = impl->circuit;
-    require_digest_key(c);
-    if (!message || !key || (!hdr && mode_header_bytes(c))) throw std::invalid_argument("null argument");
-    if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
-    std::vector<uint8_t> h(mode_header_bytes(c) + 32);
-    digest_header(c, hdr, h_in, h.data());
-    return witness_of(impl, message, len, key, h.data());
-}
-std::vector<Proof> ProvingKey::prove_digest_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins, size_t n, size_t n_contexts, const uint8_t *zk_seed,
-                                                  uint64_t index_offset, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null) {
-    const Circuit &c = impl->circuit;
-    require_digest_key(c);
-    const size_t hb = mode_header_bytes(c), L = c.message_bytes;
-    if (n && (!messages || !keys || (!headers && hb))) throw std::invalid_argument("null argument");
-    std::vector<uint8_t> hs((hb + 32) * n);
-    for (size_t i = 0; i < n; i++) {
-        uint8_t *h = &hs[(hb + 32) * i];
-        digest_header(c, headers ? headers + hb * i : nullptr, h_ins ? h_ins + 32 * i : nullptr, h);
-        digest_host_side(c, messages + L * i, keys + c.key_bytes * i, h, h + hb, ciphertexts_or_null ? ciphertexts_or_null + L * i : nullptr, tags_or_null ? tags_or_null + 16 * i : nullptr,
-                         h_outs_or_null ? h_outs_or_null + 32 * i : nullptr);
-    }
-    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, hs.data(), hb + 32);
-}
-std::vector<Proof> ProvingKey::prove_digest_chunked(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, size_t n_contexts, const uint8_t *zk_seed,
-                                                    uint64_t index_offset, uint8_t *ciphertext_or_null, uint8_t *states_or_null) {
-    const Circuit &c = impl->circuit;
-    require_digest_key(c);
-    if (c.digest_kind != DIGEST_CHAIN) throw std::invalid_argument("a chunked digest job takes a chain key (a final key proves one lone tail: zkaes_encrypt_digest_batch_seeded_at)");
-    if (c.kind != CIRCUIT_AES && c.kind != CIRCUIT_AES_CBC && c.kind != CIRCUIT_AES_CTR) throw std::invalid_argument("a chunked digest job takes an ECB, CBC or CTR key (GCM records go through the batch entry)");
-    const size_t hb = mode_header_bytes(c), chunk = c.message_bytes;
-    if (!message || !key || (hb ? !hdr : hdr != nullptr)) throw std::invalid_argument("a chunked digest job takes an iv or initial counter block for CBC and CTR, NULL for ECB");
-    if (len == 0 || len % chunk) throw std::invalid_argument("message length must be a non-zero multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
-    const size_t n_chunks = len / chunk;
-    // the cipher and the hash once on the host: every chaining value of either is public, so the chunk-proofs are independent and run side by side
-    std::vector<uint8_t> ct(len), hs((hb + 32) * n_chunks), states(32 * (n_chunks + 1));
-    if (c.kind == CIRCUIT_AES) aes_ecb_encrypt_host(message, len, key, c.key_bytes, ct.data());
-    else if (c.kind == CIRCUIT_AES_CBC) aes128_cbc_encrypt_host(message, len, key, hdr, ct.data(), c.key_bytes);
-    else aes128_ctr_crypt_host(message, len, key, hdr, ct.data(), c.key_bytes);
-    if (h_in) memcpy(states.data(), h_in, 32); else sha256_chain(nullptr, nullptr, 0, states.data());
-    for (size_t j = 0; j < n_chunks; j++) {
-        uint8_t *h = &hs[(hb + 32) * j];
-        if (c.kind == CIRCUIT_AES_CBC) memcpy(h, j ? &ct[chunk * j - 16] : hdr, 16);
-        if (c.kind == CIRCUIT_AES_CTR) ctr_counter_add(hdr, (uint64_t)j * c.n_blocks, h);
-        memcpy(h + hb, &states[32 * j], 32);
-        sha256_chain(&states[32 * j], message + chunk * j, chunk, &states[32 * (j + 1)]);
-    }
-    std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, hs.data(), hb + 32);
-    if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
-    if (states_or_null) memcpy(states_or_null, states.data(), states.size());
     return proofs;
 }
 Proof ProvingKey::prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed) {

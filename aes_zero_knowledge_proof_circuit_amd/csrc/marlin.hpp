@@ -68,68 +68,43 @@ class ProvingKey {
     // T = 0, 1 or 2: the key-tag blocks this key was synthesized with.  Every proving and witness call below takes a tagged key as it is: the last 128 T
     // public-input bits of each proof are AES_K(D_0) (, AES_K(D_1)) for that proof's key, filled from the trace like every other column
     size_t key_tag_blocks() const;
-    // ---- plaintext digests (circuit().digest_kind != 0).  Every proving and witness call of this class other than the three below refuses a digest
-    // key, and these three refuse a key without one (op_lists_json takes either: its proof of a digest key starts from the initial value).  A proof's public header is what its mode takes -- nothing (ECB), the 16 bytes of the iv (CBC) or the initial counter
-    // block (CTR), iv (12) then aad (GCM) -- and hdr_stride below is that length; a state (h_in, h_out) is 32 bytes, SHA-256's big-endian word serialisation, and a null
-    // h_in(s) is the initial value.  The device is handed message, key, header and H_in; H_out reaches the instance from the trace, and the host's own hash (sha256_chain /
-    // sha256_finish) meets it in the constraints.
-    // witness generation only: z = padded instance || witness
-    std::vector<uint8_t> aes_witness_digest(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr_or_null, const uint8_t *h_in_or_null);
-    // n independent proofs of any mode: messages n x L, keys n x key_bytes(), headers n x hdr_stride (null for ECB), h_ins n x 32 or null.  Receives on request the host's
-    // ciphertexts (n x L), GCM tags (n x 16, GCM keys only) and every proof's H_out (n x 32).  Seeds as prove_aes_chunked
-    std::vector<Proof> prove_digest_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins_or_null, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
-                                          uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr, uint8_t *h_outs_or_null = nullptr);
-    // chunk-proofs of one message under one key over a CHAIN key of ECB, CBC or CTR: the host runs plain SHA-256 (and, for CBC, the cipher chain) over the message once,
-    // chunk j is proven under its mode header (as prove_aes_cbc_chunked / prove_aes_ctr_chunked derive it from hdr, the header entering this call's first chunk) and under
-    // (states[j], states[j + 1]), states[0] = h_in.  states_or_null receives the n + 1 states (32 bytes each), ciphertext_or_null len bytes
-    std::vector<Proof> prove_digest_chunked(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr_or_null, const uint8_t *h_in_or_null, size_t n_contexts,
-                                            const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr, uint8_t *states_or_null = nullptr);
-    // encrypt(): message length must equal the length the key was synthesized for; zk_seed = 32-byte StdRng seed or nullptr for
-    // ark_std::test_rng()'s (what simpleworks::marlin::generate_rand() returns)
-    Proof prove_aes(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t *zk_seed);
-    // ceil(len / chunk) independent chunk-proofs of a long ECB message, `n_contexts` proofs in flight on separate HIP streams
-    // zk_seed: 32-byte seed, domain-separated per proof: proof i of the call draws from StdRng(Blake2s(seed || (index_offset + i) as u64 LE)), so callers that
-    // split one job over several calls / ranks pass the job-global index of their first proof and reuse one seed.  nullptr = the reference's fixed
-    // test_rng seed for every proof (byte-parity mode for tests; NOT zero-knowledge across proofs)
-    std::vector<Proof> prove_aes_chunked(const uint8_t *message, size_t len, const uint8_t key[16], size_t n_contexts, const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0);
-    // n independent (message_i, key_i) pairs, each message of the key's plaintext length; keys = n x key_bytes() bytes
-    std::vector<Proof> prove_aes_batch(const uint8_t *messages, const uint8_t *keys, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0);
+    // ---- The four shapes of call, for every AES mode (statement.hpp).  kind: the mode the caller's entry point is for -- CIRCUIT_AES (ECB), _CBC, _CTR, _GCM; a key of
+    // another kind is refused -- or ANY_AES_KIND.  hdr: the mode's public header, mode_header_bytes(circuit()) bytes: nothing (ECB, null), the iv (CBC), the initial
+    // counter block (CTR), iv (12 bytes) then aad (GCM); headers: n of them.  aad_len: what the caller's aad argument holds, checked against the key's, or KEY_AAD.  len:
+    // the key's message length (CTR and GCM: any value >= 1 the key was synthesized for).  digest: the caller is a _digest_ entry: the key must carry a
+    // digest, h_in(s) are 32-byte SHA-256 states (null: the initial value) and every proof states (H_in, H_out) behind its key tag; every other caller passes false and a
+    // digest key is refused, for its proofs carry two states the caller has no argument for.  A key with key-tag blocks is taken as it is.
+    // zk_seed of a lone proof: a 32-byte StdRng seed, or nullptr for ark_std::test_rng()'s (what simpleworks::marlin::generate_rand() returns).  zk_seed of a batch or a
+    // chunked job: proof i draws from StdRng(Blake2s(seed || (index_offset + i) as u64 LE)), so callers that split one job over several calls / ranks pass the job-global
+    // index of their first proof and reuse one seed; nullptr = the reference's fixed test_rng seed for EVERY proof (byte-parity mode for tests; NOT zero-knowledge across
+    // proofs).  n_contexts proofs are in flight on separate HIP streams.
+    // The host computes the ciphertext (GCM: and the tag, 16 bytes) by plain AES where a buffer is given, and H_out by plain SHA-256; the device is handed message, key,
+    // header and H_in only and derives the rest, so the two meet in the constraints
+    enum : int { ANY_AES_KIND = -1 };
+    static constexpr size_t KEY_AAD = ~(size_t)0;
+    // witness generation only (the trace kernels + witness_expand): z = padded instance || witness, one byte per variable
+    std::vector<uint8_t> witness(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len = KEY_AAD, const uint8_t *h_in_or_null = nullptr);
+    // one proof on context 0 (keys without a digest: a lone digest proof is a batch of one)
+    Proof prove_lone(int kind, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr,
+                     uint8_t *tag_or_null = nullptr);
+    // n independent statements: messages n x L, keys n x key_bytes(), headers n x the mode's header (null for ECB), h_ins n x 32 or null.  Receives on request the
+    // ciphertexts (n x L), GCM tags (n x 16, GCM keys only) and every proof's H_out (n x 32, digest keys only)
+    std::vector<Proof> prove_batch(int kind, bool digest, const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins_or_null, size_t n, size_t n_contexts,
+                                   const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr,
+                                   uint8_t *h_outs_or_null = nullptr);
+    // len / L chunk-proofs of one ECB, CBC or CTR message under one key.  hdr = the header entering this call's first chunk; chunk j is proven under chunk_mode_header(j):
+    // the public chaining value entering it (CBC), hdr + j x the key's blocks (CTR: a key for whole blocks; a job split over calls passes ctr_counter_add(icb, blocks
+    // before)).  Over a chain key it is also proven under (states[j], states[j + 1]), states[0] = h_in; states_or_null receives the n + 1 states, ciphertext_or_null len bytes
+    std::vector<Proof> prove_chunked(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in_or_null, size_t n_contexts,
+                                     const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr, uint8_t *states_or_null = nullptr);
     Proof prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed);
-    // ---- AES-128-CBC (keys of kind CIRCUIT_AES_CBC only; the calls above refuse such a key).  Public input: iv, ciphertext.
-    // one proof; ciphertext_or_null receives len bytes (the host's CBC encryption: the device recomputes the chain from iv alone, so the two check each other through the constraints)
-    Proof prove_aes_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr);
-    // chunk-proofs of a long CBC message: the host chain runs once over the whole message, chunk j is proven under the public chaining value entering it (iv for j = 0, else
-    // the last ciphertext block of chunk j - 1), all contexts side by side as in prove_aes_chunked; iv = the chaining value entering this call's first chunk.  Seeds as there.
-    std::vector<Proof> prove_aes_cbc_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16], size_t n_contexts, const uint8_t *zk_seed = nullptr,
-                                             uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr);
-    std::vector<uint8_t> aes_witness_cbc(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[16]);
-    // ---- AES-128-CTR (keys of kind CIRCUIT_AES_CTR only; every other call refuses such a key).  Public input: icb, ciphertext; len = the key's byte length, any value >= 1.
-    // one proof; ciphertext_or_null receives len bytes of the host's CTR encryption (the device derives every counter and keystream block from icb alone)
-    Proof prove_aes_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr);
-    // chunk-proofs of a long CTR message over a key for whole blocks: chunk j is proven under icb + j * (the key's blocks); icb = the counter of this call's first block
-    // (a job split over calls or ranks passes ctr_counter_add(icb, blocks before)).  Nothing serial runs ahead of the contexts.  Seeds as prove_aes_chunked.
-    std::vector<Proof> prove_aes_ctr_chunked(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16], size_t n_contexts, const uint8_t *zk_seed = nullptr,
-                                             uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr);
-    std::vector<uint8_t> aes_witness_ctr(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t icb[16]);
-    // ---- AES-128-GCM (keys of kind CIRCUIT_AES_GCM only; every other call refuses such a key).  Public input: iv (12 bytes), aad, ciphertext, tag; len and aad_len are
-    // the key's.  One proof per record: GHASH's chaining value is secret, so there are no chunk-proofs of one message (DESIGN.md "GCM").
-    // ciphertext_or_null (len bytes) and tag_or_null (16) receive the host's GCM encryption; the device is handed key, iv, aad and message only
-    Proof prove_aes_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *zk_seed,
-                        uint8_t *ciphertext_or_null = nullptr, uint8_t *tag_or_null = nullptr);
-    // n independent records over one key: messages = n x L bytes, keys = n x key_bytes(), headers = n x (12 + A) bytes (each record's iv, then its aad), all contexts side by side.
-    // Seeds as prove_aes_chunked.  ciphertexts_or_null = n x L bytes, tags_or_null = n x 16
-    std::vector<Proof> prove_aes_gcm_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
-                                           uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr);
-    std::vector<uint8_t> aes_witness_gcm(const uint8_t *message, size_t len, const uint8_t key[16], const uint8_t iv[12], const uint8_t *aad, size_t aad_len);
     // ---- GCM segments (keys of kind CIRCUIT_AES_GCM_SEG only, from synthesize_keys_gcm_segment; every call above refuses such a key, and the GCM calls name the segment
     // entries).  header = the segment proof's TRS_HDR_BYTES(A) bytes (trace_layout.h): iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad
     std::vector<uint8_t> aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len);
-    // n independent segment proofs of this key's role, each under its own header (n x TRS_HDR_BYTES(A)), all contexts side by side; seeds as prove_aes_chunked.  The
+    // n independent segment proofs of this key's role, each under its own header (n x TRS_HDR_BYTES(A)), all contexts side by side; seeds as prove_batch.  The
     // caller answers for what the headers say: prove_gcm_segments below derives them from one record
     std::vector<Proof> prove_gcm_segment_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
                                                uint64_t index_offset = 0);
-    // witness generation only (kernels aes_trace + witness_expand): z = padded instance || witness, one byte per variable
-    std::vector<uint8_t> aes_witness(const uint8_t *message, size_t len, const uint8_t key[16]);
     const ProverTimings &last_timings() const;
     // one proof with the op recorder open: JSON of the transforms and MSMs the library actually launched (marlin.cpp; SURVEY.md 8d op lists)
     std::string op_lists_json(const uint8_t *message, size_t len, const uint8_t key[16], bool throughput_path);
@@ -142,7 +117,7 @@ class ProvingKey {
     // window tables), device bytes, keys sharing it now, bytes of the Lagrange-basis points (shared per |H|, |X|)}; secs = {seconds this key's synthesis spent BUILDING
     // the SRS (0 when it was shared), seconds of the whole synthesis}
     void srs_info(uint64_t out[6], double secs[2]) const;
-    // proofs in flight per multi-proof call on this key (prove_aes_chunked / _batch with n_contexts = contexts()); 0 restores the process default
+    // proofs in flight per multi-proof call on this key (prove_chunked, prove_batch with n_contexts = contexts()); 0 restores the process default
     size_t contexts() const;
     void set_contexts(size_t n);
     // ark-serialize image of the arkworks IndexProverKey this key corresponds to, streamed to `path`; returns the bytes written (marlin.cpp has the layout).
@@ -168,7 +143,7 @@ std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, 
 // blocks; mid_or_null may be null when n = 2; the tail key is the one for the record's last len - 16 c (n - 1) bytes.  The host computes the record's ciphertext and tag,
 // Y at every boundary and the n - 1 commitments from salts_or_null (16 (n - 1) bytes; null = fresh OS randomness, allowed only when the call covers the whole record);
 // the device is handed key, iv, aad, message, ctr0, Y_in, the salts and the length block.  Segment s draws from StdRng(Blake2s(zk_seed || s)) whichever call proves it
-// (nullptr = the fixed test stream, as prove_aes_chunked); the middle segments run side by side over the mid key's contexts.  Receives on request the whole record's
+// (nullptr = the fixed test stream, as prove_batch); the middle segments run side by side over the mid key's contexts.  Receives on request the whole record's
 // ciphertext (len), tag (16) and commitments (32 (n - 1))
 std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad,
                                       size_t aad_len, const uint8_t *salts_or_null, size_t first_segment, size_t count, const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr,
