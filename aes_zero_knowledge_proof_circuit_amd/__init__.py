@@ -12,4 +12,5 @@ from .api import (ZkAesError, ProvingKey, VerifyingKey, synthesize_keys, encrypt
                   ecb_ciphertext, circuit_info, circuit_matrix,
                   key_tag, verify_chunked_tagged, verify_encryption_gcm_tagged,
                   sha256_chain, sha256_finish, verify_digest_chunked, verify_encryption_gcm_digest,
-                  verify_batch, chunk_public_inputs, verify_chunked_batch)
+                  verify_batch, chunk_public_inputs, verify_chunked_batch,
+                  reveal_mask, reveal_bytes, verify_reveal_chunked, verify_encryption_gcm_reveal)

@@ -188,9 +188,88 @@ class ProvingKey:
 
     def _message_bytes(self, header_bits):
         """the key's plaintext length: the public input is One, header_bits bits of iv / counter, 8 bits per ciphertext byte, then 128 bits per key-tag block and, for a
-        key with a digest, the 512 bits of H_in and H_out"""
+        key with a digest, the 512 bits of H_in and H_out, and for a reveal key 8 ceil(L / 8) mask bits and 8 L revealed bits"""
+        rv = self.reveal_info()
+        if rv["reveal"]:
+            return rv["message_bytes"]
         digest_bits = 512 if self.digest_info()["kind"] else 0
         return (self.info()["raw_instance"] - 1 - header_bits - 128 * self.key_tag_blocks() - digest_bits) // 8
+
+    def reveal_info(self):
+        """{"reveal": bool, "message_bytes": L, "mask_bytes": ceil(L / 8), "offset": the reveal region's offset in a trace} of this key (synthesize_keys(..., reveal=True);
+        DESIGN.md 9i); False and zeros for a key without reveal"""
+        out = (C.c_uint64 * 4)()
+        _check(lib().zkaes_pk_reveal_info(self._p, out))
+        return {"reveal": bool(out[0]), "message_bytes": int(out[1]), "mask_bytes": int(out[2]), "offset": int(out[3])}
+
+    def witness_reveal(self, message, secret_key, mask, header=None, h_in=None):
+        """z (padded instance + witness, one byte per variable) of a reveal key of any mode.  mask: bytes of ceil(L / 8), or byte indices / ranges (reveal_mask); header and
+        h_in as witness_digest (h_in is read by a key with a digest only).  The last 8 ceil(L / 8) + 8 L instance bits are the mask and the revealed bytes the device computed"""
+        self._need_key(secret_key)
+        if h_in is not None and len(h_in) != 32:
+            raise ZkAesError("h_in must be 32 bytes")
+        hdr = self._digest_header_bytes(header)
+        self._need_header(hdr)
+        m = reveal_mask(mask, len(message))
+        return self._witness(lib().zkaes_aes_witness_rv, bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in), m, C.c_size_t(len(m)))
+
+    def encrypt_reveal_batch(self, messages, secret_keys, masks, headers=None, h_ins=None, zk_seed=None, first_proof_index=0):
+        """n independent proofs over a reveal key of any mode -> (ciphertexts, gcm_tags, h_outs, revealed, proofs), five lists (gcm_tags holds None for every mode but GCM,
+        h_outs None for a key without a digest).  masks: one per message, bytes of ceil(L / 8) or byte indices / ranges (reveal_mask); headers, h_ins, zk_seed and
+        first_proof_index as encrypt_digest_batch"""
+        n = len(messages)
+        hb = self.header_bytes()
+        if headers is None:
+            headers = [b""] * n
+        if not (len(secret_keys) == len(headers) == len(masks) == n) or (h_ins is not None and len(h_ins) != n):
+            raise ZkAesError("one secret key, one header, one mask and one h_in per message")
+        kb = self.key_bytes()
+        if any(len(k) != kb for k in secret_keys) or any(len(h) != hb for h in headers):
+            raise ZkAesError("secret_key must be %d bytes and every header %d bytes" % (kb, hb))
+        if h_ins is not None and any(len(h) != 32 for h in h_ins):
+            raise ZkAesError("h_in must be 32 bytes")
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        mb, kbuf, hbuf = b"".join(bytes(m) for m in messages), b"".join(bytes(k) for k in secret_keys), b"".join(bytes(h) for h in headers)
+        mk = b"".join(reveal_mask(masks[i], len(messages[i])) for i in range(n))
+        cts, tags, outs, rev = (C.create_string_buffer(max(len(mb), 1)), C.create_string_buffer(max(16 * n, 1)), C.create_string_buffer(max(32 * n, 1)),
+                                C.create_string_buffer(max(len(mb), 1)))
+        lens = (C.c_size_t * max(n, 1))()
+        out, total = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_reveal_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kbuf, C.c_size_t(len(kbuf)), hbuf or None, C.c_size_t(len(hbuf)),
+                                                          None if h_ins is None else b"".join(bytes(h) for h in h_ins), mk, C.c_size_t(len(mk)), self._p, seed, C.c_uint64(first_proof_index),
+                                                          cts, tags, outs, rev, C.byref(out), C.byref(total), lens))
+        proofs = _split(_take(out, total), lens, n)
+        size = len(mb) // n if n else 0
+        gcm, dig = self.mode()[0] == CIRCUIT_AES_GCM, self.digest_info()["kind"] is not None
+        return ([cts.raw[size * i:size * (i + 1)] for i in range(n)], [tags.raw[16 * i:16 * i + 16] if gcm else None for i in range(n)],
+                [outs.raw[32 * i:32 * i + 32] if dig else None for i in range(n)], [rev.raw[size * i:size * (i + 1)] for i in range(n)], proofs)
+
+    def encrypt_reveal_chunked(self, message, secret_key, mask, header=None, h_in=None, zk_seed=None, first_proof_index=0):
+        """chunk-proofs of one ECB, CBC or CTR message over a reveal key under ONE mask over the whole message -> (ciphertext, states or None, revealed, proofs).  mask: bytes
+        of ceil(len(message) / 8) or byte indices / ranges (reveal_mask); chunk j is proven under its slice of it.  states: the n + 1 SHA-256 states of a chain key, None for
+        a key without a digest.  header, h_in, zk_seed and first_proof_index as encrypt_digest_chunked; a job split over calls passes each call its part of message and mask"""
+        self._need_key(secret_key)
+        if h_in is not None and len(h_in) != 32:
+            raise ZkAesError("h_in must be 32 bytes")
+        hdr = self._digest_header_bytes(header)
+        self._need_header(hdr)
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        chunk = self._message_bytes(8 * len(hdr))
+        if chunk == 0 or len(message) == 0 or len(message) % chunk:
+            raise ZkAesError("message length must be a non-zero multiple of the key's plaintext length (%d bytes)" % chunk)
+        n_chunks = len(message) // chunk
+        m = reveal_mask(mask, len(message))
+        dig = self.digest_info()["kind"] is not None
+        ct, states, rev = C.create_string_buffer(len(message)), C.create_string_buffer(32 * (n_chunks + 1)), C.create_string_buffer(len(message))
+        lens = (C.c_size_t * n_chunks)()
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_reveal_chunked_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), hdr or None, None if h_in is None else bytes(h_in), m, C.c_size_t(len(m)),
+                                                            self._p, seed, C.c_uint64(first_proof_index), ct, states if dig else None, rev, C.byref(out), C.byref(n), lens, C.c_size_t(n_chunks)))
+        return (ct.raw[:len(message)], [states.raw[32 * j:32 * j + 32] for j in range(n_chunks + 1)] if dig else None, rev.raw[:len(message)], _split(_take(out, n), lens, n_chunks))
 
     def _digest_header_bytes(self, header):
         """how long the mode's public header is for this digest key, learned from the header itself: None or b"" (ECB), 16 bytes (CBC, CTR), 12 + aad (GCM); the library
@@ -510,21 +589,47 @@ def _digest_args(digest, digest_prefix):
     return C.c_uint(_DIGEST_NAMES.index(digest)), C.c_uint64(int(digest_prefix))
 
 
-def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks=0, digest=None, digest_prefix=0):
+def reveal_mask(mask, length):
+    """a reveal mask over `length` message bytes as the C ABI takes it: ceil(length / 8) bytes, bit i = bit i % 8 of byte i / 8.  mask is those bytes already,
+    or an iterable of byte indices and / or range objects to reveal.  The one conversion every reveal call goes through"""
+    n = (int(length) + 7) // 8
+    if isinstance(mask, (bytes, bytearray, memoryview)):
+        if len(mask) != n:
+            raise ZkAesError("a mask over %d bytes has %d bytes" % (length, n))
+        return bytes(mask)
+    out = bytearray(n)
+    for item in mask:
+        for i in (item if isinstance(item, range) else (item,)):
+            if not 0 <= int(i) < length:
+                raise ZkAesError("reveal: byte index %d is outside the message (%d bytes)" % (i, length))
+            out[int(i) // 8] |= 1 << (int(i) % 8)
+    return bytes(out)
+
+
+def reveal_bytes(message, mask):
+    """revealed[i] = message[i] where mask bit i is set, else 0 (zkaes_reveal_bytes; no GPU): what a reveal proof states beside its mask.  mask as reveal_mask takes it"""
+    m = reveal_mask(mask, len(message))
+    out = C.create_string_buffer(max(len(message), 1))
+    _check(lib().zkaes_reveal_bytes(bytes(message), C.c_size_t(len(message)), m, C.c_size_t(len(m)), out))
+    return out.raw[:len(message)]
+
+
+def _synthesize(circuit, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks=0, digest=None, digest_prefix=0, reveal=False):
     pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib().zkaes_synthesize_keys_pd(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_size_t(plaintext_length),
+    _check(lib().zkaes_synthesize_keys_rv(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_uint(int(bool(reveal))), C.c_size_t(plaintext_length),
                                           C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
     return ProvingKey(pk.value), VerifyingKey(vk.value)
 
 
-def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
+def synthesize_keys(plaintext_length, circuit=CIRCUIT_AES, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0, reveal=False):
     """zk_aes::synthesize_keys (src/lib.rs:138-174) -> (ProvingKey, VerifyingKey).  flags: KEY_NO_TABLES.  key_bits: 128 (the reference's AES-128), 192 or 256 for
     the AES kinds; the proving key then takes secret keys of key_bits / 8 bytes (ProvingKey.key_bytes()).  key_tag_blocks: 0 (no key tag, the default), 1 or 2: every
     proof of the key also exposes key_tag(secret_key, key_tag_blocks) as public input, and is checked with verify_chunked_tagged.  digest: None (the
     default), "chain" or "final": every proof of the key also proves the SHA-256 compressions of its hidden message from a public H_in to a public H_out -- "chain" over
     the message's 64-byte blocks, "final" over the message with SHA-256's padding for digest_prefix + plaintext_length bytes -- is made through encrypt_digest_chunked /
-    encrypt_digest_batch and checked with verify_digest_chunked"""
-    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags, key_tag_blocks, digest, digest_prefix)
+    encrypt_digest_batch and checked with verify_digest_chunked.  reveal: False (the default) or True: every proof of the key also exposes a per-proof
+    mask and the message bytes it opens, is made through encrypt_reveal_batch / encrypt_reveal_chunked and checked with verify_reveal_chunked"""
+    return _synthesize(circuit, key_bits, plaintext_length, 0, srs, flags, key_tag_blocks, digest, digest_prefix, reveal)
 
 
 def sha256_chain(data, h_in=None):
@@ -567,6 +672,33 @@ def verify_digest_chunked(verifying_key, circuit, proofs, ciphertext, states, he
                                              b"".join(bytes(st) for st in states), each, C.byref(ok)))
     accepted = [bool(each[i]) for i in range(n)]
     return accepted, (sha256_finish(states[-1], len(ciphertext), b"") if n and all(accepted) and len(ciphertext) % 64 == 0 else None)
+
+
+def _verify_reveal_args(ciphertext, mask, revealed):
+    m = reveal_mask(mask, len(ciphertext))
+    if len(revealed) != len(ciphertext):
+        raise ZkAesError("revealed must be as long as the ciphertext")
+    return m, C.c_size_t(len(m)), bytes(revealed)
+
+
+def verify_reveal_chunked(verifying_key, circuit, proofs, ciphertext, mask, revealed, header=None, key_tag=None, states=None):
+    """the chunk-proofs of one ECB, CBC or CTR job over a reveal key against ONE mask and ONE array of revealed bytes over the whole job -> list of bools.  Chunk j is checked
+    as verify_digest_chunked checks it (key_tag None for a key without tag blocks, states None for a key without a digest), with its slice of mask and revealed behind.  One
+    proof is the lone form.  A mask bit at or beyond the length, or a non-zero revealed byte whose mask bit is 0, RAISES: it is not a rejection"""
+    n = len(proofs)
+    if states is not None and (len(states) != n + 1 or any(len(st) != 32 for st in states)):
+        raise ZkAesError("states must be one 32-byte state more than there are proofs")
+    if key_tag is not None and len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    if header is not None and len(header) != 16:
+        raise ZkAesError("iv / icb must be 16 bytes")
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each = (C.c_int * max(n, 1))()
+    ok = C.c_size_t()
+    _check(lib().zkaes_verify_reveal_chunked(verifying_key._p, int(circuit), b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), None if header is None else bytes(header), bytes(ciphertext),
+                                             C.c_size_t(len(ciphertext)), None if key_tag is None else bytes(key_tag), C.c_size_t(0 if key_tag is None else len(key_tag)),
+                                             None if states is None else b"".join(bytes(st) for st in states), *_verify_reveal_args(ciphertext, mask, revealed), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
 
 
 def key_tag(secret_key, blocks=2):
@@ -627,10 +759,11 @@ def verify_batch_timings():
     return d
 
 
-def chunk_public_inputs(circuit, ciphertext, header=None, key_tag=None, states=None, n_chunks=None):
+def chunk_public_inputs(circuit, ciphertext, header=None, key_tag=None, states=None, n_chunks=None, mask=None, revealed=None):
     """the public-input rows of a chunked ECB, CBC or CTR job, one bytes object of 0/1 per chunk: exactly what verify_encryption / verify_cbc_chunked / verify_ctr_chunked /
     verify_chunked_tagged / verify_digest_chunked derive for chunk j (zkaes_chunk_public_inputs; no GPU).  header: None for ECB, the IV for CBC, the initial counter block
-    for CTR; key_tag: 16 or 32 bytes or None; states: the n + 1 digest states or None; n_chunks: default len(states) - 1 with states, else 1"""
+    for CTR; key_tag: 16 or 32 bytes or None; states: the n + 1 digest states or None; n_chunks: default len(states) - 1 with states, else 1; mask and revealed: a reveal
+    key's ONE mask and revealed bytes over the whole job (zkaes_chunk_public_inputs_rv), or None for both"""
     if n_chunks is None:
         n_chunks = len(states) - 1 if states is not None else 1
     if states is not None and (len(states) != n_chunks + 1 or any(len(st) != 32 for st in states)):
@@ -640,15 +773,21 @@ def chunk_public_inputs(circuit, ciphertext, header=None, key_tag=None, states=N
     args = (int(circuit), C.c_size_t(n_chunks), None if header is None else bytes(header), bytes(ciphertext), C.c_size_t(len(ciphertext)), None if key_tag is None else bytes(key_tag),
             C.c_size_t(0 if key_tag is None else len(key_tag)), None if states is None else b"".join(bytes(st) for st in states))
     n_bits = C.c_size_t()
-    _check(lib().zkaes_chunk_public_inputs(*args, None, C.byref(n_bits)))
+    fn = lib().zkaes_chunk_public_inputs
+    if (mask is None) != (revealed is None):
+        raise ZkAesError("mask and revealed go together")
+    if mask is not None:
+        fn, args = lib().zkaes_chunk_public_inputs_rv, args + _verify_reveal_args(ciphertext, mask, revealed)
+    _check(fn(*args, None, C.byref(n_bits)))
     out = C.create_string_buffer(max(1, n_chunks * n_bits.value))
-    _check(lib().zkaes_chunk_public_inputs(*args, out, C.byref(n_bits)))
+    _check(fn(*args, out, C.byref(n_bits)))
     return [out.raw[j * n_bits.value:(j + 1) * n_bits.value] for j in range(n_chunks)]
 
 
-def verify_chunked_batch(verifying_key, circuit, proofs, ciphertext, header=None, key_tag=None, states=None, device=True):
-    """the chunk-proofs of one ECB, CBC or CTR job through the batch verifier -> list of bools: chunk_public_inputs for the rows, verify_batch for the proofs"""
-    return verify_batch(verifying_key, proofs, chunk_public_inputs(circuit, ciphertext, header, key_tag, states, n_chunks=len(proofs)), device=device)
+def verify_chunked_batch(verifying_key, circuit, proofs, ciphertext, header=None, key_tag=None, states=None, device=True, mask=None, revealed=None):
+    """the chunk-proofs of one ECB, CBC or CTR job through the batch verifier -> list of bools: chunk_public_inputs for the rows (with mask and revealed for a reveal key),
+    verify_batch for the proofs"""
+    return verify_batch(verifying_key, proofs, chunk_public_inputs(circuit, ciphertext, header, key_tag, states, n_chunks=len(proofs), mask=mask, revealed=revealed), device=device)
 
 
 def g1_decompress_batch(points48):
@@ -803,11 +942,12 @@ def _gcm_args(secret_key, iv, key_bytes=None):
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
 
 
-def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
+def synthesize_keys_gcm(plaintext_length, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0, reveal=False):
     """(ProvingKey, VerifyingKey) for AES-GCM records of exactly plaintext_length message bytes (>= 1) and aad_length aad bytes (>= 0).  flags: KEY_NO_TABLES;
     key_bits: 128, 192 or 256; key_tag_blocks: 0, 1 or 2 as synthesize_keys (records are then checked with verify_encryption_gcm_tagged); digest and digest_prefix as
-    synthesize_keys (records are then made with encrypt_digest_batch and checked with verify_encryption_gcm_digest)"""
-    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks, digest, digest_prefix)
+    synthesize_keys (records are then made with encrypt_digest_batch and checked with verify_encryption_gcm_digest); reveal as synthesize_keys (records are then made
+    with encrypt_reveal_batch and checked with verify_encryption_gcm_reveal)"""
+    return _synthesize(CIRCUIT_AES_GCM, key_bits, plaintext_length, aad_length, srs, flags, key_tag_blocks, digest, digest_prefix, reveal)
 
 
 def gcm_encrypt(message, secret_key, iv, aad=b""):
@@ -892,6 +1032,23 @@ SEG_HEAD, SEG_MID, SEG_TAIL = 0, 1, 2
 _SEG_ROLES = {"head": SEG_HEAD, "mid": SEG_MID, "tail": SEG_TAIL, SEG_HEAD: SEG_HEAD, SEG_MID: SEG_MID, SEG_TAIL: SEG_TAIL}
 # the largest c (data blocks per segment) at which all three roles stay inside the default SRS literal, per key size (tests/test_gcm_segments_host.py)
 GCM_SEGMENT_DEFAULT_C = {128: 4, 192: 3, 256: 2}
+
+
+def verify_encryption_gcm_reveal(verifying_key, proof, iv, aad, ciphertext, tag, mask, revealed, key_tag=None, h_out=None, h_in=None):
+    """verify_encryption_gcm_digest for a reveal key (h_out None for a key without a digest, key_tag None for one without tag blocks) with the record's mask and revealed
+    bytes behind.  A mask bit at or beyond the length, or a non-zero revealed byte whose mask bit is 0, raises"""
+    if len(iv) != 12 or len(tag) != 16:
+        raise ZkAesError("iv must be 12 bytes and tag 16 bytes")
+    if (h_out is not None and len(h_out) != 32) or (h_in is not None and len(h_in) != 32):
+        raise ZkAesError("h_in and h_out must be 32 bytes")
+    if key_tag is not None and len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    acc = C.c_int()
+    _check(lib().zkaes_verify_encryption_gcm_reveal(verifying_key._p, bytes(proof), C.c_size_t(len(proof)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext),
+                                                    C.c_size_t(len(ciphertext)), bytes(tag), None if key_tag is None else bytes(key_tag), C.c_size_t(0 if key_tag is None else len(key_tag)),
+                                                    None if h_in is None else bytes(h_in), None if h_out is None else bytes(h_out), *_verify_reveal_args(ciphertext, mask, revealed),
+                                                    C.byref(acc)))
+    return bool(acc.value)
 
 
 def _seg_role(role):
@@ -1036,23 +1193,23 @@ def proof_roundtrip(proof):
     return _take(out, n)
 
 
-def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
+def circuit_info(circuit, plaintext_length, aad_length=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0, reveal=False):
     """aad_length: GCM circuits only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2 and digest: None, "chain" or "final" (with digest_prefix) for the AES kinds"""
     out = (C.c_uint64 * 12)()
-    _check(lib().zkaes_circuit_info_pd(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_size_t(plaintext_length),
+    _check(lib().zkaes_circuit_info_rv(int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_uint(int(bool(reveal))), C.c_size_t(plaintext_length),
                                        C.c_size_t(aad_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0):
+def circuit_matrix(circuit, plaintext_length, which, aad_length=0, key_bits=128, key_tag_blocks=0, digest=None, digest_prefix=0, reveal=False):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    head = (int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
-    _check(lib().zkaes_circuit_matrix_pd(*head, C.byref(rows), C.byref(nnz), None, None, None))
+    head = (int(circuit), C.c_uint(int(key_bits)), _tag_blocks(key_tag_blocks), *_digest_args(digest, digest_prefix), C.c_uint(int(bool(reveal))), C.c_size_t(plaintext_length), C.c_size_t(aad_length), which)
+    _check(lib().zkaes_circuit_matrix_rv(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
     coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-    _check(lib().zkaes_circuit_matrix_pd(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
+    _check(lib().zkaes_circuit_matrix_rv(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 

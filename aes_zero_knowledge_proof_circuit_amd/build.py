@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libzkaes.so")
 OBJ = os.path.join(CSRC, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-HIP_SOURCES = ["runtime.hip", "kernels_ntt.hip", "kernels_msm.hip", "kernels_poly.hip", "kernels_witness.hip", "kernels_digest.hip", "kernels_verify.hip", "capi_kernels.hip", "capi_probe.hip"]
+HIP_SOURCES = ["runtime.hip", "kernels_ntt.hip", "kernels_msm.hip", "kernels_poly.hip", "kernels_witness.hip", "kernels_digest.hip", "kernels_reveal.hip", "kernels_verify.hip", "capi_kernels.hip", "capi_probe.hip"]
 CXX_SOURCES = ["circuit.cpp", "marlin.cpp", "marlin_codec.cpp", "capi.cpp", "capi_host.cpp"]
 HOST_ONLY_SOURCES = ["circuit.cpp", "marlin_codec.cpp", "capi_host.cpp"]      # no device code path: what the stand-alone sanitizer programs of tests/ link against
 HEADERS = ["ff.cuh", "ff28.cuh", "ff29.cuh", "ec.cuh", "ec28.cuh", "te28.cuh", "gpu.hpp", "hip_util.hpp", "consts32.h", "trace_layout.h", "circuit.hpp", "marlin.hpp", "marlin_host.hpp", "capi_common.hpp", "pairing.hpp", "transcript.hpp", "arith_probe.cuh", "fq_sqrt.cuh", "verify_batch.hpp", "statement.hpp",

@@ -21,13 +21,14 @@ unsigned key_flags(unsigned flags) {
 }
 zk::SrsLiterals srs_literals(size_t nc, size_t nv, size_t nnz) { zk::SrsLiterals srs; srs.num_constraints = nc; srs.num_variables = nv; srs.num_non_zero = nnz; return srs; }
 int synthesize(int kind, size_t len, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk, size_t key_bits = 128, size_t key_tag_blocks = 0,
-               unsigned digest_kind = 0, uint64_t digest_prefix = 0) {
+               unsigned digest_kind = 0, uint64_t digest_prefix = 0, unsigned reveal = 0) {
     return guard([&] {
         const unsigned f = key_flags(flags);
         if (key_bits != 128 && key_bits != 192 && key_bits != 256) throw std::invalid_argument("synthesize_keys: key_bits must be 128, 192 or 256");
         if (key_tag_blocks > 2) throw std::invalid_argument("synthesize_keys: key_tag_blocks must be 0, 1 or 2");
         if (digest_kind > 2) throw std::invalid_argument("synthesize_keys: digest_kind must be 0 (none), 1 (chain) or 2 (final)");
-        give_keys(zk::synthesize_keys(kind, len, srs_literals(nc, nv, nnz), f, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix), pk, vk);
+        if (reveal > 1) throw std::invalid_argument("synthesize_keys: reveal must be 0 or 1");
+        give_keys(zk::synthesize_keys(kind, len, srs_literals(nc, nv, nnz), f, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix, (int)reveal), pk, vk);
     });
 }
 // the unseeded multi-proof entry points draw a fresh seed from the OS per call and go on as their _seeded_at form.  The reference's fixed ark_std::test_rng() stream for
@@ -90,6 +91,10 @@ int zkaes_synthesize_keys_pd(int kind, unsigned key_bits, unsigned key_tag_block
                              unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
     return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks, digest_kind, digest_prefix);
 }
+int zkaes_synthesize_keys_rv(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, unsigned reveal, size_t len, size_t aad_len, size_t nc, size_t nv,
+                             size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return synthesize(kind, len, aad_len, nc, nv, nnz, flags, pk, vk, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
+}
 int zkaes_synthesize_keys_ex(int kind, size_t len, size_t nc, size_t nv, size_t nnz, zkaes_pk **pk, zkaes_vk **vk) {
     return zkaes_synthesize_keys_ex2(kind, len, nc, nv, nnz, 0u, pk, vk);
 }
@@ -108,6 +113,13 @@ int zkaes_pk_digest_info(const zkaes_pk *pk, uint64_t out[4]) {
         if (!pk || !out) throw std::invalid_argument("null argument");
         const zk::Circuit &c = pk->pk->circuit();
         out[0] = (uint64_t)c.digest_kind; out[1] = c.digest_prefix; out[2] = c.digest_blocks; out[3] = c.digest_off;
+    });
+}
+int zkaes_pk_reveal_info(const zkaes_pk *pk, uint64_t out[4]) {
+    return guard([&] {
+        if (!pk || !out) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        out[0] = (uint64_t)c.reveal; out[1] = c.reveal ? c.message_bytes : 0; out[2] = zk::reveal_mask_bytes(c); out[3] = c.reveal_off;
     });
 }
 int zkaes_pk_key_bytes(const zkaes_pk *pk, size_t *n) {
@@ -313,7 +325,7 @@ int zkaes_encrypt_digest_batch_seeded_at(size_t n, const uint8_t *messages, size
     return guard([&] {
         if (!pk || !proofs || !proofs_len || (n && (!messages || !secret_keys))) throw std::invalid_argument("null argument");
         const zk::Circuit &c = pk->pk->circuit();
-        if (!c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
+        if (!c.digest_kind && !c.reveal) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");      // (a reveal key: prove_batch names its entries)
         const size_t hb = zk::mode_header_bytes(c);
         require_packed(c, n, messages_len, secret_keys_len);
         if (headers_len != n * hb || (n && hb && !headers)) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (the mode's public header)");
@@ -329,6 +341,48 @@ int zkaes_encrypt_digest_chunked_seeded_at(const uint8_t *msg, size_t len, const
         const size_t chunk = pk->pk->circuit().message_bytes;
         if (chunk == 0 || len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
         pack_proofs(pk->pk->prove_chunked(ANY, true, msg, len, key, hdr, h_in, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null, states_or_null), proofs, proofs_len, proof_lens);
+    });
+}
+// -- selective disclosure: every mode, every digest kind through one set of entries; hdr = the mode's public header, NULL for ECB; h_in(s) are read by a
+// key with a digest only
+int zkaes_aes_witness_rv(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, const uint8_t *mask, size_t mask_len, uint8_t *z,
+                         size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk || !mask) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (!c.reveal) throw std::invalid_argument("the _reveal_ entry points take a proving key synthesized with reveal = 1 (zkaes_synthesize_keys_rv)");
+        if (mask_len != zk::reveal_mask_bytes(c)) throw std::invalid_argument("the mask of this key has " + std::to_string(zk::reveal_mask_bytes(c)) + " bytes");
+        give_witness(pk->pk->witness(ANY, c.digest_kind != 0, msg, len, key, hdr, zk::ProvingKey::KEY_AAD, h_in, mask), z, z_cap, z_len);
+    });
+}
+int zkaes_encrypt_reveal_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                         const uint8_t *h_ins, const uint8_t *masks, size_t masks_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
+                                         uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null, uint8_t *revealed_or_null, uint8_t **proofs, size_t *proofs_len,
+                                         size_t *proof_lens) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || !masks || (n && (!messages || !secret_keys))) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (!c.reveal) throw std::invalid_argument("the _reveal_ entry points take a proving key synthesized with reveal = 1 (zkaes_synthesize_keys_rv)");
+        const size_t hb = zk::mode_header_bytes(c), mb = zk::reveal_mask_bytes(c);
+        require_packed(c, n, messages_len, secret_keys_len);
+        if (headers_len != n * hb || (n && hb && !headers)) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (the mode's public header)");
+        if (masks_len != n * mb) throw std::invalid_argument("masks must hold n x " + std::to_string(mb) + " bytes (one bit per message byte)");
+        pack_proofs(pk->pk->prove_batch(ANY, c.digest_kind != 0, messages, secret_keys, hb ? headers : nullptr, h_ins, n, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertexts_or_null,
+                                        tags_or_null, h_outs_or_null, masks, revealed_or_null), proofs, proofs_len, proof_lens);
+    });
+}
+int zkaes_encrypt_reveal_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, const uint8_t *mask, size_t mask_len, const zkaes_pk *pk,
+                                           const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t *ciphertext_or_null, uint8_t *states_or_null, uint8_t *revealed_or_null, uint8_t **proofs,
+                                           size_t *proofs_len, size_t *proof_lens, size_t n_chunks) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || !key || !msg || !mask) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (!c.reveal) throw std::invalid_argument("the _reveal_ entry points take a proving key synthesized with reveal = 1 (zkaes_synthesize_keys_rv)");
+        const size_t chunk = c.message_bytes;
+        if (chunk == 0 || len == 0 || len % chunk || len / chunk != n_chunks) throw std::invalid_argument("message length must be n_chunks * the key's plaintext length");
+        if (mask_len != (len + 7) / 8) throw std::invalid_argument("ONE mask over the whole job: " + std::to_string((len + 7) / 8) + " bytes for this message");
+        pack_proofs(pk->pk->prove_chunked(ANY, c.digest_kind != 0, msg, len, key, hdr, h_in, pk->pk->contexts(), zk_seed32, first_proof_index, ciphertext_or_null, states_or_null, mask,
+                                          revealed_or_null), proofs, proofs_len, proof_lens);
     });
 }
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *seed, uint8_t **proof, size_t *proof_len) {

@@ -6,21 +6,24 @@
 
 namespace {
 thread_local std::string g_err;
-zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0) {
-    return zk::compile_circuit(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+zk::Circuit compile(int kind, size_t len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0) {
+    return zk::compile_circuit(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
 }
 void require_key_len(size_t key_len) { if (key_len != 16 && key_len != 24 && key_len != 32) throw std::invalid_argument("the AES key must have 16, 24 or 32 bytes"); }
 // Chunk j's public input without the leading One, as every chunked verifier and zkaes_chunk_public_inputs derive it: the header entering the chunk (statement.hpp, the
-// prover's own rule), the chunk's ciphertext bits, the key tag's when there is one, and (states[j], states[j + 1]) when there are states
-std::vector<zk::Fr> chunk_public_input(int circuit_kind, size_t j, size_t chunk, const uint8_t *iv_or_icb, const uint8_t *ct, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states) {
+// prover's own rule), the chunk's ciphertext bits, the key tag's when there is one, (states[j], states[j + 1]) when there are states, and the chunk's slice of the job's
+// mask and of its revealed bytes when there is a mask
+std::vector<zk::Fr> chunk_public_input(int circuit_kind, size_t j, size_t chunk, const uint8_t *iv_or_icb, const uint8_t *ct, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states,
+                                       const uint8_t *mask = nullptr, const uint8_t *revealed = nullptr) {
     uint8_t hdr[16];
     const size_t hb = zk::chunk_mode_header(circuit_kind, j, chunk, iv_or_icb, ct, hdr);
-    return zk::public_input_of({{hdr, hb}, {ct + chunk * j, chunk}, {key_tag, key_tag_len}, {states ? states + 32 * j : nullptr, 64}});      // states[j] is H_in, states[j + 1] H_out
+    return zk::public_input_of({{hdr, hb}, {ct + chunk * j, chunk}, {key_tag, key_tag_len}, {states ? states + 32 * j : nullptr, 64},      // states[j] is H_in, states[j + 1] H_out
+                                {mask ? zk::chunk_mask_slice(mask, j, chunk) : nullptr, zk::mask_bytes(chunk)}, {mask ? revealed + chunk * j : nullptr, chunk}});
 }
 // a GCM record's public input without the leading One: iv, aad, ciphertext, tag, then the key tag and (h_in, h_out) of the keys that carry them (null otherwise)
 std::vector<zk::Fr> gcm_public_input(const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *key_tag, size_t key_tag_len,
-                                     const uint8_t *h_in, const uint8_t *h_out) {
-    return zk::public_input_of({{iv, 12}, {aad, aad_len}, {ct, ct_len}, {tag, 16}, {key_tag, key_tag_len}, {h_in, 32}, {h_out, 32}});
+                                     const uint8_t *h_in, const uint8_t *h_out, const uint8_t *mask = nullptr, const uint8_t *revealed = nullptr) {
+    return zk::public_input_of({{iv, 12}, {aad, aad_len}, {ct, ct_len}, {tag, 16}, {key_tag, key_tag_len}, {h_in, 32}, {h_out, 32}, {mask, zk::mask_bytes(ct_len)}, {mask ? revealed : nullptr, ct_len}});
 }
 // n proofs packed one behind the other, each checked by accept(j, proof): a proof whose bytes do not parse is a rejected proof, not an error of the call
 template <class Accept> void verify_each(const uint8_t *proofs, const size_t *proof_lens, size_t n, int *accepted_each, size_t *n_accepted, Accept &&accept) {
@@ -39,9 +42,9 @@ template <class Accept> void verify_each(const uint8_t *proofs, const size_t *pr
 }
 // the chunk-proofs of one ECB, CBC or CTR job of n_chunks slices of `chunk` bytes, chunk j against chunk_public_input(j)
 void verify_chunks(const zk::VerifyingKey &vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, size_t chunk, const uint8_t *iv_or_icb, const uint8_t *ct,
-                   const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, int *accepted_each, size_t *n_accepted) {
+                   const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, int *accepted_each, size_t *n_accepted, const uint8_t *mask = nullptr, const uint8_t *revealed = nullptr) {
     verify_each(proofs, proof_lens, n_chunks, accepted_each, n_accepted, [&](size_t j, const zk::Proof &p) {
-        return zk::verify(vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states), p);
+        return zk::verify(vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states, mask, revealed), p);
     });
 }
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
@@ -380,6 +383,47 @@ int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof,
         *accepted = zk::verify(vk->vk, gcm_public_input(iv, aad, aad_len, ct, ct_len, tag, key_tag, key_tag_len, h_in ? h_in : iv0, h_out), p) ? 1 : 0;
     });
 }
+// ---- selective disclosure (include/zkaes.h): the masking on the host, and the verifiers that check every proof of a job against ONE mask and ONE array of
+// revealed bytes.  A mask bit at or beyond the length, or a non-zero revealed byte under a zero mask bit, is an ERROR of the call (statement.hpp), never a rejection
+int zkaes_reveal_bytes(const uint8_t *msg, size_t len, const uint8_t *mask, size_t mask_len, uint8_t *out) {
+    return guard([&] {
+        if ((len && (!msg || !out)) || !mask) throw std::invalid_argument("null argument");
+        if (mask_len != zk::mask_bytes(len)) throw std::invalid_argument("reveal_bytes: a mask over " + std::to_string(len) + " bytes has " + std::to_string(zk::mask_bytes(len)) + " bytes");
+        zk::require_mask(mask, len);
+        zk::reveal_bytes(msg, mask, len, out);
+    });
+}
+int zkaes_verify_reveal_chunked(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len,
+                                const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, int *accepted_each,
+                                size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t j = 0; j < n_chunks; j++) accepted_each[j] = 0;
+        if (!vk || !proofs || !proof_lens || !ct || !mask || !revealed) throw std::invalid_argument("null argument");
+        const size_t chunk = require_slices("verify_reveal_chunked", "zkaes_verify_encryption_gcm_reveal", circuit_kind, iv_or_icb, n_chunks, ct_len, key_tag, key_tag_len, false);
+        if (mask_len != zk::mask_bytes(ct_len)) throw std::invalid_argument("verify_reveal_chunked: ONE mask over the whole job, " + std::to_string(zk::mask_bytes(ct_len)) + " bytes for this ciphertext");
+        zk::require_revealed(mask, revealed, ct_len);
+        if (!fits_key(vk->vk, (iv_or_icb ? 128 : 0) + 8 * chunk + 8 * key_tag_len + (states ? 512 : 0) + 8 * zk::mask_bytes(chunk) + 8 * chunk, "verify_reveal_chunked")) return;      // every chunk rejected
+        verify_chunks(vk->vk, circuit_kind, proofs, proof_lens, n_chunks, chunk, iv_or_icb, ct, key_tag, key_tag_len, states, accepted_each, n_accepted, mask, revealed);
+    });
+}
+int zkaes_verify_encryption_gcm_reveal(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len,
+                                       const uint8_t tag[16], const uint8_t *key_tag, size_t key_tag_len, const uint8_t *h_in, const uint8_t *h_out, const uint8_t *mask, size_t mask_len,
+                                       const uint8_t *revealed, int *accepted) {
+    return guard([&] {
+        if (accepted) *accepted = 0;
+        if (!vk || !proof || !iv || !ct || !tag || !mask || !revealed || !accepted || (aad_len && !aad) || (h_in && !h_out)) throw std::invalid_argument("null argument");
+        require_opt_key_tag(key_tag, key_tag_len);
+        if (ct_len == 0) throw std::invalid_argument("GCM: the ciphertext must have at least one byte");
+        if (mask_len != zk::mask_bytes(ct_len)) throw std::invalid_argument("GCM: a mask over this ciphertext has " + std::to_string(zk::mask_bytes(ct_len)) + " bytes");
+        zk::require_revealed(mask, revealed, ct_len);
+        if (!fits_key(vk->vk, 224 + 8 * (aad_len + ct_len) + 8 * key_tag_len + (h_out ? 512 : 0) + 8 * mask_len + 8 * ct_len, "GCM")) return;
+        zk::Proof p = zk::deserialize_proof(proof, proof_len);
+        uint8_t iv0[32];
+        zk::sha256_chain(nullptr, nullptr, 0, iv0);
+        *accepted = zk::verify(vk->vk, gcm_public_input(iv, aad, aad_len, ct, ct_len, tag, key_tag, key_tag_len, h_out ? (h_in ? h_in : iv0) : nullptr, h_out, mask, revealed), p) ? 1 : 0;
+    });
+}
 int zkaes_proof_roundtrip(const uint8_t *proof, size_t proof_len, uint8_t **out, size_t *out_len) {
     return guard([&] { auto b = zk::serialize_proof(zk::deserialize_proof(proof, proof_len)); *out = give(b); *out_len = b.size(); });
 }
@@ -459,10 +503,13 @@ int zkaes_circuit_info_kt(int kind, unsigned key_bits, unsigned key_tag_blocks, 
 int zkaes_circuit_info_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, uint64_t out[12]) {
     return guard([&] { fill_info(compile(kind, len, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix), out); });
 }
+int zkaes_circuit_info_rv(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, unsigned reveal, size_t len, size_t aad_len, uint64_t out[12]) {
+    return guard([&] { fill_info(compile(kind, len, aad_len, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix, reveal > 1 ? 2 : (int)reveal), out); });
+}
 static int circuit_matrix(int kind, size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff, size_t key_bits = 128,
-                          size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0) {
+                          size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0) {
     return guard([&] {
-        zk::Circuit c = compile(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+        zk::Circuit c = compile(kind, len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -484,6 +531,10 @@ int zkaes_circuit_matrix_kt(int kind, unsigned key_bits, unsigned key_tag_blocks
 int zkaes_circuit_matrix_pd(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, size_t len, size_t aad_len, int which, uint64_t *n_rows,
                             uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix);
+}
+int zkaes_circuit_matrix_rv(int kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, unsigned reveal, size_t len, size_t aad_len, int which,
+                            uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix(kind, len, aad_len, which, n_rows, nnz, rowptr, col, coeff, key_bits, key_tag_blocks, (int)digest_kind, digest_prefix, reveal > 1 ? 2 : (int)reveal);
 }
 int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return circuit_matrix(zk::CIRCUIT_AES_GCM, len, aad_len, which, n_rows, nnz, rowptr, col, coeff);
@@ -527,19 +578,30 @@ int zkaes_verify_batch_timings(double out[8]) {
         out[0] = t.parse_ms; out[1] = t.decompress_ms; out[2] = t.transcripts_ms; out[3] = t.xhat_ms; out[4] = t.msm_ms; out[5] = t.pairing_ms; out[6] = t.total_ms; out[7] = (double)t.sub_batches;
     });
 }
-int zkaes_chunk_public_inputs(int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states,
-                              uint8_t *out_bits, size_t *n_bits) {
+// the rows of a chunked job for batch verification; with a mask (the _rv form) every row ends in the chunk's slice of the mask and of the revealed bytes
+static int chunk_public_inputs(const char *entry, int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len, const uint8_t *key_tag, size_t key_tag_len,
+                               const uint8_t *states, const uint8_t *mask, const uint8_t *revealed, uint8_t *out_bits, size_t *n_bits) {
     return guard([&] {
         if (!ct) throw std::invalid_argument("null argument");
-        const size_t chunk = require_slices("chunk_public_inputs", nullptr, circuit_kind, iv_or_icb, n_chunks, ct_len, key_tag, key_tag_len, false);
-        const size_t row = (iv_or_icb ? 128 : 0) + 8 * chunk + 8 * key_tag_len + (states ? 512 : 0);
+        const size_t chunk = require_slices(entry, nullptr, circuit_kind, iv_or_icb, n_chunks, ct_len, key_tag, key_tag_len, false);
+        if (mask) zk::require_revealed(mask, revealed, ct_len);
+        const size_t row = (iv_or_icb ? 128 : 0) + 8 * chunk + 8 * key_tag_len + (states ? 512 : 0) + (mask ? 8 * zk::mask_bytes(chunk) + 8 * chunk : 0);
         if (n_bits) *n_bits = row;
         if (!out_bits) return;
         for (size_t j = 0; j < n_chunks; j++) {
-            std::vector<zk::Fr> pub = chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states);
+            std::vector<zk::Fr> pub = chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states, mask, revealed);
             for (size_t i = 0; i < row; i++) out_bits[j * row + i] = pub[i].is_zero() ? 0 : 1;
         }
     });
+}
+int zkaes_chunk_public_inputs(int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states,
+                              uint8_t *out_bits, size_t *n_bits) {
+    return chunk_public_inputs("chunk_public_inputs", circuit_kind, n_chunks, iv_or_icb, ct, ct_len, key_tag, key_tag_len, states, nullptr, nullptr, out_bits, n_bits);
+}
+int zkaes_chunk_public_inputs_rv(int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ct, size_t ct_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states,
+                                 const uint8_t *mask, size_t mask_len, const uint8_t *revealed, uint8_t *out_bits, size_t *n_bits) {
+    if (!mask || !revealed || mask_len != zk::mask_bytes(ct_len)) return guard([&] { throw std::invalid_argument("chunk_public_inputs_rv: ONE mask over the whole job (ceil(ct_len / 8) bytes) and its revealed bytes"); });
+    return chunk_public_inputs("chunk_public_inputs_rv", circuit_kind, n_chunks, iv_or_icb, ct, ct_len, key_tag, key_tag_len, states, mask, revealed, out_bits, n_bits);
 }
 int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return guard([&] {

@@ -493,23 +493,49 @@ void require_digest(int digest_kind, uint64_t digest_prefix, size_t len) {
     if (digest_kind == DIGEST_FINAL && (digest_prefix % 64 || digest_prefix >= ((uint64_t)1 << 61) || (uint64_t)len >= ((uint64_t)1 << 61) - digest_prefix))
         throw std::invalid_argument("digest_prefix must be a multiple of 64 with digest_prefix + the message length below 2^61");
 }
-// finish() for a mode whose own trace takes mode_bytes: the key-tag blocks go behind it, the digest region behind them
-Circuit finish_aes(Builder &b, AesGates &g, int kind, size_t n_blocks, size_t mode_bytes, size_t key_tag_blocks, const std::vector<Byte> &msg, int digest_kind, uint64_t digest_prefix) {
+// Selective disclosure, behind everything else a key emits: ceil(L / 8) mask bytes and L revealed bytes as inputs, the mask first (trace_layout.h TRV_*); one
+// row mask_i * 1 = 0 per mask bit at or beyond L; per message bit ONE row mask_i * m_ij = r_ij with the mask input in A, the message witness of alloc_message_and_key
+// in B and the revealed input in C.  No witness is allocated.  `bytes` = the trace length ahead of the region; returns the length with it
+size_t reveal(Builder &b, const std::vector<Byte> &msg, size_t bytes) {
+    const size_t len = msg.size(), mb = TRV_MASK_BYTES(len);
+    const uint32_t rv = (uint32_t)TRV(bytes), rev = rv + (uint32_t)TRV_REVEALED(len);
+    std::vector<Byte> mask(mb);
+    for (size_t i = 0; i < mb; i++) mask[i] = b.alloc_byte(true, rv + TRV_MASK + (uint32_t)i);
+    for (size_t i = len; i < 8 * mb; i++) b.enforce_equal(mask[i / 8][i % 8], Bit::konst(false));
+    for (size_t i = 0; i < len; i++) {
+        Byte r = b.alloc_byte(true, rev + (uint32_t)i);
+        for (int k = 0; k < 8; k++) {
+            LC A_, B_, C_;
+            A_.add(1, mask[i / 8][i % 8]); B_.add(1, msg[i][k]); C_.add(1, r[k]);
+            b.enforce(A_, B_, C_);
+        }
+    }
+    return TRV_BYTES(bytes, 1, len);
+}
+void require_reveal(int reveal) {
+    if (reveal != 0 && reveal != 1) throw std::invalid_argument("reveal must be 0 or 1");
+}
+// finish() for a mode whose own trace takes mode_bytes: the key-tag blocks go behind it, the digest region behind them, the reveal region last
+Circuit finish_aes(Builder &b, AesGates &g, int kind, size_t n_blocks, size_t mode_bytes, size_t key_tag_blocks, const std::vector<Byte> &msg, int digest_kind, uint64_t digest_prefix, int rv) {
     size_t trace_bytes = g.key_tag(key_tag_blocks, mode_bytes);
     const size_t digest_off = digest_kind ? TRD(trace_bytes) : 0;
     if (digest_kind) { Sha256Gates sha(b); trace_bytes = sha.digest(msg, digest_kind, digest_prefix, trace_bytes); }
+    const size_t reveal_off = rv ? TRV(trace_bytes) : 0;
+    if (rv) trace_bytes = reveal(b, msg, trace_bytes);
     Circuit c = finish(b, kind, n_blocks, trace_bytes, g.key_bytes());
     c.key_tag_blocks = key_tag_blocks; c.key_tag_off = key_tag_blocks ? TRK_KT(mode_bytes) : 0;
     c.digest_kind = digest_kind; c.digest_prefix = digest_prefix; c.digest_blocks = TRD_BLOCKS(digest_kind, msg.size()); c.digest_off = digest_off;
+    c.reveal = rv; c.reveal_off = reveal_off;
     return c;
 }
 }  // namespace
 
-Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
+Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int reveal) {
     if (len % 16) throw std::invalid_argument("Input must be 16 bytes length when adding round key");
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
     require_digest(digest_kind, digest_prefix, len);
+    require_reveal(reveal);
     size_t nb = len / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -521,16 +547,17 @@ Circuit compile_aes_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, 
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = s[i];
     }
     g.ciphertext_inputs(ct);
-    return finish_aes(b, g, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), key_tag_blocks, msg, digest_kind, digest_prefix);
+    return finish_aes(b, g, CIRCUIT_AES, nb, TRK_ECB_BYTES(g.nk, nb), key_tag_blocks, msg, digest_kind, digest_prefix, reveal);
 }
 
 // Gate order: message and key witnesses, the 16 IV bytes as inputs, the key schedule, per block the 128 xor gates of X_b = M_b ^ prev (prev = the IV bytes, then the
 // previous block's S_10) and the block's rounds from X_b, the ciphertext inputs.  The instance is One, 128 IV bits, 128 nb ciphertext bits.
-Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
+Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int reveal) {
     if (len == 0 || len % 16) throw std::invalid_argument("CBC: the message must be a non-zero multiple of 16 bytes");
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
     require_digest(digest_kind, digest_prefix, len);
+    require_reveal(reveal);
     size_t nb = len / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -547,7 +574,7 @@ Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
         for (int i = 0; i < 16; i++) ct[16 * bi + i] = prev[i];
     }
     g.ciphertext_inputs(ct);
-    return finish_aes(b, g, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, key_tag_blocks, msg, digest_kind, digest_prefix);
+    return finish_aes(b, g, CIRCUIT_AES_CBC, nb, cbc + TR_CBC_X + 16 * nb, key_tag_blocks, msg, digest_kind, digest_prefix, reveal);
 }
 
 // Gate order: message and key witnesses, the 16 ICB bytes as inputs, the key schedule, per block (from the second on) the incrementer over the previous block's counter
@@ -555,11 +582,12 @@ Circuit compile_aes_cbc_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
 // 128 ICB bits, 8 len ciphertext bits.
 // Incrementer: counter bit i (weight 2^i) is bit i % 8 of byte 15 - i / 8.  c_0 = 1, y_i = x_i ^ c_i, c_{i+1} = x_i & c_i (none behind i = 127: the sum is mod 2^128).
 // Position 0 folds away (y_0 = !x_0, c_1 = x_0), which leaves 127 xor and 126 and gates per increment.
-Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
+Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int reveal) {
     if (len == 0) throw std::invalid_argument("CTR: the message must have at least one byte");
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
     require_digest(digest_kind, digest_prefix, len);
+    require_reveal(reveal);
     size_t nb = (len + 15) / 16;
     Builder b;
     AesGates g(b, key_bits);
@@ -594,7 +622,7 @@ Circuit compile_aes_ctr_circuit(size_t len, size_t key_bits, size_t key_tag_bloc
         Byte pi = b.alloc_byte(true, slot(i / 16) + TR_CTR_BL_CT + (uint32_t)(i % 16));
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], ct[i][k]);
     }
-    Circuit c = finish_aes(b, g, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), key_tag_blocks, msg, digest_kind, digest_prefix);
+    Circuit c = finish_aes(b, g, CIRCUIT_AES_CTR, nb, TRK_CTR_BYTES(g.nk, nb), key_tag_blocks, msg, digest_kind, digest_prefix, reveal);
     c.message_bytes = len;
     return c;
 }
@@ -654,10 +682,11 @@ Blk ghash_multiply(Builder &b, const Blk &X, const std::vector<Blk> &V, uint32_t
 }
 }  // namespace
 
-Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
+Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int reveal) {
     require_key_bits(key_bits);
     require_key_tag_blocks(key_tag_blocks);
     require_digest(digest_kind, digest_prefix, len);
+    require_reveal(reveal);
     if (len == 0) throw std::invalid_argument("GCM: the message must have at least one byte");
     if (len > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM: message and aad of one proof are limited to 65536 bytes each");
     const size_t nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TR_GCM_MULS(na, nb);
@@ -707,7 +736,7 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
         Byte pi = b.alloc_byte(true, tag_off + (uint32_t)j);
         for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], tag[j][k]);
     }
-    Circuit c = finish_aes(b, g, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), key_tag_blocks, msg, digest_kind, digest_prefix);
+    Circuit c = finish_aes(b, g, CIRCUIT_AES_GCM, nb, TRK_GCM_BYTES(g.nk, na, nb), key_tag_blocks, msg, digest_kind, digest_prefix, reveal);
     c.message_bytes = len; c.aad_bytes = alen;
     return c;
 }
@@ -823,14 +852,16 @@ Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, siz
     return c;
 }
 
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix) {
-    if (kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment circuit has a role: use the _gcm_seg entry points (zkaes_circuit_info_gcm_seg, zkaes_synthesize_keys_gcm_seg)");
-    if (kind == CIRCUIT_AES_GCM)return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int reveal) {
+    require_reveal(reveal);
+    if (kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment circuit has a role: use the _gcm_seg entry points (zkaes_circuit_info_gcm_seg, zkaes_synthesize_keys_gcm_seg); segments have no reveal form");
+    if (kind == CIRCUIT_AES_GCM)return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
-    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
-    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
-    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
+    if (kind == CIRCUIT_AES_CBC) return compile_aes_cbc_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
+    if (kind == CIRCUIT_AES_CTR) return compile_aes_ctr_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     if (digest_kind || digest_prefix) throw std::invalid_argument("the ops circuits have no message: digest_kind must be 0");
+    if (reveal) throw std::invalid_argument("the ops circuits have no message: reveal must be 0");
     if (key_bits != 128) throw std::invalid_argument("the ops circuits have no AES key: key_bits must be 128");
     if (key_tag_blocks) throw std::invalid_argument("the ops circuits have no AES key: key_tag_blocks must be 0");
     return compile_ops_circuit(kind);
@@ -1079,6 +1110,8 @@ void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *ta
     for (size_t o = 0; o < n; o += 64) sha256_compress(st, blk + o);
     sha256_store(st, digest);
 }
+
+size_t reveal_mask_bytes(const Circuit &c) { return c.reveal ? TRV_MASK_BYTES(c.message_bytes) : 0; }
 
 size_t mode_header_bytes(const Circuit &c) {
     return c.kind == CIRCUIT_AES_GCM_SEG ? TRS_HDR_BYTES(c.aad_bytes) : c.kind == CIRCUIT_AES_GCM ? 12 + c.aad_bytes : (c.kind == CIRCUIT_AES_CBC || c.kind == CIRCUIT_AES_CTR) ? 16 : 0;

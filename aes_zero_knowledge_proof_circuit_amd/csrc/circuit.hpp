@@ -45,6 +45,8 @@ struct Circuit {
     uint64_t digest_prefix = 0;          // final keys: P, the message bytes hashed ahead of this proof's (a multiple of 64); the padding's length field is 8 (P + message_bytes)
     size_t digest_blocks = 0;            // compressions per proof (trace_layout.h TRD_BLOCKS), 0 when D = 0
     size_t digest_off = 0;               // trace offset of the digest region (trace_layout.h TRD), 0 when D = 0
+    int reveal = 0;                      // R = 0 or 1: a reveal key's last 8 ceil(L / 8) + 8 L instance bits are a per-proof mask and revealed[i] = mask_i ? M[i] : 0, L = message_bytes
+    size_t reveal_off = 0;               // trace offset of the reveal region (trace_layout.h TRV), 0 when R = 0
     int seg_role = -1;                   // a GCM segment key (kind CIRCUIT_AES_GCM_SEG): 0 head, 1 mid, 2 tail (trace_layout.h TRS_*); -1 for every other key
     size_t seg_off = 0;                  // trace offset of the segment region (trace_layout.h TRS_SEG), 0 for every other key
     size_t num_variables() const { return num_instance + num_witness; }
@@ -59,20 +61,23 @@ struct Circuit {
 // (FIPS 180-4 6.2.2) of the hidden message's 64-byte blocks from H_in, and 256 inputs H_out equal to the last feed-forward; the message must then be a non-zero multiple
 // of 64 bytes.  DIGEST_FINAL does the same over message || 0x80 || zeros || be64(8 (digest_prefix + message_len)) for any message length the mode allows; digest_prefix
 // is a multiple of 64 with digest_prefix + message_len < 2^61, and 0 for the other kinds.  Anything else is std::invalid_argument
+// reveal (every AES compiler, default 0 = the circuit as it was): 1 appends, behind the digest, ceil(L / 8) mask bytes and L revealed bytes as inputs (the mask first),
+// one row per mask bit at or beyond L that pins it to zero, and per message bit ONE row mask_i * m_ij = r_ij over the message witnesses: no new witness.
+// Anything but 0 or 1 is std::invalid_argument; the ops circuits and the GCM segment circuits have no reveal form
 enum DigestKind { DIGEST_NONE = 0, DIGEST_CHAIN = 1, DIGEST_FINAL = 2 };
-Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
 Circuit compile_ops_circuit(int kind);
 // AES-128-CBC over the same gadgets (no upstream counterpart; DESIGN.md "CBC"): public = 16 IV bytes then the ciphertext, private = message and key;
 // per block X_b = M_b ^ C_{b-1} (C_{-1} = IV) ahead of the block's round 0.  message_len must be a non-zero multiple of 16 (else std::invalid_argument)
-Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+Circuit compile_aes_cbc_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
 // AES-128-CTR over the same gadgets (DESIGN.md "CTR"): public = the 16 bytes of the initial counter block then the ciphertext, private = message and key;
 // CTR_0 = icb, CTR_b = CTR_{b-1} + 1 mod 2^128 (big-endian, SP 800-38A B.1 with m = 128), C_b = M_b ^ AES(key, CTR_b), the last block cut to the bytes that exist.
 // message_len is any byte count >= 1 (else std::invalid_argument)
-Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+Circuit compile_aes_ctr_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
 // AES-128-GCM (SP 800-38D, 96-bit IV, full tag; DESIGN.md "GCM"): public = iv (12 bytes), aad (aad_len bytes), ciphertext (message_len bytes), tag (16 bytes), private =
 // message and key.  The trace holds nb + 2 AES blocks (the message blocks under iv || be32(b + 2), H = AES_K(0), AES_K(iv || 1)), the V table of H and, per GHASH block,
 // one multiplication by H as 16,384 and gates and 128 parity rows.  message_len >= 1, aad_len >= 0; both are fixed by the key (else std::invalid_argument)
-Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
 // One segment of a GCM record longer than one proof.  role = 0 head, 1 mid, 2 tail; units = c, the data blocks of a head or mid segment, or Lt, the
 // 1 .. 16 c bytes of a tail; aad_len = the record's whole aad (head only, else 0).  Public input, in order: iv (12 bytes), ctr0 (4, big-endian: the counter of the
 // segment's first data block), head: aad, ciphertext, com_out (32); mid: ciphertext, com_in, com_out; tail: ciphertext, the length block be64(8 A) || be64(8 L) of the
@@ -82,7 +87,7 @@ Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_b
 Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
 // 128, key_tag_blocks 0 and digest_kind 0 for the ops kinds
-Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);
+Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
 // SHA-256 on the host (FIPS 180-4), for the verifier and the prover's chaining alike.  A state is 32 bytes, the eight words in big-endian serialisation; h_in = nullptr is
 // the initial value.  sha256_chain: h_out = the compressions of data's len / 64 blocks from h_in, no padding; len must be a multiple of 64 (else std::invalid_argument).
 // sha256_finish: digest = the chain from h_in over tail || 0x80 || zeros || be64(8 (prefix_bytes + tail_len)); prefix_bytes a multiple of 64, prefix_bytes + tail_len < 2^61
@@ -91,6 +96,8 @@ void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *ta
 // the bytes of the per-proof public header a key's mode takes ahead of a digest key's H_in: 0 (ECB), 16 (CBC, CTR), 12 + aad_bytes (GCM); for a GCM segment key the
 // 80 + aad_bytes of a segment header (trace_layout.h TRS_HDR_*), which also carries that proof's witnesses Y_in and the salts
 size_t mode_header_bytes(const Circuit &c);
+// the ceil(message_bytes / 8) mask bytes a reveal key's per-proof header carries behind H_in, 0 for every other key
+size_t reveal_mask_bytes(const Circuit &c);
 // the key tag itself on the host: out = 16 tag_blocks bytes, AES_K(D_0) (|| AES_K(D_1)); key_len = 16, 24 or 32, tag_blocks = 1 or 2 (else std::invalid_argument)
 void aes_key_tag_host(const uint8_t *key, size_t key_len, size_t tag_blocks, uint8_t *out);
 // D_t, the constant block behind tag block t

@@ -284,6 +284,12 @@ void key_tag_trace(uint8_t *trace, size_t trace_stride, size_t tag_off, const ui
 // kernel on the same stream, it writes bytes disjoint from theirs.  stride >= digest_off + 64 + compressions x 4032; stride, digest_off and the trace 16-byte aligned
 void sha256_trace(uint8_t *trace, size_t trace_stride, size_t digest_off, const uint8_t *msgs, const uint8_t *hdrs, size_t hdr_stride, size_t hin_off, uint32_t nproofs, size_t msg_len, int digest_kind,
                   uint64_t digest_prefix, stream_t s);
+// Selective disclosure, any mode (kernels_reveal.hip): fills the reveal region of each proof's trace at reveal_off (trace_layout.h TRV) -- the proof's mask, the
+// ceil(msg_len / 8) bytes at mask_off of its header, and revealed[i] = mask_i ? M[i] : 0 -- from the messages and the masks alone.  Launched behind the mode's kernel(s),
+// the tag kernel and the digest kernel on the same stream, it writes bytes disjoint from theirs.  reveal = the key's flag (must be 1), key_msg_len = the key's message
+// length (must be msg_len); stride >= reveal_off + TRV_REGION_BYTES(msg_len); stride, reveal_off and the trace 16-byte aligned
+void reveal_trace(uint8_t *trace, size_t trace_stride, size_t reveal_off, const uint8_t *msgs, const uint8_t *hdrs, size_t hdr_stride, size_t mask_off, uint32_t nproofs, size_t msg_len, int reveal,
+                  size_t key_msg_len, stream_t s);
 // GCM segments (trace_layout.h TRS_*): role = 0 head, 1 mid, 2 tail; msg_len = 16 c for a head or mid, 1 .. 16 c for a tail; aad_len = 0 except for a
 // head; hdrs = nproofs x TRS_HDR_BYTES(aad_len) bytes (iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad).  aes_trace_gcm_seg fills the AES slots, the header
 // part of the tail and of the segment region and the per-block counters; ghash_trace_seg behind it the V table, the multiplications from Y_in on and a tail's tag;

@@ -330,10 +330,10 @@ class ProvingKeyImpl {
         const Circuit &c = circuit;
         size_t n4 = next_pow2(3 * n + 1);
         cx.d_trace.alloc(c.trace_bytes + 64); cx.d_z.alloc(c.num_variables() + 64);
-        // the layout's alignment padding (ahead of the GCM tail, the key-tag slots and the digest region) is written by no kernel and read by no variable: zeroed once, on the
+        // the layout's alignment padding (ahead of the GCM tail, the key-tag slots, the digest region and the reveal region) is written by no kernel and read by no variable: zeroed once, on the
         // stream every trace kernel of this context runs on, so that the trace a debug fetch returns depends on the inputs only and not on what the allocation held before
         gpu::dzero(cx.d_trace, c.trace_bytes + 64, cx.stream);
-        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, mode_header_bytes(c)) + (c.digest_kind ? 32 : 0));      // (a digest key's header carries H_in behind the mode's own)
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, mode_header_bytes(c)) + (c.digest_kind ? 32 : 0) + reveal_mask_bytes(c));      // (a digest key's header carries H_in behind the mode's own, a reveal key's the mask behind that)
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
@@ -491,7 +491,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role = -1);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role = -1, int reveal = 0);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -500,7 +500,7 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role, int reveal) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
@@ -510,7 +510,7 @@ void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lit
     if (kind == CIRCUIT_AES_GCM_SEG) {                                             // message_len_ = the segment's units: c data blocks (head, mid) or Lt bytes (tail)
         circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits);
         message_len = circuit.message_bytes;
-    } else circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    } else circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     const Circuit &c = circuit;
     // ---- joint matrix (sum_matrices): per-row sorted union of the A, B, C column supports
     size_t rows = c.num_constraints;
@@ -675,6 +675,13 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
         const size_t hb = mode_header_bytes(c);
         gpu::h2d(cx.d_iv.p + hb, iv + hb, 32, s);
         gpu::sha256_trace(cx.d_trace, c.trace_bytes, c.digest_off, cx.d_msg, cx.d_iv, hb + 32, hb, 1, c.message_bytes, c.digest_kind, c.digest_prefix, s);
+    }
+    // a reveal key: the proof's header carries the mask behind H_in; the reveal region behind the digest region, from the message and the mask alone
+    if (c.reveal) {
+        if (!iv) throw std::invalid_argument("a reveal proving key needs a header that ends in the mask");
+        const size_t at = mode_header_bytes(c) + (c.digest_kind ? 32 : 0), mb = reveal_mask_bytes(c);
+        gpu::h2d(cx.d_iv.p + at, iv + at, mb, s);
+        gpu::reveal_trace(cx.d_trace, c.trace_bytes, c.reveal_off, cx.d_msg, cx.d_iv, at + mb, at, 1, len, c.reveal, c.message_bytes, s);
     }
 }
 
@@ -1010,9 +1017,11 @@ void ProvingKey::msm_powers_partial_device(const uint8_t *scalars, size_t n_loca
 // ---- The statement layer: every mode is "message, key, a public header of mode_header_bytes(c) bytes, H_in where the key has a digest" (statement.hpp), so there is one
 // body per shape of call -- witness, lone proof, batch, chunked job -- and none per mode.  DESIGN.md has the statements: "CBC", "CTR", "GCM", 9e (key tags), 9f (digests).
 // Is this the key the entry point is for?  kind: the mode the entry names, or ANY_AES_KIND (the _digest_ entries take every mode); digest: does the entry carry H_in and
-// H_out -- a digest key's proofs do, which the entries from before have no argument for; len: the message's; aad_len: the aad's, or KEY_AAD where the entry takes the
+// H_out -- a digest key's proofs do, which the entries from before have no argument for; reveal: does the entry carry a mask (the same rule); len: the message's; aad_len: the aad's, or KEY_AAD where the entry takes the
 // header whole
-static void require_key(const Circuit &c, int kind, bool digest, size_t len, size_t aad_len) {
+static void require_key(const Circuit &c, int kind, bool digest, size_t len, size_t aad_len, bool reveal = false) {
+    if (reveal && !c.reveal) throw std::invalid_argument("the _reveal_ entry points take a proving key synthesized with reveal = 1 (zkaes_synthesize_keys_rv)");
+    if (!reveal && c.reveal) throw std::invalid_argument("this proving key reveals plaintext bytes under a per-proof mask: use the _reveal_ entry points (zkaes_encrypt_reveal_batch_seeded_at, zkaes_encrypt_reveal_chunked_seeded_at, zkaes_aes_witness_rv)");
     if (digest && !c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
     if (!digest && c.digest_kind) throw std::invalid_argument("this proving key carries a plaintext digest: use the _digest_ entry points (zkaes_encrypt_digest_batch_seeded_at, zkaes_encrypt_digest_chunked_seeded_at, zkaes_aes_witness_pd)");
     if (kind != ProvingKey::ANY_AES_KIND) {
@@ -1030,12 +1039,13 @@ static void require_key(const Circuit &c, int kind, bool digest, size_t len, siz
 //    "msm":[[points,"buckets"|"second_bases"|"class_sum"],..]}
 // -- what bench.py computes the whole-proof roofline of SURVEY.md 8(d) from.  Process-global recorder: call with no other proof in flight.
 std::string ProvingKey::op_lists_json(const uint8_t *message, size_t len, const uint8_t key[16], bool throughput_path) {
-    require_key(impl->circuit, CIRCUIT_AES, impl->circuit.digest_kind != 0, len, KEY_AAD);      // (an ECB key with or without a digest)
+    require_key(impl->circuit, CIRCUIT_AES, impl->circuit.digest_kind != 0, len, KEY_AAD, impl->circuit.reveal != 0);      // (an ECB key with or without a digest, with or without reveal)
     gpu::OpRecord rec;
     gpu::oplog_begin();
-    uint8_t h_in[32];                                                              // an ECB key with a digest: its header is H_in alone; the recorded proof starts from the initial value
-    sha256_chain(nullptr, nullptr, 0, h_in);
-    try { impl->prove(impl->context(0), nullptr, message, len, key, nullptr, throughput_path, impl->circuit.digest_kind ? h_in : nullptr); }
+    // an ECB key's header is H_in (with a digest), then the mask (with reveal): the recorded proof starts from the initial value and reveals nothing
+    std::vector<uint8_t> hdr((impl->circuit.digest_kind ? 32 : 0) + reveal_mask_bytes(impl->circuit), 0);
+    if (impl->circuit.digest_kind) sha256_chain(nullptr, nullptr, 0, hdr.data());
+    try { impl->prove(impl->context(0), nullptr, message, len, key, nullptr, throughput_path, hdr.empty() ? nullptr : hdr.data()); }
     catch (...) { gpu::oplog_end(); throw; }
     rec = gpu::oplog_end();
     const Circuit &c = impl->circuit;
@@ -1113,25 +1123,31 @@ static std::vector<Proof> prove_many(ProvingKeyImpl *impl, const uint8_t *messag
     return proofs;
 }
 // what a trace kernel reads beside message and key, at out: the mode's header, then -- for a digest key -- H_in, null being SHA-256's initial value
-static void trace_header(const Circuit &c, const uint8_t *hdr, const uint8_t *h_in, uint8_t *out) {
-    const size_t hb = mode_header_bytes(c);
+// -- then, for a reveal key, the proof's mask, checked here: no bit at or beyond the message's length
+static void trace_header(const Circuit &c, const uint8_t *hdr, const uint8_t *h_in, uint8_t *out, const uint8_t *mask = nullptr) {
+    size_t hb = mode_header_bytes(c);
     if (hb) memcpy(out, hdr, hb);
-    if (!c.digest_kind) return;
-    if (h_in) memcpy(out + hb, h_in, 32); else sha256_chain(nullptr, nullptr, 0, out + hb);        // (no blocks: the initial value)
+    if (c.digest_kind) {
+        if (h_in) memcpy(out + hb, h_in, 32); else sha256_chain(nullptr, nullptr, 0, out + hb);    // (no blocks: the initial value)
+        hb += 32;
+    }
+    if (!c.reveal) return;
+    require_mask(mask, c.message_bytes);
+    memcpy(out + hb, mask, reveal_mask_bytes(c));
 }
-static size_t trace_header_bytes(const Circuit &c) { return mode_header_bytes(c) + (c.digest_kind ? 32 : 0); }
+static size_t trace_header_bytes(const Circuit &c) { return mode_header_bytes(c) + (c.digest_kind ? 32 : 0) + reveal_mask_bytes(c); }
 // the host's side of one statement into whichever buffers the caller gave: the ciphertext, GCM's tag
 static void host_side(const Circuit &c, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, uint8_t *ct_or_null, uint8_t *tag_or_null) {
     if (!ct_or_null && !(tag_or_null && c.kind == CIRCUIT_AES_GCM)) return;
     std::vector<uint8_t> unwanted(ct_or_null ? 0 : len);
     host_encrypt(c, msg, len, key, hdr, ct_or_null ? ct_or_null : unwanted.data(), tag_or_null);
 }
-std::vector<uint8_t> ProvingKey::witness(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *h_in) {
+std::vector<uint8_t> ProvingKey::witness(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *h_in, const uint8_t *mask) {
     const Circuit &c = impl->circuit;
-    require_key(c, kind, digest, len, aad_len);
+    require_key(c, kind, digest, len, aad_len, mask != nullptr);
     if (!message || !key || (!hdr && mode_header_bytes(c))) throw std::invalid_argument("null argument");
     std::vector<uint8_t> h(trace_header_bytes(c));
-    trace_header(c, hdr, h_in, h.data());
+    trace_header(c, hdr, h_in, h.data(), mask);
     return witness_of(impl, message, len, key, h.empty() ? nullptr : h.data());
 }
 Proof ProvingKey::prove_lone(int kind, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *zk_seed, uint8_t *ciphertext_or_null,
@@ -1143,16 +1159,18 @@ Proof ProvingKey::prove_lone(int kind, const uint8_t *message, size_t len, const
     return impl->prove(impl->context(0), nullptr, message, len, key, zk_seed, false, hdr);
 }
 std::vector<Proof> ProvingKey::prove_batch(int kind, bool digest, const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins, size_t n, size_t n_contexts,
-                                           const uint8_t *zk_seed, uint64_t index_offset, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null) {
+                                           const uint8_t *zk_seed, uint64_t index_offset, uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null, const uint8_t *masks,
+                                           uint8_t *revealed_or_null) {
     const Circuit &c = impl->circuit;
-    require_key(c, kind, digest, c.message_bytes, KEY_AAD);                  // (the entry points check the packed lengths against the key)
+    require_key(c, kind, digest, c.message_bytes, KEY_AAD, masks != nullptr);                  // (the entry points check the packed lengths against the key)
     if (c.message_bytes == 0) throw std::invalid_argument("proving key has an empty plaintext");
     const size_t hb = mode_header_bytes(c), stride = trace_header_bytes(c), L = c.message_bytes;
     if (n && (!messages || !keys || (!headers && hb))) throw std::invalid_argument("null argument");
     std::vector<uint8_t> hs(stride * n);
     for (size_t i = 0; i < n; i++) {
         uint8_t *h = hs.data() + stride * i;
-        trace_header(c, hb ? headers + hb * i : nullptr, h_ins ? h_ins + 32 * i : nullptr, h);
+        trace_header(c, hb ? headers + hb * i : nullptr, h_ins ? h_ins + 32 * i : nullptr, h, masks ? masks + reveal_mask_bytes(c) * i : nullptr);
+        if (masks && revealed_or_null) reveal_bytes(messages + L * i, masks + reveal_mask_bytes(c) * i, L, revealed_or_null + L * i);      // by the verifier's own masking: the device's meets it in the constraints
         host_side(c, messages + L * i, L, keys + c.key_bytes * i, h, ciphertexts_or_null ? ciphertexts_or_null + L * i : nullptr, tags_or_null ? tags_or_null + 16 * i : nullptr);
         if (!digest || !h_outs_or_null) continue;                            // H_out by plain SHA-256: the device's own meets it in the constraints
         if (c.digest_kind == DIGEST_CHAIN) sha256_chain(h + hb, messages + L * i, L, h_outs_or_null + 32 * i);
@@ -1163,9 +1181,9 @@ std::vector<Proof> ProvingKey::prove_batch(int kind, bool digest, const uint8_t 
 // The cipher (where it is asked for, or chains) and the hash run once on the host: every chaining value of either is public, so the chunk-proofs are independent and run
 // side by side.  Chunk j is proven under chunk_mode_header(j) -- any chunk from (hdr, j) alone for CTR -- and, over a chain key, under (states[j], states[j + 1])
 std::vector<Proof> ProvingKey::prove_chunked(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, size_t n_contexts,
-                                             const uint8_t *zk_seed, uint64_t index_offset, uint8_t *ciphertext_or_null, uint8_t *states_or_null) {
+                                             const uint8_t *zk_seed, uint64_t index_offset, uint8_t *ciphertext_or_null, uint8_t *states_or_null, const uint8_t *mask, uint8_t *revealed_or_null) {
     const Circuit &c = impl->circuit;
-    require_key(c, kind, digest, c.message_bytes, KEY_AAD);                  // (the job's length: below)
+    require_key(c, kind, digest, c.message_bytes, KEY_AAD, mask != nullptr);                  // (the job's length: below)
     if (digest && c.digest_kind != DIGEST_CHAIN) throw std::invalid_argument("a chunked digest job takes a chain key (a final key proves one lone tail: zkaes_encrypt_digest_batch_seeded_at)");
     if (c.kind != CIRCUIT_AES && c.kind != CIRCUIT_AES_CBC && c.kind != CIRCUIT_AES_CTR) throw std::invalid_argument("a chunked digest job takes an ECB, CBC or CTR key (GCM records go through the batch entry)");
     const size_t hb = mode_header_bytes(c), stride = trace_header_bytes(c), chunk = c.message_bytes;
@@ -1175,6 +1193,7 @@ std::vector<Proof> ProvingKey::prove_chunked(int kind, bool digest, const uint8_
     if (chunk == 0 || len % chunk || (len == 0 && !may_be_empty))
         throw std::invalid_argument(std::string("message length must be a ") + (may_be_empty ? "" : "non-zero ") + "multiple of the key's plaintext length (" + std::to_string(chunk) + " bytes)");
     const size_t n_chunks = len / chunk;
+    if (mask) require_mask(mask, len);
     std::vector<uint8_t> ct, hs(stride * n_chunks), states(digest ? 32 * (n_chunks + 1) : 0);
     if (ciphertext_or_null || c.kind == CIRCUIT_AES_CBC) { ct.resize(len); host_encrypt(c, message, len, key, hdr, ct.data(), nullptr); }
     if (digest && h_in) memcpy(states.data(), h_in, 32);                     // states[0] = H_in
@@ -1182,10 +1201,12 @@ std::vector<Proof> ProvingKey::prove_chunked(int kind, bool digest, const uint8_
     for (size_t j = 0; j < n_chunks; j++) {
         uint8_t *h = hs.data() + stride * j;
         chunk_mode_header(c.kind, j, chunk, hdr, ct.data(), h);
+        if (mask) memcpy(h + stride - reveal_mask_bytes(c), chunk_mask_slice(mask, j, chunk), reveal_mask_bytes(c));      // (whole blocks: every slice begins on a mask byte)
         if (!digest) continue;
         memcpy(h + hb, &states[32 * j], 32);
         sha256_chain(&states[32 * j], message + chunk * j, chunk, &states[32 * (j + 1)]);
     }
+    if (mask && revealed_or_null) reveal_bytes(message, mask, len, revealed_or_null);
     std::vector<Proof> proofs = prove_many(impl, message, key, 0, n_chunks, n_contexts, zk_seed, index_offset, stride ? hs.data() : nullptr, stride);
     if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
     if (states_or_null) memcpy(states_or_null, states.data(), states.size());
@@ -1391,11 +1412,11 @@ size_t ProvingKey::key_bytes() const { return impl->circuit.key_bytes; }
 size_t ProvingKey::key_tag_blocks() const { return impl->circuit.key_tag_blocks; }
 
 std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind,
-                                            uint64_t digest_prefix) {
+                                            uint64_t digest_prefix, int reveal) {
     if (circuit_kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment key has a role: use synthesize_keys_gcm_segment (zkaes_synthesize_keys_gcm_seg)");
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix);
+    pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, -1, reveal);
     return pk;
 }
 std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags) {

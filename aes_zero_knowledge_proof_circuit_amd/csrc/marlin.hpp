@@ -74,6 +74,10 @@ class ProvingKey {
     // the key's message length (CTR and GCM: any value >= 1 the key was synthesized for).  digest: the caller is a _digest_ entry: the key must carry a
     // digest, h_in(s) are 32-byte SHA-256 states (null: the initial value) and every proof states (H_in, H_out) behind its key tag; every other caller passes false and a
     // digest key is refused, for its proofs carry two states the caller has no argument for.  A key with key-tag blocks is taken as it is.
+    // mask(s): the caller is a _reveal_ entry: the key must have been synthesized with reveal = 1, and every proof states (mask, revealed) last of all; a
+    // witness or batch mask is ceil(L / 8) bytes per proof, a chunked job's ONE mask of ceil(len / 8) bytes over the whole job, chunk j proven under its slice
+    // (statement.hpp); a bit at or beyond the length is std::invalid_argument.  Every caller without a mask is refused a reveal key.  revealed_or_null receives
+    // reveal_bytes(message, mask) per proof (n x L) or for the whole job (len)
     // zk_seed of a lone proof: a 32-byte StdRng seed, or nullptr for ark_std::test_rng()'s (what simpleworks::marlin::generate_rand() returns).  zk_seed of a batch or a
     // chunked job: proof i draws from StdRng(Blake2s(seed || (index_offset + i) as u64 LE)), so callers that split one job over several calls / ranks pass the job-global
     // index of their first proof and reuse one seed; nullptr = the reference's fixed test_rng seed for EVERY proof (byte-parity mode for tests; NOT zero-knowledge across
@@ -83,7 +87,8 @@ class ProvingKey {
     enum : int { ANY_AES_KIND = -1 };
     static constexpr size_t KEY_AAD = ~(size_t)0;
     // witness generation only (the trace kernels + witness_expand): z = padded instance || witness, one byte per variable
-    std::vector<uint8_t> witness(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len = KEY_AAD, const uint8_t *h_in_or_null = nullptr);
+    std::vector<uint8_t> witness(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len = KEY_AAD, const uint8_t *h_in_or_null = nullptr,
+                                 const uint8_t *mask_or_null = nullptr);
     // one proof on context 0 (keys without a digest: a lone digest proof is a batch of one)
     Proof prove_lone(int kind, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, size_t aad_len, const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr,
                      uint8_t *tag_or_null = nullptr);
@@ -91,12 +96,13 @@ class ProvingKey {
     // ciphertexts (n x L), GCM tags (n x 16, GCM keys only) and every proof's H_out (n x 32, digest keys only)
     std::vector<Proof> prove_batch(int kind, bool digest, const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, const uint8_t *h_ins_or_null, size_t n, size_t n_contexts,
                                    const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertexts_or_null = nullptr, uint8_t *tags_or_null = nullptr,
-                                   uint8_t *h_outs_or_null = nullptr);
+                                   uint8_t *h_outs_or_null = nullptr, const uint8_t *masks_or_null = nullptr, uint8_t *revealed_or_null = nullptr);
     // len / L chunk-proofs of one ECB, CBC or CTR message under one key.  hdr = the header entering this call's first chunk; chunk j is proven under chunk_mode_header(j):
     // the public chaining value entering it (CBC), hdr + j x the key's blocks (CTR: a key for whole blocks; a job split over calls passes ctr_counter_add(icb, blocks
     // before)).  Over a chain key it is also proven under (states[j], states[j + 1]), states[0] = h_in; states_or_null receives the n + 1 states, ciphertext_or_null len bytes
     std::vector<Proof> prove_chunked(int kind, bool digest, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in_or_null, size_t n_contexts,
-                                     const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr, uint8_t *states_or_null = nullptr);
+                                     const uint8_t *zk_seed = nullptr, uint64_t index_offset = 0, uint8_t *ciphertext_or_null = nullptr, uint8_t *states_or_null = nullptr,
+                                     const uint8_t *mask_or_null = nullptr, uint8_t *revealed_or_null = nullptr);
     Proof prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed);
     // ---- GCM segments (keys of kind CIRCUIT_AES_GCM_SEG only, from synthesize_keys_gcm_segment; every call above refuses such a key, and the GCM calls name the segment
     // entries).  header = the segment proof's TRS_HDR_BYTES(A) bytes (trace_layout.h): iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad
@@ -136,7 +142,7 @@ class ProvingKey {
 // Without the flag the tables are built when memory allows (hipMemGetInfo) and silently skipped otherwise.
 enum : unsigned { KEY_NO_TABLES = 1u };
 std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128,
-                                            size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, digest_kind: 0, 1 or 2 (circuit.hpp DigestKind), the AES kinds only)
+                                            size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, digest_kind: 0, 1 or 2 (circuit.hpp DigestKind), reveal: 0 or 1, the AES kinds only)
 // A GCM segment key: role = 0 head, 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); aad_len: head only.  No key tag, no digest
 std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags = 0);
 // Segments [first_segment, first_segment + count) of ONE GCM record of len bytes as segment-proofs: n = ceil(ceil(len / 16) / c) >= 2 segments, c = the head key's data

@@ -1,10 +1,13 @@
 // csrc/statement.hpp -- what a proof states, in one place, for the prover (marlin.cpp) and the verifiers (capi_host.cpp).  Host only, no device header.
 // Every mode is "message, key, a public header of mode_header_bytes(c) bytes, optionally H_in": nothing (ECB), the iv (CBC), the initial counter block (CTR), iv then aad
-// (GCM).  The public input behind the leading One is the header's bits, the ciphertext's, GCM's tag, the key tag, then H_in and H_out -- each byte LSB first.  The prover
+// (GCM).  The public input behind the leading One is the header's bits, the ciphertext's, GCM's tag, the key tag, then H_in and H_out, then a reveal key's mask and
+// revealed bytes -- each byte LSB first.  The prover
 // and the verifier must agree on all of it bit for bit, so neither side has a copy of its own (tests/statement_host_check.cpp).
 #pragma once
 #include <cstring>
 #include <initializer_list>
+#include <stdexcept>
+#include <string>
 #include "circuit.hpp"
 #include "marlin.hpp"
 
@@ -28,7 +31,31 @@ inline void host_encrypt(const Circuit &c, const uint8_t *msg, size_t len, const
     else aes128_gcm_encrypt_host(msg, len, key, hdr, hdr + 12, c.aad_bytes, ct, tag_or_null ? tag_or_null : tag, c.key_bytes);
 }
 
-// The public input without the leading One: the bits of every part in order; a part without bytes (no aad, no key tag, no states) adds nothing
+// ---- selective disclosure.  A mask over L bytes is ceil(L / 8) bytes, bit i = bit i % 8 of byte i / 8; a reveal key's public input ends in the mask's
+// bits, then revealed's
+inline size_t mask_bytes(size_t len) { return (len + 7) / 8; }
+// the mask of chunk j of a chunked job under ONE mask over the whole job: chunk boundaries are multiples of 16 bytes, so every slice begins on a mask byte (a lone
+// proof, j = 0, takes any length)
+inline const uint8_t *chunk_mask_slice(const uint8_t *mask, size_t j, size_t chunk_bytes) { return mask + chunk_bytes * j / 8; }
+// revealed[i] = mask_i ? msg[i] : 0
+inline void reveal_bytes(const uint8_t *msg, const uint8_t *mask, size_t len, uint8_t *out) {
+    for (size_t i = 0; i < len; i++) out[i] = ((mask[i / 8] >> (i % 8)) & 1) ? msg[i] : 0;
+}
+// what both sides refuse as an argument, not as a proof: no mask, a mask bit at or beyond the length -- and, on the verifier's side, a non-zero revealed byte whose mask
+// bit is 0, which a verifier that ignored it would let a caller believe proven
+inline void require_mask(const uint8_t *mask, size_t len) {
+    if (!mask) throw std::invalid_argument("reveal: no mask");
+    for (size_t i = len; i < 8 * mask_bytes(len); i++)
+        if ((mask[i / 8] >> (i % 8)) & 1) throw std::invalid_argument("reveal: the mask has a bit set at or beyond the message length");
+}
+inline void require_revealed(const uint8_t *mask, const uint8_t *revealed, size_t len) {
+    require_mask(mask, len);
+    if (!revealed) throw std::invalid_argument("reveal: no revealed bytes");
+    for (size_t i = 0; i < len; i++)
+        if (revealed[i] && !((mask[i / 8] >> (i % 8)) & 1)) throw std::invalid_argument("reveal: revealed byte " + std::to_string(i) + " is non-zero but its mask bit is 0");
+}
+
+// The public input without the leading One: the bits of every part in order; a part without bytes (no aad, no key tag, no states, no mask) adds nothing
 struct PublicPart { const uint8_t *bytes; size_t len; };
 inline std::vector<Fr> public_input_of(std::initializer_list<PublicPart> parts) {
     std::vector<Fr> pub;

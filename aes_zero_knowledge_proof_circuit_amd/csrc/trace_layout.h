@@ -180,6 +180,24 @@ static_assert(TRD_RND == 1152 && TRD_FF == 3968 && TRD_SLOT_STRIDE == 4032 && TR
 static_assert(TRD(TRK_ECB_BYTES(6, 1)) == TRK_ECB_BYTES(6, 1) + 8 && TRD(TRK_CTR_BYTES(4, 2)) % 16 == 0 && TRD_BYTES(TRK_ECB_BYTES(8, 4), 1, 1) % 16 == 0, "the digest region begins and ends on a multiple of 16");
 static_assert(TRD_BLOCKS(1, 128) == 2 && TRD_BLOCKS(2, 55) == 1 && TRD_BLOCKS(2, 56) == 2 && TRD_BLOCKS(2, 17) == 1 && TRD_BLOCKS(0, 64) == 0, "compressions per proof");
 
+// ---- selective disclosure: a key synthesized with the reveal flag R = 1 also proves revealed[i] = mask_i ? M[i] : 0 for a public mask chosen per proof.
+// The reveal region lies BEHIND the digest region, so no offset above moves: `bytes` = the trace length with tag slots and digest region (TRD_BYTES), TRV(bytes) = that
+// length rounded up to 16 is the region's base rv, and with R = 0 a trace is what it was.  For a message of L bytes:
+//   rv + 0                 the mask, ceil(L / 8) bytes: bit i of the mask is bit i % 8 of byte i / 8; zero-padded to a multiple of 16
+//   rv + TRV_REVEALED(L)   revealed, L bytes; zero-padded to a multiple of 16
+#define TRV(bytes) (((bytes) + 15) / 16 * 16)
+#define TRV_MASK 0
+#define TRV_MASK_BYTES(L) (((L) + 7) / 8)
+#define TRV_REVEALED(L) ((TRV_MASK_BYTES(L) + 15) / 16 * 16)
+#define TRV_REGION_BYTES(L) (TRV_REVEALED(L) + ((L) + 15) / 16 * 16)
+#define TRV_BYTES(bytes, R, L) ((R) ? TRV(bytes) + TRV_REGION_BYTES(L) : (bytes))
+static_assert(TRV_BYTES(TRK_ECB_BYTES(4, 1), 0, 16) == TR_BLOCK0 + TR_BLOCK_STRIDE && TRV_BYTES(TRD_BYTES(TRK_KT_BYTES(8, TRK_CTR_BYTES(8, 2), 2), 2, 1), 0, 17) == TRD_BYTES(TRK_KT_BYTES(8, TRK_CTR_BYTES(8, 2), 2), 2, 1) &&
+              TRV_BYTES(TRK_GCM_BYTES(6, 1, 2), 0, 17) == TRK_GCM_BYTES(6, 1, 2), "without reveal a trace keeps its length");
+static_assert(TRV(TRK_ECB_BYTES(4, 1)) == TRK_ECB_BYTES(4, 1) && TRV(TRK_ECB_BYTES(6, 1)) == TRK_ECB_BYTES(6, 1) + 8 && TRV(TRK_ECB_BYTES(8, 2)) == TRK_ECB_BYTES(8, 2) + 8 && TRV(TRK_CTR_BYTES(6, 2)) % 16 == 0 &&
+              TRV(TRK_CTR_BYTES(8, 1)) % 16 == 0, "the reveal region begins on a multiple of 16 for nk = 4, 6, 8");
+static_assert(TRV_MASK_BYTES(1) == 1 && TRV_MASK_BYTES(17) == 3 && TRV_REVEALED(1) == 16 && TRV_REVEALED(128) == 16 && TRV_REVEALED(129) == 32 && TRV_REGION_BYTES(1) == 32 && TRV_REGION_BYTES(17) == 48 &&
+              TRV_REGION_BYTES(64) == 80 && TRV_BYTES(TRK_ECB_BYTES(6, 1), 1, 16) % 16 == 0, "mask and revealed are each zero-padded to a multiple of 16");
+
 // ---- GCM segments: a record longer than one proof is n >= 2 segment-proofs, role head / mid / tail.  A segment key's trace keeps the GCM tail's inner
 // layout (the TR_GCM_* offsets) behind its AES slots -- the nb data blocks, then H, then (tail only) J_0 -- with these differences: the four bytes behind the iv hold
 // ctr0, big-endian, the 32-bit counter of the segment's first data block; only a head has aad (na = 0 otherwise); the multiplications are na + nb (head), nb (mid),

@@ -341,6 +341,57 @@ int zkaes_verify_digest_chunked(const zkaes_vk *vk, int circuit_kind, const uint
 /* host only: zkaes_verify_encryption_gcm_kt (key_tag NULL and key_tag_len 0 for a key without tag blocks) with h_in (NULL = the initial value) and h_out behind it */
 int zkaes_verify_encryption_gcm_digest(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext,
                                        size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *key_tag, size_t key_tag_len, const uint8_t *h_in, const uint8_t h_out[32], int *accepted);
+/* ---- selective disclosure.
+ * Every statement above keeps the whole message hidden.  A key synthesized with reveal = 1 (reveal = 0 = every key above: nothing changes) proves, beside its mode's
+ * statement, its key tag and its digest, for a message M of L bytes
+ *     revealed[i] = mask_i ? M[i] : 0,   i < L
+ * and exposes, as the LAST 8 ceil(L / 8) + 8 L public-input bits, the mask (ceil(L / 8) bytes; mask_i = bit i % 8 of byte i / 8; the bits at or beyond L must be zero) and
+ * then revealed (L bytes), bytes as 8 LSB-first bits as everywhere.  The mask is public INPUT chosen per proof -- one key serves every mask -- and revealed is public
+ * OUTPUT.  A chunked job takes ONE mask over the whole job; chunk boundaries are multiples of 16 bytes, so chunk j is proven under mask bytes [chunk j / 8, chunk (j + 1) / 8).
+ * What it leaks: in CTR and GCM a revealed byte gives away that keystream byte, as any known plaintext does; the mask itself is public; a hidden byte and a revealed zero
+ * byte are told apart by the mask, not by revealed.  Every mode, key size, key-tag count and digest kind has a reveal form; GCM segment keys and the ops kinds have none.
+ * Every proving and witness entry above refuses a reveal key and names the entries below; the entries below refuse a key without reveal. */
+/* as zkaes_synthesize_keys_pd with reveal = 0 or 1 (at 0 the same key) */
+int zkaes_synthesize_keys_rv(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, unsigned reveal, size_t plaintext_length,
+                             size_t aad_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero, unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* host only: zkaes_circuit_info_pd / zkaes_circuit_matrix_pd with the reveal flag; at reveal 0 they return what those return */
+int zkaes_circuit_info_rv(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, unsigned reveal, size_t plaintext_length,
+                          size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_rv(int circuit_kind, unsigned key_bits, unsigned key_tag_blocks, unsigned digest_kind, uint64_t digest_prefix, unsigned reveal, size_t plaintext_length,
+                            size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+/* out = {reveal flag, message bytes L, mask bytes ceil(L / 8), offset of the reveal region in a trace}; all zero for a key without reveal */
+int zkaes_pk_reveal_info(const zkaes_pk *pk, uint64_t out[4]);
+/* host only: out (len bytes) = revealed for (msg, mask); mask_len must be ceil(len / 8) and no mask bit at or beyond len may be set */
+int zkaes_reveal_bytes(const uint8_t *msg, size_t len, const uint8_t *mask, size_t mask_len, uint8_t *out);
+/* witness generation only, for a reveal key of any mode: hdr and h_in as zkaes_aes_witness_pd (h_in is read by a key with a digest only), mask = ceil(len / 8) bytes */
+int zkaes_aes_witness_rv(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *secret_key, const uint8_t *hdr, const uint8_t *h_in, const uint8_t *mask, size_t mask_len,
+                         uint8_t *z, size_t z_cap, size_t *z_len);
+/* n independent proofs over a reveal key of any mode: messages, secret_keys, headers, h_ins as zkaes_encrypt_digest_batch_seeded_at (h_ins is read by a key with a digest
+ * only), masks = n x ceil(L / 8) bytes.  Receives, where the pointer is not NULL, the ciphertexts, the GCM tags (GCM keys only), every proof's H_out (keys with a digest
+ * only) and every proof's revealed bytes (n x L) */
+int zkaes_encrypt_reveal_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers, size_t headers_len,
+                                         const uint8_t *h_ins, const uint8_t *masks, size_t masks_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
+                                         uint8_t *ciphertexts_or_null, uint8_t *tags_or_null, uint8_t *h_outs_or_null, uint8_t *revealed_or_null, uint8_t **proofs, size_t *proofs_len,
+                                         size_t *proof_lens);
+/* the chunk-proofs of one ECB, CBC or CTR message over a reveal key, ONE mask of ceil(len / 8) bytes over this call's message: hdr, h_in, states_or_null (a chain key
+ * only) as zkaes_encrypt_digest_chunked_seeded_at; revealed_or_null receives len bytes.  A job split over calls passes each call its part of the message and of the mask */
+int zkaes_encrypt_reveal_chunked_seeded_at(const uint8_t *msg, size_t len, const uint8_t *secret_key, const uint8_t *hdr, const uint8_t *h_in, const uint8_t *mask, size_t mask_len,
+                                           const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t *ciphertext_or_null, uint8_t *states_or_null,
+                                           uint8_t *revealed_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens, size_t n_chunks);
+/* host only: the chunk-proofs of one ECB, CBC or CTR job over a reveal key.  Chunk j's public input is what zkaes_verify_digest_chunked derives for it (key_tag NULL / 0
+ * for a key without tag blocks, states NULL for a key without a digest), then its slice of mask (ceil(ciphertext_len / 8) bytes over the whole job) and of revealed
+ * (ciphertext_len bytes).  n_chunks = 1 is the lone-proof form.  A mask bit at or beyond the length, or a non-zero revealed byte whose mask bit is 0, is an ERROR of the
+ * call, not a rejection: ignoring such a byte would let a caller believe it proven */
+int zkaes_verify_reveal_chunked(const zkaes_vk *vk, int circuit_kind, const uint8_t *proofs, const size_t *proof_lens, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ciphertext,
+                                size_t ciphertext_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *states, const uint8_t *mask, size_t mask_len, const uint8_t *revealed,
+                                int *accepted_each, size_t *n_accepted);
+/* host only: zkaes_verify_encryption_gcm_digest (h_out NULL for a key without a digest) with mask and revealed behind it; the same two errors */
+int zkaes_verify_encryption_gcm_reveal(const zkaes_vk *vk, const uint8_t *proof, size_t proof_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext,
+                                       size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *key_tag, size_t key_tag_len, const uint8_t *h_in, const uint8_t *h_out,
+                                       const uint8_t *mask, size_t mask_len, const uint8_t *revealed, int *accepted);
+/* host only: zkaes_chunk_public_inputs for a reveal key: every row ends in the chunk's slice of mask and of revealed; the same two errors */
+int zkaes_chunk_public_inputs_rv(int circuit_kind, size_t n_chunks, const uint8_t *iv_or_icb, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t *key_tag, size_t key_tag_len,
+                                 const uint8_t *states, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, uint8_t *out_bits, size_t *n_bits);
 /* ---- GCM records longer than one proof: segment-proofs --------------------------------------------------
  * A record (iv, aad, ciphertext, tag) of L bytes whose ceil(L / 16) data blocks do not fit one proof is proven as n = ceil(ceil(L / 16) / c) >= 2 segment-proofs, c data
  * blocks each, the last with Lt = L - 16 c (n - 1) bytes.  Three roles, each with its own key: role 0 = head (fixed by c and A, the whole aad), 1 = mid (c), 2 = tail

@@ -129,6 +129,34 @@ extern "C" {
                                    ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize, states: *const u8, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
     fn zkaes_verify_encryption_gcm_digest(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
                                           ciphertext_len: usize, tag16: *const u8, key_tag: *const u8, key_tag_len: usize, h_in: *const u8, h_out: *const u8, accepted: *mut c_int) -> c_int;
+    // selective disclosure (include/zkaes.h, section "selective disclosure"; declarations only, no wrappers yet, and not compiled: no cargo in the build image).  reveal: 0 or 1;
+    // a mask over L bytes is ceil(L / 8) bytes, bit i = bit i % 8 of byte i / 8; revealed is L bytes
+    fn zkaes_synthesize_keys_rv(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, digest_kind: c_uint, digest_prefix: u64, reveal: c_uint, plaintext_length: usize,
+                                aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize, srs_num_non_zero: usize, flags: c_uint, pk: *mut *mut zkaes_pk,
+                                vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_circuit_info_rv(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, digest_kind: c_uint, digest_prefix: u64, reveal: c_uint, plaintext_length: usize,
+                             aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_rv(circuit_kind: c_int, key_bits: c_uint, key_tag_blocks: c_uint, digest_kind: c_uint, digest_prefix: u64, reveal: c_uint, plaintext_length: usize,
+                               aad_length: usize, which: c_int, n_rows: *mut u64, nnz: *mut u64, rowptr: *mut u32, col: *mut u32, coeff: *mut i64) -> c_int;
+    fn zkaes_pk_reveal_info(pk: *const zkaes_pk, out: *mut u64) -> c_int;
+    fn zkaes_reveal_bytes(msg: *const u8, len: usize, mask: *const u8, mask_len: usize, out: *mut u8) -> c_int;
+    fn zkaes_aes_witness_rv(pk: *const zkaes_pk, msg: *const u8, len: usize, secret_key: *const u8, hdr: *const u8, h_in: *const u8, mask: *const u8, mask_len: usize, z: *mut u8,
+                            z_cap: usize, z_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_reveal_batch_seeded_at(n: usize, messages: *const u8, messages_len: usize, secret_keys: *const u8, secret_keys_len: usize, headers: *const u8, headers_len: usize,
+                                            h_ins: *const u8, masks: *const u8, masks_len: usize, pk: *const zkaes_pk, zk_seed32: *const u8, first_proof_index: u64,
+                                            ciphertexts_or_null: *mut u8, tags_or_null: *mut u8, h_outs_or_null: *mut u8, revealed_or_null: *mut u8, proofs: *mut *mut u8,
+                                            proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_encrypt_reveal_chunked_seeded_at(msg: *const u8, len: usize, secret_key: *const u8, hdr: *const u8, h_in: *const u8, mask: *const u8, mask_len: usize, pk: *const zkaes_pk,
+                                              zk_seed32: *const u8, first_proof_index: u64, ciphertext_or_null: *mut u8, states_or_null: *mut u8, revealed_or_null: *mut u8,
+                                              proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize, n_chunks: usize) -> c_int;
+    fn zkaes_verify_reveal_chunked(vk: *const zkaes_vk, circuit_kind: c_int, proofs: *const u8, proof_lens: *const usize, n_chunks: usize, iv_or_icb: *const u8, ciphertext: *const u8,
+                                   ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize, states: *const u8, mask: *const u8, mask_len: usize, revealed: *const u8,
+                                   accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    fn zkaes_verify_encryption_gcm_reveal(vk: *const zkaes_vk, proof: *const u8, proof_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8,
+                                          ciphertext_len: usize, tag16: *const u8, key_tag: *const u8, key_tag_len: usize, h_in: *const u8, h_out: *const u8, mask: *const u8,
+                                          mask_len: usize, revealed: *const u8, accepted: *mut c_int) -> c_int;
+    fn zkaes_chunk_public_inputs_rv(circuit_kind: c_int, n_chunks: usize, iv_or_icb: *const u8, ciphertext: *const u8, ciphertext_len: usize, key_tag: *const u8, key_tag_len: usize,
+                                    states: *const u8, mask: *const u8, mask_len: usize, revealed: *const u8, out_bits: *mut u8, n_bits: *mut usize) -> c_int;
     // GCM records longer than one proof (include/zkaes.h, section "segment-proofs"; declarations only, no wrappers yet, and not compiled: no cargo in the build image).  role: 0 head,
     // 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); a commitment is 32 bytes, a Y and a salt 16; a segment header is 80 + A bytes
     fn zkaes_synthesize_keys_gcm_seg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize, srs_num_non_zero: usize,
