@@ -474,10 +474,36 @@ class ProvingKey:
             return None
         return {"role": ("head", "mid", "tail")[out[0] - 1], "blocks": int(out[1]), "message_bytes": int(out[2]), "aad_bytes": int(out[3])}
 
-    def witness_gcm_segment(self, message, secret_key, header):
-        """z (padded instance + witness, one byte per variable) of a segment key; header = gcm_segment_header(...)"""
+    def witness_gcm_segment(self, message, secret_key, header, mask=None):
+        """z (padded instance + witness, one byte per variable) of a segment key; header = gcm_segment_header(...).  mask (a reveal segment key): the
+        segment's own mask, bytes of ceil(len(message) / 8) or byte indices / ranges (reveal_mask) -- or a header made with gcm_segment_header(..., mask=), which ends in it"""
         self._need_key(secret_key)
-        return self._witness(lib().zkaes_aes_witness_gcm_seg, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(header), C.c_size_t(len(header)))
+        info = self.segment_info()
+        if mask is None and info is not None and self.reveal_info()["reveal"] and len(header) > 80 + info["aad_bytes"]:
+            header, mask = bytes(header)[:80 + info["aad_bytes"]], bytes(header)[80 + info["aad_bytes"]:]
+        if mask is None:
+            return self._witness(lib().zkaes_aes_witness_gcm_seg, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(header), C.c_size_t(len(header)))
+        m = reveal_mask(mask, len(message))
+        return self._witness(lib().zkaes_aes_witness_gcm_seg_rv, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(header), C.c_size_t(len(header)), m, C.c_size_t(len(m)))
+
+    def encrypt_gcm_segment_reveal_batch(self, messages, secret_keys, headers, masks, zk_seed=None, first_proof_index=0):
+        """encrypt_gcm_segment_batch over a reveal segment key -> (revealed, proofs), two lists.  masks: one per message, the segment's own mask as bytes
+        of ceil(len / 8) or byte indices / ranges (reveal_mask); headers as encrypt_gcm_segment_batch (80 + A bytes each, without a mask)"""
+        n = len(messages)
+        if not len(secret_keys) == len(headers) == len(masks) == n:
+            raise ZkAesError("one secret key, one header and one mask per message")
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        mb, kb, hb = b"".join(bytes(m) for m in messages), b"".join(bytes(k) for k in secret_keys), b"".join(bytes(h) for h in headers)
+        mk = b"".join(reveal_mask(masks[i], len(messages[i])) for i in range(n))
+        rev = C.create_string_buffer(max(len(mb), 1))
+        lens = (C.c_size_t * max(n, 1))()
+        out, total = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_gcm_segment_reveal_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), mk, C.c_size_t(len(mk)), self._p,
+                                                                      seed, C.c_uint64(first_proof_index), rev, C.byref(out), C.byref(total), lens))
+        size = len(mb) // n if n else 0
+        return [rev.raw[size * i:size * (i + 1)] for i in range(n)], _split(_take(out, total), lens, n)
 
     def encrypt_gcm_segment_batch(self, messages, secret_keys, headers, zk_seed=None, first_proof_index=0):
         """n independent proofs over this segment key, each under its own gcm_segment_header -> the proofs; the caller answers for what the headers say
@@ -1032,6 +1058,7 @@ SEG_HEAD, SEG_MID, SEG_TAIL = 0, 1, 2
 _SEG_ROLES = {"head": SEG_HEAD, "mid": SEG_MID, "tail": SEG_TAIL, SEG_HEAD: SEG_HEAD, SEG_MID: SEG_MID, SEG_TAIL: SEG_TAIL}
 # the largest c (data blocks per segment) at which all three roles stay inside the default SRS literal, per key size (tests/test_gcm_segments_host.py)
 GCM_SEGMENT_DEFAULT_C = {128: 4, 192: 3, 256: 2}
+GCM_SEGMENT_REVEAL_DEFAULT_C = dict(GCM_SEGMENT_DEFAULT_C)      # reveal segment keys fit the same c (the capacity table; tests/test_gcm_segments_reveal_host.py asserts it)
 
 
 def verify_encryption_gcm_reveal(verifying_key, proof, iv, aad, ciphertext, tag, mask, revealed, key_tag=None, h_out=None, h_in=None):
@@ -1057,38 +1084,42 @@ def _seg_role(role):
     return _SEG_ROLES[role]
 
 
-def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128):
+def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, reveal=False):
     """(ProvingKey, VerifyingKey) of one segment role.  role: "head", "mid" or "tail"; units: c, the data blocks per segment, for a head or mid, and Lt, the bytes of
-    the record's last segment (1 .. 16 c), for a tail; aad_length: the record's whole aad, head only.  flags and key_bits as synthesize_keys; no key tag, no digest"""
+    the record's last segment (1 .. 16 c), for a tail; aad_length: the record's whole aad, head only.  flags and key_bits as synthesize_keys; no key tag, no digest.
+    reveal: False (the default) or True: every proof of the key also exposes the segment's slice of the record's mask and of its revealed bytes, is made through
+    encrypt_gcm_segments(..., mask=) and checked with verify_gcm_segments(..., mask=, revealed=)"""
     pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib().zkaes_synthesize_keys_gcm_seg(_seg_role(role), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]),
-                                               C.c_uint(flags), C.byref(pk), C.byref(vk)))
+    _check(lib().zkaes_synthesize_keys_gcm_seg_rv(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), C.c_size_t(srs[0]),
+                                                  C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
     return ProvingKey(pk.value), VerifyingKey(vk.value)
 
 
-def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128):
+def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128, reveal=False):
     out = (C.c_uint64 * 12)()
-    _check(lib().zkaes_circuit_info_gcm_seg(_seg_role(role), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), out))
+    _check(lib().zkaes_circuit_info_gcm_seg_rv(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128):
+def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128, reveal=False):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    head = (_seg_role(role), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), which)
-    _check(lib().zkaes_circuit_matrix_gcm_seg(*head, C.byref(rows), C.byref(nnz), None, None, None))
+    head = (_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), which)
+    _check(lib().zkaes_circuit_matrix_gcm_seg_rv(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
     coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-    _check(lib().zkaes_circuit_matrix_gcm_seg(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
+    _check(lib().zkaes_circuit_matrix_gcm_seg_rv(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 
-def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128):
+def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128, reveal=False):
     """how a record of `length` bytes splits into segments of c data blocks (None = GCM_SEGMENT_DEFAULT_C[key_bits]) -> {"n", "c", "aad", "tail_bytes", "segments"};
-    a segment is {"role", "offset", "bytes", "ctr0"}.  The keys the record needs: head (c, aad_length), mid (c) when n > 2, tail (tail_bytes)"""
+    a segment is {"role", "offset", "bytes", "ctr0"}.  The keys the record needs: head (c, aad_length), mid (c) when n > 2, tail (tail_bytes).  reveal: the plan for
+    reveal segment keys: the default c is GCM_SEGMENT_REVEAL_DEFAULT_C[key_bits] -- equal to the plain one, the capacity table of 9j has the room -- and
+    every segment also carries "mask_offset" and "mask_bytes", its slice of the record's mask"""
     if c is None:
-        c = GCM_SEGMENT_DEFAULT_C[key_bits]
+        c = (GCM_SEGMENT_REVEAL_DEFAULT_C if reveal else GCM_SEGMENT_DEFAULT_C)[key_bits]
     if c < 1 or not 1 <= length <= 1 << 20 or not 0 <= aad_length <= 1 << 16:
         raise ZkAesError("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block")
     nb = (length + 15) // 16
@@ -1096,6 +1127,9 @@ def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128):
     if n < 2:
         raise ZkAesError("GCM segments: this record fits one segment; a record that fits one proof goes through synthesize_keys_gcm")
     segs = [{"role": "head" if s == 0 else "tail" if s == n - 1 else "mid", "offset": 16 * c * s, "bytes": min(16 * c, length - 16 * c * s), "ctr0": 2 + s * c} for s in range(n)]
+    if reveal:
+        for seg in segs:
+            seg["mask_offset"], seg["mask_bytes"] = seg["offset"] // 8, (seg["bytes"] + 7) // 8
     return {"n": n, "c": c, "aad": aad_length, "tail_bytes": segs[-1]["bytes"], "segments": segs}
 
 
@@ -1124,8 +1158,9 @@ def gcm_length_block(aad_length, length):
     return (8 * aad_length).to_bytes(8, "big") + (8 * length).to_bytes(8, "big")
 
 
-def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_block=None, aad=b""):
-    """the 80 + A bytes a segment witness takes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad; a field the role does not use may stay None"""
+def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_block=None, aad=b"", mask=None):
+    """the 80 + A bytes a segment witness takes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad; a field the role does not use may stay None.  mask (a
+    reveal segment key): the segment's own mask as bytes of ceil(len / 8), appended last: the 80 + A + ceil(len / 8) bytes of a reveal segment proof's header"""
     if len(iv) != 12:
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
     parts = [bytes(iv), int(ctr0).to_bytes(4, "big")]
@@ -1134,14 +1169,15 @@ def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_
         if len(field) != 16:
             raise ZkAesError("Y_in, the salts and the length block are 16 bytes each")
         parts.append(field)
-    return b"".join(parts) + bytes(aad)
+    return b"".join(parts) + bytes(aad) + (b"" if mask is None else bytes(mask))
 
 
-def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_segment=0, count=None, zk_seed=None):
+def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_segment=0, count=None, zk_seed=None, mask=None):
     """segments [first_segment, first_segment + count) of one record as segment-proofs -> (ciphertext, tag, commitments, proofs): the WHOLE record's ciphertext and tag,
     its n - 1 commitments (32 bytes each) and the call's proofs.  keys = (head, mid or None, tail) proving keys; count None = to the record's end; salts = n - 1 strings
     of 16 bytes or None for os.urandom (a job split over calls passes them: every call must make the same commitments); zk_seed as encrypt_batch, segment s drawing at
-    index s whichever call proves it"""
+    index s whichever call proves it.  mask (three reveal segment keys): ONE mask over the whole record, bytes of ceil(len(message) / 8) or byte indices /
+    ranges (reveal_mask); the call then returns (ciphertext, tag, commitments, revealed, proofs), revealed = reveal_bytes(message, mask) for the whole record"""
     head, mid, tail = keys
     _gcm_args(secret_key, iv, head.key_bytes())
     info = head.segment_info()
@@ -1161,16 +1197,24 @@ def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_s
     ct, tag, coms = C.create_string_buffer(len(message)), C.create_string_buffer(16), C.create_string_buffer(32 * (n - 1))
     lens = (C.c_size_t * max(count, 1))()
     out, total = C.c_void_p(), C.c_size_t()
+    if mask is not None:
+        m, rev = reveal_mask(mask, len(message)), C.create_string_buffer(len(message))
+        _check(lib().zkaes_encrypt_gcm_segments_reveal_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), head._p,
+                                                                 None if mid is None else mid._p, tail._p, b"".join(bytes(s) for s in salts), m, C.c_size_t(len(m)), seed, C.c_size_t(first_segment),
+                                                                 C.c_size_t(count), ct, tag, coms, rev, C.byref(out), C.byref(total), lens))
+        return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], rev.raw[:len(message)], _split(_take(out, total), lens, count)
     _check(lib().zkaes_encrypt_gcm_segments_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), head._p,
                                                       None if mid is None else mid._p, tail._p, b"".join(bytes(s) for s in salts), seed, C.c_size_t(first_segment), C.c_size_t(count), ct, tag,
                                                       coms, C.byref(out), C.byref(total), lens))
     return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], _split(_take(out, total), lens, count)
 
 
-def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c):
+def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None):
     """the n segment-proofs of one record against ONE list of n - 1 commitments -> a list of n bools.  vks = (head, mid or None, tail) verifying keys; c = the data
     blocks per segment.  The verifier sets every segment's ctr0 = 2 + s c, cuts the ciphertext, builds the length block from the lengths it sees and hands the tag to
-    the tail alone; lengths that do not fit the keys, the proof count or the commitment count raise"""
+    the tail alone; lengths that do not fit the keys, the proof count or the commitment count raise.  mask and revealed (proofs of reveal segment keys):
+    ONE mask over the record (reveal_mask) and its len(ciphertext) revealed bytes, both or neither; a mask bit at or beyond the length, or a non-zero revealed byte whose
+    mask bit is 0, raises"""
     if len(iv) != 12:
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
     if len(tag) != 16:
@@ -1182,6 +1226,14 @@ def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c):
     lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
     each, ok = (C.c_int * max(n, 1))(), C.c_size_t()
     coms = b"".join(bytes(x) for x in commitments)
+    if (mask is None) != (revealed is None):
+        raise ZkAesError("verify_gcm_segments: mask and revealed go together")
+    if mask is not None:
+        m = reveal_mask(mask, len(ciphertext))
+        _check(lib().zkaes_verify_gcm_segments_reveal(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv),
+                                                      bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), m,
+                                                      C.c_size_t(len(m)), bytes(revealed), C.c_size_t(len(revealed)), each, C.byref(ok)))
+        return [bool(each[i]) for i in range(n)]
     _check(lib().zkaes_verify_gcm_segments(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad),
                                            C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), each, C.byref(ok)))
     return [bool(each[i]) for i in range(n)]

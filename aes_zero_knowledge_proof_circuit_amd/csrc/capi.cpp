@@ -312,6 +312,48 @@ int zkaes_encrypt_gcm_segments_seeded_at(const uint8_t *msg, size_t len, const u
                                            zk_seed32, ciphertext_or_null, tag_or_null, commitments_or_null), proofs, proofs_len, proof_lens);
     });
 }
+// -- selective disclosure on segments: the entries above with a mask; they take keys of zkaes_synthesize_keys_gcm_seg_rv with reveal = 1 only, and the
+// entries above refuse such keys
+int zkaes_synthesize_keys_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return guard([&] {
+        const unsigned f = key_flags(flags);
+        if (reveal > 1) throw std::invalid_argument("synthesize_keys: reveal must be 0 or 1");
+        give_keys(zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs_literals(nc, nv, nnz), f, (int)reveal), pk, vk);
+    });
+}
+int zkaes_aes_witness_gcm_seg_rv(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, const uint8_t *mask, size_t mask_len,
+                                 uint8_t *z, size_t z_cap, size_t *z_len) {
+    return guard([&] {
+        if (!pk || !mask) throw std::invalid_argument("null argument");
+        give_witness(pk->pk->aes_witness_gcm_segment(msg, len, key, header, header_len, mask, mask_len), z, z_cap, z_len);
+    });
+}
+int zkaes_encrypt_gcm_segment_reveal_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers,
+                                                     size_t headers_len, const uint8_t *masks, size_t masks_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
+                                                     uint8_t *revealed_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len || !masks) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (c.kind != zk::CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("the key is not a GCM segment key: the segment _reveal_ entry points take keys of zkaes_synthesize_keys_gcm_seg_rv (other reveal keys go through zkaes_encrypt_reveal_batch_seeded_at)");
+        if (!c.reveal) throw std::invalid_argument("the key has no reveal region: the segment _reveal_ entry points take keys synthesized with reveal = 1 (zkaes_synthesize_keys_gcm_seg_rv)");
+        const size_t hb = zk::mode_header_bytes(c), mb = zk::reveal_mask_bytes(c);
+        require_packed(c, n, messages_len, secret_keys_len);
+        if (headers_len != n * hb) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad)");
+        if (masks_len != n * mb) throw std::invalid_argument("masks must hold n x " + std::to_string(mb) + " bytes (one bit per message byte of the segment)");
+        pack_proofs(pk->pk->prove_gcm_segment_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index, masks, revealed_or_null), proofs, proofs_len, proof_lens);
+    });
+}
+int zkaes_encrypt_gcm_segments_reveal_seeded_at(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const zkaes_pk *head,
+                                                const zkaes_pk *mid_or_null, const zkaes_pk *tail, const uint8_t *salts_or_null, const uint8_t *mask, size_t mask_len, const uint8_t *zk_seed32,
+                                                size_t first_segment, size_t count, uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t *commitments_or_null, uint8_t *revealed_or_null,
+                                                uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!head || !tail || !proofs || !proofs_len || !mask) throw std::invalid_argument("null argument");
+        if (mask_len != (len + 7) / 8) throw std::invalid_argument("ONE mask over the whole record: " + std::to_string((len + 7) / 8) + " bytes for this message");
+        pack_proofs(zk::prove_gcm_segments(head->pk.get(), mid_or_null ? mid_or_null->pk.get() : nullptr, tail->pk.get(), msg, len, key, iv, aad, aad_len, salts_or_null, first_segment, count,
+                                           zk_seed32, ciphertext_or_null, tag_or_null, commitments_or_null, mask, revealed_or_null), proofs, proofs_len, proof_lens);
+    });
+}
 // -- plaintext digests: every mode through one set of entries; hdr = the mode's public header, NULL for ECB
 int zkaes_aes_witness_pd(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {

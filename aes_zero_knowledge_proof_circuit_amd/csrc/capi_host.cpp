@@ -47,6 +47,57 @@ void verify_chunks(const zk::VerifyingKey &vk, int circuit_kind, const uint8_t *
         return zk::verify(vk, chunk_public_input(circuit_kind, j, chunk, iv_or_icb, ct, key_tag, key_tag_len, states, mask, revealed), p);
     });
 }
+// ---- GCM segments: segment s's public input, and the one body of zkaes_verify_gcm_segments and zkaes_verify_gcm_segments_reveal (described at the entries)
+std::vector<zk::Fr> gcm_segment_public_input(size_t s, size_t n, size_t c, size_t lt, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, const uint8_t lenblk[16],
+                                             const uint8_t tag[16], const uint8_t *commitments, const uint8_t *mask, const uint8_t *revealed) {
+    uint8_t hd[16];
+    memcpy(hd, iv, 12);
+    const uint32_t ctr0 = (uint32_t)(2 + s * c);
+    for (int i = 0; i < 4; i++) hd[12 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
+    const bool first = s == 0, last = s + 1 == n;
+    const size_t len = last ? lt : 16 * c;
+    return zk::public_input_of({{hd, 16}, {first ? aad : nullptr, aad_len}, {ct + 16 * c * s, len}, {last ? lenblk : nullptr, 16}, {last ? tag : nullptr, 16},
+                                {first ? nullptr : commitments + 32 * (s - 1), 32}, {last ? nullptr : commitments + 32 * s, 32},
+                                {mask ? zk::chunk_mask_slice(mask, s, 16 * c) : nullptr, zk::mask_bytes(len)}, {mask ? revealed + 16 * c * s : nullptr, len}});
+}
+void verify_gcm_segments(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                         const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
+                         bool reveal, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+    if (n_accepted) *n_accepted = 0;
+    if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+    if (!head || !tail || !proofs || !proof_lens || !iv || !ct || !tag || !commitments || (aad_len && !aad) || (reveal && (!mask || !revealed))) throw std::invalid_argument("null argument");
+    if (c == 0 || ct_len == 0 || ct_len > ((size_t)1 << 20) || aad_len > ((size_t)1 << 16)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block");
+    const size_t nb = (ct_len + 15) / 16, n = (nb + c - 1) / c;
+    if (n < 2) throw std::invalid_argument("GCM segments: this record fits one segment; a record that fits one proof is checked with zkaes_verify_encryption_gcm");
+    if (n_segments != n) throw std::invalid_argument("GCM segments: the record has " + std::to_string(n) + " segments of " + std::to_string(c) + " blocks");
+    if (commitments_len != 32 * (n - 1)) throw std::invalid_argument("GCM segments: one 32-byte commitment per boundary, " + std::to_string(32 * (n - 1)) + " bytes for this record");
+    if (n > 2 && !mid_or_null) throw std::invalid_argument("GCM segments: a record of more than two segments needs the mid key");
+    if (reveal) {
+        if (mask_len != zk::mask_bytes(ct_len)) throw std::invalid_argument(std::string(entry) + ": ONE mask over the whole record, " + std::to_string(zk::mask_bytes(ct_len)) + " bytes for this ciphertext");
+        if (revealed_len != ct_len) throw std::invalid_argument(std::string(entry) + ": ONE revealed array over the whole record, " + std::to_string(ct_len) + " bytes for this ciphertext");
+        zk::require_revealed(mask, revealed, ct_len);
+    }
+    const size_t lt = ct_len - 16 * c * (n - 1);
+    // the verifier zero-pads the public input, so the lengths are part of the statement (as require_gcm_lengths): a key that knows its exact count pins them -- and
+    // tells a reveal key from a plain one, whose count lacks the mask's and the revealed bytes' bits
+    auto exact = [&](const zk::VerifyingKey &vk, size_t bits, size_t len, const char *name) {
+        if (vk.num_public_inputs + 1 == vk.num_instance) return;
+        const size_t rv_bits = 8 * zk::mask_bytes(len) + 8 * len;
+        if (vk.num_public_inputs == bits + (reveal ? 0 : rv_bits))
+            throw std::invalid_argument(std::string("GCM segments: the ") + name + (reveal ? " key has no reveal region: zkaes_verify_gcm_segments_reveal takes keys synthesized with reveal = 1 (zkaes_verify_gcm_segments checks this one)"
+                                                                                           : " key reveals plaintext bytes: its proofs are checked with zkaes_verify_gcm_segments_reveal"));
+        if (vk.num_public_inputs != bits + (reveal ? rv_bits : 0)) throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths");
+    };
+    exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 16 * c, "head");
+    if (n > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, 16 * c, "mid");
+    exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, lt, "tail");
+    uint8_t lenblk[16];
+    for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); }
+    verify_each(proofs, proof_lens, n, accepted_each, n_accepted, [&](size_t s, const zk::Proof &p) {
+        return zk::verify(s == 0 ? head->vk : s + 1 == n ? tail->vk : mid_or_null->vk,
+                          gcm_segment_public_input(s, n, c, lt, iv, aad, aad_len, ct, lenblk, tag, commitments, reveal ? mask : nullptr, revealed), p);
+    });
+}
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
 // image of the struct: reading it back from untrusted bytes put arbitrary limbs into field elements and an arbitrary byte into a bool, and skipped the curve / subgroup
 // checks the ark path makes -- found while writing the fuzz target (tests/fuzz_host.cpp).  v2 goes through deserialize_vk_ark and inherits every check.
@@ -250,40 +301,24 @@ int zkaes_gcm_commit(const uint8_t *key, size_t key_len, const uint8_t y[16], co
 }
 // Segment s is checked against (iv, ctr0 = 2 + s c, its slice of the ciphertext) and its role's further inputs: the aad and commitments[0] (head), commitments[s - 1]
 // and commitments[s] (mid), the length block built from the aad and ciphertext lengths seen HERE, the tag and commitments[n - 2] (tail).  One array of n - 1 commitments
-// serves both sides of every boundary.  A segment whose proof bytes do not parse is a rejected segment, not an error of the call
+// serves both sides of every boundary.  A segment whose proof bytes do not parse is a rejected segment, not an error of the call.
+// With a mask (the _reveal entry) every segment's input ends in its slice of the record's ONE mask and of its revealed bytes, as a chunk's does
+// (chunk_public_input): head, mid and tail together state revealed[i] = mask_i ? M[i] : 0 over the whole record.  The two entries refuse each other's keys: where a key
+// carries its exact public-input count a proof of the other kind raises, otherwise it is rejected (its |X| or its index commitments differ)
 int zkaes_verify_gcm_segments(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
                               const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
                               int *accepted_each, size_t *n_accepted) {
     return guard([&] {
-        if (n_accepted) *n_accepted = 0;
-        if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
-        if (!head || !tail || !proofs || !proof_lens || !iv || !ct || !tag || !commitments || (aad_len && !aad)) throw std::invalid_argument("null argument");
-        if (c == 0 || ct_len == 0 || ct_len > ((size_t)1 << 20) || aad_len > ((size_t)1 << 16)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block");
-        const size_t nb = (ct_len + 15) / 16, n = (nb + c - 1) / c;
-        if (n < 2) throw std::invalid_argument("GCM segments: this record fits one segment; a record that fits one proof is checked with zkaes_verify_encryption_gcm");
-        if (n_segments != n) throw std::invalid_argument("GCM segments: the record has " + std::to_string(n) + " segments of " + std::to_string(c) + " blocks");
-        if (commitments_len != 32 * (n - 1)) throw std::invalid_argument("GCM segments: one 32-byte commitment per boundary, " + std::to_string(32 * (n - 1)) + " bytes for this record");
-        if (n > 2 && !mid_or_null) throw std::invalid_argument("GCM segments: a record of more than two segments needs the mid key");
-        const size_t lt = ct_len - 16 * c * (n - 1);
-        // the verifier zero-pads the public input, so the lengths are part of the statement (as require_gcm_lengths): a key that knows its exact count pins them
-        auto exact = [](const zk::VerifyingKey &vk, size_t bits, const char *name) {
-            if (vk.num_public_inputs + 1 != vk.num_instance && vk.num_public_inputs != bits) throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths");
-        };
-        exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, "head");
-        if (n > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, "mid");
-        exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, "tail");
-        uint8_t lenblk[16];
-        for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); }
-        verify_each(proofs, proof_lens, n, accepted_each, n_accepted, [&](size_t s, const zk::Proof &p) {
-            uint8_t hd[16];
-            memcpy(hd, iv, 12);
-            const uint32_t ctr0 = (uint32_t)(2 + s * c);
-            for (int i = 0; i < 4; i++) hd[12 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
-            const bool first = s == 0, last = s + 1 == n;
-            std::vector<zk::Fr> pub = zk::public_input_of({{hd, 16}, {first ? aad : nullptr, aad_len}, {ct + 16 * c * s, last ? lt : 16 * c}, {last ? lenblk : nullptr, 16}, {last ? tag : nullptr, 16},
-                                                           {first ? nullptr : commitments + 32 * (s - 1), 32}, {last ? nullptr : commitments + 32 * s, 32}});
-            return zk::verify(first ? head->vk : last ? tail->vk : mid_or_null->vk, pub, p);
-        });
+        verify_gcm_segments("verify_gcm_segments", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, false, nullptr, 0,
+                            nullptr, 0, accepted_each, n_accepted);
+    });
+}
+int zkaes_verify_gcm_segments_reveal(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                     const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                     size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        verify_gcm_segments("verify_gcm_segments_reveal", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, true, mask,
+                            mask_len, revealed, revealed_len, accepted_each, n_accepted);
     });
 }
 // ---- key tags (include/zkaes.h): the tag on the host, and the verifiers that check every proof of a job against ONE tag
@@ -541,9 +576,9 @@ int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_
 }
 // (this query also fills out[9 .. 11]: the non-zeros of the joint matrix -- the positions where A, B or C has an entry, as the indexer merges them -- and |H|, |K|, so
 // that a caller can size a record's segments against an SRS without a device)
-int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, uint64_t out[12]) {
+static int circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, uint64_t out[12]) {
     return guard([&] {
-        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits);
+        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal);
         fill_info(c, out);
         uint64_t joint = 0;
         for (size_t r = 0; r < c.num_constraints; r++) {
@@ -564,6 +599,8 @@ int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t
         out[9] = joint; out[10] = next_pow2(c.num_constraints); out[11] = next_pow2(joint);
     });
 }
+int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, 0, out); }
+int zkaes_circuit_info_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, reveal, out); }
 // ---- batch verification (include/zkaes.h): the host back end; zkaes_verify_batch_gpu and the kernel probes are in capi.cpp
 int zkaes_verify_batch(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each, size_t *n_accepted) {
     return guard([&] {
@@ -603,9 +640,9 @@ int zkaes_chunk_public_inputs_rv(int circuit_kind, size_t n_chunks, const uint8_
     if (!mask || !revealed || mask_len != zk::mask_bytes(ct_len)) return guard([&] { throw std::invalid_argument("chunk_public_inputs_rv: ONE mask over the whole job (ceil(ct_len / 8) bytes) and its revealed bytes"); });
     return chunk_public_inputs("chunk_public_inputs_rv", circuit_kind, n_chunks, iv_or_icb, ct, ct_len, key_tag, key_tag_len, states, mask, revealed, out_bits, n_bits);
 }
-int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+static int circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
     return guard([&] {
-        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits);
+        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -613,6 +650,13 @@ int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size
         if (col) memcpy(col, m.col.data(), m.col.size() * 4);
         if (coeff) memcpy(coeff, m.coeff.data(), m.coeff.size() * 8);
     });
+}
+int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, 0, which, n_rows, nnz, rowptr, col, coeff);
+}
+int zkaes_circuit_matrix_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col,
+                                    int64_t *coeff) {
+    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, reveal, which, n_rows, nnz, rowptr, col, coeff);
 }
 
 }  // extern "C"

@@ -747,9 +747,10 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
 // position 31) and the block's rounds from iv || counter; one xor gate per existing message bit; the ciphertext inputs and (tail) the 128 length-block inputs; the V
 // table; GHASH -- a head starts at its first block as the lone circuit does, a mid or tail with X_0 = Y_in ^ C_0, and a tail's last multiplication runs over the
 // length-block INPUTS; (tail) the tag's xor gates and inputs; last com_in (mid, tail), then com_out (head, mid): 256 inputs each, one compression from the constant
-// initial value over key || zeros || Y || salt, 256 equalities.
-Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits) {
+// initial value over key || zeros || Y || salt, 256 equalities.  With reveal = 1 the mask and revealed inputs and their rows (reveal() above) come last of all.
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits, int rv) {
     require_key_bits(key_bits);
+    require_reveal(rv);
     if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw std::invalid_argument("GCM segment: the role must be 0 (head), 1 (mid) or 2 (tail)");
     if (units == 0) throw std::invalid_argument("GCM segment: a head or mid has at least one data block, a tail at least one byte");
     if (role != TRS_HEAD && alen) throw std::invalid_argument("GCM segment: only the head segment takes the aad");
@@ -847,14 +848,19 @@ Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, siz
         for (int j = 0; j < 16; j++) for (int bit = 0; bit < 8; bit++) yout[j][bit] = Y[8 * j + 7 - bit];
         commit(yout, salt_out, sg + TRS_COM_OUT, sg + (uint32_t)TRS_SLOT_OUT(nb));
     }
-    Circuit c = finish(b, CIRCUIT_AES_GCM_SEG, nb, TRS_BYTES(nk, role, na, nb), g.key_bytes());
+    // ---- selective disclosure: the segment's slice of the record's mask and revealed bytes, behind the commitments as finish_aes puts them behind the digest
+    size_t trace_bytes = TRS_BYTES(nk, role, na, nb);
+    const size_t reveal_off = rv ? TRV(trace_bytes) : 0;
+    if (rv) trace_bytes = reveal(b, msg, trace_bytes);
+    Circuit c = finish(b, CIRCUIT_AES_GCM_SEG, nb, trace_bytes, g.key_bytes());
     c.message_bytes = len; c.aad_bytes = alen; c.seg_role = role; c.seg_off = sg;
+    c.reveal = rv; c.reveal_off = reveal_off;
     return c;
 }
 
 Circuit compile_circuit(int kind, size_t message_len, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int reveal) {
     require_reveal(reveal);
-    if (kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment circuit has a role: use the _gcm_seg entry points (zkaes_circuit_info_gcm_seg, zkaes_synthesize_keys_gcm_seg); segments have no reveal form");
+    if (kind == CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("a GCM segment circuit has a role: use the _gcm_seg entry points (zkaes_circuit_info_gcm_seg, zkaes_synthesize_keys_gcm_seg); through the plain queries segments have no reveal form, their _gcm_seg_rv entries take the flag");
     if (kind == CIRCUIT_AES_GCM)return compile_aes_gcm_circuit(message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     if (aad_len) throw std::invalid_argument("only a GCM circuit takes additional authenticated data");
     if (kind == CIRCUIT_AES) return compile_aes_circuit(message_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);

@@ -63,7 +63,7 @@ struct Circuit {
 // is a multiple of 64 with digest_prefix + message_len < 2^61, and 0 for the other kinds.  Anything else is std::invalid_argument
 // reveal (every AES compiler, default 0 = the circuit as it was): 1 appends, behind the digest, ceil(L / 8) mask bytes and L revealed bytes as inputs (the mask first),
 // one row per mask bit at or beyond L that pins it to zero, and per message bit ONE row mask_i * m_ij = r_ij over the message witnesses: no new witness.
-// Anything but 0 or 1 is std::invalid_argument; the ops circuits and the GCM segment circuits have no reveal form
+// Anything but 0 or 1 is std::invalid_argument; the ops circuits have no reveal form
 enum DigestKind { DIGEST_NONE = 0, DIGEST_CHAIN = 1, DIGEST_FINAL = 2 };
 Circuit compile_aes_circuit(size_t message_len, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
 Circuit compile_ops_circuit(int kind);
@@ -83,8 +83,10 @@ Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_b
 // segment's first data block), head: aad, ciphertext, com_out (32); mid: ciphertext, com_in, com_out; tail: ciphertext, the length block be64(8 A) || be64(8 L) of the
 // whole record (16), tag (16), com_in.  Private: message, key, Y_in (the GHASH accumulator entering a mid or tail), the salts.  A commitment is ONE SHA-256 compression
 // from the initial value over key || zeros to 32 bytes || Y || salt.  Block b runs under iv || (ctr0 + b mod 2^32), by CTR's xor/and incrementer over the low 32 bits.
-// No key tag and no digest; anything out of range is std::invalid_argument
-Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128);
+// No key tag and no digest.  reveal = 1 appends, behind everything above, the segment's slice of the record's mask (ceil(len / 8) bytes) and of its
+// revealed bytes (len), len = 16 c for a head or mid and Lt for a tail, with the rows of the lone reveal form; reveal = 0 is the circuit as it was.  Anything out of
+// range is std::invalid_argument
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128, int reveal = 0);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
 // 128, key_tag_blocks 0 and digest_kind 0 for the ops kinds
 Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
@@ -94,7 +96,7 @@ Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t
 void sha256_chain(const uint8_t *h_in, const uint8_t *data, size_t len, uint8_t h_out[32]);
 void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *tail, size_t tail_len, uint8_t digest[32]);
 // the bytes of the per-proof public header a key's mode takes ahead of a digest key's H_in: 0 (ECB), 16 (CBC, CTR), 12 + aad_bytes (GCM); for a GCM segment key the
-// 80 + aad_bytes of a segment header (trace_layout.h TRS_HDR_*), which also carries that proof's witnesses Y_in and the salts
+// 80 + aad_bytes of a segment header (trace_layout.h TRS_HDR_*), which also carries that proof's witnesses Y_in and the salts (a reveal segment key's mask follows it)
 size_t mode_header_bytes(const Circuit &c);
 // the ceil(message_bytes / 8) mask bytes a reveal key's per-proof header carries behind H_in, 0 for every other key
 size_t reveal_mask_bytes(const Circuit &c);

@@ -508,7 +508,7 @@ void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lit
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
     if (kind == CIRCUIT_AES_GCM_SEG) {                                             // message_len_ = the segment's units: c data blocks (head, mid) or Lt bytes (tail)
-        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits);
+        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits, reveal);
         message_len = circuit.message_bytes;
     } else circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     const Circuit &c = circuit;
@@ -1020,6 +1020,8 @@ void ProvingKey::msm_powers_partial_device(const uint8_t *scalars, size_t n_loca
 // H_out -- a digest key's proofs do, which the entries from before have no argument for; reveal: does the entry carry a mask (the same rule); len: the message's; aad_len: the aad's, or KEY_AAD where the entry takes the
 // header whole
 static void require_key(const Circuit &c, int kind, bool digest, size_t len, size_t aad_len, bool reveal = false) {
+    if (c.kind == CIRCUIT_AES_GCM_SEG && kind == ProvingKey::ANY_AES_KIND)
+        throw std::invalid_argument("this proving key is a GCM segment key: use the segment entry points (zkaes_encrypt_gcm_segments_seeded_at, zkaes_encrypt_gcm_segments_reveal_seeded_at, zkaes_aes_witness_gcm_seg, zkaes_aes_witness_gcm_seg_rv)");
     if (reveal && !c.reveal) throw std::invalid_argument("the _reveal_ entry points take a proving key synthesized with reveal = 1 (zkaes_synthesize_keys_rv)");
     if (!reveal && c.reveal) throw std::invalid_argument("this proving key reveals plaintext bytes under a per-proof mask: use the _reveal_ entry points (zkaes_encrypt_reveal_batch_seeded_at, zkaes_encrypt_reveal_chunked_seeded_at, zkaes_aes_witness_rv)");
     if (digest && !c.digest_kind) throw std::invalid_argument("the _digest_ entry points take a proving key synthesized with a digest (digest_kind = 1 or 2)");
@@ -1212,30 +1214,53 @@ std::vector<Proof> ProvingKey::prove_chunked(int kind, bool digest, const uint8_
     if (states_or_null) memcpy(states_or_null, states.data(), states.size());
     return proofs;
 }
-// ---- GCM segments.  A segment proof's header is TRS_HDR_BYTES(A) bytes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad
-static const Circuit &require_segment_key(const ProvingKey *pk, int role, const char *name) {
+// ---- GCM segments.  A segment proof's header is TRS_HDR_BYTES(A) bytes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad -- and, for
+// a key synthesized with reveal = 1, the segment's slice of the record's mask behind them.  reveal: does the entry carry a mask (9i's rule, as require_key)
+static const Circuit &require_segment_key(const ProvingKey *pk, int role, const char *name, bool reveal = false) {
     if (!pk) throw std::invalid_argument(std::string("null ") + name + " segment key");
     const Circuit &c = pk->impl->circuit;
     if (c.kind != CIRCUIT_AES_GCM_SEG) throw std::invalid_argument(std::string("the ") + name + " key is not a GCM segment key: the segment entry points take keys of zkaes_synthesize_keys_gcm_seg (a lone record goes through zkaes_encrypt_gcm_seeded)");
+    if (reveal && !c.reveal) throw std::invalid_argument(std::string("the ") + name + " key has no reveal region: the segment _reveal_ entry points take keys synthesized with reveal = 1 (zkaes_synthesize_keys_gcm_seg_rv)");
+    if (!reveal && c.reveal)
+        throw std::invalid_argument(std::string("the ") + name + " key reveals plaintext bytes under a per-proof mask: use the segment _reveal_ entry points (zkaes_encrypt_gcm_segments_reveal_seeded_at, zkaes_encrypt_gcm_segment_reveal_batch_seeded_at, zkaes_aes_witness_gcm_seg_rv)");
     if (role >= 0 && c.seg_role != role) throw std::invalid_argument(std::string("the ") + name + " key was synthesized for another segment role");
     return c;
 }
-std::vector<uint8_t> ProvingKey::aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len) {
-    const Circuit &c = require_segment_key(this, -1, "proving");
+// n segment headers with their masks behind them, as launch_trace takes them: n x (TRS_HDR_BYTES(A) + ceil(len / 8)) bytes; every mask is checked against the key's length
+static std::vector<uint8_t> segment_reveal_headers(const Circuit &c, const uint8_t *headers, const uint8_t *masks, size_t n) {
+    const size_t hb = TRS_HDR_BYTES(c.aad_bytes), mb = reveal_mask_bytes(c);
+    std::vector<uint8_t> hs((hb + mb) * n);
+    for (size_t i = 0; i < n; i++) {
+        require_mask(masks + mb * i, c.message_bytes);
+        memcpy(&hs[(hb + mb) * i], headers + hb * i, hb);
+        memcpy(&hs[(hb + mb) * i + hb], masks + mb * i, mb);
+    }
+    return hs;
+}
+std::vector<uint8_t> ProvingKey::aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, const uint8_t *mask, size_t mask_len) {
+    const Circuit &c = require_segment_key(this, -1, "proving", mask != nullptr);
     if (!message || !key || !header) throw std::invalid_argument("null argument");
     if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
     if (header_len != TRS_HDR_BYTES(c.aad_bytes)) throw std::invalid_argument("a segment header of this key has " + std::to_string(TRS_HDR_BYTES(c.aad_bytes)) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad)");
-    return witness_of(impl, message, len, key, header);
+    if (!mask) return witness_of(impl, message, len, key, header);
+    if (mask_len != reveal_mask_bytes(c)) throw std::invalid_argument("the mask of this key has " + std::to_string(reveal_mask_bytes(c)) + " bytes");
+    return witness_of(impl, message, len, key, segment_reveal_headers(c, header, mask, 1).data());
 }
-std::vector<Proof> ProvingKey::prove_gcm_segment_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
-    const Circuit &c = require_segment_key(this, -1, "proving");
+std::vector<Proof> ProvingKey::prove_gcm_segment_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset,
+                                                       const uint8_t *masks, uint8_t *revealed_or_null) {
+    const Circuit &c = require_segment_key(this, -1, "proving", masks != nullptr);
     if (n && (!messages || !keys || !headers)) throw std::invalid_argument("null argument");
-    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, TRS_HDR_BYTES(c.aad_bytes));
+    if (!masks) return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, TRS_HDR_BYTES(c.aad_bytes));
+    const std::vector<uint8_t> hs = segment_reveal_headers(c, headers, masks, n);
+    const size_t L = c.message_bytes, mb = reveal_mask_bytes(c);
+    if (revealed_or_null) for (size_t i = 0; i < n; i++) reveal_bytes(messages + L * i, masks + mb * i, L, revealed_or_null + L * i);      // by the verifier's own masking, as prove_batch
+    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, hs.data(), TRS_HDR_BYTES(c.aad_bytes) + mb);
 }
 std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad,
                                       size_t aad_len, const uint8_t *salts_or_null, size_t first_segment, size_t count, const uint8_t *zk_seed, uint8_t *ciphertext_or_null, uint8_t *tag_or_null,
-                                      uint8_t *commitments_or_null) {
-    const Circuit &ch = require_segment_key(head, TRS_HEAD, "head"), &ct_ = require_segment_key(tail, TRS_TAIL, "tail");
+                                      uint8_t *commitments_or_null, const uint8_t *mask, uint8_t *revealed_or_null) {
+    const bool rv = mask != nullptr;
+    const Circuit &ch = require_segment_key(head, TRS_HEAD, "head", rv), &ct_ = require_segment_key(tail, TRS_TAIL, "tail", rv);
     if (!message || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
     const size_t c = ch.n_blocks, kb = ch.key_bytes;
     if (len == 0 || len > ((size_t)1 << 20)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes");
@@ -1246,12 +1271,13 @@ std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null,
     if (ct_.message_bytes != lt) throw std::invalid_argument("InstanceDoesNotMatchIndex: the record's last segment has " + std::to_string(lt) + " bytes, the tail key was synthesized for " + std::to_string(ct_.message_bytes));
     if (ct_.key_bytes != kb) throw std::invalid_argument("the segment keys were synthesized for different AES key sizes");
     if (n > 2) {
-        const Circuit &cm = require_segment_key(mid_or_null, TRS_MID, "mid");
+        const Circuit &cm = require_segment_key(mid_or_null, TRS_MID, "mid", rv);
         if (cm.n_blocks != c) throw std::invalid_argument("head and mid keys were synthesized for different segment lengths");
         if (cm.key_bytes != kb) throw std::invalid_argument("the segment keys were synthesized for different AES key sizes");
     }
     if (first_segment > n || count > n - first_segment) throw std::invalid_argument("GCM segments: first_segment + count exceeds the record's " + std::to_string(n) + " segments");
     if (!salts_or_null && (first_segment != 0 || count != n)) throw std::invalid_argument("GCM segments: a job split over calls passes its salts, so that every call makes the same commitments");
+    if (rv) require_mask(mask, len);                                              // ONE mask over the record: no bit at or beyond L
     // ---- the host's side: the record's GCM encryption, Y at every boundary, the salts and the commitments
     std::vector<uint8_t> ct(len), ys(16 * (n - 1)), salts(16 * (n - 1)), coms(32 * (n - 1));
     uint8_t tag[16], lenblk[16];
@@ -1264,8 +1290,11 @@ std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null,
     if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
     if (tag_or_null) memcpy(tag_or_null, tag, 16);
     if (commitments_or_null) memcpy(commitments_or_null, coms.data(), coms.size());
+    if (rv && revealed_or_null) reveal_bytes(message, mask, len, revealed_or_null);
+    // segment s's header; with a mask its slice of the record's mask behind it (segment boundaries are multiples of 16 bytes: every slice begins on a mask byte)
     auto header = [&](size_t s, size_t A) {
-        std::vector<uint8_t> h(TRS_HDR_BYTES(A), 0);
+        const size_t mb = rv ? mask_bytes(s + 1 < n ? 16 * c : lt) : 0;
+        std::vector<uint8_t> h(TRS_HDR_BYTES(A) + mb, 0);
         memcpy(&h[TRS_HDR_IV], iv, 12);
         const uint32_t ctr0 = (uint32_t)(2 + s * c);
         for (int i = 0; i < 4; i++) h[TRS_HDR_CTR0 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
@@ -1273,6 +1302,7 @@ std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null,
         if (s + 1 < n) memcpy(&h[TRS_HDR_SALT_OUT], &salts[16 * s], 16);
         memcpy(&h[TRS_HDR_LEN], lenblk, 16);
         if (A) memcpy(&h[TRS_HDR_AAD], aad, A);
+        if (mb) memcpy(&h[TRS_HDR_BYTES(A)], chunk_mask_slice(mask, s, 16 * c), mb);
         return h;
     };
     // ---- the proofs: segment s draws from the job's seed at index s, whichever call proves it; the middle segments run side by side over the mid key's contexts
@@ -1289,7 +1319,7 @@ std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null,
     if (m0 < m1) {
         std::vector<uint8_t> hs;
         for (size_t s = m0; s < m1; s++) { const std::vector<uint8_t> h = header(s, 0); hs.insert(hs.end(), h.begin(), h.end()); }
-        std::vector<Proof> mids = prove_many(mid_or_null->impl, message + 16 * c * m0, key, 0, m1 - m0, mid_or_null->contexts(), zk_seed, (uint64_t)m0, hs.data(), TRS_HDR_BYTES(0));
+        std::vector<Proof> mids = prove_many(mid_or_null->impl, message + 16 * c * m0, key, 0, m1 - m0, mid_or_null->contexts(), zk_seed, (uint64_t)m0, hs.data(), TRS_HDR_BYTES(0) + (rv ? mask_bytes(16 * c) : 0));
         for (size_t s = m0; s < m1; s++) proofs[s - first_segment] = mids[s - m0];
     }
     if (count && last == n) lone(tail, n - 1, 0);
@@ -1419,10 +1449,10 @@ std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len
     pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, -1, reveal);
     return pk;
 }
-std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags) {
+std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags, int reveal) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, 0, 0, 0, role);
+    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, 0, 0, 0, role, reveal);
     return pk;
 }
 

@@ -106,11 +106,14 @@ class ProvingKey {
     Proof prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed);
     // ---- GCM segments (keys of kind CIRCUIT_AES_GCM_SEG only, from synthesize_keys_gcm_segment; every call above refuses such a key, and the GCM calls name the segment
     // entries).  header = the segment proof's TRS_HDR_BYTES(A) bytes (trace_layout.h): iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad
-    std::vector<uint8_t> aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len);
+    // A key synthesized with reveal = 1 takes, beside the header, the segment's mask of ceil(len / 8) bytes -- its slice of the record's -- and is refused
+    // without one; a key with reveal = 0 is refused with one.  masks: n x ceil(len / 8); revealed_or_null receives reveal_bytes(message, mask) per proof (n x len)
+    std::vector<uint8_t> aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, const uint8_t *mask_or_null = nullptr,
+                                                 size_t mask_len = 0);
     // n independent segment proofs of this key's role, each under its own header (n x TRS_HDR_BYTES(A)), all contexts side by side; seeds as prove_batch.  The
     // caller answers for what the headers say: prove_gcm_segments below derives them from one record
     std::vector<Proof> prove_gcm_segment_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
-                                               uint64_t index_offset = 0);
+                                               uint64_t index_offset = 0, const uint8_t *masks_or_null = nullptr, uint8_t *revealed_or_null = nullptr);
     const ProverTimings &last_timings() const;
     // one proof with the op recorder open: JSON of the transforms and MSMs the library actually launched (marlin.cpp; SURVEY.md 8d op lists)
     std::string op_lists_json(const uint8_t *message, size_t len, const uint8_t key[16], bool throughput_path);
@@ -143,17 +146,20 @@ class ProvingKey {
 enum : unsigned { KEY_NO_TABLES = 1u };
 std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128,
                                             size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, digest_kind: 0, 1 or 2 (circuit.hpp DigestKind), reveal: 0 or 1, the AES kinds only)
-// A GCM segment key: role = 0 head, 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); aad_len: head only.  No key tag, no digest
-std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags = 0);
+// A GCM segment key: role = 0 head, 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); aad_len: head only.  No key tag, no digest;
+// reveal: 0 or 1
+std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags = 0, int reveal = 0);
 // Segments [first_segment, first_segment + count) of ONE GCM record of len bytes as segment-proofs: n = ceil(ceil(len / 16) / c) >= 2 segments, c = the head key's data
 // blocks; mid_or_null may be null when n = 2; the tail key is the one for the record's last len - 16 c (n - 1) bytes.  The host computes the record's ciphertext and tag,
 // Y at every boundary and the n - 1 commitments from salts_or_null (16 (n - 1) bytes; null = fresh OS randomness, allowed only when the call covers the whole record);
 // the device is handed key, iv, aad, message, ctr0, Y_in, the salts and the length block.  Segment s draws from StdRng(Blake2s(zk_seed || s)) whichever call proves it
 // (nullptr = the fixed test stream, as prove_batch); the middle segments run side by side over the mid key's contexts.  Receives on request the whole record's
-// ciphertext (len), tag (16) and commitments (32 (n - 1))
+// ciphertext (len), tag (16) and commitments (32 (n - 1)).  mask_or_null: ONE mask of ceil(len / 8) bytes over the whole record; the three keys must then
+// be reveal keys (and must not be without it), segment s is proven under chunk_mask_slice(mask, s, 16 c), a bit at or beyond len is std::invalid_argument and
+// revealed_or_null receives reveal_bytes(message, mask) for the whole record (len), whichever segments the call proves
 std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad,
                                       size_t aad_len, const uint8_t *salts_or_null, size_t first_segment, size_t count, const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr,
-                                      uint8_t *tag_or_null = nullptr, uint8_t *commitments_or_null = nullptr);
+                                      uint8_t *tag_or_null = nullptr, uint8_t *commitments_or_null = nullptr, const uint8_t *mask_or_null = nullptr, uint8_t *revealed_or_null = nullptr);
 // hold = true: every universal / Lagrange SRS built (or alive) from now on stays resident after its last key is freed; false: back to "freed with the last key"
 void srs_hold(bool hold);
 // process default of ProvingKey::contexts(): ZKAES_CONTEXTS from the environment (read once), else ZKAES_DEFAULT_CONTEXTS

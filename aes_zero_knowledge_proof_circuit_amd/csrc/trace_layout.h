@@ -247,6 +247,21 @@ static_assert(TRS_GCM(4, TRS_TAIL, 3) == TRK_GCM(4, 3) && TRS_GCM(8, TRS_TAIL, 2
 static_assert(TRS_SEG(TRS_TAIL, 0, 3) == TR_GCM_BYTES(0, 3) - TR_GCM(3) && TRS_BYTES(4, TRS_TAIL, 0, 3) == TRK_GCM_BYTES(4, 0, 3) + TRS_SEG_BYTES(3), "the segment region lies behind the GCM tail: no offset ahead of it moves");
 static_assert(TRS_GCM(6, TRS_MID, 1) % 16 == 0 && TRS_SEG(TRS_HEAD, 1, 2) % 16 == 0 && TRS_SLOT_IN(1) == 144 && TRS_SLOT_IN(2) == 144 && TRS_SLOT_IN(3) == 160 && TRS_SEG_BYTES(4) % 16 == 0, "the segment region and its compression slots are 16-byte aligned");
 static_assert(TRS_MULS(TRS_HEAD, 1, 4) == 5 && TRS_MULS(TRS_MID, 0, 4) == 4 && TRS_MULS(TRS_TAIL, 0, 4) == 5 && TRS_SLOTS(TRS_MID, 4) == 5 && TRS_SLOTS(TRS_TAIL, 4) == 6, "multiplications and AES slots per role");
+// ---- selective disclosure on segments: a segment key synthesized with R = 1 has the reveal region of 9i (the TRV_* inner layout, for the segment's own
+// len = 16 c or Lt bytes) BEHIND the segment region's two compression slots, at the next multiple of 16.  No TRS_* offset moves, and with R = 0 a trace is what it was.
+// The proof's header grows by the segment's slice of the record's mask: TRS_HDR_BYTES(A) + ceil(len / 8) bytes, the mask last
+#define TRS_RV(nk, role, na, nb) TRV(TRS_BYTES(nk, role, na, nb))
+#define TRS_RV_BYTES(nk, role, na, nb, R, len) TRV_BYTES(TRS_BYTES(nk, role, na, nb), R, len)
+#define TRS_HDR_MASK(A) TRS_HDR_BYTES(A)
+#define TRS_HDR_RV_BYTES(A, R, len) (TRS_HDR_BYTES(A) + ((R) ? TRV_MASK_BYTES(len) : 0))
+#define TRS_RV_ASSERT(nk) \
+    static_assert(TRS_RV_BYTES(nk, TRS_HEAD, 1, 2, 0, 32) == TRS_BYTES(nk, TRS_HEAD, 1, 2) && TRS_RV_BYTES(nk, TRS_MID, 0, 1, 0, 16) == TRS_BYTES(nk, TRS_MID, 0, 1) && \
+                  TRS_RV_BYTES(nk, TRS_TAIL, 0, 2, 0, 17) == TRS_BYTES(nk, TRS_TAIL, 0, 2), "without reveal a segment trace keeps its length"); \
+    static_assert(TRS_RV(nk, TRS_HEAD, 1, 2) % 16 == 0 && TRS_RV(nk, TRS_MID, 0, 1) % 16 == 0 && TRS_RV(nk, TRS_TAIL, 0, 2) % 16 == 0 && TRS_RV(nk, TRS_HEAD, 1, 2) >= TRS_BYTES(nk, TRS_HEAD, 1, 2) && \
+                  TRS_RV(nk, TRS_MID, 0, 1) - TRS_BYTES(nk, TRS_MID, 0, 1) < 16 && TRS_RV_BYTES(nk, TRS_TAIL, 0, 2, 1, 17) == TRS_RV(nk, TRS_TAIL, 0, 2) + 48 && \
+                  TRS_RV_BYTES(nk, TRS_MID, 0, 4, 1, 64) % 16 == 0, "a segment's reveal region begins on the next multiple of 16 behind the compression slots and ends on one")
+TRS_RV_ASSERT(4); TRS_RV_ASSERT(6); TRS_RV_ASSERT(8);
+static_assert(TRS_HDR_RV_BYTES(13, 0, 16) == 93 && TRS_HDR_RV_BYTES(13, 1, 16) == 95 && TRS_HDR_RV_BYTES(0, 1, 17) == 83 && TRS_HDR_MASK(13) == 93, "a reveal segment header ends in the mask");
 
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30

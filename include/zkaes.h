@@ -443,6 +443,41 @@ int zkaes_encrypt_gcm_segments_seeded_at(const uint8_t *message, size_t message_
 int zkaes_verify_gcm_segments(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
                               const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16], const uint8_t *commitments,
                               size_t commitments_len, int *accepted_each, size_t *n_accepted);
+/* ---- selective disclosure on segmented records.  A segment key synthesized with reveal = 1 proves, beside its role's statement above, revealed[i] =
+ * mask_i ? M[i] : 0 over the segment's own len = 16 c (head, mid) or Lt (tail) bytes; its public input gains, behind everything listed above, 8 ceil(len / 8) mask bits
+ * and 8 len revealed bits, in the order and bit order of the lone reveal form, and mask bits at or beyond len are pinned to zero.  There is ONE mask of ceil(L / 8) bytes
+ * and ONE revealed array of L bytes over the whole record: segment boundaries are multiples of 16 bytes, so segment s is proven and checked under the mask bytes from
+ * 2 c s on and the revealed bytes from 16 c s on, and head, mid and tail together are the lone reveal statement for (iv, aad, ciphertext, tag).  The aad is public and
+ * not covered by the mask; commitments, salts, ctr0 and the length block are as above.  reveal = 0 is every segment key from before, bit for bit.  Every entry above
+ * refuses a reveal = 1 key and the entries below refuse reveal = 0 keys and keys that are no segment keys; zkaes_pk_segment_info and zkaes_pk_reveal_info answer for
+ * both.  The provers and the verifier treat a mask bit at or beyond L -- and the verifier a non-zero revealed byte under a zero mask bit -- as an invalid argument,
+ * never as a rejected proof */
+int zkaes_synthesize_keys_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_length, size_t srs_num_constraints, size_t srs_num_variables,
+                                     size_t srs_num_non_zero, unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* host only: zkaes_circuit_info_gcm_seg / zkaes_circuit_matrix_gcm_seg with the reveal flag; reveal = 0 answers what they answer */
+int zkaes_circuit_info_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col,
+                                    int64_t *coeff);
+/* zkaes_aes_witness_gcm_seg for a reveal key: header as there (80 + A bytes), mask = the segment's ceil(len / 8) bytes */
+int zkaes_aes_witness_gcm_seg_rv(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t *secret_key, const uint8_t *header, size_t header_len, const uint8_t *mask,
+                                 size_t mask_len, uint8_t *z, size_t z_cap, size_t *z_len);
+/* zkaes_encrypt_gcm_segment_batch_seeded_at for a reveal key: masks = n x ceil(len / 8) bytes, one mask per proof; revealed_or_null receives n x len bytes */
+int zkaes_encrypt_gcm_segment_reveal_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers,
+                                                     size_t headers_len, const uint8_t *masks, size_t masks_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index,
+                                                     uint8_t *revealed_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* zkaes_encrypt_gcm_segments_seeded_at for three reveal keys under ONE mask of ceil(message_len / 8) bytes over the record.  revealed_or_null receives the whole record's
+ * message_len revealed bytes whichever segments the call proves; a job split over calls passes every call the same mask and salts and stays byte-identical to the whole */
+int zkaes_encrypt_gcm_segments_reveal_seeded_at(const uint8_t *message, size_t message_len, const uint8_t *secret_key, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                                                const zkaes_pk *head, const zkaes_pk *mid_or_null, const zkaes_pk *tail, const uint8_t *salts_or_null, const uint8_t *mask, size_t mask_len,
+                                                const uint8_t *zk_seed32, size_t first_segment, size_t count, uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t *commitments_or_null,
+                                                uint8_t *revealed_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* host only: zkaes_verify_gcm_segments for the proofs of three reveal keys against ONE mask (mask_len = ceil(ciphertext_len / 8)) and ONE revealed array (revealed_len =
+ * ciphertext_len).  Proofs of reveal = 0 keys are never accepted here, nor proofs of reveal = 1 keys by zkaes_verify_gcm_segments: a key that carries its public-input
+ * count raises, any other rejects */
+int zkaes_verify_gcm_segments_reveal(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                     const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
+                                     const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
+                                     int *accepted_each, size_t *n_accepted);
 /* src/ops.rs toy gates proven with Marlin (public input: none) */
 int zkaes_prove_ops(const zkaes_pk *pk, uint32_t x, uint32_t y, const uint8_t *zk_seed32, uint8_t **proof, size_t *proof_len);
 /* generic verify: public_input_bits = instance assignment without the leading One, one byte (0/1) per variable */

@@ -179,6 +179,26 @@ extern "C" {
     fn zkaes_verify_gcm_segments(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize, c: usize,
                                  iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8, commitments: *const u8,
                                  commitments_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    // selective disclosure on segmented records (include/zkaes.h, the section behind "segment-proofs"; declarations only, no wrappers yet, and not compiled: no cargo in
+    // the build image).  ONE mask of ceil(L / 8) bytes and ONE revealed array of L bytes over the record; a segment's own mask is ceil(len / 8) bytes
+    fn zkaes_synthesize_keys_gcm_seg_rv(role: c_int, key_bits: c_uint, reveal: c_uint, units: usize, aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize,
+                                        srs_num_non_zero: usize, flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_circuit_info_gcm_seg_rv(role: c_int, key_bits: c_uint, reveal: c_uint, units: usize, aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_gcm_seg_rv(role: c_int, key_bits: c_uint, reveal: c_uint, units: usize, aad_length: usize, which: c_int, n_rows: *mut u64, nnz: *mut u64, rowptr: *mut u32,
+                                       col: *mut u32, coeff: *mut i64) -> c_int;
+    fn zkaes_aes_witness_gcm_seg_rv(pk: *const zkaes_pk, message: *const u8, message_len: usize, secret_key: *const u8, header: *const u8, header_len: usize, mask: *const u8,
+                                    mask_len: usize, z: *mut u8, z_cap: usize, z_len: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_segment_reveal_batch_seeded_at(n: usize, messages: *const u8, messages_len: usize, secret_keys: *const u8, secret_keys_len: usize, headers: *const u8,
+                                                        headers_len: usize, masks: *const u8, masks_len: usize, pk: *const zkaes_pk, zk_seed32: *const u8, first_proof_index: u64,
+                                                        revealed_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_segments_reveal_seeded_at(message: *const u8, message_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, head: *const zkaes_pk,
+                                                   mid_or_null: *const zkaes_pk, tail: *const zkaes_pk, salts_or_null: *const u8, mask: *const u8, mask_len: usize, zk_seed32: *const u8,
+                                                   first_segment: usize, count: usize, ciphertext_or_null: *mut u8, tag_or_null: *mut u8, commitments_or_null: *mut u8,
+                                                   revealed_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_verify_gcm_segments_reveal(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize,
+                                        c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
+                                        commitments: *const u8, commitments_len: usize, mask: *const u8, mask_len: usize, revealed: *const u8, revealed_len: usize,
+                                        accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
     // kernel-level entries of the kernels that build a key (include/zkaes.h, "kernels that BUILD A KEY": test surface, not product API; declarations only, no wrappers, and
     // not compiled: no cargo in the build image).  A point is 96 bytes of affine x || y in Montgomery form, infinity 96 zero bytes; a field element 32 bytes; a Niels record
     // 192 bytes; every output of zkaes_index_evals holds 2^lg_k + 64 elements

@@ -1,0 +1,111 @@
+"""What selective disclosure costs on a GCM segment: proofs of the mid key at the default c with reveal = 0 against the mid key at the same c with reveal = 1 and every
+second byte masked in, in ONE process over the shared default universal SRS, the legs alternating for three rounds after a warm-up leg each, every proof verified
+against the public input the Python models give for its header and mask (ciphertext under ctr0, both commitments, the mask, the revealed bytes).
+
+    python tools/gcm_segments_reveal_vs_plain.py [--proofs 48] [--rounds 3] [--out profiles/gcm_segments_reveal.json]      (run on the GPU box)
+
+Writes proofs/s per leg (the median of the rounds), the ratio of the reveal leg to the plain leg and each leg's own run-to-run spread, (max - min) / median.  No
+threshold is fixed in advance: the yardstick is the R = 0 leg of the same run and its own spread, never a constant.  Measurement only -- nothing here is a pass/fail
+threshold except that every proof must verify.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+try:
+    import torch  # noqa: F401  -- before libzkaes.so where torch exists (tests/conftest.py: one process, two HIP runtimes)
+except ImportError:
+    pass
+import numpy as np
+
+from aes_zero_knowledge_proof_circuit_amd import api
+import gcm_segment_model as model
+import gcm_segment_reveal_model as reveal_model
+
+LEGS = ("mid_r0", "mid_r1")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--proofs", type=int, default=48)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join("profiles", "gcm_segments_reveal.json"))
+    args = ap.parse_args()
+    n, c = args.proofs, api.GCM_SEGMENT_DEFAULT_C[128]
+    assert c == api.GCM_SEGMENT_REVEAL_DEFAULT_C[128]
+    rs = np.random.RandomState(0x5EEE)
+    seed = rs.bytes(32)
+    msgs, keys_, ivs = [rs.bytes(16 * c) for _ in range(n)], [rs.bytes(16) for _ in range(n)], [rs.bytes(12) for _ in range(n)]
+    y_ins, salts = [rs.bytes(16) for _ in range(n)], [(rs.bytes(16), rs.bytes(16)) for _ in range(n)]
+    ctr0s = [2 + c * (1 + i % 250) for i in range(n)]
+    headers = [api.gcm_segment_header(iv, ctr0, y, s[0], s[1]) for iv, ctr0, y, s in zip(ivs, ctr0s, y_ins, salts)]
+    mask = api.reveal_mask(range(0, 16 * c, 2), 16 * c)                                         # every second byte masked in
+    publics = {name: [] for name in LEGS}
+    for m, k, iv, ctr0, y, s in zip(msgs, keys_, ivs, ctr0s, y_ins, salts):                     # what each proof must say, from the models
+        tr = model.segment_trace("mid", m, k, iv, ctr0, y)
+        plain = reveal_model.bits(iv + ctr0.to_bytes(4, "big") + tr["ct"] + model.commitment(k, y, s[0]) + model.commitment(k, tr["ys"][-1].to_bytes(16, "big"), s[1]))
+        publics["mid_r0"].append(plain)
+        publics["mid_r1"].append(plain + reveal_model.bits(mask + reveal_model.revealed_of(m, mask)))
+
+    t = time.perf_counter()
+    keys = {"mid_r0": api.synthesize_keys_gcm_segment("mid", c), "mid_r1": api.synthesize_keys_gcm_segment("mid", c, reveal=True)}
+    setup_s = time.perf_counter() - t
+    infos = {name: keys[name][0].info() for name in LEGS}
+    contexts = keys["mid_r0"][0].contexts()
+
+    def leg(name):
+        t0 = time.perf_counter()
+        if name == "mid_r0":
+            out = keys[name][0].encrypt_gcm_segment_batch(msgs, keys_, headers, zk_seed=seed)
+        else:
+            out = keys[name][0].encrypt_gcm_segment_reveal_batch(msgs, keys_, headers, [mask] * n, zk_seed=seed)[1]
+        return time.perf_counter() - t0, out
+
+    def verify(name, out):
+        return sum(keys[name][1].verify(p, pub) for p, pub in zip(out, publics[name]))
+
+    for name in LEGS:                                                      # warm-up: one full leg each (every context's workspace, the caches a timed leg finds filled)
+        _, out = leg(name)
+        assert verify(name, out) == n
+    times = {name: [] for name in LEGS}
+    verified = {name: 0 for name in LEGS}
+    for _ in range(args.rounds):
+        for name in LEGS:
+            dt, out = leg(name)
+            times[name].append(dt)
+            verified[name] += verify(name, out)                            # outside the timed region
+
+    proofs_s = {name: [n / dt for dt in v] for name, v in times.items()}
+    med = {name: float(np.median(v)) for name, v in proofs_s.items()}
+    spread = {name: round((max(v) - min(v)) / med[name], 4) for name, v in proofs_s.items()}
+    out = {
+        "what": "GCM segment proving, %d mid proofs of 64 message bytes at c = %d per leg: the plain mid key (R = 0) against the reveal mid key (R = 1) with every second "
+                "byte masked in; legs alternating in one process after a warm-up leg each" % (n, c),
+        "cmd": "python tools/gcm_segments_reveal_vs_plain.py --proofs %d --rounds %d" % (n, args.rounds),
+        "contexts": contexts,
+        "window_tables": {name: keys[name][0].tables_built()[0] for name in LEGS},
+        "h_k_x": {name: [int(i["h"]), int(i["k"]), int(i["instance"])] for name, i in infos.items()},
+        "raw_constraints": {name: int(i["raw_constraints"]) for name, i in infos.items()},
+        "joint_nnz": {name: int(i["joint_nnz"]) for name, i in infos.items()},
+        "proofs_per_s": {name: [round(v, 3) for v in vs] for name, vs in proofs_s.items()},
+        "median_proofs_per_s": {name: round(v, 3) for name, v in med.items()},
+        "reveal_over_plain": round(med["mid_r1"] / med["mid_r0"], 4),
+        "spread": spread,
+        "spread_note": "(max - min) / median of a leg's proofs/s over the rounds: what run-to-run noise looks like in this process",
+        "proofs_verified": {name: "%d/%d" % (v, n * args.rounds) for name, v in verified.items()},
+        "key_setup_s": round(setup_s, 2),
+    }
+    assert all(v == n * args.rounds for v in verified.values()), out["proofs_verified"]
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
