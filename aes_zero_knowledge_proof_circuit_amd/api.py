@@ -775,6 +775,29 @@ def verify_batch(verifying_key, proofs, public_inputs, device=True):
     return [bool(each[i]) for i in range(n)]
 
 
+def verify_batch_keys(verifying_keys, key_of, proofs, public_inputs, device=True):
+    """verify_batch over proofs of SEVERAL verifying keys (include/zkaes.h): proof i is checked under verifying_keys[key_of[i]] against public_inputs[i]
+    (one 0/1 byte per variable; rows may differ in length) -> list of bools, the answers of n per-proof verify calls for two MSMs and ONE pairing product.  The keys
+    must share one setup (every key this library synthesizes does); no key, a key index out of range or keys of different setups raise.  A row that does not fit its
+    own key rejects that proof alone.  device as in verify_batch (zkaes_verify_batch_keys_gpu / zkaes_verify_batch_keys)"""
+    n, nk = len(proofs), len(verifying_keys)
+    if n == 0 or len(public_inputs) != n or len(key_of) != n:
+        raise ZkAesError("verify_batch_keys takes at least one proof, and one key index and one public-input row per proof")
+    if any(not 0 <= int(k) < 1 << 32 for k in key_of):
+        raise ZkAesError("verify_batch_keys: a key index is a 32-bit unsigned number")
+    rows = [bytes(r) for r in public_inputs]
+    keys = (C.c_void_p * max(nk, 1))(*[vk._p.value for vk in verifying_keys])
+    idx = (C.c_uint32 * n)(*[int(k) for k in key_of])
+    lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+    row_lens = (C.c_size_t * n)(*[len(r) for r in rows])
+    each = (C.c_int * n)()
+    ok = C.c_size_t()
+    fn = lib().zkaes_verify_batch_keys_gpu if device else lib().zkaes_verify_batch_keys
+    bits = b"".join(rows)
+    _check(fn(keys, C.c_size_t(nk), idx, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), bits if bits else None, row_lens, each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
+
+
 def verify_batch_timings():
     """where this thread's last verify_batch spent its time (zkaes_verify_batch_timings): ms per stage and the number of (sub-)batches checked"""
     out = (C.c_double * 8)()
@@ -839,6 +862,22 @@ def public_input_eval(lg_m, betas, bits_rows):
     n, n_bits = len(rows), len(rows[0]) if rows else 0
     out = C.create_string_buffer(32 * max(n, 1))
     _check(lib().zkaes_public_input_eval(int(lg_m), bytes(betas), b"".join(rows) if n_bits else None, C.c_size_t(n), C.c_size_t(n_bits), out))
+    return out.raw[:32 * n]
+
+
+def public_input_eval_keyed(keys, key_of, betas, bits_rows):
+    """kernel probe (zkaes_public_input_eval_keyed): keys = [(lg_m, n_bits), ...]; row i (n_bits of its key 0/1 bytes) is evaluated at betas[i] over the domain of key
+    key_of[i], all rows in ONE launch; betas n x 32 bytes Montgomery -> n x 32"""
+    rows = [bytes(r) for r in bits_rows]
+    n, nk = len(rows), len(keys)
+    lg = (C.c_int * max(nk, 1))(*[int(k[0]) for k in keys])
+    nb = (C.c_size_t * max(nk, 1))(*[int(k[1]) for k in keys])
+    idx = (C.c_uint32 * max(n, 1))(*[int(k) for k in key_of])
+    if any(0 <= k < nk and len(r) != keys[k][1] for r, k in zip(rows, key_of)):
+        raise ZkAesError("public_input_eval_keyed: every row has its own key's n_bits bytes")
+    out = C.create_string_buffer(32 * max(n, 1))
+    bits = b"".join(rows)
+    _check(lib().zkaes_public_input_eval_keyed(lg, nb, C.c_size_t(nk), idx, bytes(betas), bits if bits else None, C.c_size_t(n), out))
     return out.raw[:32 * n]
 
 
@@ -1237,6 +1276,87 @@ def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c, m
     _check(lib().zkaes_verify_gcm_segments(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad),
                                            C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), each, C.byref(ok)))
     return [bool(each[i]) for i in range(n)]
+
+
+def _gcm_segment_args(iv, aad, ciphertext, tag, commitments, mask, revealed):
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    if any(len(x) != 32 for x in commitments):
+        raise ZkAesError("a commitment is 32 bytes")
+    if (mask is None) != (revealed is None):
+        raise ZkAesError("GCM segments: mask and revealed go together")
+    coms = b"".join(bytes(x) for x in commitments)
+    m = None if mask is None else reveal_mask(mask, len(ciphertext))
+    if m is not None and len(revealed) != len(ciphertext):
+        raise ZkAesError("GCM segments: ONE revealed array over the whole record, %d bytes for this ciphertext" % len(ciphertext))
+    return coms, m
+
+
+def gcm_segment_public_inputs(n_segments, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None):
+    """the public-input rows of a segmented GCM record -> (rows, roles): one bytes object of 0/1 per segment -- exactly what verify_gcm_segments checks segment s against
+    -- and its role "head", "mid" or "tail" (zkaes_gcm_segment_public_inputs; no GPU).  The rows differ in length.  mask and revealed as in verify_gcm_segments"""
+    coms, m = _gcm_segment_args(iv, aad, ciphertext, tag, commitments, mask, revealed)
+    n = int(n_segments)
+    lens, roles = (C.c_size_t * max(n, 1))(), (C.c_int * max(n, 1))()
+    args = (C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), m,
+            C.c_size_t(0 if m is None else len(m)), None if m is None else bytes(revealed))
+    _check(lib().zkaes_gcm_segment_public_inputs(*args, None, lens, roles))
+    out = C.create_string_buffer(max(1, sum(lens[s] for s in range(n))))
+    _check(lib().zkaes_gcm_segment_public_inputs(*args, out, lens, roles))
+    rows, off = [], 0
+    for s in range(n):
+        rows.append(out.raw[off:off + lens[s]])
+        off += lens[s]
+    return rows, [("head", "mid", "tail")[roles[s]] for s in range(n)]
+
+
+def verify_gcm_segments_batch(vks, proofs, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None, device=True):
+    """verify_gcm_segments through ONE multi-key batch: the same arguments, checks, errors and answers, for two MSMs and one pairing product instead of
+    one pairing product per segment.  device as in verify_batch (zkaes_verify_gcm_segments_batch_gpu / zkaes_verify_gcm_segments_batch)"""
+    coms, m = _gcm_segment_args(iv, aad, ciphertext, tag, commitments, mask, revealed)
+    head, mid, tail = vks
+    n = len(proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each, ok = (C.c_int * max(n, 1))(), C.c_size_t()
+    fn = lib().zkaes_verify_gcm_segments_batch_gpu if device else lib().zkaes_verify_gcm_segments_batch
+    _check(fn(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad), C.c_size_t(len(aad)),
+              bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), m, C.c_size_t(0 if m is None else len(m)), None if m is None else bytes(revealed),
+              C.c_size_t(0 if m is None else len(revealed)), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
+
+
+def verify_gcm_records_batch(records, device=True):
+    """the segment-proofs of SEVERAL records in ONE verify_batch_keys call -> one list of bools per record.  A record is the argument tuple of verify_gcm_segments_batch
+    without device: (vks, proofs, iv, aad, ciphertext, tag, commitments, c[, mask, revealed]).  Key objects that several records share (the same head and mid keys, say)
+    enter the batch once: they are told apart by identity.  The rows come from gcm_segment_public_inputs, which raises where verify_gcm_segments would for a record's
+    lengths and counts; that a key fits its segment is left to the proof, which is rejected under a key of another shape"""
+    keys, key_index, key_of, proofs, rows, counts = [], {}, [], [], [], []
+    for rec in records:
+        vks, rec_proofs, iv, aad, ciphertext, tag, commitments, c = rec[:8]
+        mask, revealed = (tuple(rec[8:]) + (None, None))[:2]
+        rec_rows, roles = gcm_segment_public_inputs(len(rec_proofs), iv, aad, ciphertext, tag, commitments, c, mask=mask, revealed=revealed)
+        by_role = dict(zip(("head", "mid", "tail"), vks))
+        for proof, row, role in zip(rec_proofs, rec_rows, roles):
+            vk = by_role[role]
+            if vk is None:
+                raise ZkAesError("GCM segments: a record of more than two segments needs the mid key")
+            if id(vk) not in key_index:
+                key_index[id(vk)] = len(keys)
+                keys.append(vk)
+            key_of.append(key_index[id(vk)])
+            proofs.append(proof)
+            rows.append(row)
+        counts.append(len(rec_proofs))
+    if not proofs:
+        return [[] for _ in counts]
+    flat = verify_batch_keys(keys, key_of, proofs, rows, device=device)
+    out, off = [], 0
+    for k in counts:
+        out.append(flat[off:off + k])
+        off += k
+    return out
 
 
 def proof_roundtrip(proof):

@@ -558,6 +558,48 @@ int zkaes_public_input_eval(int lg_m, const uint8_t *betas, const uint8_t *bits,
         memcpy(out, o.data(), 32 * n);
     });
 }
+// ---- batch verification across keys on the device (include/zkaes.h); the host entries are in capi_host.cpp
+int zkaes_verify_batch_keys_gpu(const zkaes_vk *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits,
+                                const size_t *n_bits_each, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        zk::capi::verify_batch_keys_call(vks, n_keys, key_of, proofs, proof_lens, n, public_input_bits, n_bits_each, accepted_each, n_accepted, *be);
+    });
+}
+int zkaes_verify_gcm_segments_batch_gpu(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                        const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                        size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        zk::capi::verify_gcm_segments_batch_call("verify_gcm_segments_batch_gpu", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments,
+                                                 commitments_len, mask, mask_len, revealed, revealed_len, accepted_each, n_accepted, *be);
+    });
+}
+// the keyed public-input kernel, one launch per call (tests/test_gpu_verify_batch_keys.py): key k has the domain 2^lg_m[k] and rows of n_bits[k] 0/1 bytes, row i belongs
+// to key key_of[i] and follows row i - 1 in bits
+int zkaes_public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t n_keys, const uint32_t *key_of, const uint8_t *betas, const uint8_t *bits, size_t n, uint8_t *out) {
+    return guard([&] {
+        if (!lg_m || !n_bits || !key_of || !betas || !out) throw std::invalid_argument("null argument");
+        if (n_keys == 0 || n_keys > ((size_t)1 << 16) || n == 0 || n > ((size_t)1 << 20)) throw std::invalid_argument("zkaes_public_input_eval_keyed: 1 .. 2^16 keys, 1 .. 2^20 rows");
+        for (size_t k = 0; k < n_keys; k++)
+            if (lg_m[k] < 0 || lg_m[k] > 30 || n_bits[k] >= ((size_t)1 << lg_m[k])) throw std::invalid_argument("zkaes_public_input_eval_keyed: rows of fewer than 2^lg_m bits, lg_m <= 30");
+        std::vector<zk::Fr> b(n), o(n);
+        std::vector<size_t> off(n);
+        size_t total = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (key_of[i] >= n_keys) throw std::invalid_argument("zkaes_public_input_eval_keyed: key index out of range");
+            memcpy(b[i].l, betas + 32 * i, 32);
+            if (zk::Fr::geq_mod(b[i].l)) throw std::invalid_argument("zkaes_public_input_eval_keyed: limbs not below the modulus");
+            off[i] = total; total += n_bits[key_of[i]];
+        }
+        if (total && !bits) throw std::invalid_argument("null argument");
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        be->public_input_eval_keyed(lg_m, n_bits, n_keys, key_of, b.data(), bits, off.data(), n, o.data());
+        memcpy(out, o.data(), 32 * n);
+    });
+}
 int zkaes_msm_stats(double out[5], int reset) {
     return guard([&] {
         auto s = zk::gpu::msm_stats(reset != 0);

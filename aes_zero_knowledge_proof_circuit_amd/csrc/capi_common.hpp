@@ -51,6 +51,34 @@ inline void verify_batch_call(const zkaes_vk *vk, const uint8_t *proofs, const s
     for (size_t i = 0; i < n; i++) { if (accepted_each) accepted_each[i] = acc[i]; ok += acc[i]; }
     if (n_accepted) *n_accepted = ok;
 }
+// zkaes_verify_batch_keys and zkaes_verify_batch_keys_gpu: the same call over the two back ends
+inline void verify_batch_keys_call(const zkaes_vk *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *bits,
+                                   const size_t *n_bits_each, int *accepted_each, size_t *n_accepted, BatchBackend &be) {
+    if (n_accepted) *n_accepted = 0;
+    if (accepted_each) for (size_t i = 0; i < n; i++) accepted_each[i] = 0;
+    if (n_keys == 0) throw std::invalid_argument("verify_batch_keys: at least one verifying key");
+    if (!vks || !key_of || !proofs || !proof_lens || !n_bits_each) throw std::invalid_argument("null argument");
+    if (n == 0) throw std::invalid_argument("verify_batch_keys: at least one proof");
+    std::vector<const VerifyingKey *> keys(n_keys);
+    for (size_t k = 0; k < n_keys; k++) { if (!vks[k]) throw std::invalid_argument("null argument"); keys[k] = &vks[k]->vk; }
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (n_bits_each[i] >= ((size_t)1 << 46) || total + n_bits_each[i] >= ((size_t)1 << 46)) throw std::invalid_argument("verify_batch_keys: n_bits out of range");
+        total += n_bits_each[i];
+    }
+    if (total && !bits) throw std::invalid_argument("null argument");
+    BatchTimings t;
+    std::vector<uint8_t> acc = verify_batch_keys(keys.data(), n_keys, key_of, proofs, proof_lens, n, bits, n_bits_each, be, &t);
+    set_last_batch_timings(t);
+    size_t ok = 0;
+    for (size_t i = 0; i < n; i++) { if (accepted_each) accepted_each[i] = acc[i]; ok += acc[i]; }
+    if (n_accepted) *n_accepted = ok;
+}
+// zkaes_verify_gcm_segments_batch and _batch_gpu: the argument checks and rows of zkaes_verify_gcm_segments[_reveal], the proofs through verify_batch_keys (capi_host.cpp)
+void verify_gcm_segments_batch_call(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments,
+                                    size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                    size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted,
+                                    BatchBackend &be);
 inline size_t next_pow2(size_t n) { if (n > ((size_t)1 << 62)) throw std::length_error("size out of range"); size_t p = 1; while (p < n) p <<= 1; return p; }
 }  // namespace capi
 }  // namespace zk

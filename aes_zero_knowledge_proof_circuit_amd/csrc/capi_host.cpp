@@ -60,18 +60,19 @@ std::vector<zk::Fr> gcm_segment_public_input(size_t s, size_t n, size_t c, size_
                                 {first ? nullptr : commitments + 32 * (s - 1), 32}, {last ? nullptr : commitments + 32 * s, 32},
                                 {mask ? zk::chunk_mask_slice(mask, s, 16 * c) : nullptr, zk::mask_bytes(len)}, {mask ? revealed + 16 * c * s : nullptr, len}});
 }
-void verify_gcm_segments(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
-                         const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
-                         bool reveal, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
-    if (n_accepted) *n_accepted = 0;
-    if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
-    if (!head || !tail || !proofs || !proof_lens || !iv || !ct || !tag || !commitments || (aad_len && !aad) || (reveal && (!mask || !revealed))) throw std::invalid_argument("null argument");
+// what both verifiers of a segmented record and zkaes_gcm_segment_public_inputs check before any proof is looked at: the lengths and counts, and (keys given) that
+// the three keys fit them.  Returns n, the tail's bytes and the length block
+struct SegShape { size_t n, lt; uint8_t lenblk[16]; };
+SegShape gcm_segments_shape(const char *entry, bool with_keys, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, size_t n_segments, size_t c, const uint8_t iv[12],
+                            const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len, bool reveal,
+                            const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len) {
+    if ((with_keys && (!head || !tail)) || !iv || !ct || !tag || !commitments || (aad_len && !aad) || (reveal && (!mask || !revealed))) throw std::invalid_argument("null argument");
     if (c == 0 || ct_len == 0 || ct_len > ((size_t)1 << 20) || aad_len > ((size_t)1 << 16)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block");
     const size_t nb = (ct_len + 15) / 16, n = (nb + c - 1) / c;
     if (n < 2) throw std::invalid_argument("GCM segments: this record fits one segment; a record that fits one proof is checked with zkaes_verify_encryption_gcm");
     if (n_segments != n) throw std::invalid_argument("GCM segments: the record has " + std::to_string(n) + " segments of " + std::to_string(c) + " blocks");
     if (commitments_len != 32 * (n - 1)) throw std::invalid_argument("GCM segments: one 32-byte commitment per boundary, " + std::to_string(32 * (n - 1)) + " bytes for this record");
-    if (n > 2 && !mid_or_null) throw std::invalid_argument("GCM segments: a record of more than two segments needs the mid key");
+    if (with_keys && n > 2 && !mid_or_null) throw std::invalid_argument("GCM segments: a record of more than two segments needs the mid key");
     if (reveal) {
         if (mask_len != zk::mask_bytes(ct_len)) throw std::invalid_argument(std::string(entry) + ": ONE mask over the whole record, " + std::to_string(zk::mask_bytes(ct_len)) + " bytes for this ciphertext");
         if (revealed_len != ct_len) throw std::invalid_argument(std::string(entry) + ": ONE revealed array over the whole record, " + std::to_string(ct_len) + " bytes for this ciphertext");
@@ -88,15 +89,47 @@ void verify_gcm_segments(const char *entry, const zkaes_vk *head, const zkaes_vk
                                                                                            : " key reveals plaintext bytes: its proofs are checked with zkaes_verify_gcm_segments_reveal"));
         if (vk.num_public_inputs != bits + (reveal ? rv_bits : 0)) throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths");
     };
-    exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 16 * c, "head");
-    if (n > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, 16 * c, "mid");
-    exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, lt, "tail");
-    uint8_t lenblk[16];
+    if (with_keys) {
+        exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 16 * c, "head");
+        if (n > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, 16 * c, "mid");
+        exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, lt, "tail");
+    }
+    SegShape S;
+    S.n = n; S.lt = lt;
+    uint8_t *lenblk = S.lenblk;
     for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); }
+    return S;
+}
+void verify_gcm_segments(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                         const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
+                         bool reveal, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+    if (n_accepted) *n_accepted = 0;
+    if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+    if (!proofs || !proof_lens) throw std::invalid_argument("null argument");
+    const SegShape S = gcm_segments_shape(entry, true, head, mid_or_null, tail, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, reveal, mask, mask_len, revealed,
+                                          revealed_len);
+    const size_t n = S.n, lt = S.lt;
+    const uint8_t *lenblk = S.lenblk;
     verify_each(proofs, proof_lens, n, accepted_each, n_accepted, [&](size_t s, const zk::Proof &p) {
         return zk::verify(s == 0 ? head->vk : s + 1 == n ? tail->vk : mid_or_null->vk,
                           gcm_segment_public_input(s, n, c, lt, iv, aad, aad_len, ct, lenblk, tag, commitments, reveal ? mask : nullptr, revealed), p);
     });
+}
+// the n rows of one record as 0/1 bytes, one behind the other (ragged: head, mid and tail rows differ in length), through gcm_segment_public_input: what the per-proof
+// verifier above checks segment s against.  role: 0 head, 1 mid, 2 tail
+void gcm_segment_rows(const SegShape &S, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, const uint8_t tag[16], const uint8_t *commitments,
+                      const uint8_t *mask, const uint8_t *revealed, std::vector<uint8_t> *bits, std::vector<size_t> &lens, std::vector<int> &roles) {
+    lens.assign(S.n, 0); roles.assign(S.n, 1);
+    roles[0] = 0; roles[S.n - 1] = 2;
+    for (size_t s = 0; s < S.n; s++) {
+        const bool first = s == 0, last = s + 1 == S.n;
+        const size_t len = last ? S.lt : 16 * c;
+        lens[s] = 128 + (first ? 8 * aad_len : 0) + 8 * len + (last ? 256 : 0) + (first || last ? 256 : 512) + (mask ? 8 * zk::mask_bytes(len) + 8 * len : 0);
+        if (!bits) continue;
+        const std::vector<zk::Fr> pub = gcm_segment_public_input(s, S.n, c, S.lt, iv, aad, aad_len, ct, S.lenblk, tag, commitments, mask, revealed);
+        if (pub.size() != lens[s]) throw std::logic_error("GCM segments: a segment's public input has not the documented length");
+        for (const zk::Fr &v : pub) bits->push_back(v.is_zero() ? 0 : 1);
+    }
 }
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
 // image of the struct: reading it back from untrusted bytes put arbitrary limbs into field elements and an arbitrary byte into a bool, and skipped the curve / subgroup
@@ -106,6 +139,28 @@ constexpr uint8_t VK_MAGIC[4] = {'Z', 'V', 'K', '2'};
 namespace zk { void capi_set_error(const std::string &m) { g_err = m; } }
 namespace { thread_local zk::BatchTimings g_batch_timings; }
 namespace zk { namespace capi { void set_last_batch_timings(const BatchTimings &t) { g_batch_timings = t; } } }
+// The segment-proofs of one record through ONE multi-key batch: the checks of verify_gcm_segments, the rows of gcm_segment_public_input, head, mid and
+// tail as keys 0, 1 and 2 of verify_batch_keys (a record of two segments has no mid: its tail is key 1).  mask = NULL: plain keys
+void zk::capi::verify_gcm_segments_batch_call(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens,
+                                              size_t n_segments, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16],
+                                              const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
+                                              int *accepted_each, size_t *n_accepted, BatchBackend &be) {
+    if (n_accepted) *n_accepted = 0;
+    if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+    if (!proofs || !proof_lens) throw std::invalid_argument("null argument");
+    const bool reveal = mask != nullptr;
+    const SegShape S = gcm_segments_shape(entry, true, head, mid_or_null, tail, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, reveal, mask, mask_len, revealed,
+                                          revealed_len);
+    std::vector<uint8_t> bits;
+    std::vector<size_t> lens;
+    std::vector<int> roles;
+    gcm_segment_rows(S, c, iv, aad, aad_len, ct, tag, commitments, mask, revealed, &bits, lens, roles);
+    const zkaes_vk *vks[3] = {head, S.n > 2 ? mid_or_null : tail, tail};
+    const size_t n_keys = S.n > 2 ? 3 : 2;
+    std::vector<uint32_t> key_of(S.n);
+    for (size_t s = 0; s < S.n; s++) key_of[s] = s == 0 ? 0 : (uint32_t)(s + 1 == S.n ? n_keys - 1 : 1);
+    verify_batch_keys_call(vks, n_keys, key_of.data(), proofs, proof_lens, S.n, bits.data(), lens.data(), accepted_each, n_accepted, be);
+}
 using zk::capi::guard; using zk::capi::give; using zk::capi::fill_info; using zk::capi::next_pow2;
 
 extern "C" {
@@ -613,6 +668,37 @@ int zkaes_verify_batch_timings(double out[8]) {
         if (!out) throw std::invalid_argument("null argument");
         const zk::BatchTimings &t = g_batch_timings;
         out[0] = t.parse_ms; out[1] = t.decompress_ms; out[2] = t.transcripts_ms; out[3] = t.xhat_ms; out[4] = t.msm_ms; out[5] = t.pairing_ms; out[6] = t.total_ms; out[7] = (double)t.sub_batches;
+    });
+}
+// ---- batch verification across keys (include/zkaes.h): the host back end; the _gpu entries and the kernel probe are in capi.cpp
+int zkaes_verify_batch_keys(const zkaes_vk *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits,
+                            const size_t *n_bits_each, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        std::unique_ptr<zk::BatchBackend> be = zk::make_host_batch_backend();
+        zk::capi::verify_batch_keys_call(vks, n_keys, key_of, proofs, proof_lens, n, public_input_bits, n_bits_each, accepted_each, n_accepted, *be);
+    });
+}
+int zkaes_gcm_segment_public_inputs(size_t n_segments, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16],
+                                    const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, uint8_t *out_bits, size_t *n_bits_each,
+                                    int *roles) {
+    return guard([&] {
+        const SegShape S = gcm_segments_shape("gcm_segment_public_inputs", false, nullptr, nullptr, nullptr, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len,
+                                              mask != nullptr, mask, mask_len, revealed, ct_len);
+        std::vector<uint8_t> bits;
+        std::vector<size_t> lens;
+        std::vector<int> rl;
+        gcm_segment_rows(S, c, iv, aad, aad_len, ct, tag, commitments, mask, revealed, out_bits ? &bits : nullptr, lens, rl);
+        for (size_t s = 0; s < S.n; s++) { if (n_bits_each) n_bits_each[s] = lens[s]; if (roles) roles[s] = rl[s]; }
+        if (out_bits && !bits.empty()) memcpy(out_bits, bits.data(), bits.size());
+    });
+}
+int zkaes_verify_gcm_segments_batch(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                    const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                    size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        std::unique_ptr<zk::BatchBackend> be = zk::make_host_batch_backend();
+        zk::capi::verify_gcm_segments_batch_call("verify_gcm_segments_batch", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments,
+                                                 commitments_len, mask, mask_len, revealed, revealed_len, accepted_each, n_accepted, *be);
     });
 }
 // the rows of a chunked job for batch verification; with a mask (the _rv form) every row ends in the chunk's slice of the mask and of the revealed bytes

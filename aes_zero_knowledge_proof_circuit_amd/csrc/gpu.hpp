@@ -229,6 +229,14 @@ void fq_sqrt_batch(const Fq377 *in, size_t n, Fq377 *out, uint8_t *ok, stream_t 
 // out[i] = x^(betas[i]) over the domain of size 2^lg_m (generator gx), x = [1, row i's n_bits bits, zeros]; bits = n rows of `words` 32-bit words, LSB first.  One
 // workgroup per row; takes the indicator branch when a beta lies in the domain
 void public_input_eval(F *out, const F *betas, const uint32_t *bits, size_t words, size_t n, size_t n_bits, int lg_m, const F &gx, stream_t s);
+// The keyed form: rows of several verifying keys in one launch.  keys[k] describes key k's domain and row length (pie_key checks n_bits < 2^lg_m,
+// lg_m <= 30 and fills m_inv); proof p belongs to key key_of[p] and its row starts at word row_word_off[p] of bits -- ceil(n_bits / 32) words, possibly none.
+// h holds the HOST copies of the three tables (the device ones are their uploads) and the word count of bits: every key index and every row is checked against them
+// before the launch
+struct PieKey { F gx, m_inv; uint32_t lg_m, n_bits; };
+struct PieKeyedHost { const uint32_t *key_of; const uint32_t *row_word_off; const PieKey *keys; size_t n_keys; size_t words; };
+PieKey pie_key(int lg_m, size_t n_bits, const F &gx);
+void public_input_eval_keyed(F *out, const F *betas, const uint32_t *bits, const uint32_t *key_of, const uint32_t *row_word_off, const PieKey *keys, const PieKeyedHost &h, size_t n, stream_t s);
 
 void poly_set_at(F *p, size_t idx, const F &val, stream_t s);                 // p[idx] = val
 void poly_add_at(F *p, size_t idx, const F &val, stream_t s);                 // p[idx] += val

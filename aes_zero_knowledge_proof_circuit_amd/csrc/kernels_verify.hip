@@ -74,6 +74,50 @@ __global__ void __launch_bounds__(PIE_THREADS) k_public_input_eval(const F *__re
     if (t == 0) out[p] = shN[0] * shD[0].inverse() * vx * m_inv;
 }
 
+// The keyed form: proofs of several verifying keys in one launch.  Proof p reads its key index, takes {lg_m, n_bits, gx, m_inv} from that key's
+// descriptor and its packed bits from bits + row_word_off[p]: rows are ragged, ceil(n_bits / 32) words each, possibly none (a row without bits is never read).
+// Everything behind the descriptor is k_public_input_eval's: lg_m is the block's own, so the indicator branch's early return stays uniform over the workgroup.
+__global__ void __launch_bounds__(PIE_THREADS) k_public_input_eval_keyed(const F *__restrict__ betas, const uint32_t *__restrict__ bits, const uint32_t *__restrict__ key_of,
+                                                                         const uint32_t *__restrict__ row_word_off, const PieKey *__restrict__ keys, F *__restrict__ out) {
+    __shared__ F shN[PIE_THREADS], shD[PIE_THREADS];
+    const uint32_t p = blockIdx.x, t = threadIdx.x;
+    const PieKey *key = keys + key_of[p];
+    const int lg_m = (int)key->lg_m;
+    const uint32_t n_bits = key->n_bits, m = 1u << lg_m;
+    const F gx = key->gx;
+    const F beta = betas[p];
+    const uint32_t *row = bits + row_word_off[p];
+    F vx = beta;
+    for (int k = 0; k < lg_m; k++) vx = vx.sqr();
+    vx = vx - F::one();
+    const bool indicator = vx.is_zero();
+    const F step = gx.pow_u64(PIE_THREADS);
+    F e = gx.pow_u64(t), N = F::zero(), D = F::one();
+    for (uint32_t j = t; j < m; j += PIE_THREADS, e = e * step) {
+        const bool xj = j == 0 || (j - 1 < n_bits && ((row[(j - 1) >> 5] >> ((j - 1) & 31)) & 1));
+        if (indicator) {
+            if (e == beta) out[p] = xj ? F::one() : F::zero();
+            continue;
+        }
+        if (!xj) continue;
+        const F d = beta - e;
+        N = N * d + e * D;
+        D = D * d;
+    }
+    if (indicator) return;                                     // (uniform over the workgroup: beta and the key are the block's own)
+    shN[t] = N; shD[t] = D;
+    __syncthreads();
+    for (int h = PIE_THREADS / 2; h >= 1; h >>= 1) {
+        if ((int)t < h) {
+            const F n1 = shN[t], d1 = shD[t], n2 = shN[t + h], d2 = shD[t + h];
+            shN[t] = n1 * d2 + n2 * d1;
+            shD[t] = d1 * d2;
+        }
+        __syncthreads();
+    }
+    if (t == 0) out[p] = shN[0] * shD[0].inverse() * vx * key->m_inv;
+}
+
 void g1_decompress_check(const G1Compressed *pts, size_t n, Affine<Fq377> *out, uint8_t *status, stream_t s) {
     if (!n) return;
     if (n >= ((size_t)1 << 31)) throw GpuError("g1_decompress_check: too many points");
@@ -92,6 +136,27 @@ void public_input_eval(F *out, const F *betas, const uint32_t *bits, size_t word
         throw GpuError("public_input_eval: the rows do not fit the domain");
     const F m_inv = F::from_u64((uint64_t)1 << lg_m).inverse();
     hipLaunchKernelGGL(k_public_input_eval, dim3((unsigned)n), dim3(PIE_THREADS), 0, (hipStream_t)s, betas, bits, (uint32_t)words, (uint32_t)n_bits, lg_m, gx, m_inv, out);
+    HIP_LAUNCH_CHECK();
+}
+PieKey pie_key(int lg_m, size_t n_bits, const F &gx) {
+    if (lg_m < 0 || lg_m > 30 || n_bits >= ((size_t)1 << lg_m)) throw GpuError("public_input_eval_keyed: the rows do not fit the domain");
+    PieKey k;
+    k.gx = gx;
+    k.m_inv = F::from_u64((uint64_t)1 << lg_m).inverse();
+    k.lg_m = (uint32_t)lg_m; k.n_bits = (uint32_t)n_bits;
+    return k;
+}
+void public_input_eval_keyed(F *out, const F *betas, const uint32_t *bits, const uint32_t *key_of, const uint32_t *row_word_off, const PieKey *keys, const PieKeyedHost &h, size_t n, stream_t s) {
+    if (!n) return;
+    if (n >= ((size_t)1 << 31) || h.n_keys == 0 || h.n_keys >= ((size_t)1 << 31) || h.words >= ((size_t)1 << 31)) throw GpuError("public_input_eval_keyed: the rows do not fit the domain");
+    for (size_t k = 0; k < h.n_keys; k++)
+        if (h.keys[k].lg_m > 30 || h.keys[k].n_bits >= ((uint32_t)1 << h.keys[k].lg_m) || (h.keys[k].n_bits + 31) / 32 >= ((uint32_t)1 << 26)) throw GpuError("public_input_eval_keyed: the rows do not fit the domain");
+    for (size_t p = 0; p < n; p++) {                           // every row lies inside the packed buffer: the kernel reads row_word_off[p] .. + ceil(n_bits / 32) and nothing else
+        if (h.key_of[p] >= h.n_keys) throw GpuError("public_input_eval_keyed: key index out of range");
+        const size_t w = (h.keys[h.key_of[p]].n_bits + 31) / 32;
+        if ((size_t)h.row_word_off[p] > h.words || w > h.words - h.row_word_off[p]) throw GpuError("public_input_eval_keyed: a row lies outside the packed bits");
+    }
+    hipLaunchKernelGGL(k_public_input_eval_keyed, dim3((unsigned)n), dim3(PIE_THREADS), 0, (hipStream_t)s, betas, bits, key_of, row_word_off, keys, out);
     HIP_LAUNCH_CHECK();
 }
 

@@ -1469,7 +1469,7 @@ struct DeviceBatchBackend : BatchBackend {
     gpu::DevPtr<Affine28<Fq377P>> bases28, w28;      // np x VB_OWN own points then the key's VB_SHARED | W_beta, W_gamma of every proof
     gpu::DevPtr<F> d_own, d_shared, d_w;
     const Fr *own_up = nullptr, *w_up = nullptr;     // the host arrays d_own / d_w hold
-    size_t np = 0;
+    size_t np = 0, nkeys = 1;
     void decompress(const G1Compressed *pts, size_t n, G1A *out, uint8_t *status) override {
         gpu::DevPtr<G1Compressed> d_pts(n);
         gpu::DevPtr<G1A> d_out(n);
@@ -1490,29 +1490,58 @@ struct DeviceBatchBackend : BatchBackend {
         gpu::public_input_eval(d_out, d_betas, d_bits, words, n, n_bits, lg_m, domain_gen(lg_m), s);
         gpu::d2h(out, d_out, n * sizeof(F), s);
     }
-    void set_bases(const G1A *own, size_t np_, const G1A *shared) override {
-        np = np_;
-        const size_t nb = np * VB_OWN + VB_SHARED;
+    // the keyed form: one launch of k_public_input_eval_keyed over ragged packed rows; a key no proof of the call names gets an empty descriptor
+    void public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t n_keys, const uint32_t *key_of, const Fr *betas, const uint8_t *bits, const size_t *row_off, size_t n,
+                                 Fr *out) override {
+        if (!n) return;
+        std::vector<uint8_t> used(n_keys, 0);
+        for (size_t i = 0; i < n; i++) { if (key_of[i] >= n_keys) throw std::invalid_argument("public_input_eval_keyed: key index out of range"); used[key_of[i]] = 1; }
+        std::vector<gpu::PieKey> keys(n_keys);
+        for (size_t k = 0; k < n_keys; k++) keys[k] = used[k] ? gpu::pie_key(lg_m[k], n_bits[k], domain_gen(lg_m[k])) : gpu::pie_key(0, 0, domain_gen(0));
+        std::vector<uint32_t> woff(n);
+        size_t words = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (words >= ((size_t)1 << 31)) throw std::invalid_argument("public_input_eval_keyed: too many public-input bits for one call");
+            woff[i] = (uint32_t)words; words += (n_bits[key_of[i]] + 31) / 32;
+        }
+        std::vector<uint32_t> packed(words + 1, 0);
+        for (size_t i = 0; i < n; i++) { const uint8_t *r = bits + row_off[i]; for (size_t j = 0; j < n_bits[key_of[i]]; j++) if (r[j]) packed[woff[i] + (j >> 5)] |= 1u << (j & 31); }
+        gpu::DevPtr<uint32_t> d_bits(packed.size()), d_key_of(n), d_woff(n);
+        gpu::DevPtr<gpu::PieKey> d_keys(n_keys);
+        gpu::DevPtr<F> d_betas(n), d_out(n);
+        gpu::h2d(d_bits, packed.data(), packed.size() * 4, s);
+        gpu::h2d(d_key_of, key_of, n * 4, s);
+        gpu::h2d(d_woff, woff.data(), n * 4, s);
+        gpu::h2d(d_keys, keys.data(), n_keys * sizeof(gpu::PieKey), s);
+        gpu::h2d(d_betas, betas, n * sizeof(F), s);
+        const gpu::PieKeyedHost h = {key_of, woff.data(), keys.data(), n_keys, words};
+        gpu::public_input_eval_keyed(d_out, d_betas, d_bits, d_key_of, d_woff, d_keys, h, n, s);
+        gpu::d2h(out, d_out, n * sizeof(F), s);
+    }
+    void set_bases(const G1A *own, size_t np_, const G1A *shared) override { set_bases_keyed(own, np_, shared, 1); }
+    void set_bases_keyed(const G1A *own, size_t np_, const G1A *shared, size_t n_keys) override {
+        np = np_; nkeys = n_keys;
+        const size_t nb = np * VB_OWN + nkeys * VB_SHARED;
         std::vector<G1A> w(2 * np);
         for (size_t i = 0; i < np; i++) { w[2 * i] = own[i * VB_OWN + 11]; w[2 * i + 1] = own[i * VB_OWN + 12]; }
         gpu::DevPtr<G1A> tmp(nb + 2 * np);
         gpu::h2d(tmp, own, np * VB_OWN * sizeof(G1A), s);
-        gpu::h2d(tmp + np * VB_OWN, shared, VB_SHARED * sizeof(G1A), s);
+        gpu::h2d(tmp + np * VB_OWN, shared, nkeys * VB_SHARED * sizeof(G1A), s);
         gpu::h2d(tmp + nb, w.data(), w.size() * sizeof(G1A), s);
         bases28.alloc(nb); w28.alloc(2 * np);
         gpu::convert_bases<Bls377>(bases28, tmp, nb, s);
         gpu::convert_bases<Bls377>(w28, tmp + nb, 2 * np, s);
-        d_own.alloc(np * VB_OWN); d_shared.alloc(VB_SHARED); d_w.alloc(2 * np);
+        d_own.alloc(np * VB_OWN); d_shared.alloc(nkeys * VB_SHARED); d_w.alloc(2 * np);
         own_up = w_up = nullptr;
         gpu::sync(s);
     }
     XYZZ<Fq377> msm_main(const Fr *own_scalars, size_t lo, size_t hi, const Fr *shared_scalars) override {
         if (lo >= hi || hi > np) throw std::invalid_argument("verify_batch: bad sub-batch range");
         if (own_up != own_scalars) { gpu::h2d(d_own, own_scalars, np * VB_OWN * sizeof(F), s); own_up = own_scalars; }
-        gpu::h2d(d_shared, shared_scalars, VB_SHARED * sizeof(F), s);
+        gpu::h2d(d_shared, shared_scalars, nkeys * VB_SHARED * sizeof(F), s);
         gpu::sync(s);
-        // bases index from the range's first point: the key's ten sit (np - lo) x VB_OWN further on
-        gpu::msm_prepare<Bls377>(ws, d_own + lo * VB_OWN, (hi - lo) * VB_OWN, d_shared, VB_SHARED, (np - lo) * VB_OWN, s);
+        // bases index from the range's first point: the keys' ten each sit (np - lo) x VB_OWN further on
+        gpu::msm_prepare<Bls377>(ws, d_own + lo * VB_OWN, (hi - lo) * VB_OWN, d_shared, nkeys * VB_SHARED, (np - lo) * VB_OWN, s);
         return gpu::msm_finish<Bls377>(ws, bases28 + lo * VB_OWN, s);
     }
     XYZZ<Fq377> msm_w(const Fr *w_scalars, size_t lo, size_t hi) override {

@@ -599,22 +599,26 @@ XYZZ<Fq377> host_msm(const G1A *bases, const Fr *scalars, size_t n, int bits) {
 }
 
 struct HostBatchBackend : BatchBackend {
-    std::vector<G1A> bases;      // np x VB_OWN own points, then the key's VB_SHARED
-    size_t np = 0;
+    std::vector<G1A> bases;      // np x VB_OWN own points, then VB_SHARED per key
+    size_t np = 0, nkeys = 1;
     void decompress(const G1Compressed *pts, size_t n, G1A *out, uint8_t *status) override {
         for (size_t i = 0; i < n; i++) status[i] = g1_decompress_check(sqrt_consts(), pts[i].x, pts[i].y_gt != 0, out[i]);
     }
     void public_input_eval(int lg_m, const Fr *betas, const uint8_t *bits, size_t n, size_t n_bits, Fr *out) override {
         for (size_t i = 0; i < n; i++) out[i] = host_public_input_eval(lg_m, betas[i], bits + i * n_bits, n_bits);
     }
-    void set_bases(const G1A *own, size_t np_, const G1A *shared) override {
-        np = np_;
+    void public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t, const uint32_t *key_of, const Fr *betas, const uint8_t *bits, const size_t *row_off, size_t n, Fr *out) override {
+        for (size_t i = 0; i < n; i++) out[i] = host_public_input_eval(lg_m[key_of[i]], betas[i], bits + row_off[i], n_bits[key_of[i]]);
+    }
+    void set_bases(const G1A *own, size_t np_, const G1A *shared) override { set_bases_keyed(own, np_, shared, 1); }
+    void set_bases_keyed(const G1A *own, size_t np_, const G1A *shared, size_t n_keys) override {
+        np = np_; nkeys = n_keys;
         bases.assign(own, own + np * VB_OWN);
-        bases.insert(bases.end(), shared, shared + VB_SHARED);
+        bases.insert(bases.end(), shared, shared + nkeys * VB_SHARED);
     }
     XYZZ<Fq377> msm_main(const Fr *own_scalars, size_t lo, size_t hi, const Fr *shared_scalars) override {
         XYZZ<Fq377> r = host_msm(&bases[lo * VB_OWN], own_scalars + lo * VB_OWN, (hi - lo) * VB_OWN, Fr::BITS);
-        r.add(host_msm(&bases[np * VB_OWN], shared_scalars, VB_SHARED, Fr::BITS));
+        r.add(host_msm(&bases[np * VB_OWN], shared_scalars, nkeys * VB_SHARED, Fr::BITS));
         return r;
     }
     XYZZ<Fq377> msm_w(const Fr *w_scalars, size_t lo, size_t hi) override {
@@ -743,6 +747,167 @@ std::vector<uint8_t> verify_batch(const VerifyingKey &vk, const uint8_t *proofs,
     };
     // bisection: a range that holds is accepted whole; one that fails is halved, and a lone proof's answer is its own two equations under its own randomizers.
     // When the left half of a failing range holds, the right half is known to fail and is not checked again as a whole
+    std::function<bool(size_t, size_t, bool)> solve = [&](size_t lo, size_t hi, bool known_bad) {
+        if (!known_bad && holds(lo, hi)) { for (size_t a = lo; a < hi; a++) accepted[alive[a]] = 1; return true; }
+        if (hi - lo == 1) return false;
+        const size_t mid = lo + (hi - lo) / 2;
+        const bool left = solve(lo, mid, false);
+        solve(mid, hi, left);
+        return false;
+    };
+    solve(0, np, false);
+    T.total_ms = ms_since(t_all);
+    if (timings) *timings = T;
+    return accepted;
+}
+
+// verify_batch over proofs of several keys.  kzg_setup_points draws beta, g, gamma_g and h from one fixed stream whatever the SRS size, so the keys of this
+// library share g, gamma_g, h and beta_h, and the batch equation holds over proofs of different keys with every key's index commitments and shift powers as further
+// bases.  Per key: the transcript prefix, scalar_rows' sizes and the domain X of x^(beta).  The stages, the bisection and the timings are verify_batch's
+std::vector<uint8_t> verify_batch_keys(const VerifyingKey *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *bits,
+                                       const size_t *n_bits_each, BatchBackend &be, BatchTimings *timings) {
+    BatchTimings T;
+    const auto t_all = Clock::now();
+    if (n_keys == 0) throw std::invalid_argument("verify_batch_keys: at least one verifying key");
+    if (n_keys > ((size_t)1 << 16)) throw std::invalid_argument("verify_batch_keys: at most 65536 verifying keys");
+    for (size_t i = 0; i < n; i++) if (key_of[i] >= n_keys) throw std::invalid_argument("verify_batch_keys: proof " + std::to_string(i) + " names key " + std::to_string(key_of[i]) + " of " + std::to_string(n_keys));
+    auto same_g2 = [](const pairing::G2Affine &a, const pairing::G2Affine &b) { return a.inf == b.inf && a.x == b.x && a.y == b.y; };
+    auto same_g1 = [](const G1A &a, const G1A &b) { return a.x == b.x && a.y == b.y; };
+    for (size_t k = 1; k < n_keys; k++)
+        if (!same_g1(vks[k]->g, vks[0]->g) || !same_g1(vks[k]->gamma_g, vks[0]->gamma_g) || !same_g2(vks[k]->h, vks[0]->h) || !same_g2(vks[k]->beta_h, vks[0]->beta_h))
+            throw std::invalid_argument("verify_batch_keys: the keys do not share one setup (g, gamma_g, h and beta_h of key " + std::to_string(k) + " differ from key 0's)");
+    std::vector<uint8_t> accepted(n, 0);
+    std::vector<size_t> nh(n_keys), nk(n_keys), mk(n_keys), kbits(n_keys);      // per key: |H|, |K|, |X| and the row length the back end evaluates (|X| - 1)
+    std::vector<int> lgm(n_keys);
+    for (size_t k = 0; k < n_keys; k++) {
+        nh[k] = next_pow2(vks[k]->num_constraints); nk[k] = next_pow2(vks[k]->num_non_zero); mk[k] = vks[k]->num_instance;
+        if (mk[k] == 0 || (mk[k] & (mk[k] - 1))) mk[k] = 0;                      // |X| no power of two: no row pads to it, every proof of the key is rejected
+    }
+    // ---- parse; the points stay compressed.  A row that does not pad to its own key's |X| rejects its proof alone
+    auto t0 = Clock::now();
+    std::vector<size_t> offs(n + 1, 0), roffs(n + 1, 0);
+    for (size_t i = 0; i < n; i++) { offs[i + 1] = offs[i] + proof_lens[i]; roffs[i + 1] = roffs[i] + n_bits_each[i]; }
+    std::vector<RawProof> raw(n);
+    std::vector<size_t> alive;
+    for (size_t i = 0; i < n; i++) {
+        if (n_bits_each[i] >= ((size_t)1 << 46) || next_pow2(n_bits_each[i] + 1) != mk[key_of[i]]) continue;
+        if (parse_raw_proof(proofs + offs[i], proof_lens[i], raw[i])) alive.push_back(i);
+    }
+    T.parse_ms = ms_since(t0);
+    // ---- decompression and subgroup checks, every point of every parsed proof in one call
+    t0 = Clock::now();
+    std::vector<G1A> own;
+    {
+        std::vector<G1Compressed> todo;
+        std::vector<size_t> where;
+        for (size_t a = 0; a < alive.size(); a++) for (size_t s = 0; s < VB_OWN; s++) if (!raw[alive[a]].inf[s]) { todo.push_back(raw[alive[a]].pts[s]); where.push_back(a * VB_OWN + s); }
+        std::vector<G1A> pts(todo.size() ? todo.size() : 1);
+        std::vector<uint8_t> st(todo.size() ? todo.size() : 1, 0);
+        if (!todo.empty()) be.decompress(todo.data(), todo.size(), pts.data(), st.data());
+        std::vector<G1A> all(alive.size() * VB_OWN, G1A::inf());
+        std::vector<uint8_t> bad(alive.size(), 0);
+        for (size_t j = 0; j < todo.size(); j++) { if (st[j] != G1_OK) bad[where[j] / VB_OWN] = 1; else all[where[j]] = pts[j]; }
+        std::vector<size_t> keep;
+        for (size_t a = 0; a < alive.size(); a++) if (!bad[a]) { keep.push_back(alive[a]); own.insert(own.end(), all.begin() + a * VB_OWN, all.begin() + (a + 1) * VB_OWN); }
+        alive.swap(keep);
+    }
+    T.decompress_ms = ms_since(t0);
+    const size_t np = alive.size();
+    if (np == 0) { T.total_ms = ms_since(t_all); if (timings) *timings = T; return accepted; }
+    // ---- transcripts: one prefix per key, the proof's own key's sizes
+    t0 = Clock::now();
+    std::vector<Bytes> prefix(n_keys);
+    std::vector<uint8_t> have_prefix(n_keys, 0);
+    std::vector<Challenges> ch(np);
+    std::vector<Fr> betas(np);
+    std::vector<uint32_t> akey(np);
+    std::vector<size_t> arow(np);             // where the survivor's row starts in the caller's bits
+    for (size_t a = 0; a < np; a++) {
+        const size_t i = alive[a], k = key_of[i];
+        if (!have_prefix[k]) { prefix[k] = transcript_prefix(*vks[k]); have_prefix[k] = 1; }
+        akey[a] = (uint32_t)k; arow[a] = roffs[i];
+        ch[a] = run_transcript(prefix[k], nh[k], mk[k], bits + roffs[i], n_bits_each[i], &own[a * VB_OWN], raw[i].evals);
+        betas[a] = ch[a].beta;
+    }
+    T.transcripts_ms = ms_since(t0);
+    // ---- x^(beta_i), every proof over its own key's X.  The back end takes ONE row length per key: rows are handed over zero-padded to |X| - 1, the same statement
+    t0 = Clock::now();
+    std::vector<Fr> xhat(np);
+    {
+        std::vector<size_t> prow(np);
+        size_t total = 0;
+        for (size_t k = 0; k < n_keys; k++) { lgm[k] = mk[k] ? log2_exact(mk[k]) : 0; kbits[k] = mk[k] ? mk[k] - 1 : 0; }
+        for (size_t a = 0; a < np; a++) { prow[a] = total; total += kbits[akey[a]]; }
+        std::vector<uint8_t> padded(total ? total : 1, 0);
+        for (size_t a = 0; a < np; a++) { const size_t nb = n_bits_each[alive[a]]; if (nb) memcpy(&padded[prow[a]], bits + arow[a], nb); }
+        be.public_input_eval_keyed(lgm.data(), kbits.data(), n_keys, akey.data(), betas.data(), padded.data(), prow.data(), np, xhat.data());
+    }
+    T.xhat_ms = ms_since(t0);
+    // ---- randomizers: as verify_batch's, over every key and every proof with its key index and its row
+    t0 = Clock::now();
+    ChaChaRng rrng;
+    {
+        Bytes d;
+        static const char domain[] = "zkaes verify_batch_keys v1";
+        d.put(domain, sizeof domain);
+        d.u64(n_keys);
+        for (size_t k = 0; k < n_keys; k++) { std::vector<uint8_t> ark = serialize_vk_ark(*vks[k]); d.u64(ark.size()); d.put(ark.data(), ark.size()); }
+        d.u64(n);
+        for (size_t i = 0; i < n; i++) {
+            d.u64(key_of[i]); d.u64(n_bits_each[i]);
+            d.u64(proof_lens[i]); d.put(proofs + offs[i], proof_lens[i]);
+            for (size_t j = 0; j < n_bits_each[i]; j++) d.u8(bits[roffs[i] + j] ? 1 : 0);
+        }
+        const size_t whole = d.b.size() / 64 * 64;
+        uint8_t h[32], seed[32];
+        sha256_chain(nullptr, d.b.data(), whole, h);
+        sha256_finish(h, whole, d.b.data() + whole, d.b.size() - whole, seed);
+        rrng.reseed(seed, 20);
+    }
+    auto draw128 = [&]() {
+        for (;;) {
+            uint64_t lo = rrng.next_u64(), hi = rrng.next_u64();
+            if (!(lo | hi)) continue;          // a zero weight would take its equation out of the check
+            uint32_t r[8] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32), 0, 0, 0, 0};
+            return Fr::from_raw(r);
+        }
+    };
+    std::vector<Fr> rnd(2 * n);               // drawn for every proof of the call, in order, whether it is still in the batch or not
+    for (auto &r : rnd) r = draw128();
+    std::vector<Fr> own_sc(np * VB_OWN), w_sc(2 * np);
+    std::vector<Rows> rows(np);
+    for (size_t a = 0; a < np; a++) {
+        const size_t i = alive[a], k = akey[a];
+        rows[a] = scalar_rows(*vks[k], nh[k], mk[k], nk[k], ch[a], xhat[a], raw[i].evals, raw[i].random_v_beta, rnd[2 * i], rnd[2 * i + 1]);
+        for (size_t s = 0; s < VB_OWN; s++) own_sc[a * VB_OWN + s] = rows[a].own[s];
+        w_sc[2 * a] = rows[a].w[0]; w_sc[2 * a + 1] = rows[a].w[1];
+    }
+    T.transcripts_ms += ms_since(t0);
+    std::vector<G1A> shared(n_keys * VB_SHARED);
+    for (size_t k = 0; k < n_keys; k++) {
+        G1A *sk = &shared[k * VB_SHARED];
+        for (int i = 0; i < 6; i++) sk[K_IX + i] = vks[k]->index_comms[i];
+        sk[K_SP] = vks[k]->shift_powers[0]; sk[K_SP + 1] = vks[k]->shift_powers[1]; sk[K_G] = vks[k]->g; sk[K_GG] = vks[k]->gamma_g;
+    }
+    t0 = Clock::now();
+    be.set_bases_keyed(own.data(), np, shared.data(), n_keys);
+    T.msm_ms += ms_since(t0);
+    // ---- the batch equation over proofs [lo, hi) of the survivors: every proof's shared scalars go into its own key's slot
+    std::vector<Fr> sh(n_keys * VB_SHARED);
+    auto holds = [&](size_t lo, size_t hi) {
+        auto t1 = Clock::now();
+        for (auto &v : sh) v = Fr::zero();
+        for (size_t a = lo; a < hi; a++) for (size_t s = 0; s < VB_SHARED; s++) sh[akey[a] * VB_SHARED + s] = sh[akey[a] * VB_SHARED + s] + rows[a].shared[s];
+        XYZZ<Fq377> total_c = be.msm_main(own_sc.data(), lo, hi, sh.data()), total_w = be.msm_w(w_sc.data(), lo, hi);
+        T.msm_ms += ms_since(t1);
+        t1 = Clock::now();
+        G1A Ps[2] = {total_w.neg().to_affine(), total_c.to_affine()};
+        pairing::G2Affine Qs[2] = {vks[0]->beta_h, vks[0]->h};
+        bool ok = pairing::pairing_product_is_one(Ps, Qs, 2);
+        T.pairing_ms += ms_since(t1);
+        T.sub_batches++;
+        return ok;
+    };
     std::function<bool(size_t, size_t, bool)> solve = [&](size_t lo, size_t hi, bool known_bad) {
         if (!known_bad && holds(lo, hi)) { for (size_t a = lo; a < hi; a++) accepted[alive[a]] = 1; return true; }
         if (hi - lo == 1) return false;

@@ -1,4 +1,5 @@
-// csrc/verify_batch.hpp -- the batch verifier: n proofs under ONE verifying key, each with its own public input, one product of two pairings.
+// csrc/verify_batch.hpp -- the batch verifier: n proofs under ONE verifying key, each with its own public input, one product of two pairings;
+// and (9k) n proofs under several keys of one setup, still one product of two pairings.
 // Host-only header: the protocol (parse, transcripts, scalar rows, randomizers, bisection, pairing) lives in marlin_codec.cpp and reaches the elliptic-curve work
 // through BatchBackend -- the host implementation in the same file, the device one (kernels_verify.hip + the variable-base MSM) in marlin.cpp.
 #pragma once
@@ -30,6 +31,14 @@ struct BatchBackend {
     virtual XYZZ<Fq377> msm_main(const Fr *own_scalars, size_t lo, size_t hi, const Fr *shared_scalars) = 0;
     // sum over proofs lo <= i < hi of w_scalars[i][0] * W_beta(i) + w_scalars[i][1] * W_gamma(i)   (128-bit scalars)
     virtual XYZZ<Fq377> msm_w(const Fr *w_scalars, size_t lo, size_t hi) = 0;
+    // ---- the keyed forms: proofs of n_keys verifying keys in one batch
+    // out[i] = x^(beta_i) over the domain of proof i's key: key k has |X| = 2^lg_m[k] and rows of n_bits[k] 0/1 bytes; proof i belongs to key key_of[i] and its row
+    // starts at bits + row_off[i] (rows are ragged and may be empty)
+    virtual void public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t n_keys, const uint32_t *key_of, const Fr *betas, const uint8_t *bits, const size_t *row_off, size_t n,
+                                         Fr *out) = 0;
+    // set_bases for n_keys keys: np x VB_OWN own points, then n_keys x VB_SHARED key points (key-major).  msm_main then takes n_keys x VB_SHARED shared scalars:
+    // per key the sums over the sub-batch's proofs of that key.  set_bases is this call with one key
+    virtual void set_bases_keyed(const G1A *own, size_t np, const G1A *shared, size_t n_keys) = 0;
 };
 std::unique_ptr<BatchBackend> make_host_batch_backend();      // the HIP-free implementation: one object per call
 std::unique_ptr<BatchBackend> make_device_batch_backend();    // marlin.cpp: kernels_verify.hip + the variable-base MSM; throws GpuError without a device
@@ -37,6 +46,12 @@ std::unique_ptr<BatchBackend> make_device_batch_backend();    // marlin.cpp: ker
 // public_input_bits: n rows of n_bits bytes (any non-zero byte is a One).  accepted[i] = 1 / 0.  Never throws on what the proof BYTES hold
 std::vector<uint8_t> verify_batch(const VerifyingKey &vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits,
                                   BatchBackend &be, BatchTimings *timings = nullptr);
+
+// The same over proofs of n_keys verifying keys that share one setup (g, gamma_g, h, beta_h: every key this library synthesizes does), DESIGN.md 9k: proof i is checked
+// under vks[key_of[i]] against the row of n_bits_each[i] bytes that starts where the rows before it end.  One pairing product for the whole batch.  Throws
+// std::invalid_argument for n_keys = 0, a key index out of range or keys of different setups; a row that does not pad to its own key's |X| rejects that proof alone
+std::vector<uint8_t> verify_batch_keys(const VerifyingKey *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n,
+                                       const uint8_t *public_input_bits, const size_t *n_bits_each, BatchBackend &be, BatchTimings *timings = nullptr);
 
 // host probes of the pieces (tests): parse 48 compressed bytes; false = malformed (both flags, x >= q, infinity over a non-zero x).  *inf: the infinity encoding
 bool g1_parse_compressed(const uint8_t bytes[48], G1Compressed &out, bool *inf);

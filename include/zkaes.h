@@ -776,6 +776,40 @@ int zkaes_chunk_public_inputs(int circuit_kind, size_t n_chunks, const uint8_t *
 int zkaes_g1_decompress_batch(const uint8_t *points48, size_t n, uint8_t *out_xy, uint8_t *status);
 int zkaes_fq_sqrt_batch(const uint8_t *in, size_t n, uint8_t *out, uint8_t *is_square);
 int zkaes_public_input_eval(int lg_m, const uint8_t *betas, const uint8_t *bits, size_t n, size_t n_bits, uint8_t *out);
+/* ---- batch verification across keys.  zkaes_verify_batch over proofs of n_keys verifying keys: proof i is checked under vks[key_of[i]] against its own
+ * row of n_bits_each[i] 0/1 bytes; the rows lie one behind the other in public_input_bits (NULL when they are all empty).  Still two MSMs and ONE pairing product per
+ * (sub-)batch: every key this library synthesizes has the same g, gamma_g, h and beta_h (the setup draws them from one fixed stream whatever the SRS size), so the batch
+ * equation of zkaes_verify_batch holds over proofs of different keys, with each key's 6 index commitments and 2 shift powers as further bases (13 n + 10 n_keys in all).
+ * The answers are those of n calls of zkaes_verify, proof i under its own key.  Errors of the call, before any work: n_keys = 0, a key index >= n_keys, and keys whose
+ * g, gamma_g, h or beta_h differ ("the keys do not share one setup").  A row that does not pad to its own key's |X| rejects that proof alone.  The randomizers are
+ * drawn as zkaes_verify_batch draws them, seeded over a domain string of their own, every key's ark-serialize bytes, n, and every proof's key index, row length, length,
+ * bytes and bits.  zkaes_verify_batch_timings reports the last call of either family.  The _gpu form runs the point checks, the public-input evaluation (one launch
+ * over all keys) and the MSMs on the device. */
+int zkaes_verify_batch_keys(const zkaes_vk *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits,
+                            const size_t *n_bits_each, int *accepted_each, size_t *n_accepted);
+int zkaes_verify_batch_keys_gpu(const zkaes_vk *const *vks, size_t n_keys, const uint32_t *key_of, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits,
+                                const size_t *n_bits_each, int *accepted_each, size_t *n_accepted);
+/* The public-input rows of a segmented GCM record (host only): row s is exactly what zkaes_verify_gcm_segments (mask = NULL) or zkaes_verify_gcm_segments_reveal (ONE mask
+ * of mask_len bytes over the record and its ciphertext_len revealed bytes) checks segment s against.  The rows are ragged -- head, mid and tail differ -- and are written
+ * one behind the other; n_bits_each[s] receives row s's length and roles[s] 0 (head), 1 (mid) or 2 (tail); both may be NULL.  out_bits = NULL only asks for the sizes.
+ * The lengths and counts are checked as zkaes_verify_gcm_segments checks them, with the same messages. */
+int zkaes_gcm_segment_public_inputs(size_t n_segments, size_t c, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len,
+                                    const uint8_t tag16[16], const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed,
+                                    uint8_t *out_bits, size_t *n_bits_each, int *roles);
+/* zkaes_verify_gcm_segments (mask = NULL: plain keys; mask_len, revealed and revealed_len are then ignored) or zkaes_verify_gcm_segments_reveal (mask != NULL) through ONE
+ * zkaes_verify_batch_keys call: the same argument and key-fit checks, the same errors and the same per-segment answers; head, mid and tail are keys 0, 1 and 2 (a record
+ * of two segments has no mid key: its tail is key 1).  The three keys must share one setup. */
+int zkaes_verify_gcm_segments_batch(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                    const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
+                                    const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each,
+                                    size_t *n_accepted);
+int zkaes_verify_gcm_segments_batch_gpu(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                        const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
+                                        const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
+                                        int *accepted_each, size_t *n_accepted);
+/* The keyed public-input kernel, one launch per call (tests): zkaes_public_input_eval over rows of n_keys domains.  Key k has |X| = 2^lg_m[k] and rows of n_bits[k] 0/1
+ * bytes; row i belongs to key key_of[i] and follows row i - 1 in bits.  out[i] = x^(betas[i]) over row i's own domain. */
+int zkaes_public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t n_keys, const uint32_t *key_of, const uint8_t *betas, const uint8_t *bits, size_t n, uint8_t *out);
 /* AES witness only: fills z (padded instance + witness, one byte per variable) for a message under the key's circuit */
 int zkaes_aes_witness(const zkaes_pk *pk, const uint8_t *message, size_t message_len, const uint8_t secret_key[16], uint8_t *z, size_t z_cap, size_t *z_len);
 
