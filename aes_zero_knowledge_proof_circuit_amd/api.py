@@ -173,8 +173,8 @@ class ProvingKey:
         return int(n.value)
 
     def key_tag_blocks(self):
-        """T = 0, 1 or 2: the key-tag blocks this proving key was synthesized with (synthesize_keys(..., key_tag_blocks=)); the last 128 T public-input bits of every proof
-        it makes are key_tag(secret_key, T)"""
+        """T = 0, 1 or 2: the key-tag blocks this proving key was synthesized with (synthesize_keys(..., key_tag_blocks=), or a head of synthesize_keys_gcm_segment(..., key_tag_blocks=));
+        128 T public-input bits of every proof it makes are key_tag(secret_key, T): the last ones ahead of a digest's states and a reveal key's mask and revealed bytes"""
         n = C.c_size_t()
         _check(lib().zkaes_pk_key_tag_blocks(self._p, C.byref(n)))
         return int(n.value)
@@ -1098,6 +1098,9 @@ _SEG_ROLES = {"head": SEG_HEAD, "mid": SEG_MID, "tail": SEG_TAIL, SEG_HEAD: SEG_
 # the largest c (data blocks per segment) at which all three roles stay inside the default SRS literal, per key size (tests/test_gcm_segments_host.py)
 GCM_SEGMENT_DEFAULT_C = {128: 4, 192: 3, 256: 2}
 GCM_SEGMENT_REVEAL_DEFAULT_C = dict(GCM_SEGMENT_DEFAULT_C)      # reveal segment keys fit the same c (the capacity table; tests/test_gcm_segments_reveal_host.py asserts it)
+# the same per key-tag blocks T of the head (the capacity table; tests/test_gcm_segments_keytag_host.py asserts it): one tag block fits the default c of
+# every key size, with and without reveal, up to 13 bytes of aad; two tag blocks need one block less per segment
+GCM_SEGMENT_KEYTAG_DEFAULT_C = {0: dict(GCM_SEGMENT_DEFAULT_C), 1: {128: 4, 192: 3, 256: 2}, 2: {128: 3, 192: 2, 256: 1}}
 
 
 def verify_encryption_gcm_reveal(verifying_key, proof, iv, aad, ciphertext, tag, mask, revealed, key_tag=None, h_out=None, h_in=None):
@@ -1123,42 +1126,64 @@ def _seg_role(role):
     return _SEG_ROLES[role]
 
 
-def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, reveal=False):
+def _seg_key_tag_blocks(key_tag_blocks):
+    if key_tag_blocks not in (0, 1, 2):
+        raise ZkAesError("key_tag_blocks must be 0, 1 or 2")
+    return int(key_tag_blocks)
+
+
+def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, reveal=False, key_tag_blocks=0):
     """(ProvingKey, VerifyingKey) of one segment role.  role: "head", "mid" or "tail"; units: c, the data blocks per segment, for a head or mid, and Lt, the bytes of
-    the record's last segment (1 .. 16 c), for a tail; aad_length: the record's whole aad, head only.  flags and key_bits as synthesize_keys; no key tag, no digest.
+    the record's last segment (1 .. 16 c), for a tail; aad_length: the record's whole aad, head only.  flags and key_bits as synthesize_keys; no digest.
     reveal: False (the default) or True: every proof of the key also exposes the segment's slice of the record's mask and of its revealed bytes, is made through
-    encrypt_gcm_segments(..., mask=) and checked with verify_gcm_segments(..., mask=, revealed=)"""
+    encrypt_gcm_segments(..., mask=) and checked with verify_gcm_segments(..., mask=, revealed=).
+    key_tag_blocks: 0 (the default: the key as it was), 1 or 2 for a HEAD: every proof of the key also exposes key_tag(secret_key, key_tag_blocks) and is
+    checked with verify_gcm_segments(..., key_tag=); the proving calls are the same.  A mid or tail with key_tag_blocks != 0 raises: the head carries the record's tag
+    and the boundary commitments carry the key to every later segment"""
     pk, vk = C.c_void_p(), C.c_void_p()
+    if _seg_key_tag_blocks(key_tag_blocks):
+        _check(lib().zkaes_synthesize_keys_gcm_seg_kt(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_uint(key_tag_blocks), C.c_size_t(units), C.c_size_t(aad_length),
+                                                      C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
+        return ProvingKey(pk.value), VerifyingKey(vk.value)
     _check(lib().zkaes_synthesize_keys_gcm_seg_rv(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), C.c_size_t(srs[0]),
                                                   C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
     return ProvingKey(pk.value), VerifyingKey(vk.value)
 
 
-def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128, reveal=False):
+def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128, reveal=False, key_tag_blocks=0):
     out = (C.c_uint64 * 12)()
-    _check(lib().zkaes_circuit_info_gcm_seg_rv(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), out))
+    if _seg_key_tag_blocks(key_tag_blocks):
+        _check(lib().zkaes_circuit_info_gcm_seg_kt(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_uint(key_tag_blocks), C.c_size_t(units), C.c_size_t(aad_length), out))
+    else:
+        _check(lib().zkaes_circuit_info_gcm_seg_rv(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), out))
     keys = ["raw_constraints", "raw_instance", "raw_witness", "nnz_a", "nnz_b", "nnz_c", "constraints", "instance", "witness", "joint_nnz", "h", "k"]
     return dict(zip(keys, out))
 
 
-def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128, reveal=False):
+def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128, reveal=False, key_tag_blocks=0):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    head = (_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), which)
-    _check(lib().zkaes_circuit_matrix_gcm_seg_rv(*head, C.byref(rows), C.byref(nnz), None, None, None))
+    fn, head = lib().zkaes_circuit_matrix_gcm_seg_rv, (_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), which)
+    if _seg_key_tag_blocks(key_tag_blocks):
+        fn, head = lib().zkaes_circuit_matrix_gcm_seg_kt, head[:3] + (C.c_uint(key_tag_blocks),) + head[3:]
+    _check(fn(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
     col = np.zeros(max(nnz.value, 1), dtype=np.uint32)
     coeff = np.zeros(max(nnz.value, 1), dtype=np.int64)
-    _check(lib().zkaes_circuit_matrix_gcm_seg_rv(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
+    _check(fn(*head, None, None, rowptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), coeff.ctypes.data_as(C.c_void_p)))
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 
-def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128, reveal=False):
+def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128, reveal=False, key_tag_blocks=0):
     """how a record of `length` bytes splits into segments of c data blocks (None = GCM_SEGMENT_DEFAULT_C[key_bits]) -> {"n", "c", "aad", "tail_bytes", "segments"};
     a segment is {"role", "offset", "bytes", "ctr0"}.  The keys the record needs: head (c, aad_length), mid (c) when n > 2, tail (tail_bytes).  reveal: the plan for
     reveal segment keys: the default c is GCM_SEGMENT_REVEAL_DEFAULT_C[key_bits] -- equal to the plain one, the capacity table of 9j has the room -- and
-    every segment also carries "mask_offset" and "mask_bytes", its slice of the record's mask"""
+    every segment also carries "mask_offset" and "mask_bytes", its slice of the record's mask.  key_tag_blocks: the plan for a head with that many key-tag blocks
+    (DESIGN.md 9l): the default c is GCM_SEGMENT_KEYTAG_DEFAULT_C[key_tag_blocks][key_bits], with and without reveal -- the plain one for one block, one less for two"""
     if c is None:
-        c = (GCM_SEGMENT_REVEAL_DEFAULT_C if reveal else GCM_SEGMENT_DEFAULT_C)[key_bits]
+        if _seg_key_tag_blocks(key_tag_blocks):
+            c = GCM_SEGMENT_KEYTAG_DEFAULT_C[key_tag_blocks][key_bits]
+        else:
+            c = (GCM_SEGMENT_REVEAL_DEFAULT_C if reveal else GCM_SEGMENT_DEFAULT_C)[key_bits]
     if c < 1 or not 1 <= length <= 1 << 20 or not 0 <= aad_length <= 1 << 16:
         raise ZkAesError("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block")
     nb = (length + 15) // 16
@@ -1248,12 +1273,21 @@ def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_s
     return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], _split(_take(out, total), lens, count)
 
 
-def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None):
+def _seg_key_tag(key_tag):
+    if key_tag is not None and len(key_tag) not in (16, 32):
+        raise ZkAesError("key_tag must be 16 or 32 bytes")
+    return None if key_tag is None else bytes(key_tag)
+
+
+def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None, key_tag=None):
     """the n segment-proofs of one record against ONE list of n - 1 commitments -> a list of n bools.  vks = (head, mid or None, tail) verifying keys; c = the data
     blocks per segment.  The verifier sets every segment's ctr0 = 2 + s c, cuts the ciphertext, builds the length block from the lengths it sees and hands the tag to
     the tail alone; lengths that do not fit the keys, the proof count or the commitment count raise.  mask and revealed (proofs of reveal segment keys):
     ONE mask over the record (reveal_mask) and its len(ciphertext) revealed bytes, both or neither; a mask bit at or beyond the length, or a non-zero revealed byte whose
-    mask bit is 0, raises"""
+    mask bit is 0, raises.  key_tag (a head synthesized with key_tag_blocks = 1 or 2): the 16 or 32 bytes every record of the session is checked
+    against, key_tag(secret_key, blocks) for an honest prover; its bits enter the head's row alone.  The cross cases are 9e's: a tagged head without key_tag, an
+    untagged head with one, or a key_tag of the other length RAISES for a head key of this process or of serialize_vk / deserialize_vk (it carries its public-input
+    count) and REJECTS the head segment for a key from the ark transport; a key_tag that is not 16 or 32 bytes always raises"""
     if len(iv) != 12:
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
     if len(tag) != 16:
@@ -1267,6 +1301,14 @@ def verify_gcm_segments(vks, proofs, iv, aad, ciphertext, tag, commitments, c, m
     coms = b"".join(bytes(x) for x in commitments)
     if (mask is None) != (revealed is None):
         raise ZkAesError("verify_gcm_segments: mask and revealed go together")
+    kt = _seg_key_tag(key_tag)
+    if kt is not None:
+        m = None if mask is None else reveal_mask(mask, len(ciphertext))
+        _check(lib().zkaes_verify_gcm_segments_kt(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad),
+                                                  C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), kt, C.c_size_t(len(kt)), m,
+                                                  C.c_size_t(0 if m is None else len(m)), None if m is None else bytes(revealed), C.c_size_t(0 if m is None else len(revealed)), each,
+                                                  C.byref(ok)))
+        return [bool(each[i]) for i in range(n)]
     if mask is not None:
         m = reveal_mask(mask, len(ciphertext))
         _check(lib().zkaes_verify_gcm_segments_reveal(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv),
@@ -1294,17 +1336,22 @@ def _gcm_segment_args(iv, aad, ciphertext, tag, commitments, mask, revealed):
     return coms, m
 
 
-def gcm_segment_public_inputs(n_segments, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None):
+def gcm_segment_public_inputs(n_segments, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None, key_tag=None):
     """the public-input rows of a segmented GCM record -> (rows, roles): one bytes object of 0/1 per segment -- exactly what verify_gcm_segments checks segment s against
-    -- and its role "head", "mid" or "tail" (zkaes_gcm_segment_public_inputs; no GPU).  The rows differ in length.  mask and revealed as in verify_gcm_segments"""
+    -- and its role "head", "mid" or "tail" (zkaes_gcm_segment_public_inputs; no GPU).  The rows differ in length.  mask and revealed as in verify_gcm_segments.
+    key_tag (16 or 32 bytes): its bits, LSB first per byte, in the HEAD's row behind com_out and ahead of the mask; the other rows are unchanged"""
     coms, m = _gcm_segment_args(iv, aad, ciphertext, tag, commitments, mask, revealed)
     n = int(n_segments)
     lens, roles = (C.c_size_t * max(n, 1))(), (C.c_int * max(n, 1))()
     args = (C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), m,
             C.c_size_t(0 if m is None else len(m)), None if m is None else bytes(revealed))
-    _check(lib().zkaes_gcm_segment_public_inputs(*args, None, lens, roles))
+    fn = lib().zkaes_gcm_segment_public_inputs
+    kt = _seg_key_tag(key_tag)
+    if kt is not None:
+        args, fn = args[:10] + (kt, C.c_size_t(len(kt))) + args[10:], lib().zkaes_gcm_segment_public_inputs_kt
+    _check(fn(*args, None, lens, roles))
     out = C.create_string_buffer(max(1, sum(lens[s] for s in range(n))))
-    _check(lib().zkaes_gcm_segment_public_inputs(*args, out, lens, roles))
+    _check(fn(*args, out, lens, roles))
     rows, off = [], 0
     for s in range(n):
         rows.append(out.raw[off:off + lens[s]])
@@ -1312,14 +1359,22 @@ def gcm_segment_public_inputs(n_segments, iv, aad, ciphertext, tag, commitments,
     return rows, [("head", "mid", "tail")[roles[s]] for s in range(n)]
 
 
-def verify_gcm_segments_batch(vks, proofs, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None, device=True):
+def verify_gcm_segments_batch(vks, proofs, iv, aad, ciphertext, tag, commitments, c, mask=None, revealed=None, device=True, key_tag=None):
     """verify_gcm_segments through ONE multi-key batch: the same arguments, checks, errors and answers, for two MSMs and one pairing product instead of
-    one pairing product per segment.  device as in verify_batch (zkaes_verify_gcm_segments_batch_gpu / zkaes_verify_gcm_segments_batch)"""
+    one pairing product per segment.  device as in verify_batch (zkaes_verify_gcm_segments_batch_gpu / zkaes_verify_gcm_segments_batch).  key_tag as in
+    verify_gcm_segments, with the same cross cases"""
     coms, m = _gcm_segment_args(iv, aad, ciphertext, tag, commitments, mask, revealed)
     head, mid, tail = vks
     n = len(proofs)
     lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
     each, ok = (C.c_int * max(n, 1))(), C.c_size_t()
+    kt = _seg_key_tag(key_tag)
+    if kt is not None:
+        fn = lib().zkaes_verify_gcm_segments_batch_kt_gpu if device else lib().zkaes_verify_gcm_segments_batch_kt
+        _check(fn(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad), C.c_size_t(len(aad)),
+                  bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), kt, C.c_size_t(len(kt)), m, C.c_size_t(0 if m is None else len(m)),
+                  None if m is None else bytes(revealed), C.c_size_t(0 if m is None else len(revealed)), each, C.byref(ok)))
+        return [bool(each[i]) for i in range(n)]
     fn = lib().zkaes_verify_gcm_segments_batch_gpu if device else lib().zkaes_verify_gcm_segments_batch
     _check(fn(head._p, None if mid is None else mid._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad), C.c_size_t(len(aad)),
               bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), m, C.c_size_t(0 if m is None else len(m)), None if m is None else bytes(revealed),
@@ -1327,16 +1382,18 @@ def verify_gcm_segments_batch(vks, proofs, iv, aad, ciphertext, tag, commitments
     return [bool(each[i]) for i in range(n)]
 
 
-def verify_gcm_records_batch(records, device=True):
+def verify_gcm_records_batch(records, device=True, key_tag=None):
     """the segment-proofs of SEVERAL records in ONE verify_batch_keys call -> one list of bools per record.  A record is the argument tuple of verify_gcm_segments_batch
     without device: (vks, proofs, iv, aad, ciphertext, tag, commitments, c[, mask, revealed]).  Key objects that several records share (the same head and mid keys, say)
     enter the batch once: they are told apart by identity.  The rows come from gcm_segment_public_inputs, which raises where verify_gcm_segments would for a record's
-    lengths and counts; that a key fits its segment is left to the proof, which is rejected under a key of another shape"""
+    lengths and counts; that a key fits its segment is left to the proof, which is rejected under a key of another shape.  key_tag: ONE tag of 16 or 32
+    bytes for every record of the call -- the session's -- whose bits enter every head's row; a record made under another AES key has its head rejected, and so has a head
+    whose key_tag_blocks do not fit the tag's length (here the cross cases reject and never raise, as every key-fit question of this call)"""
     keys, key_index, key_of, proofs, rows, counts = [], {}, [], [], [], []
     for rec in records:
         vks, rec_proofs, iv, aad, ciphertext, tag, commitments, c = rec[:8]
         mask, revealed = (tuple(rec[8:]) + (None, None))[:2]
-        rec_rows, roles = gcm_segment_public_inputs(len(rec_proofs), iv, aad, ciphertext, tag, commitments, c, mask=mask, revealed=revealed)
+        rec_rows, roles = gcm_segment_public_inputs(len(rec_proofs), iv, aad, ciphertext, tag, commitments, c, mask=mask, revealed=revealed, key_tag=key_tag)
         by_role = dict(zip(("head", "mid", "tail"), vks))
         for proof, row, role in zip(rec_proofs, rec_rows, roles):
             vk = by_role[role]

@@ -321,6 +321,16 @@ int zkaes_synthesize_keys_gcm_seg_rv(int role, unsigned key_bits, unsigned revea
         give_keys(zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs_literals(nc, nv, nnz), f, (int)reveal), pk, vk);
     });
 }
+// -- key tags on segments: a head key with key_tag_blocks = 1 or 2; the proving and witness entries above take it as they take any head key
+int zkaes_synthesize_keys_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags,
+                                     zkaes_pk **pk, zkaes_vk **vk) {
+    return guard([&] {
+        const unsigned f = key_flags(flags);
+        if (reveal > 1) throw std::invalid_argument("synthesize_keys: reveal must be 0 or 1");
+        if (key_tag_blocks > 2) throw std::invalid_argument("synthesize_keys: key_tag_blocks must be 0, 1 or 2");
+        give_keys(zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs_literals(nc, nv, nnz), f, (int)reveal, key_tag_blocks), pk, vk);
+    });
+}
 int zkaes_aes_witness_gcm_seg_rv(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, const uint8_t *mask, size_t mask_len,
                                  uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {
@@ -575,6 +585,19 @@ int zkaes_verify_gcm_segments_batch_gpu(const zkaes_vk *head, const zkaes_vk *mi
         std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
         zk::capi::verify_gcm_segments_batch_call("verify_gcm_segments_batch_gpu", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments,
                                                  commitments_len, mask, mask_len, revealed, revealed_len, accepted_each, n_accepted, *be);
+    });
+}
+int zkaes_verify_gcm_segments_batch_kt_gpu(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                           const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                           size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed,
+                                           size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+        if (!key_tag) throw std::invalid_argument("null argument");
+        std::unique_ptr<zk::BatchBackend> be = zk::make_device_batch_backend();
+        zk::capi::verify_gcm_segments_batch_call("verify_gcm_segments_batch_kt_gpu", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments,
+                                                 commitments_len, mask, mask_len, revealed, revealed_len, accepted_each, n_accepted, *be, key_tag, key_tag_len);
     });
 }
 // the keyed public-input kernel, one launch per call (tests/test_gpu_verify_batch_keys.py): key k has the domain 2^lg_m[k] and rows of n_bits[k] 0/1 bytes, row i belongs

@@ -78,7 +78,7 @@ inline void verify_batch_keys_call(const zkaes_vk *const *vks, size_t n_keys, co
 void verify_gcm_segments_batch_call(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments,
                                     size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
                                     size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted,
-                                    BatchBackend &be);
+                                    BatchBackend &be, const uint8_t *key_tag = nullptr, size_t key_tag_len = 0);      // (a key tag, DESIGN.md 9l: the head's row ends in its bits ahead of the mask)
 inline size_t next_pow2(size_t n) { if (n > ((size_t)1 << 62)) throw std::length_error("size out of range"); size_t p = 1; while (p < n) p <<= 1; return p; }
 }  // namespace capi
 }  // namespace zk

@@ -49,7 +49,8 @@ void verify_chunks(const zk::VerifyingKey &vk, int circuit_kind, const uint8_t *
 }
 // ---- GCM segments: segment s's public input, and the one body of zkaes_verify_gcm_segments and zkaes_verify_gcm_segments_reveal (described at the entries)
 std::vector<zk::Fr> gcm_segment_public_input(size_t s, size_t n, size_t c, size_t lt, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, const uint8_t lenblk[16],
-                                             const uint8_t tag[16], const uint8_t *commitments, const uint8_t *mask, const uint8_t *revealed) {
+                                             const uint8_t tag[16], const uint8_t *commitments, const uint8_t *mask, const uint8_t *revealed, const uint8_t *key_tag = nullptr,
+                                             size_t key_tag_len = 0) {
     uint8_t hd[16];
     memcpy(hd, iv, 12);
     const uint32_t ctr0 = (uint32_t)(2 + s * c);
@@ -57,15 +58,16 @@ std::vector<zk::Fr> gcm_segment_public_input(size_t s, size_t n, size_t c, size_
     const bool first = s == 0, last = s + 1 == n;
     const size_t len = last ? lt : 16 * c;
     return zk::public_input_of({{hd, 16}, {first ? aad : nullptr, aad_len}, {ct + 16 * c * s, len}, {last ? lenblk : nullptr, 16}, {last ? tag : nullptr, 16},
-                                {first ? nullptr : commitments + 32 * (s - 1), 32}, {last ? nullptr : commitments + 32 * s, 32},
+                                {first ? nullptr : commitments + 32 * (s - 1), 32}, {last ? nullptr : commitments + 32 * s, 32}, {first ? key_tag : nullptr, key_tag_len},      // (9l: the head alone carries the tag)
                                 {mask ? zk::chunk_mask_slice(mask, s, 16 * c) : nullptr, zk::mask_bytes(len)}, {mask ? revealed + 16 * c * s : nullptr, len}});
 }
 // what both verifiers of a segmented record and zkaes_gcm_segment_public_inputs check before any proof is looked at: the lengths and counts, and (keys given) that
 // the three keys fit them.  Returns n, the tail's bytes and the length block
-struct SegShape { size_t n, lt; uint8_t lenblk[16]; };
+struct SegShape { size_t n, lt; uint8_t lenblk[16]; bool head_fits; };
 SegShape gcm_segments_shape(const char *entry, bool with_keys, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, size_t n_segments, size_t c, const uint8_t iv[12],
                             const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len, bool reveal,
-                            const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len) {
+                            const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, const uint8_t *key_tag = nullptr, size_t key_tag_len = 0) {
+    if (key_tag ? (key_tag_len != 16 && key_tag_len != 32) : key_tag_len != 0) throw std::invalid_argument(std::string(entry) + ": key_tag_len must be 16 or 32 with a key tag (one or two tag blocks), 0 with NULL");
     if ((with_keys && (!head || !tail)) || !iv || !ct || !tag || !commitments || (aad_len && !aad) || (reveal && (!mask || !revealed))) throw std::invalid_argument("null argument");
     if (c == 0 || ct_len == 0 || ct_len > ((size_t)1 << 20) || aad_len > ((size_t)1 << 16)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and a segment at least one block");
     const size_t nb = (ct_len + 15) / 16, n = (nb + c - 1) / c;
@@ -81,52 +83,65 @@ SegShape gcm_segments_shape(const char *entry, bool with_keys, const zkaes_vk *h
     const size_t lt = ct_len - 16 * c * (n - 1);
     // the verifier zero-pads the public input, so the lengths are part of the statement (as require_gcm_lengths): a key that knows its exact count pins them -- and
     // tells a reveal key from a plain one, whose count lacks the mask's and the revealed bytes' bits
-    auto exact = [&](const zk::VerifyingKey &vk, size_t bits, size_t len, const char *name) {
+    // A head also tells its tag blocks: a tagged head checked without a tag, an untagged one with a tag, or a tag of the other length raises here
+    auto exact = [&](const zk::VerifyingKey &vk, size_t bits, size_t len, const char *name, size_t tag_bits = 0, bool is_head = false) {
         if (vk.num_public_inputs + 1 == vk.num_instance) return;
         const size_t rv_bits = 8 * zk::mask_bytes(len) + 8 * len;
+        if (is_head && vk.num_public_inputs != bits + tag_bits + (reveal ? rv_bits : 0))
+            for (size_t other : {(size_t)0, (size_t)128, (size_t)256})
+                if (other != tag_bits && vk.num_public_inputs == bits + other + (reveal ? rv_bits : 0))
+                    throw std::invalid_argument(std::string(entry) + ": the head key was synthesized with key_tag_blocks = " + std::to_string(other / 128) + ": it is checked " +
+                                                (other ? "against a key tag of " + std::to_string(other / 8) + " bytes (the _kt entries)" : std::string("without a key tag")));
+        bits += tag_bits;
         if (vk.num_public_inputs == bits + (reveal ? 0 : rv_bits))
             throw std::invalid_argument(std::string("GCM segments: the ") + name + (reveal ? " key has no reveal region: zkaes_verify_gcm_segments_reveal takes keys synthesized with reveal = 1 (zkaes_verify_gcm_segments checks this one)"
                                                                                            : " key reveals plaintext bytes: its proofs are checked with zkaes_verify_gcm_segments_reveal"));
         if (vk.num_public_inputs != bits + (reveal ? rv_bits : 0)) throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths");
     };
     if (with_keys) {
-        exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 16 * c, "head");
+        exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 16 * c, "head", 8 * key_tag_len, true);
         if (n > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, 16 * c, "mid");
         exact(tail->vk, 128 + 8 * lt + 128 + 128 + 256, lt, "tail");
     }
     SegShape S;
     S.n = n; S.lt = lt;
+    // a head from the ark transport carries only |X|: a tag whose bits do not pad to it rejects the head segment (9e's rule, fits_key)
+    S.head_fits = !with_keys || !key_tag_len || head->vk.num_public_inputs + 1 != head->vk.num_instance ||
+                  zk::capi::next_pow2(128 + 8 * aad_len + 128 * c + 256 + 8 * key_tag_len + (reveal ? 8 * zk::mask_bytes(16 * c) + 128 * c : 0) + 1) == head->vk.num_instance;
     uint8_t *lenblk = S.lenblk;
     for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); }
     return S;
 }
 void verify_gcm_segments(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
                          const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
-                         bool reveal, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted) {
+                         bool reveal, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted,
+                         const uint8_t *key_tag = nullptr, size_t key_tag_len = 0) {
     if (n_accepted) *n_accepted = 0;
     if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
     if (!proofs || !proof_lens) throw std::invalid_argument("null argument");
     const SegShape S = gcm_segments_shape(entry, true, head, mid_or_null, tail, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, reveal, mask, mask_len, revealed,
-                                          revealed_len);
+                                          revealed_len, key_tag, key_tag_len);
     const size_t n = S.n, lt = S.lt;
     const uint8_t *lenblk = S.lenblk;
     verify_each(proofs, proof_lens, n, accepted_each, n_accepted, [&](size_t s, const zk::Proof &p) {
+        if (s == 0 && !S.head_fits) return false;
         return zk::verify(s == 0 ? head->vk : s + 1 == n ? tail->vk : mid_or_null->vk,
-                          gcm_segment_public_input(s, n, c, lt, iv, aad, aad_len, ct, lenblk, tag, commitments, reveal ? mask : nullptr, revealed), p);
+                          gcm_segment_public_input(s, n, c, lt, iv, aad, aad_len, ct, lenblk, tag, commitments, reveal ? mask : nullptr, revealed, key_tag, key_tag_len), p);
     });
 }
 // the n rows of one record as 0/1 bytes, one behind the other (ragged: head, mid and tail rows differ in length), through gcm_segment_public_input: what the per-proof
 // verifier above checks segment s against.  role: 0 head, 1 mid, 2 tail
 void gcm_segment_rows(const SegShape &S, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, const uint8_t tag[16], const uint8_t *commitments,
-                      const uint8_t *mask, const uint8_t *revealed, std::vector<uint8_t> *bits, std::vector<size_t> &lens, std::vector<int> &roles) {
+                      const uint8_t *mask, const uint8_t *revealed, std::vector<uint8_t> *bits, std::vector<size_t> &lens, std::vector<int> &roles, const uint8_t *key_tag = nullptr,
+                      size_t key_tag_len = 0) {
     lens.assign(S.n, 0); roles.assign(S.n, 1);
     roles[0] = 0; roles[S.n - 1] = 2;
     for (size_t s = 0; s < S.n; s++) {
         const bool first = s == 0, last = s + 1 == S.n;
         const size_t len = last ? S.lt : 16 * c;
-        lens[s] = 128 + (first ? 8 * aad_len : 0) + 8 * len + (last ? 256 : 0) + (first || last ? 256 : 512) + (mask ? 8 * zk::mask_bytes(len) + 8 * len : 0);
+        lens[s] = 128 + (first ? 8 * aad_len : 0) + 8 * len + (last ? 256 : 0) + (first || last ? 256 : 512) + (first ? 8 * key_tag_len : 0) + (mask ? 8 * zk::mask_bytes(len) + 8 * len : 0);
         if (!bits) continue;
-        const std::vector<zk::Fr> pub = gcm_segment_public_input(s, S.n, c, S.lt, iv, aad, aad_len, ct, S.lenblk, tag, commitments, mask, revealed);
+        const std::vector<zk::Fr> pub = gcm_segment_public_input(s, S.n, c, S.lt, iv, aad, aad_len, ct, S.lenblk, tag, commitments, mask, revealed, key_tag, key_tag_len);
         if (pub.size() != lens[s]) throw std::logic_error("GCM segments: a segment's public input has not the documented length");
         for (const zk::Fr &v : pub) bits->push_back(v.is_zero() ? 0 : 1);
     }
@@ -144,17 +159,17 @@ namespace zk { namespace capi { void set_last_batch_timings(const BatchTimings &
 void zk::capi::verify_gcm_segments_batch_call(const char *entry, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens,
                                               size_t n_segments, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16],
                                               const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
-                                              int *accepted_each, size_t *n_accepted, BatchBackend &be) {
+                                              int *accepted_each, size_t *n_accepted, BatchBackend &be, const uint8_t *key_tag, size_t key_tag_len) {
     if (n_accepted) *n_accepted = 0;
     if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
     if (!proofs || !proof_lens) throw std::invalid_argument("null argument");
     const bool reveal = mask != nullptr;
     const SegShape S = gcm_segments_shape(entry, true, head, mid_or_null, tail, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, reveal, mask, mask_len, revealed,
-                                          revealed_len);
+                                          revealed_len, key_tag, key_tag_len);
     std::vector<uint8_t> bits;
     std::vector<size_t> lens;
     std::vector<int> roles;
-    gcm_segment_rows(S, c, iv, aad, aad_len, ct, tag, commitments, mask, revealed, &bits, lens, roles);
+    gcm_segment_rows(S, c, iv, aad, aad_len, ct, tag, commitments, mask, revealed, &bits, lens, roles, key_tag, key_tag_len);      // (a head row that does not pad to its key's |X| is rejected alone)
     const zkaes_vk *vks[3] = {head, S.n > 2 ? mid_or_null : tail, tail};
     const size_t n_keys = S.n > 2 ? 3 : 2;
     std::vector<uint32_t> key_of(S.n);
@@ -631,9 +646,9 @@ int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_
 }
 // (this query also fills out[9 .. 11]: the non-zeros of the joint matrix -- the positions where A, B or C has an entry, as the indexer merges them -- and |H|, |K|, so
 // that a caller can size a record's segments against an SRS without a device)
-static int circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, uint64_t out[12]) {
+static int circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, unsigned key_tag_blocks, uint64_t out[12]) {
     return guard([&] {
-        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal);
+        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal, key_tag_blocks);
         fill_info(c, out);
         uint64_t joint = 0;
         for (size_t r = 0; r < c.num_constraints; r++) {
@@ -654,8 +669,11 @@ static int circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_
         out[9] = joint; out[10] = next_pow2(c.num_constraints); out[11] = next_pow2(joint);
     });
 }
-int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, 0, out); }
-int zkaes_circuit_info_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, reveal, out); }
+int zkaes_circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, 0, 0, out); }
+int zkaes_circuit_info_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, reveal, 0, out); }
+int zkaes_circuit_info_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_len, uint64_t out[12]) {
+    return circuit_info_gcm_seg(role, key_bits, units, aad_len, reveal, key_tag_blocks, out);
+}
 // ---- batch verification (include/zkaes.h): the host back end; zkaes_verify_batch_gpu and the kernel probes are in capi.cpp
 int zkaes_verify_batch(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each, size_t *n_accepted) {
     return guard([&] {
@@ -726,9 +744,10 @@ int zkaes_chunk_public_inputs_rv(int circuit_kind, size_t n_chunks, const uint8_
     if (!mask || !revealed || mask_len != zk::mask_bytes(ct_len)) return guard([&] { throw std::invalid_argument("chunk_public_inputs_rv: ONE mask over the whole job (ceil(ct_len / 8) bytes) and its revealed bytes"); });
     return chunk_public_inputs("chunk_public_inputs_rv", circuit_kind, n_chunks, iv_or_icb, ct, ct_len, key_tag, key_tag_len, states, mask, revealed, out_bits, n_bits);
 }
-static int circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+static int circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, unsigned key_tag_blocks, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr,
+                                  uint32_t *col, int64_t *coeff) {
     return guard([&] {
-        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal);
+        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal, key_tag_blocks);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -738,11 +757,56 @@ static int circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, siz
     });
 }
 int zkaes_circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
-    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, 0, which, n_rows, nnz, rowptr, col, coeff);
+    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, 0, 0, which, n_rows, nnz, rowptr, col, coeff);
 }
 int zkaes_circuit_matrix_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col,
                                     int64_t *coeff) {
-    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, reveal, which, n_rows, nnz, rowptr, col, coeff);
+    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, reveal, 0, which, n_rows, nnz, rowptr, col, coeff);
+}
+int zkaes_circuit_matrix_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr,
+                                    uint32_t *col, int64_t *coeff) {
+    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, reveal, key_tag_blocks, which, n_rows, nnz, rowptr, col, coeff);
+}
+// ---- key tags on segmented records (include/zkaes.h): the rows and the verifiers of a record whose head carries a key tag.  mask = NULL: plain keys
+int zkaes_gcm_segment_public_inputs_kt(size_t n_segments, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16],
+                                       const uint8_t *commitments, size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len,
+                                       const uint8_t *revealed, uint8_t *out_bits, size_t *n_bits_each, int *roles) {
+    return guard([&] {
+        if (!key_tag) throw std::invalid_argument("null argument");
+        const SegShape S = gcm_segments_shape("gcm_segment_public_inputs_kt", false, nullptr, nullptr, nullptr, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len,
+                                              mask != nullptr, mask, mask_len, revealed, ct_len, key_tag, key_tag_len);
+        std::vector<uint8_t> bits;
+        std::vector<size_t> lens;
+        std::vector<int> rl;
+        gcm_segment_rows(S, c, iv, aad, aad_len, ct, tag, commitments, mask, revealed, out_bits ? &bits : nullptr, lens, rl, key_tag, key_tag_len);
+        for (size_t s = 0; s < S.n; s++) { if (n_bits_each) n_bits_each[s] = lens[s]; if (roles) roles[s] = rl[s]; }
+        if (out_bits && !bits.empty()) memcpy(out_bits, bits.data(), bits.size());
+    });
+}
+int zkaes_verify_gcm_segments_kt(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                 const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                 size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
+                                 int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+        if (!key_tag) throw std::invalid_argument("null argument");
+        verify_gcm_segments("verify_gcm_segments_kt", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, mask != nullptr,
+                            mask, mask_len, revealed, revealed_len, accepted_each, n_accepted, key_tag, key_tag_len);
+    });
+}
+int zkaes_verify_gcm_segments_batch_kt(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                       const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                       size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
+                                       int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t s = 0; s < n_segments; s++) accepted_each[s] = 0;
+        if (!key_tag) throw std::invalid_argument("null argument");
+        std::unique_ptr<zk::BatchBackend> be = zk::make_host_batch_backend();
+        zk::capi::verify_gcm_segments_batch_call("verify_gcm_segments_batch_kt", head, mid_or_null, tail, proofs, proof_lens, n_segments, c, iv, aad, aad_len, ct, ct_len, tag, commitments,
+                                                 commitments_len, mask, mask_len, revealed, revealed_len, accepted_each, n_accepted, *be, key_tag, key_tag_len);
+    });
 }
 
 }  // extern "C"

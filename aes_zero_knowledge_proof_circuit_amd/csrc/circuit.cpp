@@ -747,11 +747,15 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
 // position 31) and the block's rounds from iv || counter; one xor gate per existing message bit; the ciphertext inputs and (tail) the 128 length-block inputs; the V
 // table; GHASH -- a head starts at its first block as the lone circuit does, a mid or tail with X_0 = Y_in ^ C_0, and a tail's last multiplication runs over the
 // length-block INPUTS; (tail) the tag's xor gates and inputs; last com_in (mid, tail), then com_out (head, mid): 256 inputs each, one compression from the constant
-// initial value over key || zeros || Y || salt, 256 equalities.  With reveal = 1 the mask and revealed inputs and their rows (reveal() above) come last of all.
-Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits, int rv) {
+// initial value over key || zeros || Y || salt, 256 equalities.  A head with key_tag_blocks = T then has the T tag blocks of key_tag() and their 128 T
+// inputs.  With reveal = 1 the mask and revealed inputs and their rows (reveal() above) come last of all.
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits, int rv, size_t key_tag_blocks) {
     require_key_bits(key_bits);
     require_reveal(rv);
+    require_key_tag_blocks(key_tag_blocks);
     if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw std::invalid_argument("GCM segment: the role must be 0 (head), 1 (mid) or 2 (tail)");
+    if (role != TRS_HEAD && key_tag_blocks)
+        throw std::invalid_argument("GCM segment: only the head segment takes key_tag_blocks: the head carries the record's key tag and the boundary commitments carry the key to every later segment");
     if (units == 0) throw std::invalid_argument("GCM segment: a head or mid has at least one data block, a tail at least one byte");
     if (role != TRS_HEAD && alen) throw std::invalid_argument("GCM segment: only the head segment takes the aad");
     if (units > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM segment: message and aad of one proof are limited to 65536 bytes each");
@@ -848,12 +852,15 @@ Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, siz
         for (int j = 0; j < 16; j++) for (int bit = 0; bit < 8; bit++) yout[j][bit] = Y[8 * j + 7 - bit];
         commit(yout, salt_out, sg + TRS_COM_OUT, sg + (uint32_t)TRS_SLOT_OUT(nb));
     }
+    // ---- the key tag of a head: the tag slots behind the segment region and its compression slots, as finish_aes puts them behind a mode's tail
+    const size_t seg_bytes = TRS_BYTES(nk, role, na, nb);
+    size_t trace_bytes = g.key_tag(key_tag_blocks, seg_bytes);
     // ---- selective disclosure: the segment's slice of the record's mask and revealed bytes, behind the commitments as finish_aes puts them behind the digest
-    size_t trace_bytes = TRS_BYTES(nk, role, na, nb);
     const size_t reveal_off = rv ? TRV(trace_bytes) : 0;
     if (rv) trace_bytes = reveal(b, msg, trace_bytes);
     Circuit c = finish(b, CIRCUIT_AES_GCM_SEG, nb, trace_bytes, g.key_bytes());
     c.message_bytes = len; c.aad_bytes = alen; c.seg_role = role; c.seg_off = sg;
+    c.key_tag_blocks = key_tag_blocks; c.key_tag_off = key_tag_blocks ? TRK_KT(seg_bytes) : 0;
     c.reveal = rv; c.reveal_off = reveal_off;
     return c;
 }

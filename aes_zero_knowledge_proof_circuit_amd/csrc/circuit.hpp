@@ -83,10 +83,11 @@ Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_b
 // segment's first data block), head: aad, ciphertext, com_out (32); mid: ciphertext, com_in, com_out; tail: ciphertext, the length block be64(8 A) || be64(8 L) of the
 // whole record (16), tag (16), com_in.  Private: message, key, Y_in (the GHASH accumulator entering a mid or tail), the salts.  A commitment is ONE SHA-256 compression
 // from the initial value over key || zeros to 32 bytes || Y || salt.  Block b runs under iv || (ctr0 + b mod 2^32), by CTR's xor/and incrementer over the low 32 bits.
-// No key tag and no digest.  reveal = 1 appends, behind everything above, the segment's slice of the record's mask (ceil(len / 8) bytes) and of its
-// revealed bytes (len), len = 16 c for a head or mid and Lt for a tail, with the rows of the lone reveal form; reveal = 0 is the circuit as it was.  Anything out of
-// range is std::invalid_argument
-Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128, int reveal = 0);
+// No digest.  reveal = 1 appends, behind everything above, the segment's slice of the record's mask (ceil(len / 8) bytes) and of its
+// revealed bytes (len), len = 16 c for a head or mid and Lt for a tail, with the rows of the lone reveal form; reveal = 0 is the circuit as it was.
+// key_tag_blocks = T in 1, 2 (a HEAD only, since the commitments carry the key to every later segment) appends 9e's tag blocks: 128 T inputs behind
+// com_out and ahead of the reveal inputs, their slots at TRK_KT(TRS_BYTES(..)); T = 0 is the circuit as it was.  Anything out of range is std::invalid_argument
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128, int reveal = 0, size_t key_tag_blocks = 0);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
 // 128, key_tag_blocks 0 and digest_kind 0 for the ops kinds
 Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);

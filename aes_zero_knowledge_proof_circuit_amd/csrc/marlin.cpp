@@ -508,7 +508,7 @@ void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lit
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
     if (kind == CIRCUIT_AES_GCM_SEG) {                                             // message_len_ = the segment's units: c data blocks (head, mid) or Lt bytes (tail)
-        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits, reveal);
+        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits, reveal, key_tag_blocks);
         message_len = circuit.message_bytes;
     } else circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     const Circuit &c = circuit;
@@ -1449,10 +1449,10 @@ std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len
     pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, -1, reveal);
     return pk;
 }
-std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags, int reveal) {
+std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags, int reveal, size_t key_tag_blocks) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, 0, 0, 0, role, reveal);
+    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, key_tag_blocks, 0, 0, role, reveal);
     return pk;
 }
 

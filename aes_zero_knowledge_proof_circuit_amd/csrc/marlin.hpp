@@ -146,9 +146,10 @@ class ProvingKey {
 enum : unsigned { KEY_NO_TABLES = 1u };
 std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len, const SrsLiterals &srs, unsigned flags = 0, size_t aad_len = 0, size_t key_bits = 128,
                                             size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);      // (aad_len: GCM keys only; key_bits: 128, 192 or 256, key_tag_blocks: 0, 1 or 2, digest_kind: 0, 1 or 2 (circuit.hpp DigestKind), reveal: 0 or 1, the AES kinds only)
-// A GCM segment key: role = 0 head, 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); aad_len: head only.  No key tag, no digest;
-// reveal: 0 or 1
-std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags = 0, int reveal = 0);
+// A GCM segment key: role = 0 head, 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); aad_len: head only.  No digest;
+// reveal: 0 or 1; key_tag_blocks: 0, 1 or 2 for a head, 0 for a mid or tail
+std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags = 0, int reveal = 0,
+                                                        size_t key_tag_blocks = 0);
 // Segments [first_segment, first_segment + count) of ONE GCM record of len bytes as segment-proofs: n = ceil(ceil(len / 16) / c) >= 2 segments, c = the head key's data
 // blocks; mid_or_null may be null when n = 2; the tail key is the one for the record's last len - 16 c (n - 1) bytes.  The host computes the record's ciphertext and tag,
 // Y at every boundary and the n - 1 commitments from salts_or_null (16 (n - 1) bytes; null = fresh OS randomness, allowed only when the call covers the whole record);

@@ -262,6 +262,22 @@ static_assert(TRS_MULS(TRS_HEAD, 1, 4) == 5 && TRS_MULS(TRS_MID, 0, 4) == 4 && T
                   TRS_RV_BYTES(nk, TRS_MID, 0, 4, 1, 64) % 16 == 0, "a segment's reveal region begins on the next multiple of 16 behind the compression slots and ends on one")
 TRS_RV_ASSERT(4); TRS_RV_ASSERT(6); TRS_RV_ASSERT(8);
 static_assert(TRS_HDR_RV_BYTES(13, 0, 16) == 93 && TRS_HDR_RV_BYTES(13, 1, 16) == 95 && TRS_HDR_RV_BYTES(0, 1, 17) == 83 && TRS_HDR_MASK(13) == 93, "a reveal segment header ends in the mask");
+// ---- key tags on segments: a HEAD key synthesized with T = 1 or 2 key-tag blocks has the tag slots of 9e (TRK_KT_SLOT, the ordinary block-slot layout)
+// BEHIND the segment region's two compression slots, slot 0 at TRK_KT(TRS_BYTES(..)), and a reveal region behind THEM, at TRV of the length with the slots.  No TRS_*
+// offset moves, the proof's header is what it was (the tag comes from the key alone), and with T = 0 a trace is what it was.
+#define TRS_KT(nk, role, na, nb) TRK_KT(TRS_BYTES(nk, role, na, nb))
+#define TRS_KT_BYTES(nk, role, na, nb, T) TRK_KT_BYTES(nk, TRS_BYTES(nk, role, na, nb), T)
+#define TRS_KT_RV(nk, role, na, nb, T) TRV(TRS_KT_BYTES(nk, role, na, nb, T))
+#define TRS_KT_RV_BYTES(nk, role, na, nb, T, R, len) TRV_BYTES(TRS_KT_BYTES(nk, role, na, nb, T), R, len)
+#define TRS_KT_ASSERT(nk) \
+    static_assert(TRS_KT_BYTES(nk, TRS_HEAD, 1, 2, 0) == TRS_BYTES(nk, TRS_HEAD, 1, 2) && TRS_KT_RV_BYTES(nk, TRS_HEAD, 1, 2, 0, 1, 32) == TRS_RV_BYTES(nk, TRS_HEAD, 1, 2, 1, 32) && \
+                  TRS_KT_RV(nk, TRS_HEAD, 1, 2, 0) == TRS_RV(nk, TRS_HEAD, 1, 2), "without key tags a segment trace keeps its length and its reveal region its place"); \
+    static_assert(TRS_KT(nk, TRS_HEAD, 1, 2) % 16 == 0 && TRS_KT(nk, TRS_HEAD, 0, 1) % 16 == 0 && TRS_KT(nk, TRS_HEAD, 1, 2) >= TRS_BYTES(nk, TRS_HEAD, 1, 2) && TRK_BLOCK_STRIDE(nk) % 16 == 0 && \
+                  TRS_KT_BYTES(nk, TRS_HEAD, 1, 2, 1) % 16 == 0 && TRS_KT_BYTES(nk, TRS_HEAD, 1, 2, 2) % 16 == 0 && TRS_KT_RV_BYTES(nk, TRS_HEAD, 1, 2, 2, 1, 32) % 16 == 0, \
+                  "a head's tag slots begin on a multiple of 16 behind the compression slots, and the tagged stride is one"); \
+    static_assert(TRS_KT_RV(nk, TRS_HEAD, 1, 2, 1) == TRS_KT(nk, TRS_HEAD, 1, 2) + TRK_BLOCK_STRIDE(nk) && TRS_KT_RV(nk, TRS_HEAD, 0, 4, 2) == TRS_KT(nk, TRS_HEAD, 0, 4) + 2 * TRK_BLOCK_STRIDE(nk), \
+                  "the reveal region of a tagged head begins where the tag slots end")
+TRS_KT_ASSERT(4); TRS_KT_ASSERT(6); TRS_KT_ASSERT(8);
 
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30

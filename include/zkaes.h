@@ -807,6 +807,39 @@ int zkaes_verify_gcm_segments_batch_gpu(const zkaes_vk *head, const zkaes_vk *mi
                                         const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
                                         const uint8_t *commitments, size_t commitments_len, const uint8_t *mask, size_t mask_len, const uint8_t *revealed, size_t revealed_len,
                                         int *accepted_each, size_t *n_accepted);
+/* ---- key tags on segmented GCM records.  A HEAD segment key may be synthesized with key_tag_blocks = T in 1, 2: beside the head's statement it proves
+ * tag_t = AES_K(D_t), t < T, for the constants D_t of the key tags above (zkaes_key_tag names them).  The 128 T tag bits are public input behind com_out and ahead of a
+ * reveal key's mask and revealed bits; the tag slots lie behind the head's segment region in the trace and no other offset moves.  The boundary commitments carry the
+ * head's key to every later segment, so a mid or tail key takes T = 0 only (T != 0 is an error that says so) and ONE tag covers the record.  T = 0 through these entries
+ * is every entry above, bit for bit; reveal is 0 or 1 as in the _rv entries.  The proving and witness entries (zkaes_encrypt_gcm_segments[_reveal]_seeded_at,
+ * zkaes_encrypt_gcm_segment[_reveal]_batch_seeded_at, zkaes_aes_witness_gcm_seg[_rv]) take a tagged head as they take any head: the tag's witness comes from the key, and
+ * zkaes_pk_key_tag_blocks answers for segment keys.  The verifiers below take key_tag != NULL with key_tag_len = 16 or 32 (anything else is an error), append its bits to
+ * the head's row ALONE, and are otherwise zkaes_gcm_segment_public_inputs, zkaes_verify_gcm_segments[_reveal] (mask = NULL: plain keys) and
+ * zkaes_verify_gcm_segments_batch[_gpu].  A tag length that does not fit the head key -- a tag for an untagged head, 32 bytes for a T = 1 head, and, through the entries
+ * without a tag above, a tagged head without one -- is an error of the call where the key carries its public-input count and rejects the head segment for a key from the
+ * ark transport.  A session is bound to one AES key by checking every record's head, and every lone tagged GCM record, against ONE tag. */
+int zkaes_synthesize_keys_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_length, size_t srs_num_constraints,
+                                     size_t srs_num_variables, size_t srs_num_non_zero, unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* host only */
+int zkaes_circuit_info_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz,
+                                    uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+int zkaes_gcm_segment_public_inputs_kt(size_t n_segments, size_t c, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len,
+                                       const uint8_t tag16[16], const uint8_t *commitments, size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask,
+                                       size_t mask_len, const uint8_t *revealed, uint8_t *out_bits, size_t *n_bits_each, int *roles);
+int zkaes_verify_gcm_segments_kt(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                 const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
+                                 const uint8_t *commitments, size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len,
+                                 const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted);
+int zkaes_verify_gcm_segments_batch_kt(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments, size_t c,
+                                       const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
+                                       const uint8_t *commitments, size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len,
+                                       const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted);
+/* (device) */
+int zkaes_verify_gcm_segments_batch_kt_gpu(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_segments,
+                                           size_t c, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
+                                           const uint8_t *commitments, size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len,
+                                           const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted);
 /* The keyed public-input kernel, one launch per call (tests): zkaes_public_input_eval over rows of n_keys domains.  Key k has |X| = 2^lg_m[k] and rows of n_bits[k] 0/1
  * bytes; row i belongs to key key_of[i] and follows row i - 1 in bits.  out[i] = x^(betas[i]) over row i's own domain. */
 int zkaes_public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t n_keys, const uint32_t *key_of, const uint8_t *betas, const uint8_t *bits, size_t n, uint8_t *out);

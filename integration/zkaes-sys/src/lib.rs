@@ -199,6 +199,28 @@ extern "C" {
                                         c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
                                         commitments: *const u8, commitments_len: usize, mask: *const u8, mask_len: usize, revealed: *const u8, revealed_len: usize,
                                         accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    // key tags on segmented records (include/zkaes.h, "key tags on segmented GCM records"; declarations only, no wrappers yet, and not compiled: no cargo in the build
+    // image).  A HEAD key takes key_tag_blocks = 0, 1 or 2, a mid or tail 0 only; the verifiers take key_tag != NULL of 16 or 32 bytes and mask = NULL for plain keys
+    fn zkaes_synthesize_keys_gcm_seg_kt(role: c_int, key_bits: c_uint, reveal: c_uint, key_tag_blocks: c_uint, units: usize, aad_length: usize, srs_num_constraints: usize,
+                                        srs_num_variables: usize, srs_num_non_zero: usize, flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_circuit_info_gcm_seg_kt(role: c_int, key_bits: c_uint, reveal: c_uint, key_tag_blocks: c_uint, units: usize, aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_gcm_seg_kt(role: c_int, key_bits: c_uint, reveal: c_uint, key_tag_blocks: c_uint, units: usize, aad_length: usize, which: c_int, n_rows: *mut u64,
+                                       nnz: *mut u64, rowptr: *mut u32, col: *mut u32, coeff: *mut i64) -> c_int;
+    fn zkaes_gcm_segment_public_inputs_kt(n_segments: usize, c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
+                                          commitments: *const u8, commitments_len: usize, key_tag: *const u8, key_tag_len: usize, mask: *const u8, mask_len: usize,
+                                          revealed: *const u8, out_bits: *mut u8, n_bits_each: *mut usize, roles: *mut c_int) -> c_int;
+    fn zkaes_verify_gcm_segments_kt(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize, c: usize,
+                                    iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8, commitments: *const u8,
+                                    commitments_len: usize, key_tag: *const u8, key_tag_len: usize, mask: *const u8, mask_len: usize, revealed: *const u8, revealed_len: usize,
+                                    accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    fn zkaes_verify_gcm_segments_batch_kt(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize,
+                                          c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
+                                          commitments: *const u8, commitments_len: usize, key_tag: *const u8, key_tag_len: usize, mask: *const u8, mask_len: usize,
+                                          revealed: *const u8, revealed_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    fn zkaes_verify_gcm_segments_batch_kt_gpu(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize, n_segments: usize,
+                                              c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
+                                              commitments: *const u8, commitments_len: usize, key_tag: *const u8, key_tag_len: usize, mask: *const u8, mask_len: usize,
+                                              revealed: *const u8, revealed_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
     // kernel-level entries of the kernels that build a key (include/zkaes.h, "kernels that BUILD A KEY": test surface, not product API; declarations only, no wrappers, and
     // not compiled: no cargo in the build image).  A point is 96 bytes of affine x || y in Montgomery form, infinity 96 zero bytes; a field element 32 bytes; a Niels record
     // 192 bytes; every output of zkaes_index_evals holds 2^lg_k + 64 elements
