@@ -18,6 +18,7 @@ HIP_SOURCES = ["runtime.hip", "kernels_ntt.hip", "kernels_msm.hip", "kernels_pol
 CXX_SOURCES = ["circuit.cpp", "marlin.cpp", "marlin_codec.cpp", "capi.cpp", "capi_host.cpp"]
 HOST_ONLY_SOURCES = ["circuit.cpp", "marlin_codec.cpp", "capi_host.cpp"]      # no device code path: what the stand-alone sanitizer programs of tests/ link against
 HEADERS = ["ff.cuh", "ff28.cuh", "ff29.cuh", "ec.cuh", "ec28.cuh", "te28.cuh", "gpu.hpp", "hip_util.hpp", "consts32.h", "trace_layout.h", "circuit.hpp", "marlin.hpp", "marlin_host.hpp", "capi_common.hpp", "pairing.hpp", "transcript.hpp", "arith_probe.cuh", "fq_sqrt.cuh", "verify_batch.hpp", "statement.hpp",
+           "kernels_witness.cuh", "kernels_digest.cuh", "kernels_reveal.cuh",      # the trace kernels' device code (each included by the .hip file of its name)
            os.path.join("..", "..", "include", "zkaes.h")]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-I", CSRC, "-Wno-unused-result"]
 if os.environ.get("ZK_EXTRA_DEFINES"):      # e.g. "-DZKAES_MEASURE" (knock-in hooks of the measurement builds) for A/B builds on the GPU box

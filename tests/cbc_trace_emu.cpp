@@ -1,5 +1,5 @@
-// tests/cbc_trace_emu.cpp -- the AES trace kernel (both modes) and k_witness_expand of csrc/kernels_witness.hip run lane by lane ON THE HOST: tests/test_cbc_host.py cuts the two
-// kernels' source text out of the .hip file into kern_extract.inc and builds this file around it with -fsanitize=address,undefined.  For nb = 1, 2, 3 and two proofs per
+// tests/cbc_trace_emu.cpp -- the AES trace kernel (both modes) and k_witness_expand of csrc/kernels_witness.cuh run lane by lane ON THE HOST: tests/test_cbc_host.py builds
+// this file, which includes that header behind tests/lane_emu.h, with -fsanitize=address,undefined.  For nb = 1, 2, 3 and two proofs per
 // launch it checks that no lane writes outside the traces, that the expanded assignment satisfies every row of (A z) o (B z) = C z, that the instance is One, (the IV bits,)
 // the bits of the host's own ciphertext and zero padding, and that flipping one instance bit leaves exactly one row unsatisfied.  No GPU: what the device adds is the launch.
 #include "circuit.hpp"
@@ -8,14 +8,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 int main() {
     uint8_t sb[256]; for (int i = 0; i < 256; i++) sb[i] = aes_sbox_value((uint8_t)i);

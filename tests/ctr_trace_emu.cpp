@@ -1,5 +1,5 @@
-// tests/ctr_trace_emu.cpp -- k_aes_trace_ctr and k_witness_expand of csrc/kernels_witness.hip run lane by lane ON THE HOST: tests/test_ctr_host.py cuts the kernels' source
-// text out of the .hip file into kern_extract.inc and builds this file around it with -fsanitize=address,undefined.  Shapes: L = 1, 16, 17, 33, 48 bytes, two proofs per
+// tests/ctr_trace_emu.cpp -- k_aes_trace_ctr and k_witness_expand of csrc/kernels_witness.cuh run lane by lane ON THE HOST: tests/test_ctr_host.py builds this file,
+// which includes that header behind tests/lane_emu.h, with -fsanitize=address,undefined.  Shapes: L = 1, 16, 17, 33, 48 bytes, two proofs per
 // launch under different counters, the counters whose increment carries furthest among them (ff..ff wraps to zero, ..00 ffffffff carries into byte 11, ff..fe wraps at
 // the second increment).  The message buffer holds exactly nproofs * L bytes on the heap, so a lane of the partial block that reads past byte L is a sanitizer report;
 // guard bytes lie behind the traces.  Checked per proof: every row of (A z) o (B z) = C z holds; the instance is One, the icb bits, the bits of zkaes_ctr_crypt's
@@ -13,14 +13,10 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

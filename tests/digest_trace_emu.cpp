@@ -1,5 +1,5 @@
-// tests/digest_trace_emu.cpp -- k_sha256_trace of csrc/kernels_digest.hip behind each mode's own trace kernel(s) and the key-tag kernel, and k_witness_expand, run lane by
-// lane ON THE HOST: tests/test_digest_host.py cuts the kernels' source text out of the two .hip files into kern_extract.inc and builds this file around it with
+// tests/digest_trace_emu.cpp -- k_sha256_trace of csrc/kernels_digest.cuh behind each mode's own trace kernel(s) and the key-tag kernel, and k_witness_expand, run lane by
+// lane ON THE HOST: tests/test_digest_host.py builds this file, which includes the two kernel headers behind tests/lane_emu.h, with
 // -fsanitize=address,undefined.  Shapes (mode, key bits, L, A, T, digest kind, P): ECB-128 64 T = 0 chain; ECB-128 128 T = 0 chain (the second lane re-walks, the midstate
 // is a witness); CTR-128 17 T = 1 final; CTR-128 55 and 56 T = 0 final (one compression / two); CBC-192 64 T = 1 chain; GCM-256 (17, 5) T = 1 final P = 64; ECB-256 64
 // T = 2 chain.  Two proofs with different keys, messages, headers and H_in per launch (proof 0 starts from SHA-256's initial value except for CBC); the message, key and
@@ -17,14 +17,11 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
+#include "kernels_digest.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

@@ -1,7 +1,7 @@
 // tests/gcm_segment_keytag_trace_emu.cpp -- the trace of a GCM segment HEAD key with key_tag_blocks = T: k_aes_trace_gcm_seg, k_ghash_trace_seg and
-// k_key_tag_trace of csrc/kernels_witness.hip, k_commit_trace of csrc/kernels_digest.hip, k_reveal_trace of csrc/kernels_reveal.hip for the reveal shape and
-// k_witness_expand, run lane by lane ON THE HOST: tests/test_gcm_segments_keytag_host.py cuts the kernels' source text out of the three .hip files into kern_extract.inc
-// and builds this file around it with -fsanitize=address,undefined.  Shapes: head c = 1, A = 0, AES-128, T = 1; head c = 2, A = 5, AES-128, T = 2; head c = 1, A = 13,
+// k_key_tag_trace of csrc/kernels_witness.cuh, k_commit_trace of csrc/kernels_digest.cuh, k_reveal_trace of csrc/kernels_reveal.cuh for the reveal shape and
+// k_witness_expand, run lane by lane ON THE HOST: tests/test_gcm_segments_keytag_host.py builds this file, which includes the three kernel headers behind
+// tests/lane_emu.h, with -fsanitize=address,undefined.  Shapes: head c = 1, A = 0, AES-128, T = 1; head c = 2, A = 5, AES-128, T = 2; head c = 1, A = 13,
 // AES-256, T = 1; head c = 1, A = 5, AES-192, T = 1 with reveal.  Every head is segment 0 of a real record of two segments, as in tests/gcm_segment_trace_emu.cpp.  Two
 // proofs with different keys, messages, ivs, aad and salts per launch; the message, key and header buffers hold exactly the bytes that exist, on the heap, and guard
 // bytes lie behind the traces.  The kernels are launched as ProvingKeyImpl::launch_trace launches them: the segment kernels, the tag kernel at the circuit's key_tag_off
@@ -23,16 +23,12 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-struct alignas(16) uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
+#include "kernels_digest.cuh"
+#include "kernels_reveal.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

@@ -1,6 +1,6 @@
 // tests/gcm_segment_reveal_trace_emu.cpp -- the trace of a GCM segment key with reveal = 1: k_aes_trace_gcm_seg and k_ghash_trace_seg of
-// csrc/kernels_witness.hip, k_commit_trace of csrc/kernels_digest.hip, k_reveal_trace of csrc/kernels_reveal.hip behind them and k_witness_expand, run lane by lane ON THE
-// HOST: tests/test_gcm_segments_reveal_host.py cuts the kernels' source text out of the three .hip files into kern_extract.inc and builds this file around it with
+// csrc/kernels_witness.cuh, k_commit_trace of csrc/kernels_digest.cuh, k_reveal_trace of csrc/kernels_reveal.cuh behind them and k_witness_expand, run lane by lane ON THE
+// HOST: tests/test_gcm_segments_reveal_host.py builds this file, which includes the three kernel headers behind tests/lane_emu.h, with
 // -fsanitize=address,undefined.  Shapes: head (A = 13, c = 1), mid (c = 1), tail (Lt = 7, c = 1); head (A = 0, c = 2), tail (Lt = 17, c = 2); an AES-256 mid (c = 1).
 // Every shape is a segment of a real record, as in tests/gcm_segment_trace_emu.cpp -- a head is segment 0 of two, a mid segment 1 of three, a tail segment 1 of two --
 // under ONE mask over the record, every second byte of it open and then some, so that the segment is proven under its slice (statement.hpp chunk_mask_slice) and the
@@ -25,16 +25,12 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-struct alignas(16) uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
+#include "kernels_digest.cuh"
+#include "kernels_reveal.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

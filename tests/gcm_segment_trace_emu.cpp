@@ -1,6 +1,6 @@
-// tests/gcm_segment_trace_emu.cpp -- k_aes_trace_gcm_seg and k_ghash_trace_seg of csrc/kernels_witness.hip, k_commit_trace of csrc/kernels_digest.hip and
-// k_witness_expand, run lane by lane ON THE HOST: tests/test_gcm_segments_host.py cuts the kernels' source text out of the two .hip files into kern_extract.inc and builds
-// this file around it with -fsanitize=address,undefined.  Shapes: head (A = 5, c = 1), head (A = 0, c = 2), mid (c = 1), mid (c = 2), tail (Lt = 7, c = 1), tail
+// tests/gcm_segment_trace_emu.cpp -- k_aes_trace_gcm_seg and k_ghash_trace_seg of csrc/kernels_witness.cuh, k_commit_trace of csrc/kernels_digest.cuh and
+// k_witness_expand, run lane by lane ON THE HOST: tests/test_gcm_segments_host.py builds this file, which includes the two kernel headers behind
+// tests/lane_emu.h, with -fsanitize=address,undefined.  Shapes: head (A = 5, c = 1), head (A = 0, c = 2), mid (c = 1), mid (c = 2), tail (Lt = 7, c = 1), tail
 // (Lt = 32, c = 2), an AES-256 mid (c = 1).  Every shape is a segment of a real record -- a head is segment 0 of a two-segment record, a mid segment 1 of three, a tail
 // segment 1 of two -- so that everything the instance is compared with comes from the host-only entries: zkaes_gcm_encrypt_ks, zkaes_gcm_boundaries, zkaes_gcm_commit.
 // Two proofs with different keys, messages, ivs, aad and salts per launch; the message, key and header buffers hold exactly the bytes that exist, on the heap, and guard
@@ -19,14 +19,11 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
+#include "kernels_digest.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

@@ -1,5 +1,5 @@
-// tests/gcm_trace_emu.cpp -- k_aes_trace_gcm, k_ghash_trace and k_witness_expand of csrc/kernels_witness.hip run lane by lane ON THE HOST: tests/test_gcm_host.py cuts the
-// kernels' source text out of the .hip file into kern_extract.inc and builds this file around it with -fsanitize=address,undefined.  Shapes: (L, A) = (1, 0), (16, 0),
+// tests/gcm_trace_emu.cpp -- k_aes_trace_gcm, k_ghash_trace and k_witness_expand of csrc/kernels_witness.cuh run lane by lane ON THE HOST: tests/test_gcm_host.py builds
+// this file, which includes that header behind tests/lane_emu.h, with -fsanitize=address,undefined.  Shapes: (L, A) = (1, 0), (16, 0),
 // (17, 5), (16, 20), (33, 16), two proofs per launch.  The message buffer holds exactly nproofs * L bytes and the header buffer exactly nproofs * (12 + A) bytes on the
 // heap, so a lane that reads past a partial block is a sanitizer report; guard bytes lie behind the traces, and every byte of the GCM tail must have been written.
 // Checked per proof: every row of (A z) o (B z) = C z holds; the instance is One, the iv, aad, ciphertext and tag bits of zkaes_gcm_encrypt, zero padding; every q byte
@@ -13,14 +13,10 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

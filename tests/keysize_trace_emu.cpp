@@ -1,5 +1,5 @@
-// tests/keysize_trace_emu.cpp -- the trace kernels of csrc/kernels_witness.hip instantiated for NK = 6 and 8 (AES-192, AES-256) and k_witness_expand, run lane by lane ON
-// THE HOST: tests/test_keysize_host.py cuts the kernels' source text out of the .hip file into kern_extract.inc and builds this file around it with
+// tests/keysize_trace_emu.cpp -- the trace kernels of csrc/kernels_witness.cuh instantiated for NK = 6 and 8 (AES-192, AES-256) and k_witness_expand, run lane by lane ON
+// THE HOST: tests/test_keysize_host.py builds this file, which includes that header behind tests/lane_emu.h, with
 // -fsanitize=address,undefined.  Shapes per key size: ECB nb = 1 and 2, CBC nb = 2, CTR L = 17 under the counter ff..ff (it wraps at the one increment), GCM (L, A) =
 // (17, 5) and (1, 0); two proofs with different keys per launch.  The message, key and header buffers hold exactly the bytes that exist, on the heap, so a lane that
 // reads a key at the AES-128 stride, or past a partial block, is a sanitizer report; guard bytes lie behind the traces, whose size is the layout macros' for that NK.
@@ -13,14 +13,10 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

@@ -1,5 +1,5 @@
-// tests/keytag_trace_emu.cpp -- k_key_tag_trace of csrc/kernels_witness.hip behind each mode's own trace kernel(s), and k_witness_expand, run lane by lane ON THE HOST:
-// tests/test_keytag_host.py cuts the kernels' source text out of the .hip file into kern_extract.inc and builds this file around it with -fsanitize=address,undefined.
+// tests/keytag_trace_emu.cpp -- k_key_tag_trace of csrc/kernels_witness.cuh behind each mode's own trace kernel(s), and k_witness_expand, run lane by lane ON THE HOST:
+// tests/test_keytag_host.py builds this file, which includes that header behind tests/lane_emu.h, with -fsanitize=address,undefined.
 // Shapes: ECB-128 16 B T = 1, ECB-256 16 B T = 2, CBC-192 32 B T = 1, CTR-128 17 B T = 2, GCM-256 (17, 5) T = 1; two proofs with different keys per launch; the message,
 // key and header buffers hold exactly the bytes that exist, on the heap, and guard bytes lie behind the traces.
 // Checked per shape: the tagged circuit's header (T, the tag offset = the untagged circuit's trace length rounded up to 16, the trace length); every byte of the tag
@@ -15,14 +15,10 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

@@ -1,6 +1,6 @@
-// tests/reveal_trace_emu.cpp -- k_reveal_trace of csrc/kernels_reveal.hip behind each mode's own trace kernel(s), the key-tag kernel and k_sha256_trace, and
-// k_witness_expand, run lane by lane ON THE HOST: tests/test_reveal_host.py cuts the kernels' source text out of the three .hip files into kern_extract.inc and builds this
-// file around it with -fsanitize=address,undefined.  Shapes (mode, key bits, L, A, T, digest kind): ECB-128 16; CTR-128 1 and 17 with T = 1 and a final digest; CBC-192 32;
+// tests/reveal_trace_emu.cpp -- k_reveal_trace of csrc/kernels_reveal.cuh behind each mode's own trace kernel(s), the key-tag kernel and k_sha256_trace, and
+// k_witness_expand, run lane by lane ON THE HOST: tests/test_reveal_host.py builds this file, which includes the three kernel headers behind tests/lane_emu.h,
+// with -fsanitize=address,undefined.  Shapes (mode, key bits, L, A, T, digest kind): ECB-128 16; CTR-128 1 and 17 with T = 1 and a final digest; CBC-192 32;
 // GCM-256 (17, 5); ECB-256 64 with T = 2 and a chain digest.  Masks: all zero, all one, only byte 0, only byte L - 1, bytes 15 and 16 (the lane boundary; the ones that
 // exist), alternating -- two proofs with different masks, keys, messages and headers per launch, three launches per shape.  The message, key and header buffers hold
 // exactly the bytes that exist, on the heap, and guard bytes lie behind the traces.
@@ -19,16 +19,12 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-struct D3 { unsigned x; };
-static D3 blockIdx, blockDim{1}, threadIdx{0};
-struct alignas(16) uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-#include "kern_extract.inc"
+#include "lane_emu.h"
+#include "kernels_witness.cuh"
+#include "kernels_digest.cuh"
+#include "kernels_reveal.cuh"
 using namespace zk;
+using namespace zk::gpu;
 static long long rowdot(const CsrMatrix &m, size_t r, const std::vector<uint8_t> &z) { long long a = 0; for (uint32_t i = m.rowptr[r]; i < m.rowptr[r + 1]; i++) a += z[m.col[i]] ? m.coeff[i] : 0; return a; }
 static size_t unsatisfied(const Circuit &c, const std::vector<uint8_t> &z) {
     size_t bad = 0;

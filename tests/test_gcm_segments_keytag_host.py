@@ -206,11 +206,6 @@ def test_verifiers_refuse_a_tag_that_does_not_fit_the_head(api):
             api.verify_gcm_records_batch([rec], device=False, key_tag=kt[:15])
 
 
-def _cut(text, begin, end):
-    a = text.index(begin)
-    return text[a:text.index(end, a)]
-
-
 def test_layout_macros_of_a_tagged_head():
     """trace_layout.h through the preprocessor: its static_asserts hold (it compiles); a head's tag slot 0 lies at its segment trace length, a multiple of 16, the slots
     follow at the block stride, the reveal region begins where they end, and T = 0 leaves every length what it was"""
@@ -230,22 +225,16 @@ def test_layout_macros_of_a_tagged_head():
 
 
 def test_segment_keytag_kernels_on_host_under_sanitizers():
-    """the source text of k_aes_trace_gcm_seg, k_ghash_trace_seg and k_key_tag_trace (csrc/kernels_witness.hip), k_commit_trace (csrc/kernels_digest.hip), k_reveal_trace
-    (csrc/kernels_reveal.hip) and k_witness_expand, compiled for the host and run lane by lane under ASan + UBSan (tests/gcm_segment_keytag_trace_emu.cpp, a stand-alone
-    program: nothing is loaded into python), over the four head shapes listed there, two proofs per launch"""
-    wit = open(os.path.join(CSRC, "kernels_witness.hip")).read()
-    dig = open(os.path.join(CSRC, "kernels_digest.hip")).read()
-    rev = open(os.path.join(CSRC, "kernels_reveal.hip")).read()
-    parts = [_cut(wit, "__device__ __forceinline__ uint8_t xtime", "template <bool CBC>\nstatic void launch_aes_trace"), _cut(wit, "__global__ void k_witness_expand(", "void witness_expand("),
-             _cut(dig, "__device__ const uint32_t SHA256_RK[64]", "// what the entry checks before any lane runs"), _cut(rev, "// hdrs: nproofs x hdr_stride bytes", "// what the entry checks before any lane runs")]
-    assert "k_aes_trace_gcm_seg" in parts[0] and "k_ghash_trace_seg" in parts[0] and "k_key_tag_trace" in parts[0] and "k_commit_trace" in parts[2] and "k_reveal_trace" in parts[3]
+    """k_aes_trace_gcm_seg, k_ghash_trace_seg and k_key_tag_trace (csrc/kernels_witness.cuh), k_commit_trace (csrc/kernels_digest.cuh), k_reveal_trace
+    (csrc/kernels_reveal.cuh) and k_witness_expand -- the very headers the library compiles for the device -- compiled for the host and run lane by lane under ASan + UBSan
+    (tests/gcm_segment_keytag_trace_emu.cpp, a stand-alone program: nothing is loaded into python), over the four head shapes listed there, two proofs per launch"""
+    wit, dig, rev = (open(os.path.join(CSRC, "kernels_%s.cuh" % name)).read() for name in ("witness", "digest", "reveal"))
+    assert "k_aes_trace_gcm_seg" in wit and "k_ghash_trace_seg" in wit and "k_key_tag_trace" in wit and "k_witness_expand" in wit and "k_commit_trace" in dig and "k_reveal_trace" in rev
     for word in ("atomic", "__shared__", "__syncthreads", "__shfl", "hipLaunch"):                   # one writer per byte needs no atomics; no LDS, barrier or cross-lane operation
-        assert word not in parts[0] and word not in parts[2] and word not in parts[3]
+        assert word not in wit and word not in dig and word not in rev
     with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "kern_extract.inc"), "w") as f:
-            f.write("\n".join(parts))
         exe = os.path.join(d, "gcm_segment_keytag_trace_emu")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unknown-pragmas", "-I", CSRC, "-I", d,
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unknown-pragmas", "-I", CSRC, "-I", os.path.join(ROOT, "tests"),
                                os.path.join(ROOT, "tests", "gcm_segment_keytag_trace_emu.cpp")] + HOST_SOURCES + ["-o", exe])
         out = subprocess.run([exe], capture_output=True, text=True, timeout=1800)
         assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]

@@ -207,29 +207,23 @@ def test_verifier_refuses_the_two_invalid_arguments_and_the_other_kind(api):
     assert api.verify_gcm_segments((ark, None, ark), [proof, proof], iv, b"", ct, tag, coms, 1) == [False, False]
 
 
-def _cut(text, begin, end):
-    a = text.index(begin)
-    return text[a:text.index(end, a)]
+def _signature(text, kernel):
+    a = text.index("__global__ void %s(" % kernel)
+    return text[a:text.index(") {", a)]
 
 
 def test_segment_reveal_kernels_on_host_under_sanitizers():
-    """the source text of k_aes_trace_gcm_seg and k_ghash_trace_seg (csrc/kernels_witness.hip), k_commit_trace (csrc/kernels_digest.hip), k_reveal_trace
-    (csrc/kernels_reveal.hip) and k_witness_expand, compiled for the host and run lane by lane under ASan + UBSan (tests/gcm_segment_reveal_trace_emu.cpp, a stand-alone
-    program: nothing is loaded into python), over the shapes listed there, two proofs per launch"""
-    wit = open(os.path.join(CSRC, "kernels_witness.hip")).read()
-    dig = open(os.path.join(CSRC, "kernels_digest.hip")).read()
-    rev = open(os.path.join(CSRC, "kernels_reveal.hip")).read()
-    parts = [_cut(wit, "__device__ __forceinline__ uint8_t xtime", "template <bool CBC>\nstatic void launch_aes_trace"), _cut(wit, "__global__ void k_witness_expand(", "void witness_expand("),
-             _cut(dig, "__device__ const uint32_t SHA256_RK[64]", "// what the entry checks before any lane runs"), _cut(rev, "// hdrs: nproofs x hdr_stride bytes", "// what the entry checks before any lane runs")]
-    assert "k_aes_trace_gcm_seg" in parts[0] and "k_ghash_trace_seg" in parts[0] and "k_commit_trace" in parts[2] and "k_reveal_trace" in parts[3]
+    """k_aes_trace_gcm_seg and k_ghash_trace_seg (csrc/kernels_witness.cuh), k_commit_trace (csrc/kernels_digest.cuh), k_reveal_trace (csrc/kernels_reveal.cuh) and
+    k_witness_expand -- the very headers the library compiles for the device -- compiled for the host and run lane by lane under ASan + UBSan
+    (tests/gcm_segment_reveal_trace_emu.cpp, a stand-alone program: nothing is loaded into python), over the shapes listed there, two proofs per launch"""
+    wit, dig, rev = (open(os.path.join(CSRC, "kernels_%s.cuh" % name)).read() for name in ("witness", "digest", "reveal"))
+    assert "k_aes_trace_gcm_seg" in wit and "k_ghash_trace_seg" in wit and "k_witness_expand" in wit and "k_commit_trace" in dig and "k_reveal_trace" in rev
     for word in ("atomic", "__shared__", "__syncthreads", "__shfl", "hipLaunch"):                   # one writer per byte needs no atomics; no LDS, barrier or cross-lane operation
-        assert word not in parts[0] and word not in parts[2] and word not in parts[3]
-    assert "revealed" not in _cut(rev, "__global__ void k_reveal_trace(", ") {")                   # the kernel is never handed `revealed`
+        assert word not in wit and word not in dig and word not in rev
+    assert "revealed" not in _signature(rev, "k_reveal_trace")                                     # the kernel is never handed `revealed`
     with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "kern_extract.inc"), "w") as f:
-            f.write("\n".join(parts))
         exe = os.path.join(d, "gcm_segment_reveal_trace_emu")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unknown-pragmas", "-I", CSRC, "-I", d,
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unknown-pragmas", "-I", CSRC, "-I", os.path.join(ROOT, "tests"),
                                os.path.join(ROOT, "tests", "gcm_segment_reveal_trace_emu.cpp")] + HOST_SOURCES + ["-o", exe])
         out = subprocess.run([exe], capture_output=True, text=True, timeout=1800)
         assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]

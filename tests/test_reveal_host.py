@@ -201,29 +201,23 @@ def test_verifiers_refuse_the_two_invalid_arguments(api):
         assert rows[j] == plain[j] + bits(mask[2 * j:2 * j + 2]) + bits(api.reveal_bytes(m, mask)[16 * j:16 * j + 16])
 
 
-def _cut(text, begin, end):
-    a = text.index(begin)
-    return text[a:text.index(end, a)]
+def _signature(text, kernel):
+    a = text.index("__global__ void %s(" % kernel)
+    return text[a:text.index(") {", a)]
 
 
 def test_reveal_trace_kernel_on_host_under_sanitizers():
-    """the source text of k_reveal_trace (csrc/kernels_reveal.hip), behind the mode kernels and the tag kernel of csrc/kernels_witness.hip and k_sha256_trace of
-    csrc/kernels_digest.hip and ahead of k_witness_expand, compiled for the host and run lane by lane under ASan + UBSan (tests/reveal_trace_emu.cpp, a stand-alone program:
-    nothing is loaded into python), over the shapes and masks listed there, two proofs per launch"""
-    wit = open(os.path.join(CSRC, "kernels_witness.hip")).read()
-    dig = open(os.path.join(CSRC, "kernels_digest.hip")).read()
-    rev = open(os.path.join(CSRC, "kernels_reveal.hip")).read()
-    parts = [_cut(wit, "__device__ __forceinline__ uint8_t xtime", "template <bool CBC>\nstatic void launch_aes_trace"), _cut(wit, "__global__ void k_witness_expand(", "void witness_expand("),
-             _cut(dig, "__device__ const uint32_t SHA256_RK[64]", "// The boundary commitments of a GCM segment"), _cut(rev, "// hdrs: nproofs x hdr_stride bytes", "// what the entry checks before any lane runs")]
-    assert "k_reveal_trace" in parts[3] and "k_sha256_trace" in parts[2]
+    """k_reveal_trace (csrc/kernels_reveal.cuh), behind the mode kernels and the tag kernel of csrc/kernels_witness.cuh and k_sha256_trace of csrc/kernels_digest.cuh and
+    ahead of k_witness_expand -- the very headers the library compiles for the device -- compiled for the host and run lane by lane under ASan + UBSan
+    (tests/reveal_trace_emu.cpp, a stand-alone program: nothing is loaded into python), over the shapes and masks listed there, two proofs per launch"""
+    wit, dig, rev = (open(os.path.join(CSRC, "kernels_%s.cuh" % name)).read() for name in ("witness", "digest", "reveal"))
+    assert "k_reveal_trace" in rev and "k_sha256_trace" in dig and "k_witness_expand" in wit
     for word in ("atomic", "__shared__", "__syncthreads", "__shfl", "hipLaunch"):                   # one writer per byte needs no atomics; no LDS, barrier or cross-lane operation
-        assert word not in parts[3]
-    assert "revealed" not in _cut(rev, "__global__ void k_reveal_trace(", ") {")                   # the kernel is never handed `revealed`
+        assert word not in rev and word not in dig and word not in wit
+    assert "revealed" not in _signature(rev, "k_reveal_trace")                                     # the kernel is never handed `revealed`
     with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "kern_extract.inc"), "w") as f:
-            f.write("\n".join(parts))
         exe = os.path.join(d, "reveal_trace_emu")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unknown-pragmas", "-I", CSRC, "-I", d,
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wno-unknown-pragmas", "-I", CSRC, "-I", os.path.join(ROOT, "tests"),
                                os.path.join(ROOT, "tests", "reveal_trace_emu.cpp")] + HOST_SOURCES + ["-o", exe])
         out = subprocess.run([exe], capture_output=True, text=True, timeout=1800)
         assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
