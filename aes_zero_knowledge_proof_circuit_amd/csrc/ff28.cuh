@@ -161,29 +161,89 @@ struct Fp28 {
         r.l[N - 1] = (uint32_t)(t[2 * N - 1] + c);
         return r;
     }
-    // The same product with the rows' "+ 2^28 - 1" riding on the multiply-accumulate chains: columns 0..13 START at `bias`, which must hold 2^28 - 1 in a register pair
-    // the compiler cannot see through and that was defined before the operands (hot_loop_bias() at kernel entry).  A known constant is re-associated to the end
-    // of every column's sum and costs a 64-bit add per row -- 14 per product; an unknown early value stays the chain's first addend.
-    ZK_HD static Fp28 mul_biased(const Fp28 &a, const Fp28 &b, uint64_t bias) {
+
+    // ---- the hot loop's product, in two halves (p = 1 (mod 2^28) only: BLS12-377's q).  The row-wise form above sums every column first and joins the carries afterwards:
+    // 27 stand-alone 64-bit adds (v_lshl_add_u64) per product, 14 row carries and 13 limb normalisations.
+    // LOWER half (mul_low: columns 0..N-1, row-wise as above, restricted to the columns i + j < N): it leaves the N multipliers m_i and the carry out of column N - 1.
+    // UPPER half (mul_high: columns N..2N-2, product scanning): a column's multiply-add chain STARTS from the carry of the column below -- v_mad_u64_u32 has a 64-bit
+    // addend slot, so joining the carry costs nothing and the 13 normalisation adds go away.  (The lower columns keep the row-wise order: seeded with the carry a row would
+    // cost the same shift, add of the bias and v_bitop3 it costs now.)  LLVM re-associates a late-defined addend to the END of a sum, so on the device every step of a chain
+    // is followed by an empty asm that pins the order; the host branch has none and adds the same terms in the same order.
+    // Bound: a chain adds the non-negative terms of the row-wise form's column k and the carry that column was joined with, in another order; every partial sum is at most
+    // that total, which is below 2^64 for every operand pair the callers document (normalized x lazy: < 2^63; te_madd_hot's lazy pairs: 181 x 2^56, te28.cuh).  Each
+    // column yields the same limb and the same carry as the row-wise form: the result is the same integer limb for limb, not merely the same residue.
+    // Price: a chain is a run of dependent v_mad_u64_u32, and gfx950 wants one wait state between a v_mad_u64_u32 and the one that reads its result.  A lone product
+    // (W = 1) gets an s_nop wherever the compiler finds no independent instruction; te_madd_hot therefore ZIPS the products of one level (W = 3, W = 4): the chains advance
+    // in turn, the pins are volatile -- which holds them, and with them the steps, in source order -- and a scheduling barrier at the entry keeps the lower halves (28
+    // column registers each) from sinking into the zip, where they would overlap the W x 13 live multipliers.  k_accumulate<EdwardsLaw>: 188 -> 97 v_lshl_add_u64,
+    // 3,495 -> 3,404 VALU, 7 s_nop in the loop, 165 registers (profiles/fq_product_carry_seed.md).
+    // operator*, fma2 and sqr stay row-wise: their callers (bucket reduction, class sums, conversions) run them one at a time, the chains fill with s_nop (k_reduce_l1_pair:
+    // 1,484; k_class_partials: 1,160) and with the upper half carry-seeded k_class_partials measured 12 % and k_quad_sum 5 % SLOWER, the reduction kernels no faster (same file).
+    struct Low { uint32_t m[N]; uint64_t carry; };
+    template <bool ZIPPED> ZK_HD static void pin(uint64_t &acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (ZIPPED) asm volatile("" : "+v"(acc)); else asm("" : "+v"(acc));
+#else
+        (void)acc;
+#endif
+    }
+    // columns start at `bias` = 2^28 - 1 (see mul_biased): when row i is reached, u = column i + 2^28 - 1, its high part is the row's carry and m_i = ~u mod 2^28 (reduce_row)
+    ZK_HD static Low mul_low(const Fp28 &a, const Fp28 &b, uint64_t bias) {
         static_assert(mod28(0) == 1u && PINV == MASK, "written for p = 1 (mod 2^28)");
-        uint64_t t[2 * N];
+        uint64_t t[N];
+        Low lo;
 #pragma unroll
-        for (int i = 0; i < 2 * N; i++) t[i] = i < N ? bias : 0;
+        for (int i = 0; i < N; i++) t[i] = bias;
 #pragma unroll
         for (int i = 0; i < N; i++) {
 #pragma unroll
-            for (int j = 0; j < N; j++) t[i + j] += (uint64_t)a.l[j] * b.l[i];
-            const uint64_t u = t[i];                            // = column + 2^28 - 1 (see reduce_row)
-            const uint32_t m = ~(uint32_t)u & MASK;
+            for (int j = 0; i + j < N; j++) t[i + j] += (uint64_t)a.l[j] * b.l[i];
+            const uint64_t u = t[i];
+            lo.m[i] = ~(uint32_t)u & MASK;
 #pragma unroll
-            for (int j = 1; j < N; j++) t[i + j] += (uint64_t)m * mod28(j);
-            t[i + 1] += u >> 28;
+            for (int j = 1; i + j < N; j++) t[i + j] += (uint64_t)lo.m[i] * mod28(j);
+            if (i + 1 < N) t[i + 1] += u >> 28; else lo.carry = u >> 28;
         }
-        Fp28 r;
-        uint64_t c = 0;
+        return lo;
+    }
+    // the upper halves of the W independent products a[w] b[w] whose lower halves are lo[w], zipped step by step; r[w] must not alias an operand
+    template <int W>
+    ZK_HD static void mul_high(const Fp28 *const (&a)[W], const Fp28 *const (&b)[W], const Low (&lo)[W], Fp28 *const (&r)[W]) {
+        uint64_t carry[W];
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (W > 1) __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
-        for (int i = 0; i < N - 1; i++) { uint64_t v = t[N + i] + c; r.l[i] = (uint32_t)v & MASK; c = v >> 28; }
-        r.l[N - 1] = (uint32_t)(t[2 * N - 1] + c);
+        for (int w = 0; w < W; w++) carry[w] = lo[w].carry;
+#pragma unroll
+        for (int k = N; k < 2 * N - 1; k++) {
+            uint64_t acc[W];
+#pragma unroll
+            for (int w = 0; w < W; w++) acc[w] = carry[w];
+#pragma unroll
+            for (int i = k - N + 1; i < N; i++) {
+#pragma unroll
+                for (int w = 0; w < W; w++) {
+                    acc[w] += (uint64_t)a[w]->l[k - i] * b[w]->l[i]; pin<(W > 1)>(acc[w]);
+                    acc[w] += (uint64_t)lo[w].m[i] * mod28(k - i); pin<(W > 1)>(acc[w]);
+                }
+            }
+#pragma unroll
+            for (int w = 0; w < W; w++) { r[w]->l[k - N] = (uint32_t)acc[w] & MASK; carry[w] = acc[w] >> 28; }
+        }
+#pragma unroll
+        for (int w = 0; w < W; w++) r[w]->l[N - 1] = (uint32_t)carry[w];       // column 2N - 1 holds nothing but the last carry: the top limb keeps the excess
+    }
+    // The same product as operator* in the two halves above (mul_low, mul_high<1>), with the rows' "+ 2^28 - 1" riding on the multiply-accumulate chains: columns 0..13
+    // START at `bias`, which must hold 2^28 - 1 in a register pair the compiler cannot see through and that was defined before the operands (hot_loop_bias() at kernel
+    // entry).  A known constant is re-associated to the end of every column's sum and costs a 64-bit add per row -- 14 per product; an unknown early value stays the
+    // chain's first addend.
+    ZK_HD static Fp28 mul_biased(const Fp28 &a, const Fp28 &b, uint64_t bias) {
+        Fp28 r;
+        const Low lo[1] = {mul_low(a, b, bias)};
+        const Fp28 *const pa[1] = {&a}, *const pb[1] = {&b};
+        Fp28 *const pr[1] = {&r};
+        mul_high<1>(pa, pb, lo, pr);
         return r;
     }
     ZK_HD static uint64_t hot_loop_bias() {

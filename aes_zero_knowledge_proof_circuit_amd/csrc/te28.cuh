@@ -82,12 +82,22 @@ ZK_HD Niels28<P> niels_load_signed(const Niels28<P> *rec, bool neg) {
 // (2p' = kp_spread<2> < 2 per limb).  The widest products, E U and U V, put 14 x 12 x 2^56 into a column, the reduction 13 x 2^56 more: 181 x 2^56 < 2^64
 // (tests/test_gpu_arith.py multiplies at exactly those bounds on the device -- mul_biased with the opaque bias, and te_madd_hot itself in chains of seven -- against the
 // big-integer model of tests/arith_model.py; tests/test_ff28_host.py and tests/test_arith_model.py do the same with the host branch).
+// The products of a level are independent: their lower halves run one after the other, their upper halves -- carry-seeded multiply-add chains, ff28.cuh mul_high -- are
+// ZIPPED, three chains wide for A, B, C and four wide for the second level, so that no v_mad_u64_u32 follows the one it depends on (7 s_nop in k_accumulate, 165 registers:
+// the width was chosen with the disassembly open, profiles/fq_product_carry_seed.md; tests/test_gpu_product_columns.py and tests/ff28_columns_host_check.cpp compare the
+// zipped form limb for limb with big-integer arithmetic, every limb of E, H, U, V at its bound).
 template <class P>
 ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *next, bool next_neg, uint64_t bias) {
     using G = FpMsm<P>;
-    G A = G::mul_biased(a.y.template sub_lazy<3>(a.x), n.ymx, bias);
-    G B = G::mul_biased(a.y.add_lazy(a.x), n.ypx, bias);
-    G C = G::mul_biased(a.t, n.td, bias);
+    using Low = typename G::Low;
+    G A, B, C;
+    {
+        const G ymx = a.y.template sub_lazy<3>(a.x), ypx = a.y.add_lazy(a.x);
+        const Low lo[3] = {G::mul_low(ymx, n.ymx, bias), G::mul_low(ypx, n.ypx, bias), G::mul_low(a.t, n.td, bias)};
+        const G *const pa[3] = {&ymx, &ypx, &a.t}, *const pb[3] = {&n.ymx, &n.ypx, &n.td};
+        G *const pr[3] = {&A, &B, &C};
+        G::template mul_high<3>(pa, pb, lo, pr);
+    }
 #if defined(__HIP_DEVICE_COMPILE__)
     // pin the gather between the three products and the other four: without the first fence the compiler hoists the loads to the top of the iteration (a second register
     // set), without the second one the scheduler sinks them to its end (the gather's latency is then exposed at the top of the next addition)
@@ -102,7 +112,12 @@ ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *n
     G U = D.template sub_lazy<2>(C), V = D.add_lazy(C), F, Gg;
 #pragma unroll
     for (int i = 0; i < G::N; i++) { F.l[i] = neg ? V.l[i] : U.l[i]; Gg.l[i] = neg ? U.l[i] : V.l[i]; }
-    a.x = G::mul_biased(E, F, bias); a.y = G::mul_biased(Gg, H, bias); a.t = G::mul_biased(E, H, bias); a.z = G::mul_biased(F, Gg, bias);
+    {
+        const Low lo[4] = {G::mul_low(E, F, bias), G::mul_low(Gg, H, bias), G::mul_low(E, H, bias), G::mul_low(F, Gg, bias)};
+        const G *const pa[4] = {&E, &Gg, &E, &F}, *const pb[4] = {&F, &H, &H, &Gg};
+        G *const pr[4] = {&a.x, &a.y, &a.t, &a.z};
+        G::template mul_high<4>(pa, pb, lo, pr);
+    }
 }
 // a += b, unified (add-2008-hwcd-3): nine products.  te_add_inline is the body for the one kernel that wants two additions of a step in ONE instruction stream
 // (k_reduce_l1: a lone wave per SIMD issues dependent multiply-adds at half rate; the two independent additions of its running sums interleave); te_add is the call

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Instruction counts of the shipped gfx950 code object, per kernel (no GPU needed).
 
-    python tools/disasm_count.py [object] [kernel-substring ...]
+    python tools/disasm_count.py [--md] [object] [kernel-substring ...]
 
-Default object: csrc/build/kernels_msm.hip.o; default kernels: k_accumulate.  Prints VALU / v_mad_u64_u32 / MFMA / LDS / scratch counts
-and the VGPR / scratch figures from the kernel descriptor notes -- the numbers DESIGN.md section 3 quotes for k_accumulate<EdwardsLaw>.
+Default object: csrc/build/kernels_msm.hip.o; default kernels: k_accumulate.  Prints VALU / v_mad_u64_u32 / v_lshl_add_u64 / s_nop / MFMA / LDS / scratch counts
+and the VGPR / scratch / LDS-bytes figures from the kernel descriptor notes -- the numbers DESIGN.md section 3 quotes for k_accumulate<EdwardsLaw>.
+--md: one markdown table row per kernel (VALU, v_mad_u64_u32, v_lshl_add_u64, s_nop, VGPRs, scratch, LDS bytes): the tables of profiles/fq_product_carry_seed.md.
 """
 import os
 import re
@@ -34,6 +35,8 @@ def demangle(names):
 
 def main():
     args = sys.argv[1:]
+    md = "--md" in args
+    args = [a for a in args if a != "--md"]
     obj = os.path.join(ROOT, "aes_zero_knowledge_proof_circuit_amd", "csrc", "build", "kernels_msm.hip.o")
     if args and os.path.exists(args[0]):
         obj = os.path.abspath(args.pop(0))
@@ -59,12 +62,14 @@ def main():
             if ins:
                 funcs[cur].append(ins[0])
     meta = {}
-    for blk in re.split(r"\n\s+- ", notes):
-        name = re.search(r"\.name:\s+(\S+)", blk)
+    for blk in re.split(r"\n  - (?=\.agpr_count)", notes):          # one block per kernel (the argument list's own items stay inside it)
+        name = re.search(r"\.symbol:\s+(\S+)\.kd", blk)               # (.name also names the kernel's arguments)
         if name:
             g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, blk) or [None, "?"])[1]
-            meta[name.group(1)] = dict(vgpr=g("vgpr_count"), sgpr=g("sgpr_count"), scratch=g("private_segment_fixed_size"), lds=g("group_segment_fixed_size"), spill=g("vgpr_spill_count"))
+            meta[name.group(1)] = dict(vgpr=g("vgpr_count"), sgpr=g("sgpr_count"), scratch=g("private_segment_fixed_size"), lds_bytes=g("group_segment_fixed_size"), spill=g("vgpr_spill_count"))
     names = list(funcs)
+    if md:
+        print("| kernel | VALU | `v_mad_u64_u32` | `v_lshl_add_u64` | `s_nop` | VGPRs | scratch | LDS bytes |\n|---|---:|---:|---:|---:|---:|---:|---:|")
     dem = dict(zip(names, demangle(names)))
     for n in names:
         d = dem[n]
@@ -77,6 +82,10 @@ def main():
                    lds=sum(i.startswith("ds_") for i in ins), scratch_ops=sum(i.startswith("scratch_") for i in ins), global_loads=sum(i.startswith("global_load") for i in ins),
                    s_nop=ins.count("s_nop"), total=len(ins))
         row.update(meta.get(n, {}))
+        if md:
+            short = re.sub(r"^void ", "", d).split("(")[0].replace("zk::gpu::", "").replace("zk::", "")
+            print("| `%s` | %s |" % (short, " | ".join(str(row[k]) for k in ("valu", "mad_u64_u32", "lshl_add_u64", "s_nop", "vgpr", "scratch", "lds_bytes"))))
+            continue
         print(d[:150])
         print("   " + "  ".join("%s=%s" % kv for kv in row.items()))
 
