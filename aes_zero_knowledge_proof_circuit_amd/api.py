@@ -467,12 +467,19 @@ class ProvingKey:
         return self._witness(lib().zkaes_aes_witness_gcm, bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)))
 
     def segment_info(self):
-        """None for a key that is no GCM segment key, else {"role", "blocks", "message_bytes", "aad_bytes"}"""
+        """None for a key that is no GCM segment key, else {"role", "blocks", "message_bytes", "aad_bytes"}.  A segment key of a digest record
+        (synthesize_keys_gcm_segment(..., digest=True)) also has "digest": True and "header_bytes", the length of its proofs' headers; its role may be
+        "last", and its tail has 0 blocks and 0 message bytes"""
         out = (C.c_uint64 * 4)()
         _check(lib().zkaes_pk_segment_info(self._p, out))
         if not out[0]:
             return None
-        return {"role": ("head", "mid", "tail")[out[0] - 1], "blocks": int(out[1]), "message_bytes": int(out[2]), "aad_bytes": int(out[3])}
+        info = {"role": ("head", "mid", "tail", "last")[out[0] - 1], "blocks": int(out[1]), "message_bytes": int(out[2]), "aad_bytes": int(out[3])}
+        dg, hb = C.c_int(), C.c_size_t()
+        _check(lib().zkaes_pk_segment_digest(self._p, C.byref(dg), C.byref(hb)))
+        if dg.value:
+            info["digest"], info["header_bytes"] = True, int(hb.value)
+        return info
 
     def witness_gcm_segment(self, message, secret_key, header, mask=None):
         """z (padded instance + witness, one byte per variable) of a segment key; header = gcm_segment_header(...).  mask (a reveal segment key): the
@@ -519,6 +526,22 @@ class ProvingKey:
         out, total = C.c_void_p(), C.c_size_t()
         _check(lib().zkaes_encrypt_gcm_segment_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), self._p, seed,
                                                                C.c_uint64(first_proof_index), C.byref(out), C.byref(total), lens))
+        return _split(_take(out, total), lens, n)
+
+    def encrypt_gcm_segment_digest_batch(self, messages, secret_keys, headers, zk_seed=None, first_proof_index=0):
+        """encrypt_gcm_segment_batch over a segment key of a digest record -> the proofs.  headers: gcm_segment_header(..., h_in=) for a head or mid,
+        gcm_segment_header(..., h_in=, total_bits=) for a last, the plain header for the closing tail, whose messages are empty"""
+        n = len(messages)
+        if not len(secret_keys) == len(headers) == n:
+            raise ZkAesError("one secret key and one header per message")
+        if zk_seed is None:
+            zk_seed = os.urandom(32)
+        seed = self._seed_arg(zk_seed)
+        mb, kb, hb = b"".join(bytes(m) for m in messages), b"".join(bytes(k) for k in secret_keys), b"".join(bytes(h) for h in headers)
+        lens = (C.c_size_t * max(n, 1))()
+        out, total = C.c_void_p(), C.c_size_t()
+        _check(lib().zkaes_encrypt_gcm_segment_digest_batch_seeded_at(C.c_size_t(n), mb, C.c_size_t(len(mb)), kb, C.c_size_t(len(kb)), hb, C.c_size_t(len(hb)), self._p, seed,
+                                                                      C.c_uint64(first_proof_index), C.byref(out), C.byref(total), lens))
         return _split(_take(out, total), lens, n)
 
     def encrypt_gcm_batch(self, messages, secret_keys, ivs, aads, zk_seed=None, first_proof_index=0):
@@ -1094,7 +1117,13 @@ def verify_encryption_gcm_digest(verifying_key, proof, iv, aad, ciphertext, tag,
 # ---- GCM records longer than one proof: segment-proofs over hidden commitments (include/zkaes.h)
 CIRCUIT_AES_GCM_SEG = 6            # what ProvingKey.mode() reports for a segment key
 SEG_HEAD, SEG_MID, SEG_TAIL = 0, 1, 2
+SEG_LAST = 3                       # digest records only: the segment with the record's last data bytes, a mid with a byte length
 _SEG_ROLES = {"head": SEG_HEAD, "mid": SEG_MID, "tail": SEG_TAIL, SEG_HEAD: SEG_HEAD, SEG_MID: SEG_MID, SEG_TAIL: SEG_TAIL}
+_SEG_DIGEST_ROLES = dict(_SEG_ROLES, **{"last": SEG_LAST})
+_SEG_DIGEST_ROLES[SEG_LAST] = SEG_LAST
+# the c (data blocks per segment) of a DIGEST record over the default SRS literal (the capacity table; tests/test_gcm_segments_digest_host.py asserts it): a
+# digest segment holds whole 64-byte blocks, so c is a multiple of 4, and only AES-128 fits c = 4 there; 192- and 256-bit keys take an explicit c and a larger srs=
+GCM_SEGMENT_DIGEST_DEFAULT_C = {128: 4}
 # the largest c (data blocks per segment) at which all three roles stay inside the default SRS literal, per key size (tests/test_gcm_segments_host.py)
 GCM_SEGMENT_DEFAULT_C = {128: 4, 192: 3, 256: 2}
 GCM_SEGMENT_REVEAL_DEFAULT_C = dict(GCM_SEGMENT_DEFAULT_C)      # reveal segment keys fit the same c (the capacity table; tests/test_gcm_segments_reveal_host.py asserts it)
@@ -1120,10 +1149,23 @@ def verify_encryption_gcm_reveal(verifying_key, proof, iv, aad, ciphertext, tag,
     return bool(acc.value)
 
 
-def _seg_role(role):
+def _seg_role(role, digest=False):
+    if digest:
+        if role not in _SEG_DIGEST_ROLES:
+            raise ZkAesError('role must be "head", "mid", "last" or "tail"')
+        return _SEG_DIGEST_ROLES[role]
     if role not in _SEG_ROLES:
-        raise ZkAesError('role must be "head", "mid" or "tail"')
+        raise ZkAesError('role must be "head", "mid" or "tail" ("last" belongs to a digest record: pass digest=True)')
     return _SEG_ROLES[role]
+
+
+def _seg_digest_args(digest, reveal, key_tag_blocks):
+    """digest=True with reveal or key-tag blocks is refused here as the library refuses it"""
+    if digest and reveal:
+        raise ZkAesError("a digest segment key has no reveal form: use a reveal segment key without a digest, or a lone GCM key with digest= and reveal=True for a record of one proof")
+    if digest and _seg_key_tag_blocks(key_tag_blocks):
+        raise ZkAesError("a digest segment key takes no key_tag_blocks (a tagged digest head does not fit the default SRS): use a tagged head without a digest")
+    return bool(digest)
 
 
 def _seg_key_tag_blocks(key_tag_blocks):
@@ -1132,15 +1174,23 @@ def _seg_key_tag_blocks(key_tag_blocks):
     return int(key_tag_blocks)
 
 
-def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, reveal=False, key_tag_blocks=0):
+def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_062_064), flags=0, key_bits=128, reveal=False, key_tag_blocks=0, digest=False):
     """(ProvingKey, VerifyingKey) of one segment role.  role: "head", "mid" or "tail"; units: c, the data blocks per segment, for a head or mid, and Lt, the bytes of
     the record's last segment (1 .. 16 c), for a tail; aad_length: the record's whole aad, head only.  flags and key_bits as synthesize_keys; no digest.
     reveal: False (the default) or True: every proof of the key also exposes the segment's slice of the record's mask and of its revealed bytes, is made through
     encrypt_gcm_segments(..., mask=) and checked with verify_gcm_segments(..., mask=, revealed=).
     key_tag_blocks: 0 (the default: the key as it was), 1 or 2 for a HEAD: every proof of the key also exposes key_tag(secret_key, key_tag_blocks) and is
     checked with verify_gcm_segments(..., key_tag=); the proving calls are the same.  A mid or tail with key_tag_blocks != 0 raises: the head carries the record's tag
-    and the boundary commitments carry the key to every later segment"""
+    and the boundary commitments carry the key to every later segment.
+    digest: False (the default: the key as it was) or True: a segment key of a DIGEST record, which is nd data segments and one closing tail.  role
+    may then be "last", units = Lr, the bytes of the record's last data segment (1 .. 16 c); a "head" or "mid" takes c a multiple of 4 (whole 64-byte blocks) and
+    also proves the SHA-256 chain over its bytes; a "tail" takes units = 0 only.  The proofs are made through encrypt_gcm_segments_digest and checked with
+    verify_gcm_segments_digest against the record's states; states[-1] is hashlib.sha256(message).digest().  No reveal and no key_tag_blocks with digest=True"""
     pk, vk = C.c_void_p(), C.c_void_p()
+    if _seg_digest_args(digest, reveal, key_tag_blocks):
+        _check(lib().zkaes_synthesize_keys_gcm_seg_dg(_seg_role(role, True), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), C.c_size_t(srs[0]), C.c_size_t(srs[1]),
+                                                      C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
+        return ProvingKey(pk.value), VerifyingKey(vk.value)
     if _seg_key_tag_blocks(key_tag_blocks):
         _check(lib().zkaes_synthesize_keys_gcm_seg_kt(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_uint(key_tag_blocks), C.c_size_t(units), C.c_size_t(aad_length),
                                                       C.c_size_t(srs[0]), C.c_size_t(srs[1]), C.c_size_t(srs[2]), C.c_uint(flags), C.byref(pk), C.byref(vk)))
@@ -1150,9 +1200,11 @@ def synthesize_keys_gcm_segment(role, units, aad_length=0, srs=(866_944, 513, 4_
     return ProvingKey(pk.value), VerifyingKey(vk.value)
 
 
-def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128, reveal=False, key_tag_blocks=0):
+def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128, reveal=False, key_tag_blocks=0, digest=False):
     out = (C.c_uint64 * 12)()
-    if _seg_key_tag_blocks(key_tag_blocks):
+    if _seg_digest_args(digest, reveal, key_tag_blocks):
+        _check(lib().zkaes_circuit_info_gcm_seg_dg(_seg_role(role, True), C.c_uint(int(key_bits)), C.c_size_t(units), C.c_size_t(aad_length), out))
+    elif _seg_key_tag_blocks(key_tag_blocks):
         _check(lib().zkaes_circuit_info_gcm_seg_kt(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_uint(key_tag_blocks), C.c_size_t(units), C.c_size_t(aad_length), out))
     else:
         _check(lib().zkaes_circuit_info_gcm_seg_rv(_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), out))
@@ -1160,10 +1212,13 @@ def circuit_info_gcm_segment(role, units, aad_length=0, key_bits=128, reveal=Fal
     return dict(zip(keys, out))
 
 
-def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128, reveal=False, key_tag_blocks=0):
+def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128, reveal=False, key_tag_blocks=0, digest=False):
     rows, nnz = C.c_uint64(), C.c_uint64()
-    fn, head = lib().zkaes_circuit_matrix_gcm_seg_rv, (_seg_role(role), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), which)
-    if _seg_key_tag_blocks(key_tag_blocks):
+    dg = _seg_digest_args(digest, reveal, key_tag_blocks)
+    fn, head = lib().zkaes_circuit_matrix_gcm_seg_rv, (_seg_role(role, dg), C.c_uint(int(key_bits)), C.c_uint(int(bool(reveal))), C.c_size_t(units), C.c_size_t(aad_length), which)
+    if dg:
+        fn, head = lib().zkaes_circuit_matrix_gcm_seg_dg, head[:2] + head[3:]
+    elif _seg_key_tag_blocks(key_tag_blocks):
         fn, head = lib().zkaes_circuit_matrix_gcm_seg_kt, head[:3] + (C.c_uint(key_tag_blocks),) + head[3:]
     _check(fn(*head, C.byref(rows), C.byref(nnz), None, None, None))
     rowptr = np.zeros(rows.value + 1, dtype=np.uint32)
@@ -1173,12 +1228,31 @@ def circuit_matrix_gcm_segment(role, units, which, aad_length=0, key_bits=128, r
     return rowptr, col[:nnz.value], coeff[:nnz.value]
 
 
-def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128, reveal=False, key_tag_blocks=0):
+def gcm_segment_plan(length, aad_length=0, c=None, key_bits=128, reveal=False, key_tag_blocks=0, digest=False):
     """how a record of `length` bytes splits into segments of c data blocks (None = GCM_SEGMENT_DEFAULT_C[key_bits]) -> {"n", "c", "aad", "tail_bytes", "segments"};
     a segment is {"role", "offset", "bytes", "ctr0"}.  The keys the record needs: head (c, aad_length), mid (c) when n > 2, tail (tail_bytes).  reveal: the plan for
     reveal segment keys: the default c is GCM_SEGMENT_REVEAL_DEFAULT_C[key_bits] -- equal to the plain one, the capacity table of 9j has the room -- and
     every segment also carries "mask_offset" and "mask_bytes", its slice of the record's mask.  key_tag_blocks: the plan for a head with that many key-tag blocks
-    (DESIGN.md 9l): the default c is GCM_SEGMENT_KEYTAG_DEFAULT_C[key_tag_blocks][key_bits], with and without reveal -- the plain one for one block, one less for two"""
+    (DESIGN.md 9l): the default c is GCM_SEGMENT_KEYTAG_DEFAULT_C[key_tag_blocks][key_bits], with and without reveal -- the plain one for one block, one less for two.
+    digest=True: the plan of a DIGEST record -> {"n", "nd", "c", "aad", "last_bytes", "tail_bytes": 0, "segments"}: nd = ceil(length / (16 c)) data
+    segments -- roles "head", "mid" and, for the one with the record's last "last_bytes" = 1 .. 16 c bytes, "last" -- and the closing "tail" of 0 bytes: n = nd + 1 proofs.
+    The keys the record needs: head (c, aad_length), mid (c) when nd > 2, last (last_bytes), tail (0), all with digest=True.  c is a multiple of 4 and defaults to
+    GCM_SEGMENT_DIGEST_DEFAULT_C[key_bits], which has 128-bit keys only: 192- and 256-bit keys must pass c, and their digest segment keys need a larger srs= than the
+    default literal.  A record with length <= 16 c raises: it fits one proof of a lone GCM key with digest="final" (synthesize_keys_gcm)"""
+    if digest:
+        _seg_digest_args(digest, reveal, key_tag_blocks)
+        if c is None:
+            if key_bits not in GCM_SEGMENT_DIGEST_DEFAULT_C:
+                raise ZkAesError("GCM digest segments: no default c for %d-bit keys over the default SRS: pass c (a multiple of 4) and synthesize the keys over a larger srs=" % key_bits)
+            c = GCM_SEGMENT_DIGEST_DEFAULT_C[key_bits]
+        if c < 1 or c % 4 or not 1 <= length <= 1 << 20 or not 0 <= aad_length <= 1 << 16:
+            raise ZkAesError("GCM digest segments: a record has 1 .. 2^20 bytes, at most 65536 bytes of aad, and c is a multiple of 4 (a digest segment holds whole 64-byte blocks)")
+        if length <= 16 * c:
+            raise ZkAesError("GCM digest segments: this record fits one segment; a record that fits one proof goes through the lone digest key, synthesize_keys_gcm(..., digest=\"final\")")
+        nd = (length + 16 * c - 1) // (16 * c)
+        segs = [{"role": "head" if s == 0 else "last" if s == nd - 1 else "mid", "offset": 16 * c * s, "bytes": min(16 * c, length - 16 * c * s), "ctr0": 2 + s * c} for s in range(nd)]
+        segs.append({"role": "tail", "offset": length, "bytes": 0, "ctr0": 2 + nd * c})
+        return {"n": nd + 1, "nd": nd, "c": c, "aad": aad_length, "last_bytes": segs[nd - 1]["bytes"], "tail_bytes": 0, "segments": segs}
     if c is None:
         if _seg_key_tag_blocks(key_tag_blocks):
             c = GCM_SEGMENT_KEYTAG_DEFAULT_C[key_tag_blocks][key_bits]
@@ -1222,9 +1296,15 @@ def gcm_length_block(aad_length, length):
     return (8 * aad_length).to_bytes(8, "big") + (8 * length).to_bytes(8, "big")
 
 
-def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_block=None, aad=b"", mask=None):
+def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_block=None, aad=b"", mask=None, h_in=None, total_bits=None):
     """the 80 + A bytes a segment witness takes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad; a field the role does not use may stay None.  mask (a
-    reveal segment key): the segment's own mask as bytes of ceil(len / 8), appended last: the 80 + A + ceil(len / 8) bytes of a reveal segment proof's header"""
+    reveal segment key): the segment's own mask as bytes of ceil(len / 8), appended last: the 80 + A + ceil(len / 8) bytes of a reveal segment proof's header.
+    h_in (a digest segment key): the 32-byte state entering the segment, behind the aad; total_bits (a last): 8 x the bytes hashed up to the record's end,
+    appended as be64 and eight zero bytes.  The closing tail of a digest record takes neither"""
+    if (h_in is not None and len(h_in) != 32) or (total_bits is not None and (h_in is None or not 0 <= int(total_bits) < 1 << 64)):
+        raise ZkAesError("h_in is 32 bytes, and total_bits (below 2^64) goes with h_in")
+    if h_in is not None and mask is not None:
+        raise ZkAesError("a digest segment key has no reveal form: h_in and mask do not go together")
     if len(iv) != 12:
         raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
     parts = [bytes(iv), int(ctr0).to_bytes(4, "big")]
@@ -1233,7 +1313,8 @@ def gcm_segment_header(iv, ctr0, y_in=None, salt_in=None, salt_out=None, length_
         if len(field) != 16:
             raise ZkAesError("Y_in, the salts and the length block are 16 bytes each")
         parts.append(field)
-    return b"".join(parts) + bytes(aad) + (b"" if mask is None else bytes(mask))
+    dg = b"" if h_in is None else bytes(h_in) + (b"" if total_bits is None else int(total_bits).to_bytes(8, "big") + bytes(8))
+    return b"".join(parts) + bytes(aad) + dg + (b"" if mask is None else bytes(mask))
 
 
 def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_segment=0, count=None, zk_seed=None, mask=None):
@@ -1271,6 +1352,108 @@ def encrypt_gcm_segments(message, secret_key, iv, aad, keys, salts=None, first_s
                                                       None if mid is None else mid._p, tail._p, b"".join(bytes(s) for s in salts), seed, C.c_size_t(first_segment), C.c_size_t(count), ct, tag,
                                                       coms, C.byref(out), C.byref(total), lens))
     return ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(n - 1)], _split(_take(out, total), lens, count)
+
+
+def gcm_digest_plan(message, secret_key, iv, aad, c, h_in=None, digest_prefix=0):
+    """(ys, states) of a DIGEST record (host only): the nd GHASH accumulators behind its data segments -- gcm_boundaries stops one short; the last one here is
+    the accumulator behind the record's last data block, ahead of the length block, which enters the closing tail -- and the nd + 1 SHA-256 states, states[0] = h_in
+    (None = the initial value), states[nd] = the digest of (digest_prefix bytes hashed into h_in) || message: hashlib.sha256(message).digest() with the defaults"""
+    _gcm_args(secret_key, iv)
+    if h_in is not None and len(h_in) != 32:
+        raise ZkAesError("h_in must be 32 bytes")
+    nd = C.c_size_t()
+    args = (bytes(message), C.c_size_t(len(message)), bytes(secret_key), C.c_size_t(len(secret_key)), bytes(iv), bytes(aad), C.c_size_t(len(aad)), C.c_size_t(c),
+            None if h_in is None else bytes(h_in), C.c_uint64(digest_prefix))
+    _check(lib().zkaes_gcm_digest_plan(*args, None, C.c_size_t(0), None, C.c_size_t(0), C.byref(nd)))
+    ys, st = C.create_string_buffer(16 * nd.value), C.create_string_buffer(32 * (nd.value + 1))
+    _check(lib().zkaes_gcm_digest_plan(*args, ys, C.c_size_t(len(ys)), st, C.c_size_t(len(st)), C.byref(nd)))
+    return [ys.raw[16 * s:16 * s + 16] for s in range(nd.value)], [st.raw[32 * s:32 * s + 32] for s in range(nd.value + 1)]
+
+
+def encrypt_gcm_segments_digest(message, secret_key, iv, aad, keys, salts=None, first_segment=0, count=None, zk_seed=None, h_in=None, digest_prefix=0):
+    """proofs [first_segment, first_segment + count) of one DIGEST record -> (ciphertext, tag, commitments, states, proofs): the WHOLE record's ciphertext
+    and tag, its nd commitments (one behind every data segment), its nd + 1 states and the call's proofs, of the record's nd + 1 (the last is the closing tail).
+    keys = (head, mid or None, last, tail) proving keys of synthesize_keys_gcm_segment(..., digest=True); count None = to the record's end; salts = nd strings of 16
+    bytes or None for os.urandom (a job split over calls passes them); zk_seed as encrypt_batch, proof s drawing at index s whichever call makes it, so a split job is
+    byte-identical to the whole one.  h_in: states[0], None = SHA-256's initial value; digest_prefix: the bytes hashed into h_in ahead of the record, a multiple of 64.
+    states[-1] is the SHA-256 digest of prefix || message: hashlib.sha256(message).digest() with the defaults"""
+    head, mid, last, tail = keys
+    _gcm_args(secret_key, iv, head.key_bytes())
+    info = head.segment_info()
+    if info is None:
+        raise ZkAesError("the head key is not a GCM segment key: the segment _digest_ entry points take keys of synthesize_keys_gcm_segment(..., digest=True)")
+    if h_in is not None and len(h_in) != 32:
+        raise ZkAesError("h_in must be 32 bytes")
+    c = info["blocks"]
+    if not info.get("digest"):
+        raise ZkAesError("the head key is a plain segment key: encrypt_gcm_segments_digest takes keys of synthesize_keys_gcm_segment(..., digest=True) (this one goes through encrypt_gcm_segments)")
+    plan = gcm_segment_plan(len(message), len(aad), c, digest=True)
+    n, nd = plan["n"], plan["nd"]
+    if count is None:
+        count = n - first_segment
+    if salts is None:
+        salts = [os.urandom(16) for _ in range(nd)]
+    if len(salts) != nd or any(len(x) != 16 for x in salts):
+        raise ZkAesError("salts: one 16-byte salt behind every data segment, %d for this record" % nd)
+    if zk_seed is None:
+        zk_seed = os.urandom(32)
+    seed = ProvingKey._seed_arg(zk_seed)
+    ct, tag, coms, st = C.create_string_buffer(len(message)), C.create_string_buffer(16), C.create_string_buffer(32 * nd), C.create_string_buffer(32 * (nd + 1))
+    lens = (C.c_size_t * max(count, 1))()
+    out, total = C.c_void_p(), C.c_size_t()
+    _check(lib().zkaes_encrypt_gcm_segments_digest_seeded_at(bytes(message), C.c_size_t(len(message)), bytes(secret_key), bytes(iv), bytes(aad), C.c_size_t(len(aad)), head._p,
+                                                             None if mid is None else mid._p, last._p, tail._p, b"".join(bytes(x) for x in salts), None if h_in is None else bytes(h_in),
+                                                             C.c_uint64(digest_prefix), seed, C.c_size_t(first_segment), C.c_size_t(count), ct, tag, coms, st, C.byref(out), C.byref(total), lens))
+    return (ct.raw[:len(message)], tag.raw, [coms.raw[32 * s:32 * s + 32] for s in range(nd)], [st.raw[32 * s:32 * s + 32] for s in range(nd + 1)],
+            _split(_take(out, total), lens, count))
+
+
+def _gcm_digest_args(iv, tag, commitments, states):
+    if len(iv) != 12:
+        raise ZkAesError("GCM: only 96-bit (12-byte) IVs are supported")
+    if len(tag) != 16:
+        raise ZkAesError("GCM: only full 16-byte tags are supported")
+    if any(len(x) != 32 for x in commitments) or any(len(x) != 32 for x in states):
+        raise ZkAesError("a commitment and a state are 32 bytes each")
+    return b"".join(bytes(x) for x in commitments), b"".join(bytes(x) for x in states)
+
+
+def verify_gcm_segments_digest(vks, proofs, iv, aad, ciphertext, tag, commitments, c, states, digest_prefix=0):
+    """the nd + 1 proofs of one DIGEST record against ONE list of nd commitments and ONE list of nd + 1 states -> a list of nd + 1 bools.  vks = (head,
+    mid or None, last, tail) verifying keys; c = the data blocks per segment.  The verifier sets every ctr0 = 2 + s c, cuts the ciphertext, sets total_bits =
+    8 (digest_prefix + len(ciphertext)), builds the length block from the lengths it sees and hands the tag to the closing tail alone; data segment s is checked under
+    (states[s], states[s + 1]).  Accepted throughout, the record's plaintext has the SHA-256 digest states[-1] when hashed from states[0] behind digest_prefix bytes:
+    the caller compares states[0] with the state it started from (sha256_chain(b"") is the initial value) and states[-1] with the digest it expects.  Lengths that do
+    not fit the keys, the proof count, the commitment count or the state count raise; a proof that does not parse is a rejected segment"""
+    coms, st = _gcm_digest_args(iv, tag, commitments, states)
+    head, mid, last, tail = vks
+    n = len(proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    each, ok = (C.c_int * max(n, 1))(), C.c_size_t()
+    _check(lib().zkaes_verify_gcm_segments_digest(head._p, None if mid is None else mid._p, last._p, tail._p, b"".join(bytes(p) for p in proofs), lens, C.c_size_t(n), C.c_size_t(c), bytes(iv),
+                                                  bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), st,
+                                                  C.c_size_t(len(st)), C.c_uint64(digest_prefix), each, C.byref(ok)))
+    return [bool(each[i]) for i in range(n)]
+
+
+def gcm_segment_digest_public_inputs(n_proofs, iv, aad, ciphertext, tag, commitments, c, states, digest_prefix=0):
+    """the public-input rows of a DIGEST record -> (key_of, rows): per proof the index of its key in (head, mid, last, tail) -- 0, 1, 2 or 3 -- and one bytes object of
+    0/1, exactly what verify_gcm_segments_digest checks it against (zkaes_gcm_segment_digest_public_inputs; no GPU).  With them the record's nd + 1 proofs go through
+    verify_batch_keys([head, mid, last, tail], key_of, proofs, rows) in one pairing check; a record without a mid (nd = 2) passes its three keys and
+    [k if k == 0 else k - 1 for k in key_of]"""
+    coms, st = _gcm_digest_args(iv, tag, commitments, states)
+    n = int(n_proofs)
+    lens, roles = (C.c_size_t * max(n, 1))(), (C.c_int * max(n, 1))()
+    args = (C.c_size_t(n), C.c_size_t(c), bytes(iv), bytes(aad), C.c_size_t(len(aad)), bytes(ciphertext), C.c_size_t(len(ciphertext)), bytes(tag), coms, C.c_size_t(len(coms)), st,
+            C.c_size_t(len(st)), C.c_uint64(digest_prefix))
+    _check(lib().zkaes_gcm_segment_digest_public_inputs(*args, None, lens, roles))
+    out = C.create_string_buffer(max(1, sum(lens[s] for s in range(n))))
+    _check(lib().zkaes_gcm_segment_digest_public_inputs(*args, out, lens, roles))
+    rows, off = [], 0
+    for s in range(n):
+        rows.append(out.raw[off:off + lens[s]])
+        off += lens[s]
+    return [{SEG_HEAD: 0, SEG_MID: 1, SEG_LAST: 2, SEG_TAIL: 3}[roles[s]] for s in range(n)], rows
 
 
 def _seg_key_tag(key_tag):

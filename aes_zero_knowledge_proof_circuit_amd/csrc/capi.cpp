@@ -364,6 +364,47 @@ int zkaes_encrypt_gcm_segments_reveal_seeded_at(const uint8_t *msg, size_t len, 
                                            zk_seed32, ciphertext_or_null, tag_or_null, commitments_or_null, mask, revealed_or_null), proofs, proofs_len, proof_lens);
     });
 }
+// -- digests on segments: keys of a digest record -- head, mid, last (role 3), the closing tail (role 2, units 0) -- and their proving entries; the
+// entries above refuse such keys (zkaes_aes_witness_gcm_seg takes them with their longer header), and these refuse every other key
+int zkaes_synthesize_keys_gcm_seg_dg(int role, unsigned key_bits, size_t units, size_t aad_len, size_t nc, size_t nv, size_t nnz, unsigned flags, zkaes_pk **pk, zkaes_vk **vk) {
+    return guard([&] {
+        const unsigned f = key_flags(flags);
+        give_keys(zk::synthesize_keys_gcm_segment(role, units, aad_len, key_bits, srs_literals(nc, nv, nnz), f, 0, 0, 1), pk, vk);
+    });
+}
+int zkaes_pk_segment_digest(const zkaes_pk *pk, int *digest, size_t *header_bytes) {
+    return guard([&] {
+        if (!pk) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (digest) *digest = c.kind == zk::CIRCUIT_AES_GCM_SEG ? c.seg_digest : 0;
+        if (header_bytes) *header_bytes = c.kind == zk::CIRCUIT_AES_GCM_SEG ? zk::segment_header_bytes(c) : 0;
+    });
+}
+int zkaes_encrypt_gcm_segment_digest_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers,
+                                                     size_t headers_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs, size_t *proofs_len,
+                                                     size_t *proof_lens) {
+    return guard([&] {
+        if (!pk || !proofs || !proofs_len) throw std::invalid_argument("null argument");
+        const zk::Circuit &c = pk->pk->circuit();
+        if (c.kind != zk::CIRCUIT_AES_GCM_SEG) throw std::invalid_argument("the key is not a GCM segment key: the segment _digest_ entry points take keys of zkaes_synthesize_keys_gcm_seg_dg (other digest keys go through zkaes_encrypt_digest_batch_seeded_at)");
+        if (!c.seg_digest) throw std::invalid_argument("the key is a plain segment key: the segment _digest_ entry points take keys of zkaes_synthesize_keys_gcm_seg_dg (this one goes through zkaes_encrypt_gcm_segment_batch_seeded_at)");
+        const size_t hb = zk::segment_header_bytes(c);
+        require_packed(c, n, messages_len, secret_keys_len);
+        if (headers_len != n * hb) throw std::invalid_argument("headers must hold n x " + std::to_string(hb) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad, then H_in, then a last's be64(total_bits) padded to 16)");
+        pack_proofs(pk->pk->prove_gcm_segment_digest_batch(messages, secret_keys, headers, n, pk->pk->contexts(), zk_seed32, first_proof_index), proofs, proofs_len, proof_lens);
+    });
+}
+int zkaes_encrypt_gcm_segments_digest_seeded_at(const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const zkaes_pk *head,
+                                                const zkaes_pk *mid_or_null, const zkaes_pk *last, const zkaes_pk *tail, const uint8_t *salts_or_null, const uint8_t *h_in_or_null,
+                                                uint64_t digest_prefix, const uint8_t *zk_seed32, size_t first_segment, size_t count, uint8_t *ciphertext_or_null, uint8_t *tag_or_null,
+                                                uint8_t *commitments_or_null, uint8_t *states_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens) {
+    return guard([&] {
+        if (!head || !last || !tail || !proofs || !proofs_len) throw std::invalid_argument("null argument");
+        pack_proofs(zk::prove_gcm_segments_digest(head->pk.get(), mid_or_null ? mid_or_null->pk.get() : nullptr, last->pk.get(), tail->pk.get(), msg, len, key, iv, aad, aad_len, salts_or_null,
+                                                  h_in_or_null, digest_prefix, first_segment, count, zk_seed32, ciphertext_or_null, tag_or_null, commitments_or_null, states_or_null),
+                    proofs, proofs_len, proof_lens);
+    });
+}
 // -- plaintext digests: every mode through one set of entries; hdr = the mode's public header, NULL for ECB
 int zkaes_aes_witness_pd(const zkaes_pk *pk, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *hdr, const uint8_t *h_in, uint8_t *z, size_t z_cap, size_t *z_len) {
     return guard([&] {

@@ -96,7 +96,12 @@ SegShape gcm_segments_shape(const char *entry, bool with_keys, const zkaes_vk *h
         if (vk.num_public_inputs == bits + (reveal ? 0 : rv_bits))
             throw std::invalid_argument(std::string("GCM segments: the ") + name + (reveal ? " key has no reveal region: zkaes_verify_gcm_segments_reveal takes keys synthesized with reveal = 1 (zkaes_verify_gcm_segments checks this one)"
                                                                                            : " key reveals plaintext bytes: its proofs are checked with zkaes_verify_gcm_segments_reveal"));
-        if (vk.num_public_inputs != bits + (reveal ? rv_bits : 0)) throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths");
+        // (a verifying key carries its public-input count and no digest flag: a count 512 or 576 bits over is what a segment key of a digest record has, and also what a
+        // plain key for other lengths can have, so the message names both)
+        const bool dg_count = !reveal && (vk.num_public_inputs == bits + 512 || vk.num_public_inputs == bits + 576);
+        if (vk.num_public_inputs != bits + (reveal ? rv_bits : 0))
+            throw std::invalid_argument(std::string("GCM segments: the ") + name + " key was not synthesized for this segment's lengths" +
+                                        (dg_count ? " (its count fits a segment key of a digest record: those proofs are checked with zkaes_verify_gcm_segments_digest)" : ""));
     };
     if (with_keys) {
         exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 16 * c, "head", 8 * key_tag_len, true);
@@ -145,6 +150,51 @@ void gcm_segment_rows(const SegShape &S, size_t c, const uint8_t iv[12], const u
         if (pub.size() != lens[s]) throw std::logic_error("GCM segments: a segment's public input has not the documented length");
         for (const zk::Fr &v : pub) bits->push_back(v.is_zero() ? 0 : 1);
     }
+}
+// ---- digests on segmented records: nd data segments (head, mids, last) and the closing tail, nd + 1 proofs.  What the verifier and
+// zkaes_gcm_segment_digest_public_inputs check before any proof is looked at, and proof s's public input
+struct DgShape { size_t nd, lr; uint8_t lenblk[16], bits[8]; };
+DgShape gcm_digest_shape(const char *entry, bool with_keys, const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *last, const zkaes_vk *tail, size_t n_proofs, size_t c,
+                         const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments, size_t commitments_len,
+                         const uint8_t *states, size_t states_len, uint64_t digest_prefix) {
+    if ((with_keys && (!head || !last || !tail)) || !iv || !ct || !tag || !commitments || !states || (aad_len && !aad)) throw std::invalid_argument("null argument");
+    if (ct_len == 0 || ct_len > ((size_t)1 << 20) || aad_len > ((size_t)1 << 16)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes and at most 65536 bytes of aad");
+    if (c == 0 || c % 4) throw std::invalid_argument(std::string(entry) + ": a digest segment holds whole 64-byte blocks: c must be a multiple of 4");
+    if (ct_len <= 16 * c) throw std::invalid_argument(std::string(entry) + ": this record fits one segment; a record that fits one proof is checked with zkaes_verify_encryption_gcm_digest");
+    if (digest_prefix % 64 || digest_prefix >= ((uint64_t)1 << 61) - ct_len) throw std::invalid_argument(std::string(entry) + ": digest_prefix must be a multiple of 64 with digest_prefix + the record's length below 2^61");
+    DgShape S;
+    S.nd = (ct_len + 16 * c - 1) / (16 * c); S.lr = ct_len - 16 * c * (S.nd - 1);
+    if (n_proofs != S.nd + 1) throw std::invalid_argument(std::string(entry) + ": the record has " + std::to_string(S.nd) + " data segments of " + std::to_string(c) + " blocks and the closing tail: " + std::to_string(S.nd + 1) + " proofs");
+    if (commitments_len != 32 * S.nd) throw std::invalid_argument(std::string(entry) + ": one 32-byte commitment behind every data segment, " + std::to_string(32 * S.nd) + " bytes for this record");
+    if (states_len != 32 * (S.nd + 1)) throw std::invalid_argument(std::string(entry) + ": one 32-byte state per data segment and one more, " + std::to_string(32 * (S.nd + 1)) + " bytes for this record");
+    if (with_keys && S.nd > 2 && !mid_or_null) throw std::invalid_argument(std::string(entry) + ": a record of more than two data segments needs the mid key");
+    // a key that knows its exact public-input count pins the lengths, and tells a digest segment key from a plain one, whose count lacks the states' bits
+    auto exact = [&](const zk::VerifyingKey &vk, size_t plain_bits, size_t dg_bits, const char *name) {
+        if (vk.num_public_inputs + 1 == vk.num_instance) return;
+        if (dg_bits && vk.num_public_inputs == plain_bits)
+            throw std::invalid_argument(std::string(entry) + ": the " + name + " key is a plain segment key: its proofs are checked with zkaes_verify_gcm_segments (digest segment keys come from zkaes_synthesize_keys_gcm_seg_dg)");
+        if (vk.num_public_inputs != plain_bits + dg_bits) throw std::invalid_argument(std::string(entry) + ": the " + name + " key was not synthesized for this segment's lengths");
+    };
+    if (with_keys) {
+        exact(head->vk, 128 + 8 * aad_len + 128 * c + 256, 512, "head");
+        if (S.nd > 2) exact(mid_or_null->vk, 128 + 128 * c + 512, 512, "mid");
+        exact(last->vk, 128 + 8 * S.lr + 512, 512 + 64, "last");
+        exact(tail->vk, 128 + 128 + 128 + 256, 0, "tail");
+    }
+    const uint64_t total_bits = 8 * (digest_prefix + (uint64_t)ct_len);
+    for (int i = 0; i < 8; i++) { S.lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); S.lenblk[8 + i] = (uint8_t)((uint64_t)(8 * ct_len) >> (56 - 8 * i)); S.bits[i] = (uint8_t)(total_bits >> (56 - 8 * i)); }
+    return S;
+}
+std::vector<zk::Fr> gcm_digest_public_input(size_t s, const DgShape &S, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, const uint8_t tag[16],
+                                            const uint8_t *commitments, const uint8_t *states) {
+    uint8_t hd[16];
+    memcpy(hd, iv, 12);
+    const uint32_t ctr0 = (uint32_t)(2 + s * c);
+    for (int i = 0; i < 4; i++) hd[12 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
+    const bool first = s == 0, data = s < S.nd, fin = s + 1 == S.nd;
+    return zk::public_input_of({{hd, 16}, {first ? aad : nullptr, aad_len}, {data ? ct + 16 * c * s : nullptr, fin ? S.lr : 16 * c}, {data ? nullptr : S.lenblk, 16}, {data ? nullptr : tag, 16},
+                                {first ? nullptr : commitments + 32 * (s - 1), 32}, {data ? commitments + 32 * s : nullptr, 32}, {data ? states + 32 * s : nullptr, 64},
+                                {fin ? S.bits : nullptr, 8}});
 }
 // ---- VK transport, library-private layout v2: "ZVK2", num_public_inputs (u64 LE), then the ark-serialize compressed image (marlin_codec.cpp).  Round 5's v1 was a memory
 // image of the struct: reading it back from untrusted bytes put arbitrary limbs into field elements and an arbitrary byte into a bool, and skipped the curve / subgroup
@@ -646,9 +696,9 @@ int zkaes_circuit_matrix_gcm(size_t len, size_t aad_len, int which, uint64_t *n_
 }
 // (this query also fills out[9 .. 11]: the non-zeros of the joint matrix -- the positions where A, B or C has an entry, as the indexer merges them -- and |H|, |K|, so
 // that a caller can size a record's segments against an SRS without a device)
-static int circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, unsigned key_tag_blocks, uint64_t out[12]) {
+static int circuit_info_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, unsigned key_tag_blocks, uint64_t out[12], int digest = 0) {
     return guard([&] {
-        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal, key_tag_blocks);
+        const zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal, key_tag_blocks, digest);
         fill_info(c, out);
         uint64_t joint = 0;
         for (size_t r = 0; r < c.num_constraints; r++) {
@@ -674,6 +724,7 @@ int zkaes_circuit_info_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal, 
 int zkaes_circuit_info_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_len, uint64_t out[12]) {
     return circuit_info_gcm_seg(role, key_bits, units, aad_len, reveal, key_tag_blocks, out);
 }
+int zkaes_circuit_info_gcm_seg_dg(int role, unsigned key_bits, size_t units, size_t aad_len, uint64_t out[12]) { return circuit_info_gcm_seg(role, key_bits, units, aad_len, 0, 0, out, 1); }
 // ---- batch verification (include/zkaes.h): the host back end; zkaes_verify_batch_gpu and the kernel probes are in capi.cpp
 int zkaes_verify_batch(const zkaes_vk *vk, const uint8_t *proofs, const size_t *proof_lens, size_t n, const uint8_t *public_input_bits, size_t n_bits, int *accepted_each, size_t *n_accepted) {
     return guard([&] {
@@ -745,9 +796,9 @@ int zkaes_chunk_public_inputs_rv(int circuit_kind, size_t n_chunks, const uint8_
     return chunk_public_inputs("chunk_public_inputs_rv", circuit_kind, n_chunks, iv_or_icb, ct, ct_len, key_tag, key_tag_len, states, mask, revealed, out_bits, n_bits);
 }
 static int circuit_matrix_gcm_seg(int role, unsigned key_bits, size_t units, size_t aad_len, unsigned reveal, unsigned key_tag_blocks, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr,
-                                  uint32_t *col, int64_t *coeff) {
+                                  uint32_t *col, int64_t *coeff, int digest = 0) {
     return guard([&] {
-        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal, key_tag_blocks);
+        zk::Circuit c = zk::compile_aes_gcm_segment_circuit(role, units, aad_len, key_bits, reveal > 1 ? 2 : (int)reveal, key_tag_blocks, digest);
         const zk::CsrMatrix &m = which == 0 ? c.A : which == 1 ? c.B : c.C;
         if (n_rows) *n_rows = m.rows();
         if (nnz) *nnz = m.nnz();
@@ -766,6 +817,58 @@ int zkaes_circuit_matrix_gcm_seg_rv(int role, unsigned key_bits, unsigned reveal
 int zkaes_circuit_matrix_gcm_seg_kt(int role, unsigned key_bits, unsigned reveal, unsigned key_tag_blocks, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr,
                                     uint32_t *col, int64_t *coeff) {
     return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, reveal, key_tag_blocks, which, n_rows, nnz, rowptr, col, coeff);
+}
+int zkaes_circuit_matrix_gcm_seg_dg(int role, unsigned key_bits, size_t units, size_t aad_len, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff) {
+    return circuit_matrix_gcm_seg(role, key_bits, units, aad_len, 0, 0, which, n_rows, nnz, rowptr, col, coeff, 1);
+}
+// ---- digests on segmented records (include/zkaes.h): the record helper, the rows and the verifier of a digest record's nd + 1 proofs
+int zkaes_gcm_digest_plan(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, const uint8_t *h_in_or_null,
+                          uint64_t digest_prefix, uint8_t *ys, size_t ys_cap, uint8_t *states, size_t states_cap, size_t *n_data_segments) {
+    return guard([&] {
+        if (!msg || !key || !iv || (aad_len && !aad)) throw std::invalid_argument("null argument");
+        require_key_len(key_len);
+        if (len == 0 || len > ((size_t)1 << 20)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes");
+        if (c == 0 || c % 4) throw std::invalid_argument("GCM digest segments: a digest segment holds whole 64-byte blocks: c must be a multiple of 4");
+        if (len <= 16 * c) throw std::invalid_argument("GCM digest segments: this record fits one segment; a record that fits one proof takes a lone GCM key with a final digest (zkaes_synthesize_keys_pd)");
+        if (digest_prefix % 64 || digest_prefix >= ((uint64_t)1 << 61) - len) throw std::invalid_argument("zkaes_gcm_digest_plan: digest_prefix must be a multiple of 64 with digest_prefix + the record's length below 2^61");
+        const size_t nd = (len + 16 * c - 1) / (16 * c);
+        if (n_data_segments) *n_data_segments = nd;
+        if (!ys && !states) return;
+        if (!ys || !states || ys_cap < 16 * nd || states_cap < 32 * (nd + 1)) throw std::invalid_argument("gcm_digest_plan: ys takes 16 bytes per data segment and states 32 bytes per data segment and 32 more");
+        zk::gcm_digest_plan_host(msg, len, key, key_len, iv, aad, aad_len, c, h_in_or_null, digest_prefix, ys, states);
+    });
+}
+int zkaes_gcm_segment_digest_public_inputs(size_t n_proofs, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16],
+                                           const uint8_t *commitments, size_t commitments_len, const uint8_t *states, size_t states_len, uint64_t digest_prefix, uint8_t *out_bits,
+                                           size_t *n_bits_each, int *roles) {
+    return guard([&] {
+        const DgShape S = gcm_digest_shape("gcm_segment_digest_public_inputs", false, nullptr, nullptr, nullptr, nullptr, n_proofs, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len,
+                                           states, states_len, digest_prefix);
+        for (size_t s = 0; s <= S.nd; s++) {
+            const std::vector<zk::Fr> pub = gcm_digest_public_input(s, S, c, iv, aad, aad_len, ct, tag, commitments, states);
+            if (n_bits_each) n_bits_each[s] = pub.size();
+            if (roles) roles[s] = s == 0 ? 0 : s < S.nd - 1 ? 1 : s == S.nd - 1 ? 3 : 2;
+            if (out_bits) for (const zk::Fr &v : pub) *out_bits++ = v.is_zero() ? 0 : 1;
+        }
+    });
+}
+// Proof s < nd is checked against (iv, ctr0 = 2 + s c, its slice of the ciphertext), the aad (head), commitments[s - 1] (mid, last) and commitments[s], then
+// (states[s], states[s + 1]) and, for the last, total_bits = 8 (digest_prefix + ct_len) as the verifier computes it HERE; proof nd, the closing tail, against (iv,
+// ctr0 = 2 + nd c), the length block built from the lengths seen here, the tag and commitments[nd - 1].  ONE commitments array (nd) and ONE states array (nd + 1) serve
+// both sides of every boundary.  A proof that does not parse is a rejected segment
+int zkaes_verify_gcm_segments_digest(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *last, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens, size_t n_proofs,
+                                     size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16], const uint8_t *commitments,
+                                     size_t commitments_len, const uint8_t *states, size_t states_len, uint64_t digest_prefix, int *accepted_each, size_t *n_accepted) {
+    return guard([&] {
+        if (n_accepted) *n_accepted = 0;
+        if (accepted_each) for (size_t s = 0; s < n_proofs; s++) accepted_each[s] = 0;
+        if (!proofs || !proof_lens) throw std::invalid_argument("null argument");
+        const DgShape S = gcm_digest_shape("verify_gcm_segments_digest", true, head, mid_or_null, last, tail, n_proofs, c, iv, aad, aad_len, ct, ct_len, tag, commitments, commitments_len, states,
+                                           states_len, digest_prefix);
+        verify_each(proofs, proof_lens, S.nd + 1, accepted_each, n_accepted, [&](size_t s, const zk::Proof &p) {
+            return zk::verify(s == 0 ? head->vk : s < S.nd - 1 ? mid_or_null->vk : s == S.nd - 1 ? last->vk : tail->vk, gcm_digest_public_input(s, S, c, iv, aad, aad_len, ct, tag, commitments, states), p);
+        });
+    });
 }
 // ---- key tags on segmented records (include/zkaes.h): the rows and the verifiers of a record whose head carries a key tag.  mask = NULL: plain keys
 int zkaes_gcm_segment_public_inputs_kt(size_t n_segments, size_t c, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, const uint8_t *ct, size_t ct_len, const uint8_t tag[16],

@@ -449,7 +449,10 @@ struct Sha256Gates {
     // The whole digest part of a key, behind everything else it emits: 256 inputs H_in, the compressions over msg (and, for a final key, the padding constants), 256
     // inputs H_out equal to the last feed-forward.  Message word t of block j, bit i, is bit i % 8 of byte 64 j + 4 t + 3 - i / 8: a re-wiring of the message witnesses.
     // `bytes` = the trace length ahead of the region; returns the length with it
-    size_t digest(const std::vector<Byte> &msg, int kind, uint64_t prefix, size_t bytes) {
+    // bits_input (the last segment of a GCM digest record; final keys only): the padding's eight length bytes are INPUTS, the big-endian bit count of
+    // everything hashed, which the verifier sets; their trace bytes lie behind the region's slots (TRS_DG_BITS).  The 256 H_out inputs are then allocated ahead of them
+    // and of the compressions, so that the instance reads H_in, H_out, total_bits; their equalities stay where they were
+    size_t digest(const std::vector<Byte> &msg, int kind, uint64_t prefix, size_t bytes, bool bits_input = false) {
         const size_t len = msg.size(), nblk = TRD_BLOCKS(kind, len);
         const uint32_t dg = (uint32_t)TRD(bytes);
         std::vector<Byte> padded(msg);
@@ -459,8 +462,12 @@ struct Sha256Gates {
             const uint64_t bits = 8 * (prefix + (uint64_t)len);
             for (int i = 0; i < 8; i++) padded[64 * nblk - 8 + i] = Builder::const_byte((uint8_t)(bits >> (56 - 8 * i)));
         }
-        std::array<Byte, 32> hin;
+        std::array<Byte, 32> hin, hout;
         for (int j = 0; j < 32; j++) hin[j] = b.alloc_byte(true, dg + TRD_HIN + (uint32_t)j);
+        if (bits_input) {
+            for (int j = 0; j < 32; j++) hout[j] = b.alloc_byte(true, dg + TRD_HOUT + (uint32_t)j);
+            for (int i = 0; i < 8; i++) padded[64 * nblk - 8 + i] = b.alloc_byte(true, dg + (uint32_t)TRS_DG_BITS(nblk) + (uint32_t)i);
+        }
         std::array<Word, 8> st;
         for (int k = 0; k < 8; k++) st[k] = be_word(&hin[4 * k]);
         for (size_t j = 0; j < nblk; j++) {
@@ -469,10 +476,10 @@ struct Sha256Gates {
             st = compress(st, block, dg + TRD_SLOT0 + (uint32_t)(j * TRD_SLOT_STRIDE));
         }
         for (int j = 0; j < 32; j++) {
-            Byte pi = b.alloc_byte(true, dg + TRD_HOUT + (uint32_t)j);
+            Byte pi = bits_input ? hout[j] : b.alloc_byte(true, dg + TRD_HOUT + (uint32_t)j);
             for (int k = 0; k < 8; k++) b.enforce_equal(pi[k], st[j / 4][8 * (3 - j % 4) + k]);
         }
-        return TRD_BYTES(bytes, kind, nblk);
+        return TRD_BYTES(bytes, kind, nblk) + (bits_input ? 16 : 0);
     }
 };
 
@@ -749,18 +756,34 @@ Circuit compile_aes_gcm_circuit(size_t len, size_t alen, size_t key_bits, size_t
 // length-block INPUTS; (tail) the tag's xor gates and inputs; last com_in (mid, tail), then com_out (head, mid): 256 inputs each, one compression from the constant
 // initial value over key || zeros || Y || salt, 256 equalities.  A head with key_tag_blocks = T then has the T tag blocks of key_tag() and their 128 T
 // inputs.  With reveal = 1 the mask and revealed inputs and their rows (reveal() above) come last of all.
-Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits, int rv, size_t key_tag_blocks) {
+// With digest = 1 a head or mid ends in 9f's chain digest over its 16 c bytes, the new role "last" (a mid of `units` = Lr BYTES, the final block cut and
+// zero-padded for GHASH as a tail's) in a final digest whose length field is the eight total_bits INPUTS, and the tail is the data-less closing tail: units = 0, no
+// message, the H slot and the J_0 slot, ONE multiplication over X = Y_in ^ the length block, the tag, com_in.  The digest region's inputs -- H_in, H_out, (last)
+// total_bits -- come last of all.
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, size_t key_bits, int rv, size_t key_tag_blocks, int digest) {
     require_key_bits(key_bits);
     require_reveal(rv);
     require_key_tag_blocks(key_tag_blocks);
-    if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw std::invalid_argument("GCM segment: the role must be 0 (head), 1 (mid) or 2 (tail)");
+    if (digest != 0 && digest != 1) throw std::invalid_argument("GCM segment: digest must be 0 or 1");
+    if (!digest) {
+        if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL)
+            throw std::invalid_argument("GCM segment: the role must be 0 (head), 1 (mid) or 2 (tail); 3 (last) belongs to a digest record: use the _gcm_seg_dg entries (zkaes_synthesize_keys_gcm_seg_dg)");
+    } else {
+        if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL && role != TRS_LAST) throw std::invalid_argument("GCM digest segment: the role must be 0 (head), 1 (mid), 2 (tail) or 3 (last)");
+        if (rv) throw std::invalid_argument("GCM digest segment: a digest segment key has no reveal form: use a reveal segment key without a digest (zkaes_synthesize_keys_gcm_seg_rv), or a lone GCM key with digest and reveal for a record of one proof");
+        if (key_tag_blocks) throw std::invalid_argument("GCM digest segment: a digest segment key takes no key_tag_blocks (a tagged digest head does not fit the default SRS): use a tagged head without a digest (zkaes_synthesize_keys_gcm_seg_kt)");
+        if ((role == TRS_HEAD || role == TRS_MID) && (16 * units) % 64)
+            throw std::invalid_argument("GCM digest segment: SHA-256 absorbs 64 bytes at a time, so a digest head or mid holds whole 64-byte blocks: use c, the data blocks per segment, a multiple of 4");
+        if (role == TRS_TAIL && units) throw std::invalid_argument("GCM digest segment: the tail of a digest record holds no data: use units = 0 for it, and role 3 (last) with units = the last data bytes for the segment ahead of it");
+    }
     if (role != TRS_HEAD && key_tag_blocks)
         throw std::invalid_argument("GCM segment: only the head segment takes key_tag_blocks: the head carries the record's key tag and the boundary commitments carry the key to every later segment");
-    if (units == 0) throw std::invalid_argument("GCM segment: a head or mid has at least one data block, a tail at least one byte");
+    const bool begins = role == TRS_HEAD, ends = role == TRS_TAIL, bytes_role = ends || role == TRS_LAST;
+    if (units == 0 && !(digest && ends))
+        throw std::invalid_argument("GCM segment: a head or mid has at least one data block, a tail at least one byte (a tail of 0 bytes is the closing tail of a digest record: the _gcm_seg_dg entries)");
     if (role != TRS_HEAD && alen) throw std::invalid_argument("GCM segment: only the head segment takes the aad");
     if (units > (1u << 16) || alen > (1u << 16)) throw std::invalid_argument("GCM segment: message and aad of one proof are limited to 65536 bytes each");
-    const bool begins = role == TRS_HEAD, ends = role == TRS_TAIL;
-    const size_t len = ends ? units : 16 * units, nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TRS_MULS(role, na, nb);
+    const size_t len = bytes_role ? units : 16 * units, nb = (len + 15) / 16, na = (alen + 15) / 16, n_mul = TRS_MULS(role, na, nb);
     const int nk = (int)(key_bits / 32);
     const uint32_t gcm = (uint32_t)TRS_GCM(nk, role, nb), sg = gcm + (uint32_t)TRS_SEG(role, na, nb);
     Builder b;
@@ -856,10 +879,16 @@ Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t alen, siz
     const size_t seg_bytes = TRS_BYTES(nk, role, na, nb);
     size_t trace_bytes = g.key_tag(key_tag_blocks, seg_bytes);
     // ---- selective disclosure: the segment's slice of the record's mask and revealed bytes, behind the commitments as finish_aes puts them behind the digest
+    // ---- the digest of a digest record's data segment: 9f's region behind the segment region and its compression slots, as finish_aes puts it behind a
+    // mode's tail (a digest key has neither tag blocks nor reveal, so nothing lies between or behind)
+    const int digest_kind = digest ? TRS_DG_KIND(role) : DIGEST_NONE;
+    const size_t digest_off = digest_kind ? TRD(trace_bytes) : 0;
+    if (digest_kind) trace_bytes = sha.digest(msg, digest_kind, 0, trace_bytes, role == TRS_LAST);
     const size_t reveal_off = rv ? TRV(trace_bytes) : 0;
     if (rv) trace_bytes = reveal(b, msg, trace_bytes);
     Circuit c = finish(b, CIRCUIT_AES_GCM_SEG, nb, trace_bytes, g.key_bytes());
-    c.message_bytes = len; c.aad_bytes = alen; c.seg_role = role; c.seg_off = sg;
+    c.message_bytes = len; c.aad_bytes = alen; c.seg_role = role; c.seg_off = sg; c.seg_digest = digest;
+    c.digest_kind = digest_kind; c.digest_blocks = TRD_BLOCKS(digest_kind, len); c.digest_off = digest_off;
     c.key_tag_blocks = key_tag_blocks; c.key_tag_off = key_tag_blocks ? TRK_KT(seg_bytes) : 0;
     c.reveal = rv; c.reveal_off = reveal_off;
     return c;
@@ -1128,6 +1157,36 @@ size_t reveal_mask_bytes(const Circuit &c) { return c.reveal ? TRV_MASK_BYTES(c.
 
 size_t mode_header_bytes(const Circuit &c) {
     return c.kind == CIRCUIT_AES_GCM_SEG ? TRS_HDR_BYTES(c.aad_bytes) : c.kind == CIRCUIT_AES_GCM ? 12 + c.aad_bytes : (c.kind == CIRCUIT_AES_CBC || c.kind == CIRCUIT_AES_CTR) ? 16 : 0;
+}
+
+size_t segment_header_bytes(const Circuit &c) { return TRS_HDR_DG_BYTES(c.aad_bytes, c.digest_kind) + reveal_mask_bytes(c); }
+
+void gcm_digest_plan_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, const uint8_t *h_in, uint64_t prefix,
+                          uint8_t *ys, uint8_t *states) {
+    if (c == 0 || (16 * c) % 64) throw std::invalid_argument("gcm_digest_plan: a digest segment holds whole 64-byte blocks: c must be a multiple of 4");
+    if (len <= 16 * c) throw std::invalid_argument("gcm_digest_plan: this record fits one segment; a record that fits one proof takes a lone GCM key with a final digest (zkaes_synthesize_keys_pd)");
+    const size_t nd = (len + 16 * c - 1) / (16 * c);
+    // the accumulators behind every data segment but the last are the plain plan's; the one behind the last data block, ahead of the length block, is the chain's end
+    gcm_boundaries_host(msg, len, key, key_len, iv, aad, aad_len, c, ys);
+    {
+        std::vector<uint8_t> ct(len);
+        uint8_t tag[16], hb[16] = {0}, blk[16];
+        aes128_gcm_encrypt_host(msg, len, key, iv, aad, aad_len, ct.data(), tag, key_len);
+        HostAes128 aes(key, key_len);
+        aes.encrypt_block(hb);
+        const Gf128 h = gf_load(hb);
+        Gf128 y = nd > 1 ? gf_load(ys + 16 * (nd - 2)) : Gf128();
+        for (size_t off = 16 * c * (nd - 1); off < len; off += 16) {
+            for (size_t i = 0; i < 16; i++) blk[i] = off + i < len ? ct[off + i] : 0;
+            Gf128 x = gf_load(blk);
+            x.hi ^= y.hi; x.lo ^= y.lo;
+            y = gf_mul(x, h);
+        }
+        for (int i = 0; i < 8; i++) { ys[16 * (nd - 1) + i] = (uint8_t)(y.hi >> (56 - 8 * i)); ys[16 * (nd - 1) + 8 + i] = (uint8_t)(y.lo >> (56 - 8 * i)); }
+    }
+    sha256_chain(h_in, nullptr, 0, states);                                        // states[0] = H_in, null being the initial value
+    for (size_t s = 0; s + 1 < nd; s++) sha256_chain(states + 32 * s, msg + 16 * c * s, 16 * c, states + 32 * (s + 1));
+    sha256_finish(states + 32 * (nd - 1), prefix + 16 * c * (nd - 1), msg + 16 * c * (nd - 1), len - 16 * c * (nd - 1), states + 32 * nd);
 }
 
 }  // namespace zk

@@ -49,6 +49,7 @@ struct Circuit {
     size_t reveal_off = 0;               // trace offset of the reveal region (trace_layout.h TRV), 0 when R = 0
     int seg_role = -1;                   // a GCM segment key (kind CIRCUIT_AES_GCM_SEG): 0 head, 1 mid, 2 tail (trace_layout.h TRS_*); -1 for every other key
     size_t seg_off = 0;                  // trace offset of the segment region (trace_layout.h TRS_SEG), 0 for every other key
+    int seg_digest = 0;                  // a segment key of a digest record: role 3 (last) exists, a tail is the data-less closing tail, and digest_kind is chain (head, mid), final (last) or none (tail)
     size_t num_variables() const { return num_instance + num_witness; }
 };
 
@@ -87,7 +88,13 @@ Circuit compile_aes_gcm_circuit(size_t message_len, size_t aad_len, size_t key_b
 // revealed bytes (len), len = 16 c for a head or mid and Lt for a tail, with the rows of the lone reveal form; reveal = 0 is the circuit as it was.
 // key_tag_blocks = T in 1, 2 (a HEAD only, since the commitments carry the key to every later segment) appends 9e's tag blocks: 128 T inputs behind
 // com_out and ahead of the reveal inputs, their slots at TRK_KT(TRS_BYTES(..)); T = 0 is the circuit as it was.  Anything out of range is std::invalid_argument
-Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128, int reveal = 0, size_t key_tag_blocks = 0);
+// digest = 1: a segment of a DIGEST record, which is nd data segments and one closing tail.  A head or mid (16 units a multiple of 64) appends 512 inputs
+// H_in, H_out: the chain digest over its 16 units bytes.  role 3, "last" (with the flag only): a mid whose units are Lr = 1 .. 65536 BYTES -- Y_in, com_in, com_out, no
+// tag, the final block zero-padded for GHASH -- which appends H_in, H_out and the 64 inputs total_bits (8 bytes, big-endian): the final digest over its Lr bytes with
+// the padding 0x80, zeros, total_bits in ceil((Lr + 9) / 64) compressions.  A tail takes units = 0 only: no data, no digest; iv, ctr0, the length block, the tag, com_in.
+// digest with reveal or key_tag_blocks, a head or mid whose 16 units is no multiple of 64, and a tail with units != 0 are std::invalid_argument; digest = 0 is the
+// circuit as it was, role 3 and a tail of 0 bytes refused
+Circuit compile_aes_gcm_segment_circuit(int role, size_t units, size_t aad_len = 0, size_t key_bits = 128, int reveal = 0, size_t key_tag_blocks = 0, int digest = 0);
 // kind = CIRCUIT_AES, CIRCUIT_AES_CBC, CIRCUIT_AES_CTR, CIRCUIT_AES_GCM, or an ops kind (message_len ignored); aad_len must be 0 for every kind but GCM, key_bits
 // 128, key_tag_blocks 0 and digest_kind 0 for the ops kinds
 Circuit compile_circuit(int kind, size_t message_len, size_t aad_len = 0, size_t key_bits = 128, size_t key_tag_blocks = 0, int digest_kind = 0, uint64_t digest_prefix = 0, int reveal = 0);
@@ -99,6 +106,9 @@ void sha256_finish(const uint8_t *h_in, uint64_t prefix_bytes, const uint8_t *ta
 // the bytes of the per-proof public header a key's mode takes ahead of a digest key's H_in: 0 (ECB), 16 (CBC, CTR), 12 + aad_bytes (GCM); for a GCM segment key the
 // 80 + aad_bytes of a segment header (trace_layout.h TRS_HDR_*), which also carries that proof's witnesses Y_in and the salts (a reveal segment key's mask follows it)
 size_t mode_header_bytes(const Circuit &c);
+// the whole per-proof header of a GCM segment key (trace_layout.h TRS_HDR_*): mode_header_bytes, then for a digest segment key H_in (32) and for a last be64(total_bits)
+// padded to 16, then a reveal key's mask
+size_t segment_header_bytes(const Circuit &c);
 // the ceil(message_bytes / 8) mask bytes a reveal key's per-proof header carries behind H_in, 0 for every other key
 size_t reveal_mask_bytes(const Circuit &c);
 // the key tag itself on the host: out = 16 tag_blocks bytes, AES_K(D_0) (|| AES_K(D_1)); key_len = 16, 24 or 32, tag_blocks = 1 or 2 (else std::invalid_argument)
@@ -122,5 +132,10 @@ void aes128_gcm_encrypt_host(const uint8_t *msg, size_t len, const uint8_t *key,
 // key || zeros to 32 bytes || y || salt
 void gcm_boundaries_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, uint8_t *ys);
 void gcm_commit_host(const uint8_t *key, size_t key_len, const uint8_t y[16], const uint8_t salt[16], uint8_t com[32]);
+// a DIGEST record's host side: nd = ceil(len / (16 c)) >= 2 data segments of c data blocks, c a multiple of 4.  ys = 16 nd bytes: the nd - 1 accumulators
+// of gcm_boundaries_host and, last, the one behind the record's last data block, ahead of the length block -- what enters the closing tail.  states = 32 (nd + 1) bytes:
+// states[0] = h_in (nullptr = the initial value), states[s + 1] = the chain over segment s, states[nd] = the real digest of prefix || msg, prefix a multiple of 64
+void gcm_digest_plan_host(const uint8_t *msg, size_t len, const uint8_t *key, size_t key_len, const uint8_t iv[12], const uint8_t *aad, size_t aad_len, size_t c, const uint8_t *h_in, uint64_t prefix,
+                          uint8_t *ys, uint8_t *states);
 
 }  // namespace zk

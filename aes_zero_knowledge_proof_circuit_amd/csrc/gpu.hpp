@@ -306,6 +306,10 @@ void reveal_trace(uint8_t *trace, size_t trace_stride, size_t reveal_off, const 
 void aes_trace_gcm_seg(uint8_t *trace, size_t trace_stride, const uint8_t *msgs, const uint8_t *keys, const uint8_t *hdrs, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, stream_t s,
                        size_t key_bytes = 16);
 void ghash_trace_seg(uint8_t *trace, size_t trace_stride, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, stream_t s, size_t key_bytes = 16);
+// the digest region of a digest record's data segment, behind commit_trace on the same stream: role 0, 1 (kind 1, chain) or 3 (kind 2, final); H_in and a
+// last's total_bits are read per proof from its header at TRS_HDR_HIN / TRS_HDR_BITS; hdr_stride >= TRS_HDR_DG_BYTES(aad_len, digest_kind)
+void sha256_trace_seg(uint8_t *trace, size_t trace_stride, size_t digest_off, const uint8_t *msgs, const uint8_t *hdrs, size_t hdr_stride, uint32_t nproofs, int role, size_t msg_len, size_t aad_len,
+                      int digest_kind, stream_t s);
 void commit_trace(uint8_t *trace, size_t trace_stride, size_t seg_off, size_t yout_off, const uint8_t *keys, size_t key_bytes, const uint8_t *hdrs, size_t hdr_stride, uint32_t nproofs, int role,
                   uint32_t nblocks, stream_t s);
 // z[col] (0/1 bytes) for every column, by descriptor

@@ -5,6 +5,8 @@
 //                    proof's public header, re-walks compressions 0 .. c - 1 in registers without a store -- the way a CBC lane re-walks its chain -- then runs
 //                    compression c and stores every word of its slot.  Lane c = 0 also stores H_in, the last lane H_out.  The kernel is handed message and H_in only, never
 //                    a state made on the host: the host's hash and the device's meet in the constraints.
+//   k_sha256_trace_seg   the digest region of a GCM segment of a digest record: k_sha256_trace's lanes, with H_in AND the padding's total_bits read per proof
+//                    from the proof's segment header -- a launch may hold the last segments of records of different lengths.
 //   k_commit_trace   the boundary commitments of a GCM segment: one lane per commitment, ONE compression from the initial value over key || zeros || Y ||
 //                    salt through the same sha_compress, into the segment region's slots.
 // Every byte of the region has exactly one writer and no byte ahead of it is touched; no LDS, no barrier, no cross-lane operation.  The 16-word schedule ring and the
@@ -85,15 +87,12 @@ __device__ __forceinline__ void sha_compress(uint32_t st[8], uint32_t w[16], uin
     }
 }
 
-// hdrs: nproofs x hdr_stride bytes, the proofs' public headers; a proof's H_in is the 32 bytes at hin_off of its header.  msgs: nproofs x msg_len bytes, packed.
-// dg_off: the digest region's offset in a trace (16-byte aligned, as are the traces: the slots are written with word stores)
-__global__ void k_sha256_trace(uint8_t *__restrict__ trace, size_t stride, size_t dg_off, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ hdrs, size_t hdr_stride, size_t hin_off,
-                               uint32_t nproofs, uint32_t nblk, uint32_t msg_len, uint32_t kind, uint64_t total_bits) {
-    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nproofs * nblk) return;
-    const uint32_t p = t / nblk, c = t % nblk;
-    const uint8_t *msg = msgs + (size_t)p * msg_len, *hin = hdrs + (size_t)p * hdr_stride + hin_off;
-    uint8_t *dg = trace + (size_t)p * stride + dg_off;
+// Lane (p, c) of either digest kernel, the proof's region at dg: H_in from the 32 bytes at hin, compressions 0 .. c - 1 re-walked in registers, compression c stored
+// into its slot; lane c = 0 also stores H_in, the last lane H_out and -- BITS: the region of a GCM digest record's last segment -- the 16 bytes be64(total_bits) ||
+// zeros behind the slots
+template <bool BITS>
+__device__ __forceinline__ void sha_trace_lane(uint8_t *__restrict__ dg, const uint8_t *__restrict__ msg, uint32_t msg_len, const uint8_t *__restrict__ hin, uint32_t kind, uint32_t nblk,
+                                               uint64_t total_bits, uint32_t c) {
     uint32_t st[8], w[16];
 #pragma unroll
     for (int k = 0; k < 8; k++) st[k] = (uint32_t)hin[4 * k] << 24 | (uint32_t)hin[4 * k + 1] << 16 | (uint32_t)hin[4 * k + 2] << 8 | (uint32_t)hin[4 * k + 3];
@@ -112,7 +111,41 @@ __global__ void k_sha256_trace(uint8_t *__restrict__ trace, size_t stride, size_
         uint32_t *o = reinterpret_cast<uint32_t *>(dg + TRD_HOUT);
 #pragma unroll
         for (int k = 0; k < 8; k++) o[k] = __builtin_bswap32(st[k]);
+        if (BITS) {
+            uint32_t *b = reinterpret_cast<uint32_t *>(dg + TRS_DG_BITS((size_t)nblk));
+            b[0] = __builtin_bswap32((uint32_t)(total_bits >> 32)); b[1] = __builtin_bswap32((uint32_t)total_bits); b[2] = 0; b[3] = 0;
+        }
     }
+}
+
+// hdrs: nproofs x hdr_stride bytes, the proofs' public headers; a proof's H_in is the 32 bytes at hin_off of its header.  msgs: nproofs x msg_len bytes, packed.
+// dg_off: the digest region's offset in a trace (16-byte aligned, as are the traces: the slots are written with word stores)
+__global__ void k_sha256_trace(uint8_t *__restrict__ trace, size_t stride, size_t dg_off, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ hdrs, size_t hdr_stride, size_t hin_off,
+                               uint32_t nproofs, uint32_t nblk, uint32_t msg_len, uint32_t kind, uint64_t total_bits) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nproofs * nblk) return;
+    const uint32_t p = t / nblk, c = t % nblk;
+    sha_trace_lane<false>(trace + (size_t)p * stride + dg_off, msgs + (size_t)p * msg_len, msg_len, hdrs + (size_t)p * hdr_stride + hin_off, kind, nblk, total_bits, c);
+}
+
+// The digest region of a digest record's data segment (trace_layout.h TRS_DG*), launched behind k_commit_trace on the same stream.  nproofs * nblk lanes in
+// k_sha256_trace's shape and with its lane body.  What differs: H_in is the 32 bytes at TRS_HDR_HIN(aad_len) of the proof's OWN header and, for a final region (kind 2,
+// a last), total_bits is the be64 at TRS_HDR_BITS(aad_len) of that header -- no kernel argument, since the proofs of one launch end records of different lengths -- and
+// the last lane stores those eight bytes and eight zero bytes behind the slots, where the circuit's length inputs point.  The kernel is handed message, H_in and
+// total_bits only, never a state made on the host.  One writer per byte, none ahead of the region; no LDS, no barrier, no cross-lane operation.
+__global__ void k_sha256_trace_seg(uint8_t *__restrict__ trace, size_t stride, size_t dg_off, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ hdrs, size_t hdr_stride, uint32_t aad_len,
+                                   uint32_t nproofs, uint32_t nblk, uint32_t msg_len, uint32_t kind) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nproofs * nblk) return;
+    const uint32_t p = t / nblk, c = t % nblk;
+    const uint8_t *hdr = hdrs + (size_t)p * hdr_stride;
+    uint8_t *dg = trace + (size_t)p * stride + dg_off;
+    const uint8_t *msg = msgs + (size_t)p * msg_len, *hin = hdr + TRS_HDR_HIN((size_t)aad_len);
+    if (kind != 2) { sha_trace_lane<false>(dg, msg, msg_len, hin, kind, nblk, 0, c); return; }
+    uint64_t total_bits = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) total_bits = (total_bits << 8) | hdr[TRS_HDR_BITS((size_t)aad_len) + i];
+    sha_trace_lane<true>(dg, msg, msg_len, hin, kind, nblk, total_bits, c);
 }
 
 // The boundary commitments of a GCM segment (trace_layout.h TRS_*), launched behind the segment's GHASH kernel on the same stream: com_out needs Y_out,
@@ -123,10 +156,10 @@ __global__ void k_sha256_trace(uint8_t *__restrict__ trace, size_t stride, size_
 __global__ void k_commit_trace(uint8_t *__restrict__ trace, size_t stride, size_t seg_off, size_t yout_off, const uint8_t *__restrict__ keys, uint32_t key_bytes, const uint8_t *__restrict__ hdrs,
                                size_t hdr_stride, uint32_t nproofs, uint32_t role, uint32_t nblocks) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t ncom = role == TRS_MID ? 2 : 1;
+    const uint32_t ncom = (role == TRS_MID || role == TRS_LAST) ? 2 : 1;               // (a last is a mid here: com_in, then com_out)
     if (t >= nproofs * ncom) return;
     const uint32_t p = t / ncom;
-    const bool out = role == TRS_HEAD || (role == TRS_MID && t % ncom == 1);
+    const bool out = role == TRS_HEAD || (ncom == 2 && t % ncom == 1);
     uint8_t *tr = trace + (size_t)p * stride, *sg = tr + seg_off;
     const uint8_t *key = keys + (size_t)key_bytes * p, *hdr = hdrs + hdr_stride * p;
     const uint8_t *y = out ? tr + yout_off : hdr + TRS_HDR_YIN, *salt = hdr + (out ? TRS_HDR_SALT_OUT : TRS_HDR_SALT_IN);

@@ -312,6 +312,8 @@ __global__ void k_key_tag_trace(uint8_t *__restrict__ trace, size_t stride, size
 // iv || be32(ctr0 + s mod 2^32), with its counter and carry bytes stored in the segment region, then H from the zero block, then (tail) J_0 = iv || 00000001.  A data
 // lane stores C_s = M_s ^ S_Nr for the bytes that exist and zeros behind them.  hdrs: nproofs x TRS_HDR_BYTES(aad_len) bytes; the kernel is handed key, iv, ctr0, aad,
 // message, Y_in, the salts and the length block only.
+// A digest record adds two shapes, which take the same path: role = TRS_LAST is a mid whose msg_len is a byte count, its final block cut as a tail's; and
+// a tail with nblocks = 0, the closing tail, has the two lanes H (slot 0) and J_0 (slot 1) behind lane (p, 0) and reads no message byte.
 template <int NK = 4>
 __global__ void k_aes_trace_gcm_seg(uint8_t *__restrict__ trace, size_t stride, const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ keys, const uint8_t *__restrict__ hdrs,
                                     uint32_t nproofs, uint32_t role, uint32_t nblocks, uint32_t naad, uint32_t msg_len, uint32_t aad_len, const uint8_t *__restrict__ sbox) {
@@ -359,6 +361,8 @@ __global__ void k_aes_trace_gcm_seg(uint8_t *__restrict__ trace, size_t stride, 
 // length block and (tail) S_Nr of the J_0 slot from the trace.  nproofs * (n_mul + 1) * 16 lanes, n_mul = TRS_MULS.  The chain starts from zero for a head and from Y_in
 // otherwise; the blocks are the aad (head), the C_b and, as a tail's last, the length block.  Only the lanes of a tail's last multiplication store a tag byte.  Every
 // byte has exactly one writer; no LDS, no barrier, no cross-lane operation.
+// A last (TRS_LAST) chains from Y_in over its nblocks C_b as a mid does (TRS_MULS); the closing tail (nblocks = 0) runs its ONE multiplication over
+// X = Y_in ^ the length block and stores the tag.
 template <int NK = 4>
 __global__ void k_ghash_trace_seg(uint8_t *__restrict__ trace, size_t stride, uint32_t nproofs, uint32_t role, uint32_t nblocks, uint32_t naad) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;

@@ -112,9 +112,13 @@ void ghash_trace(uint8_t *trace, size_t stride, uint32_t nproofs, uint32_t msg_l
 // what the segment entries check before any lane runs: the role, the key size, the lengths by role, and the stride and alignment against the segment trace's size
 static int gcm_seg_shape(const char *who, const uint8_t *trace, size_t stride, uint32_t nproofs, int role, uint32_t msg_len, uint32_t aad_len, size_t key_bytes, uint32_t &nblocks, uint32_t &naad) {
     const int nk = trace_nk(who, key_bytes);
-    if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL) throw GpuError(std::string(who) + ": the role must be 0 (head), 1 (mid) or 2 (tail)");
-    gcm_lengths(who, msg_len, aad_len, nblocks, naad);
-    if (role != TRS_TAIL && msg_len % 16) throw GpuError(std::string(who) + ": a head or mid segment takes whole blocks");
+    if (role != TRS_HEAD && role != TRS_MID && role != TRS_TAIL && role != TRS_LAST) throw GpuError(std::string(who) + ": the role must be 0 (head), 1 (mid), 2 (tail) or 3 (last)");
+    // (a tail of 0 bytes is the closing tail of a digest record, DESIGN.md 9m: no data block, nblocks = 0)
+    if (role == TRS_TAIL && msg_len == 0) {
+        if (aad_len > (1u << 16)) throw GpuError(std::string(who) + ": the aad has at most 65536 bytes");
+        nblocks = 0; naad = (aad_len + 15) / 16;
+    } else gcm_lengths(who, msg_len, aad_len, nblocks, naad);
+    if (role != TRS_TAIL && role != TRS_LAST && msg_len % 16) throw GpuError(std::string(who) + ": a head or mid segment takes whole blocks");
     if (role != TRS_HEAD && aad_len) throw GpuError(std::string(who) + ": only a head segment takes aad");
     if (!trace) throw GpuError(std::string(who) + ": no trace buffer");
     gcm_trace_fits(who, trace, stride, nproofs, TRS_BYTES(nk, role, (size_t)naad, (size_t)nblocks), "segment region");

@@ -333,7 +333,7 @@ class ProvingKeyImpl {
         // the layout's alignment padding (ahead of the GCM tail, the key-tag slots, the digest region and the reveal region) is written by no kernel and read by no variable: zeroed once, on the
         // stream every trace kernel of this context runs on, so that the trace a debug fetch returns depends on the inputs only and not on what the allocation held before
         gpu::dzero(cx.d_trace, c.trace_bytes + 64, cx.stream);
-        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(std::max<size_t>(16, mode_header_bytes(c)) + (c.digest_kind ? 32 : 0) + reveal_mask_bytes(c));      // (a digest key's header carries H_in behind the mode's own, a reveal key's the mask behind that)
+        cx.d_msg.alloc(std::max<size_t>(message_len, 16)); cx.d_key.alloc(c.key_bytes); cx.d_iv.alloc(c.kind == CIRCUIT_AES_GCM_SEG ? segment_header_bytes(c) : std::max<size_t>(16, mode_header_bytes(c)) + (c.digest_kind ? 32 : 0) + reveal_mask_bytes(c));      // (a digest key's header carries H_in behind the mode's own, a reveal key's the mask behind that)
         for (auto &p : cx.d_cls) p.alloc(n + 64);
         { size_t ncand = (size_t)(3.0 * n / 0.58 * 1.02) + 8192; cx.d_rng.alloc((ncand * 8 / 16 + 2) * 64 + ncand * 8 + (4u << 20)); }
         cx.za_ev.alloc(n); cx.zb_ev.alloc(n); cx.x_poly.alloc(m); cx.x_tmp.alloc(m); cx.x_evals.alloc(n); cx.tmp_n.alloc(n + 1); cx.ra_ev.alloc(n); cx.ra_poly.alloc(n);
@@ -491,7 +491,7 @@ class ProvingKeyImpl {
     };
     Fr sample_outside_h(FiatShamirRng &fs) const;
 
-    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role = -1, int reveal = 0);
+    void setup(int kind, size_t message_len, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role = -1, int reveal = 0, int seg_digest = 0);
     Proof prove(ProverContext &cx, const uint8_t *trace_or_null, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *zk_seed, bool throughput = false, const uint8_t *iv = nullptr);
     void launch_trace(ProverContext &cx, const uint8_t *msg, size_t len, const uint8_t *key, const uint8_t *iv);      // message, key (, IV) -> the context's trace buffer, by the key's mode
     void prove_round1(ProofRun &R);      // randomness, mask polynomial, witness, interpolations, commitments of w z_A z_B mask -> alpha, eta
@@ -500,7 +500,7 @@ class ProvingKeyImpl {
     void prove_open(ProofRun &R);        // the four evaluations, the opening challenge, the two batched KZG openings side by side
 };
 
-void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role, int reveal) {
+void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lits, unsigned flags, size_t aad_len, size_t key_bits, size_t key_tag_blocks, int digest_kind, uint64_t digest_prefix, int seg_role, int reveal, int seg_digest) {
     auto t_setup = Clock::now();
     gpu::require_device();
     device = gpu::current_device();
@@ -508,7 +508,7 @@ void ProvingKeyImpl::setup(int kind, size_t message_len_, const SrsLiterals &lit
     std::unique_ptr<ProverContext> cx0(new ProverContext());
     gpu::stream_t stream = cx0->stream;
     if (kind == CIRCUIT_AES_GCM_SEG) {                                             // message_len_ = the segment's units: c data blocks (head, mid) or Lt bytes (tail)
-        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits, reveal, key_tag_blocks);
+        circuit = compile_aes_gcm_segment_circuit(seg_role, message_len_, aad_len, key_bits, reveal, key_tag_blocks, seg_digest);
         message_len = circuit.message_bytes;
     } else circuit = compile_circuit(kind, message_len, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, reveal);
     const Circuit &c = circuit;
@@ -659,17 +659,20 @@ void ProvingKeyImpl::launch_trace(ProverContext &cx, const uint8_t *msg, size_t 
         if (len != c.message_bytes) throw std::invalid_argument("a GCM segment trace takes exactly the key's message length");
         const size_t na = (c.aad_bytes + 15) / 16, nb = c.n_blocks, n_mul = TRS_MULS(c.seg_role, na, nb);
         const size_t yout_off = c.seg_off - TRS_SEG(c.seg_role, na, nb) + TR_GCM_MUL0(na, nb) + (n_mul - 1) * TR_GCM_MUL_STRIDE + TR_GCM_MUL_Y;
-        gpu::h2d(cx.d_iv, iv, TRS_HDR_BYTES(c.aad_bytes), s);
+        // a digest segment key's header carries H_in and, for a last, total_bits behind the aad: the digest kernel reads both per proof
+        const size_t hdr_bytes = TRS_HDR_DG_BYTES(c.aad_bytes, c.digest_kind);
+        gpu::h2d(cx.d_iv, iv, hdr_bytes, s);
         gpu::aes_trace_gcm_seg(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, cx.d_iv, 1, c.seg_role, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
         gpu::ghash_trace_seg(cx.d_trace, c.trace_bytes, 1, c.seg_role, (uint32_t)c.message_bytes, (uint32_t)c.aad_bytes, s, c.key_bytes);
-        gpu::commit_trace(cx.d_trace, c.trace_bytes, c.seg_off, yout_off, cx.d_key, c.key_bytes, cx.d_iv, TRS_HDR_BYTES(c.aad_bytes), 1, c.seg_role, (uint32_t)nb, s);
+        gpu::commit_trace(cx.d_trace, c.trace_bytes, c.seg_off, yout_off, cx.d_key, c.key_bytes, cx.d_iv, hdr_bytes, 1, c.seg_role, (uint32_t)nb, s);
+        if (c.digest_kind) gpu::sha256_trace_seg(cx.d_trace, c.trace_bytes, c.digest_off, cx.d_msg, cx.d_iv, hdr_bytes, 1, c.seg_role, c.message_bytes, c.aad_bytes, c.digest_kind, s);
     } else {
         gpu::aes_trace(cx.d_trace, c.trace_bytes, cx.d_msg, cx.d_key, 1, (uint32_t)c.n_blocks, s, c.key_bytes);
     }
     // a key with key-tag blocks: the tag slots behind the mode's tail, from the key alone (bytes disjoint from those the kernels above write)
     if (c.key_tag_blocks) gpu::key_tag_trace(cx.d_trace, c.trace_bytes, c.key_tag_off, cx.d_key, 1, (uint32_t)c.key_tag_blocks, s, c.key_bytes);
     // a key with a digest: the proof's header carries H_in behind the mode's own bytes; the digest region behind the tag slots, from the message and H_in alone
-    if (c.digest_kind) {
+    if (c.digest_kind && c.kind != CIRCUIT_AES_GCM_SEG) {                          // (a digest segment key's region is written in its branch above)
         if (!iv) throw std::invalid_argument("a digest proving key needs a header that ends in H_in");
         if (len != c.message_bytes) throw std::invalid_argument("a digest trace takes exactly the key's message length");
         const size_t hb = mode_header_bytes(c);
@@ -1216,10 +1219,15 @@ std::vector<Proof> ProvingKey::prove_chunked(int kind, bool digest, const uint8_
 }
 // ---- GCM segments.  A segment proof's header is TRS_HDR_BYTES(A) bytes: iv, ctr0, Y_in, salt_in, salt_out, the length block, the aad -- and, for
 // a key synthesized with reveal = 1, the segment's slice of the record's mask behind them.  reveal: does the entry carry a mask (9i's rule, as require_key)
-static const Circuit &require_segment_key(const ProvingKey *pk, int role, const char *name, bool reveal = false) {
+// digest: is the entry one of a digest record's; a digest segment key goes through those and no other segment key does
+static const Circuit &require_segment_key(const ProvingKey *pk, int role, const char *name, bool reveal = false, bool digest = false) {
     if (!pk) throw std::invalid_argument(std::string("null ") + name + " segment key");
     const Circuit &c = pk->impl->circuit;
     if (c.kind != CIRCUIT_AES_GCM_SEG) throw std::invalid_argument(std::string("the ") + name + " key is not a GCM segment key: the segment entry points take keys of zkaes_synthesize_keys_gcm_seg (a lone record goes through zkaes_encrypt_gcm_seeded)");
+    if (digest && !c.seg_digest)
+        throw std::invalid_argument(std::string("the ") + name + " key is a plain segment key: the segment _digest_ entry points take keys of zkaes_synthesize_keys_gcm_seg_dg (this one goes through zkaes_encrypt_gcm_segments_seeded_at, zkaes_encrypt_gcm_segment_batch_seeded_at)");
+    if (!digest && c.seg_digest)
+        throw std::invalid_argument(std::string("the ") + name + " key is a segment key of a digest record: use the segment _digest_ entry points (zkaes_encrypt_gcm_segments_digest_seeded_at, zkaes_encrypt_gcm_segment_digest_batch_seeded_at, zkaes_verify_gcm_segments_digest)");
     if (reveal && !c.reveal) throw std::invalid_argument(std::string("the ") + name + " key has no reveal region: the segment _reveal_ entry points take keys synthesized with reveal = 1 (zkaes_synthesize_keys_gcm_seg_rv)");
     if (!reveal && c.reveal)
         throw std::invalid_argument(std::string("the ") + name + " key reveals plaintext bytes under a per-proof mask: use the segment _reveal_ entry points (zkaes_encrypt_gcm_segments_reveal_seeded_at, zkaes_encrypt_gcm_segment_reveal_batch_seeded_at, zkaes_aes_witness_gcm_seg_rv)");
@@ -1238,10 +1246,12 @@ static std::vector<uint8_t> segment_reveal_headers(const Circuit &c, const uint8
     return hs;
 }
 std::vector<uint8_t> ProvingKey::aes_witness_gcm_segment(const uint8_t *message, size_t len, const uint8_t *key, const uint8_t *header, size_t header_len, const uint8_t *mask, size_t mask_len) {
-    const Circuit &c = require_segment_key(this, -1, "proving", mask != nullptr);
-    if (!message || !key || !header) throw std::invalid_argument("null argument");
+    const Circuit &c = require_segment_key(this, -1, "proving", mask != nullptr, impl->circuit.seg_digest != 0);      // (the witness entry takes plain and digest segment keys: the header's length tells them apart)
+    if ((!message && len) || !key || !header) throw std::invalid_argument("null argument");
     if (len != c.message_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: proving key was synthesized for " + std::to_string(c.message_bytes) + " bytes");
-    if (header_len != TRS_HDR_BYTES(c.aad_bytes)) throw std::invalid_argument("a segment header of this key has " + std::to_string(TRS_HDR_BYTES(c.aad_bytes)) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad)");
+    const size_t want = TRS_HDR_DG_BYTES(c.aad_bytes, c.digest_kind);
+    if (header_len != want)
+        throw std::invalid_argument("a segment header of this key has " + std::to_string(want) + " bytes (iv, ctr0, Y_in, salt_in, salt_out, length block, aad" + (c.digest_kind ? ", H_in" : "") + (c.digest_kind == DIGEST_FINAL ? ", be64(total_bits) padded to 16" : "") + ")");
     if (!mask) return witness_of(impl, message, len, key, header);
     if (mask_len != reveal_mask_bytes(c)) throw std::invalid_argument("the mask of this key has " + std::to_string(reveal_mask_bytes(c)) + " bytes");
     return witness_of(impl, message, len, key, segment_reveal_headers(c, header, mask, 1).data());
@@ -1323,6 +1333,84 @@ std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null,
         for (size_t s = m0; s < m1; s++) proofs[s - first_segment] = mids[s - m0];
     }
     if (count && last == n) lone(tail, n - 1, 0);
+    return proofs;
+}
+// ---- digests on segmented records.  A digest segment proof's header is TRS_HDR_DG_BYTES(A, kind) bytes: the plain segment header, H_in, and for a last
+// be64(total_bits) padded to 16
+std::vector<Proof> ProvingKey::prove_gcm_segment_digest_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed, uint64_t index_offset) {
+    const Circuit &c = require_segment_key(this, -1, "proving", false, true);
+    if (n && ((!messages && c.message_bytes) || !keys || !headers)) throw std::invalid_argument("null argument");
+    return prove_many(impl, messages, keys, c.key_bytes, n, n_contexts, zk_seed, index_offset, headers, TRS_HDR_DG_BYTES(c.aad_bytes, c.digest_kind));
+}
+std::vector<Proof> prove_gcm_segments_digest(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *last, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12],
+                                             const uint8_t *aad, size_t aad_len, const uint8_t *salts_or_null, const uint8_t *h_in_or_null, uint64_t digest_prefix, size_t first_segment, size_t count,
+                                             const uint8_t *zk_seed, uint8_t *ciphertext_or_null, uint8_t *tag_or_null, uint8_t *commitments_or_null, uint8_t *states_or_null) {
+    const Circuit &ch = require_segment_key(head, TRS_HEAD, "head", false, true), &cl = require_segment_key(last, TRS_LAST, "last", false, true), &ct_ = require_segment_key(tail, TRS_TAIL, "tail", false, true);
+    if (!message || !key || !iv || (!aad && aad_len)) throw std::invalid_argument("null argument");
+    const size_t c = ch.n_blocks, kb = ch.key_bytes;
+    if (len == 0 || len > ((size_t)1 << 20)) throw std::invalid_argument("GCM segments: a record has 1 .. 2^20 bytes");
+    if (digest_prefix % 64 || digest_prefix >= ((uint64_t)1 << 61) - len)
+        throw std::invalid_argument("zkaes_encrypt_gcm_segments_digest_seeded_at: digest_prefix must be a multiple of 64 with digest_prefix + the record's length below 2^61");
+    if (len <= 16 * c) throw std::invalid_argument("GCM digest segments: this record fits one segment of the head key; a record that fits one proof goes through a lone GCM key with a final digest (zkaes_synthesize_keys_pd, zkaes_encrypt_digest_batch_seeded_at)");
+    const size_t nd = (len + 16 * c - 1) / (16 * c), n = nd + 1, lr = len - 16 * c * (nd - 1);
+    if (aad_len != ch.aad_bytes) throw std::invalid_argument("InstanceDoesNotMatchIndex: the head key was synthesized for " + std::to_string(ch.aad_bytes) + " bytes of aad");
+    if (cl.message_bytes != lr) throw std::invalid_argument("InstanceDoesNotMatchIndex: the record's last data segment has " + std::to_string(lr) + " bytes, the last key was synthesized for " + std::to_string(cl.message_bytes));
+    if (cl.key_bytes != kb || ct_.key_bytes != kb) throw std::invalid_argument("the segment keys were synthesized for different AES key sizes");
+    if (nd > 2) {
+        const Circuit &cm = require_segment_key(mid_or_null, TRS_MID, "mid", false, true);
+        if (cm.n_blocks != c) throw std::invalid_argument("head and mid keys were synthesized for different segment lengths");
+        if (cm.key_bytes != kb) throw std::invalid_argument("the segment keys were synthesized for different AES key sizes");
+    }
+    if (first_segment > n || count > n - first_segment) throw std::invalid_argument("GCM digest segments: first_segment + count exceeds the record's " + std::to_string(n) + " proofs (" + std::to_string(nd) + " data segments and the closing tail)");
+    if (!salts_or_null && (first_segment != 0 || count != n)) throw std::invalid_argument("GCM segments: a job split over calls passes its salts, so that every call makes the same commitments");
+    // ---- the host's side: the record's GCM encryption, Y behind every data segment, the states of plain SHA-256, the salts and the nd commitments
+    std::vector<uint8_t> ct(len), ys(16 * nd), states(32 * (nd + 1)), salts(16 * nd), coms(32 * nd);
+    uint8_t tag[16], lenblk[16];
+    aes128_gcm_encrypt_host(message, len, key, iv, aad, aad_len, ct.data(), tag, kb);
+    gcm_digest_plan_host(message, len, key, kb, iv, aad, aad_len, c, h_in_or_null, digest_prefix, ys.data(), states.data());
+    if (salts_or_null) memcpy(salts.data(), salts_or_null, salts.size());
+    else for (size_t off = 0; off < salts.size(); off += 32) { uint8_t r[32]; os_random_seed(r); memcpy(&salts[off], r, std::min<size_t>(32, salts.size() - off)); }
+    for (size_t s = 0; s < nd; s++) gcm_commit_host(key, kb, &ys[16 * s], &salts[16 * s], &coms[32 * s]);
+    for (int i = 0; i < 8; i++) { lenblk[i] = (uint8_t)((uint64_t)(8 * aad_len) >> (56 - 8 * i)); lenblk[8 + i] = (uint8_t)((uint64_t)(8 * len) >> (56 - 8 * i)); }
+    const uint64_t total_bits = 8 * (digest_prefix + (uint64_t)len);
+    if (ciphertext_or_null) memcpy(ciphertext_or_null, ct.data(), len);
+    if (tag_or_null) memcpy(tag_or_null, tag, 16);
+    if (commitments_or_null) memcpy(commitments_or_null, coms.data(), coms.size());
+    if (states_or_null) memcpy(states_or_null, states.data(), states.size());
+    // proof s < nd is data segment s under (states[s], states[s + 1]); proof nd is the closing tail: Y_in = the accumulator behind the last data block
+    auto header = [&](size_t s, size_t A) {
+        const int kind = s < nd - 1 ? DIGEST_CHAIN : s == nd - 1 ? DIGEST_FINAL : DIGEST_NONE;
+        std::vector<uint8_t> h(TRS_HDR_DG_BYTES(A, kind), 0);
+        memcpy(&h[TRS_HDR_IV], iv, 12);
+        const uint32_t ctr0 = (uint32_t)(2 + s * c);
+        for (int i = 0; i < 4; i++) h[TRS_HDR_CTR0 + i] = (uint8_t)(ctr0 >> (24 - 8 * i));
+        if (s) { memcpy(&h[TRS_HDR_YIN], &ys[16 * (s - 1)], 16); memcpy(&h[TRS_HDR_SALT_IN], &salts[16 * (s - 1)], 16); }
+        if (s < nd) memcpy(&h[TRS_HDR_SALT_OUT], &salts[16 * s], 16);
+        memcpy(&h[TRS_HDR_LEN], lenblk, 16);
+        if (A) memcpy(&h[TRS_HDR_AAD], aad, A);
+        if (kind) memcpy(&h[TRS_HDR_HIN(A)], &states[32 * s], 32);
+        if (kind == DIGEST_FINAL) for (int i = 0; i < 8; i++) h[TRS_HDR_BITS(A) + i] = (uint8_t)(total_bits >> (56 - 8 * i));
+        return h;
+    };
+    // ---- the proofs: proof s draws from the job's seed at index s, whichever call makes it; the mids run side by side over the mid key's contexts
+    std::vector<Proof> proofs(count);
+    auto lone = [&](ProvingKey *pk, size_t s, size_t A) {
+        uint8_t seed_s[32];
+        if (zk_seed) derive_zk_seed(seed_s, zk_seed, (uint64_t)s);
+        const size_t seg_len = s < nd - 1 ? 16 * c : s == nd - 1 ? lr : 0;
+        proofs[s - first_segment] = pk->impl->prove(pk->impl->context(0), nullptr, seg_len ? message + 16 * c * s : nullptr, seg_len, key, zk_seed ? seed_s : nullptr, false, header(s, A).data());
+    };
+    const size_t end = first_segment + count;
+    if (count && first_segment == 0) lone(head, 0, aad_len);
+    const size_t m0 = std::max<size_t>(first_segment, 1), m1 = std::min(end, nd - 1);
+    if (m0 < m1) {
+        std::vector<uint8_t> hs;
+        for (size_t s = m0; s < m1; s++) { const std::vector<uint8_t> h = header(s, 0); hs.insert(hs.end(), h.begin(), h.end()); }
+        std::vector<Proof> mids = prove_many(mid_or_null->impl, message + 16 * c * m0, key, 0, m1 - m0, mid_or_null->contexts(), zk_seed, (uint64_t)m0, hs.data(), TRS_HDR_DG_BYTES(0, DIGEST_CHAIN));
+        for (size_t s = m0; s < m1; s++) proofs[s - first_segment] = mids[s - m0];
+    }
+    if (first_segment <= nd - 1 && nd - 1 < end) lone(last, nd - 1, 0);
+    if (first_segment <= nd && nd < end) lone(tail, nd, 0);
     return proofs;
 }
 Proof ProvingKey::prove_ops(uint32_t x, uint32_t y, const uint8_t *zk_seed) {
@@ -1449,10 +1537,10 @@ std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len
     pk->impl->setup(circuit_kind, message_len, srs, flags, aad_len, key_bits, key_tag_blocks, digest_kind, digest_prefix, -1, reveal);
     return pk;
 }
-std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags, int reveal, size_t key_tag_blocks) {
+std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags, int reveal, size_t key_tag_blocks, int digest) {
     std::unique_ptr<ProvingKey> pk(new ProvingKey());
     pk->impl = new ProvingKeyImpl();
-    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, key_tag_blocks, 0, 0, role, reveal);
+    pk->impl->setup(CIRCUIT_AES_GCM_SEG, units, srs, flags, aad_len, key_bits, key_tag_blocks, 0, 0, role, reveal, digest);
     return pk;
 }
 

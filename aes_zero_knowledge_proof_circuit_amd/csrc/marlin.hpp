@@ -114,6 +114,11 @@ class ProvingKey {
     // caller answers for what the headers say: prove_gcm_segments below derives them from one record
     std::vector<Proof> prove_gcm_segment_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
                                                uint64_t index_offset = 0, const uint8_t *masks_or_null = nullptr, uint8_t *revealed_or_null = nullptr);
+    // the same for a segment key of a DIGEST record (from synthesize_keys_gcm_segment with digest = 1, which every call above but the witness refuses,
+    // as this one refuses every other key): headers = n x TRS_HDR_DG_BYTES(A, kind) bytes, the plain segment header, then H_in (head, mid, last), then a last's
+    // be64(total_bits) padded to 16.  The closing tail has no message: messages may be null for it
+    std::vector<Proof> prove_gcm_segment_digest_batch(const uint8_t *messages, const uint8_t *keys, const uint8_t *headers, size_t n, size_t n_contexts, const uint8_t *zk_seed = nullptr,
+                                                      uint64_t index_offset = 0);
     const ProverTimings &last_timings() const;
     // one proof with the op recorder open: JSON of the transforms and MSMs the library actually launched (marlin.cpp; SURVEY.md 8d op lists)
     std::string op_lists_json(const uint8_t *message, size_t len, const uint8_t key[16], bool throughput_path);
@@ -149,7 +154,7 @@ std::unique_ptr<ProvingKey> synthesize_keys(int circuit_kind, size_t message_len
 // A GCM segment key: role = 0 head, 1 mid, 2 tail; units = c data blocks (head, mid) or Lt bytes (tail); aad_len: head only.  No digest;
 // reveal: 0 or 1; key_tag_blocks: 0, 1 or 2 for a head, 0 for a mid or tail
 std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, size_t aad_len, size_t key_bits, const SrsLiterals &srs, unsigned flags = 0, int reveal = 0,
-                                                        size_t key_tag_blocks = 0);
+                                                        size_t key_tag_blocks = 0, int digest = 0);      // (digest = 1: a segment of a digest record, DESIGN.md 9m: role 3 = last, a tail takes units = 0, no reveal and no key tag)
 // Segments [first_segment, first_segment + count) of ONE GCM record of len bytes as segment-proofs: n = ceil(ceil(len / 16) / c) >= 2 segments, c = the head key's data
 // blocks; mid_or_null may be null when n = 2; the tail key is the one for the record's last len - 16 c (n - 1) bytes.  The host computes the record's ciphertext and tag,
 // Y at every boundary and the n - 1 commitments from salts_or_null (16 (n - 1) bytes; null = fresh OS randomness, allowed only when the call covers the whole record);
@@ -161,6 +166,16 @@ std::unique_ptr<ProvingKey> synthesize_keys_gcm_segment(int role, size_t units, 
 std::vector<Proof> prove_gcm_segments(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12], const uint8_t *aad,
                                       size_t aad_len, const uint8_t *salts_or_null, size_t first_segment, size_t count, const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr,
                                       uint8_t *tag_or_null = nullptr, uint8_t *commitments_or_null = nullptr, const uint8_t *mask_or_null = nullptr, uint8_t *revealed_or_null = nullptr);
+// Proofs [first_segment, first_segment + count) of ONE GCM DIGEST record of len > 16 c bytes: nd = ceil(len / (16 c)) data segments -- head, nd - 2 mids,
+// the last with len - 16 c (nd - 1) bytes -- and, as proof nd, the closing tail: nd + 1 proofs, mid_or_null may be null when nd = 2.  The host computes ciphertext, tag, Y
+// behind every data segment, the nd commitments (salts_or_null: 16 nd bytes, as above) and the nd + 1 states of plain SHA-256 from h_in_or_null (null = the initial
+// value) with digest_prefix bytes hashed ahead (a multiple of 64): data segment s is proven under (states[s], states[s + 1]), the last with total_bits =
+// 8 (digest_prefix + len), and states[nd] is the digest of prefix || message.  Proof s draws at index s.  Receives on request ciphertext (len), tag (16), commitments
+// (32 nd) and states (32 (nd + 1))
+std::vector<Proof> prove_gcm_segments_digest(ProvingKey *head, ProvingKey *mid_or_null, ProvingKey *last, ProvingKey *tail, const uint8_t *message, size_t len, const uint8_t *key, const uint8_t iv[12],
+                                             const uint8_t *aad, size_t aad_len, const uint8_t *salts_or_null, const uint8_t *h_in_or_null, uint64_t digest_prefix, size_t first_segment, size_t count,
+                                             const uint8_t *zk_seed, uint8_t *ciphertext_or_null = nullptr, uint8_t *tag_or_null = nullptr, uint8_t *commitments_or_null = nullptr,
+                                             uint8_t *states_or_null = nullptr);
 // hold = true: every universal / Lagrange SRS built (or alive) from now on stays resident after its last key is freed; false: back to "freed with the last key"
 void srs_hold(bool hold);
 // process default of ProvingKey::contexts(): ZKAES_CONTEXTS from the environment (read once), else ZKAES_DEFAULT_CONTEXTS

@@ -213,9 +213,10 @@ static_assert(TRV_MASK_BYTES(1) == 1 && TRV_MASK_BYTES(17) == 3 && TRV_REVEALED(
 #define TRS_HEAD 0
 #define TRS_MID 1
 #define TRS_TAIL 2
+#define TRS_LAST 3                                                        // digest records only (below): a mid with a byte length
 #define TRS_SLOTS(role, nb) ((nb) + 1 + ((role) == TRS_TAIL ? 1 : 0))
 #define TRS_GCM(nk, role, nb) ((TRK_CBC(nk, TRS_SLOTS(role, nb)) + 15) / 16 * 16)
-#define TRS_MULS(role, na, nb) ((role) == TRS_HEAD ? (na) + (nb) : (role) == TRS_MID ? (nb) : (nb) + 1)
+#define TRS_MULS(role, na, nb) ((role) == TRS_HEAD ? (na) + (nb) : ((role) == TRS_MID || (role) == TRS_LAST) ? (nb) : (nb) + 1)
 #define TRS_CTR0 12                                                       // inside the tail's iv slot
 #define TRS_TAG(role, na, nb) (TR_GCM_MUL0(na, nb) + TRS_MULS(role, na, nb) * TR_GCM_MUL_STRIDE)
 #define TRS_SEG(role, na, nb) (TRS_TAG(role, na, nb) + 16)               // sg, relative to the tail's base TRS_GCM
@@ -278,6 +279,37 @@ static_assert(TRS_HDR_RV_BYTES(13, 0, 16) == 93 && TRS_HDR_RV_BYTES(13, 1, 16) =
     static_assert(TRS_KT_RV(nk, TRS_HEAD, 1, 2, 1) == TRS_KT(nk, TRS_HEAD, 1, 2) + TRK_BLOCK_STRIDE(nk) && TRS_KT_RV(nk, TRS_HEAD, 0, 4, 2) == TRS_KT(nk, TRS_HEAD, 0, 4) + 2 * TRK_BLOCK_STRIDE(nk), \
                   "the reveal region of a tagged head begins where the tag slots end")
 TRS_KT_ASSERT(4); TRS_KT_ASSERT(6); TRS_KT_ASSERT(8);
+// ---- digests on segments: a record whose segment keys were synthesized with the digest flag ends differently.  Its last data bytes lie in a segment of
+// role TRS_LAST: a mid -- Y_in, com_in, com_out, nb + 1 AES slots, nb multiplications, two compression slots -- whose length is Lr = 1 .. 16 nb BYTES, the final block
+// zero-padded for GHASH as a tail's.  Its tail holds no data block (nb = 0, the "closing tail"): slot 0 is H, slot 1 is J_0, its ONE multiplication runs over
+// X = Y_in ^ the length block, and it has the tag and com_in.  A head, mid or last of such a record has 9f's digest region (the TRD_* inner layout) BEHIND the segment
+// region's two compression slots, at the next multiple of 16: chain (D = 1) over the 16 nb bytes of a head or mid, final (D = 2) over the Lr bytes of a last.  No TRS_*
+// offset moves, and without the flag a trace is what it was.
+// The proof's header grows: TRS_HDR_BYTES(A), then H_in (32), then for a last be64(total_bits) and eight zero bytes -- the bit count of everything hashed up to the
+// record's end, which the padding's length field takes from the header and not from the key, so that one last key serves every record whose last segment has Lr bytes
+#define TRS_DG(nk, role, na, nb) TRD(TRS_BYTES(nk, role, na, nb))
+#define TRS_DG_KIND(role) ((role) == TRS_LAST ? 2 : (role) == TRS_TAIL ? 0 : 1)
+// a last's region ends, behind its slots, in the 16 bytes be64(total_bits) || eight zero bytes as the header gave them (the padding's length inputs)
+#define TRS_DG_BITS(nblk) (TRD_SLOT0 + (nblk) * TRD_SLOT_STRIDE)
+#define TRS_DG_BYTES(nk, role, na, nb, D, len) (TRD_BYTES(TRS_BYTES(nk, role, na, nb), D, TRD_BLOCKS(D, len)) + ((D) == 2 ? 16 : 0))
+#define TRS_HDR_HIN(A) TRS_HDR_BYTES(A)
+#define TRS_HDR_BITS(A) (TRS_HDR_BYTES(A) + 32)
+#define TRS_HDR_DG_BYTES(A, D) (TRS_HDR_BYTES(A) + ((D) ? 32 : 0) + ((D) == 2 ? 16 : 0))
+static_assert(TRS_MULS(TRS_HEAD, 1, 4) == 5 && TRS_MULS(TRS_MID, 0, 4) == 4 && TRS_MULS(TRS_TAIL, 0, 4) == 5 && TRS_SLOTS(TRS_HEAD, 4) == 5 && TRS_SLOTS(TRS_MID, 4) == 5 && TRS_SLOTS(TRS_TAIL, 4) == 6 &&
+              TRS_BYTES(4, TRS_TAIL, 0, 3) == TRK_GCM_BYTES(4, 0, 3) + TRS_SEG_BYTES(3), "the older roles keep their slots, multiplications and lengths");
+#define TRS_DG_ASSERT(nk) \
+    static_assert(TRS_SLOTS(TRS_LAST, 4) == TRS_SLOTS(TRS_MID, 4) && TRS_MULS(TRS_LAST, 0, 4) == TRS_MULS(TRS_MID, 0, 4) && TRS_GCM(nk, TRS_LAST, 4) == TRS_GCM(nk, TRS_MID, 4) && \
+                  TRS_TAG(TRS_LAST, 0, 4) == TRS_TAG(TRS_MID, 0, 4) && TRS_SEG(TRS_LAST, 0, 4) == TRS_SEG(TRS_MID, 0, 4) && TRS_BYTES(nk, TRS_LAST, 0, 4) == TRS_BYTES(nk, TRS_MID, 0, 4), \
+                  "a last of 16 c bytes has the offsets of a mid of c"); \
+    static_assert(TRS_SLOTS(TRS_TAIL, 0) == 2 && TRS_MULS(TRS_TAIL, 0, 0) == 1 && TRS_GCM(nk, TRS_TAIL, 0) % 16 == 0 && TRS_GCM(nk, TRS_TAIL, 0) >= TRK_CBC(nk, 2) && TR_GCM_V(0, 0) == 16 && \
+                  TRS_TAG(TRS_TAIL, 0, 0) == 16 + 2048 + TR_GCM_MUL_STRIDE && TRS_SEG(TRS_TAIL, 0, 0) % 16 == 0 && TRS_SLOT_IN(0) == 128 && TRS_BYTES(nk, TRS_TAIL, 0, 0) % 16 == 0, \
+                  "the closing tail (nb = 0) is well-formed and 16-byte aligned"); \
+    static_assert(TRS_DG(nk, TRS_HEAD, 1, 4) % 16 == 0 && TRS_DG(nk, TRS_MID, 0, 4) % 16 == 0 && TRS_DG(nk, TRS_LAST, 0, 1) % 16 == 0 && TRS_DG(nk, TRS_LAST, 0, 4) >= TRS_BYTES(nk, TRS_LAST, 0, 4) && \
+                  TRS_DG_BYTES(nk, TRS_MID, 0, 4, 0, 64) == TRS_BYTES(nk, TRS_MID, 0, 4) && TRS_DG_BYTES(nk, TRS_MID, 0, 4, 1, 64) == TRS_DG(nk, TRS_MID, 0, 4) + TRD_SLOT0 + TRD_SLOT_STRIDE && \
+                  TRS_DG_BYTES(nk, TRS_LAST, 0, 4, 2, 56) == TRS_DG(nk, TRS_LAST, 0, 4) + TRS_DG_BITS(2) + 16 && TRS_DG_BITS(2) % 16 == 0, "a segment's digest region begins on a multiple of 16 behind the compression slots")
+TRS_DG_ASSERT(4); TRS_DG_ASSERT(6); TRS_DG_ASSERT(8);
+static_assert(TRS_DG_KIND(TRS_HEAD) == 1 && TRS_DG_KIND(TRS_MID) == 1 && TRS_DG_KIND(TRS_LAST) == 2 && TRS_DG_KIND(TRS_TAIL) == 0 && TRS_HDR_DG_BYTES(13, 0) == 93 && TRS_HDR_DG_BYTES(13, 1) == 125 &&
+              TRS_HDR_DG_BYTES(0, 2) == 128 && TRS_HDR_HIN(0) == 80 && TRS_HDR_BITS(0) == 112, "a digest segment header: H_in behind the aad, a last's total_bits behind H_in");
 
 // witness descriptors (one u32 per column of z)
 #define WD_KIND_SHIFT 30

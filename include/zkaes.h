@@ -840,6 +840,48 @@ int zkaes_verify_gcm_segments_batch_kt_gpu(const zkaes_vk *head, const zkaes_vk 
                                            size_t c, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len, const uint8_t tag16[16],
                                            const uint8_t *commitments, size_t commitments_len, const uint8_t *key_tag, size_t key_tag_len, const uint8_t *mask, size_t mask_len,
                                            const uint8_t *revealed, size_t revealed_len, int *accepted_each, size_t *n_accepted);
+/* ---- digests on segmented GCM records.  A DIGEST record of L > 16 c bytes, c a multiple of 4, is nd = ceil(L / (16 c)) data segments and ONE closing tail:
+ * nd + 1 proofs.  Roles: 0 head (units = c), 1 mid (units = c), 3 LAST (units = Lr = L - 16 c (nd - 1) bytes, 1 .. 16 c: a mid with a byte length, com_in and com_out, no
+ * tag) and 2 tail with units = 0: no data block, the H and J_0 slots, ONE multiplication over Y_in ^ the length block, the tag, com_in.  A head or mid also proves the chain
+ * digest H_out = C(..C(H_in, M[0:64])..) over its 16 c bytes, a last the FINAL digest over its Lr bytes with the padding 0x80, zeros and the 64 public input bits total_bits.
+ * Public input, behind the role's of the plain segment entries: H_in (32), H_out (32) in SHA-256's big-endian serialisation; a last then the 8 bytes of total_bits,
+ * big-endian; each byte LSB first.  The states between the proofs are public, as in a chunked digest job: segment s is proven under (states[s], states[s + 1]),
+ * states[0] = H_in (NULL = the initial value) and states[nd] = the SHA-256 digest of prefix || M.  There are nd commitments, one behind every data segment.
+ * A proof's header is the plain segment header (80 + A bytes), then H_in (32), then for a last be64(total_bits) and eight zero bytes; the closing tail's is the plain one.
+ * Digest segment keys take neither reveal nor key_tag_blocks.  Every other segment entry refuses a digest segment key (zkaes_aes_witness_gcm_seg takes one, with its longer
+ * header), these entries refuse every other key, and each refusal names the entry to use. */
+int zkaes_synthesize_keys_gcm_seg_dg(int role, unsigned key_bits, size_t units, size_t aad_length, size_t srs_num_constraints, size_t srs_num_variables, size_t srs_num_non_zero,
+                                     unsigned flags, zkaes_pk **pk, zkaes_vk **vk);
+/* digest: 1 for a segment key of a digest record, else 0; header_bytes: a segment key's whole per-proof header (0 for every other key) */
+int zkaes_pk_segment_digest(const zkaes_pk *pk, int *digest, size_t *header_bytes);
+/* n proofs of ONE digest segment key under caller headers (n x header_bytes), as zkaes_encrypt_gcm_segment_batch_seeded_at; a closing tail takes messages_len = 0 */
+int zkaes_encrypt_gcm_segment_digest_batch_seeded_at(size_t n, const uint8_t *messages, size_t messages_len, const uint8_t *secret_keys, size_t secret_keys_len, const uint8_t *headers,
+                                                     size_t headers_len, const zkaes_pk *pk, const uint8_t *zk_seed32, uint64_t first_proof_index, uint8_t **proofs, size_t *proofs_len,
+                                                     size_t *proof_lens);
+/* proofs [first_segment, first_segment + count) of one record's nd + 1 (proof nd is the closing tail); mid_or_null may be NULL when nd = 2; salts: 16 nd bytes or NULL (whole
+ * record only); h_in_or_null: states[0]; digest_prefix: bytes hashed ahead of the record, a multiple of 64.  Proof s draws its zero-knowledge randomness at index s, so a job
+ * split over calls is byte-identical to the whole job.  Receives on request the record's ciphertext (L), tag (16), commitments (32 nd) and states (32 (nd + 1)). */
+int zkaes_encrypt_gcm_segments_digest_seeded_at(const uint8_t *message, size_t message_len, const uint8_t *secret_key, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len,
+                                                const zkaes_pk *head, const zkaes_pk *mid_or_null, const zkaes_pk *last, const zkaes_pk *tail, const uint8_t *salts_or_null,
+                                                const uint8_t *h_in_or_null, uint64_t digest_prefix, const uint8_t *zk_seed32, size_t first_segment, size_t count, uint8_t *ciphertext_or_null,
+                                                uint8_t *tag_or_null, uint8_t *commitments_or_null, uint8_t *states_or_null, uint8_t **proofs, size_t *proofs_len, size_t *proof_lens);
+/* host only */
+int zkaes_circuit_info_gcm_seg_dg(int role, unsigned key_bits, size_t units, size_t aad_length, uint64_t out[12]);
+int zkaes_circuit_matrix_gcm_seg_dg(int role, unsigned key_bits, size_t units, size_t aad_length, int which, uint64_t *n_rows, uint64_t *nnz, uint32_t *rowptr, uint32_t *col, int64_t *coeff);
+/* the record helper: ys = the nd accumulators behind the data segments (zkaes_gcm_boundaries stops one short: the last is the one behind the record's last data block, ahead
+ * of the length block), states = the nd + 1 states through zkaes_sha256_chain / _finish.  ys = states = NULL: only *n_data_segments */
+int zkaes_gcm_digest_plan(const uint8_t *message, size_t message_len, const uint8_t *secret_key, size_t key_len, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, size_t c,
+                          const uint8_t *h_in_or_null, uint64_t digest_prefix, uint8_t *ys, size_t ys_cap, uint8_t *states, size_t states_cap, size_t *n_data_segments);
+/* the nd + 1 rows the verifier below checks the proofs against, ragged, as zkaes_gcm_segment_public_inputs; roles: 0 head, 1 mid, 3 last, 2 tail */
+int zkaes_gcm_segment_digest_public_inputs(size_t n_proofs, size_t c, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len,
+                                           const uint8_t tag16[16], const uint8_t *commitments, size_t commitments_len, const uint8_t *states, size_t states_len, uint64_t digest_prefix,
+                                           uint8_t *out_bits, size_t *n_bits_each, int *roles);
+/* The verifier sets every ctr0 = 2 + s c, cuts the ciphertext, sets total_bits = 8 (digest_prefix + ciphertext_len), builds the length block and gives the tag to the closing
+ * tail only; ONE commitments array (32 nd) and ONE states array (32 (nd + 1)).  Per-proof verdicts; a proof that does not parse is a rejected segment. */
+int zkaes_verify_gcm_segments_digest(const zkaes_vk *head, const zkaes_vk *mid_or_null, const zkaes_vk *last, const zkaes_vk *tail, const uint8_t *proofs, const size_t *proof_lens,
+                                     size_t n_proofs, size_t c, const uint8_t iv12[12], const uint8_t *aad, size_t aad_len, const uint8_t *ciphertext, size_t ciphertext_len,
+                                     const uint8_t tag16[16], const uint8_t *commitments, size_t commitments_len, const uint8_t *states, size_t states_len, uint64_t digest_prefix,
+                                     int *accepted_each, size_t *n_accepted);
 /* The keyed public-input kernel, one launch per call (tests): zkaes_public_input_eval over rows of n_keys domains.  Key k has |X| = 2^lg_m[k] and rows of n_bits[k] 0/1
  * bytes; row i belongs to key key_of[i] and follows row i - 1 in bits.  out[i] = x^(betas[i]) over row i's own domain. */
 int zkaes_public_input_eval_keyed(const int *lg_m, const size_t *n_bits, size_t n_keys, const uint32_t *key_of, const uint8_t *betas, const uint8_t *bits, size_t n, uint8_t *out);

@@ -221,6 +221,30 @@ extern "C" {
                                               c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
                                               commitments: *const u8, commitments_len: usize, key_tag: *const u8, key_tag_len: usize, mask: *const u8, mask_len: usize,
                                               revealed: *const u8, revealed_len: usize, accepted_each: *mut c_int, n_accepted: *mut usize) -> c_int;
+    // digests on segmented records (include/zkaes.h, "digests on segmented GCM records"; declarations only, no wrappers yet, and not compiled: no cargo in the build
+    // image).  Roles 0 head, 1 mid, 3 last (units = the last data segment's bytes), 2 tail with units = 0; a record is nd data segments and the closing tail
+    fn zkaes_synthesize_keys_gcm_seg_dg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, srs_num_constraints: usize, srs_num_variables: usize, srs_num_non_zero: usize,
+                                        flags: c_uint, pk: *mut *mut zkaes_pk, vk: *mut *mut zkaes_vk) -> c_int;
+    fn zkaes_pk_segment_digest(pk: *const zkaes_pk, digest: *mut c_int, header_bytes: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_segment_digest_batch_seeded_at(n: usize, messages: *const u8, messages_len: usize, secret_keys: *const u8, secret_keys_len: usize, headers: *const u8,
+                                                        headers_len: usize, pk: *const zkaes_pk, zk_seed32: *const u8, first_proof_index: u64, proofs: *mut *mut u8, proofs_len: *mut usize,
+                                                        proof_lens: *mut usize) -> c_int;
+    fn zkaes_encrypt_gcm_segments_digest_seeded_at(message: *const u8, message_len: usize, secret_key: *const u8, iv12: *const u8, aad: *const u8, aad_len: usize, head: *const zkaes_pk,
+                                                   mid_or_null: *const zkaes_pk, last: *const zkaes_pk, tail: *const zkaes_pk, salts_or_null: *const u8, h_in_or_null: *const u8,
+                                                   digest_prefix: u64, zk_seed32: *const u8, first_segment: usize, count: usize, ciphertext_or_null: *mut u8, tag_or_null: *mut u8,
+                                                   commitments_or_null: *mut u8, states_or_null: *mut u8, proofs: *mut *mut u8, proofs_len: *mut usize, proof_lens: *mut usize) -> c_int;
+    fn zkaes_circuit_info_gcm_seg_dg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, out: *mut u64) -> c_int;
+    fn zkaes_circuit_matrix_gcm_seg_dg(role: c_int, key_bits: c_uint, units: usize, aad_length: usize, which: c_int, n_rows: *mut u64, nnz: *mut u64, rowptr: *mut u32, col: *mut u32,
+                                       coeff: *mut i64) -> c_int;
+    fn zkaes_gcm_digest_plan(message: *const u8, message_len: usize, secret_key: *const u8, key_len: usize, iv12: *const u8, aad: *const u8, aad_len: usize, c: usize,
+                             h_in_or_null: *const u8, digest_prefix: u64, ys: *mut u8, ys_cap: usize, states: *mut u8, states_cap: usize, n_data_segments: *mut usize) -> c_int;
+    fn zkaes_gcm_segment_digest_public_inputs(n_proofs: usize, c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
+                                              commitments: *const u8, commitments_len: usize, states: *const u8, states_len: usize, digest_prefix: u64, out_bits: *mut u8,
+                                              n_bits_each: *mut usize, roles: *mut c_int) -> c_int;
+    fn zkaes_verify_gcm_segments_digest(head: *const zkaes_vk, mid_or_null: *const zkaes_vk, last: *const zkaes_vk, tail: *const zkaes_vk, proofs: *const u8, proof_lens: *const usize,
+                                        n_proofs: usize, c: usize, iv12: *const u8, aad: *const u8, aad_len: usize, ciphertext: *const u8, ciphertext_len: usize, tag16: *const u8,
+                                        commitments: *const u8, commitments_len: usize, states: *const u8, states_len: usize, digest_prefix: u64, accepted_each: *mut c_int,
+                                        n_accepted: *mut usize) -> c_int;
     // kernel-level entries of the kernels that build a key (include/zkaes.h, "kernels that BUILD A KEY": test surface, not product API; declarations only, no wrappers, and
     // not compiled: no cargo in the build image).  A point is 96 bytes of affine x || y in Montgomery form, infinity 96 zero bytes; a field element 32 bytes; a Niels record
     // 192 bytes; every output of zkaes_index_evals holds 2^lg_k + 64 elements
