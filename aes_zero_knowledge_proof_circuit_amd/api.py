@@ -1789,12 +1789,15 @@ def _arith_ops():
 
 
 ARITH_OPS = _arith_ops()
+# the zipped products of te_madd_hot (arith_probe.cuh ZK_PROBE_ZIP_OPS; device only, outside ARITH_OPS: tests/test_gpu_lower_seed.py).  Per case: a_0 b_0 a_1 b_1 ... in,
+# the products out; the digits are the bound products (in units of 2^56) of the operand pairs each probe was instantiated for.
+ARITH_ZIP_OPS = {"fq377x28.mul_zip_12": (232, 28, 14), "fq377x28.mul_zip_8": (233, 28, 14), "fq377x28.mul_zip_5_2_1": (234, 84, 42), "fq377x28.mul_zip_12_8_6_12": (235, 112, 56)}
 ARITH_QUAD_OPS = ("te377.te_add_quad", "te377.te_dbl_quad")      # four lanes per case on the device; no host body
 
 
 def arith_probe(op_name, cases):
     """cases: bytes of little-endian 32-bit words, a whole number of cases (1 .. 65536) of ARITH_OPS[op_name][1] words each -> the output words as bytes"""
-    op, nin, nout = ARITH_OPS[op_name]
+    op, nin, nout = ARITH_OPS[op_name] if op_name in ARITH_OPS else ARITH_ZIP_OPS[op_name]
     cases = bytes(cases)
     n, rest = divmod(len(cases), 4 * nin)
     if rest:

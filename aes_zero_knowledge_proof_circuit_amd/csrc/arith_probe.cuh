@@ -17,7 +17,7 @@ namespace probe {
 
 template <class T> ZK_HD T ld(const uint32_t *in) { T r; for (int i = 0; i < T::N; i++) r.l[i] = in[i]; return r; }
 template <class T> ZK_HD void st(uint32_t *out, const T &v) { for (int i = 0; i < T::N; i++) out[i] = v.l[i]; }
-struct OpBase { static constexpr bool QUAD = false; };
+struct OpBase { static constexpr bool QUAD = false, SEEDED = false; };      // SEEDED: has run_seeded(in, out, seed) for the kernel that took hot_loop_seed() at its entry
 
 // ---- unary / binary shapes shared by the three field classes: T -> T and T x T -> T
 #define ZK_PROBE_UN(NAME, EXPR)                                                                                                                   \
@@ -118,14 +118,32 @@ struct NielsFromW : OpBase { using P = Fq377P; static constexpr int NIN = 2 * P:
     } };
 // in: accumulator, the current record AS LOADED (niels_load_signed with the current sign), the next record as it lies in the table, neg, next_neg;
 // out: accumulator, then the record left in n (the next one, loaded with ITS sign)
-struct TeMaddHot : OpBase { using P = Fq377P; static constexpr int NIN = PTW + 2 * NIW + 2, NOUT = PTW + NIW;
-    ZK_HD static void run(const uint32_t *in, uint32_t *out, uint64_t bias) {
+struct TeMaddHot : OpBase { using P = Fq377P; static constexpr bool SEEDED = true; static constexpr int NIN = PTW + 2 * NIW + 2, NOUT = PTW + NIW;
+    ZK_HD static void run_seeded(const uint32_t *in, uint32_t *out, FpMsm<P>::Seed seed) {
         AccTE<P> a = ld_te<P>(in);
         Niels28<P> n = ld_niels<P>(in + PTW);
         const Niels28<P> next = ld_niels<P>(in + PTW + NIW);
-        te_madd_hot<P>(a, n, in[PTW + 2 * NIW] != 0, &next, in[PTW + 2 * NIW + 1] != 0, bias);
+        te_madd_hot<P>(a, n, in[PTW + 2 * NIW] != 0, &next, in[PTW + 2 * NIW + 1] != 0, seed);
         st_te<P>(out, a); st_niels<P>(out + PTW, n);
-    } };
+    }
+    ZK_HD static void run(const uint32_t *in, uint32_t *out, uint64_t) { run_seeded(in, out, FpMsm<P>::hot_loop_seed()); } };
+// W products at once as te_madd_hot multiplies them: the zipped lower halves on the bias -1 (ff28.cuh mul_low_zip<X...>, X = the bound product of each operand pair),
+// then the zipped upper halves.  in: a_0 b_0 a_1 b_1 ...; out: the W products
+template <int... X> struct MulZip : OpBase { using G = Fp28<Fq377P>; static constexpr int W = sizeof...(X); static constexpr bool SEEDED = true;
+    static constexpr int NIN = 2 * W * G::N, NOUT = W * G::N;
+    ZK_HD static void run_seeded(const uint32_t *in, uint32_t *out, G::Seed seed) {
+        G a[W], b[W], r[W];
+        const G *pa[W], *pb[W];
+        G *pr[W];
+        typename G::Low lo[W];
+        for (int w = 0; w < W; w++) { a[w] = ld<G>(in + 2 * w * G::N); b[w] = ld<G>(in + (2 * w + 1) * G::N); pa[w] = &a[w]; pb[w] = &b[w]; pr[w] = &r[w]; }
+        const G *const (&cpa)[W] = pa; const G *const (&cpb)[W] = pb; G *const (&cpr)[W] = pr;
+        G::template mul_low_zip<X...>(cpa, cpb, seed, lo);
+        const typename G::Low (&clo)[W] = lo;
+        G::template mul_high<W>(cpa, cpb, clo, cpr);
+        for (int w = 0; w < W; w++) st<G>(out + w * G::N, r[w]);
+    }
+    ZK_HD static void run(const uint32_t *in, uint32_t *out, uint64_t) { run_seeded(in, out, G::hot_loop_seed()); } };
 // in: accumulator, Affine28 (x, y); out: accumulator, then madd28's return value
 template <class P> struct Madd28 : OpBase { static constexpr int NIN = PTW + 2 * GW, NOUT = PTW + 1;
     ZK_HD static void run(const uint32_t *in, uint32_t *out, uint64_t) {
@@ -177,12 +195,24 @@ struct TeDblQuad { using P = Fq377P; static constexpr bool QUAD = true; static c
     X(192, TeMadd) X(193, TeAdd) X(194, TeDbl) X(195, TeNeg) X(196, TeToStd) X(197, NielsFromW) X(198, TeMaddHot) X(199, TeAddQuad) X(200, TeDblQuad) \
     ZK_PROBE_W28(X, 208, Fq377P) ZK_PROBE_W28(X, 216, Fq381P)
 
+// the zip probes, outside the table above (ids beyond MAX_OP_ID; api.py ARITH_ZIP_OPS names them): a lone product at the two bound products that differ in their
+// switch-over column, and the two zips of te_madd_hot
+#define ZK_PROBE_ZIP_OPS(X) X(232, MulZip<12>) X(233, MulZip<8>) X(234, MulZip<5, 2, 1>) X(235, MulZip<12, 8, 6, 12>)
+
 template <class O> struct Tag { using type = O; };
 // fn(Tag<Op>{}) for the operation with this id; false for an unknown id
 template <class Fn> bool dispatch(int op, Fn &&fn) {
     switch (op) {
 #define ZK_PROBE_CASE(ID, ...) case ID: fn(Tag<__VA_ARGS__>{}); return true;
         ZK_PROBE_OPS(ZK_PROBE_CASE)
+#undef ZK_PROBE_CASE
+        default: return false;
+    }
+}
+template <class Fn> bool dispatch_zip(int op, Fn &&fn) {
+    switch (op) {
+#define ZK_PROBE_CASE(ID, ...) case ID: fn(Tag<__VA_ARGS__>{}); return true;
+        ZK_PROBE_ZIP_OPS(ZK_PROBE_CASE)
 #undef ZK_PROBE_CASE
         default: return false;
     }

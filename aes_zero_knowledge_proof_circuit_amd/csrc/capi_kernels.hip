@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(64) k_cal_fqmul(CalStamp *st, zk::FpMsm<zk::Fq
 }
 __global__ void __launch_bounds__(64, 2) k_cal_hot_loop(CalStamp *st, zk::AccTE<zk::Fq377P> *sink, const zk::Niels28<zk::Fq377P> *__restrict__ tab, uint32_t mask, int iters) {
     using P = zk::Fq377P;
-    const uint64_t bias = zk::FpMsm<P>::hot_loop_bias();
+    const zk::FpMsm<P>::Seed seed = zk::FpMsm<P>::hot_loop_seed();
     uint32_t t = blockIdx.x * 64 + threadIdx.x, x = t * 2654435761u + 12345u;
     zk::AccTE<P> acc = zk::te_identity<P>();
     zk::Niels28<P> pt = zk::niels_load_signed<P>(tab + (x & mask), false);
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(64, 2) k_cal_hot_loop(CalStamp *st, zk::AccTE<
     for (int i = 0; i < iters; i++) {
         const uint32_t cur = x;
         x = x * 1664525u + 1013904223u;
-        zk::te_madd_hot<P>(acc, pt, cur >> 31, tab + ((x >> 8) & mask), x >> 31, bias);
+        zk::te_madd_hot<P>(acc, pt, cur >> 31, tab + ((x >> 8) & mask), x >> 31, seed);
     }
     const uint64_t c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0) { st[blockIdx.x].cyc = c1 - c0; st[blockIdx.x].rt = r1 - r0; }

@@ -7,15 +7,16 @@
 #include "arith_probe.cuh"
 
 // One kernel per operation: the operation is the template parameter, chosen on the host (a kernel holding every group law at once would spill).  One case per lane.
-// The hot loop's bias is taken at kernel entry, before any operand is loaded, as k_accumulate takes it.
+// The hot loop's bias and seed are taken at kernel entry, before any operand is loaded, as k_accumulate takes its seed.
 template <class O> __global__ void __launch_bounds__(64) k_arith_probe(const uint32_t *__restrict__ in, uint32_t n_cases, uint32_t *__restrict__ out) {
     const uint64_t bias = zk::FpMsm<zk::Fq377P>::hot_loop_bias();
+    const zk::FpMsm<zk::Fq377P>::Seed seed = zk::FpMsm<zk::Fq377P>::hot_loop_seed();
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
     if (c >= n_cases) return;
     uint32_t a[O::NIN], r[O::NOUT];
 #pragma unroll
     for (int i = 0; i < O::NIN; i++) a[i] = in[(size_t)c * O::NIN + i];
-    O::run(a, r, bias);
+    if constexpr (O::SEEDED) O::run_seeded(a, r, seed); else O::run(a, r, bias);
 #pragma unroll
     for (int i = 0; i < O::NOUT; i++) out[(size_t)c * O::NOUT + i] = r[i];
 }
@@ -50,7 +51,8 @@ extern "C" int zkaes_arith_probe(int op, const uint32_t *in, size_t n_cases, uin
         zk::capi_set_error("");
         if (!in || !out) throw std::invalid_argument("zkaes_arith_probe: null argument");
         if (n_cases == 0 || n_cases > zk::probe::MAX_CASES) throw std::invalid_argument("zkaes_arith_probe: n_cases must be in [1, 65536]");
-        if (!zk::probe::dispatch(op, [&](auto tag) { run_probe<typename decltype(tag)::type>(in, n_cases, out); })) throw std::invalid_argument("zkaes_arith_probe: unknown op " + std::to_string(op));
+        const auto run = [&](auto tag) { run_probe<typename decltype(tag)::type>(in, n_cases, out); };
+        if (!zk::probe::dispatch(op, run) && !zk::probe::dispatch_zip(op, run)) throw std::invalid_argument("zkaes_arith_probe: unknown op " + std::to_string(op));
         return 0;
     } catch (const std::exception &e) { zk::capi_set_error(e.what()); return 1; }
     catch (...) { zk::capi_set_error("unknown error"); return 1; }

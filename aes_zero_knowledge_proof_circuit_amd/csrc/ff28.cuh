@@ -166,8 +166,8 @@ struct Fp28 {
     // 27 stand-alone 64-bit adds (v_lshl_add_u64) per product, 14 row carries and 13 limb normalisations.
     // LOWER half (mul_low: columns 0..N-1, row-wise as above, restricted to the columns i + j < N): it leaves the N multipliers m_i and the carry out of column N - 1.
     // UPPER half (mul_high: columns N..2N-2, product scanning): a column's multiply-add chain STARTS from the carry of the column below -- v_mad_u64_u32 has a 64-bit
-    // addend slot, so joining the carry costs nothing and the 13 normalisation adds go away.  (The lower columns keep the row-wise order: seeded with the carry a row would
-    // cost the same shift, add of the bias and v_bitop3 it costs now.)  LLVM re-associates a late-defined addend to the END of a sum, so on the device every step of a chain
+    // addend slot, so joining the carry costs nothing and the 13 normalisation adds go away.  (mul_low keeps the row-wise order: on ITS bias, 2^28 - 1, a row seeded with the
+    // carry would cost the same shift, add of the bias and v_bitop3 it costs now; mul_low_zip below seeds the lower columns on the bias -1, where it does pay.)  LLVM re-associates a late-defined addend to the END of a sum, so on the device every step of a chain
     // is followed by an empty asm that pins the order; the host branch has none and adds the same terms in the same order.
     // Bound: a chain adds the non-negative terms of the row-wise form's column k and the carry that column was joined with, in another order; every partial sum is at most
     // that total, which is below 2^64 for every operand pair the callers document (normalized x lazy: < 2^63; te_madd_hot's lazy pairs: 181 x 2^56, te28.cuh).  Each
@@ -176,7 +176,8 @@ struct Fp28 {
     // (W = 1) gets an s_nop wherever the compiler finds no independent instruction; te_madd_hot therefore ZIPS the products of one level (W = 3, W = 4): the chains advance
     // in turn, the pins are volatile -- which holds them, and with them the steps, in source order -- and a scheduling barrier at the entry keeps the lower halves (28
     // column registers each) from sinking into the zip, where they would overlap the W x 13 live multipliers.  k_accumulate<EdwardsLaw>: 188 -> 97 v_lshl_add_u64,
-    // 3,495 -> 3,404 VALU, 7 s_nop in the loop, 165 registers (profiles/fq_product_carry_seed.md).
+    // 3,495 -> 3,404 VALU, 7 s_nop in the loop, 165 registers (profiles/fq_product_carry_seed.md); with the lower half zipped as well (mul_low_zip) 21 v_lshl_add_u64,
+    // 3,327 VALU, 23 s_nop, 166 registers (profiles/fq_product_lower_seed.md).
     // operator*, fma2 and sqr stay row-wise: their callers (bucket reduction, class sums, conversions) run them one at a time, the chains fill with s_nop (k_reduce_l1_pair:
     // 1,484; k_class_partials: 1,160) and with the upper half carry-seeded k_class_partials measured 12 % and k_quad_sum 5 % SLOWER, the reduction kernels no faster (same file).
     struct Low { uint32_t m[N]; uint64_t carry; };
@@ -205,6 +206,70 @@ struct Fp28 {
             if (i + 1 < N) t[i + 1] += u >> 28; else lo.carry = u >> 28;
         }
         return lo;
+    }
+    // ---- the lower half as product scanning too, on a bias of -1 (te_madd_hot's seven products; p = 1 (mod 2^28) only).  A column is held as u' = t - 1, t its true value
+    // with the carry from below:  ~u' mod 2^28 = -t mod 2^28 is the same multiplier m as above, and the carry into the next column, ceil(t / 2^28) = floor((t - 1) / 2^28) + 1,
+    // is (u' >> 28, ARITHMETIC) + 1 -- so the next column's own "- 1" cancels the "+ 1" and the shift result IS the seed of the next column's multiply-add chain: one
+    // v_bitop3_b32 and one v_ashrrev_i64 per column, no 64-bit add (the bias 2^28 - 1 of mul_low needs its "+ 2^28 - 1" again in every column, which rides free on a chain's
+    // first addend only while the carry is joined by a separate add; -1 is the only bias that reproduces itself).  t = 0 (te_identity's all-zero x and t) gives u' = -1,
+    // m = 0 and the seed -1 = the true carry 0, less one.  Column k's chain: the seed, the k + 1 terms a_(k-i) b_i, the k terms m_i p_(k-i) with m_(k-1) p_1 last.
+    // Range: the arithmetic shift needs u' < 2^63 = 128 x 2^56.  With X the product of the two operands' limb bounds in units of 2^28, column k holds less than
+    // ((k + 1) X + k + 1) x 2^56 (the a b terms, the m p terms, a carry below 2^36); signed_columns(X) is the number of columns, from column 0 up, for which that stays at or
+    // below 128 -- all 14 for X <= 8, nine for X = 12.  The columns above switch to mul_low's unsigned form: the first of them adds 2^28 to its seed (from the bias -1 to
+    // the bias 2^28 - 1), the later ones are seeded with (u >> 28, logical) + 2^28 - 1, and the carry out of column 13 is then the true carry; a product that stays signed
+    // to the end adds 1 once, where it hands its carry to mul_high.  Both bounds are static assertions on X: wider operands do not compile.
+    // `seed` must hold -1 in a register pair the compiler cannot see through, defined before the operands (hot_loop_seed() at kernel entry), for the reason `bias` must.
+    // The same m_i enter the same columns as in mul_low: lo is the same, and with it the product, limb for limb.  Chains of dependent v_mad_u64_u32 again: the W products
+    // are zipped, pins volatile, a scheduling barrier at the entry (see mul_high).
+    struct Seed { uint64_t v; };                                   // a type of its own: the row-wise bias 2^28 - 1 must not be passed for it
+    ZK_HD static constexpr int signed_columns(int x) { int k = 0; while (k < N && (k + 1) * x + k + 1 <= 128) k++; return k; }
+    template <int... X>
+    ZK_HD static void mul_low_zip(const Fp28 *const (&a)[sizeof...(X)], const Fp28 *const (&b)[sizeof...(X)], Seed seed, Low (&lo)[sizeof...(X)]) {
+        static_assert(mod28(0) == 1u && PINV == MASK, "written for p = 1 (mod 2^28)");
+        constexpr int W = sizeof...(X);
+        constexpr int SW[W] = {signed_columns(X)...};
+        static_assert(((X >= 1 && signed_columns(X) >= 1 && N * X + N <= 256) && ...), "operand limb bounds too wide for the 64-bit columns");
+        uint64_t acc[W];
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (W > 1) __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+        for (int w = 0; w < W; w++) acc[w] = seed.v;
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+#pragma unroll
+            for (int i = 0; i <= k; i++) {
+#pragma unroll
+                for (int w = 0; w < W; w++) { acc[w] += (uint64_t)a[w]->l[k - i] * b[w]->l[i]; pin<(W > 1)>(acc[w]); }
+            }
+#pragma unroll
+            for (int i = 0; i < k; i++) {
+#pragma unroll
+                for (int w = 0; w < W; w++) { acc[w] += (uint64_t)lo[w].m[i] * mod28(k - i); pin<(W > 1)>(acc[w]); }
+            }
+#pragma unroll
+            for (int w = 0; w < W; w++) {
+                const uint64_t u = acc[w];
+                lo[w].m[k] = ~(uint32_t)u & MASK;
+                uint64_t next;
+                if (k < SW[w]) {                                   // u = t - 1: the seed of the next column, which is the true carry less one
+                    next = (uint64_t)((int64_t)u >> 28);
+                    if (k + 1 == N) next += 1;
+                    else if (k + 1 == SW[w]) next += (uint64_t)MASK + 1;
+                } else {                                           // u = t + 2^28 - 1: the true carry
+                    next = u >> 28;
+                    if (k + 1 < N) next += MASK;
+                }
+                if (k + 1 < N) acc[w] = next; else lo[w].carry = next;
+            }
+        }
+    }
+    ZK_HD static Seed hot_loop_seed() {
+        uint64_t v = ~(uint64_t)0;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(v));
+#endif
+        return Seed{v};
     }
     // the upper halves of the W independent products a[w] b[w] whose lower halves are lo[w], zipped step by step; r[w] must not alias an operand
     template <int W>

@@ -292,8 +292,8 @@ __global__ void __launch_bounds__(64, 2) k_accumulate(const typename Law::Base *
                                                        uint32_t *__restrict__ deferred, uint32_t deferred_cap, uint32_t *__restrict__ deferred_count) {
     using P = typename Law::Params;
     using G = FpMsm<P>;
-    [[maybe_unused]] uint64_t bias = 0;
-    if constexpr (Law::edwards) bias = FpMsm<P>::hot_loop_bias();           // before anything else: see ff28.cuh mul_biased
+    [[maybe_unused]] typename G::Seed seed{0};
+    if constexpr (Law::edwards) seed = G::hot_loop_seed();                  // before anything else: see ff28.cuh mul_low_zip
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nbuckets_total) return;
     uint32_t k = order[t];
@@ -311,7 +311,7 @@ __global__ void __launch_bounds__(64, 2) k_accumulate(const typename Law::Base *
                 if (i + 1 < e) idx = vals[i + 1];
                 const Niels28<P> *next = bases + (idx & VAL_INDEX);        // the last iteration re-reads its own point: no branch around the load
                 if (cur & VAL_SKIP) { p = niels_load_signed<P>(next, idx >> 31); continue; }
-                te_madd_hot<P>(acc, p, cur >> 31, next, idx >> 31, bias);
+                te_madd_hot<P>(acc, p, cur >> 31, next, idx >> 31, seed);
             }
         }
         buckets[k] = acc;

@@ -77,24 +77,33 @@ ZK_HD Niels28<P> niels_load_signed(const Niels28<P> *rec, bool neg) {
 // The hot loop's addition: acc += (neg ? -n : n), where n was loaded with niels_load_signed(.., neg).  A negative digit changes the sign of C, which swaps F = D - C and G = D + C
 // (28 per-limb selects, no negated copy of the point).  `next` is the record of the lane's NEXT addition, loaded (with the sign of ITS digit, next_neg) into n as soon as the three
 // products that read n are done: the gather flies under the remaining four products and lands in the registers the current point just vacated -- no second register set, no copies
-// at the loop's back edge.  `bias` = FpMsm<P>::hot_loop_bias() taken at kernel entry (ff28.cuh mul_biased: 14 fewer 64-bit adds per product).
+// at the loop's back edge.  `seed` = FpMsm<P>::hot_loop_seed() taken at kernel entry: the opaque -1 every product's column 0 starts from (ff28.cuh mul_low_zip).
 // All four factors of the second level are lazy.  Limb bounds in units of 2^28: E = B + 2p' - A < 3, H = B + A < 2, D = 2 Z1 < 2, U = D + 2p' - C < 4, V = D + C < 3
 // (2p' = kp_spread<2> < 2 per limb).  The widest products, E U and U V, put 14 x 12 x 2^56 into a column, the reduction 13 x 2^56 more: 181 x 2^56 < 2^64
 // (tests/test_gpu_arith.py multiplies at exactly those bounds on the device -- mul_biased with the opaque bias, and te_madd_hot itself in chains of seven -- against the
 // big-integer model of tests/arith_model.py; tests/test_ff28_host.py and tests/test_arith_model.py do the same with the host branch).
-// The products of a level are independent: their lower halves run one after the other, their upper halves -- carry-seeded multiply-add chains, ff28.cuh mul_high -- are
-// ZIPPED, three chains wide for A, B, C and four wide for the second level, so that no v_mad_u64_u32 follows the one it depends on (7 s_nop in k_accumulate, 165 registers:
-// the width was chosen with the disassembly open, profiles/fq_product_carry_seed.md; tests/test_gpu_product_columns.py and tests/ff28_columns_host_check.cpp compare the
-// zipped form limb for limb with big-integer arithmetic, every limb of E, H, U, V at its bound).
+// The products of a level are independent: both halves of a product are carry-seeded multiply-add chains (ff28.cuh mul_low_zip, mul_high) and both are ZIPPED, three
+// chains wide for A, B, C and four wide for the second level, so that no v_mad_u64_u32 follows the one it depends on (23 s_nop in k_accumulate, 166 registers: the widths
+// were chosen with the disassembly open, profiles/fq_product_carry_seed.md, fq_product_lower_seed.md; tests/test_gpu_product_columns.py, tests/test_gpu_lower_seed.py and
+// the two host checks tests/ff28_columns_host_check.cpp, tests/ff28_lower_seed_host_check.cpp compare the zipped forms limb for limb with integer arithmetic, every limb
+// of E, H, U, V at its bound).
+// The lower halves hold a column as t - 1 in a SIGNED 64-bit register while it stays below 2^63.  X = product of the two operands' limb bounds (units of 2^28), the template
+// arguments of mul_low_zip; column k < ((k + 1) X + k + 1) x 2^56, signed while that is <= 128:
+//      A = (Y1 - X1 + 3p') ymx   5 x 1 = 5     all 14 columns signed            E F   3 x 4 = 12   columns 0..8 signed (117), 9..13 unsigned (182 < 256)
+//      B = (Y1 + X1) ypx         2 x 1 = 2     all 14                           G H   4 x 2 = 8    all 14 (126)
+//      C = T1 td                 1 x 1 = 1     all 14                           E H   3 x 2 = 6    all 14
+//                                                                               F G   4 x 3 = 12   columns 0..8 signed, 9..13 unsigned
+// (F and G are per-limb selects of U < 4 and V < 3: statically 4 each against E and H, U V against each other.)  Wider operands fail mul_low_zip's static assertions.
 template <class P>
-ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *next, bool next_neg, uint64_t bias) {
+ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *next, bool next_neg, typename FpMsm<P>::Seed seed) {
     using G = FpMsm<P>;
     using Low = typename G::Low;
     G A, B, C;
     {
         const G ymx = a.y.template sub_lazy<3>(a.x), ypx = a.y.add_lazy(a.x);
-        const Low lo[3] = {G::mul_low(ymx, n.ymx, bias), G::mul_low(ypx, n.ypx, bias), G::mul_low(a.t, n.td, bias)};
         const G *const pa[3] = {&ymx, &ypx, &a.t}, *const pb[3] = {&n.ymx, &n.ypx, &n.td};
+        Low lo[3];
+        G::template mul_low_zip<5, 2, 1>(pa, pb, seed, lo);
         G *const pr[3] = {&A, &B, &C};
         G::template mul_high<3>(pa, pb, lo, pr);
     }
@@ -113,11 +122,17 @@ ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *n
 #pragma unroll
     for (int i = 0; i < G::N; i++) { F.l[i] = neg ? V.l[i] : U.l[i]; Gg.l[i] = neg ? U.l[i] : V.l[i]; }
     {
-        const Low lo[4] = {G::mul_low(E, F, bias), G::mul_low(Gg, H, bias), G::mul_low(E, H, bias), G::mul_low(F, Gg, bias)};
         const G *const pa[4] = {&E, &Gg, &E, &F}, *const pb[4] = {&F, &H, &H, &Gg};
+        Low lo[4];
+        G::template mul_low_zip<12, 8, 6, 12>(pa, pb, seed, lo);
         G *const pr[4] = {&a.x, &a.y, &a.t, &a.z};
         G::template mul_high<4>(pa, pb, lo, pr);
     }
+}
+// the signature of the row-wise lower halves, for callers that hold hot_loop_bias(): the same addition, the seed taken here (a kernel's loop takes it at kernel entry instead)
+template <class P>
+ZK_HD void te_madd_hot(AccTE<P> &a, Niels28<P> &n, bool neg, const Niels28<P> *next, bool next_neg, uint64_t) {
+    te_madd_hot<P>(a, n, neg, next, next_neg, FpMsm<P>::hot_loop_seed());
 }
 // a += b, unified (add-2008-hwcd-3): nine products.  te_add_inline is the body for the one kernel that wants two additions of a step in ONE instruction stream
 // (k_reduce_l1: a lone wave per SIMD issues dependent multiply-adds at half rate; the two independent additions of its running sums interleave); te_add is the call

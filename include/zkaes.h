@@ -653,7 +653,7 @@ int zkaes_index_evals(const uint32_t *ci, const uint32_t *ri, const int64_t *ca,
                       uint8_t *va, uint8_t *vb, uint8_t *vc, uint8_t *uinv_or_null);
 /* TEST-ONLY: ONE field or curve operation of csrc/ff.cuh, ff28.cuh, ff29.cuh, ec28.cuh, te28.cuh per launch, on raw limbs exactly as the operation sees them (no conversion
  * in or out, so lazy and non-canonical operands can be passed).  op: an id of csrc/arith_probe.cuh ZK_PROBE_OPS (named by api.py ARITH_OPS, which also holds the words per
- * case); in: n_cases x input words, out: n_cases x output words; 1 <= n_cases <= 65536.  tests/test_gpu_arith.py compares it with the big-integer model. */
+ * case) or of ZK_PROBE_ZIP_OPS (api.py ARITH_ZIP_OPS: te_madd_hot's zipped products); in: n_cases x input words, out: n_cases x output words; 1 <= n_cases <= 65536.  tests/test_gpu_arith.py compares it with the big-integer model. */
 int zkaes_arith_probe(int op, const uint32_t *in, size_t n_cases, uint32_t *out);
 
 /* ---- MSM ---- */
