@@ -1915,6 +1915,33 @@ def msm_second_bases(bases, scalars, off, shift, window_bits=0):
     return [(out.raw[96 * i:96 * i + 96], bool(inf[i])) for i in range(2)]
 
 
+STEP_WINDOW, STEP_TABLE, STEP_SECOND, STEP_CLASS, STEP_REFINISH = 0, 1, 2, 3, 4
+MSM_SEQ_MAX_STEPS, MSM_SEQ_ERR_BYTES = 32, 128
+
+
+class MsmStep(C.Structure):
+    """zkaes_msm_step (include/zkaes.h): lengths and offsets in elements of the bases, the scalars and the class values of the call"""
+    _fields_ = [("kind", C.c_uint32), ("edwards", C.c_uint32), ("window_bits", C.c_uint32), ("reserved", C.c_uint32),
+                ("n1", C.c_uint64), ("off1", C.c_uint64), ("scal1", C.c_uint64), ("n2", C.c_uint64), ("off2", C.c_uint64), ("scal2", C.c_uint64), ("shift", C.c_uint64)]
+
+
+def msm_sequence(bases, scalars, class_vals, steps, poison=False):
+    """`steps` (MsmStep or dicts of its fields) in order on ONE workspace and stream -> per step a dict: status (0, or 1 for a step the library refused: the sequence
+    went on), error (its message), accepted (False: a class sum declined, or the step was refused), points [(xy, is_inf), (xy, is_inf)] (the second one: STEP_SECOND)"""
+    st = (MsmStep * max(len(steps), 1))(*[s if isinstance(s, MsmStep) else MsmStep(**s) for s in steps])
+    v = np.ascontiguousarray(class_vals, dtype=np.int8)
+    k = max(len(steps), 1)
+    out, inf, ok, status, err = C.create_string_buffer(192 * k), (C.c_int * (2 * k))(), (C.c_int * k)(), (C.c_int * k)(), C.create_string_buffer(MSM_SEQ_ERR_BYTES * k)
+    _check(lib().zkaes_msm_sequence(_host(bases), C.c_size_t(_nbytes(bases) // 96), bytes(scalars), C.c_size_t(len(scalars) // 32), v.ctypes.data_as(C.c_void_p), C.c_size_t(v.size),
+                                    st, C.c_size_t(len(steps)), 1 if poison else 0, out, inf, ok, status, err))
+    res = []
+    for i in range(len(steps)):
+        msg = err.raw[MSM_SEQ_ERR_BYTES * i:MSM_SEQ_ERR_BYTES * (i + 1)].split(b"\0")[0].decode()
+        res.append({"status": int(status[i]), "error": msg, "accepted": bool(ok[i]),
+                    "points": [(out.raw[192 * i + 96 * j:192 * i + 96 * j + 96], bool(inf[2 * i + j])) for j in range(2)]})
+    return res
+
+
 # ---- TEST SURFACE, not product API: the prover's R1CS and randomness kernels, one entry per kernel group (include/zkaes.h; tests/test_gpu_r1cs.py).  Field elements are
 # 32-byte Montgomery limbs; a matrix is a CSR triple (rowptr uint32[rows + 1], col uint32[nnz], coeff int64[nnz]).  Arguments are passed on as they are: the C side refuses.
 def _csr(rowptr, col, coeff):

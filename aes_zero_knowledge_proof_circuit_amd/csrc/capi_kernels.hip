@@ -1,5 +1,6 @@
 // csrc/capi_kernels.hip -- kernel-level C entry points (parity tests + roofline measurement) and device selection
 #include "../../include/zkaes.h"
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -347,6 +348,153 @@ void run_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *sc
     for (int i = 0; i < 2; i++) give_affine(r[i].to_affine(), out_xy + 96 * i, out_inf + i);
 }
 
+// ---- the same forms as a SEQUENCE on one workspace and one stream (include/zkaes.h zkaes_msm_sequence; tests/test_gpu_msm_workspace.py): what a prover context and the batch
+// verifier do with theirs, and what every runner above, with a workspace of its own per call, cannot show.
+constexpr size_t MSM_SEQ_MAX_TABLES = 8;              // distinct window bits per law and call
+// the bases in one law's forms: the plain records, and window tables of stride nbases per distinct window bits
+template <bool EDWARDS> struct SeqForms {
+    DevPtr<MsmBase<EDWARDS>> plain;
+    std::vector<std::pair<int, DevPtr<MsmBase<EDWARDS>>>> tables;
+    bool want_plain = false;
+    std::vector<int> want_bits;
+    void want(int c) {
+        if (!c) want_plain = true;
+        else if (std::find(want_bits.begin(), want_bits.end(), c) == want_bits.end()) want_bits.push_back(c);
+    }
+    void build(const uint8_t *bases, size_t nbases, zk::gpu::stream_t s) {
+        if (want_plain) {
+            DevPtr<zk::Affine<MFq>> db = upload_points(bases, nbases, nbases, s);
+            plain = law_bases<EDWARDS>(db, nbases, s);
+        }
+        for (int c : want_bits) tables.emplace_back(c, law_tables<EDWARDS>(bases, nbases, c, s));
+    }
+    const MsmBase<EDWARDS> *get(int c) const {
+        if (!c) return plain.get();
+        for (auto &t : tables) if (t.first == c) return t.second.get();
+        return nullptr;
+    }
+};
+struct SeqBases {
+    SeqForms<true> te;
+    SeqForms<false> we;
+    void want(bool edwards, int c) { if (edwards) te.want(c); else we.want(c); }
+    // msm_finish over the form (law, c), every base index moved up by `at`
+    zk::XYZZ<MFq> finish(zk::gpu::MsmWorkspace *ws, bool edwards, int c, size_t at, zk::gpu::stream_t s) const {
+        if (edwards) { const zk::Niels28<MP> *b = te.get(c); need(b != nullptr, "zkaes_msm_sequence", "no base form for this step"); return zk::gpu::msm_finish<MC>(ws, b + at, s); }
+        const zk::Affine28<MP> *b = we.get(c);
+        need(b != nullptr, "zkaes_msm_sequence", "no base form for this step");
+        return zk::gpu::msm_finish<MC>(ws, b + at, s);
+    }
+};
+// what the last preparing step left in the workspace: window bits (0: per-window), the index its base pointer started at, one past the highest index it names from there
+struct SeqPrepared { bool live = false; int c = 0; size_t origin = 0, extent = 0; };
+bool seq_prepares(uint32_t kind) { return kind == ZKAES_STEP_WINDOW || kind == ZKAES_STEP_TABLE || kind == ZKAES_STEP_SECOND; }
+// everything that can be judged without the device, before anything is allocated; leaves the forms the steps need in `forms`
+void check_msm_sequence(const zkaes_msm_step *steps, size_t nsteps, size_t nbases, size_t nscalars, size_t nvals, SeqBases &forms) {
+    const char *who = "zkaes_msm_sequence";
+    int prepared_c = -1;
+    for (size_t i = 0; i < nsteps; i++) {
+        const zkaes_msm_step &st = steps[i];
+        need(st.kind <= ZKAES_STEP_REFINISH && st.reserved == 0, who, "unknown step kind");
+        need(st.off1 <= MSM_FORM_MAX && st.off2 <= MSM_FORM_MAX && st.shift <= MSM_FORM_MAX && st.n1 <= MSM_FORM_MAX && st.n2 <= MSM_FORM_MAX, who, "step lengths and offsets must not exceed 2^26");
+        const bool edwards = st.edwards != 0;
+        const int c = (int)st.window_bits;
+        if (st.kind == ZKAES_STEP_CLASS) {
+            need(st.scal1 <= nvals && st.n1 <= nvals - st.scal1, who, "value range outside the class values");
+            forms.want(edwards, 0);
+        } else if (st.kind == ZKAES_STEP_REFINISH) {
+            need(prepared_c >= 0, who, "a refinish step needs a preparing step before it");
+            forms.want(edwards, prepared_c);
+        } else {
+            need(st.scal1 <= nscalars && st.n1 <= nscalars - st.scal1, who, "scalar range outside the scalars");
+            const bool pair = st.kind != ZKAES_STEP_SECOND && st.n2;
+            need(!pair || (st.scal2 <= nscalars && st.n2 <= nscalars - st.scal2), who, "scalar range outside the scalars");
+            need(st.kind != ZKAES_STEP_SECOND || edwards, who, "two base arrays per prepared state need the Edwards law");
+            const bool table = st.kind == ZKAES_STEP_TABLE || (st.kind == ZKAES_STEP_SECOND && c != 0);
+            if (table) check_table_bits(c, nbases, who);
+            prepared_c = table ? c : 0;
+            forms.want(edwards, prepared_c);
+        }
+    }
+    need(forms.te.want_bits.size() <= MSM_SEQ_MAX_TABLES && forms.we.want_bits.size() <= MSM_SEQ_MAX_TABLES, who, "at most 8 distinct window bits per law");
+}
+void run_msm_sequence(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t nscalars, const int8_t *vals, size_t nvals, const zkaes_msm_step *steps, size_t nsteps, bool poison,
+                      SeqBases &forms, uint8_t *out_xy, int *out_inf, int *out_ok, int *out_status, char *out_err) {
+    const char *who = "zkaes_msm_sequence";
+    zk::gpu::require_device();
+    StreamGuard s;
+    forms.te.build(bases, nbases, s);
+    forms.we.build(bases, nbases, s);
+    DevPtr<MFr> ds = upload_scalars(scalars, nscalars, s);
+    DevPtr<int8_t> dv(nvals ? nvals : 1);
+    zk::gpu::h2d(dv, vals, nvals, s);
+    zk::gpu::sync(s);
+    WorkspaceGuard ws;                   // ONE workspace for every step: nothing below may make another
+    SeqPrepared prep;
+    for (size_t i = 0; i < nsteps; i++) {
+        const zkaes_msm_step &st = steps[i];
+        uint8_t *xy = out_xy + 192 * i;
+        int *inf = out_inf + 2 * i;
+        memset(xy, 0, 192); inf[0] = inf[1] = 0; out_ok[i] = 0; out_status[i] = 0; out_err[ZKAES_MSM_SEQ_ERR_BYTES * i] = 0;
+        const bool edwards = st.edwards != 0;
+        const int c = (int)st.window_bits;
+        const SeqPrepared before = prep;
+        prep.live = false;               // (set again by a step that leaves a prepared state behind)
+        try {
+            if (poison && i) zk::gpu::msm_workspace_poison_accumulators(ws, s);
+            const MFr *s1 = seq_prepares(st.kind) ? ds.get() + st.scal1 : nullptr, *s2 = s1 && st.kind != ZKAES_STEP_SECOND && st.n2 ? ds.get() + st.scal2 : nullptr;
+            if (st.kind == ZKAES_STEP_WINDOW) {
+                const size_t off2 = st.n2 ? st.off2 : 0;
+                need(st.off1 <= nbases && st.n1 <= nbases - st.off1 && off2 <= nbases - st.off1 && st.n2 <= nbases - st.off1 - off2, who, "range exceeds the bases");
+                zk::gpu::msm_prepare<MC>(ws, s1, st.n1, s2, st.n2, off2, s);
+                give_affine(forms.finish(ws, edwards, 0, st.off1, s).to_affine(), xy, inf);
+                prep = SeqPrepared{true, 0, (size_t)st.off1, std::max((size_t)st.n1, (size_t)(off2 + st.n2))};
+            } else if (st.kind == ZKAES_STEP_TABLE) {       // (its ranges are msm_prepare_table's to judge: "msm_table: range exceeds the table")
+                zk::gpu::msm_prepare_table<MC>(ws, s1, st.n1, st.off1, s2, st.n2, st.n2 ? st.off2 : 0, c, nbases, s);
+                give_affine(forms.finish(ws, edwards, c, 0, s).to_affine(), xy, inf);
+                prep = SeqPrepared{true, c, 0, std::max((size_t)(st.n1 ? st.off1 + st.n1 : 0), (size_t)(st.n2 ? st.off2 + st.n2 : 0))};
+            } else if (st.kind == ZKAES_STEP_SECOND) {
+                const zk::Niels28<MP> *b = forms.te.get(c);
+                need(b != nullptr, who, "no base form for this step");
+                if (st.off1 > nbases || st.shift > nbases - st.off1 || st.n1 > nbases - st.off1 - st.shift)
+                    throw std::invalid_argument(c ? "msm_table: range exceeds the table" : "zkaes_msm_sequence: range exceeds the bases");
+                zk::XYZZ<MFq> r[2];
+                if (c == 0) {
+                    zk::gpu::msm_prepare<MC>(ws, s1, st.n1, nullptr, 0, 0, s);
+                    zk::gpu::msm_finish2<MC>(ws, b + st.off1, b + st.off1 + st.shift, r, s);
+                    prep = SeqPrepared{true, 0, (size_t)st.off1, (size_t)st.n1};
+                } else {
+                    zk::gpu::msm_prepare_table<MC>(ws, s1, st.n1, st.off1, nullptr, 0, 0, c, nbases, s);
+                    zk::gpu::msm_finish2<MC>(ws, b, b + st.shift, r, s);
+                    prep = SeqPrepared{true, c, 0, (size_t)(st.n1 ? st.off1 + st.n1 : 0)};
+                }
+                for (int k = 0; k < 2; k++) give_affine(r[k].to_affine(), xy + 96 * k, inf + k);
+            } else if (st.kind == ZKAES_STEP_CLASS) {
+                need(st.off1 <= nbases && st.n1 <= nbases - st.off1, who, "range exceeds the bases");
+                zk::XYZZ<MFq> r;
+                const int8_t *v = dv.get() + st.scal1;
+                const bool ok = edwards ? zk::gpu::class_sum<MC>(ws, forms.te.get(0) + st.off1, v, st.n1, &r, s) : zk::gpu::class_sum<MC>(ws, forms.we.get(0) + st.off1, v, st.n1, &r, s);
+                if (ok) give_affine(r.to_affine(), xy, inf);
+                out_ok[i] = ok ? 1 : 0;
+                continue;
+            } else {                                        // ZKAES_STEP_REFINISH
+                need(before.live, who, "no prepared state to finish again: the step before prepared none");
+                need(before.origin + before.extent + st.shift <= nbases, who, "range exceeds the bases");
+                give_affine(forms.finish(ws, edwards, before.c, before.origin + st.shift, s).to_affine(), xy, inf);
+                prep = before;
+            }
+            out_ok[i] = 1;
+        } catch (const std::exception &e) {
+            // a refusal is recorded and the sequence goes on; after an error of the device itself nothing more is launched
+            if (!strncmp(e.what(), "HIP error", 9)) throw;
+            prep.live = false;
+            memset(xy, 0, 192); inf[0] = inf[1] = 0;
+            out_status[i] = 1;
+            snprintf(out_err + ZKAES_MSM_SEQ_ERR_BYTES * i, ZKAES_MSM_SEQ_ERR_BYTES, "%s", e.what());
+        }
+    }
+}
+
 // ---- the prover's R1CS and randomness kernels (kernels_witness.hip, kernels_poly.hip), which run only inside whole proofs otherwise (tests/test_gpu_r1cs.py).  Every
 // output and scratch buffer is filled with 0xAB bytes on the device before the call, so that a slot a kernel fails to write shows up as a mismatch.
 template <class T> DevPtr<T> poisoned(size_t count, zk::gpu::stream_t s) {
@@ -456,6 +604,19 @@ int zkaes_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *s
         if (window_bits) check_table_bits(window_bits, nbases, who);
         if (off > nbases || shift > nbases - off || n > nbases - off - shift) throw std::invalid_argument(window_bits ? "msm_table: range exceeds the table" : "zkaes_msm_second_bases: range exceeds the bases");
         run_msm_second_bases(bases, nbases, scalars, n, off, shift, window_bits, out_xy, out_inf);
+    });
+}
+int zkaes_msm_sequence(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t nscalars, const int8_t *class_vals, size_t nvals, const zkaes_msm_step *steps, size_t nsteps,
+                       int poison, uint8_t *out_xy, int *out_inf, int *out_accepted, int *out_status, char *out_errors) {
+    return guardk([&] {
+        const char *who = "zkaes_msm_sequence";
+        need(bases && steps && out_xy && out_inf && out_accepted && out_status && out_errors && (scalars || !nscalars) && (class_vals || !nvals), who, "null argument");
+        need(nbases >= 1 && nbases <= MSM_FORM_MAX, who, "nbases out of range");
+        need(nscalars <= MSM_FORM_MAX && nvals <= MSM_FORM_MAX, who, "too many scalars or class values");
+        need(nsteps >= 1 && nsteps <= ZKAES_MSM_SEQ_MAX_STEPS, who, "1..32 steps");
+        SeqBases forms;
+        check_msm_sequence(steps, nsteps, nbases, nscalars, nvals, forms);
+        run_msm_sequence(bases, nbases, scalars, nscalars, class_vals, nvals, steps, nsteps, poison != 0, forms, out_xy, out_inf, out_accepted, out_status, out_errors);
     });
 }
 int zkaes_msm_sharded_plan(int curve_id, size_t n_total, int *window_bits, int *n_windows, size_t *bytes_per_rank) {

@@ -135,6 +135,11 @@ struct MsmWorkspace;
 MsmWorkspace *msm_workspace_create();
 void msm_workspace_destroy(MsmWorkspace *ws);
 using WorkspaceGuard = Handle<MsmWorkspace *, msm_workspace_create, msm_workspace_destroy>;
+// TEST HOOK (zkaes_msm_sequence): fills the workspace's ACCUMULATOR buffers -- the buckets, both first-level sums, the reduction's partials and the overflow partials, as far
+// as they are allocated -- with 0xAB bytes on the stream, so that a slot an MSM reads without having written it gives a wrong sum.  The armed words (ctrl, deferred_count)
+// and every index-bearing buffer (pairs, ranges, order, overflow list, partition scratch) are left as they are: their state between MSMs is what such a test is about,
+// and a byte pattern in an index would turn a stale read into a wild address.
+void msm_workspace_poison_accumulators(MsmWorkspace *ws, stream_t s);
 // Bases are consumed in the reduced-radix form (Affine28, ff28.cuh): convert once with convert_bases (the SRS at key synthesis).
 template <class Curve> void convert_bases(Affine28<typename Curve::FqP> *dst, const Affine<typename Curve::Fq> *src, size_t n, stream_t s);
 template <class Curve>

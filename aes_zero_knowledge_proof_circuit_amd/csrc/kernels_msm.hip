@@ -808,6 +808,11 @@ static void ensure_scratch(MsmWorkspace &S, size_t pairs, size_t buckets, size_t
 }
 MsmWorkspace *msm_workspace_create() { return new MsmWorkspace(); }
 void msm_workspace_destroy(MsmWorkspace *w) { delete w; }
+void msm_workspace_poison_accumulators(MsmWorkspace *ws, stream_t s_) {        // (test hook: gpu.hpp)
+    if (!ws) throw GpuError("msm: null workspace");
+    for (const DevPtr<void> *b : {&ws->buckets, &ws->seg_s, &ws->seg_w, &ws->partial, &ws->ovf_partial})
+        if (b->p) HIP_CHECK(hipMemsetAsync(b->p, 0xAB, b->n, (hipStream_t)s_));
+}
 
 // size-balanced visiting order of the buckets + the overflow list: three small launches, no memset, no generic sort (k_order_* above).  The same path serves lone calls
 // and multi-proof calls: positions are deterministic (buckets of one size keep the order of their index ranges), which the generic stable sort used to provide at ~16 launches.

@@ -595,6 +595,45 @@ int zkaes_msm_table_pair(const uint8_t *bases, size_t stride, const uint8_t *sca
  * bases[off + shift + i]; off + shift + n <= nbases.  window_bits = 0: per-window buckets (sequential when the two sets of window sums exceed one reduction's 64),
  * > 0: window tables of stride nbases.  out_xy: 2 x 96 B, out_inf: 2 flags */
 int zkaes_msm_second_bases(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t n, size_t off, size_t shift, int window_bits, uint8_t *out_xy, int *out_inf);
+/* ---- a SEQUENCE of those forms on ONE workspace and ONE stream, as a prover context and the batch verifier run them (tests/test_gpu_msm_workspace.py): TEST SURFACE.
+ * The contract under test is "any MSM form after any other on one workspace": the workspace keeps its armed words (the overflow list's counter, length and segment total,
+ * the class-sum flag word, the tail kernel's ticket and the deferred count) and every index-bearing buffer of the MSM before (pairs, bucket ranges, visiting order, overflow
+ * list, partition scratch) from step to step, and only ever grows.  bases: nbases standard affine points, uploaded once and converted, before the first step, to the forms
+ * the steps need (Affine28 / Niels28 records, window tables of stride nbases per distinct window_bits and law).  scalars: nscalars Montgomery Fr; class_vals: nvals int8.
+ * A step names its inputs by element offsets into those three arrays:
+ *   ZKAES_STEP_WINDOW    msm_prepare + msm_finish on the bases from off1 on: sum_i scalars[scal1 + i] bases[off1 + i] + sum_j scalars[scal2 + j] bases[off1 + off2 + j]
+ *                        (i < n1, j < n2; off2 = msm_prepare's val_off2; n2 = 0: one vector)
+ *   ZKAES_STEP_TABLE     msm_prepare_table(window_bits, stride = nbases) + msm_finish: sum_i scalars[scal1 + i] bases[off1 + i] + sum_j scalars[scal2 + j] bases[off2 + j]
+ *   ZKAES_STEP_SECOND    one prepared state, msm_finish2 (Edwards law only): point 0 = sum_i scalars[scal1 + i] bases[off1 + i], point 1 the same over
+ *                        bases[off1 + shift + i]; window_bits = 0: per-window buckets, > 0: window tables
+ *   ZKAES_STEP_CLASS     class_sum: sum_i class_vals[scal1 + i] bases[off1 + i], i < n1; accepted = 0 (point zeroed) when class_sum declines
+ *   ZKAES_STEP_REFINISH  msm_finish AGAIN on the state the step before prepared (a WINDOW, TABLE, SECOND or REFINISH step that succeeded), every base index moved up by
+ *                        `shift`: the sum of that step's scalars over bases[index + shift]
+ * edwards selects the law of the step's accumulation (the prepared state itself belongs to neither).  poison != 0: before every step but the first the workspace's
+ * ACCUMULATOR buffers (buckets, both first-level sums, the reduction's partials, the overflow partials) are filled with 0xAB bytes on the stream; the armed words and the
+ * index-bearing buffers keep what the step before left, which is the state under test.
+ * Refused before anything is allocated (non-zero return, zkaes_last_error): null pointers, nbases or nsteps out of range (1 .. ZKAES_MSM_SEQ_MAX_STEPS steps), an unknown
+ * kind, a scalar or value range outside its array, offsets above 2^26, window bits outside [2, 22] (or more than 8 distinct ones per law), a SECOND step on the Weierstrass
+ * law, a REFINISH with no preparing step before it.  Whether a step's BASE range fits is judged when the step runs, as the single-form entry points above and
+ * msm_prepare_table judge it: such a step -- like any other the library refuses without touching the device -- gets status 1 and its message (nul-terminated, at most
+ * ZKAES_MSM_SEQ_ERR_BYTES - 1 characters) in out_errors, zeroed points, and the sequence GOES ON with the next step.  A HIP error ends the call.
+ * Per step i: out_xy[192 i ..] two points (the second one only for SECOND), out_inf[2 i ..], out_accepted[i] (1 unless a class sum was declined or the step refused),
+ * out_status[i], out_errors[ZKAES_MSM_SEQ_ERR_BYTES i ..]. */
+#define ZKAES_STEP_WINDOW 0
+#define ZKAES_STEP_TABLE 1
+#define ZKAES_STEP_SECOND 2
+#define ZKAES_STEP_CLASS 3
+#define ZKAES_STEP_REFINISH 4
+#define ZKAES_MSM_SEQ_MAX_STEPS 32
+#define ZKAES_MSM_SEQ_ERR_BYTES 128
+typedef struct zkaes_msm_step {
+    uint32_t kind, edwards, window_bits, reserved;      /* reserved = 0 */
+    uint64_t n1, off1, scal1;                           /* first vector: length, first base, first scalar (CLASS: first value) */
+    uint64_t n2, off2, scal2;                           /* second vector (WINDOW, TABLE) */
+    uint64_t shift;                                     /* SECOND, REFINISH */
+} zkaes_msm_step;
+int zkaes_msm_sequence(const uint8_t *bases, size_t nbases, const uint8_t *scalars, size_t nscalars, const int8_t *class_vals, size_t nvals, const zkaes_msm_step *steps, size_t nsteps,
+                       int poison, uint8_t *out_xy, int *out_inf, int *out_accepted, int *out_status, char *out_errors);
 /* ---- kernel-level entry points of the prover's R1CS and randomness kernels (csrc/kernels_witness.hip, csrc/kernels_poly.hip): TEST SURFACE, not product API -- the layer
  * between the AES trace and the polynomials, which otherwise runs only inside whole proofs (tests/test_gpu_r1cs.py compares each with the big-integer model of
  * tests/r1cs_model.py).  BLS12-377 Fr; field elements are 32-byte Montgomery limbs, canonical (< r), not checked one by one.  Every call uploads, launches, copies back and
